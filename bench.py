@@ -17,7 +17,10 @@ overlaps the renders of the frames behind it).  `value` is that
 pipelined throughput over exactly K steps; `latency_ms` is one frame (render + gather) issued alone with a
 full synchronisation around it, at the same N -- so the numbers at N = 1, 2, 4, 8 are like for like.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline fields (metric, value,
+unit, ms_per_step, ...; `roofline` and `bit_exact` null, no `cpu_baseline`); with --dump-outputs DIR it first writes what the last
+timed step computed (dump_outputs below).  Everything else the line can carry is measured and checked with --full only:
+  value_repeats the same K steps twice more; `latency_ms` / `value_single_frame`: one frame issued alone.
   roofline      the DOMINANT kernel (by HIP events on its launch stream, three further frames issued one after the
                 other).  `bound` names the resource that binds it: f64 VALU issue ("valu_f64": algorithmic unfused f64
                 operations of the reference's algorithm per launch, from the kernels' own deterministic counters,
@@ -32,6 +35,7 @@ Prints ONE JSON line on rank 0.
                 cpu_baseline leg renders on the oracle, on every pixel of that sample (the whole film when the host is fast
                 enough: n = 1); a mismatch makes the run exit non-zero after the line is printed.
   roofline_mesh the same bookkeeping for configs[3] (100k-triangle mesh, glass + mirror, 4096^2) from two untimed frames.
+  N > 1         the gathered film against rank 0's own render (`gathered_equals_single_gpu`), per-rank times and `gather_ms`.
 """
 import argparse
 import json
@@ -166,6 +170,23 @@ def oracle_sample_check(width, height, gpu_film, n, build=None):
     bad = int((want != got).sum())
     return {"bit_exact": bad == 0, "mismatched_bytes": bad, "checked_pixels": int(want.shape[0]),
             "checked": "the timed (gathered) frame against the oracle, pixels {0, n, 2n, ...}, n = %d" % n}
+
+
+DUMP_PIXELS = 1 << 21    # --dump-outputs: pixel indices drawn with replacement, duplicates dropped: <= 32 MiB of float32 RGBA
+DUMP_SEED = 0x1A56D0
+
+
+def dump_outputs(directory, film):
+    """--dump-outputs DIR: the film the last timed step gave rank 0 ((h, w, 4) uint8 on the host), as float32 .npy files that two builds
+    can be compared by -- `film_sample.npy` (n, 4): the RGBA of a fixed, seeded sample of pixels, `film_sample_index.npy` (n,): their flat
+    indices y * w + x (float64, exact), `film_row_sums.npy` (h, 4): every row's per-channel sum (float64), so that no pixel goes unseen."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    px = film.reshape(-1, 4)
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, px.shape[0], DUMP_PIXELS))  # sorted; the same for every run at this size
+    np.save(os.path.join(directory, "film_sample.npy"), px[idx].astype(np.float32))
+    np.save(os.path.join(directory, "film_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "film_row_sums.npy"), film.sum(axis=1, dtype=np.float64))
 
 
 def profiled_traffic(kernel_name, world, size):
@@ -380,18 +401,22 @@ def library_collective(args):
     for _ in range(args.steps):
         m.capture_device(w, h, film.data_ptr())  # synchronous: every device's render + the exchange
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, film.cpu().numpy())
     st = G.capture_stats(m.accel(0), w, h)
     rays = st["primary_rays"] + st["shadow_rays"]
-    acc = G.Accel(scene)
-    ref = torch.zeros_like(film)
-    G.capture_rows_device(acc, w, h, 0, h, ref.data_ptr(), row0=0)
-    G.synchronize(acc)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
+    single_ms = same = None
+    if args.full:  # the same frames on one device alone: its time, and its film against the exchanged one
+        acc = G.Accel(scene)
+        ref = torch.zeros_like(film)
         G.capture_rows_device(acc, w, h, 0, h, ref.data_ptr(), row0=0)
-    G.synchronize(acc)
-    single_ms = (time.perf_counter() - t1) / args.steps * 1e3
-    same = bool(torch.equal(film, ref))
+        G.synchronize(acc)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            G.capture_rows_device(acc, w, h, 0, h, ref.data_ptr(), row0=0)
+        G.synchronize(acc)
+        single_ms = (time.perf_counter() - t1) / args.steps * 1e3
+        same = bool(torch.equal(film, ref))
     out = {"metric": "Mrays/s (primary+shadow) at 4096x4096; bit-exact RGBA8 vs CPU", "value": rays * args.steps / elapsed / 1e6, "unit": "Mrays/s",
            "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -402,7 +427,7 @@ def library_collective(args):
            "multi_create_s": create_s, "single_device_ms_per_step": single_ms, "gathered_equals_single_gpu": same,
            "roofline": None, "cpu_baseline": None}
     print(json.dumps(out), flush=True)
-    if not same:
+    if same is False:
         sys.exit(4)
 
 
@@ -426,7 +451,14 @@ def main():
     ap.add_argument("--collective", default="torch", choices=["torch", "library"],
                     help="torch = one process per GPU, torch.distributed gather (the driver's contract); library = ONE process drives the N devices "
                          "through the product's own lg_multi_capture_device (multi.cpp: one grouped RCCL send / recv into the root's film)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: repeats, single-frame latency, per-kernel roofline, "
+                         "the extras, the CPU baseline with its byte-for-byte check, the N > 1 gathered-film check (off: a plain run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a seeded sample of the film, and its row sums) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.collective == "library":
         return library_collective(args)
@@ -533,44 +565,50 @@ def main():
     full = finish()  # waits for the last gather (inside the timed region)
     fence()
     elapsed = time.perf_counter() - t0
-    timed_film = full.cpu().numpy().copy() if (rank == 0 and full is not None) else None  # the frame `value` was measured on
+    timed_film = None  # the frame `value` was measured on
+    if rank == 0 and full is not None and (args.full or args.dump_outputs):
+        timed_film = full.cpu().numpy().copy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_film)
 
-    # the same K steps twice more (not `value`: the spread between back-to-back blocks of the same run, reported beside it)
     repeats = [elapsed]
-    for _ in range(2):
-        for _ in range(args.warmup):  # (the film's D2H copy above left the GPU idle: the same warm-up as before the first block)
-            step()
-        finish()
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        finish()
-        fence()
-        repeats.append(time.perf_counter() - t1)
+    kernel_ms = launches = latency_ms = kinds = None
+    if args.full:
+        # the same K steps twice more (not `value`: the spread between back-to-back blocks of the same run, reported beside it)
+        for _ in range(2):
+            for _ in range(args.warmup):  # (the film's D2H copy above left the GPU idle: the same warm-up as before the first block)
+                step()
+            finish()
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            finish()
+            fence()
+            repeats.append(time.perf_counter() - t1)
 
-    # one frame at a time (render + gather, nothing else in flight): latency at this N
-    was = overlap[0]
-    overlap[0] = False
-    lat = []
-    for _ in range(3):
-        fence()
-        t1 = time.perf_counter()
-        step()
+        # one frame at a time (render + gather, nothing else in flight): latency at this N
+        was = overlap[0]
+        overlap[0] = False
+        lat = []
+        for _ in range(3):
+            fence()
+            t1 = time.perf_counter()
+            step()
+            finish()
+            fence()
+            lat.append(time.perf_counter() - t1)
+        latency_ms = min(lat) * 1e3
+        # per-kernel durations for the roofline: HIP events around every kernel of three frames issued one after the other
+        G.profile_enable(acc, True)
+        for _ in range(3):
+            step()
         finish()
         fence()
-        lat.append(time.perf_counter() - t1)
-    latency_ms = min(lat) * 1e3
-    # per-kernel durations for the roofline: HIP events around every kernel of three frames issued one after the other
-    G.profile_enable(acc, True)
-    for _ in range(3):
-        step()
-    finish()
-    fence()
-    kernel_ms, launches = G.profile_read(acc)   # device time of whole frames (all kernels of a frame)
-    kinds = G.profile_read_kinds(acc)           # streaming pipeline: HIP events around each kernel
-    G.profile_enable(acc, False)
-    overlap[0] = was
+        kernel_ms, launches = G.profile_read(acc)   # device time of whole frames (all kernels of a frame)
+        kinds = G.profile_read_kinds(acc)           # streaming pipeline: HIP events around each kernel
+        G.profile_enable(acc, False)
+        overlap[0] = was
 
     # deterministic work counters of this rank's share (untimed, counting kernel variant)
     def share_stats(kind=None):
@@ -589,37 +627,43 @@ def main():
     keys = sorted(st)
     rdev = "cuda" if args.backend == "nccl" else "cpu"
     vec = torch.tensor([st[k] for k in keys] + [0], dtype=torch.float64, device=rdev)
-    tmax = torch.tensor([elapsed, kernel_ms / max(launches, 1), latency_ms] + repeats, dtype=torch.float64, device=rdev)
-    # per rank: ms per timed step as this rank saw it, and its own share rendered alone (no collective): what the gather adds to a frame
-    render_only_ms = latency_ms
-    if multi and balanced:
-        alone = []
-        for _ in range(3):
-            fence()
-            t1 = time.perf_counter()
-            G.capture_interleaved_device(acc, w, h, BLOCK_ROWS, world, rank, (cuda_tile if cuda_tile is not None else ig.tiles[0]).data_ptr(), stream=cur_stream.cuda_stream)
-            torch.cuda.synchronize()
-            alone.append(time.perf_counter() - t1)
-        render_only_ms = min(alone) * 1e3
-    per_rank = torch.zeros((max(world, 1), 3), dtype=torch.float64, device=rdev)
-    per_rank[rank if multi else 0] = torch.tensor([elapsed / args.steps * 1e3, latency_ms, render_only_ms], dtype=torch.float64, device=rdev)
+    tmax = torch.tensor([elapsed, kernel_ms / max(launches, 1), latency_ms] + repeats if args.full else [elapsed], dtype=torch.float64, device=rdev)
+    per_rank = None
+    if args.full:
+        # per rank: ms per timed step as this rank saw it, and its own share rendered alone (no collective): what the gather adds to a frame
+        render_only_ms = latency_ms
+        if multi and balanced:
+            alone = []
+            for _ in range(3):
+                fence()
+                t1 = time.perf_counter()
+                G.capture_interleaved_device(acc, w, h, BLOCK_ROWS, world, rank, (cuda_tile if cuda_tile is not None else ig.tiles[0]).data_ptr(), stream=cur_stream.cuda_stream)
+                torch.cuda.synchronize()
+                alone.append(time.perf_counter() - t1)
+            render_only_ms = min(alone) * 1e3
+        per_rank = torch.zeros((max(world, 1), 3), dtype=torch.float64, device=rdev)
+        per_rank[rank if multi else 0] = torch.tensor([elapsed / args.steps * 1e3, latency_ms, render_only_ms], dtype=torch.float64, device=rdev)
     if multi:
         dist.all_reduce(vec, op=dist.ReduceOp.SUM)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        dist.all_reduce(per_rank, op=dist.ReduceOp.SUM)
-    per_rank = per_rank.tolist()
+        if per_rank is not None:
+            dist.all_reduce(per_rank, op=dist.ReduceOp.SUM)
+    if per_rank is not None:
+        per_rank = per_rank.tolist()
     total = {k: int(v) for k, v in zip(keys, vec.tolist())}
-    elapsed, latency_ms = float(tmax[0]), float(tmax[2])
-    repeats = [float(x) for x in tmax[3:]]
+    elapsed = float(tmax[0])
+    if args.full:
+        latency_ms = float(tmax[2])
+        repeats = [float(x) for x in tmax[3:]]
     # the metric counts primary + shadow rays; neither workload has a specular material, so there are no secondary rays
     assert total["secondary_rays"] == 0, "the bench workloads must not cast secondary rays"
     rays = total["primary_rays"] + total["shadow_rays"]
 
-    # N > 1 (always, no switch): the TIMED frame as gathered on rank 0 against the same frame rendered by rank 0's GPU alone --
+    # N > 1 (--full): the TIMED frame as gathered on rank 0 against the same frame rendered by rank 0's GPU alone --
     # every byte -- so that a multi-GPU number never comes without a correctness statement (lib.rs:110-162: a pixel's value does
     # not depend on the partition).  The oracle is consulted too, on a bounded sample (below); a mismatch exits non-zero.
     gathered_ok = None
-    if rank == 0 and multi:
+    if rank == 0 and multi and args.full:
         ref = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
         G.capture_rows_device(acc, w, h, 0, h, ref.data_ptr(), row0=0, stream=cur_stream.cuda_stream)
         torch.cuda.synchronize()
@@ -627,7 +671,7 @@ def main():
         print("verify: gathered %d-rank film %s single-GPU film" % (world, "==" if gathered_ok else "!="), file=sys.stderr)
         del ref
 
-    extras = rank == 0 and world == 1 and not args.no_extras and not args.force_dist
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and not args.force_dist
     e2e_ms = fast_info = probes = mesh_info = mixed_info = None
     if extras:
         # PCIe-inclusive figure (never `value`): lg_capture into a HOST film = host BVH build + upload + render + 64 MiB D2H
@@ -665,43 +709,11 @@ def main():
 
     if rank == 0:
         value = rays * args.steps / elapsed / 1e6
-        frame_ms = kernel_ms / max(launches, 1)
-        per_kernel = {k: v[0] / v[1] for k, v in kinds.items() if v[1] > 0}
-        if per_kernel and (len(per_kernel) > 1 or "trace_kernel" not in per_kernel):  # pipeline: closest trace (+ frame), shadow trace, shade
-            dom = max(kinds, key=lambda k: kinds[k][0])  # the kind the frame spends most time in
-            dom_ms = per_kernel[dom]
-            dst = dict(share_stats(2 if "shadow" in dom else 1))
-            dst["primary_rays"] = 0  # the RGBA write belongs to the shade kernel, not to a traversal kernel
-            # a film cut into chunks (8192^2: two) launches a kind once per chunk: the frame's work of that kind over its launches is one launch's
-            per_frame = max(1, round(kinds[dom][1] / 3.0))  # (three frames were profiled)
-            if per_frame > 1:
-                dst = {k: v / per_frame for k, v in dst.items()}
-            # wavefront pipeline: lg::wf_trace_kernel<FAST, SHADOW, scene tables resident in LDS>, lg::wf_shade_kernel
-            # wavefront pipeline: lg::wf_trace_kernel<FAST, SHADOW, scene tables resident in LDS, level-0 closest pass>, lg::wf_shade_kernel<KIND, L0>
-            shadow = "shadow" in dom
-            pruned = "true" if G.get_prune(acc) else "false"  # (LASGUN_PRUNE / lg_accel_set_prune: the PRUNE template argument of the kernel that ran)
-            # (the sixth argument: the refilling shadow pass -- level 0 of a big launch over an LDS-resident scene, k_wavefront.hip: launch_wf_trace)
-            refill = "true" if (shadow and lds_scene and pruned == "false" and os.environ.get("LASGUN_REFILL", "0") == "1" and w * h >= (1 << 20) * world) else "false"
-            kernel_name = ("lg::wf_trace_kernel<false, %s, %s, %s, %s, %s>" % ("true" if shadow else "false", "true" if lds_scene else "false", "false" if shadow else "true", pruned, refill)
-                           if dom.startswith("trace<") else "lg::wf_shade_kernel<0, true>")
-        else:  # megakernel (a share too small for the pipeline, e.g. a small --size over many ranks)
-            dom_ms, dst, kernel_name = frame_ms, st, "lg::trace_kernel<false, false, %s, %s, 1024>" % ("true" if lds_scene else "false", "true" if G.get_prune(acc) else "false")
-            per_kernel = {"trace_kernel": frame_ms}
-        dom_bytes, dom_flops = algorithmic_bytes(dst), algorithmic_flops(dst)
-        secs = dom_ms * 1e-3
-        traffic, traffic_src = profiled_traffic(kernel_name, world, args.size) if headline else (None, None)
-        tops = dom_flops / secs / 1e12
-        gbs = dom_bytes / secs / 1e9
-        hbm_measured = probes["hbm_copy_GBps"] if probes else None
-        lds_measured = probes["lds_read_GBps"] if probes else None
         out = {
             "metric": "Mrays/s (primary+shadow) at 4096x4096; bit-exact RGBA8 vs CPU",
             "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "latency_ms": latency_ms,
-            "value_repeats": [rays * args.steps / r / 1e6 for r in repeats],  # [0] is `value`; the other two: the same K steps again
-            "value_single_frame": rays / latency_ms / 1e3,  # Mrays/s of ONE frame issued alone (render + gather), nothing else in flight
             "config": {"workload": wl["desc"] % (w, h), "workload_key": args.workload,
                        "rays_per_frame": rays, "primary": total["primary_rays"], "shadow": total["shadow_rays"],
                        "parallelism": ("64-row blocks dealt round-robin over %d rank(s)%s; consecutive frames %s"
@@ -710,37 +722,73 @@ def main():
                        else ("contiguous row tiles x%d + 1 gather, frames one after the other" % world),
                        "accel_build_s": accel_build_s, "host_film_capture_ms": e2e_ms,
                        "work_per_frame": {k: total[k] for k in ("nodes_tested", "spheres_tested", "cuboids_tested", "triangles_tested", "accel_entries", "hits")}},
-            "roofline": {"bound": "valu_f64", "achieved": tops, "peak": VALU_F64_PEAK_TOPS, "unit": "TFLOP/s", "frac": tops / VALU_F64_PEAK_TOPS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernel_name, "kernel_ms_avg": dom_ms,
-                         "algorithmic_flops_per_launch": dom_flops, "algorithmic_bytes_per_launch": dom_bytes,
-                         "frame_device_ms": frame_ms, "kernels_ms_avg": per_kernel,
-                         "scene_tables": "LDS" if lds_scene else "L1/L2",
-                         "hbm_algorithmic": {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "x_peak": gbs / HBM_PEAK_GBS,
-                                             "measured_copy_peak": hbm_measured,
-                                             "x_measured_copy_peak": (gbs / hbm_measured) if hbm_measured else None,
-                                             "note": "SURVEY 8(d) bytes (node / primitive records the traversal demands) over the kernel's duration; "
-                                                     "the scene is resident in LDS (or L2), so these bytes never reach HBM and the ratio is not a fraction"},
-                         "lds": {"achieved": gbs, "peak": LDS_PEAK_GBS, "unit": "GB/s", "frac": gbs / LDS_PEAK_GBS,
-                                 "measured_read_peak": lds_measured, "frac_of_measured": (gbs / lds_measured) if lds_measured else None},
-                         "note": "unit = unfused f64 operations (no FMA: -ffp-contract=off is part of the parity contract); counts are lower bounds "
-                                 "of the reference's algorithm (DESIGN.md, Roofline bookkeeping)"},
+            "roofline": None,
         }
-        at_clock(out["roofline"], kernel_name)
-        if mesh_info is not None:
-            at_clock(mesh_info, mesh_info["kernel"])
-        if mixed_info is not None:
-            at_clock(mixed_info, mixed_info["kernel"])
-        if fast_info is not None:
-            out["fast_mode"] = fast_info
-        if mesh_info is not None:
-            out["roofline_mesh"] = mesh_info
-        if mixed_info is not None:
-            out["roofline_mixed"] = mixed_info
+        if args.full:
+            frame_ms = kernel_ms / max(launches, 1)
+            per_kernel = {k: v[0] / v[1] for k, v in kinds.items() if v[1] > 0}
+            if per_kernel and (len(per_kernel) > 1 or "trace_kernel" not in per_kernel):  # pipeline: closest trace (+ frame), shadow trace, shade
+                dom = max(kinds, key=lambda k: kinds[k][0])  # the kind the frame spends most time in
+                dom_ms = per_kernel[dom]
+                dst = dict(share_stats(2 if "shadow" in dom else 1))
+                dst["primary_rays"] = 0  # the RGBA write belongs to the shade kernel, not to a traversal kernel
+                # a film cut into chunks (8192^2: two) launches a kind once per chunk: the frame's work of that kind over its launches is one launch's
+                per_frame = max(1, round(kinds[dom][1] / 3.0))  # (three frames were profiled)
+                if per_frame > 1:
+                    dst = {k: v / per_frame for k, v in dst.items()}
+                # wavefront pipeline: lg::wf_trace_kernel<FAST, SHADOW, scene tables resident in LDS>, lg::wf_shade_kernel
+                # wavefront pipeline: lg::wf_trace_kernel<FAST, SHADOW, scene tables resident in LDS, level-0 closest pass>, lg::wf_shade_kernel<KIND, L0>
+                shadow = "shadow" in dom
+                pruned = "true" if G.get_prune(acc) else "false"  # (LASGUN_PRUNE / lg_accel_set_prune: the PRUNE template argument of the kernel that ran)
+                # (the sixth argument: the refilling shadow pass -- level 0 of a big launch over an LDS-resident scene, k_wavefront.hip: launch_wf_trace)
+                refill = "true" if (shadow and lds_scene and pruned == "false" and os.environ.get("LASGUN_REFILL", "0") == "1" and w * h >= (1 << 20) * world) else "false"
+                kernel_name = ("lg::wf_trace_kernel<false, %s, %s, %s, %s, %s>" % ("true" if shadow else "false", "true" if lds_scene else "false", "false" if shadow else "true", pruned, refill)
+                               if dom.startswith("trace<") else "lg::wf_shade_kernel<0, true>")
+            else:  # megakernel (a share too small for the pipeline, e.g. a small --size over many ranks)
+                dom_ms, dst, kernel_name = frame_ms, st, "lg::trace_kernel<false, false, %s, %s, 1024>" % ("true" if lds_scene else "false", "true" if G.get_prune(acc) else "false")
+                per_kernel = {"trace_kernel": frame_ms}
+            dom_bytes, dom_flops = algorithmic_bytes(dst), algorithmic_flops(dst)
+            secs = dom_ms * 1e-3
+            traffic, traffic_src = profiled_traffic(kernel_name, world, args.size) if headline else (None, None)
+            tops = dom_flops / secs / 1e12
+            gbs = dom_bytes / secs / 1e9
+            hbm_measured = probes["hbm_copy_GBps"] if probes else None
+            lds_measured = probes["lds_read_GBps"] if probes else None
+            out.update({
+                "latency_ms": latency_ms,
+                "value_repeats": [rays * args.steps / r / 1e6 for r in repeats],  # [0] is `value`; the other two: the same K steps again
+                "value_single_frame": rays / latency_ms / 1e3,  # Mrays/s of ONE frame issued alone (render + gather), nothing else in flight
+                "roofline": {"bound": "valu_f64", "achieved": tops, "peak": VALU_F64_PEAK_TOPS, "unit": "TFLOP/s", "frac": tops / VALU_F64_PEAK_TOPS,
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": kernel_name, "kernel_ms_avg": dom_ms,
+                             "algorithmic_flops_per_launch": dom_flops, "algorithmic_bytes_per_launch": dom_bytes,
+                             "frame_device_ms": frame_ms, "kernels_ms_avg": per_kernel,
+                             "scene_tables": "LDS" if lds_scene else "L1/L2",
+                             "hbm_algorithmic": {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "x_peak": gbs / HBM_PEAK_GBS,
+                                                 "measured_copy_peak": hbm_measured,
+                                                 "x_measured_copy_peak": (gbs / hbm_measured) if hbm_measured else None,
+                                                 "note": "SURVEY 8(d) bytes (node / primitive records the traversal demands) over the kernel's duration; "
+                                                         "the scene is resident in LDS (or L2), so these bytes never reach HBM and the ratio is not a fraction"},
+                             "lds": {"achieved": gbs, "peak": LDS_PEAK_GBS, "unit": "GB/s", "frac": gbs / LDS_PEAK_GBS,
+                                     "measured_read_peak": lds_measured, "frac_of_measured": (gbs / lds_measured) if lds_measured else None},
+                             "note": "unit = unfused f64 operations (no FMA: -ffp-contract=off is part of the parity contract); counts are lower bounds "
+                                     "of the reference's algorithm (DESIGN.md, Roofline bookkeeping)"},
+            })
+            at_clock(out["roofline"], kernel_name)
+            if mesh_info is not None:
+                at_clock(mesh_info, mesh_info["kernel"])
+            if mixed_info is not None:
+                at_clock(mixed_info, mixed_info["kernel"])
+            if fast_info is not None:
+                out["fast_mode"] = fast_info
+            if mesh_info is not None:
+                out["roofline_mesh"] = mesh_info
+            if mixed_info is not None:
+                out["roofline_mixed"] = mixed_info
         check = None
-        if world == 1 and not args.no_cpu_baseline and not args.force_dist and not args.no_extras:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.force_dist and not args.no_extras:
             out["cpu_baseline"], check = cpu_baseline(w, h, timed_film, build=wl["build"])
-        elif multi and not args.no_cpu_baseline:
+        elif args.full and multi and not args.no_cpu_baseline:
             # N > 1: no CPU baseline figure (rank 0 at N = 1 only), but the gathered frame still meets the oracle on a bounded
             # sample (every 64th pixel: a fraction of a second of host time)
             check = oracle_sample_check(w, h, timed_film, 64 if headline else 1024, build=wl["build"])
@@ -749,11 +797,12 @@ def main():
             out["rccl_ranks"] = dist.get_world_size()
             out["collective_backend"] = args.backend
             out["collective"] = "torch"
-            # per rank: ms per timed step (frames overlapped), one frame alone with its gather, the rank's share alone without it;
-            # gather_ms = what the collective adds to a frame issued alone, slowest rank
-            out["per_rank_ms"] = [{"rank": r, "ms_per_step": v[0], "latency_ms": v[1], "render_only_ms": v[2]} for r, v in enumerate(per_rank)]
-            out["gather_ms"] = max(v[1] for v in per_rank) - max(v[2] for v in per_rank)
-        out["bit_exact"] = check["bit_exact"] if check else None       # null: the oracle leg did not run (--no-cpu-baseline)
+            if per_rank is not None:
+                # per rank: ms per timed step (frames overlapped), one frame alone with its gather, the rank's share alone without it;
+                # gather_ms = what the collective adds to a frame issued alone, slowest rank
+                out["per_rank_ms"] = [{"rank": r, "ms_per_step": v[0], "latency_ms": v[1], "render_only_ms": v[2]} for r, v in enumerate(per_rank)]
+                out["gather_ms"] = max(v[1] for v in per_rank) - max(v[2] for v in per_rank)
+        out["bit_exact"] = check["bit_exact"] if check else None       # null: the oracle leg did not run (a plain run, or --no-cpu-baseline)
         out["mismatched_bytes"] = check["mismatched_bytes"] if check else None
         out["bit_exact_check"] = check
         sys.stdout.flush()

@@ -379,7 +379,7 @@ def test_bench_gpus_2_without_a_launcher():
     process, before the parent has touched the GPU), stdout is rank 0's one JSON line and the exit code the child's.  gloo on this box's one GPU
     (both ranks render on device 0, tiles staged through host memory): the gathered film == one GPU's film == the oracle sample.
     Reference counterpart: the fan-out over threads, src/lib.rs:55-104."""
-    d = _bench_line(["--gpus", "2", "--backend", "gloo", "--size", "1024", "--steps", "3", "--warmup", "1"])
+    d = _bench_line(["--gpus", "2", "--backend", "gloo", "--size", "1024", "--steps", "3", "--warmup", "1", "--full"])
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["collective_backend"] == "gloo" and d["collective"] == "torch"
     assert d["gathered_equals_single_gpu"] is True and d["bit_exact"] is True
     assert [r["rank"] for r in d["per_rank_ms"]] == [0, 1] and all(r["ms_per_step"] > 0.0 and r["render_only_ms"] > 0.0 for r in d["per_rank_ms"])
@@ -389,5 +389,5 @@ def test_bench_gpus_2_without_a_launcher():
 def test_bench_library_collective_on_same_device_shares():
     """`bench.py --gpus 2 --collective library`: the product's own exchange (lg_multi_capture_device, multi.cpp) timed by the same script --
     here two shares on device 0; the film equals the single-device film."""
-    d = _bench_line(["--gpus", "2", "--collective", "library", "--size", "1024", "--steps", "3", "--warmup", "1"])
+    d = _bench_line(["--gpus", "2", "--collective", "library", "--size", "1024", "--steps", "3", "--warmup", "1", "--full"])
     assert d["collective"] == "library" and d["n_gpus"] == 2 and d["gathered_equals_single_gpu"] is True and d["value"] > 0.0

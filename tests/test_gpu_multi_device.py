@@ -120,7 +120,7 @@ def test_bench_gathered_film_is_verified_at_n_ranks():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(29650 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--size", "1024",
-           "--steps", "3", "--warmup", "1"]
+           "--steps", "3", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -1157,7 +1157,7 @@ def test_bench_multi_gpu_path_over_rccl_world1():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--size", "1024", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert "verify: gathered 1-rank film == single-GPU film" in p.stderr
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -1179,7 +1179,7 @@ def test_bench_two_ranks_end_to_end_under_torchrun(collective):
         env.pop(k, None)
     port = str(29600 + (os.getpid() % 300) + (0 if collective == "gather" else 301))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "512", "--steps", "3", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "512", "--steps", "3", "--warmup", "1", "--full"]
     if collective == "all-gather":
         cmd.append("--all-gather")
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -1206,7 +1206,7 @@ def test_bench_configs4_workload_two_ranks_under_torchrun():
         env.pop(k, None)
     port = str(30300 + (os.getpid() % 300))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "configs4", "--size", "1024", "--steps", "2", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "configs4", "--size", "1024", "--steps", "2", "--warmup", "1", "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert "verify: gathered 2-rank film == single-GPU film" in p.stderr, p.stderr[-3000:]

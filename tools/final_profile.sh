@@ -10,7 +10,7 @@ cd "${GRAFT_REPO_ROOT:?}"
 part=${1:-a}
 O=gpurun_out/final6; mkdir -p "$O"
 if [ "$part" = a ]; then
-timeout -k 10 400 python3 bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+timeout -k 10 400 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
 # per-kernel durations: frames one after the other (the form bench.py's roofline.kernel_ms_avg is measured in) ...
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -- python3 bench.py --steps 5 --warmup 1 --no-extras --sequential > "$O/prof.log" 2>&1; echo "stats rc=$?"
 # ... and the default command (consecutive frames overlap, four in flight: kernels of several frames share the chip, durations stretch)

@@ -24,5 +24,5 @@ if fs:
             f.write("%.1f,%.4f,%s,%s\n" % ((int(r["Start_Timestamp"]) - t0) / 1e3, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6, r.get("Grid_Size", r.get("Grid_Size_X", "")), r["Kernel_Name"].replace("void ", "").replace("(lg::DParams)", "")))
 PY
 rm -rf "$O/trace_c4_wf"
-timeout -k 10 500 python3 bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+timeout -k 10 500 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
 tail -c 300 "$O/bench.json"

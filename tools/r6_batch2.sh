@@ -29,8 +29,8 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$O/gputest.log" 2>&1; e
 # lane use of the shadow pass, before / after (one counter set per run)
 LASGUN_REFILL=0 bash tools/pmc_sets.sh norefill "SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SALU" -- tools/bench_configs.py "3 sph" > /dev/null 2>&1; cp gpurun_out/pmcs_norefill/summary.txt "$O/pmc_norefill.txt"
 bash tools/pmc_sets.sh refill "SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SALU" -- tools/bench_configs.py "3 sph" > /dev/null 2>&1; cp gpurun_out/pmcs_refill/summary.txt "$O/pmc_refill.txt"
-timeout -k 10 500 python3 bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
-LASGUN_REFILL=0 timeout -k 10 500 python3 bench.py --no-cpu-baseline > "$O/bench_norefill.json" 2> "$O/bench_norefill.err"; echo "bench (no refill) rc=$?"
+timeout -k 10 500 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+LASGUN_REFILL=0 timeout -k 10 500 python3 bench.py --no-cpu-baseline --full > "$O/bench_norefill.json" 2> "$O/bench_norefill.err"; echo "bench (no refill) rc=$?"
 python3 - "$O" <<'PY'
 import json, sys
 for n in ("bench.json", "bench_norefill.json"):

@@ -6,10 +6,10 @@ cd "${GRAFT_REPO_ROOT:?}"
 O=gpurun_out/r6final; mkdir -p "$O"
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$O/gputest.log" 2>&1; echo "gpu tests rc=$?"; tail -2 "$O/gputest.log"
 timeout -k 10 300 python __graft_entry__.py smoke > "$O/smoke.log" 2>&1; echo "smoke rc=$?"; tail -1 "$O/smoke.log"
-timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
-timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 > "$O/bench_gloo2.json" 2> "$O/bench_gloo2.err"; echo "bench --gpus 2 (gloo, no launcher) rc=$?"
-LASGUN_MULTI_FORCE_RCCL=1 timeout -k 10 300 python3 bench.py --gpus 2 --collective library --steps 5 --warmup 2 > "$O/bench_library2.json" 2> "$O/bench_library2.err"; echo "bench --collective library rc=$?"
-timeout -k 10 400 python3 bench.py --workload configs4 --steps 5 --warmup 2 --no-extras --no-cpu-baseline > "$O/bench_configs4.json" 2> "$O/bench_configs4.err"; echo "bench configs4 rc=$?"
+timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+timeout -k 10 300 python3 bench.py --gpus 2 --backend gloo --steps 5 --warmup 2 --full > "$O/bench_gloo2.json" 2> "$O/bench_gloo2.err"; echo "bench --gpus 2 (gloo, no launcher) rc=$?"
+LASGUN_MULTI_FORCE_RCCL=1 timeout -k 10 300 python3 bench.py --gpus 2 --collective library --steps 5 --warmup 2 --full > "$O/bench_library2.json" 2> "$O/bench_library2.err"; echo "bench --collective library rc=$?"
+timeout -k 10 400 python3 bench.py --workload configs4 --steps 5 --warmup 2 --no-extras --no-cpu-baseline --full > "$O/bench_configs4.json" 2> "$O/bench_configs4.err"; echo "bench configs4 rc=$?"
 python3 - "$O" <<'PY'
 import json, sys
 for n in ("bench.json", "bench_gloo2.json", "bench_library2.json", "bench_configs4.json"):
