@@ -78,9 +78,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                 }
                 if (longest > 0.0 && std::isfinite(longest)) min_edge = std::fmin(min_edge, longest);
             }
-            // (LASGUN_FAST_NO_GATE=1: measurement only -- lg_audit_fast on exactly the meshes the gate refuses, tools/fast_adversarial.py)
-            static const bool no_gate = [] { const char *e = std::getenv("LASGUN_FAST_NO_GATE"); return e && e[0] == '1'; }();
-            if (!no_gate && std::isfinite(min_edge) && max_abs > min_edge * 0x1p20) {
+            if (std::isfinite(min_edge) && max_abs > min_edge * 0x1p20) {
                 a->fast_available = false;
                 a->fast_refusal = "fast mode unavailable: a mesh whose coordinates exceed 2^20 times its smallest triangle (a ray in a far triangle's plane is accepted by the reference wherever it passes)";
             }
@@ -114,7 +112,6 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         a->wf_blocks_fast = (uint32_t)((wbf < 1 ? 1 : wbf) * cus);
         int qb = 0;
         HIP_TRY(queue_occupancy(a->stack_depth, extra_lds, &qb));
-        if (const char *e = std::getenv("LASGUN_QUEUE_BLOCKS_PER_CU")) { const int v = std::atoi(e); if (v >= 1 && v < qb) qb = v; } // (diagnostic: how much the kernel gains from each resident workgroup)
         a->queue_blocks = (uint32_t)((qb < 1 ? 1 : qb) * cus);
         a->cus = (uint32_t)cus;
         // LDS-resident scene: the REFERENCE tree's nodes (56 of 64 bytes, padded to 80 when that fits),
@@ -231,7 +228,6 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
             a->prune_default = big_mesh >= PRUNE_MIN_TRIS;
             a->streaming_pays = f.spheres.size() + f.cuboids.size() >= 512 && !(f.has_specular && big_mesh >= 4096);
             a->mega_narrow = f.spheres.size() + f.cuboids.size() < 512;
-            if (const char *e = std::getenv("LASGUN_MEGA_LANES")) a->mega_narrow = std::atoi(e) == 768; // (A/B)
             // a big mesh of glass / mirror: the queue organisation (round 4; config 4: 38.7 against the megakernel's 40.8 ms and the
             // level-by-level pipeline's 80; a metal mesh beside a small mirror -- config 4m -- stays in the megakernel: 14.7 / 16.4)
             bool specular_mesh = false; // a mesh of >= 4096 triangles that is itself glass / mirror: every hit on it spawns secondary rays

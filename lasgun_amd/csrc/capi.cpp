@@ -1038,7 +1038,7 @@ extern "C" int lg_debug_queue_packets(const lg_accel *a, void *hip_stream, unsig
     });
 }
 
-#if defined(LG_PKT_STATS) || defined(LG_STAMPS) || defined(LG_QIDLE)
+#if defined(LG_STAMPS) || defined(LG_QIDLE)
 extern "C" int lg_debug_stats(const lg_accel *a, int clear, unsigned long long *out9) { // analysis builds only
     return guarded([&] {
         use_device(a->device);

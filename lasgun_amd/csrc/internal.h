@@ -348,16 +348,9 @@ struct lg_accel {
         // launch is enqueued, so neither a later batch on the stream nor the caller's freed array can reach it
         struct KsTable { DevBuf<unsigned long long> buf; PinnedBuf stage; hipEvent_t done = nullptr; };
         std::vector<std::unique_ptr<KsTable>> ks_live;
-        // the level-by-level chain of a SMALL frame as a HIP graph (enqueue_wavefront): what the chain was captured for (a hash of its
-        // parameters), and the chain the context saw last -- a chain is captured when it comes a second time in a row, so a one-frame
-        // program never pays for a capture
-        hipGraphExec_t wf_graph = nullptr;
-        uint64_t wf_graph_sig = 0, wf_last_sig = 0;
-        unsigned wf_graph_captures = 0;
         ~LaunchCtx() {
             for (auto &k : ks_live) if (k->done) (void)hipEventDestroy(k->done);
             for (auto &r : rowtabs) if (r->up) (void)hipEventDestroy(r->up);
-            if (wf_graph) (void)hipGraphExecDestroy(wf_graph);
         }
     };
     mutable std::vector<std::unique_ptr<LaunchCtx>> ctxs;

@@ -88,49 +88,136 @@ void ensure_aux_streams(const lg_accel &a, unsigned n) {
     if (!a.aux_fork) HIP_TRY(hipEventCreateWithFlags(&a.aux_fork, hipEventDisableTiming));
 }
 
-// The wavefront pipeline (k_wavefront.hip): per chunk of the film and per supersample, levels 0 .. L-1 top-down (closest,
-// shadow, shade), then the combine passes bottom-up.  Queue capacities are worst case (level d holds at most 2^d rays per
-// pixel of the chunk), so the chunk is sized to the memory budget of the launch context: nothing can overflow.
+// ---- the two organisations that keep every recursion level's rays in arrays of their own (k_wavefront.hip, k_queue.hip) -------------
+static uint32_t levels_of(const lg_accel &a, const DParams &P) { return (a.flat.has_specular && P.recursion > 0) ? P.recursion + 1u : 1u; }
 constexpr size_t WF_FULL_MIN_HOST = 48; // == WF_FULL_MIN of k_wavefront.hip
 constexpr uint32_t MEGA_SPLIT = 4;      // the parts a small launch's tiles are handed out in where the measured choice found that faster (enqueue_mega, enqueue_queue)
+
+// HIP events around ONE kernel on its launch stream
+template <class F> static void timed(const lg_accel &a, int kind, hipStream_t s, F &&launch) {
+    hipEvent_t k0 = nullptr, k1 = nullptr;
+    if (a.profiling) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); HIP_TRY(hipEventRecord(k0, s)); }
+    HIP_TRY(launch());
+    if (a.profiling) { HIP_TRY(hipEventRecord(k1, s)); a.kind_events[kind].emplace_back(k0, k1); }
+}
+
+// A chunk's level arrays, carved from a launch context's wf_mem
+struct LevelArrays {
+    std::vector<double *> q, out, spec;
+    std::vector<uint32_t *> child;
+    double *accum = nullptr;
+};
+// The chunks a launch of either organisation is cut into.  Queue capacities are worst case (level d holds at most 2^d rays per level-0
+// work item of the chunk), so nothing can overflow, and the chunk is sized to the memory budget of a launch context.
+struct ChunkPlan {
+    bool queue;                    // the queue organisation's constants, else the level-by-level pipeline's
+    uint32_t levels, nsamples, S;  // S: level-0 work items per pixel
+    size_t per_item = 0;           // bytes per level-0 work item
+    size_t *budget;                // a.queue_budget / a.wf_budget
+    unsigned long long chunk_tiles = 0;
+
+    // `extra`: the organisation's own bytes per level-0 work item beside the level arrays
+    ChunkPlan(const lg_accel &a, const DParams &P0, bool queue_org, uint32_t S_, size_t extra)
+        : queue(queue_org), levels(levels_of(a, P0)), nsamples(P0.ss_root * P0.ss_root), S(S_), budget(queue_org ? &a.queue_budget : &a.wf_budget) {
+        per_item = (nsamples > 1 ? 3 * 8 : 0) + extra;
+        for (uint32_t d = 0; d < levels; ++d) {
+            size_t b = 0;                                 // per ray of level d
+            if (d >= 1) b += 6 * 8;                       // ray queue
+            if (levels > 1) b += 3 * 8;                   // output / li
+            if (d + 1 < levels) b += 8 * 8 + 2 * 4;       // children's weights and indices
+            per_item += b << d;
+        }
+        if (*budget == 0) *budget = budget_from_free_memory();
+        chunk_tiles = *budget / (per_item * S * 64);
+        const unsigned long long cap_limit = ((queue ? 0xFFFFFF00ull : 0xFFFFFFF0ull) >> (levels - 1)) / (64ull * S); // ray indices are 32-bit
+        if (chunk_tiles > cap_limit) chunk_tiles = cap_limit;
+        if (chunk_tiles < 1) chunk_tiles = 1;
+        if (chunk_tiles > P0.ntiles) chunk_tiles = P0.ntiles;
+        if (queue && chunk_tiles < P0.ntiles && P0.mode == 0u && P0.tiles_x != 0u && chunk_tiles >= (unsigned long long)P0.tiles_x * 32ull)
+            chunk_tiles -= chunk_tiles % ((unsigned long long)P0.tiles_x * 32ull); // whole rows of 32 x 32-tile blocks: the block order applies to every chunk
+    }
+    // Per launch CONTEXT, and an accel keeps up to MAX_LAUNCH_CTXS of them plus the band contexts (a caller with four frames in flight uses
+    // five): a sixteenth of the free memory, at most 8 GiB each (the headline frame needs 3.3 GB and stays one chunk).  The queue
+    // organisation with a recursive scene: up to a quarter (at most 48 GiB), so that a 4096^2 frame is one launch.  An allocation that
+    // fails anyway halves the chunk (fit).
+    size_t budget_from_free_memory() const {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const bool deep = queue && levels > 1;
+        size_t b = deep ? free_b / 4 : free_b / 16;
+        const char *env = std::getenv(queue ? "LASGUN_QUEUE_BUDGET_MB" : "LASGUN_WF_BUDGET_MB");
+        if (env && std::atoll(env) > 0) {
+            b = (size_t)std::atoll(env) << 20;
+            if (queue) return b; // (as given: tests cut small films into many chunks with it)
+        } else if (b > (deep ? (48ull << 30) : (8ull << 30))) b = deep ? (48ull << 30) : (8ull << 30);
+        return b < (64ull << 20) ? (64ull << 20) : b;
+    }
+    unsigned long long n0() const { return chunk_tiles * 64ull * S; } // level 0's work items per chunk
+    size_t need() const { return (size_t)n0() * per_item + 4096 * ((queue ? 4 : 3) * levels + 4); } // (+ the carve's alignment)
+
+    // Runs `alloc` (the organisation's allocations for a chunk); memory that is not there (other contexts, other accels, other processes):
+    // halve the chunk and run it again
+    template <class F> void fit(F &&alloc) {
+        for (;;) {
+            try { alloc(); return; }
+            catch (const Error &e) {
+                if (std::string(e.what()).find("hipMalloc") == std::string::npos || chunk_tiles <= 1) throw;
+                (void)hipGetLastError(); // (the failed allocation's error must not be what the next launch reports)
+                chunk_tiles = (chunk_tiles + 1) / 2;
+                *budget = std::max<size_t>(*budget / 2, 64ull << 20); // (later launches start from what fitted)
+                if (std::getenv("LASGUN_DEBUG")) std::fprintf(stderr, "[lasgun] %s: %s -- chunks of %llu tiles instead\n", queue ? "queue" : "wavefront", e.what(), chunk_tiles);
+            }
+        }
+    }
+    // One chunk's level arrays in `mem` (256-byte aligned): each level's rays, output, children's weights and indices; then whatever `mid`
+    // takes; then the sample accumulator
+    template <class F> LevelArrays carve(uint8_t *mem, F &&mid) const {
+        LevelArrays k;
+        k.q.assign(levels, nullptr); k.out.assign(levels, nullptr); k.spec.assign(levels, nullptr); k.child.assign(levels, nullptr);
+        uint8_t *cur = mem;
+        auto take = [&](size_t bytes) { uint8_t *p = cur; cur += (bytes + 255) & ~(size_t)255; return p; };
+        for (uint32_t d = 0; d < levels; ++d) {
+            const size_t cap = (size_t)n0() << d;
+            if (d >= 1) k.q[d] = (double *)take(cap * 6 * 8);
+            if (levels > 1) k.out[d] = (double *)take(cap * 3 * 8);
+            if (d + 1 < levels) { k.spec[d] = (double *)take(cap * 8 * 8); k.child[d] = (uint32_t *)take(cap * 2 * 4); }
+        }
+        mid(take);
+        k.accum = nsamples > 1 ? (double *)take((size_t)n0() * 3 * 8) : nullptr;
+        return k;
+    }
+};
+
+// Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
+static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s) {
+    const unsigned long long n0 = plan.n0();
+    const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull), flat_cap = a.cus * 16u; // (level 0: one thread per work item)
+    for (uint32_t d = plan.levels - 1; d-- > 0;) {
+        P.wf_level = d;
+        P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
+        P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
+        timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
+    }
+}
+// ... and a pixel's samples summed in their order (k_wavefront.hip, wf_resolve_kernel)
+static void resolve_samples(const lg_accel &a, const DParams &P, uint32_t pixel_tiles, hipStream_t s) {
+    DParams R = P;
+    R.ntiles = pixel_tiles;
+    timed(a, 1, s, [&] { return launch_wf_resolve(R, (uint32_t)(((unsigned long long)pixel_tiles * 64ull + 255ull) / 256ull), s); });
+}
+
+// The wavefront pipeline (k_wavefront.hip): per chunk of the film and per supersample, levels 0 .. L-1 top-down (closest,
+// shadow, shade), then the combine passes bottom-up.
 static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c, hipStream_t stream) {
-    const uint32_t levels = (a.flat.has_specular && P0.recursion > 0) ? P0.recursion + 1u : 1u;
+    const uint32_t levels = levels_of(a, P0);
     const uint32_t nsamples = P0.ss_root * P0.ss_root;
     // A supersampled launch runs its samples SIDE BY SIDE (DParams::ss_par): level 0 holds pixels x samples work items, one chain of
     // launches per chunk instead of one per sample, and a resolve pass sums each pixel's samples in their order.  The levels of a 9-sample
     // frame are nine times as wide -- a 512^2 film of glass fills the machine at its deep levels, which one sample at a time does not.
-    // lg_accel_set_sample_order(1) / LASGUN_SS_SERIAL=1 (A/B): one chain per sample, summed as they come.
-    static const bool ss_serial = [] { const char *e = std::getenv("LASGUN_SS_SERIAL"); return e && e[0] == '1'; }();
-    const uint32_t S = nsamples > 1 && !ss_serial && a.sample_order != 1 ? nsamples : 1u; // level-0 work items per pixel
-    // bytes per level-0 work item of a chunk
-    auto level_bytes = [&](uint32_t d) -> size_t {
-        size_t b = 0;
-        if (d >= 1) b += 6 * 8;                       // ray queue
-        if (levels > 1) b += 3 * 8;                   // output / li
-        if (d + 1 < levels) b += 8 * 8 + 2 * 4;       // children's weights and indices
-        return b;
-    };
-    size_t per_item = (nsamples > 1 ? 3 * 8 : 0);
-    for (uint32_t d = 0; d < levels; ++d) per_item += level_bytes(d) << d;
-    per_item += ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4; // hit queue, frame, visibility of the widest level: dense part + appended part
-    const size_t per_pixel = per_item * S;
-    if (a.wf_budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        // per launch CONTEXT, and an accel keeps up to MAX_LAUNCH_CTXS of them plus the band contexts (a caller with
-        // four frames in flight uses five): a sixteenth of the free memory, at most 8 GiB each (the headline frame
-        // needs 3.3 GB and stays one chunk; an allocation that fails anyway halves the chunk below)
-        size_t budget = free_b / 16;
-        const char *env = std::getenv("LASGUN_WF_BUDGET_MB");
-        if (env && std::atoll(env) > 0) budget = (size_t)std::atoll(env) << 20;
-        else if (budget > (8ull << 30)) budget = 8ull << 30;
-        a.wf_budget = budget < (64ull << 20) ? (64ull << 20) : budget;
-    }
-    unsigned long long chunk_tiles = a.wf_budget / (per_pixel * 64);
-    const unsigned long long cap_limit = (0xFFFFFFF0ull >> (levels - 1)) / (64ull * S); // ray indices are 32-bit
-    if (chunk_tiles > cap_limit) chunk_tiles = cap_limit;
-    if (chunk_tiles < 1) chunk_tiles = 1;
-    if (chunk_tiles > P0.ntiles) chunk_tiles = P0.ntiles;
+    // lg_accel_set_sample_order(1): one chain per sample, summed as they come.
+    const uint32_t S = nsamples > 1 && a.sample_order != 1 ? nsamples : 1u; // level-0 work items per pixel
+    // beside the level arrays: the hit queue, frame and visibility of the widest level, dense part + appended part
+    ChunkPlan plan(a, P0, false, S, ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4);
     // Bands on internal streams: opt-in (lg_accel_set_wf_split, or LASGUN_WF_SPLIT=n as the default), launches of 2 Mpixel and
     // more.  Measured: one headline frame at a time 7.79 -> 7.50 ms with 4 bands, but 7.20 -> 7.46 ms
     // when the caller already keeps four frames in flight -- which is why it is not the default.
@@ -139,65 +226,39 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
     // (at most MAX_WF_BANDS bands: their contexts and the callers' streams share the accel's MAX_LAUNCH_CTXS slots, and a
     // context that has to be recycled costs a device-wide synchronise)
     const unsigned split = (unsigned long long)P0.ntiles * 64ull >= (1ull << 21) ? std::min(want, MAX_WF_BANDS) : 1u;
-    if (split > 1) chunk_tiles = std::min<unsigned long long>(chunk_tiles, (P0.ntiles + split - 1) / split);
-    unsigned long long nchunks = (P0.ntiles + chunk_tiles - 1) / chunk_tiles;
+    if (split > 1) plan.chunk_tiles = std::min<unsigned long long>(plan.chunk_tiles, (P0.ntiles + split - 1) / split);
+    const unsigned long long nchunks = (P0.ntiles + plan.chunk_tiles - 1) / plan.chunk_tiles;
     const unsigned nstreams = split > 1 && nchunks > 1 ? (unsigned)std::min<unsigned long long>(split, nchunks) : 0u; // 0: everything on the caller's stream
     if (nstreams) ensure_aux_streams(a, nstreams);
-    unsigned long long n0 = 0;
-    size_t need = 0, hit_cap = 0, hit_len = 0;
     const uint32_t nlaunch = 4 * levels;
     const uint32_t CL = TILE_COUNTER_WORDS; // the queue counts (3 per level) in the first block, then a block of tile heads per launch (one head per XCD, each on a line of its own)
-    auto size_chunk = [&] {
-        n0 = chunk_tiles * 64ull * S;
-        need = (size_t)n0 * per_item + 4096 * (3 * levels + 4);
-        hit_cap = (size_t)n0 << (levels - 1);
-        hit_len = hit_cap + hit_cap / 64 * (WF_FULL_MIN_HOST - 1); // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
-        nchunks = (P0.ntiles + chunk_tiles - 1) / chunk_tiles;
-    };
-    size_chunk();
+    auto hit_cap = [&] { return (size_t)plan.n0() << (levels - 1); };
+    auto hit_len = [&] { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); }; // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
     struct Carved {
-        std::vector<double *> q, out, spec;
-        std::vector<uint32_t *> child;
+        LevelArrays L;
         uint32_t *hq = nullptr, *vis = nullptr, *counters = nullptr;
-        double *frame = nullptr, *accum = nullptr;
+        double *frame = nullptr;
     };
-    auto carve = [&](lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk (256-byte aligned)
-        if (cx.wf_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); cx.wf_mem.alloc(need); }
+    auto carve = [&](lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk
+        if (cx.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); cx.wf_mem.alloc(plan.need()); }
         if (cx.wf_counters.n < CL * (1 + nlaunch)) { HIP_TRY(hipDeviceSynchronize()); cx.wf_counters.alloc(CL * (1 + nlaunch)); }
         Carved k;
-        k.q.assign(levels, nullptr); k.out.assign(levels, nullptr); k.spec.assign(levels, nullptr); k.child.assign(levels, nullptr);
-        uint8_t *cur = cx.wf_mem.p;
-        auto take = [&](size_t bytes) { uint8_t *p = cur; cur += (bytes + 255) & ~(size_t)255; return p; };
-        for (uint32_t d = 0; d < levels; ++d) {
-            const size_t cap = (size_t)n0 << d;
-            if (d >= 1) k.q[d] = (double *)take(cap * 6 * 8);
-            if (levels > 1) k.out[d] = (double *)take(cap * 3 * 8);
-            if (d + 1 < levels) { k.spec[d] = (double *)take(cap * 8 * 8); k.child[d] = (uint32_t *)take(cap * 2 * 4); }
-        }
-        k.hq = (uint32_t *)take(hit_len * 4);
-        k.frame = (double *)take(hit_len * STASH_DOUBLES * 8);
-        k.vis = (uint32_t *)take(hit_len * 4);
-        k.accum = nsamples > 1 ? (double *)take((size_t)n0 * 3 * 8) : nullptr;
+        k.L = plan.carve(cx.wf_mem.p, [&](auto &take) {
+            k.hq = (uint32_t *)take(hit_len() * 4);
+            k.frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
+            k.vis = (uint32_t *)take(hit_len() * 4);
+        });
         k.counters = cx.wf_counters.p;
         return k;
     };
     std::vector<Carved> carved;
     std::vector<hipStream_t> lanes;
-    for (;;) { // memory that is not there (other contexts, other accels, other processes): halve the chunk and carve again
-        try {
-            carved.clear(); lanes.clear();
-            if (nstreams) for (unsigned j = 0; j < nstreams; ++j) { lanes.push_back(a.aux_streams[j]); carved.push_back(carve(ctx_for(a, a.aux_streams[j]))); }
-            else { lanes.push_back(stream); carved.push_back(carve(c)); }
-            break;
-        } catch (const Error &e) {
-            if (std::string(e.what()).find("hipMalloc") == std::string::npos || chunk_tiles <= 1) throw;
-            (void)hipGetLastError(); // (the failed allocation's error must not be what the next launch reports)
-            chunk_tiles = (chunk_tiles + 1) / 2;
-            a.wf_budget = std::max<size_t>(a.wf_budget / 2, 64ull << 20); // (later launches start from what fitted)
-            size_chunk();
-            if (std::getenv("LASGUN_DEBUG")) std::fprintf(stderr, "[lasgun] wavefront: %s -- chunks of %llu tiles instead\n", e.what(), chunk_tiles);
-        }
-    }
+    plan.fit([&] {
+        carved.clear(); lanes.clear();
+        if (nstreams) for (unsigned j = 0; j < nstreams; ++j) { lanes.push_back(a.aux_streams[j]); carved.push_back(carve(ctx_for(a, a.aux_streams[j]))); }
+        else { lanes.push_back(stream); carved.push_back(carve(c)); }
+    });
+    const unsigned long long chunk_tiles = plan.chunk_tiles, n0 = plan.n0();
     if (nstreams) {
         HIP_TRY(hipEventRecord(a.aux_fork, stream)); // the bands start after whatever the caller's stream holds (a film clear, the previous frame's copy)
         for (unsigned j = 0; j < nstreams; ++j) HIP_TRY(hipStreamWaitEvent(a.aux_streams[j], a.aux_fork, 0));
@@ -209,75 +270,28 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
     const uint32_t flat_cap = a.cus * 16u;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
-    hipStream_t ls = stream; // the stream of the chunk being enqueued
-    auto timed = [&](int kind, auto &&launch) { // HIP events around ONE kernel on its launch stream
-        hipEvent_t k0 = nullptr, k1 = nullptr;
-        if (a.profiling) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); HIP_TRY(hipEventRecord(k0, ls)); }
-        HIP_TRY(launch());
-        if (a.profiling) { HIP_TRY(hipEventRecord(k1, ls)); a.kind_events[kind].emplace_back(k0, k1); }
-    };
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] wavefront: levels %u, %llu tiles in chunks of %llu on %u stream(s) (%.1f MiB per context), trace grid %u x %u, stack %u, max_blocks %u\n", levels,
-                     (unsigned long long)P0.ntiles, chunk_tiles, nstreams ? nstreams : 1u, need / 1048576.0, trace_cap, ldss ? 1024u : 256u, depth, a.max_blocks);
-    // A SMALL frame's chain is a dozen dependent launches of a few microseconds each (Cornell glass 512^2: 16 launches for 0.4 ms), and
-    // what separates them on a stream is the runtime's launch path per kernel.  The chain has no host decision in it -- fixed grids, counts
-    // on the device -- so it is captured ONCE into a HIP graph and replayed: frames of <= 2^20 work items, one chunk, the caller's own
-    // stream (not the null stream), not profiling; captured when the same chain (a hash of every parameter: scene tables, camera, film
-    // pointer, carved arrays, grids) comes a second time in a row on the context, so a program that renders one frame never pays
-    // for a capture, and re-captured at most MAX_GRAPH_CAPTURES times per context (a caller that changes the film every frame gains nothing
-    // and stops paying).  The bytes are the same launches' bytes.
-    // MEASURED, and OFF unless LASGUN_GRAPH=1 (profiles/r06_small_frames.jsonl, tools/ab_small_frames.sh, variants in turn on one box): the
-    // replay is SLOWER where it was meant to pay -- the README sphere at 512^2 0.086 -> 0.093 ms alone and 0.072 -> 0.081 back to back (4 nodes),
-    // Cornell plastic 0.119 -> 0.129 / 0.104 -> 0.116 -- and within +-2 % on every longer chain (simple.rs 9 spp, Cornell glass at 256^2 / 512^2,
-    // spooky.rs, playground.rs, simplecows.rs: 16 - 28 nodes).  On this runtime (ROCm 7.2) a graph launch costs more than the stream launches it
-    // replaces and the gaps between dependent kernels do not shrink.
-    static const bool graphs_on = [] { const char *e = std::getenv("LASGUN_GRAPH"); return e && e[0] == '1'; }();
-    constexpr unsigned MAX_GRAPH_CAPTURES = 8;
-    bool capturing = false;
-    if (graphs_on && stream != nullptr && nstreams == 0 && nchunks == 1 && !a.profiling && (unsigned long long)P0.ntiles * 64ull * S <= (1ull << 20)) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusActive; }
-        if (cs == hipStreamCaptureStatusNone) {
-            uint64_t sig = 1469598103934665603ull;
-            auto mix = [&sig](const void *q, size_t n) { const uint8_t *b = (const uint8_t *)q; for (size_t i = 0; i < n; ++i) { sig ^= b[i]; sig *= 1099511628211ull; } };
-            mix(&P0, sizeof P0);
-            const Carved &K0 = carved[0];
-            mix(&K0.hq, sizeof K0.hq); mix(&K0.counters, sizeof K0.counters); mix(&K0.frame, sizeof K0.frame); mix(&K0.accum, sizeof K0.accum);
-            const uint64_t shape[8] = {levels, S, n0, chunk_tiles, trace_cap, depth, (uint64_t)a.fast | ((uint64_t)ldss << 1), (uint64_t)(uintptr_t)a.lds_image.p};
-            mix(shape, sizeof shape);
-            if (sig == 0) sig = 1;
-            if (c.wf_graph && c.wf_graph_sig == sig) {
-                const hipError_t ge = hipGraphLaunch(c.wf_graph, stream);
-                if (ge == hipSuccess) return;
-                (void)hipGetLastError(); // a replay that is refused: the plain chain below
-                (void)hipGraphExecDestroy(c.wf_graph); c.wf_graph = nullptr; c.wf_graph_sig = 0; c.wf_graph_captures = MAX_GRAPH_CAPTURES;
-            } else if (c.wf_last_sig == sig && c.wf_graph_captures < MAX_GRAPH_CAPTURES) {
-                if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess) { capturing = true; c.wf_graph_captures++; }
-                else (void)hipGetLastError();
-            }
-            c.wf_last_sig = sig;
-        }
-    }
-    const uint64_t chain_sig = c.wf_last_sig;
-    auto run_chain = [&] {
+                     (unsigned long long)P0.ntiles, chunk_tiles, nstreams ? nstreams : 1u, plan.need() / 1048576.0, trace_cap, ldss ? 1024u : 256u, depth, a.max_blocks);
+    // (A small frame's chain replayed as a HIP graph was measured in round 6 and retired: on this runtime a graph launch costs more than
+    // the stream launches it replaces -- the README sphere at 512^2 0.086 -> 0.093 ms, Cornell plastic 0.119 -> 0.129 ms, every longer
+    // chain within +-2 %; profiles/r06_small_frames.jsonl.)
     unsigned long long chunk_no = 0;
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles, ++chunk_no) {
         const Carved &K = carved[chunk_no % carved.size()];
-        ls = lanes[chunk_no % lanes.size()];
-        const std::vector<double *> &q = K.q, &out = K.out, &spec = K.spec;
-        const std::vector<uint32_t *> &child = K.child;
-        uint32_t *const hq = K.hq, *const vis = K.vis;
-        double *const frame = K.frame, *const accum = K.accum;
+        const hipStream_t ls = lanes[chunk_no % lanes.size()]; // the stream of this chunk
+        const std::vector<double *> &q = K.L.q, &out = K.L.out, &spec = K.L.spec;
+        const std::vector<uint32_t *> &child = K.L.child;
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
         const uint32_t pixel_tiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ntiles = pixel_tiles * S; // level 0's work tiles
         P.ss_par = S;
         P.n_items = n0; // stride of the sample accumulator
-        P.accum = accum;
+        P.accum = K.L.accum;
         P.wf_levels = levels;
         P.wf_counts = K.counters;
-        P.wf_hit_cap = hit_cap; P.wf_hit_stride = hit_len; P.wf_hq = hq; P.frame = frame; P.vis = vis;
+        P.wf_hit_cap = hit_cap(); P.wf_hit_stride = hit_len(); P.wf_hq = K.hq; P.frame = K.frame; P.vis = K.vis;
 #ifdef LG_STAMPS
         P.stats = a.stats.p;
         P.stamp_counts = reinterpret_cast<unsigned long long *>(a.stats.p + 1);
@@ -288,7 +302,6 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
         }
         const uint32_t tiles_needed = (P.ntiles + 3u) / 4u;
         const uint32_t trace_blocks0 = ldss ? trace_cap : std::min(trace_cap, tiles_needed);
-        const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull); // level 0: one thread per pixel
         // level-0 shade: one wave per dense tile and per tile the appended hits can fill (< WF_FULL_MIN of every 64 rays)
         const uint32_t shade_blocks0 = (uint32_t)(((unsigned long long)P.ntiles + ((unsigned long long)P.ntiles * (WF_FULL_MIN_HOST - 1) + 63ull) / 64ull + 3ull) / 4ull);
         for (uint32_t sidx = 0; sidx < nsamples / S; ++sidx) {
@@ -297,7 +310,7 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
             uint32_t launch_no = 0;
             auto level_params = [&](uint32_t d) {
                 P.wf_level = d;
-                P.wf_cap = (unsigned long long)n0 << d; P.wf_cap_next = (unsigned long long)n0 << (d + 1);
+                P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
                 P.wf_q = q[d]; P.wf_out = out[d]; P.wf_spec = spec[d]; P.wf_child = child[d];
                 P.wf_q_next = d + 1 < levels ? q[d + 1] : nullptr;
                 P.wf_out_next = d + 1 < levels ? out[d + 1] : nullptr;
@@ -308,44 +321,18 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
                 // every deeper level may exceed only in waves, never in work per wave)
                 const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
                 level_params(d);
-                timed(0, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
+                timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
                 if (P.nlights > 0) {
                     level_params(d);
-                    timed(2, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
+                    timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
                 }
                 level_params(d);
-                timed(3, [&] { return launch_wf_shade(P, fb, ls); });
+                timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
             }
-            for (uint32_t d = levels - 1; d-- > 0;) {
-                level_params(d);
-                timed(1, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, ls); });
-            }
+            combine_levels(a, P, K.L, plan, ls);
         }
-        if (S > 1) {
-            DParams R = P;
-            R.ntiles = pixel_tiles;
-            timed(1, [&] { return launch_wf_resolve(R, (uint32_t)(((unsigned long long)pixel_tiles * 64ull + 255ull) / 256ull), ls); });
-        }
+        if (S > 1) resolve_samples(a, P, pixel_tiles, ls);
     }
-    };
-    if (capturing) { // record the chain, replay it; a capture that was begun is always ended (a stream left in capture mode is lost to its owner)
-        hipGraph_t g = nullptr;
-        try { run_chain(); } catch (...) { (void)hipStreamEndCapture(stream, &g); if (g) (void)hipGraphDestroy(g); (void)hipGetLastError(); throw; }
-        bool launched = false;
-        if (hipStreamEndCapture(stream, &g) == hipSuccess && g) {
-            if (c.wf_graph) { (void)hipGraphExecDestroy(c.wf_graph); c.wf_graph = nullptr; c.wf_graph_sig = 0; }
-            hipGraphExec_t x = nullptr;
-            if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) == hipSuccess && x) {
-                if (hipGraphLaunch(x, stream) == hipSuccess) { c.wf_graph = x; c.wf_graph_sig = chain_sig; launched = true; }
-                else (void)hipGraphExecDestroy(x);
-            }
-        }
-        if (g) (void)hipGraphDestroy(g);
-        (void)hipGetLastError();
-        if (launched) return; // (no bands, no profiling on this path)
-        c.wf_graph_captures = MAX_GRAPH_CAPTURES; // captured but not launched: the frame still has to be rendered, plainly, and this context stops trying
-    }
-    run_chain();
     for (unsigned j = 0; j < nstreams; ++j) { // join: the caller's stream continues when every band is done
         HIP_TRY(hipEventRecord(a.aux_done[j], a.aux_streams[j]));
         HIP_TRY(hipStreamWaitEvent(stream, a.aux_done[j], 0));
@@ -355,47 +342,18 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
 
 // The queue organisation (k_queue.hip): per chunk of the film and per supersample ONE persistent launch that runs every recursion
 // level -- its waves pull 64-ray packets from per-level queues, deepest level first -- then the combine passes bottom-up, shared
-// with the level-by-level pipeline.  Queue capacities are worst case (level d: 2^d rays per pixel of the chunk), so nothing can
-// overflow; a recursive scene may take a large share of the HBM for it (a 4096^2 frame at recursion 3: 26 GB of 288) and keeps ONE
-// chunk in flight per launch context.
+// with the level-by-level pipeline.  A recursive scene may take a large share of the HBM for its worst-case capacities (a 4096^2
+// frame at recursion 3: 26 GB of 288) and keeps ONE chunk in flight per launch context.
 static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c, bool split, hipStream_t stream) {
-    const uint32_t levels = (a.flat.has_specular && P0.recursion > 0) ? P0.recursion + 1u : 1u;
+    const uint32_t levels = levels_of(a, P0);
     const uint32_t nsamples = P0.ss_root * P0.ss_root;
-    static const bool ss_serial = [] { const char *e = std::getenv("LASGUN_SS_SERIAL"); return e && e[0] == '1'; }();
     // level 0's tiles in parts (enqueue_mega, DParams::split_shift): the children's packets are then as narrow as their parents -- a small
     // launch's recursion chains are walked by four times the waves, 16 lanes each
     const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split ? MEGA_SPLIT : 1u, split_shift = parts == 8u ? 3u : parts == 4u ? 2u : parts == 2u ? 1u : 0u;
-    const uint32_t S = (nsamples > 1 && !ss_serial && a.sample_order != 1 ? nsamples : 1u) * parts; // samples side by side (enqueue_wavefront) x parts: level-0 tiles per pixel tile
-    auto level_bytes = [&](uint32_t d) -> size_t { // per ray of level d
-        size_t b = 0;
-        if (d >= 1) b += 6 * 8;                       // ray queue
-        if (levels > 1) b += 3 * 8;                   // output / li
-        if (d + 1 < levels) b += 8 * 8 + 2 * 4;       // children's weights and indices
-        return b;
-    };
-    size_t per_item = (nsamples > 1 ? 3 * 8 : 0) + 1;
-    for (uint32_t d = 0; d < levels; ++d) per_item += level_bytes(d) << d;
-    const size_t per_pixel = per_item * S;
-    if (a.queue_budget == 0) {
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-        // a recursive scene: up to a quarter of the free memory (at most 48 GiB) per launch context, so that a 4096^2 frame is one
-        // launch; others need a few bytes per pixel and take the wavefront pipeline's share (an allocation that fails halves the chunk)
-        size_t budget = levels > 1 ? free_b / 4 : free_b / 16;
-        const size_t cap = levels > 1 ? (48ull << 30) : (8ull << 30);
-        const char *env = std::getenv("LASGUN_QUEUE_BUDGET_MB");
-        const bool from_env = env && std::atoll(env) > 0;
-        if (from_env) budget = (size_t)std::atoll(env) << 20; // (as given: tests cut small films into many chunks with it)
-        else if (budget > cap) budget = cap;
-        a.queue_budget = !from_env && budget < (64ull << 20) ? (64ull << 20) : budget;
-    }
-    unsigned long long chunk_tiles = a.queue_budget / (per_pixel * 64);
-    const unsigned long long cap_limit = (0xFFFFFF00ull >> (levels - 1)) / (64ull * S); // ray indices are 32-bit
-    if (chunk_tiles > cap_limit) chunk_tiles = cap_limit;
-    if (chunk_tiles < 1) chunk_tiles = 1;
-    if (chunk_tiles > P0.ntiles) chunk_tiles = P0.ntiles;
-    if (chunk_tiles < P0.ntiles && P0.mode == 0u && P0.tiles_x != 0u && chunk_tiles >= (unsigned long long)P0.tiles_x * 32ull)
-        chunk_tiles -= chunk_tiles % ((unsigned long long)P0.tiles_x * 32ull); // whole rows of 32 x 32-tile blocks: the block order applies to every chunk
+    const uint32_t S = (nsamples > 1 && a.sample_order != 1 ? nsamples : 1u) * parts; // samples side by side (enqueue_wavefront) x parts: level-0 tiles per pixel tile
+    // (+ 1 byte per level-0 work item, as the organisation was first written: nothing is carved for it.  It stands in for the packets'
+    // ready words, which live in wf_counters -- 4 bytes per 64-ray packet of the levels >= 1, 7/8 of a byte per item at four levels.)
+    ChunkPlan plan(a, P0, true, S, 1);
     // level 0's work items: units of consecutive 8x8 tiles whose specular children the wave compacts into packets of its own.  Default
     // 1 (measured, config 4 / 4m in ms: 1 tile 39.0 / 16.4, 2: 40.0 / 17.0, 4: 41.0 / 18.5, 8: 44.6 / 22.2, 16: 51.7 / 31.6 -- a mesh tile is a
     // millisecond of work, so longer units lengthen the launch's tail by more than fuller packets save); LASGUN_QUEUE_UNIT: A/B
@@ -407,62 +365,28 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
     const bool ldss = a.lds_scene && a.ldss_blocks;
     const uint32_t blocks_cap = ldss ? a.ldss_blocks : a.queue_blocks;
     const unsigned long long threads = (unsigned long long)blocks_cap * (ldss ? 1024ull : 256ull);
-    unsigned long long n0 = 0;
-    size_t need = 0, nready = 0;
-    struct Carved {
-        std::vector<double *> q, out, spec;
-        std::vector<uint32_t *> child;
-        double *accum = nullptr;
-    } K;
-    for (;;) { // memory that is not there: halve the chunk and carve again
-        try {
-            n0 = chunk_tiles * 64ull * S;
-            need = (size_t)n0 * per_item + 4096 * (4 * levels + 4);
-            nready = (size_t)chunk_tiles * S * ((1ull << levels) - 2ull) + (size_t)levels * QR_SLACK; // one word per packet of the levels >= 1, + slack per level
-            if (c.wf_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); c.wf_mem.alloc(need); }
-            if (c.wf_counters.n < QC_WORDS + nready) { HIP_TRY(hipDeviceSynchronize()); c.wf_counters.alloc(QC_WORDS + nready); }
-            if (P0.nlights > 0 && c.stash.n < (size_t)threads * STASH_DOUBLES) { HIP_TRY(hipDeviceSynchronize()); c.stash.alloc((size_t)threads * STASH_DOUBLES); }
-            break;
-        } catch (const Error &e) {
-            if (std::string(e.what()).find("hipMalloc") == std::string::npos || chunk_tiles <= 1) throw;
-            (void)hipGetLastError();
-            chunk_tiles = (chunk_tiles + 1) / 2;
-            a.queue_budget = std::max<size_t>(a.queue_budget / 2, 64ull << 20);
-            if (std::getenv("LASGUN_DEBUG")) std::fprintf(stderr, "[lasgun] queue: %s -- chunks of %llu tiles instead\n", e.what(), chunk_tiles);
-        }
-    }
-    {
-        K.q.assign(levels, nullptr); K.out.assign(levels, nullptr); K.spec.assign(levels, nullptr); K.child.assign(levels, nullptr);
-        uint8_t *cur = c.wf_mem.p;
-        auto take = [&](size_t bytes) { uint8_t *p = cur; cur += (bytes + 255) & ~(size_t)255; return p; };
-        for (uint32_t d = 0; d < levels; ++d) {
-            const size_t cap = (size_t)n0 << d;
-            if (d >= 1) K.q[d] = (double *)take(cap * 6 * 8);
-            if (levels > 1) K.out[d] = (double *)take(cap * 3 * 8);
-            if (d + 1 < levels) { K.spec[d] = (double *)take(cap * 8 * 8); K.child[d] = (uint32_t *)take(cap * 2 * 4); }
-        }
-        K.accum = nsamples > 1 ? (double *)take((size_t)n0 * 3 * 8) : nullptr;
-    }
+    // one word per packet of the levels >= 1, + slack per level
+    auto nready = [&] { return (size_t)plan.chunk_tiles * S * ((1ull << levels) - 2ull) + (size_t)levels * QR_SLACK; };
+    plan.fit([&] {
+        if (c.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); c.wf_mem.alloc(plan.need()); }
+        if (c.wf_counters.n < QC_WORDS + nready()) { HIP_TRY(hipDeviceSynchronize()); c.wf_counters.alloc(QC_WORDS + nready()); }
+        if (P0.nlights > 0 && c.stash.n < (size_t)threads * STASH_DOUBLES) { HIP_TRY(hipDeviceSynchronize()); c.stash.alloc((size_t)threads * STASH_DOUBLES); }
+    });
+    const unsigned long long chunk_tiles = plan.chunk_tiles;
+    const LevelArrays K = plan.carve(c.wf_mem.p, [](auto &) {});
     if (!a.q_err) a.q_err = g_err_words.take();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
-    auto timed = [&](int kind, auto &&launch) { // HIP events around ONE kernel on its launch stream
-        hipEvent_t k0 = nullptr, k1 = nullptr;
-        if (a.profiling) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); HIP_TRY(hipEventRecord(k0, stream)); }
-        HIP_TRY(launch());
-        if (a.profiling) { HIP_TRY(hipEventRecord(k1, stream)); a.kind_events[kind].emplace_back(k0, k1); }
-    };
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] queue: levels %u, %llu tiles in chunks of %llu (%.1f MiB), grid %u x %u, stack %u\n", levels,
-                     (unsigned long long)P0.ntiles, chunk_tiles, need / 1048576.0, blocks_cap, ldss ? 1024u : 256u, a.stack_depth);
-    const uint32_t flat_cap = a.cus * 16u;
+                     (unsigned long long)P0.ntiles, chunk_tiles, plan.need() / 1048576.0, blocks_cap, ldss ? 1024u : 256u, a.stack_depth);
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
         const uint32_t pixel_tiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ntiles = pixel_tiles * S; // level 0's tiles
         P.ss_par = S / parts; P.split_shift = split_shift;
-        P.n_items = n0; // SoA stride of level 0's arrays and of the sample accumulator
+        P.n_items = plan.n0(); // SoA stride of level 0's arrays and of the sample accumulator
         P.accum = K.accum;
         P.wf_levels = levels;
         P.q_ctl = c.wf_counters.p; P.q_ready = c.wf_counters.p + QC_WORDS; P.q_err = a.q_err;
@@ -480,31 +404,19 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
             P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
         }
         const uint32_t blocks = ldss ? blocks_cap : std::min(blocks_cap, (P.q_units + 3u) / 4u);
-        const size_t nready_now = nready;
         for (uint32_t sidx = 0; sidx < nsamples / (S / parts); ++sidx) {
             P.sample_index = sidx;
-            HIP_TRY(hipMemsetAsync(c.wf_counters.p, 0, (QC_WORDS + (levels > 1 ? nready_now : 0)) * sizeof(uint32_t), stream));
-            timed(4, [&] { return launch_queue(P, blocks, stream); });
-            for (uint32_t d = levels - 1; d-- > 0;) { // bottom-up: li of level d's rays from their children's (integrate.rs:79, 103, 129)
-                P.wf_level = d;
-                P.wf_cap = (unsigned long long)n0 << d; P.wf_cap_next = (unsigned long long)n0 << (d + 1);
-                P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-                const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull);
-                timed(1, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, stream); });
-            }
+            HIP_TRY(hipMemsetAsync(c.wf_counters.p, 0, (QC_WORDS + (levels > 1 ? nready() : 0)) * sizeof(uint32_t), stream));
+            timed(a, 4, stream, [&] { return launch_queue(P, blocks, stream); });
+            combine_levels(a, P, K, plan, stream);
         }
-        if (S / parts > 1) { // a pixel's samples summed in their order (k_wavefront.hip, wf_resolve_kernel)
-            DParams R = P;
-            R.ntiles = pixel_tiles;
-            timed(1, [&] { return launch_wf_resolve(R, (uint32_t)(((unsigned long long)pixel_tiles * 64ull + 255ull) / 256ull), stream); });
-        }
+        if (S / parts > 1) resolve_samples(a, P, pixel_tiles, stream);
     }
     if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
 }
 
 // ---- which organisation renders a launch -----------------------------------------------------------------
 enum Org : int { ORG_MEGA = 0, ORG_WAVEFRONT = 1, ORG_QUEUE = 2 };
-static uint32_t levels_of(const lg_accel &a, const DParams &P) { return (a.flat.has_specular && P.recursion > 0) ? P.recursion + 1u : 1u; }
 // what each organisation can take: the queue organisation the reference traversal with <= 32 lights and <= 8 recursion levels, the
 // level-by-level pipeline any scene with <= 32 lights; neither the counting variant
 static bool org_possible(const lg_accel &a, const DParams &P, bool stats, Org org) {
@@ -547,13 +459,15 @@ static bool mega_par_possible(const DParams &P, bool stats) {
     const unsigned long long nsamples = (unsigned long long)P.ss_root * P.ss_root;
     return nsamples > 1 && !stats && (unsigned long long)P.ntiles * 64ull * nsamples * 24ull <= (1ull << 30);
 }
+// the waves of the megakernel's grid (its LDS-resident form: one 1024- or 768-lane workgroup per CU)
+static unsigned long long mega_grid_waves(const lg_accel &a) {
+    const bool lds_form = !a.fast && a.lds_scene && a.ldss_blocks;
+    return lds_form ? (unsigned long long)a.ldss_blocks * (a.mega_narrow ? 12u : 16u) : (unsigned long long)(a.fast ? a.max_blocks_fast : a.max_blocks) * 4ull;
+}
 static bool mega_par_by_rule(const lg_accel &a, const DParams &P, bool stats) {
-    static const int ss_mega = [] { const char *e = std::getenv("LASGUN_SS_MEGA"); return e ? std::atoi(e) : -1; }(); // A/B: 0 never, 1 always
     if (!mega_par_possible(P, stats) || a.sample_order == 1) return false;
     if (a.sample_order == 0) return true;
-    const bool lds_form = !a.fast && a.lds_scene && a.ldss_blocks;
-    const unsigned long long grid_waves = lds_form ? (unsigned long long)a.ldss_blocks * (a.mega_narrow ? 12u : 16u) : (unsigned long long)(a.fast ? a.max_blocks_fast : a.max_blocks) * 4ull;
-    return ss_mega >= 0 ? ss_mega == 1 : P.ntiles < SS_PAR_WAVES * grid_waves;
+    return P.ntiles < SS_PAR_WAVES * mega_grid_waves(a);
 }
 // A SMALL launch may hand its tiles out in QUARTERS (DParams::split_shift: 16 lanes of a tile per wave, four times the waves at work): a frame of
 // fewer tiles than the grid has waves is as slow as its slowest tile's recursion tree, and a quarter of a tile is a shorter tree walked by
@@ -561,10 +475,8 @@ static bool mega_par_by_rule(const lg_accel &a, const DParams &P, bool stats) {
 // 100k-triangle metal torus at 256^2 2.23 -> 1.82; cheap scenes and frames of 1024^2 and more lose (idle lanes are then lost throughput).
 // One more candidate of the measured choice; never by rule.
 static bool mega_split_possible(const lg_accel &a, const DParams &P, bool stats) {
-    const bool lds_form = !a.fast && a.lds_scene && a.ldss_blocks;
-    const unsigned long long grid_waves = lds_form ? (unsigned long long)a.ldss_blocks * (a.mega_narrow ? 12u : 16u) : (unsigned long long)(a.fast ? a.max_blocks_fast : a.max_blocks) * 4ull;
     const unsigned long long work = (unsigned long long)P.ntiles * (mega_par_by_rule(a, P, stats) ? (unsigned long long)P.ss_root * P.ss_root : 1ull);
-    return !stats && P.ntiles >= 2u && work <= 4ull * grid_waves;
+    return !stats && P.ntiles >= 2u && work <= 4ull * mega_grid_waves(a);
 }
 static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, bool par, bool split, bool stats, hipStream_t stream) {
     const uint32_t nsamples = P.ss_root * P.ss_root;
@@ -574,9 +486,8 @@ static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, 
         if (c.wf_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); c.wf_mem.alloc(need); }
         P.accum = reinterpret_cast<double *>(c.wf_mem.p); P.n_items = n_items; P.ss_par = nsamples; P.ntiles *= nsamples;
     }
-    { // tiles handed out in parts: the measured choice's candidate, or LASGUN_MEGA_SPLIT=2|4|8 (A/B)
-        static const uint32_t split_env = [] { const char *e = std::getenv("LASGUN_MEGA_SPLIT"); const int v = e ? std::atoi(e) : 0; return v == 2 || v == 4 || v == 8 ? (uint32_t)v : 1u; }();
-        const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split_env > 1u ? split_env : split ? MEGA_SPLIT : 1u;
+    { // tiles handed out in parts: lg_accel_set_tile_parts, or the measured choice's candidate
+        const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split ? MEGA_SPLIT : 1u;
         if (parts > 1u && !stats && (unsigned long long)P.ntiles * parts < (1ull << 31)) { P.split_shift = parts == 2u ? 1u : parts == 4u ? 2u : 3u; P.ntiles *= parts; }
     }
     uint32_t cap = a.fast ? a.max_blocks_fast : a.max_blocks;
@@ -688,8 +599,6 @@ std::atomic<int> g_call_depth{0};
 } // namespace
 CallScope::CallScope() { if (g_call_depth.fetch_add(1) == 0) g_call_serial.fetch_add(1); }
 CallScope::~CallScope() { g_call_depth.fetch_sub(1); }
-namespace {
-} // namespace
 extern "C" void lg_internal_call_scope(int enter) { // (multi.cpp: one lg_multi_capture* is one call, whatever its shares launch)
     if (enter) { if (g_call_depth.fetch_add(1) == 0) g_call_serial.fetch_add(1); }
     else g_call_depth.fetch_sub(1);

@@ -236,7 +236,6 @@ __device__ __forceinline__ Pixel pixel_of(const DParams &P, uint32_t tile, uint3
         px.active = px.x < P.x1 && vy < P.y1;
         px.y = P.ilv_n > 1u ? ((vy / P.ilv_b) * P.ilv_n + P.ilv_r) * P.ilv_b + vy % P.ilv_b : vy;
         px.pix = (unsigned long long)(vy - P.out_row0) * P.out_pitch + (px.x - P.out_x0);
-#ifndef LG_NO_LATTICE // (A/B: what this branch costs the kernels it is inlined into)
     } else if (P.mode == 4 || P.mode == 5) {
         // A strided subset {k + i*n} (lib.rs:152) -- mode 4 -- or several of one n (lg_capture_subsets) -- mode 5 -- as the LATTICE it is: its
         // pixels sit at x = (k - y*w) mod n + n*c in row y, one per period of n.  A tile is 64 (mode 5: sub_rows = 64 / m) consecutive rows of one
@@ -265,7 +264,6 @@ __device__ __forceinline__ Pixel pixel_of(const DParams &P, uint32_t tile, uint3
         px.y = px.active ? y : 0u;
         const unsigned long long place = P.mode == 5 ? (unsigned long long)q * P.sub_m + j : (unsigned long long)q; // (mode 3's work item q * m + j)
         px.pix = px.active ? (P.out_compact ? place : (unsigned long long)y * P.w + x) : 0ull;
-#endif
     } else {
         unsigned long long i = (unsigned long long)tile * 64ull + lane;
         px.active = i < P.sub_count;

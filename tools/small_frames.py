@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Small frames -- the sizes the reference's own examples use -- one after the other: latency (a frame alone, synchronised: median of 40) and
-back-to-back rate (40 frames on the stream, one synchronise), level by level (the organisation whose launch chain a HIP graph replays) and
-as the default picks.  Run once per variant (LASGUN_GRAPH=0 / 1) in turn: tools/ab_small_frames.sh.  Every film is compared with the
-first variant's through a checksum."""
+back-to-back rate (40 frames on the stream, one synchronise), level by level and as the default picks.  Every film's checksum is printed,
+so that runs of two builds can be compared."""
 import hashlib
 import json
 import os
@@ -55,7 +54,7 @@ def main():
                     G.capture_rows_device(acc, size, size, 0, size, film.data_ptr(), row0=0, stream=stream.cuda_stream)
                 torch.cuda.synchronize()
                 rate = (time.perf_counter() - t0) / 40 * 1e3
-            print(json.dumps({"frame": name, "organisation": label, "ran_as": G.last_organisation(acc), "graph": os.environ.get("LASGUN_GRAPH", "1"),
+            print(json.dumps({"frame": name, "organisation": label, "ran_as": G.last_organisation(acc),
                               "latency_ms_median": round(statistics.median(lat), 4), "latency_ms_min": round(min(lat), 4), "back_to_back_ms": round(rate, 4),
                               "film_sha": hashlib.sha1(film.cpu().numpy().tobytes()).hexdigest()[:12]}), flush=True)
 
