@@ -242,6 +242,23 @@ impl<'s> Accel<'s> {
     pub fn set_fast_mode(&self, fast: bool) {
         if unsafe { sys::lg_accel_set_mode(self.ptr, fast as i32) } != 0 { panic!("lasgun: {}", last_error()) }
     }
+    /// Closest hit of every ray (origin xyz, direction xyz): what the reference's `root.intersect` returns (bvh.rs:461-522), resolved to
+    /// world space as shading sees it; `t` is +inf where a ray hits nothing.  No counterpart among the reference's public items.
+    pub fn intersect(&self, rays: &[[f64; 6]]) -> Vec<sys::lg_hit> {
+        let mut hits = vec![sys::lg_hit::default(); rays.len()];
+        if rays.is_empty() { return hits }
+        let rc = unsafe { sys::lg_intersect(self.ptr, rays.as_ptr() as *const f64, rays.len(), hits.as_mut_ptr()) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        hits
+    }
+    /// Whether each segment o -> o + d is blocked (closest hit t < 1): the render's shadow test (point.rs:49)
+    pub fn occluded(&self, rays: &[[f64; 6]]) -> Vec<bool> {
+        let mut occ = vec![0u8; rays.len()];
+        if rays.is_empty() { return Vec::new() }
+        let rc = unsafe { sys::lg_occluded(self.ptr, rays.as_ptr() as *const f64, rays.len(), occ.as_mut_ptr()) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        occ.into_iter().map(|b| b != 0).collect()
+    }
 }
 impl<'s> Drop for Accel<'s> {
     fn drop(&mut self) { unsafe { sys::lg_accel_free(self.ptr) } }

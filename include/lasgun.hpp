@@ -158,6 +158,17 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded): rays are origin xyz, direction xyz
+    std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
+        std::vector<lg_hit> hits(rays.size());
+        if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
+        return hits;
+    }
+    std::vector<bool> occluded(const std::vector<std::array<double, 6>> &rays) const {
+        std::vector<uint8_t> occ(rays.size());
+        if (lg_occluded(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), occ.data())) throw Error(lg_last_error());
+        return std::vector<bool>(occ.begin(), occ.end());
+    }
 
   private:
     explicit Accel(lg_accel *a) : h_(a) {}

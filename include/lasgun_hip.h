@@ -362,6 +362,47 @@ int lg_host_check_strips(const lg_scene *, uint64_t out[8]);
  * back to the ray, and the ray to the box, that caused it. */
 int lg_trace_pixel(const lg_accel *, uint32_t width, uint32_t height, uint32_t x, uint32_t y, int fast, double *out, size_t out_len);
 
+/* Ray queries: the caller's own rays through the render's BVH walk, in the accel's traversal mode (reference, pruned --
+ * lg_accel_set_prune --, LDS-resident scene -- lg_accel_set_lds_scene --, opt-in fast mode) exactly as a capture walks them; no switch of
+ * their own.  One ray = 6 doubles: origin xyz, direction xyz (Ray3::new, ray.rs:28-33; the direction is used as given, not normalised).
+ * No counterpart among the reference's public items: its Accel and Primitive::intersect are pub (lib.rs:34,42), its Ray and RayIntersection
+ * are not. */
+typedef struct lg_hit {
+    double t;           /* closest hit's parameter, o + t*d; +INFINITY = no hit (then p / ng / ns are 0, kind 0, prim and instance
+                           0xFFFFFFFF, material -1) */
+    double p[3];        /* o + d*t in world space: the shading frame's point before the 2^-36 offset shading adds */
+    double ng[3];       /* unit geometric normal faced toward -d */
+    double ns[3];       /* unit shading normal (mesh smoothing, the cuboid's face normal, the sphere's) */
+    uint32_t kind;      /* 0 none, 1 sphere, 2 box / cube, 3 mesh triangle */
+    uint32_t prim;      /* sphere / box: its ordinal among the scene's spheres / boxes in scene-graph order (depth first, insertion
+                           order); triangle: its face number in its OBJ (triangle.rs:425-427) */
+    uint32_t instance;  /* the (nested) accel the primitive sits in: 0 = root, groups and mesh instances in scene-graph order */
+    int32_t material;   /* the material shading uses (integrate.rs:29-30, bvh.rs:513-515): an index for lg_accel_material */
+} lg_hit;               /* 96 bytes, no padding */
+
+/* Closest hit of every ray: hit i is what root.intersect(&Ray3::new(o, d), &mut isect) returns (bvh.rs:461-522), resolved to world space
+ * as shading sees it; t and the winning primitive are the reference's bit for bit, exact ties included (its visit order decides them).
+ * Any f64 input is accepted as it is (zero, infinite and NaN components included). */
+int lg_intersect(const lg_accel *, const double *rays, size_t n, lg_hit *hits);                  /* host arrays; synchronous */
+/* occluded[i] = 1 iff ray i's closest hit has t < 1.0 -- the segment o -> o + d is blocked: the shadow test of point.rs:49, run through
+ * the any-hit walk of the render's shadow passes. */
+int lg_occluded(const lg_accel *, const double *rays, size_t n, uint8_t *occluded);              /* host arrays; synchronous */
+/* Device forms: they only enqueue on hip_stream (NULL = HIP's default stream; one stream at a time per accel, as lg_capture_subset_device).
+ * dev_rays must be 8-byte aligned, dev_hits 16-byte aligned, and both device memory of the accel's device (hipPointerGetAttributes):
+ * anything else is an error before any launch.  n == 0 is a successful no-op. */
+int lg_intersect_device(const lg_accel *, const double *dev_rays, size_t n, lg_hit *dev_hits, void *hip_stream);
+int lg_occluded_device(const lg_accel *, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream);
+/* The rays the render traces for the pixels [x0,x1) x [y0,y1) of a width x height film: row-major pixels and, per pixel, the camera's
+ * samples in camera.rs order (idx = i*dim + j, camera.rs:137-146), 6 doubles each: (x1-x0) * (y1-y0) * supersamples rays. */
+int lg_camera_rays(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays);
+int lg_camera_rays_device(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                          double *dev_rays, void *hip_stream);
+uint32_t lg_camera_samples(const lg_accel *); /* rays per pixel of lg_camera_rays: the camera's supersamples */
+/* The material behind lg_hit::material: the POD as the caller passed it (or lg_material_default()). */
+int lg_accel_material(const lg_accel *, int32_t index, lg_material *out);
+/* The accel behind lg_hit::instance: its parent (-1 for the root) and, for a mesh instance, the ObjRef it was added with (-1 for a group). */
+int lg_accel_instance(const lg_accel *, uint32_t instance, int32_t *parent, int64_t *obj_ref);
+
 /* Known-answer and arithmetic probes: run the DEVICE intersectors / math on one thread. */
 int lg_kat_intersect(int kind, const double *params, const char *obj_text, size_t obj_len, const double origin[3],
                      const double d[3], double out[8]);

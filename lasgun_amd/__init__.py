@@ -77,7 +77,26 @@ _EXTRA = {
                                    _C.POINTER(_C.POINTER(_C.c_int64)), _C.POINTER(_C.c_size_t), _C.c_uint64 * 8]),
     "host_check_wide_records": (_C.c_int, [_C.c_void_p, _C.c_uint64 * 8]),
     "host_check_strips": (_C.c_int, [_C.c_void_p, _C.c_uint64 * 8]),
+    "intersect": (_C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
+    "occluded": (_C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p]),
+    "intersect_device": (_C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_void_p]),
+    "occluded_device": (_C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_size_t, _C.c_void_p, _C.c_void_p]),
+    "camera_rays": (_C.c_int, [_C.c_void_p] + [_C.c_uint32] * 6 + [_C.c_void_p]),
+    "camera_rays_device": (_C.c_int, [_C.c_void_p] + [_C.c_uint32] * 6 + [_C.c_void_p, _C.c_void_p]),
+    "camera_samples": (_C.c_uint32, [_C.c_void_p]),
+    "accel_material": (_C.c_int, [_C.c_void_p, _C.c_int32, _C.c_void_p]),
+    "accel_instance": (_C.c_int, [_C.c_void_p, _C.c_uint32, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int64)]),
 }
+
+
+class Hit(_C.Structure):  # lg_hit (include/lasgun_hip.h): one closest hit of a ray query
+    _fields_ = [("t", _C.c_double), ("p", _C.c_double * 3), ("ng", _C.c_double * 3), ("ns", _C.c_double * 3),
+                ("kind", _C.c_uint32), ("prim", _C.c_uint32), ("instance", _C.c_uint32), ("material", _C.c_int32)]
+
+
+HIT_DTYPE = _np.dtype(Hit)  # the numpy mirror of lg_hit: what HipApi.intersect returns
+assert _C.sizeof(Hit) == 96 and HIT_DTYPE.itemsize == 96, "lg_hit is 96 bytes"
+HIT_NONE, HIT_SPHERE, HIT_BOX, HIT_TRIANGLE = 0, 1, 2, 3  # lg_hit::kind
 
 
 class TuneEntry(_C.Structure):  # lg_tune_entry (include/lasgun_hip.h)
@@ -415,6 +434,74 @@ class HipApi(Api):
         if self.call("probe_rate", {"hbm_copy": 0, "lds_read": 1}[what], _C.byref(v)):
             raise LasgunError(self.last_error())
         return v.value
+
+    # ---- ray queries (include/lasgun_hip.h, lg_intersect*): the caller's own rays through the render's walk, in the accel's traversal mode
+    @staticmethod
+    def _rays(rays):
+        r = _np.ascontiguousarray(rays, dtype=_np.float64)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("rays: an (n, 6) array of origin xyz, direction xyz")
+        return r
+
+    def intersect(self, accel, rays):
+        """Closest hit of every ray of an (n, 6) float64 array (origin, direction): a structured array of HIT_DTYPE (lg_hit)."""
+        r = self._rays(rays)
+        hits = _np.zeros(r.shape[0], dtype=HIT_DTYPE)
+        if self.call("intersect", accel.h, r.ctypes.data, r.shape[0], hits.ctypes.data):
+            raise LasgunError(self.last_error())
+        return hits
+
+    def occluded(self, accel, rays):
+        """Whether each segment o -> o + d of an (n, 6) float64 array is blocked (closest hit t < 1, point.rs:49): a bool array."""
+        r = self._rays(rays)
+        occ = _np.zeros(r.shape[0], dtype=_np.uint8)
+        if self.call("occluded", accel.h, r.ctypes.data, r.shape[0], occ.ctypes.data):
+            raise LasgunError(self.last_error())
+        return occ.astype(bool)
+
+    def intersect_device(self, accel, n, rays_ptr, hits_ptr, stream=None):
+        """Enqueue the closest hits of n rays (device memory, 6 doubles each) into n lg_hit records at hits_ptr (16-byte aligned)."""
+        if self.call("intersect_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(hits_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def occluded_device(self, accel, n, rays_ptr, occluded_ptr, stream=None):
+        """Enqueue the occlusion bytes (1 = blocked) of n segments (device memory, 6 doubles each) into occluded_ptr."""
+        if self.call("occluded_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(occluded_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def camera_rays(self, accel, w, h, x0=0, y0=0, x1=None, y1=None):
+        """The rays a capture traces for the pixels [x0,x1) x [y0,y1) of a w x h film: ((y1-y0) * (x1-x0) * samples, 6) float64,
+        row-major pixels, each pixel's samples in camera.rs order."""
+        x1 = w if x1 is None else x1
+        y1 = h if y1 is None else y1
+        n = max(x1 - x0, 0) * max(y1 - y0, 0) * self.camera_samples(accel)
+        out = _np.zeros((n, 6), dtype=_np.float64)
+        if self.call("camera_rays", accel.h, w, h, x0, y0, x1, y1, out.ctypes.data if n else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def camera_rays_device(self, accel, w, h, x0, y0, x1, y1, rays_ptr, stream=None):
+        if self.call("camera_rays_device", accel.h, w, h, x0, y0, x1, y1, _C.c_void_p(int(rays_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def camera_samples(self, accel):
+        """Rays per pixel of lg_camera_rays (the camera's supersamples)."""
+        return int(self.call("camera_samples", accel.h))
+
+    def accel_material(self, accel, index):
+        """The material behind lg_hit::material: a Material as the caller passed it ({"kind", "p"} of the POD)."""
+        from ._capi import CMaterial
+        m = CMaterial()
+        if self.call("accel_material", accel.h, int(index), _C.byref(m)):
+            raise LasgunError(self.last_error())
+        return {"kind": int(m.kind), "p": tuple(m.p)}
+
+    def accel_instance(self, accel, instance):
+        """(parent, obj_ref) of the accel behind lg_hit::instance: parent -1 for the root, obj_ref -1 for a group."""
+        parent, obj = _C.c_int32(), _C.c_int64()
+        if self.call("accel_instance", accel.h, int(instance), _C.byref(parent), _C.byref(obj)):
+            raise LasgunError(self.last_error())
+        return int(parent.value), int(obj.value)
 
     def accel_info(self, accel):
         out = (_C.c_uint64 * 8)()

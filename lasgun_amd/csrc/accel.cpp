@@ -94,7 +94,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         }
         const size_t extra_lds = (size_t)a->accel_image_n16 * 16;
         size_t lds = (size_t)std::max(a->stack_depth, a->stack_depth_fast1) * 256 * 4 + extra_lds;
-        if (lds > 64 * 1024) { HIP_TRY(mega_set_lds_limit(lds, false)); HIP_TRY(wf_set_lds_limit(lds, false)); HIP_TRY(queue_set_lds_limit(lds, false)); }
+        if (lds > 64 * 1024) { HIP_TRY(mega_set_lds_limit(lds, false)); HIP_TRY(wf_set_lds_limit(lds, false)); HIP_TRY(queue_set_lds_limit(lds, false)); HIP_TRY(query_set_lds_limit(lds, false)); }
         int per_cu = 0, cus = 0;
         HIP_TRY(trace_occupancy(a->stack_depth, false, extra_lds, &per_cu));
         int per_cu_fast = 0;
@@ -190,7 +190,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                 }
                 stage.add(a->lds_image, img);
                 a->lds_image_n16 = (uint32_t)n16;
-                HIP_TRY(mega_set_lds_limit(LDS_MAX, true)); HIP_TRY(wf_set_lds_limit(LDS_MAX, true)); HIP_TRY(queue_set_lds_limit(LDS_MAX, true));
+                HIP_TRY(mega_set_lds_limit(LDS_MAX, true)); HIP_TRY(wf_set_lds_limit(LDS_MAX, true)); HIP_TRY(queue_set_lds_limit(LDS_MAX, true)); HIP_TRY(query_set_lds_limit(LDS_MAX, true));
                 a->ldss_blocks = (uint32_t)cus;
             }
             stage.add(a->accels, fm.accels); // with the compact bases
@@ -208,6 +208,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                 stage.add(a->accel_image, img);
             }
         }
+        stage.add(a->accel_tri_base, f.accel_tri_base); // (ray queries: k_query.hip)
         stage.commit(a->arena);
         // Which organisation is the default (measured, tools/threshold_sweep.py): the megakernel unless the scene has
         // so many spheres / boxes that BVH-node and sphere tests dominate a ray (>= 512: with the scene tables in LDS
@@ -260,7 +261,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.cuboids, y.cuboids); swap(x.cuboid_mat, y.cuboid_mat); swap(x.tri_v, y.tri_v); swap(x.tri_n, y.tri_n); swap(x.tri_t, y.tri_t);
     swap(x.vpos, y.vpos); swap(x.vnorm, y.vnorm); swap(x.vtex, y.vtex); swap(x.leaf_soup, y.leaf_soup); swap(x.chunks, y.chunks); swap(x.strips, y.strips);
     swap(x.sphere_ref_leaf, y.sphere_ref_leaf); swap(x.cuboid_ref_leaf, y.cuboid_ref_leaf); swap(x.tri_ref_leaf, y.tri_ref_leaf); swap(x.accel_ref_leaf, y.accel_ref_leaf);
-    swap(x.accels, y.accels); swap(x.materials, y.materials); swap(x.lights, y.lights);
+    swap(x.accels, y.accels); swap(x.materials, y.materials); swap(x.lights, y.lights); swap(x.accel_tri_base, y.accel_tri_base);
     swap(x.lds_image, y.lds_image); swap(x.accel_image, y.accel_image); swap(x.accel_image_n16, y.accel_image_n16);
     swap(x.lds_image_n16, y.lds_image_n16); swap(x.lds_node_off, y.lds_node_off); swap(x.lds_prim_off, y.lds_prim_off);
     swap(x.lds_soup_off, y.lds_soup_off); swap(x.lds_accel_off, y.lds_accel_off);

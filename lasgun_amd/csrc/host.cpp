@@ -589,6 +589,7 @@ struct Flattener {
         d.kind = m.kind;
         std::memcpy(d.p, m.p, sizeof d.p);
         out.materials.push_back(d);
+        out.material_pods.push_back(m);
         if (m.kind == MAT_GLASS || m.kind == MAT_MIRROR) out.has_specular = true;
         return (int32_t)out.materials.size() - 1;
     }
@@ -938,6 +939,8 @@ struct Flattener {
         set_chain(a, parent, id);
         prune_constants(mt.root_bounds, mt.cmax, 0.0, false, a.prune);
         out.accels[id] = a;
+        out.accel_tri_base.resize(out.accels.size(), 0u); out.accel_obj.resize(out.accels.size(), -1);
+        out.accel_tri_base[id] = mt.tri_base; out.accel_obj[id] = (int64_t)mesh;
         dump(mt.bvh, has_mat, false, idt);
         bound = b_transform(idt.m, mt.root_bounds);
         need = mt.max_stack;
@@ -1457,6 +1460,8 @@ void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with
     out.cuboid_ref_leaf.resize(out.cuboids.size(), NO_HIT);
     out.tri_ref_leaf.resize(out.tri_v.size() / 3, NO_HIT);
     out.accel_ref_leaf.resize(out.accels.size(), NO_HIT);
+    out.accel_tri_base.resize(out.accels.size(), 0u);
+    out.accel_obj.resize(out.accels.size(), -1);
     for (const Light &l : scene.lights) {
         DLight d;
         std::memcpy(d.pos, l.pos, sizeof d.pos);

@@ -127,6 +127,11 @@ struct FlatScene {
     std::vector<DMaterial> materials;
     std::vector<DLight> lights;
     int32_t default_material = 0;
+    // ray queries (query.cpp), host side only: the caller's Material behind every material-table index (lg_accel_material), and
+    // per accel its mesh's first triangle in tri_v / 3 (0 for a group) and the mesh's ObjRef (-1 for a group)
+    std::vector<Material> material_pods;
+    std::vector<uint32_t> accel_tri_base;
+    std::vector<int64_t> accel_obj;
     uint32_t max_stack = 0;      // worst-case per-lane traversal stack entries
     uint32_t max_stack_fast1 = 0; // the fast trees under the wide walk (one word per pending child, 3-word level frames)
     bool has_specular = false;   // any glass / mirror material present

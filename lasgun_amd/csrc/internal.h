@@ -34,6 +34,12 @@ hipError_t trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, in
 hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_wf_shade(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_combine(const DParams &P, uint32_t blocks, hipStream_t stream);
+// k_query.hip: ray queries (query.cpp) -- hits != nullptr: closest hit into lg_hit[n]; occluded != nullptr: the any-hit walk, one byte per ray
+hipError_t launch_query(const DParams &P, const double *rays, unsigned long long n, void *hits, uint8_t *occluded, const uint32_t *tri_base,
+                        bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long n, uint32_t blocks, hipStream_t stream);
+hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
+hipError_t query_set_lds_limit(size_t bytes, bool ldss);
 hipError_t launch_wf_resolve(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
@@ -327,6 +333,7 @@ struct lg_accel {
     DevBuf<DAccel> accels;
     DevBuf<DMaterial> materials;
     DevBuf<DLight> lights;
+    DevBuf<uint32_t> accel_tri_base; // ray queries only (k_query.hip): per accel, its mesh's first triangle (FlatScene::accel_tri_base)
     // launch resources (mutable: a `const lg_accel*` render call still enqueues work).  Everything a launch
     // scribbles on lives in a per-STREAM context, so launches of one accel on different streams (frame k+1's
     // primary pass filling the tail of frame k's shadow pass) do not share tile counters or per-pixel state.
@@ -425,6 +432,7 @@ constexpr unsigned MAX_WF_BANDS = 4; // bands of a big wavefront launch on inter
 constexpr size_t PRUNE_MIN_TRIS = 4096; // the pruned walk is the default from this many triangles in a mesh (accel.cpp; profiles/r05_prune_threshold.jsonl)
 
 // ---- launch.cpp: one render enqueued (callers hold a.mtx and have made the accel's device current)
+lg_accel::LaunchCtx &ctx_for(const lg_accel &a, hipStream_t stream);
 void check_queue_error(const lg_accel &a);
 void sync_checked(const lg_accel &a);
 DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);

@@ -5,7 +5,7 @@
 
 // The launch context of `stream` (at most MAX_LAUNCH_CTXS are kept; the least recently used one is recycled after a
 // device-wide synchronise).  Caller holds a.mtx and has made the accel's device current.
-static lg_accel::LaunchCtx &ctx_for(const lg_accel &a, hipStream_t stream) {
+lg_accel::LaunchCtx &ctx_for(const lg_accel &a, hipStream_t stream) {
     for (auto &c : a.ctxs)
         if (c->key == stream) { c->last_use = ++a.ctx_clock; return *c; }
     lg_accel::LaunchCtx *c = nullptr;

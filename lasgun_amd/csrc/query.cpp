@@ -1,0 +1,173 @@
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_camera_rays*, lg_accel_material,
+// lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like the render's
+// level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode.
+#include <cstddef>
+
+#include "internal.h"
+
+static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hit, ng) == 32 && offsetof(lg_hit, ns) == 56 &&
+                  offsetof(lg_hit, kind) == 80 && offsetof(lg_hit, prim) == 84 && offsetof(lg_hit, instance) == 88 && offsetof(lg_hit, material) == 92,
+              "lg_hit: the layout k_query.hip writes (six 16-byte stores per hit)");
+static_assert(sizeof(lg_material) == sizeof(Material), "lg_material wraps Material");
+
+static constexpr unsigned long long MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits
+
+// A caller's device buffer: not NULL, aligned, device memory of the accel's device, and `bytes` long within its allocation -- checked
+// before anything is enqueued (a pageable host pointer or another device's memory would fault the card, not fail the call).
+static void check_device_buffer(const lg_accel &a, const void *p, size_t bytes, size_t align, const char *what) {
+    if (!p) throw Error(std::string(what) + " is NULL");
+    if ((uintptr_t)p % align) throw Error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        throw Error(std::string(what) + " is not device memory (hipPointerGetAttributes)");
+    }
+    if (at.type != hipMemoryTypeDevice) throw Error(std::string(what) + " is not device memory (hipPointerGetAttributes)");
+    if (at.device != a.device) throw Error(std::string(what) + " lives on device " + std::to_string(at.device) + ", the accel on device " + std::to_string(a.device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess) {
+        if ((const char *)p + bytes > (const char *)base + size) throw Error(std::string(what) + " ends beyond its allocation");
+    } else (void)hipGetLastError();
+}
+
+// One query enqueued on `stream` (caller holds a.mtx and has made the accel's device current): hits != nullptr for closest hits,
+// occluded != nullptr for the any-hit walk
+static void enqueue_query(const lg_accel &a, const double *rays, size_t n, lg_hit *hits, uint8_t *occluded, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    if (ldss) {
+        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
+        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+    }
+    P.ntiles = (uint32_t)((n + 63) / 64);
+    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
+    uint32_t cap = a.ldss_blocks;
+    if (!ldss) {
+        int per_cu = 0;
+        HIP_TRY(query_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
+        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
+    }
+    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
+    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    P.tile_counter = c.tile_counter.p;
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(launch_query(P, rays, n, hits, occluded, a.accel_tri_base.p, a.fast, blocks, depth, stream));
+}
+
+// Both host forms: copy the rays in, enqueue on the accel's stream, copy the results out, synchronise (as lg_capture_pixels)
+static int query_host(const lg_accel *a, const double *rays, size_t n, void *out, bool any) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (!rays) throw Error("rays is NULL");
+        if (!out) throw Error(any ? "occluded is NULL" : "hits is NULL");
+        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        const size_t out_bytes = n * (any ? 1u : sizeof(lg_hit));
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        DevBuf<double> drays;
+        DevBuf<uint8_t> dout;
+        drays.alloc(n * 6);
+        dout.alloc(out_bytes);
+        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_query(*a, drays.p, n, any ? nullptr : reinterpret_cast<lg_hit *>(dout.p), any ? dout.p : nullptr, a->stream);
+        HIP_TRY(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+    });
+}
+static int query_device(const lg_accel *a, const double *dev_rays, size_t n, void *dev_out, bool any, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        check_device_buffer(*a, dev_out, n * (any ? 1u : sizeof(lg_hit)), any ? 1 : 16, any ? "occluded" : "hits");
+        enqueue_query(*a, dev_rays, n, any ? nullptr : reinterpret_cast<lg_hit *>(dev_out), any ? reinterpret_cast<uint8_t *>(dev_out) : nullptr,
+                      (hipStream_t)hip_stream);
+    });
+}
+
+// the rectangle's rays: (x1-x0) * (y1-y0) * supersamples; 0 for an empty rectangle
+static unsigned long long camera_ray_count(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
+    if (w == 0 || h == 0 || x0 > x1 || y0 > y1 || x1 > w || y1 > h) throw Error("rectangle outside the film");
+    const unsigned long long S = (unsigned long long)a.scene->camera.ss_root * a.scene->camera.ss_root;
+    return (unsigned long long)(x1 - x0) * (y1 - y0) * S;
+}
+static void enqueue_camera_rays(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays,
+                                unsigned long long n, hipStream_t stream) {
+    DParams P = base_params(a, w, h);
+    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
+    const uint32_t blocks = (uint32_t)std::min<unsigned long long>((n + 255) / 256, (unsigned long long)a.cus * 64ull);
+    HIP_TRY(launch_camera_rays(P, rays, n, blocks, stream));
+}
+
+extern "C" {
+
+int lg_intersect(const lg_accel *a, const double *rays, size_t n, lg_hit *hits) { return query_host(a, rays, n, hits, false); }
+int lg_occluded(const lg_accel *a, const double *rays, size_t n, uint8_t *occluded) { return query_host(a, rays, n, occluded, true); }
+int lg_intersect_device(const lg_accel *a, const double *dev_rays, size_t n, lg_hit *dev_hits, void *hip_stream) {
+    return query_device(a, dev_rays, n, dev_hits, false, hip_stream);
+}
+int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream) {
+    return query_device(a, dev_rays, n, dev_occluded, true, hip_stream);
+}
+
+int lg_camera_rays(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        const unsigned long long n = camera_ray_count(*a, w, h, x0, y0, x1, y1);
+        if (n == 0) return;
+        if (!rays) throw Error("rays is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        DevBuf<double> d;
+        d.alloc(n * 6);
+        enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, d.p, n, a->stream);
+        HIP_TRY(hipMemcpyAsync(rays, d.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+    });
+}
+int lg_camera_rays_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *dev_rays, void *hip_stream) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        const unsigned long long n = camera_ray_count(*a, w, h, x0, y0, x1, y1);
+        if (n == 0) return;
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, dev_rays, n, (hipStream_t)hip_stream);
+    });
+}
+
+uint32_t lg_camera_samples(const lg_accel *a) {
+    if (!a) return 0u;
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->scene->camera.ss_root * a->scene->camera.ss_root;
+}
+
+int lg_accel_material(const lg_accel *a, int32_t index, lg_material *out) {
+    return guarded([&] {
+        if (!a || !out) throw Error("accel / out is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        const std::vector<Material> &m = a->flat.material_pods;
+        if (index < 0 || (size_t)index >= m.size()) throw Error("material index " + std::to_string(index) + " outside 0 .. " + std::to_string(m.size()));
+        std::memcpy(out, &m[(size_t)index], sizeof *out);
+    });
+}
+int lg_accel_instance(const lg_accel *a, uint32_t instance, int32_t *parent, int64_t *obj_ref) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        const FlatScene &f = a->flat;
+        if ((size_t)instance >= f.accels.size()) throw Error("instance " + std::to_string(instance) + " outside 0 .. " + std::to_string(f.accels.size()));
+        if (parent) *parent = f.accels[instance].parent;
+        if (obj_ref) *obj_ref = f.accel_obj[instance];
+    });
+}
+
+} // extern "C"

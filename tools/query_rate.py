@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""Ray-query throughput (include/lasgun_hip.h, lg_intersect_device / lg_occluded_device) on three scenes: the headline (configs[2], 1024
+spheres, LDS-resident), config 4 (the glass torus mesh, pruned walk) and config 5 (mixed).  Per scene three rows:
+  (a) closest hits of the camera's 4096^2 primary rays (lg_camera_rays_device),
+  (b) the same rays in a seeded random order (incoherent),
+  (c) occlusion of the shadow segments to light 0 from (a)'s hits (the render's shadow origin: p + ng * 2^-36),
+and, as diagnostics, (a) and (c) with the rays in the render's own order (8 x 8 pixel tiles, rows a8 / c8).
+Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--out profiles/r07_query.jsonl]
+       python tools/query_rate.py --once     (one headline frame rendered, then (a) and (c) once: for rocprofv3 --kernel-trace --stats)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import torch  # noqa: E402
+
+import lasgun_amd as la  # noqa: E402
+import pyref  # noqa: E402  (the scenes' light positions, built through the same scene functions)
+from lasgun_amd import scenes as S  # noqa: E402
+
+G = la.api
+SCENES = [("configs[2] spheres (LDS-resident)", lambda api: S.spheres_scene(api)),
+          ("config 4 glass torus (pruned walk)", lambda api: S.mesh_scene(api)),
+          ("config 5 mixed", lambda api: S.mixed_scene(api))]
+ERR = 2.220446049250313e-16 * 65536.0  # the shading offset (integrate.rs:40)
+
+
+def timed(fn, calls, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def shadow_segments(hits, light):
+    """(c)'s rays from (a)'s hits: origin p + ng * 2^-36 (what the shadow passes leave from, point.rs:43-44), direction light - origin."""
+    f = hits.view(torch.float64).view(-1, 12)
+    kind = hits.view(torch.int32).view(-1, 24)[:, 20]
+    f = f[kind != 0]
+    o = f[:, 1:4] + f[:, 4:7] * ERR
+    d = torch.tensor(light, dtype=torch.float64, device=o.device) - o
+    return torch.cat([o, d], dim=1).contiguous()
+
+
+def measure(name, builder, size, calls, seed):
+    scene = builder(G)
+    accel = G.Accel.from_scene(scene)
+    light = builder(pyref.Api).lights[0][0]
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    n = size * size * G.camera_samples(accel)
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    shuffled = rays[torch.randperm(n, device="cuda", generator=gen)].contiguous()
+    hits_b = torch.empty_like(hits)
+    rows = []
+    ms = timed(lambda: G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s), calls)
+    rows.append(("a: closest, camera order", n, ms))
+    ms = timed(lambda: G.intersect_device(accel, n, shuffled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
+    rows.append(("b: closest, random order", n, ms))
+    segs = shadow_segments(hits, light)
+    occ = torch.empty((segs.shape[0],), dtype=torch.uint8, device="cuda")
+    ms = timed(lambda: G.occluded_device(accel, segs.shape[0], segs.data_ptr(), occ.data_ptr(), stream=s), calls)
+    rows.append(("c: occluded, shadow segments to light 0", segs.shape[0], ms))
+    # the same rays and segments in the render's own order -- 8 x 8 pixel tiles, a tile per wave -- instead of row-major (diagnostic rows)
+    pix = torch.arange(size * size, device="cuda")
+    key = ((pix // size // 8) * (size // 8) + (pix % size) // 8) * 64 + ((pix // size) % 8) * 8 + (pix % size) % 8
+    order = torch.argsort(key)
+    tiled = rays[order].contiguous() if n == size * size else None
+    if tiled is not None:
+        ms = timed(lambda: G.intersect_device(accel, n, tiled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
+        rows.append(("a8: closest, 8x8 pixel tiles", n, ms))
+        segs8 = shadow_segments(hits.view(-1, 96)[order].contiguous().view(-1), light)
+        ms = timed(lambda: G.occluded_device(accel, segs8.shape[0], segs8.data_ptr(), occ.data_ptr(), stream=s), calls)
+        rows.append(("c8: occluded, shadow segments in 8x8 pixel tiles", segs8.shape[0], ms))
+    out = []
+    for row, nr, ms in rows:
+        out.append({"scene": name, "row": row, "film": [size, size], "rays": int(nr), "ms": round(ms, 4), "mrays_per_s": round(nr / ms / 1e3, 1),
+                    "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel),
+                    "occluded_fraction": round(float(occ.float().mean()), 4) if row == rows[2][0] else None,
+                    "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)})
+    return out
+
+
+def once(size):
+    """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
+    scene = S.spheres_scene(G)
+    accel = G.Accel.from_scene(scene)
+    s = torch.cuda.current_stream().cuda_stream
+    film = torch.empty((size * size * 4,), dtype=torch.uint8, device="cuda")
+    G.capture_rows_device(accel, size, size, 0, size, film.data_ptr(), stream=s)
+    n = size * size
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s)
+    segs = shadow_segments(hits, S.spheres_scene(pyref.Api).lights[0][0])
+    occ = torch.empty((segs.shape[0],), dtype=torch.uint8, device="cuda")
+    G.occluded_device(accel, segs.shape[0], segs.data_ptr(), occ.data_ptr(), stream=s)
+    torch.cuda.synchronize()
+    print(json.dumps({"once": True, "rays": n, "shadow_segments": int(segs.shape[0])}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--once", action="store_true")
+    args = ap.parse_args()
+    G.set_device(0)
+    if args.once:
+        once(args.size)
+        return
+    t0 = time.time()
+    rows = []
+    for name, builder in SCENES:
+        for r in measure(name, builder, args.size, max(args.calls, 20), args.seed):
+            print(json.dumps(r), flush=True)
+            rows.append(r)
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    print("# %.1f s" % (time.time() - t0), file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
