@@ -231,6 +231,7 @@ struct DParams {
     double image_plane_height, pixel_separation, ss_distance;
     uint32_t ss_root;
     uint32_t boxes_finite; // every node box of the scene is finite: the walk may take the sign-specialised slab test (walk.h, slab_intersects_sg)
+    double ah_omax, ah_dmin, ah_dmax; // any-hit early exit range of world rays (host.h FlatScene, walk.h anyhit_exit_ok)
     V3 bg_inner, bg_outer;
     double bg_scale;
     V3 ambient;

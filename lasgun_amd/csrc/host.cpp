@@ -1425,6 +1425,59 @@ static void build_chunks(FlatScene &out) {
     out.strips.resize(out.strips.size() + 2, DStrip{0.f, 0.f, 0.f, 0u}); // two spare entries: the leaf loop keeps the next entry in flight
 }
 
+// The any-hit walk's early exit (walk.h, anyhit_exit_ok).  The reference's shadow test is the closest hit's `t < 1` (point.rs:49), and
+// a hit is accepted when !(t < 0) and !(t >= isect.t) (sphere.rs:83-86, cuboid.rs:95, triangle.rs:251): a NaN t is always accepted and
+// then lets any later t in.  Stopping at the first t < 1 is exact only when no intersector the rest of the walk calls can return NaN.
+// That holds at a level whose local ray has |o_i| <= 2^199 and max |d_i| in [2^-199, 2^199] and whose geometry has |coordinates| <=
+// 2^199: a sphere's a = d.d >= 2^-398 is a normal number, b, c, b*b and 4*a*c stay below 2^820, so the discriminant, its root and
+// both quotients are finite or +-inf, never NaN; a triangle's dominant |d_kz| >= 2^-199 keeps the shear <= 1 and 1/d_kz <= 2^199, its
+// edge functions and scaled t below 2^820, and t = tscaled / det is finite or +-inf (tscaled != 0 has det's sign); a box's slab
+// parameters meet 0 * inf only on an axis with d_i = 0, which fmin / fmax absorb, and the dominant axis is finite.  Each level's ray is
+// its parent's through minv = (A, b): |o'| <= |A| |o| + |b| and |d'| <= |A| |d| (infinity norms, rounding inside the 2^-30 slack per
+// level), and max |d'| >= max |d| / (4 |A^-1|) when |A| |A^-1| <= 2^40 (the computed product's error is below half its value).  The
+// world range is the intersection over all levels; node boxes bound every level's geometry in its own coordinates.
+static void anyhit_range(FlatScene &out) {
+    const double B = 0x1p199, SLACK = 1.0 + 0x1p-30;
+    double cmax = 0.0;
+    for (const DNode &nd : out.nodes)
+        for (int k = 0; k < 3; ++k) cmax = std::fmax(cmax, std::fmax(std::fabs(nd.bmin[k]), std::fabs(nd.bmax[k])));
+    bool ok = out.boxes_finite && cmax <= B;
+    const size_t n = out.accels.size();
+    std::vector<double> N(n, 1.0), T(n, 0.0), K(n, 1.0);
+    double omax = INFINITY, dmax = INFINITY, dmin = 0.0;
+    for (size_t id = 0; id < n && ok; ++id) { // (a parent's id is below its children's: pre-order)
+        const Affine &m = out.accels[id].minv;
+        double a[3][3], nA = 0.0, nb = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            double row = 0.0;
+            for (int c = 0; c < 3; ++c) { a[r][c] = m.c[c][r]; row += std::fabs(a[r][c]); }
+            nA = std::fmax(nA, row);
+            nb = std::fmax(nb, std::fabs(m.c[3][r]));
+        }
+        const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                           a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+        const double adj[3][3] = {{a[1][1] * a[2][2] - a[1][2] * a[2][1], a[0][2] * a[2][1] - a[0][1] * a[2][2], a[0][1] * a[1][2] - a[0][2] * a[1][1]},
+                                  {a[1][2] * a[2][0] - a[1][0] * a[2][2], a[0][0] * a[2][2] - a[0][2] * a[2][0], a[0][2] * a[1][0] - a[0][0] * a[1][2]},
+                                  {a[1][0] * a[2][1] - a[1][1] * a[2][0], a[0][1] * a[2][0] - a[0][0] * a[2][1], a[0][0] * a[1][1] - a[0][1] * a[1][0]}};
+        double nI = 0.0;
+        for (int r = 0; r < 3; ++r) nI = std::fmax(nI, (std::fabs(adj[r][0]) + std::fabs(adj[r][1]) + std::fabs(adj[r][2])) / std::fabs(det));
+        ok = std::isfinite(nA) && std::isfinite(nb) && std::isfinite(nI) && nI > 0.0 && nA * nI <= 0x1p40;
+        const int32_t p = out.accels[id].parent;
+        const double pN = p < 0 ? 1.0 : N[p], pT = p < 0 ? 0.0 : T[p], pK = p < 0 ? 1.0 : K[p];
+        N[id] = pN * nA * SLACK;
+        T[id] = (nA * pT + nb) * SLACK;
+        K[id] = pK * 4.0 * nI;
+        ok = ok && std::isfinite(N[id]) && T[id] <= 0.5 * B && std::isfinite(K[id]);
+        omax = std::fmin(omax, 0.5 * B / N[id]);
+        dmax = std::fmin(dmax, B / N[id]);
+        dmin = std::fmax(dmin, K[id] / B);
+    }
+    ok = ok && n > 0 && dmin <= dmax && omax > 0.0;
+    out.ah_omax = ok ? omax : -1.0;
+    out.ah_dmin = ok ? dmin : INFINITY;
+    out.ah_dmax = ok ? dmax : 0.0;
+}
+
 void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with_records) {
     out = FlatScene();
     Flattener fl{scene, out, {}, with_fast};
@@ -1456,6 +1509,7 @@ void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with
     for (const DNode &nd : out.nodes)
         for (int k = 0; k < 3; ++k) // finite AND ordered: slab_intersects_sg takes the near / far plane from the ray's sign, which is the reference's min / max only for bmin <= bmax
             out.boxes_finite = out.boxes_finite && std::isfinite(nd.bmin[k]) && std::isfinite(nd.bmax[k]) && nd.bmin[k] <= nd.bmax[k];
+    anyhit_range(out);
     out.sphere_ref_leaf.resize(out.spheres.size(), NO_HIT);
     out.cuboid_ref_leaf.resize(out.cuboids.size(), NO_HIT);
     out.tri_ref_leaf.resize(out.tri_v.size() / 3, NO_HIT);

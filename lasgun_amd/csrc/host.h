@@ -138,6 +138,10 @@ struct FlatScene {
     bool has_fast = false;       // the fast mode's trees are part of the tables
     bool has_records = false;    // the mesh leaves' culling records and strips are part of the tables (or there is no mesh)
     bool boxes_finite = false;   // every node box is finite with bmin <= bmax on every axis (DParams::boxes_finite: the sign-specialised slab test is exact then)
+    // World rays with |o_i| <= ah_omax and every |d_i| in [.., ah_dmax], max |d_i| >= ah_dmin, reach every level of the scene in the
+    // range where no intersector can return t = NaN (host.cpp, anyhit_range): the any-hit walk may stop at its first t < 1 only for
+    // them.  An empty range (ah_omax = -1) when the scene's magnitudes or transforms allow no such statement.
+    double ah_omax = -1.0, ah_dmin = INFINITY, ah_dmax = 0.0;
     // structure dump in the same format as the oracle's orc_accel_dump (build-parity tests)
     std::vector<double> dump_f;
     std::vector<int64_t> dump_i;

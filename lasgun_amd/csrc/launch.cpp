@@ -71,6 +71,7 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
         static const bool signs = [] { const char *e = std::getenv("LASGUN_SLAB_SIGNS"); return !(e && e[0] == '0'); }();
         P.boxes_finite = a.flat.boxes_finite && signs ? 1u : 0u;
     }
+    P.ah_omax = a.flat.ah_omax; P.ah_dmin = a.flat.ah_dmin; P.ah_dmax = a.flat.ah_dmax;
     P.bg_inner = s.bg_inner; P.bg_outer = s.bg_outer; P.bg_scale = s.bg_scale;
     P.ambient = s.ambient;
     P.w = w; P.h = h;

@@ -97,8 +97,11 @@ LG_HD V3 xf_vector(const Affine &m, V3 v) {
               ((m.c[0][1] * v.x + m.c[1][1] * v.y) + m.c[2][1] * v.z) + m.c[3][1] * 0.0,
               ((m.c[0][2] * v.x + m.c[1][2] * v.y) + m.c[2][2] * v.z) + m.c[3][2] * 0.0};
 }
-// Matrix4 * (p, 1), w == 1.
+// Point3::from_homogeneous(Matrix4 * (p, 1)) with the bottom row (0, 0, 0, 1) the host checks: w = ((0*x + 0*y) + 0*z) + 1 is
+// exactly 1 for a finite p (and the division by it exact), and NaN when a component of p is infinite or NaN (0 * inf) -- every
+// component of the reference's point is then NaN.
 LG_HD V3 xf_point(const Affine &m, V3 p) {
+    if (!(__builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z))) return V3{NAN, NAN, NAN};
     return V3{((m.c[0][0] * p.x + m.c[1][0] * p.y) + m.c[2][0] * p.z) + m.c[3][0] * 1.0,
               ((m.c[0][1] * p.x + m.c[1][1] * p.y) + m.c[2][1] * p.z) + m.c[3][1] * 1.0,
               ((m.c[0][2] * p.x + m.c[1][2] * p.y) + m.c[2][2] * p.z) + m.c[3][2] * 1.0};

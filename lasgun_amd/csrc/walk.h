@@ -36,7 +36,8 @@
 //     WINNING primitive are computed once afterwards (the reference overwrites them on every
 //     closer hit, so only the last accepted ones survive: sphere.rs:120, bvh.rs:510);
 //   * shadow rays stop at the first accepted hit with t < 1 (point.rs:49 only tests isect.t < 1.0
-//     and t only ever decreases);
+//     and t only ever decreases) when no intersector can return t = NaN for them (anyhit_exit_ok: a NaN t is always
+//     accepted and can still win); other shadow rays walk to the end;
 //   * a lane's visit order is exactly the reference's (near child first by dir_is_neg[axis],
 //     leaf primitives in order[]), which is what breaks ties between equal t.
 #pragma once
@@ -574,6 +575,13 @@ __device__ __forceinline__ double prune_limit(double tbest, bool anyhit) {
 enum : uint32_t { ST_NODE = 0u, ST_LEAF = 1u, ST_LEVEL_DONE = 2u, ST_DONE = 3u, ST_ENTER = 4u };
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 // finite and not -0: not one of sNaN, qNaN, -inf, -0, +inf (v_cmp_class_f64)
+// May the any-hit walk of this world ray stop at its first accepted t < 1?  Yes inside the host's stated range (host.cpp, anyhit_range),
+// where no later intersector can return t = NaN and isect.t therefore only decreases.  (A NaN component fails every comparison.)
+__device__ __forceinline__ bool anyhit_exit_ok(const DParams &P, const Ray &r) {
+    const double ax = fabs(r.d.x), ay = fabs(r.d.y), az = fabs(r.d.z);
+    return fabs(r.o.x) <= P.ah_omax && fabs(r.o.y) <= P.ah_omax && fabs(r.o.z) <= P.ah_omax && ax <= P.ah_dmax && ay <= P.ah_dmax &&
+           az <= P.ah_dmax && (ax >= P.ah_dmin || ay >= P.ah_dmin || az >= P.ah_dmin);
+}
 __device__ __forceinline__ bool f64_plain(double x) { return !__builtin_amdgcn_class(x, 0x001 | 0x002 | 0x004 | 0x020 | 0x200); }
 __device__ __forceinline__ bool ray_plain(const Ray &r) {
     return f64_plain(r.o.x) && f64_plain(r.o.y) && f64_plain(r.o.z) && f64_plain(r.d.x) && f64_plain(r.d.y) && f64_plain(r.d.z);
@@ -837,8 +845,8 @@ __device__ __noinline__ void audit_run(const DParams &P, uint32_t e0, uint32_t e
 
 template <int KZ, bool LDSS, bool FAST = false, bool COUNT = false, bool PRUNE = false>
 __device__ __forceinline__ bool mesh_leaf2(const DParams &P, const uint4 *scn, const Ray &ray, const TriSetup tri, uint32_t li, const uint32_t le,
-                                           const uint32_t soup_delta, const uint32_t accel, const bool anyhit, Best &best, bool &tie, Counters &cnt,
-                                           LeafCull lc) {
+                                           const uint32_t soup_delta, const uint32_t accel, const bool anyhit, const bool early, Best &best, bool &tie,
+                                           Counters &cnt, LeafCull lc) {
     const V3 o = ray.o;
     const char *base = reinterpret_cast<const char *>(P.leaf_soup);
     constexpr uint32_t REC = (uint32_t)sizeof(DLeafRec);
@@ -851,11 +859,12 @@ __device__ __forceinline__ bool mesh_leaf2(const DParams &P, const uint4 *scn, c
             if (!(h_.t >= best.t)) {                                                                                     \
                 best.t = h_.t; best.ref = load_primref<LDSS>(P, scn, (SLOT)); best.accel = accel;                        \
                 if (COUNT) dbg_event(P, 6.0, (double)best.ref, h_.t, (double)accel);                                     \
-                if (anyhit && h_.t < 1.0) return true; /* point.rs:49 */                                                 \
+                if (early && h_.t < 1.0) return true; /* point.rs:49 */                                                  \
             }                                                                                                            \
         }                                                                                                                \
     } while (0)
-    if (PRUNE && lc.ekz < INFINITY && (lc.records >> 24) != 0u) { // (a level or ray outside the stated ranges, or a leaf the host gave no records: the plain loop below, in the reference's order)
+    if (PRUNE && lc.ekz < INFINITY && (lc.records >> 24) != 0u && best.t == best.t) { // (a level or ray outside the stated ranges, a leaf the host gave no records, or a NaN best from another level, which every t
+        // replaces: the plain loop below, in the reference's order)
         // The leaf in runs of <= 32 triangles that are neighbours in space (one culling record per run; host.cpp, build_chunks): a run
         // whose record is culled is stepped over.  The reference scans the leaf in order[] sequence and keeps the FIRST of several
         // triangles with exactly the same t (triangle.rs:251: `t >= isect.t` rejects); scanning in another order gives the same
@@ -890,7 +899,7 @@ __device__ __forceinline__ bool mesh_leaf2(const DParams &P, const uint4 *scn, c
                 leaf_slot = from_;                                                                                       \
                 if (!anyhit) lc.lb = h_.t + h_.t * PRUNE_LIMIT_REL;                                                      \
                 if (COUNT) dbg_event(P, 6.0, (double)best.ref, h_.t, (double)accel);                                     \
-                if (anyhit && h_.t < 1.0) done = true; /* point.rs:49 */                                                 \
+                if (early && h_.t < 1.0) done = true; /* point.rs:49 */                                                  \
             }                                                                                                            \
         }                                                                                                                \
     } while (0)
@@ -1061,6 +1070,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
     TriSetup tri;                                  // FAST: per mesh level (its leaves hold one triangle: per leaf the three divides would dominate)
     tri.kz = 0; tri.sx = 0.0; tri.sy = 0.0; tri.sz = 0.0;
     // ---- the root accel's local ray (bvh.rs:462), kept for the returns
+    bool early = anyhit && anyhit_exit_ok(P, wray); // may stop at the first t < 1
     Ray root = wray;
     if (!((L.flags & AF_IDENTITY) && ray_plain(wray))) root = accel_local_ray<LDSS>(P, arec, 0u, wray);
     Ray ray = root;
@@ -1236,9 +1246,9 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                 lc.dhx = (float)ray.d.x * inv_len; lc.dhy = (float)ray.d.y * inv_len; lc.dhz = (float)ray.d.z * inv_len;
 #endif
             }
-            if (tri.kz == 0) done = mesh_leaf2<0, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
-            else if (tri.kz == 1) done = mesh_leaf2<1, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
-            else done = mesh_leaf2<2, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
+            if (tri.kz == 0) done = mesh_leaf2<0, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
+            else if (tri.kz == 1) done = mesh_leaf2<1, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
+            else done = mesh_leaf2<2, LDSS, FAST, COUNT, PRUNE>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
             if (FAST) limit = prune_limit(best.t, anyhit);
             if (PRUNE && !anyhit) prune_limits(best.t);
             if (done) state = ST_DONE;
@@ -1307,7 +1317,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                     best.t = t; best.ref = ref; best.accel = L.accel;
                     if (FAST) limit = prune_limit(t, anyhit);
                     if (PRUNE && !anyhit) prune_limits(t);
-                    if (anyhit && t < 1.0) state = ST_DONE; // occluded: point.rs:49 only asks isect.t < 1.0
+                    if (early && t < 1.0) state = ST_DONE; // occluded: point.rs:49 only asks isect.t < 1.0
                 }
                 if (state == ST_LEAF && li >= le) { // leaf exhausted: next pending node of this level, or the level is done
                     if (sp != base) { --sp; cur = popped; state = ST_NODE; }
@@ -1411,6 +1421,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                         best.t = INFINITY; best.ref = NO_HIT; best.accel = 0;
                         lvl_set<LDSS, FAST>(P, arec, L, 0u);
                         root = nw;
+                        early = anyhit && anyhit_exit_ok(P, nw);
                         if (!((L.flags & AF_IDENTITY) && ray_plain(nw))) root = accel_local_ray<LDSS>(P, arec, 0u, nw);
                         ray = root;
                         dd = dot(ray.d, ray.d);
@@ -1472,6 +1483,7 @@ __device__ __forceinline__ void traverse_fast(const DParams &P, const Ray &wray,
     TriSetup tri;                                  // FAST: per mesh level (its leaves hold one triangle: per leaf the three divides would dominate)
     tri.kz = 0; tri.sx = 0.0; tri.sy = 0.0; tri.sz = 0.0;
     // ---- the root accel's local ray (bvh.rs:462), kept for the returns
+    const bool early = anyhit; // (walk() sends every ray outside anyhit_exit_ok's range to the reference walk)
     Ray root = wray;
     if (!((L.flags & AF_IDENTITY) && ray_plain(wray))) root = accel_local_ray<LDSS>(P, scn, 0u, wray);
     Ray ray = root;
@@ -1554,9 +1566,9 @@ __device__ __forceinline__ void traverse_fast(const DParams &P, const Ray &wray,
             if (!FAST) tri = tri_setup(ray); // per fat leaf: amortises the three divides (triangle.rs:186-201)
             bool done;
             const LeafCull lc{INFINITY, INFINITY, dd, 0u, 0.0f, 0.0f, 0.0f};
-            if (tri.kz == 0) done = mesh_leaf2<0, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
-            else if (tri.kz == 1) done = mesh_leaf2<1, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
-            else done = mesh_leaf2<2, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, best, tie, cnt, lc);
+            if (tri.kz == 0) done = mesh_leaf2<0, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
+            else if (tri.kz == 1) done = mesh_leaf2<1, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
+            else done = mesh_leaf2<2, LDSS, FAST, COUNT>(P, scn, ray, tri, li, le, L.soup_delta, L.accel, anyhit, early, best, tie, cnt, lc);
             if (FAST) limit = prune_limit(best.t, anyhit);
             if (done) state = ST_DONE;
             else if (sp != base) { --sp; take(stk[sp * stride]); }
@@ -1619,7 +1631,7 @@ __device__ __forceinline__ void traverse_fast(const DParams &P, const Ray &wray,
                 if (accepted) {
                     best.t = t; best.ref = ref; best.accel = L.accel;
                     if (FAST) limit = prune_limit(t, anyhit);
-                    if (anyhit && t < 1.0) state = ST_DONE; // occluded: point.rs:49 only asks isect.t < 1.0
+                    if (early && t < 1.0) state = ST_DONE; // occluded: point.rs:49 only asks isect.t < 1.0
                 }
                 if (state == ST_LEAF && li >= le) { // leaf exhausted: next pending node of this level, or the level is done
                     if (sp != base) { --sp; take(popped); }
@@ -1693,6 +1705,10 @@ template <bool LDSS, bool FAST, bool PRUNE = false, bool COUNT = false>
 __device__ __forceinline__ void walk(const DParams &P, const Ray &ray, const bool anyhit, uint32_t *stack, const uint32_t stride, Best &best,
                                      const uint4 *scn, Counters &cnt, const uint4 *arec = nullptr) {
     bool tie = false;
+    if (FAST && !anyhit_exit_ok(P, ray)) { // a ray a NaN t could reach: the reference walk (its nodes may not be skipped by t, nor a shadow ray stop early)
+        traverse_ref<false, false, false, COUNT>(P, ray, anyhit, stack, stride, best, nullptr, tie, cnt, arec);
+        return;
+    }
     if (FAST) traverse_fast<COUNT>(P, ray, anyhit, stack, stride, best, scn, tie, cnt);
     else
     traverse_ref<LDSS, FAST, PRUNE, COUNT>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);

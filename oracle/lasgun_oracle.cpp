@@ -23,6 +23,7 @@
 // GPU radiance can be compared bit-for-bit.
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -409,6 +410,9 @@ static thread_local Stats tl_stats;
 
 // ---- src/primitive/mod.rs ---------------------------------------------------
 struct Primitive {
+    // identity in lg_hit's numbering (ray queries only; the walk never reads it): kind 1 sphere / 2 box / 3 triangle, its ordinal
+    // (spheres and boxes in scene-graph order, a triangle's face number) and the accel it sits in (root 0, scene-graph order)
+    uint32_t id_kind = 0, id_prim = 0, id_inst = 0;
     virtual ~Primitive() {}
     virtual Bounds bound() const = 0;
     virtual const Primitive *intersect(const Ray &ray, RayIntersection &isect) const = 0;
@@ -1035,8 +1039,10 @@ struct BVHAccel : Primitive {
 
 static const Transform ID_TRANSFORM = tr_identity();
 
-static std::unique_ptr<BVHAccel> accel_from_mesh(const Scene *scene, uint32_t mesh, bool has_mat, Material mat) { // bvh.rs:141-148
+struct IdCount { uint32_t sphere = 0, box = 0, accel = 0; }; // running ordinals of lg_hit's numbering during one build
+static std::unique_ptr<BVHAccel> accel_from_mesh(const Scene *scene, uint32_t mesh, bool has_mat, Material mat, IdCount &ids) { // bvh.rs:141-148
     if (mesh >= scene->meshes.size()) throw BuildError{"mesh handle out of range (the reference panics, bvh.rs:142)"};
+    const uint32_t me = ids.accel++;
     const Obj *obj = scene->meshes[mesh].get();
     size_t nfaces = obj->tri.size() / 3;
     std::vector<std::unique_ptr<Primitive>> tris;
@@ -1048,6 +1054,7 @@ static std::unique_ptr<BVHAccel> accel_from_mesh(const Scene *scene, uint32_t me
             if (!obj->texture.empty() && tp.t < 0) throw BuildError{"mesh has vt but a face lacks a vt index (the reference panics, triangle.rs:96)"};
         }
         auto *t = new Triangle(); t->obj = obj; t->face = (uint32_t)f;
+        t->id_kind = 3; t->id_prim = (uint32_t)f; t->id_inst = me;
         tris.emplace_back(t);
     }
     std::unique_ptr<BVHAccel> a(new BVHAccel());
@@ -1055,23 +1062,27 @@ static std::unique_ptr<BVHAccel> accel_from_mesh(const Scene *scene, uint32_t me
     a->init(scene, std::move(tris), &ID_TRANSFORM, has_mat, mat, per_node, false);
     return a;
 }
-static std::unique_ptr<BVHAccel> accel_from_aggregate(const Scene *scene, const Aggregate *agg) { // bvh.rs:150-162, 563-572
+static std::unique_ptr<BVHAccel> accel_from_aggregate(const Scene *scene, const Aggregate *agg, IdCount &ids) { // bvh.rs:150-162, 563-572
+    const uint32_t me = ids.accel++;
     std::vector<std::unique_ptr<Primitive>> prims;
     for (const SceneNode &n : agg->contents) {
         switch (n.kind) {
         case SceneNode::SPHERE: {
             auto *s = new Sphere(); s->origin = V3{n.a[0], n.a[1], n.a[2]}; s->radius = n.b[0]; s->mat = n.mat;
+            s->id_kind = 1; s->id_prim = ids.sphere++; s->id_inst = me;
             prims.emplace_back(s); break; }
         case SceneNode::CUBE: { // Cuboid::cube cuboid.rs:24-30
             auto *c = new Cuboid(); V3 o{n.a[0], n.a[1], n.a[2]};
             c->bounds = bounds_new(o, o + V3{n.b[0], n.b[0], n.b[0]}); c->mat = n.mat;
+            c->id_kind = 2; c->id_prim = ids.box++; c->id_inst = me;
             prims.emplace_back(c); break; }
         case SceneNode::CUBOID: {
             auto *c = new Cuboid();
             c->bounds = bounds_new(V3{n.a[0], n.a[1], n.a[2]}, V3{n.b[0], n.b[1], n.b[2]}); c->mat = n.mat;
+            c->id_kind = 2; c->id_prim = ids.box++; c->id_inst = me;
             prims.emplace_back(c); break; }
-        case SceneNode::MESH: prims.emplace_back(accel_from_mesh(scene, n.obj, n.has_mat, n.mat).release()); break;
-        case SceneNode::GROUP: prims.emplace_back(accel_from_aggregate(scene, n.group.get()).release()); break;
+        case SceneNode::MESH: prims.emplace_back(accel_from_mesh(scene, n.obj, n.has_mat, n.mat, ids).release()); break;
+        case SceneNode::GROUP: prims.emplace_back(accel_from_aggregate(scene, n.group.get(), ids).release()); break;
         }
     }
     std::unique_ptr<BVHAccel> a(new BVHAccel());
@@ -1567,7 +1578,8 @@ void *orc_accel_from(const void *s) {
     try {
         Accel *a = new Accel();
         a->scene = (const Scene *)s;
-        a->root = accel_from_aggregate(a->scene, a->scene->root.get());
+        IdCount ids;
+        a->root = accel_from_aggregate(a->scene, a->scene->root.get(), ids);
         return a;
     } catch (const BuildError &e) { tl_error = e.msg; return nullptr; }
 }
@@ -1649,6 +1661,73 @@ int orc_capture_pixels(const void *accel, uint32_t w, uint32_t h, const uint64_t
     for (auto &t : th) t.join();
     return 0;
 }
+// ---- ray queries: what lg_intersect / lg_occluded answer, from the reference's own walk ---------------------------------
+// orc_hit is lg_hit (include/lasgun_hip.h) restated.  The oracle keeps no material table: a hit's `material` is 0 (-1 for a
+// miss) and the POD itself goes to mats[i] when mats is not NULL (zeroed for a miss).
+typedef struct {
+    double t, p[3], ng[3], ns[3];
+    uint32_t kind, prim, instance;
+    int32_t material;
+} orc_hit;
+static_assert(sizeof(orc_hit) == 96, "lg_hit is 96 bytes");
+static_assert(offsetof(orc_hit, p) == 8 && offsetof(orc_hit, ng) == 32 && offsetof(orc_hit, ns) == 56, "lg_hit's vectors");
+static_assert(offsetof(orc_hit, kind) == 80 && offsetof(orc_hit, prim) == 84 && offsetof(orc_hit, instance) == 88 &&
+              offsetof(orc_hit, material) == 92, "lg_hit's identity words");
+static_assert(sizeof(orc_material) == 88, "lg_material is 88 bytes");
+
+extern "C++" {
+template <class F> static void for_rays(size_t n, size_t nthreads, F body) { // ray i on thread i % nthreads
+    if (nthreads == 0) nthreads = 1;
+    if (nthreads > n) nthreads = n ? n : 1;
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < nthreads; ++t) th.emplace_back([=]() { for (size_t i = t; i < n; i += nthreads) body(i); flush_stats(); });
+    for (size_t i = 0; i < n; i += nthreads) body(i);
+    flush_stats();
+    for (auto &t : th) t.join();
+}
+}
+static inline Ray query_ray(const double *r) { return ray_new(V3{r[0], r[1], r[2]}, V3{r[3], r[4], r[5]}); }
+
+// Closest hit of ray i: root.intersect (bvh.rs:461-522), resolved as shading sees it (SurfaceInteraction::from, surface.rs:158-183;
+// the material as integrate.rs:29-30 picks it).
+int orc_intersect(const void *accel, const double *rays, size_t n, orc_hit *hits, orc_material *mats, size_t nthreads) {
+    const Accel *acc = (const Accel *)accel;
+    if (n && (!rays || !hits)) { tl_error = "rays and hits must not be NULL"; return 1; }
+    for_rays(n, nthreads, [=](size_t i) {
+        const Ray ray = query_ray(rays + 6 * i);
+        RayIntersection isect = isect_default();
+        const Primitive *shape = acc->root->intersect(ray, isect);
+        orc_hit &h = hits[i];
+        std::memset(&h, 0, sizeof h);
+        if (!shape) {
+            h.t = F64_INF; h.prim = 0xFFFFFFFFu; h.instance = 0xFFFFFFFFu; h.material = -1;
+            if (mats) std::memset(&mats[i], 0, sizeof mats[i]);
+            return;
+        }
+        Material material;
+        if (!shape->material(material)) material = isect.material;
+        const SurfaceInteraction si = si_from(ray, isect);
+        h.t = isect.t;
+        const V3 *v[3] = {&si.p, &si.ng, &si.ns};
+        double *out[3] = {h.p, h.ng, h.ns};
+        for (int k = 0; k < 3; ++k) { out[k][0] = v[k]->x; out[k][1] = v[k]->y; out[k][2] = v[k]->z; }
+        h.kind = shape->id_kind; h.prim = shape->id_prim; h.instance = shape->id_inst; h.material = 0;
+        if (mats) mats[i] = from_mat(material);
+    });
+    return 0;
+}
+// occ[i] = 1 iff ray i's closest hit has t < 1.0: the shadow test of point.rs:42-54 as written, the full walk and then the compare.
+int orc_occluded(const void *accel, const double *rays, size_t n, uint8_t *occ, size_t nthreads) {
+    const Accel *acc = (const Accel *)accel;
+    if (n && (!rays || !occ)) { tl_error = "rays and occ must not be NULL"; return 1; }
+    for_rays(n, nthreads, [=](size_t i) {
+        RayIntersection isect = isect_default();
+        acc->root->intersect(query_ray(rays + 6 * i), isect);
+        occ[i] = isect.t < 1.0 ? 1 : 0;
+    });
+    return 0;
+}
+
 void orc_stats_reset(void) { std::lock_guard<std::mutex> g(*g_stats_mutex); g_stats_total = Stats(); tl_stats = Stats(); }
 void orc_stats_read(orc_stats *o) {
     flush_stats();

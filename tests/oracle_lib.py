@@ -9,7 +9,7 @@ import subprocess
 
 import numpy as np
 
-from lasgun_amd._capi import Api, CStats, LasgunError
+from lasgun_amd._capi import Api, CMaterial, CStats, LasgunError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -20,9 +20,13 @@ _EXTRA = {
     "capture_radiance": (C.c_int, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "capture_subset_mt": (C.c_int, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "capture_pixels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "stats_reset": (None, []),
     "stats_read": (None, [C.POINTER(CStats)]),
 }
+
+MATERIAL_DTYPE = np.dtype(CMaterial)  # lg_material / orc_material: what OracleApi.intersect returns per ray
 
 
 def build_oracle():
@@ -57,6 +61,25 @@ class OracleApi(Api):
         ys, xs = np.mgrid[y0:y1, x0:x1]
         rgba, rad = self.capture_pixels(accel, w, h, (ys * w + xs).ravel(), radiance, nthreads)
         return rgba.reshape(y1 - y0, x1 - x0, 4), (rad.reshape(y1 - y0, x1 - x0, 3) if radiance else None)
+
+    def intersect(self, accel, rays, nthreads=8):
+        """(hits, materials): the closest hit of every ray of an (n, 6) float64 array as lasgun_amd.HIT_DTYPE records (lg_hit; a
+        hit's `material` is 0, a miss's -1) and the winning material's POD per ray (MATERIAL_DTYPE, zero for a miss)."""
+        from lasgun_amd import HIT_DTYPE
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        hits = np.zeros(r.shape[0], dtype=HIT_DTYPE)
+        mats = np.zeros(r.shape[0], dtype=MATERIAL_DTYPE)
+        if self.call("intersect", accel.h, r.ctypes.data, r.shape[0], hits.ctypes.data, mats.ctypes.data, min(nthreads, 16)):
+            raise LasgunError(self.last_error())
+        return hits, mats
+
+    def occluded(self, accel, rays, nthreads=8):
+        """The reference's shadow test of every segment o -> o + d: the full closest-hit walk, then t < 1 (a bool array)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        occ = np.zeros(r.shape[0], dtype=np.uint8)
+        if self.call("occluded", accel.h, r.ctypes.data, r.shape[0], occ.ctypes.data, min(nthreads, 16)):
+            raise LasgunError(self.last_error())
+        return occ.astype(bool)
 
     def stats_reset(self):
         self.call("stats_reset")

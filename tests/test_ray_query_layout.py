@@ -47,7 +47,8 @@ def test_every_query_entry_point_is_exported():
 @pytest.mark.parametrize("builder", [lambda api: S.kitchen_sink_scene(api), lambda api: S.random_scene(api, 2), lambda api: S.tie_mesh_scene(api)],
                          ids=["kitchen_sink", "random_2", "tie_mesh"])
 def test_identity_witness_agrees_with_pyref(builder):
-    from test_gpu_ray_query import Witness, seeded_rays
+    from query_witness import Witness
+    from test_gpu_ray_query import seeded_rays
     traced, plain = builder(pyref.Api), builder(pyref.Api)
     pyref_bvh.install(plain)
     wit = Witness(traced)
