@@ -259,6 +259,30 @@ impl<'s> Accel<'s> {
         if rc != 0 { panic!("lasgun: {}", last_error()) }
         occ.into_iter().map(|b| b != 0).collect()
     }
+    /// The order a query's rays are walked in: false (default) as given, true sorted on the device by a coherence key -- for rays that
+    /// arrive in no particular order; the sort is part of every query's time.  The answers are the same bytes either way.
+    pub fn set_query_order(&self, sorted: bool) {
+        if unsafe { sys::lg_accel_set_query_order(self.ptr, sorted as i32) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    pub fn get_query_order(&self) -> bool {
+        unsafe { sys::lg_accel_get_query_order(self.ptr) != 0 }
+    }
+    /// The order `set_query_order(true)` walks these rays in: (perm, keys) -- perm[s] the ray walked in slot s, keys[i] ray i's key;
+    /// perm is the stable ascending sort of keys.
+    pub fn query_order(&self, rays: &[[f64; 6]]) -> (Vec<u32>, Vec<u32>) {
+        let (mut perm, mut keys) = (vec![0u32; rays.len()], vec![0u32; rays.len()]);
+        if rays.is_empty() { return (perm, keys) }
+        let rc = unsafe { sys::lg_query_order(self.ptr, rays.as_ptr() as *const f64, rays.len(), perm.as_mut_ptr(), keys.as_mut_ptr()) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        (perm, keys)
+    }
+    /// `query_order` for rays in device memory (6 doubles each), enqueued on a HIP stream: n u32 at `dev_perm` and, unless null, at `dev_keys`
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device holding n rays / n u32 (the library checks what HIP can tell it).
+    pub unsafe fn query_order_device(&self, dev_rays: *const f64, n: usize, dev_perm: *mut u32, dev_keys: *mut u32, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_query_order_device(self.ptr, dev_rays, n, dev_perm, dev_keys, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
 }
 impl<'s> Drop for Accel<'s> {
     fn drop(&mut self) { unsafe { sys::lg_accel_free(self.ptr) } }

@@ -169,6 +169,18 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         if (lg_occluded(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), occ.data())) throw Error(lg_last_error());
         return std::vector<bool>(occ.begin(), occ.end());
     }
+    // the order a query's rays are walked in (lg_accel_set_query_order): 0 as given (default), 1 sorted on the device by a coherence key
+    void set_query_order(int order) const {
+        if (lg_accel_set_query_order(h_, order)) throw Error(lg_last_error());
+    }
+    int query_order() const { return lg_accel_get_query_order(h_); }
+    // the order mode 1 walks `rays` in: perm[s] = the ray walked in slot s, the stable ascending sort of the rays' keys (*keys, if asked for)
+    std::vector<uint32_t> query_order(const std::vector<std::array<double, 6>> &rays, std::vector<uint32_t> *keys = nullptr) const {
+        std::vector<uint32_t> perm(rays.size());
+        if (keys) keys->assign(rays.size(), 0u);
+        if (lg_query_order(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), perm.data(), keys ? keys->data() : nullptr)) throw Error(lg_last_error());
+        return perm;
+    }
 
   private:
     explicit Accel(lg_accel *a) : h_(a) {}

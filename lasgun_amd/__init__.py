@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -86,6 +86,7 @@ _EXTRA = {
     "camera_samples": (_C.c_uint32, [_C.c_void_p]),
     "accel_material": (_C.c_int, [_C.c_void_p, _C.c_int32, _C.c_void_p]),
     "accel_instance": (_C.c_int, [_C.c_void_p, _C.c_uint32, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int64)]),
+    **QUERY_ORDER_SIGNATURES,
 }
 
 
@@ -467,6 +468,31 @@ class HipApi(Api):
     def occluded_device(self, accel, n, rays_ptr, occluded_ptr, stream=None):
         """Enqueue the occlusion bytes (1 = blocked) of n segments (device memory, 6 doubles each) into occluded_ptr."""
         if self.call("occluded_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(occluded_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def set_query_order(self, accel, order):
+        """The order a query's rays are walked in: 0 as given (default), 1 sorted on the device by a coherence key -- for rays that arrive
+        in no particular order; the sort is part of every call's time (include/lasgun_hip.h, lg_accel_set_query_order).  Same bytes either way."""
+        if self.call("accel_set_query_order", accel.h, int(order)):
+            raise LasgunError(self.last_error())
+
+    def get_query_order(self, accel):
+        return int(self.call("accel_get_query_order", accel.h))
+
+    def query_order(self, accel, rays):
+        """The order set_query_order(accel, 1) walks an (n, 6) float64 array of rays in: (perm, keys), two uint32 arrays -- perm[s] the ray
+        walked in slot s, keys[i] ray i's key; perm is the stable ascending sort of keys."""
+        r = self._rays(rays)
+        perm = _np.zeros(r.shape[0], dtype=_np.uint32)
+        keys = _np.zeros(r.shape[0], dtype=_np.uint32)
+        if self.call("query_order", accel.h, r.ctypes.data, r.shape[0], perm.ctypes.data, keys.ctypes.data):
+            raise LasgunError(self.last_error())
+        return perm, keys
+
+    def query_order_device(self, accel, n, rays_ptr, perm_ptr, keys_ptr=None, stream=None):
+        """Enqueue the order of n rays (device memory, 6 doubles each) into n uint32 at perm_ptr and, unless None, their keys at keys_ptr."""
+        keys = _C.c_void_p(int(keys_ptr)) if keys_ptr is not None else None
+        if self.call("query_order_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(perm_ptr)), keys, self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
     def camera_rays(self, accel, w, h, x0=0, y0=0, x1=None, y1=None):

@@ -114,6 +114,15 @@ CORE_SIGNATURES = {
     "math_eval": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# The opt-in ray order of ray queries (include/lasgun_hip.h, lg_accel_set_query_order .. lg_query_order_device): entry points of the
+# GPU library alone -- no counterpart in the reference, none in the oracle -- which its owner adds to what it binds (lasgun_amd/__init__.py).
+QUERY_ORDER_SIGNATURES = {
+    "accel_set_query_order": (C.c_int, [C.c_void_p, C.c_int]),
+    "accel_get_query_order": (C.c_int, [C.c_void_p]),
+    "query_order": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "query_order_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 class Api:
     """One bound C ABI: `Api(ctypes.CDLL(path), "lg_")`."""

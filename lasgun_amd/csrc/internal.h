@@ -25,6 +25,7 @@
 
 #include "../../include/lasgun_hip.h"
 #include "host.h"
+#include "raykey.h"
 #include "tune.h"
 
 namespace lg {
@@ -35,8 +36,13 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
 hipError_t launch_wf_shade(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_combine(const DParams &P, uint32_t blocks, hipStream_t stream);
 // k_query.hip: ray queries (query.cpp) -- hits != nullptr: closest hit into lg_hit[n]; occluded != nullptr: the any-hit walk, one byte per ray
+// perm != nullptr: the rays are walked in that order (slot s walks ray perm[s]); answers go to the ray's own slot either way
 hipError_t launch_query(const DParams &P, const double *rays, unsigned long long n, void *hits, uint8_t *occluded, const uint32_t *tri_base,
-                        bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+                        const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+// k_sort.hip: the rays' coherence keys (raykey.h) and their stable sort; scratch of sort_scratch_bytes(n) bytes, 256-byte aligned
+size_t sort_scratch_bytes(unsigned long long n);
+hipError_t launch_query_order(const double *rays, unsigned long long n, const KeyBounds &B, void *scratch, uint32_t *keys_out, uint32_t *perm_out,
+                              const uint32_t **perm, uint32_t grid_cap, hipStream_t stream);
 hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long n, uint32_t blocks, hipStream_t stream);
 hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
 hipError_t query_set_lds_limit(size_t bytes, bool ldss);
@@ -344,6 +350,7 @@ struct lg_accel {
         DevBuf<double> frames, stash;                          // megakernel: Whitted frame stack, parked shading frame
         DevBuf<uint8_t> wf_mem;                                // wavefront pipeline: every per-level array of a chunk, carved from one allocation
         DevBuf<uint32_t> wf_counters;                          // its queue counts and per-launch tile counters
+        DevBuf<uint8_t> sort_mem;                              // ray queries in sorted order (k_sort.hip): ping-pong keys and indices, histograms; grown on demand
         // strided subsets by lattice column (shade.h, modes 4 / 5): (floor(y*w / n), (y*w) mod n) per film row -- one table per (w, h, n), the
         // last MAX_ROW_TABLES of them kept (a caller that alternates periods or films on one stream finds each again), each uploaded from
         // pinned staging of its own on the context's stream (`up`: that copy is through; the staging may be rewritten)
@@ -384,6 +391,7 @@ struct lg_accel {
     mutable int last_org = -1;                    // what the last launch ran as: 0 megakernel, 1 level by level, 2 queue, + 16 with its tiles claimed bottom-up (lg_accel_last_organisation)
     mutable int tile_parts = -1;                  // lg_accel_set_tile_parts: the megakernel hands a tile out whole (1) or in 2 / 4 / 8 parts; -1 = whole unless the measured choice says quarters
     mutable int sample_order = -1;                // lg_accel_set_sample_order: 0 a pixel's samples side by side, 1 one after the other, -1 = side by side (megakernel: rule / measured)
+    mutable int query_order = 0;                  // lg_accel_set_query_order: 0 a query's rays are walked as given, 1 sorted on the device by a coherence key (k_sort.hip)
     mutable int tile_order = -1;                  // lg_accel_set_tile_order: 0 top-down, 1 bottom-up, 2 from the middle row outwards, -1 = middle-out unless the measured choice says otherwise
     bool queue_default = false;                   // glass / mirror over a big mesh: long uneven walks, sparse deep levels (k_queue.hip)
     mutable size_t queue_budget = 0;              // bytes one launch context may hold for it (0 = from the free memory at first use)

@@ -6,6 +6,10 @@
 // once per workgroup where the accel keeps it there.  A ray is 48 bytes in, read as three 16-byte loads; a closest hit is 96 bytes out
 // (lg_hit), written as six 16-byte stores -- a wave writes 6 KiB in one piece; an occlusion answer is one byte.  Lanes past the last ray
 // (n % 64) walk nothing and write nothing.
+//
+// PERM (lg_accel_set_query_order(1)): the tiles are cut from the SORTED order of the rays (k_sort.hip) -- slot s = tile * 64 + lane walks
+// ray i = perm[s], read from rays[6i] and answered in hits[6i] / occluded[i]: no gathered copy of the rays, no scatter pass over the hits
+// (either would move ~144 bytes a ray more).  perm is a permutation of 0 .. n-1, so every slot of the caller's arrays is written once.
 #include "shade.h"
 
 namespace lg {
@@ -16,6 +20,7 @@ struct QueryArgs {
     uint4 *hits;               // closest hit: [n] lg_hit, 6 x uint4 each
     uint8_t *occluded;         // any-hit: [n]
     const uint32_t *tri_base;  // per accel: its mesh's first triangle in the triangle tables (a face number is the triangle index minus this)
+    const uint32_t *perm;      // PERM forms only: [n], the ray walked in each slot
 };
 
 __device__ __forceinline__ uint4 bits2(double a, double b) {
@@ -25,7 +30,7 @@ __device__ __forceinline__ uint4 bits2(double a, double b) {
 
 // ANY = false: closest hit, resolved to world space as shading sees it (shade_frame), with the primitive's public identity;
 // ANY = true: the shadow pass's any-hit walk, occluded = t < 1 (point.rs:49)
-template <bool FAST, bool LDSS, bool PRUNE, bool ANY>
+template <bool FAST, bool LDSS, bool PRUNE, bool ANY, bool PERM>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) query_kernel(const DParams P, const QueryArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
@@ -50,8 +55,9 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
         else tile = claim_tile_single(P.tile_counter, ntiles, final);
         if (tile == NO_TILE) break;
-        const unsigned long long i = (unsigned long long)tile * 64ull + lane;
+        unsigned long long i = (unsigned long long)tile * 64ull + lane;
         const bool active = i < Q.n;
+        if (PERM && active) i = Q.perm[i];
         Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
         if (active) {
             const double2 *r = reinterpret_cast<const double2 *>(Q.rays + 6ull * i);
@@ -97,60 +103,70 @@ __global__ void __launch_bounds__(LG_BLOCK) camera_rays_kernel(const DParams P, 
 }
 
 // ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as wf_trace_kernel, LDS sized as launch_wf_trace sizes it.
+// perm != nullptr: the PERM forms
 hipError_t launch_query(const DParams &P, const double *rays, unsigned long long n, void *hits, uint8_t *occluded, const uint32_t *tri_base,
-                        bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
-    const QueryArgs Q{rays, n, reinterpret_cast<uint4 *>(hits), occluded, tri_base};
+                        const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    const QueryArgs Q{rays, n, reinterpret_cast<uint4 *>(hits), occluded, tri_base, perm};
     const bool any = occluded != nullptr;
     const bool ldss = P.lds_image && !fast;
     const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
     const uint32_t depth = fast ? stack_depth : P.stack_depth;
     const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_Q(F, L, Z) do { if (any) hipLaunchKernelGGL((query_kernel<F, L, Z, true>), dim3(blocks), dim3(block), lds, stream, P, Q); \
-                           else hipLaunchKernelGGL((query_kernel<F, L, Z, false>), dim3(blocks), dim3(block), lds, stream, P, Q); } while (0)
+#define LG_QP(F, L, Z, A) do { if (perm) hipLaunchKernelGGL((query_kernel<F, L, Z, A, true>), dim3(blocks), dim3(block), lds, stream, P, Q); \
+                               else hipLaunchKernelGGL((query_kernel<F, L, Z, A, false>), dim3(blocks), dim3(block), lds, stream, P, Q); } while (0)
+#define LG_Q(F, L, Z) do { if (any) LG_QP(F, L, Z, true); else LG_QP(F, L, Z, false); } while (0)
     if (fast) LG_Q(true, false, false);
     else if (P.prune) { if (ldss) LG_Q(false, true, true); else LG_Q(false, false, true); }
     else { if (ldss) LG_Q(false, true, false); else LG_Q(false, false, false); }
 #undef LG_Q
+#undef LG_QP
     return hipGetLastError();
 }
 hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long n, uint32_t blocks, hipStream_t stream) {
     hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(LG_BLOCK), 0, stream, P, rays, n);
     return hipGetLastError();
 }
-// workgroups per CU of the 256-lane forms (the smaller of closest and any-hit)
+// workgroups per CU of the 256-lane forms (the smallest of closest and any-hit, as given and permuted)
+template <bool FAST, bool PRUNE> static hipError_t query_occupancy_of(size_t lds, int *blocks_per_cu) {
+    const void *fns[] = {reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, false, false>), reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, true, false>),
+                         reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, false, true>), reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, true, true>)};
+    int least = 0;
+    for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
+        int v = 0;
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fns[i], LG_BLOCK, lds);
+        if (e != hipSuccess) return e;
+        if (i == 0 || v < least) least = v;
+    }
+    *blocks_per_cu = least;
+    return hipSuccess;
+}
 hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
     const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
-    int a = 0, b = 0;
-    hipError_t e;
-    if (fast) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, query_kernel<true, false, false, false>, LG_BLOCK, lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, query_kernel<true, false, false, true>, LG_BLOCK, lds);
-    } else if (prune) {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, query_kernel<false, false, true, false>, LG_BLOCK, lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, query_kernel<false, false, true, true>, LG_BLOCK, lds);
-    } else {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, query_kernel<false, false, false, false>, LG_BLOCK, lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, query_kernel<false, false, false, true>, LG_BLOCK, lds);
-    }
-    *blocks_per_cu = a < b ? a : b;
-    return e;
+    if (fast) return query_occupancy_of<true, false>(lds, blocks_per_cu);
+    if (prune) return query_occupancy_of<false, true>(lds, blocks_per_cu);
+    return query_occupancy_of<false, false>(lds, blocks_per_cu);
 }
 // raise the dynamic-LDS limit of this file's traversal kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
-hipError_t query_set_lds_limit(size_t bytes, bool ldss) {
-    const void *ldss_fns[] = {
-        reinterpret_cast<const void *>(query_kernel<false, true, false, false>), reinterpret_cast<const void *>(query_kernel<false, true, false, true>),
-        reinterpret_cast<const void *>(query_kernel<false, true, true, false>), reinterpret_cast<const void *>(query_kernel<false, true, true, true>)};
-    const void *plain_fns[] = {
-        reinterpret_cast<const void *>(query_kernel<false, false, false, false>), reinterpret_cast<const void *>(query_kernel<false, false, false, true>),
-        reinterpret_cast<const void *>(query_kernel<false, false, true, false>), reinterpret_cast<const void *>(query_kernel<false, false, true, true>),
-        reinterpret_cast<const void *>(query_kernel<true, false, false, false>), reinterpret_cast<const void *>(query_kernel<true, false, false, true>)};
-    const void *const *fns = ldss ? ldss_fns : plain_fns;
-    const size_t n = ldss ? sizeof ldss_fns / sizeof ldss_fns[0] : sizeof plain_fns / sizeof plain_fns[0];
-    for (size_t i = 0; i < n; ++i) {
-        hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+template <bool FAST, bool LDSS, bool PRUNE> static hipError_t query_lds_limit_of(int bytes) {
+    const void *fns[] = {reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, false, false>), reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, true, false>),
+                         reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, false, true>), reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, true, true>)};
+    for (const void *f : fns) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+hipError_t query_set_lds_limit(size_t bytes, bool ldss) {
+    hipError_t e;
+    if (ldss) {
+        e = query_lds_limit_of<false, true, false>((int)bytes);
+        if (e == hipSuccess) e = query_lds_limit_of<false, true, true>((int)bytes);
+        return e;
+    }
+    e = query_lds_limit_of<false, false, false>((int)bytes);
+    if (e == hipSuccess) e = query_lds_limit_of<false, false, true>((int)bytes);
+    if (e == hipSuccess) e = query_lds_limit_of<true, false, false>((int)bytes);
+    return e;
 }
 
 } // namespace lg

@@ -1,6 +1,8 @@
 // lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_camera_rays*, lg_accel_material,
 // lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like the render's
-// level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode.
+// level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode.  With
+// lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
+// its tiles from the sorted order; lg_query_order* return that order.
 #include <cstddef>
 
 #include "internal.h"
@@ -11,6 +13,9 @@ static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hi
 static_assert(sizeof(lg_material) == sizeof(Material), "lg_material wraps Material");
 
 static constexpr unsigned long long MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits
+static constexpr unsigned long long MAX_SORTED_RAYS = 0xFFFFFFFFull;  // the sorted order's indices are 32-bit
+// A query of at most 64 rays is one wave's tile whatever the order: it is walked as given (the same bytes; lg_query_order* sort any n)
+static constexpr size_t SORT_MIN_RAYS = 65;
 
 // A caller's device buffer: not NULL, aligned, device memory of the accel's device, and `bytes` long within its allocation -- checked
 // before anything is enqueued (a pageable host pointer or another device's memory would fault the card, not fail the call).
@@ -29,6 +34,34 @@ static void check_device_buffer(const lg_accel &a, const void *p, size_t bytes, 
     if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess) {
         if ((const char *)p + bytes > (const char *)base + size) throw Error(std::string(what) + " ends beyond its allocation");
     } else (void)hipGetLastError();
+}
+
+// The scene's world bounds for the key (raykey.h): the root accel's box, its corners taken to world space
+static KeyBounds world_key_bounds(const lg_accel &a) {
+    const FlatScene &f = a.flat;
+    double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {0.0, 0.0, 0.0};
+    if (!f.accels.empty() && f.accels[0].node_base < f.nodes.size()) {
+        const DNode &root = f.nodes[f.accels[0].node_base];
+        for (int c = 0; c < 8; ++c) {
+            const V3 p = xf_point(f.accels[0].m, V3{(c & 1) ? root.bmax[0] : root.bmin[0], (c & 2) ? root.bmax[1] : root.bmin[1], (c & 4) ? root.bmax[2] : root.bmin[2]});
+            const double q[3] = {p.x, p.y, p.z};
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = c == 0 ? q[k] : std::fmin(lo[k], q[k]); // (fmin / fmax: a NaN corner of a degenerate scene is stepped over)
+                hi[k] = c == 0 ? q[k] : std::fmax(hi[k], q[k]);
+            }
+        }
+    }
+    return key_bounds(lo, hi);
+}
+// The sorted order of `rays` enqueued on `stream`: the context's scratch grown if it has to be (the one step that is more than an enqueue:
+// a device-wide synchronise and an allocation, once per stream and size), then key + sort.  Returns where the permutation will be.
+static const uint32_t *enqueue_query_order(const lg_accel &a, lg_accel::LaunchCtx &c, const double *rays, size_t n, uint32_t *keys_out, uint32_t *perm_out,
+                                           hipStream_t stream) {
+    const size_t need = sort_scratch_bytes(n);
+    if (c.sort_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); c.sort_mem.alloc(need); }
+    const uint32_t *perm = nullptr;
+    HIP_TRY(launch_query_order(rays, n, world_key_bounds(a), c.sort_mem.p, keys_out, perm_out, &perm, a.cus * 8u, stream));
+    return perm;
 }
 
 // One query enqueued on `stream` (caller holds a.mtx and has made the accel's device current): hits != nullptr for closest hits,
@@ -53,8 +86,13 @@ static void enqueue_query(const lg_accel &a, const double *rays, size_t n, lg_hi
     const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
     P.tile_counter = c.tile_counter.p;
+    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
     HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
-    HIP_TRY(launch_query(P, rays, n, hits, occluded, a.accel_tri_base.p, a.fast, blocks, depth, stream));
+    HIP_TRY(launch_query(P, rays, n, hits, occluded, a.accel_tri_base.p, perm, a.fast, blocks, depth, stream));
+}
+
+static void check_sorted_count(const lg_accel &a, size_t n) {
+    if (a.query_order == 1 && n > MAX_SORTED_RAYS) throw Error("too many rays in one query for the sorted order (lg_accel_set_query_order): at most 2^32 - 1");
 }
 
 // Both host forms: copy the rays in, enqueue on the accel's stream, copy the results out, synchronise (as lg_capture_pixels)
@@ -67,6 +105,7 @@ static int query_host(const lg_accel *a, const double *rays, size_t n, void *out
         if (n > MAX_RAYS) throw Error("too many rays in one query");
         const size_t out_bytes = n * (any ? 1u : sizeof(lg_hit));
         std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
         use_device(a->device);
         DevBuf<double> drays;
         DevBuf<uint8_t> dout;
@@ -84,6 +123,7 @@ static int query_device(const lg_accel *a, const double *dev_rays, size_t n, voi
         if (!a) throw Error("accel is NULL");
         if (n > MAX_RAYS) throw Error("too many rays in one query");
         std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         check_device_buffer(*a, dev_out, n * (any ? 1u : sizeof(lg_hit)), any ? 1 : 16, any ? "occluded" : "hits");
@@ -115,6 +155,54 @@ int lg_intersect_device(const lg_accel *a, const double *dev_rays, size_t n, lg_
 }
 int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream) {
     return query_device(a, dev_rays, n, dev_occluded, true, hip_stream);
+}
+
+int lg_accel_set_query_order(const lg_accel *a, int order) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        if (order != 0 && order != 1) throw Error("query order " + std::to_string(order) + ": 0 (as given) or 1 (sorted on the device)");
+        std::lock_guard<std::mutex> g(a->mtx);
+        a->query_order = order;
+    });
+}
+int lg_accel_get_query_order(const lg_accel *a) {
+    if (!a) return 0;
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->query_order;
+}
+int lg_query_order(const lg_accel *a, const double *rays, size_t n, uint32_t *perm, uint32_t *keys) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (!rays) throw Error("rays is NULL");
+        if (!perm) throw Error("perm is NULL");
+        if (n > MAX_SORTED_RAYS) throw Error("too many rays to order: at most 2^32 - 1");
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        DevBuf<double> drays;
+        DevBuf<uint32_t> dkeys;
+        drays.alloc(n * 6);
+        if (keys) dkeys.alloc(n);
+        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        const uint32_t *dperm = enqueue_query_order(*a, ctx_for(*a, a->stream), drays.p, n, keys ? dkeys.p : nullptr, nullptr, a->stream);
+        HIP_TRY(hipMemcpyAsync(perm, dperm, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        if (keys) HIP_TRY(hipMemcpyAsync(keys, dkeys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+    });
+}
+int lg_query_order_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t *dev_perm, uint32_t *dev_keys, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (n > MAX_SORTED_RAYS) throw Error("too many rays to order: at most 2^32 - 1");
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        check_device_buffer(*a, dev_perm, n * sizeof(uint32_t), 4, "perm");
+        if (dev_keys) check_device_buffer(*a, dev_keys, n * sizeof(uint32_t), 4, "keys");
+        check_queue_error(*a);
+        (void)enqueue_query_order(*a, ctx_for(*a, (hipStream_t)hip_stream), dev_rays, n, dev_keys, dev_perm, (hipStream_t)hip_stream);
+    });
 }
 
 int lg_camera_rays(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays) {

@@ -4,9 +4,13 @@ spheres, LDS-resident), config 4 (the glass torus mesh, pruned walk) and config 
   (a) closest hits of the camera's 4096^2 primary rays (lg_camera_rays_device),
   (b) the same rays in a seeded random order (incoherent),
   (c) occlusion of the shadow segments to light 0 from (a)'s hits (the render's shadow origin: p + ng * 2^-36),
-and, as diagnostics, (a) and (c) with the rays in the render's own order (8 x 8 pixel tiles, rows a8 / c8).
-Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--out profiles/r07_query.jsonl]
+and, as diagnostics, (a) and (c) with the rays in the render's own order (8 x 8 pixel tiles, rows a8 / c8) and (c) in a seeded random order (cs).
+--order 1 walks those rows' rays in the sorted order (lg_accel_set_query_order(1)); without it every row is measured as given (order 0) and
+then again sorted (rows "... [order 1]", the key and the sort inside the timed call), and one more row times the key and the sort alone
+(lg_query_order_device on (b)'s rays).
+Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16; --repeats R measures
+everything R times (rows carry "repeat").
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a) and (c) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -54,7 +58,7 @@ def shadow_segments(hits, light):
     return torch.cat([o, d], dim=1).contiguous()
 
 
-def measure(name, builder, size, calls, seed):
+def measure(name, builder, size, calls, seed, order=None):
     scene = builder(G)
     accel = G.Accel.from_scene(scene)
     light = builder(pyref.Api).lights[0][0]
@@ -68,30 +72,48 @@ def measure(name, builder, size, calls, seed):
     shuffled = rays[torch.randperm(n, device="cuda", generator=gen)].contiguous()
     hits_b = torch.empty_like(hits)
     rows = []
-    ms = timed(lambda: G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s), calls)
-    rows.append(("a: closest, camera order", n, ms))
-    ms = timed(lambda: G.intersect_device(accel, n, shuffled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
-    rows.append(("b: closest, random order", n, ms))
-    segs = shadow_segments(hits, light)
-    occ = torch.empty((segs.shape[0],), dtype=torch.uint8, device="cuda")
-    ms = timed(lambda: G.occluded_device(accel, segs.shape[0], segs.data_ptr(), occ.data_ptr(), stream=s), calls)
-    rows.append(("c: occluded, shadow segments to light 0", segs.shape[0], ms))
-    # the same rays and segments in the render's own order -- 8 x 8 pixel tiles, a tile per wave -- instead of row-major (diagnostic rows)
     pix = torch.arange(size * size, device="cuda")
     key = ((pix // size // 8) * (size // 8) + (pix % size) // 8) * 64 + ((pix // size) % 8) * 8 + (pix % size) % 8
-    order = torch.argsort(key)
-    tiled = rays[order].contiguous() if n == size * size else None
-    if tiled is not None:
-        ms = timed(lambda: G.intersect_device(accel, n, tiled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
-        rows.append(("a8: closest, 8x8 pixel tiles", n, ms))
-        segs8 = shadow_segments(hits.view(-1, 96)[order].contiguous().view(-1), light)
-        ms = timed(lambda: G.occluded_device(accel, segs8.shape[0], segs8.data_ptr(), occ.data_ptr(), stream=s), calls)
-        rows.append(("c8: occluded, shadow segments in 8x8 pixel tiles", segs8.shape[0], ms))
+    tile_order = torch.argsort(key)
+    del pix, key
+    G.set_query_order(accel, 0)
+    G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s)
+    segs = shadow_segments(hits, light)
+    occ = torch.empty((segs.shape[0],), dtype=torch.uint8, device="cuda")
+    for mode in ((0, 1) if order is None else (order,)):
+        G.set_query_order(accel, mode)
+        tag = " [order 1]" if mode == 1 and order is None else ""
+        ms = timed(lambda: G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s), calls)
+        rows.append(("a: closest, camera order" + tag, n, ms, mode))
+        ms = timed(lambda: G.intersect_device(accel, n, shuffled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
+        rows.append(("b: closest, random order" + tag, n, ms, mode))
+        ms = timed(lambda: G.occluded_device(accel, segs.shape[0], segs.data_ptr(), occ.data_ptr(), stream=s), calls)
+        rows.append(("c: occluded, shadow segments to light 0" + tag, segs.shape[0], ms, mode))
+        occluded_fraction = round(float(occ.float().mean()), 4)
+        segs_s = segs[torch.randperm(segs.shape[0], device="cuda", generator=gen)].contiguous()
+        ms = timed(lambda: G.occluded_device(accel, segs_s.shape[0], segs_s.data_ptr(), occ.data_ptr(), stream=s), calls)
+        rows.append(("cs: occluded, shadow segments in random order" + tag, segs_s.shape[0], ms, mode))
+        del segs_s
+        # the same rays and segments in the render's own order -- 8 x 8 pixel tiles, a tile per wave -- instead of row-major (diagnostic rows)
+        if n == size * size:
+            tiled = rays[tile_order].contiguous()
+            ms = timed(lambda: G.intersect_device(accel, n, tiled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
+            rows.append(("a8: closest, 8x8 pixel tiles" + tag, n, ms, mode))
+            del tiled
+            segs8 = shadow_segments(hits.view(-1, 96)[tile_order].contiguous().view(-1), light)
+            ms = timed(lambda: G.occluded_device(accel, segs8.shape[0], segs8.data_ptr(), occ.data_ptr(), stream=s), calls)
+            rows.append(("c8: occluded, shadow segments in 8x8 pixel tiles" + tag, segs8.shape[0], ms, mode))
+            del segs8
+    if order is None and n < (1 << 32):
+        perm = torch.empty((n,), dtype=torch.int32, device="cuda")
+        ms = timed(lambda: G.query_order_device(accel, n, shuffled.data_ptr(), perm.data_ptr(), None, stream=s), calls)
+        rows.append(("sort: key and sort alone, (b)'s rays", n, ms, 1))
+    G.set_query_order(accel, 0)
     out = []
-    for row, nr, ms in rows:
-        out.append({"scene": name, "row": row, "film": [size, size], "rays": int(nr), "ms": round(ms, 4), "mrays_per_s": round(nr / ms / 1e3, 1),
+    for row, nr, ms, mode in rows:
+        out.append({"scene": name, "row": row, "order": mode, "film": [size, size], "rays": int(nr), "ms": round(ms, 4), "mrays_per_s": round(nr / ms / 1e3, 1),
                     "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel),
-                    "occluded_fraction": round(float(occ.float().mean()), 4) if row == rows[2][0] else None,
+                    "occluded_fraction": occluded_fraction if row.startswith("c:") else None,
                     "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)})
     return out
 
@@ -120,6 +142,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--order", type=int, choices=(0, 1), default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -129,10 +153,12 @@ def main():
         return
     t0 = time.time()
     rows = []
-    for name, builder in SCENES:
-        for r in measure(name, builder, args.size, max(args.calls, 20), args.seed):
-            print(json.dumps(r), flush=True)
-            rows.append(r)
+    for repeat in range(max(args.repeats, 1)):
+        for name, builder in SCENES:
+            for r in measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order):
+                r["repeat"] = repeat
+                print(json.dumps(r), flush=True)
+                rows.append(r)
     if args.out:
         with open(args.out, "w") as f:
             for r in rows:
