@@ -259,6 +259,23 @@ impl<'s> Accel<'s> {
         if rc != 0 { panic!("lasgun: {}", last_error()) }
         occ.into_iter().map(|b| b != 0).collect()
     }
+    /// Radiance along every ray (origin xyz, direction xyz): what the reference's `integrate` leaves for a pixel whose one sample is that
+    /// ray (integrate.rs:16-20, 23-132) -- lights, shadows, ambient, specular recursion, background on a miss --, f64 RGB before quantisation.
+    /// For rays no camera of the scene generates: probes, panoramas, bakes, a second view of one accel.
+    pub fn radiance(&self, rays: &[[f64; 6]]) -> Vec<[f64; 3]> {
+        let mut out = vec![[0f64; 3]; rays.len()];
+        if rays.is_empty() { return out }
+        let rc = unsafe { sys::lg_radiance(self.ptr, rays.as_ptr() as *const f64, rays.len(), out.as_mut_ptr() as *mut f64) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        out
+    }
+    /// `radiance` for rays in device memory (6 doubles each), enqueued on a HIP stream: 3 n doubles at `dev_radiance`
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device holding n rays / 3 n doubles (the library checks what HIP can tell it).
+    pub unsafe fn radiance_device(&self, dev_rays: *const f64, n: usize, dev_radiance: *mut f64, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_radiance_device(self.ptr, dev_rays, n, dev_radiance, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
     /// The order a query's rays are walked in: false (default) as given, true sorted on the device by a coherence key -- for rays that
     /// arrive in no particular order; the sort is part of every query's time.  The answers are the same bytes either way.
     pub fn set_query_order(&self, sorted: bool) {

@@ -158,7 +158,7 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
-    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded): rays are origin xyz, direction xyz
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_radiance): rays are origin xyz, direction xyz
     std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<lg_hit> hits(rays.size());
         if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
@@ -168,6 +168,12 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         std::vector<uint8_t> occ(rays.size());
         if (lg_occluded(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), occ.data())) throw Error(lg_last_error());
         return std::vector<bool>(occ.begin(), occ.end());
+    }
+    // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
+    std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
+        std::vector<std::array<double, 3>> out(rays.size());
+        if (lg_radiance(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
+        return out;
     }
     // the order a query's rays are walked in (lg_accel_set_query_order): 0 as given (default), 1 sorted on the device by a coherence key
     void set_query_order(int order) const {

@@ -392,6 +392,26 @@ int lg_occluded(const lg_accel *, const double *rays, size_t n, uint8_t *occlude
  * anything else is an error before any launch.  n == 0 is a successful no-op. */
 int lg_intersect_device(const lg_accel *, const double *dev_rays, size_t n, lg_hit *dev_hits, void *hip_stream);
 int lg_occluded_device(const lg_accel *, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream);
+/* Radiance along every ray: the third query, for rays no camera of the scene generates (a fisheye or panorama, a light probe or cube
+ * map, a lightmap bake from surface points, a caller's own path continuation, a second view of an accel without rebuilding it).
+ * radiance[3*i ..] = what integrate() leaves for a pixel whose one sample is ray i: (Color::zero() + li(root, ray_i, depth 0)) * 1.0
+ * (integrate.rs:16-20, 23-132) -- lights, shadow rays, ambient, specular reflection / transmission down to the scene's max recursion
+ * depth, background on a miss -- before quantisation.  One ray = 6 doubles as for lg_intersect; direction used as given.
+ * f64 RGB, n x 3, in the caller's order; the zero-plus-li and the times-one are kept so that the bytes are lg_capture_radiance's for the
+ * render's own rays (lg_camera_rays).  The scene's camera and its supersampling play no part: a caller who wants a supersampled pixel
+ * sums its samples' results in camera order and multiplies by 1.0 / S, which is the render's own arithmetic.
+ * Traversal is the accel's mode, as for the other queries; lg_accel_set_query_order(1) is honoured (a query of 64 rays or fewer is
+ * walked as given).  The organisation is always the level-by-level pipeline -- the caller's rays are its level 0 --, whatever
+ * lg_accel_set_streaming says, cut into chunks by that pipeline's memory budget (LASGUN_WF_BUDGET_MB); nothing is measured or
+ * remembered for it, and lg_profile_* credit its kernels as a render's.  That pipeline keeps a hit's light visibility in a 32-bit word:
+ * a scene with MORE THAN 32 LIGHTS is an error before any launch (lg_last_error), as is a recursion depth of 20 or more.
+ * n == 0 is a successful no-op; NULL arguments and n > 2^32 - 1 tiles of 64 rays are errors.
+ * Device form: dev_rays and dev_radiance must be 8-byte aligned device memory of the accel's device, checked before anything is enqueued.
+ * It only enqueues on hip_stream, with the exceptions the render and the sorted order have: the first query of a stream, and the first of
+ * more rays than any launch before it, grows the launch context's level arrays (and, in mode 1, the sort's scratch) after a device-wide
+ * synchronise.  One stream at a time per accel. */
+int lg_radiance(const lg_accel *, const double *rays, size_t n, double *radiance);                         /* host arrays; synchronous */
+int lg_radiance_device(const lg_accel *, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream);
 /* The rays the render traces for the pixels [x0,x1) x [y0,y1) of a width x height film: row-major pixels and, per pixel, the camera's
  * samples in camera.rs order (idx = i*dim + j, camera.rs:137-146), 6 doubles each: (x1-x0) * (y1-y0) * supersamples rays. */
 int lg_camera_rays(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays);

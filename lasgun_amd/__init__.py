@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -87,6 +87,7 @@ _EXTRA = {
     "accel_material": (_C.c_int, [_C.c_void_p, _C.c_int32, _C.c_void_p]),
     "accel_instance": (_C.c_int, [_C.c_void_p, _C.c_uint32, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int64)]),
     **QUERY_ORDER_SIGNATURES,
+    **RADIANCE_SIGNATURES,
 }
 
 
@@ -468,6 +469,20 @@ class HipApi(Api):
     def occluded_device(self, accel, n, rays_ptr, occluded_ptr, stream=None):
         """Enqueue the occlusion bytes (1 = blocked) of n segments (device memory, 6 doubles each) into occluded_ptr."""
         if self.call("occluded_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(occluded_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def radiance(self, accel, rays):
+        """Radiance along every ray of an (n, 6) float64 array (origin, direction): (n, 3) float64 RGB, li() as the render computes it
+        -- lights, shadows, ambient, specular recursion, background on a miss -- before quantisation (include/lasgun_hip.h, lg_radiance)."""
+        r = self._rays(rays)
+        out = _np.zeros((r.shape[0], 3), dtype=_np.float64)
+        if self.call("radiance", accel.h, r.ctypes.data, r.shape[0], out.ctypes.data):
+            raise LasgunError(self.last_error())
+        return out
+
+    def radiance_device(self, accel, n, rays_ptr, out_ptr, stream=None):
+        """Enqueue the radiance of n rays (device memory, 6 doubles each) into 3 n doubles at out_ptr (both 8-byte aligned)."""
+        if self.call("radiance_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(out_ptr)), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
     def set_query_order(self, accel, order):

@@ -123,6 +123,12 @@ QUERY_ORDER_SIGNATURES = {
     "query_order_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# Radiance queries (include/lasgun_hip.h, lg_radiance / lg_radiance_device): li() of the caller's rays; the GPU library's alone, as above.
+RADIANCE_SIGNATURES = {
+    "radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
 
 class Api:
     """One bound C ABI: `Api(ctypes.CDLL(path), "lg_")`."""

@@ -333,4 +333,13 @@ struct DParams {
     uint32_t audit;             // counting variant: also audit what the pruned walk skips (walk.h, audit_prim)
 };
 
+// A radiance query's level 0 (k_radiance.hip), beside the DParams of its chunk: the caller's buffers and where the chunk starts
+struct RadianceArgs {
+    const double *rays;        // [n][6]: origin xyz, direction xyz, as lg_intersect takes them
+    double *radiance;          // [n][3]
+    const uint32_t *perm;      // sorted order (lg_accel_set_query_order(1)): slot s is ray perm[s]; nullptr: slot s is ray s
+    unsigned long long n;      // rays of the query
+    unsigned long long base;   // the chunk's first slot: work item i of the chunk is slot base + i
+};
+
 } // namespace lg

@@ -47,6 +47,11 @@ hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long
 hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
 hipError_t query_set_lds_limit(size_t bytes, bool ldss);
 hipError_t launch_wf_resolve(const DParams &P, uint32_t blocks, hipStream_t stream);
+// k_radiance.hip: level 0 of the level-by-level pipeline for a radiance query's rays (launch.cpp, enqueue_radiance)
+hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_rq_combine(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t queue_occupancy(uint32_t stack_depth, size_t extra_lds, int *blocks_per_cu);
@@ -446,6 +451,7 @@ void sync_checked(const lg_accel &a);
 DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
+void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

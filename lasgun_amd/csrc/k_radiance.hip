@@ -1,0 +1,257 @@
+// lasgun_amd/csrc/k_radiance.hip -- radiance queries (include/lasgun_hip.h, lg_radiance*): LEVEL 0 of the level-by-level pipeline
+// (k_wavefront.hip) for rays the caller supplies instead of the rays a camera generates for a film.
+//
+// A query is li() of n rays.  The pipeline's levels >= 1 never knew where level 0's rays came from: they read a ray queue and leave li
+// in a per-level array, so the shadow pass of every level, the closest / shade passes of the levels below and every combine above
+// level 0 are the render's own kernels.  What is welded to the camera in k_wavefront.hip is level 0 -- camera_ray() / pixel_of() /
+// finish_pixel() -- and these are its three passes again with that replaced, the walk, the hit queue, the parked frame and every
+// f64 expression kept as they are there (the two files are meant to be read side by side; the existing kernels are not touched, several
+// sit at their register budget):
+//   * work item i = tile * 64 + lane of a chunk stands for SLOT s = base + i of the query, active while s < n, and walks
+//     ray r = perm ? perm[s] : s (lg_accel_set_query_order(1): the chunks are cut from the sorted order, k_sort.hip);
+//   * the ray is read from the caller's AoS buffer (48 bytes, three 16-byte loads, as k_query.hip reads it) in the closest pass and
+//     again in the shade pass (wo depends on it) -- no transposed copy of the rays, no gather pass over the results;
+//   * a finished ray is radiance[3r ..] = (0 + li) * 1.0, what integrate() leaves for a pixel of one sample (integrate.rs:16-20): no
+//     Pixel, no sample accumulator, no resolve pass.  Every r is written exactly once (perm is a permutation of 0 .. n-1).
+#include "wflevel.h"
+
+namespace lg {
+
+template <bool PERM> __device__ __forceinline__ unsigned long long rq_ray_index(const RadianceArgs &Q, unsigned long long slot) {
+    return PERM ? (unsigned long long)Q.perm[slot] : slot;
+}
+__device__ __forceinline__ Ray rq_load_ray(const RadianceArgs &Q, unsigned long long r) {
+    const double2 *p = reinterpret_cast<const double2 *>(Q.rays + 6ull * r);
+    const double2 a = p[0], b = p[1], c = p[2];
+    return ray_new(V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}); // Ray3::new: the direction as given
+}
+// integrate() for a pixel whose one sample is this ray: Color::zero() + li, then * weight with weight = 1 / 1 (integrate.rs:16-20).
+// (The sum is what turns a -0.0 of li into the +0.0 a rendered pixel holds; the product by one is exact.)
+__device__ __forceinline__ void rq_finish(const RadianceArgs &Q, unsigned long long r, V3 value) {
+    const V3 color = (vzero() + value) * 1.0;
+    double *o = Q.radiance + 3ull * r;
+    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+}
+
+// W1 of level 0 (wf_trace_kernel<FAST, false, LDSS, true, PRUNE>)
+template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
+__global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) rq_closest_kernel(const DParams P, const RadianceArgs Q) {
+    static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
+    static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t ntiles = P.ntiles;
+    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
+    uint32_t *stack = lds_stack + tid;
+    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint4 *scn = nullptr;
+    if (LDSS) {
+        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
+        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
+        __syncthreads(); // the only workgroup-wide step; every wave reaches it before pulling tiles
+        scn = dst;
+    }
+    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
+    if (!wave_has_work(ntiles)) return;
+    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
+    for (bool final = false; !final;) {
+        uint32_t tile;
+        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
+        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        if (tile == NO_TILE) break;
+        const unsigned long long i = (unsigned long long)tile * 64ull + lane; // the chunk's work item: index of level 0's arrays
+        const bool active = Q.base + i < Q.n;
+        unsigned long long r = 0;
+        Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
+        if (active) {
+            r = rq_ray_index<PERM>(Q, Q.base + i);
+            ray = rq_load_ray(Q, r);
+        }
+        Best b;
+        b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
+        if (active) walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+        const bool hit = active && b.ref != NO_HIT;
+        // ---- this wave's slots in the level's hit queue (wflevel.h: dense where most lanes hit, appended otherwise)
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+        const uint32_t nhit = (uint32_t)__builtin_popcountll(mask);
+        unsigned long long h = i;
+        if (nhit < WF_FULL_MIN) {
+            P.wf_hq[i] = WF_NONE; // (every lane stands for slot i of the dense part, a ray or a slot past the last ray: the chunk's arrays hold whole tiles)
+            if (nhit != 0u) {
+                uint32_t base_v = 0u;
+                if (lane == 0u) base_v = atomicAdd(P.wf_counts + P.wf_levels, nhit);
+                h = P.wf_hit_cap + (uint32_t)__builtin_amdgcn_readfirstlane((int)base_v) + lanes_below(mask);
+            }
+        } else if (!hit) P.wf_hq[i] = WF_NONE; // a hole of a dense block
+        if (hit) {
+            P.wf_hq[h] = (uint32_t)i;
+            Shade sh;
+            shade_frame(P, ray, b, sh);
+            const unsigned long long n = P.wf_hit_stride;
+            double *f = P.frame + h;
+            f[0 * n] = sh.praw.x; f[1 * n] = sh.praw.y; f[2 * n] = sh.praw.z;
+            f[3 * n] = sh.ng.x; f[4 * n] = sh.ng.y; f[5 * n] = sh.ng.z;
+            f[6 * n] = sh.ns.x; f[7 * n] = sh.ns.y; f[8 * n] = sh.ns.z;
+            f[9 * n] = sh.ss.x; f[10 * n] = sh.ss.y; f[11 * n] = sh.ss.z;
+            f[12 * n] = (double)sh.mat;
+        } else if (active) { // integrate.rs:26-28
+            const V3 value = background(P, normalize(ray.d));
+            if (P.wf_levels == 1u) rq_finish(Q, r, value);
+            else {
+                const unsigned long long n = P.wf_cap;
+                P.wf_out[i] = value.x; P.wf_out[n + i] = value.y; P.wf_out[2 * n + i] = value.z;
+                P.wf_child[i] = WF_MISS;
+            }
+        }
+    }
+}
+
+// W3 of level 0 (wf_shade_kernel<KIND, true>).  KIND 0: the scene has no recursion at all, li = output + 0 + 0 is the ray's radiance;
+// KIND 1: there is a level below, the specular children are appended to its ray queue (integrate.rs:69-77).
+// The grid covers the chunk's dense tiles AND the most hits that can be appended behind them, one wave per tile, no loop.
+template <int KIND, bool PERM>
+__global__ void __launch_bounds__(LG_BLOCK, 3) rq_shade_kernel(const DParams P, const RadianceArgs Q) {
+    const HitSlots hs = hit_slots(P, 0u, 64u);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const unsigned long long t = (unsigned long long)blockIdx.x * (LG_BLOCK / 64u) + wave;
+    if (t >= hs.tiles) return; // (whole waves stay together: the appends of KIND 1 are wave-wide)
+    unsigned long long h = 0;
+    const bool valid = hit_of(P, hs, (uint32_t)t, lane, h);
+    unsigned long long j = 0, r = 0;
+    bool has_r = false, has_t = false;
+    Sample sr, st;
+    Shade sh;
+    V3 output = vzero();
+    if (valid) {
+        j = P.wf_hq[h];
+        r = rq_ray_index<PERM>(Q, Q.base + j);
+        const Ray ray = rq_load_ray(Q, r);
+        const unsigned long long n = P.wf_hit_stride;
+        const double *f = P.frame + h;
+        V3 p{f[0 * n], f[1 * n], f[2 * n]};
+        sh.ng = V3{f[3 * n], f[4 * n], f[5 * n]};
+        sh.ns = V3{f[6 * n], f[7 * n], f[8 * n]};
+        sh.ss = V3{f[9 * n], f[10 * n], f[11 * n]};
+        sh.mat = (int32_t)f[12 * n];
+        sh.wo = -normalize(ray.d);
+        const double err = 2.220446049250313e-16 * 65536.0;
+        V3 p_err = sh.ng * err;
+        sh.praw = p; sh.p = p + p_err; sh.pm = p - p_err;
+        sh.ts = cross(sh.ns, sh.ss);
+        const DMaterial m = P.materials[sh.mat];
+        const uint32_t vis = P.nlights ? P.vis[h] : 0u;
+        output = shade_lights(P, m, sh, vis); // integrate.rs:47-67
+        if (KIND == 1 && (m.kind == MAT_GLASS || m.kind == MAT_MIRROR)) { // depth < max recursion (integrate.rs:69-77)
+            if (sample_specular_transmission(m, sh, st))
+                has_t = !(st.pdf <= 0.0 || veq(st.spectrum, vzero()) || fabs(dot(st.wi, sh.ns)) == 0.0);
+            if (sample_specular_reflection(m, sh, sr))
+                has_r = !(sr.pdf <= 0.0 || veq(sr.spectrum, vzero()) || dot(sr.wi, sh.ns) <= 0.0);
+        }
+    }
+    if (KIND == 0) { // integrate.rs:79 with no children
+        if (valid) rq_finish(Q, r, output + vzero() + vzero());
+        return;
+    }
+    // children: consecutive slots of level 1's ray queue per wavefront and kind
+    const uint32_t cr = wave_append(P.wf_counts + 1u, has_r);
+    const uint32_t ct = wave_append(P.wf_counts + 1u, has_t);
+    if (!valid) return;
+    const unsigned long long n = P.wf_cap, nn = P.wf_cap_next;
+    P.wf_out[j] = output.x; P.wf_out[n + j] = output.y; P.wf_out[2 * n + j] = output.z;
+    P.wf_child[j] = has_r ? cr : WF_NONE;
+    P.wf_child[n + j] = has_t ? ct : WF_NONE;
+    double *sp = P.wf_spec + j;
+    if (has_r) {
+        sp[0 * n] = sr.spectrum.x; sp[1 * n] = sr.spectrum.y; sp[2 * n] = sr.spectrum.z;
+        const V3 wr = -1.0 * sh.wo + 2.0 * dot(sh.wo, sh.ns) * sh.ns; // bxdf::util::reflect (integrate.rs:100)
+        double *q = P.wf_q_next + cr;
+        q[0 * nn] = sh.p.x; q[1 * nn] = sh.p.y; q[2 * nn] = sh.p.z; q[3 * nn] = wr.x; q[4 * nn] = wr.y; q[5 * nn] = wr.z;
+    }
+    if (has_t) {
+        sp[3 * n] = st.spectrum.x; sp[4 * n] = st.spectrum.y; sp[5 * n] = st.spectrum.z;
+        sp[6 * n] = fabs(dot(st.wi, sh.ns)); sp[7 * n] = st.pdf;
+        double *q = P.wf_q_next + ct;
+        q[0 * nn] = sh.pm.x; q[1 * nn] = sh.pm.y; q[2 * nn] = sh.pm.z; q[3 * nn] = st.wi.x; q[4 * nn] = st.wi.y; q[5 * nn] = st.wi.z;
+    }
+}
+
+// W4 of level 0 (wf_combine_kernel at level 0): li of the query's rays from their children's (integrate.rs:79, 103, 129), finished
+template <bool PERM>
+__global__ void __launch_bounds__(LG_BLOCK) rq_combine_kernel(const DParams P, const RadianceArgs Q) {
+    const unsigned long long n_work = (unsigned long long)P.ntiles * 64ull;
+    const unsigned long long n = P.wf_cap, nn = P.wf_cap_next;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * LG_BLOCK + threadIdx.x; j < n_work; j += (unsigned long long)gridDim.x * LG_BLOCK) {
+        if (Q.base + j >= Q.n) continue;
+        V3 value{P.wf_out[j], P.wf_out[n + j], P.wf_out[2 * n + j]};
+        const uint32_t c0 = P.wf_child[j];
+        if (c0 != WF_MISS) {
+            const uint32_t c1 = P.wf_child[n + j];
+            const double *sp = P.wf_spec + j;
+            V3 reflected = vzero(), refracted = vzero();
+            if (c0 != WF_NONE) {
+                const V3 l{P.wf_out_next[c0], P.wf_out_next[nn + c0], P.wf_out_next[2 * nn + c0]};
+                reflected = mul_ew(V3{sp[0 * n], sp[1 * n], sp[2 * n]}, l); // integrate.rs:103
+            }
+            if (c1 != WF_NONE) {
+                const V3 l{P.wf_out_next[c1], P.wf_out_next[nn + c1], P.wf_out_next[2 * nn + c1]};
+                refracted = mul_ew(V3{sp[3 * n], sp[4 * n], sp[5 * n]}, l) * sp[6 * n] / sp[7 * n]; // integrate.rs:129
+            }
+            value = value + reflected + refracted; // integrate.rs:79
+        }
+        rq_finish(Q, rq_ray_index<PERM>(Q, Q.base + j), value);
+    }
+}
+
+// ---- host-callable launchers (launch.cpp, enqueue_radiance).  The closest pass in the (FAST, LDSS, PRUNE) forms of wf_trace_kernel, its
+// LDS sized as launch_wf_trace sizes it; Q.perm != nullptr: the PERM forms
+hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    const bool ldss = P.lds_image && !fast;
+    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint32_t depth = fast ? stack_depth : P.stack_depth;
+    const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
+#define LG_RQ(F, L, Z) do { if (Q.perm) hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, true>), dim3(blocks), dim3(block), lds, stream, P, Q); \
+                            else hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, false>), dim3(blocks), dim3(block), lds, stream, P, Q); } while (0)
+    if (fast) LG_RQ(true, false, false);
+    else if (P.prune) { if (ldss) LG_RQ(false, true, true); else LG_RQ(false, false, true); }
+    else { if (ldss) LG_RQ(false, true, false); else LG_RQ(false, false, false); }
+#undef LG_RQ
+    return hipGetLastError();
+}
+hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
+    if (P.wf_levels == 1u) {
+        if (Q.perm) hipLaunchKernelGGL((rq_shade_kernel<0, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+        else hipLaunchKernelGGL((rq_shade_kernel<0, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    } else {
+        if (Q.perm) hipLaunchKernelGGL((rq_shade_kernel<1, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+        else hipLaunchKernelGGL((rq_shade_kernel<1, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    }
+    return hipGetLastError();
+}
+hipError_t launch_rq_combine(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
+    if (Q.perm) hipLaunchKernelGGL((rq_combine_kernel<true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    else hipLaunchKernelGGL((rq_combine_kernel<false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    return hipGetLastError();
+}
+// raise the dynamic-LDS limit of the closest pass to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
+template <bool FAST, bool LDSS, bool PRUNE> static hipError_t rq_lds_limit_of(int bytes) {
+    const void *fns[] = {reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, true>)};
+    for (const void *f : fns) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+hipError_t rq_set_lds_limit(size_t bytes, bool ldss) {
+    hipError_t e;
+    if (ldss) {
+        e = rq_lds_limit_of<false, true, false>((int)bytes);
+        if (e == hipSuccess) e = rq_lds_limit_of<false, true, true>((int)bytes);
+        return e;
+    }
+    e = rq_lds_limit_of<false, false, false>((int)bytes);
+    if (e == hipSuccess) e = rq_lds_limit_of<false, false, true>((int)bytes);
+    if (e == hipSuccess) e = rq_lds_limit_of<true, false, false>((int)bytes);
+    return e;
+}
+
+} // namespace lg

@@ -190,14 +190,16 @@ struct ChunkPlan {
 };
 
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
-static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s) {
+// (`rq`: the launch is a radiance query's -- its level 0 is k_radiance.hip's)
+static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr) {
     const unsigned long long n0 = plan.n0();
     const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull), flat_cap = a.cus * 16u; // (level 0: one thread per work item)
     for (uint32_t d = plan.levels - 1; d-- > 0;) {
         P.wf_level = d;
         P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
         P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-        timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
+        if (d == 0 && rq) timed(a, 1, s, [&] { return launch_rq_combine(P, *rq, flat_blocks0, s); });
+        else timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
     }
 }
 // ... and a pixel's samples summed in their order (k_wavefront.hip, wf_resolve_kernel)
@@ -207,8 +209,83 @@ static void resolve_samples(const lg_accel &a, const DParams &P, uint32_t pixel_
     timed(a, 1, s, [&] { return launch_wf_resolve(R, (uint32_t)(((unsigned long long)pixel_tiles * 64ull + 255ull) / 256ull), s); });
 }
 
-// The wavefront pipeline (k_wavefront.hip): per chunk of the film and per supersample, levels 0 .. L-1 top-down (closest,
-// shadow, shade), then the combine passes bottom-up.
+// ---- the level-by-level pipeline (k_wavefront.hip), shared by a render (enqueue_wavefront) and a radiance query (enqueue_radiance) ----
+// A chunk's arrays in a launch context: the level arrays, and beside them the hit queue, frame and visibility of the widest level (dense
+// part + appended part), the queue counts and a block of tile heads per launch
+struct WfChunk {
+    const ChunkPlan &plan;
+    uint32_t levels, nlaunch;
+    static constexpr uint32_t CL = TILE_COUNTER_WORDS; // the queue counts (3 per level) in the first block, then a block of tile heads per launch (one head per XCD, each on a line of its own)
+    LevelArrays L;
+    uint32_t *hq = nullptr, *vis = nullptr, *counters = nullptr;
+    double *frame = nullptr;
+    WfChunk(const ChunkPlan &p) : plan(p), levels(p.levels), nlaunch(4 * p.levels) {}
+    static size_t extra_per_item(uint32_t levels) { return ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4; } // ChunkPlan's `extra`
+    size_t hit_cap() const { return (size_t)plan.n0() << (levels - 1); }
+    size_t hit_len() const { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); } // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
+    void carve(lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk, grown if they have to be
+        if (cx.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); cx.wf_mem.alloc(plan.need()); }
+        if (cx.wf_counters.n < CL * (1 + nlaunch)) { HIP_TRY(hipDeviceSynchronize()); cx.wf_counters.alloc(CL * (1 + nlaunch)); }
+        L = plan.carve(cx.wf_mem.p, [&](auto &take) {
+            hq = (uint32_t *)take(hit_len() * 4);
+            frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
+            vis = (uint32_t *)take(hit_len() * 4);
+        });
+        counters = cx.wf_counters.p;
+    }
+    // what every launch of the chunk is told (P.ntiles = level 0's work tiles is the caller's)
+    void params(const lg_accel &a, DParams &P, bool ldss) const {
+        P.n_items = plan.n0(); // stride of the sample accumulator
+        P.accum = L.accum;
+        P.wf_levels = levels;
+        P.wf_counts = counters;
+        P.wf_hit_cap = hit_cap(); P.wf_hit_stride = hit_len(); P.wf_hq = hq; P.frame = frame; P.vis = vis;
+        if (ldss) {
+            P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
+            P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+        }
+    }
+    // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
+    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's.
+    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr) const {
+        const bool ldss = P.lds_image != nullptr;
+        const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
+        const uint32_t trace_cap = ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks), flat_cap = a.cus * 16u;
+        const uint32_t trace_blocks0 = ldss ? trace_cap : std::min(trace_cap, (P.ntiles + 3u) / 4u);
+        // level-0 shade: one wave per dense tile and per tile the appended hits can fill (< WF_FULL_MIN of every 64 rays)
+        const uint32_t shade_blocks0 = (uint32_t)(((unsigned long long)P.ntiles + ((unsigned long long)P.ntiles * (WF_FULL_MIN_HOST - 1) + 63ull) / 64ull + 3ull) / 4ull);
+        const unsigned long long n0 = plan.n0();
+        HIP_TRY(hipMemsetAsync(counters, 0, CL * (1 + nlaunch) * sizeof(uint32_t), ls));
+        uint32_t launch_no = 0;
+        auto level_params = [&](uint32_t d) {
+            P.wf_level = d;
+            P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
+            P.wf_q = L.q[d]; P.wf_out = L.out[d]; P.wf_spec = L.spec[d]; P.wf_child = L.child[d];
+            P.wf_q_next = d + 1 < levels ? L.q[d + 1] : nullptr;
+            P.wf_out_next = d + 1 < levels ? L.out[d + 1] : nullptr;
+            P.tile_counter = counters + CL * (1 + launch_no++);
+        };
+        for (uint32_t d = 0; d < levels; ++d) {
+            // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
+            // every deeper level may exceed only in waves, never in work per wave)
+            const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
+            const bool rq0 = rq && d == 0;
+            level_params(d);
+            if (rq0) timed(a, 0, ls, [&] { return launch_rq_closest(P, *rq, a.fast, tb, depth, ls); });
+            else timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
+            if (P.nlights > 0) {
+                level_params(d);
+                timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
+            }
+            level_params(d);
+            if (rq0) timed(a, 3, ls, [&] { return launch_rq_shade(P, *rq, fb, ls); });
+            else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
+        }
+        combine_levels(a, P, L, plan, ls, rq);
+    }
+};
+
+// A render: per chunk of the film and per supersample, one chain (WfChunk::run).
 static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c, hipStream_t stream) {
     const uint32_t levels = levels_of(a, P0);
     const uint32_t nsamples = P0.ss_root * P0.ss_root;
@@ -218,7 +295,7 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
     // lg_accel_set_sample_order(1): one chain per sample, summed as they come.
     const uint32_t S = nsamples > 1 && a.sample_order != 1 ? nsamples : 1u; // level-0 work items per pixel
     // beside the level arrays: the hit queue, frame and visibility of the widest level, dense part + appended part
-    ChunkPlan plan(a, P0, false, S, ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4);
+    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels));
     // Bands on internal streams: opt-in (lg_accel_set_wf_split, or LASGUN_WF_SPLIT=n as the default), launches of 2 Mpixel and
     // more.  Measured: one headline frame at a time 7.79 -> 7.50 ms with 4 bands, but 7.20 -> 7.46 ms
     // when the caller already keeps four frames in flight -- which is why it is not the default.
@@ -231,112 +308,85 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
     const unsigned long long nchunks = (P0.ntiles + plan.chunk_tiles - 1) / plan.chunk_tiles;
     const unsigned nstreams = split > 1 && nchunks > 1 ? (unsigned)std::min<unsigned long long>(split, nchunks) : 0u; // 0: everything on the caller's stream
     if (nstreams) ensure_aux_streams(a, nstreams);
-    const uint32_t nlaunch = 4 * levels;
-    const uint32_t CL = TILE_COUNTER_WORDS; // the queue counts (3 per level) in the first block, then a block of tile heads per launch (one head per XCD, each on a line of its own)
-    auto hit_cap = [&] { return (size_t)plan.n0() << (levels - 1); };
-    auto hit_len = [&] { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); }; // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
-    struct Carved {
-        LevelArrays L;
-        uint32_t *hq = nullptr, *vis = nullptr, *counters = nullptr;
-        double *frame = nullptr;
-    };
-    auto carve = [&](lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk
-        if (cx.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); cx.wf_mem.alloc(plan.need()); }
-        if (cx.wf_counters.n < CL * (1 + nlaunch)) { HIP_TRY(hipDeviceSynchronize()); cx.wf_counters.alloc(CL * (1 + nlaunch)); }
-        Carved k;
-        k.L = plan.carve(cx.wf_mem.p, [&](auto &take) {
-            k.hq = (uint32_t *)take(hit_len() * 4);
-            k.frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
-            k.vis = (uint32_t *)take(hit_len() * 4);
-        });
-        k.counters = cx.wf_counters.p;
-        return k;
-    };
-    std::vector<Carved> carved;
+    std::vector<WfChunk> carved;
     std::vector<hipStream_t> lanes;
     plan.fit([&] {
         carved.clear(); lanes.clear();
-        if (nstreams) for (unsigned j = 0; j < nstreams; ++j) { lanes.push_back(a.aux_streams[j]); carved.push_back(carve(ctx_for(a, a.aux_streams[j]))); }
-        else { lanes.push_back(stream); carved.push_back(carve(c)); }
+        if (nstreams) for (unsigned j = 0; j < nstreams; ++j) { lanes.push_back(a.aux_streams[j]); carved.emplace_back(plan); carved.back().carve(ctx_for(a, a.aux_streams[j])); }
+        else { lanes.push_back(stream); carved.emplace_back(plan); carved.back().carve(c); }
     });
-    const unsigned long long chunk_tiles = plan.chunk_tiles, n0 = plan.n0();
+    const unsigned long long chunk_tiles = plan.chunk_tiles;
     if (nstreams) {
         HIP_TRY(hipEventRecord(a.aux_fork, stream)); // the bands start after whatever the caller's stream holds (a film clear, the previous frame's copy)
         for (unsigned j = 0; j < nstreams; ++j) HIP_TRY(hipStreamWaitEvent(a.aux_streams[j], a.aux_fork, 0));
     }
 
     const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
-    const uint32_t trace_cap = ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks);
-    const uint32_t flat_cap = a.cus * 16u;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] wavefront: levels %u, %llu tiles in chunks of %llu on %u stream(s) (%.1f MiB per context), trace grid %u x %u, stack %u, max_blocks %u\n", levels,
-                     (unsigned long long)P0.ntiles, chunk_tiles, nstreams ? nstreams : 1u, plan.need() / 1048576.0, trace_cap, ldss ? 1024u : 256u, depth, a.max_blocks);
+                     (unsigned long long)P0.ntiles, chunk_tiles, nstreams ? nstreams : 1u, plan.need() / 1048576.0, ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks),
+                     ldss ? 1024u : 256u, a.fast ? a.stack_depth_fast1 : a.stack_depth, a.max_blocks);
     // (A small frame's chain replayed as a HIP graph was measured in round 6 and retired: on this runtime a graph launch costs more than
     // the stream launches it replaces -- the README sphere at 512^2 0.086 -> 0.093 ms, Cornell plastic 0.119 -> 0.129 ms, every longer
     // chain within +-2 %; profiles/r06_small_frames.jsonl.)
     unsigned long long chunk_no = 0;
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles, ++chunk_no) {
-        const Carved &K = carved[chunk_no % carved.size()];
+        const WfChunk &K = carved[chunk_no % carved.size()];
         const hipStream_t ls = lanes[chunk_no % lanes.size()]; // the stream of this chunk
-        const std::vector<double *> &q = K.L.q, &out = K.L.out, &spec = K.L.spec;
-        const std::vector<uint32_t *> &child = K.L.child;
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
         const uint32_t pixel_tiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ntiles = pixel_tiles * S; // level 0's work tiles
         P.ss_par = S;
-        P.n_items = n0; // stride of the sample accumulator
-        P.accum = K.L.accum;
-        P.wf_levels = levels;
-        P.wf_counts = K.counters;
-        P.wf_hit_cap = hit_cap(); P.wf_hit_stride = hit_len(); P.wf_hq = K.hq; P.frame = K.frame; P.vis = K.vis;
+        K.params(a, P, ldss);
 #ifdef LG_STAMPS
         P.stats = a.stats.p;
         P.stamp_counts = reinterpret_cast<unsigned long long *>(a.stats.p + 1);
 #endif
-        if (ldss) {
-            P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-            P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-        }
-        const uint32_t tiles_needed = (P.ntiles + 3u) / 4u;
-        const uint32_t trace_blocks0 = ldss ? trace_cap : std::min(trace_cap, tiles_needed);
-        // level-0 shade: one wave per dense tile and per tile the appended hits can fill (< WF_FULL_MIN of every 64 rays)
-        const uint32_t shade_blocks0 = (uint32_t)(((unsigned long long)P.ntiles + ((unsigned long long)P.ntiles * (WF_FULL_MIN_HOST - 1) + 63ull) / 64ull + 3ull) / 4ull);
         for (uint32_t sidx = 0; sidx < nsamples / S; ++sidx) {
             P.sample_index = sidx;
-            HIP_TRY(hipMemsetAsync(K.counters, 0, CL * (1 + nlaunch) * sizeof(uint32_t), ls));
-            uint32_t launch_no = 0;
-            auto level_params = [&](uint32_t d) {
-                P.wf_level = d;
-                P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
-                P.wf_q = q[d]; P.wf_out = out[d]; P.wf_spec = spec[d]; P.wf_child = child[d];
-                P.wf_q_next = d + 1 < levels ? q[d + 1] : nullptr;
-                P.wf_out_next = d + 1 < levels ? out[d + 1] : nullptr;
-                P.tile_counter = K.counters + CL * (1 + launch_no++);
-            };
-            for (uint32_t d = 0; d < levels; ++d) {
-                // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
-                // every deeper level may exceed only in waves, never in work per wave)
-                const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
-                level_params(d);
-                timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
-                if (P.nlights > 0) {
-                    level_params(d);
-                    timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
-                }
-                level_params(d);
-                timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
-            }
-            combine_levels(a, P, K.L, plan, ls);
+            K.run(a, P, ls);
         }
         if (S > 1) resolve_samples(a, P, pixel_tiles, ls);
     }
     for (unsigned j = 0; j < nstreams; ++j) { // join: the caller's stream continues when every band is done
         HIP_TRY(hipEventRecord(a.aux_done[j], a.aux_streams[j]));
         HIP_TRY(hipStreamWaitEvent(stream, a.aux_done[j], 0));
+    }
+    if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
+}
+
+// A radiance query (query.cpp, lg_radiance*): li() of `n` caller-supplied rays through the same chain, on the caller's stream alone (no
+// bands).  Level 0's work items are the query's SLOTS, 64 to a tile, cut into chunks of consecutive slots by the same plan -- with a
+// permutation (lg_accel_set_query_order(1)) slot s is ray perm[s], so the chunks are cut from the sorted order.  One sample per ray,
+// whatever the scene's camera supersamples; always this organisation, whatever lg_accel_set_streaming says: nothing is measured or
+// remembered for it.  Caller holds a.mtx, has made the accel's device current and has checked the buffers and that the scene can go
+// level by level (radiance_possible).
+void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    DParams P0 = base_params(a, 1, 1);
+    P0.ss_root = 1; // (the scene's camera may be supersampled; a query is not)
+    P0.ntiles = (uint32_t)((n + 63) / 64);
+    const uint32_t levels = levels_of(a, P0);
+    ChunkPlan plan(a, P0, false, 1u, WfChunk::extra_per_item(levels));
+    WfChunk K(plan);
+    plan.fit([&] { K.carve(c); });
+    const unsigned long long chunk_tiles = plan.chunk_tiles;
+    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    if (std::getenv("LASGUN_DEBUG"))
+        std::fprintf(stderr, "[lasgun] radiance query: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", levels, (unsigned long long)P0.ntiles, chunk_tiles,
+                     plan.need() / 1048576.0, perm ? "sorted order" : "as given");
+    for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
+        DParams P = P0;
+        P.tile0 = (uint32_t)t0;
+        P.ntiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
+        P.ss_par = 1u;
+        K.params(a, P, ldss);
+        const RadianceArgs Q{rays, radiance, perm, (unsigned long long)n, t0 * 64ull};
+        K.run(a, P, stream, &Q);
     }
     if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
 }

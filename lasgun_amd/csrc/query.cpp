@@ -1,6 +1,7 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_camera_rays*, lg_accel_material,
-// lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like the render's
-// level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode.  With
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_radiance*, lg_camera_rays*,
+// lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
+// the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
+// lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.
 #include <cstddef>
@@ -132,6 +133,56 @@ static int query_device(const lg_accel *a, const double *dev_rays, size_t n, voi
     });
 }
 
+// ---- radiance queries: li() of the caller's rays through the level-by-level pipeline (launch.cpp, enqueue_radiance; k_radiance.hip)
+// What the pipeline cannot take is refused before anything is enqueued: its visibility word holds 32 lights (as for a render, which then
+// runs as the megakernel -- a query has no other organisation)
+static void radiance_possible(const lg_accel &a) {
+    const size_t nlights = a.flat.lights.size();
+    if (nlights > 32) throw Error("radiance query: the scene has " + std::to_string(nlights) + " lights, the level-by-level pipeline's visibility word holds 32");
+    if (a.scene->recursion >= 20) throw Error("radiance query: recursion depth " + std::to_string(a.scene->recursion) + ", the level-by-level pipeline takes fewer than 20");
+}
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the count and the buffers)
+static void enqueue_radiance_query(const lg_accel &a, const double *rays, size_t n, double *radiance, hipStream_t stream) {
+    check_queue_error(a);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
+    enqueue_radiance(a, rays, n, radiance, perm, c, stream);
+}
+static int radiance_host(const lg_accel *a, const double *rays, size_t n, double *radiance) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (!rays) throw Error("rays is NULL");
+        if (!radiance) throw Error("radiance is NULL");
+        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        radiance_possible(*a);
+        use_device(a->device);
+        DevBuf<double> drays, dout;
+        drays.alloc(n * 6);
+        dout.alloc(n * 3);
+        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_radiance_query(*a, drays.p, n, dout.p, a->stream);
+        HIP_TRY(hipMemcpyAsync(radiance, dout.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+    });
+}
+static int radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        radiance_possible(*a);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        check_device_buffer(*a, dev_radiance, n * 3 * sizeof(double), 8, "radiance");
+        enqueue_radiance_query(*a, dev_rays, n, dev_radiance, (hipStream_t)hip_stream);
+    });
+}
+
 // the rectangle's rays: (x1-x0) * (y1-y0) * supersamples; 0 for an empty rectangle
 static unsigned long long camera_ray_count(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     if (w == 0 || h == 0 || x0 > x1 || y0 > y1 || x1 > w || y1 > h) throw Error("rectangle outside the film");
@@ -155,6 +206,11 @@ int lg_intersect_device(const lg_accel *a, const double *dev_rays, size_t n, lg_
 }
 int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream) {
     return query_device(a, dev_rays, n, dev_occluded, true, hip_stream);
+}
+
+int lg_radiance(const lg_accel *a, const double *rays, size_t n, double *radiance) { return radiance_host(a, rays, n, radiance); }
+int lg_radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
+    return radiance_device(a, dev_rays, n, dev_radiance, hip_stream);
 }
 
 int lg_accel_set_query_order(const lg_accel *a, int order) {

@@ -1,0 +1,25 @@
+"""Child process of tests/test_gpu_radiance_query.py: one radiance query in a fresh process, because the level-by-level pipeline's
+memory budget (LASGUN_WF_BUDGET_MB) is read once per process.
+usage: python radiance_child.py SCENE RAYS.npy OUT.npy -- with LASGUN_DEBUG=1 the library says on stderr how many chunks it cut."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    import lasgun_amd as la
+    from test_gpu_radiance_query import FORM_SCENES
+    name, rays_path, out_path = sys.argv[1:4]
+    G = la.api
+    G.set_device(0)
+    accel = G.Accel.from_scene(dict(FORM_SCENES)[name](G))
+    np.save(out_path, G.radiance(accel, np.load(rays_path)))
+
+
+if __name__ == "__main__":
+    main()

@@ -8,10 +8,14 @@ and, as diagnostics, (a) and (c) with the rays in the render's own order (8 x 8 
 --order 1 walks those rows' rays in the sorted order (lg_accel_set_query_order(1)); without it every row is measured as given (order 0) and
 then again sorted (rows "... [order 1]", the key and the sort inside the timed call), and one more row times the key and the sort alone
 (lg_query_order_device on (b)'s rays).
+Radiance queries (lg_radiance_device) -- rows r / rs / r8: the radiance of (a)'s rays as given, in a seeded random order, and in 8 x 8 pixel
+tiles, under --order 0|1 (both without it) -- beside the row they are measured against, "frame": lg_capture_rows_device of the same film at
+one sample per pixel with lg_accel_set_streaming(2), the same rays through the same passes, and "hbm": lg_probe_rate(0) in GB/s.
+--rows radiance measures these rows alone, --rows frame the frame row alone (any build of the library has it).
 Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16; --repeats R measures
 everything R times (rows carry "repeat").
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--out profiles/r08_query_order.jsonl]
-       python tools/query_rate.py --once     (one headline frame rendered, then (a) and (c) once: for rocprofv3 --kernel-trace --stats)"""
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame] [--out profiles/r08_query_order.jsonl]
+       python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
 import os
@@ -118,6 +122,46 @@ def measure(name, builder, size, calls, seed, order=None):
     return out
 
 
+def measure_radiance(name, builder, size, calls, seed, order=None, frame_only=False):
+    """Rows frame / hbm / r / rs / r8 of one scene (module docstring)."""
+    scene = builder(G)
+    accel = G.Accel.from_scene(scene)
+    s = torch.cuda.current_stream().cuda_stream
+    rows = []
+    G.set_streaming(accel, 2)  # the level-by-level pipeline: what a radiance query always runs as
+    film = torch.empty((size * size * 4,), dtype=torch.uint8, device="cuda")
+    ms = timed(lambda: G.capture_rows_device(accel, size, size, 0, size, film.data_ptr(), stream=s), calls)
+    rows.append(("frame: capture_rows_device, streaming 2", size * size, ms, 0))
+    rows.append(("hbm: lg_probe_rate(0), GB/s", 0, G.probe_rate("hbm_copy"), 0))
+    del film
+    if not frame_only:
+        assert G.camera_samples(accel) == 1
+        n = size * size
+        rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+        G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+        out = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+        gen = torch.Generator(device="cuda").manual_seed(seed)
+        pix = torch.arange(n, device="cuda")
+        key = ((pix // size // 8) * (size // 8) + (pix % size) // 8) * 64 + ((pix // size) % 8) * 8 + (pix % size) % 8
+        tile_order = torch.argsort(key)
+        del pix, key
+        for mode in ((0, 1) if order is None else (order,)):
+            G.set_query_order(accel, mode)
+            ms = timed(lambda: G.radiance_device(accel, n, rays.data_ptr(), out.data_ptr(), stream=s), calls)
+            rows.append(("r: radiance, camera order", n, ms, mode))
+            other = rays[tile_order].contiguous()
+            ms = timed(lambda: G.radiance_device(accel, n, other.data_ptr(), out.data_ptr(), stream=s), calls)
+            rows.append(("r8: radiance, 8x8 pixel tiles", n, ms, mode))
+            other = rays[torch.randperm(n, device="cuda", generator=gen)].contiguous()
+            ms = timed(lambda: G.radiance_device(accel, n, other.data_ptr(), out.data_ptr(), stream=s), calls)
+            rows.append(("rs: radiance, random order", n, ms, mode))
+            del other
+        G.set_query_order(accel, 0)
+    return [{"scene": name, "row": row, "order": mode, "film": [size, size], "rays": int(nr), "ms": round(ms, 4) if nr else None,
+             "mrays_per_s": round(nr / ms / 1e3, 1) if nr else None, "gbps": None if nr else round(ms, 1), "calls": calls,
+             "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, nr, ms, mode in rows]
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -133,6 +177,9 @@ def once(size):
     segs = shadow_segments(hits, S.spheres_scene(pyref.Api).lights[0][0])
     occ = torch.empty((segs.shape[0],), dtype=torch.uint8, device="cuda")
     G.occluded_device(accel, segs.shape[0], segs.data_ptr(), occ.data_ptr(), stream=s)
+    tiled = rays.view(size // 8, 8, size // 8, 8, 6).permute(0, 2, 1, 3, 4).contiguous().view(n, 6)  # 8 x 8 pixel tiles: row r8
+    rad = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+    G.radiance_device(accel, n, tiled.data_ptr(), rad.data_ptr(), stream=s)
     torch.cuda.synchronize()
     print(json.dumps({"once": True, "rays": n, "shadow_segments": int(segs.shape[0])}))
 
@@ -144,6 +191,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
+    ap.add_argument("--rows", choices=("all", "queries", "radiance", "frame"), default="all")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -155,7 +203,10 @@ def main():
     rows = []
     for repeat in range(max(args.repeats, 1)):
         for name, builder in SCENES:
-            for r in measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order):
+            got = measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order) if args.rows in ("all", "queries") else []
+            if args.rows != "queries":
+                got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=args.rows == "frame")
+            for r in got:
                 r["repeat"] = repeat
                 print(json.dumps(r), flush=True)
                 rows.append(r)
