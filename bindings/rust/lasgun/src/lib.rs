@@ -223,6 +223,33 @@ impl Img for Film {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Lens cameras (no counterpart in the reference): rays for `Accel::capture_rays`
+// ---------------------------------------------------------------------------------------------------------------
+/// An equirectangular panorama (kind 0) or an equidistant fisheye (kind 1; `fov_deg` across the film's shorter side) around `origin`;
+/// the basis is used as given.
+pub use sys::lg_lens as Lens;
+
+/// The rays of a lens over a width x height film, row-major pixels (or over the pixel slots `offsets` names), samples_root^2 per slot in
+/// idx = i*samples_root + j order: the layout `Accel::capture_rays` takes.  Generated on the current device.
+pub fn lens_rays(lens: &Lens, width: u32, height: u32, samples_root: u32, offsets: Option<&[u64]>) -> Vec<[f64; 6]> {
+    let slots = offsets.map_or((width as usize) * (height as usize), |o| o.len());
+    let mut out = vec![[0f64; 6]; slots * (samples_root as usize) * (samples_root as usize)];
+    if out.is_empty() { return out }
+    let rc = unsafe { sys::lg_lens_rays(lens, width, height, samples_root, offsets.map_or(std::ptr::null(), |o| o.as_ptr()), slots, out.as_mut_ptr() as *mut f64) };
+    if rc != 0 { panic!("lasgun: {}", last_error()) }
+    out
+}
+/// `lens_rays` into device memory of `device`, enqueued on a HIP stream
+///
+/// # Safety
+/// `dev_rays` must be device memory of `device` holding pixels * samples_root^2 * 6 doubles, `dev_offsets` null or `pixels` u64 there.
+#[allow(clippy::too_many_arguments)]
+pub unsafe fn lens_rays_device(device: i32, lens: &Lens, width: u32, height: u32, samples_root: u32, dev_offsets: *const u64, pixels: usize, dev_rays: *mut f64,
+                               hip_stream: *mut std::ffi::c_void) {
+    if sys::lg_lens_rays_device(device, lens, width, height, samples_root, dev_offsets, pixels, dev_rays, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Accel, render, capture, capture_subset (src/lib.rs:42-162)
 // ---------------------------------------------------------------------------------------------------------------
 /// The acceleration structure of a scene: the reference's nested HLBVH, built on the host exactly as the reference
@@ -275,6 +302,36 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device holding n rays / 3 n doubles (the library checks what HIP can tell it).
     pub unsafe fn radiance_device(&self, dev_rays: *const f64, n: usize, dev_radiance: *mut f64, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_radiance_device(self.ptr, dev_rays, n, dev_radiance, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// A film from the caller's rays (`lg_capture_rays`): pixel slot g's rays are `rays[g*samples .. (g+1)*samples]`, summed in that order,
+    /// scaled by 1 / samples, quantised like the render's pixels and written at film offset `offsets[g]` (y*width + x), or g without
+    /// offsets.  A slot whose offset lies behind the film writes nothing; pixels no slot names keep their bytes.  `rgb`: the same values
+    /// before quantisation, width*height of them, addressed like the film.  For the scene's own camera rays this is `capture`'s film.
+    pub fn capture_rays(&self, rays: &[[f64; 6]], samples: u32, offsets: Option<&[u64]>, width: u32, height: u32, pixels: &mut [Pixel], rgb: Option<&mut [[f64; 3]]>) {
+        let area = (width as usize) * (height as usize);
+        assert!(samples > 0 && rays.len() % samples as usize == 0, "capture_rays: pixel slots * samples rays");
+        let slots = rays.len() / samples as usize;
+        assert!(pixels.len() == area && offsets.map_or(true, |o| o.len() == slots) && rgb.as_ref().map_or(true, |r| r.len() == area));
+        if slots == 0 { return }
+        let film = unsafe { sys::lg_film_wrap(width, height, pixels.as_mut_ptr() as *mut u8) };
+        let rc = unsafe {
+            sys::lg_capture_rays(self.ptr, rays.as_ptr() as *const f64, slots, samples, offsets.map_or(std::ptr::null(), |o| o.as_ptr()), film,
+                                 rgb.map_or(std::ptr::null_mut(), |r| r.as_mut_ptr() as *mut f64), width, height)
+        };
+        unsafe { sys::lg_film_free(film) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `capture_rays` for buffers in device memory, enqueued on a HIP stream: width*height RGBA8 words at `dev_rgba` and / or width*height*3
+    /// doubles at `dev_rgb` (either may be null, not both); `dev_offsets` may be null
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of those sizes (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn capture_rays_device(&self, dev_rays: *const f64, pixels: usize, samples: u32, dev_offsets: *const u64, width: u32, height: u32,
+                                      dev_rgba: *mut std::ffi::c_void, dev_rgb: *mut f64, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_capture_rays_device(self.ptr, dev_rays, pixels, samples, dev_offsets, width, height, dev_rgba, dev_rgb, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
     }
     /// The order a query's rays are walked in: false (default) as given, true sorted on the device by a coherence key -- for rays that
     /// arrive in no particular order; the sort is part of every query's time.  The answers are the same bytes either way.

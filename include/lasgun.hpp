@@ -175,6 +175,19 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         if (lg_radiance(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
         return out;
     }
+    // a film from the caller's rays (lg_capture_rays): pixel slot g's rays are [g*samples, (g+1)*samples), summed in that order, scaled by
+    // 1 / samples, quantised and written at film offset offsets[g] (y*width + x), or g without offsets; *rgb (if asked for): width*height
+    // f64 RGB before quantisation, addressed like the film.  Pixels no slot names keep their bytes.
+    void capture_rays(const std::vector<std::array<double, 6>> &rays, uint32_t samples, Film &film, const std::vector<uint64_t> *offsets = nullptr,
+                      std::vector<std::array<double, 3>> *rgb = nullptr) const {
+        if (samples == 0 || rays.size() % samples) throw Error("capture_rays: pixel slots * samples rays");
+        const size_t slots = rays.size() / samples;
+        if (offsets && offsets->size() != slots) throw Error("capture_rays: one offset per pixel slot");
+        if (rgb) rgb->resize((size_t)film.w() * film.h());
+        if (lg_capture_rays(h_, rays.empty() ? nullptr : rays[0].data(), slots, samples, offsets ? offsets->data() : nullptr, film.handle(),
+                            rgb && !rgb->empty() ? (*rgb)[0].data() : nullptr, film.w(), film.h()))
+            throw Error(lg_last_error());
+    }
     // the order a query's rays are walked in (lg_accel_set_query_order): 0 as given (default), 1 sorted on the device by a coherence key
     void set_query_order(int order) const {
         if (lg_accel_set_query_order(h_, order)) throw Error(lg_last_error());
@@ -191,6 +204,24 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
   private:
     explicit Accel(lg_accel *a) : h_(a) {}
     lg_accel *h_;
+};
+
+// A lens camera the reference does not have (lg_lens, lg_lens_rays): an equirectangular panorama (kind 0) or an equidistant fisheye (kind 1)
+// around `origin`, its basis used as given.  rays(): width*height*samples_root^2 rays in the layout Accel::capture_rays takes, row-major
+// pixels -- or the pixel slots `offsets` names.
+struct Lens {
+    lg_lens c{};
+    Lens(int kind, Vec3 origin, Vec3 right, Vec3 up, Vec3 forward, double fov_deg = 180.0) {
+        c.kind = kind;
+        for (int i = 0; i < 3; ++i) { c.origin[i] = origin[i]; c.right[i] = right[i]; c.up[i] = up[i]; c.forward[i] = forward[i]; }
+        c.fov_deg = fov_deg;
+    }
+    std::vector<std::array<double, 6>> rays(uint32_t width, uint32_t height, uint32_t samples_root = 1, const std::vector<uint64_t> *offsets = nullptr) const {
+        const size_t slots = offsets ? offsets->size() : (size_t)width * height;
+        std::vector<std::array<double, 6>> out(slots * samples_root * samples_root);
+        if (lg_lens_rays(&c, width, height, samples_root, offsets ? offsets->data() : nullptr, slots, out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
+        return out;
+    }
 };
 
 // GPU-side counterpart of `scene.threads`: the devices capture() / render() split a host film over

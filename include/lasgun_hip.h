@@ -418,6 +418,68 @@ int lg_camera_rays(const lg_accel *, uint32_t width, uint32_t height, uint32_t x
 int lg_camera_rays_device(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
                           double *dev_rays, void *hip_stream);
 uint32_t lg_camera_samples(const lg_accel *); /* rays per pixel of lg_camera_rays: the camera's supersamples */
+/* Ray films: the caller's rays rendered into a film -- what a custom camera (a fisheye or panorama, a cube-map face, a second view of an
+ * accel) needs after lg_radiance: the reference's sample sum, its quantisation, and the bytes placed in a film, all on the device.
+ * rays: pixels * samples rays of 6 doubles as for lg_intersect, PIXEL-MAJOR: the rays of pixel slot g are [g*samples, (g+1)*samples), in
+ * the order they are summed.  Slot g is the film pixel at offset pixel_offsets[g] (offset = y*width + x), or g when pixel_offsets is NULL.
+ * A slot whose offset is >= width*height writes nothing (as a k behind the film is an empty subset for lg_capture_subsets); a pixel no
+ * slot names stays untouched, byte for byte; offsets are expected to be distinct -- with duplicates, which slot's value remains is
+ * unspecified.  (The indirection is what lets rays arrive in 8 x 8-tile order -- row-major shadow rays cost 1.28 x the tile order's,
+ * DESIGN.md section 3.7 --, a view be rendered a subset per call, and a crop be rendered at all.)
+ * The pixel's value is integrate()'s (integrate.rs:16-20): color = Color::zero(); color = color + li(ray_s) for s = 0 .. samples-1 in that
+ * order; color * (1.0 / (double)samples); then per channel to_byte (img.rs:65-67) with A = 255 into the RGBA8 film, and / or the three
+ * doubles before quantisation into rgb (width*height*3 doubles, addressed like the film).  At least one output is required.  For the
+ * scene's own camera -- lg_camera_rays, samples = lg_camera_samples -- that is lg_capture's film and lg_capture_radiance's doubles, bit
+ * for bit.
+ * Everything else is lg_radiance's contract: the accel's traversal mode, always the level-by-level pipeline whatever lg_accel_set_streaming
+ * says, LASGUN_WF_BUDGET_MB chunks, lg_accel_set_query_order(1) honoured (it sorts rays, not pixels: a pixel's samples may be walked in
+ * different chunks), MORE THAN 32 LIGHTS or a recursion depth of 20 or more an error before any launch.  samples == 1: a ray is finished
+ * where lg_radiance finishes it, as one 4-byte store and / or three doubles at its pixel -- no parked radiance, no second pass.
+ * samples > 1: every ray's li is parked in library scratch (24 bytes a ray, indexed by the ray, so neither chunk boundaries nor the
+ * sorted order matter), then one resolve pass, a lane per slot, sums, scales, quantises and writes.
+ * pixels == 0 is a successful no-op.  Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel or rays,
+ * samples == 0, both outputs NULL, pixels * samples beyond what lg_radiance accepts, a film that is not width x height (host form).
+ * Host form (synchronous): copies the rays to the device and copies back ONLY the named slots' pixels -- pixels * 4 and / or pixels * 24
+ * bytes, compact -- which the host then places at their offsets; the film is never uploaded and never downloaded whole.
+ * Device form: only enqueues on hip_stream.  dev_rays (pixels*samples*6 doubles), dev_pixel_offsets (pixels uint64, may be NULL), dev_rgba
+ * (width*height*4 bytes, may be NULL) and dev_rgb (width*height*3 doubles, may be NULL) must be device memory of the accel's device,
+ * dev_rays / dev_pixel_offsets / dev_rgb 8-byte aligned and dev_rgba 4-byte aligned: checked before anything is enqueued.  The one
+ * exception is the other queries': the first call of a stream, or of a larger size, may grow scratch after a device-wide synchronise.
+ * One stream at a time per accel.  No counterpart in the reference. */
+int lg_capture_rays(const lg_accel *, const double *rays, size_t pixels, uint32_t samples, const uint64_t *pixel_offsets, lg_film *film,
+                    double *rgb, uint32_t width, uint32_t height);
+int lg_capture_rays_device(const lg_accel *, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_pixel_offsets,
+                           uint32_t width, uint32_t height, void *dev_rgba, double *dev_rgb, void *hip_stream);
+/* Lens rays: the rays of two cameras the reference does not have, generated on the device in the layout lg_capture_rays takes.  An EXTRA:
+ * every expression below is this library's own, nothing of the reference is mirrored. */
+typedef struct lg_lens {
+    int32_t kind;        /* 0 equirectangular panorama, 1 equidistant fisheye */
+    int32_t reserved;    /* 0 */
+    double origin[3], right[3], up[3], forward[3]; /* used as given: not normalised, not orthogonalised */
+    double fov_deg;      /* kind 1: the full angle across the film's shorter side; kind 0: ignored */
+} lg_lens;               /* 112 bytes, no padding */
+/* Pixel slot g is the film pixel at offset pixel_offsets[g] (y*width + x), or g when pixel_offsets is NULL -- then pixels must be
+ * width*height.  Per slot S = samples_root^2 rays, sample idx = i*samples_root + j at
+ *   u = ((double)x + ((double)j + 0.5) / (double)samples_root) / (double)width,
+ *   v = ((double)y + ((double)i + 0.5) / (double)samples_root) / (double)height;
+ * rays is pixels * S * 6 doubles, slot-major, a slot's samples in idx order.  The origin is lens.origin, exactly.  A slot whose offset
+ * is >= width*height gets origin and direction all zero (lg_capture_rays writes nothing for such a slot: offsets and rays line up).
+ * The direction, in f64 with no contraction, sin / cos / atan2 the device's correctly rounded ones (the render's own, trig.h), evaluated
+ * in exactly this order, per component c of the basis vectors:
+ *   kind 0:  phi = (u - 0.5) * 6.283185307179586;  theta = (0.5 - v) * 3.141592653589793;
+ *            d_c = (((cos theta * sin phi) * right_c) + (sin theta * up_c)) + ((cos theta * cos phi) * forward_c)
+ *   kind 1:  m = min(width, height);  a = (2.0 * u - 1.0) * ((double)width / (double)m);  b = (1.0 - 2.0 * v) * ((double)height / (double)m);
+ *            r = sqrt(a * a + b * b);  psi = atan2(b, a);  theta = r * ((fov_deg * 0.5) * 0.017453292519943295);
+ *            d_c = (sin theta * ((cos psi * right_c) + (sin psi * up_c))) + (cos theta * forward_c)
+ *            -- the formula continues outside the image circle; there are no special cases.
+ * Errors: a NULL lens or rays, a kind other than 0 / 1, reserved != 0, an empty film, samples_root == 0, pixels != width*height without
+ * offsets.  pixels == 0 is a successful no-op.  Host form: runs the same kernel on the current device (lg_set_device) and copies the rays
+ * back; synchronous.  Device form: only enqueues on hip_stream of `device`; dev_rays and dev_pixel_offsets must be 8-byte aligned device
+ * memory of that device, checked before the launch. */
+int lg_lens_rays(const lg_lens *, uint32_t width, uint32_t height, uint32_t samples_root, const uint64_t *pixel_offsets, size_t pixels,
+                 double *rays);
+int lg_lens_rays_device(int device, const lg_lens *, uint32_t width, uint32_t height, uint32_t samples_root,
+                        const uint64_t *dev_pixel_offsets, size_t pixels, double *dev_rays, void *hip_stream);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.
  * Results are identical bytes either way, in the caller's order. Any other value: non-zero return, lg_last_error.
  * The walk keeps a wave's 64 rays in step; rays that arrive in no particular order (collision probes, visibility between arbitrary

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, CLens  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -88,6 +88,7 @@ _EXTRA = {
     "accel_instance": (_C.c_int, [_C.c_void_p, _C.c_uint32, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int64)]),
     **QUERY_ORDER_SIGNATURES,
     **RADIANCE_SIGNATURES,
+    **RAY_FILM_SIGNATURES,
 }
 
 
@@ -98,6 +99,25 @@ class Hit(_C.Structure):  # lg_hit (include/lasgun_hip.h): one closest hit of a 
 
 HIT_DTYPE = _np.dtype(Hit)  # the numpy mirror of lg_hit: what HipApi.intersect returns
 assert _C.sizeof(Hit) == 96 and HIT_DTYPE.itemsize == 96, "lg_hit is 96 bytes"
+LENS_EQUIRECTANGULAR, LENS_FISHEYE = 0, 1  # lg_lens::kind
+assert _C.sizeof(CLens) == 112, "lg_lens is 112 bytes"
+
+
+def Lens(kind, origin, right, up, forward, fov_deg=180.0):
+    """An lg_lens: kind LENS_EQUIRECTANGULAR or LENS_FISHEYE, a basis used as given, and (fisheye) the full angle across the shorter side."""
+    three = lambda v: (_C.c_double * 3)(*[float(c) for c in v])  # noqa: E731
+    return CLens(int(kind), 0, three(origin), three(right), three(up), three(forward), float(fov_deg))
+
+
+def tile_order_offsets(w, h, tile=8):
+    """The film offsets y*w + x of every pixel of a w x h film in tile x tile-tile order (tiles row-major, pixels row-major inside a tile):
+    the order in which neighbouring rays share a wave (uint64, w*h of them)."""
+    ys, xs = _np.meshgrid(_np.arange(h, dtype=_np.uint64), _np.arange(w, dtype=_np.uint64), indexing="ij")
+    t = _np.uint64(tile)
+    key = ((ys // t) * _np.uint64((w + tile - 1) // tile) + xs // t) * (t * t) + (ys % t) * t + xs % t
+    return (ys * _np.uint64(w) + xs).ravel()[_np.argsort(key.ravel(), kind="stable")].astype(_np.uint64)
+
+
 HIT_NONE, HIT_SPHERE, HIT_BOX, HIT_TRIANGLE = 0, 1, 2, 3  # lg_hit::kind
 
 
@@ -484,6 +504,69 @@ class HipApi(Api):
         """Enqueue the radiance of n rays (device memory, 6 doubles each) into 3 n doubles at out_ptr (both 8-byte aligned)."""
         if self.call("radiance_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(out_ptr)), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
+
+    # ---- ray films (include/lasgun_hip.h, lg_capture_rays* / lg_lens_rays*): a film from the caller's rays
+    def capture_rays(self, accel, rays, w, h, samples=1, offsets=None, rgba=True, rgb=False, into=None):
+        """The film of (slots * samples, 6) float64 rays, slot-major: slot g's rays are summed in order, scaled by 1 / samples and written at
+        film offset offsets[g] (or g).  Returns the (h, w, 4) uint8 film and / or the (h, w, 3) float64 radiance asked for (both: a pair).
+        `into` = (film array or None, rgb array or None): C-contiguous buffers written in place -- pixels no slot names keep their bytes."""
+        r = self._rays(rays)
+        samples = int(samples)
+        if samples <= 0 or r.shape[0] % samples:
+            raise ValueError("rays: slots * samples of them")
+        slots = r.shape[0] // samples
+        off = None if offsets is None else _np.ascontiguousarray(offsets, dtype=_np.uint64)
+        if off is not None and off.shape != (slots,):
+            raise ValueError("offsets: one per pixel slot")
+        out_a, out_d = into if into is not None else (_np.zeros((h, w, 4), dtype=_np.uint8) if rgba else None,
+                                                      _np.zeros((h, w, 3), dtype=_np.float64) if rgb else None)
+        film = self.Film.new_with_output(w, h, out_a) if out_a is not None else None
+        if self.call("capture_rays", accel.h, r.ctypes.data, slots, samples, off.ctypes.data if off is not None else None, film.h if film else None,
+                     out_d.ctypes.data if out_d is not None else None, int(w), int(h)):
+            raise LasgunError(self.last_error())
+        if out_a is not None and out_d is not None:
+            return out_a, out_d
+        return out_a if out_a is not None else out_d
+
+    def capture_rays_device(self, accel, slots, rays_ptr, w, h, samples=1, offsets_ptr=None, rgba_ptr=None, rgb_ptr=None, stream=None):
+        """Enqueue the film of slots * samples rays (device memory) into w*h RGBA8 words at rgba_ptr and / or w*h*3 doubles at rgb_ptr;
+        offsets_ptr: slots uint64 film offsets in device memory, or None."""
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        if self.call("capture_rays_device", accel.h, ptr(rays_ptr), int(slots), int(samples), ptr(offsets_ptr), int(w), int(h), ptr(rgba_ptr), ptr(rgb_ptr),
+                     self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def lens_rays(self, lens, w, h, samples_root=1, offsets=None):
+        """The rays of a Lens over a w x h film (or over the pixel slots `offsets` names): (slots * samples_root^2, 6) float64, slot-major."""
+        off = None if offsets is None else _np.ascontiguousarray(offsets, dtype=_np.uint64)
+        slots = w * h if off is None else off.shape[0]
+        out = _np.zeros((slots * samples_root * samples_root, 6), dtype=_np.float64)
+        if self.call("lens_rays", _C.addressof(lens), int(w), int(h), int(samples_root), off.ctypes.data if off is not None else None, slots,
+                     out.ctypes.data if out.size else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def lens_rays_device(self, device, lens, w, h, samples_root, slots, rays_ptr, offsets_ptr=None, stream=0):
+        """Enqueue the same rays into device memory of `device` on `stream` (0 = HIP's default stream)."""
+        if self.call("lens_rays_device", int(device), _C.addressof(lens), int(w), int(h), int(samples_root),
+                     _C.c_void_p(int(offsets_ptr)) if offsets_ptr is not None else None, int(slots), _C.c_void_p(int(rays_ptr)), _C.c_void_p(int(stream))):
+            raise LasgunError(self.last_error())
+
+    def capture_lens(self, accel, lens, w, h, samples_root=1, tile_order=True):
+        """A Lens's picture of the accel's scene: its rays generated on the device into a torch buffer (8 x 8-tile order by default: the order
+        in which a wave's rays are neighbours) and rendered by capture_rays_device.  Returns the (h, w, 4) uint8 film."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        slots, S = w * h, samples_root * samples_root
+        offs = torch.from_numpy(tile_order_offsets(w, h).view(_np.int64)).to(dev) if tile_order else None
+        rays = torch.empty(slots * S * 6, dtype=torch.float64, device=dev)
+        film = torch.zeros(slots * 4, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        optr = offs.data_ptr() if offs is not None else None
+        self.lens_rays_device(dev.index, lens, w, h, samples_root, slots, rays.data_ptr(), optr, stream=stream)
+        self.capture_rays_device(accel, slots, rays.data_ptr(), w, h, samples=S, offsets_ptr=optr, rgba_ptr=film.data_ptr(), stream=stream)
+        torch.cuda.current_stream().synchronize()
+        return film.cpu().numpy().reshape(h, w, 4)
 
     def set_query_order(self, accel, order):
         """The order a query's rays are walked in: 0 as given (default), 1 sorted on the device by a coherence key -- for rays that arrive

@@ -129,6 +129,20 @@ RADIANCE_SIGNATURES = {
     "radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# Ray films and lens rays (include/lasgun_hip.h, lg_capture_rays* / lg_lens_rays*): a film from the caller's rays; the GPU library's alone.
+RAY_FILM_SIGNATURES = {
+    "capture_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "capture_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "lens_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lens_rays_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
+
+class CLens(C.Structure):  # lg_lens: 112 bytes, no padding
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("origin", _D3), ("right", _D3), ("up", _D3), ("forward", _D3),
+                ("fov_deg", C.c_double)]
+
 
 class Api:
     """One bound C ABI: `Api(ctypes.CDLL(path), "lg_")`."""

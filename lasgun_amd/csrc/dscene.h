@@ -341,5 +341,21 @@ struct RadianceArgs {
     unsigned long long n;      // rays of the query
     unsigned long long base;   // the chunk's first slot: work item i of the chunk is slot base + i
 };
+// A ray film's level 0 (k_radiance.hip, the film forms; lg_capture_rays*): the same query with ONE ray per pixel slot, finished into a
+// film instead of radiance[] -- ray r is pixel slot r, written at film offset offsets[r] (or r) unless that lies behind the film.
+// (`radiance` is not used by these forms.)  The resolve pass of a film of several samples per slot takes the last four fields alone.
+struct FilmArgs : RadianceArgs {
+    const unsigned long long *offsets; // [slots]: y*width + x of each pixel slot; nullptr: slot g is offset g
+    unsigned long long npix;           // width * height: a slot whose offset is >= npix writes nothing
+    uint32_t *rgba;                    // RGBA8 film, one word per pixel (A = 255); may be nullptr
+    double *rgb;                       // f64 RGB before quantisation, 3 per pixel; may be nullptr
+};
+
+// A lens camera (k_lens.hip; include/lasgun_hip.h, lg_lens -- the same 112 bytes)
+struct DLens {
+    int32_t kind, reserved;          // 0 equirectangular panorama, 1 equidistant fisheye
+    V3 origin, right, up, forward;   // used as given
+    double fov_deg;                  // kind 1: the full angle across the film's shorter side
+};
 
 } // namespace lg

@@ -51,7 +51,15 @@ hipError_t launch_wf_resolve(const DParams &P, uint32_t blocks, hipStream_t stre
 hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rq_combine(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream);
+// ... and its film forms (lg_capture_rays*): one ray per pixel slot finished into a film; the resolve pass of several samples per slot
+hipError_t launch_rf_closest(const DParams &P, const FilmArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream);
 hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
+// k_lens.hip: the rays of a lens camera (lg_lens_rays*)
+hipError_t launch_lens_rays(const DLens &L, uint32_t w, uint32_t h, uint32_t root, const unsigned long long *offsets, unsigned long long n, double *rays,
+                            uint32_t blocks, hipStream_t stream);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t queue_occupancy(uint32_t stack_depth, size_t extra_lds, int *blocks_per_cu);
@@ -355,6 +363,7 @@ struct lg_accel {
         DevBuf<double> frames, stash;                          // megakernel: Whitted frame stack, parked shading frame
         DevBuf<uint8_t> wf_mem;                                // wavefront pipeline: every per-level array of a chunk, carved from one allocation
         DevBuf<uint32_t> wf_counters;                          // its queue counts and per-launch tile counters
+        DevBuf<double> film_li;                                // ray films of several samples per pixel (lg_capture_rays*): every ray's li, 24 bytes a ray, until the resolve pass; grown on demand
         DevBuf<uint8_t> sort_mem;                              // ray queries in sorted order (k_sort.hip): ping-pong keys and indices, histograms; grown on demand
         // strided subsets by lattice column (shade.h, modes 4 / 5): (floor(y*w / n), (y*w) mod n) per film row -- one table per (w, h, n), the
         // last MAX_ROW_TABLES of them kept (a caller that alternates periods or films on one stream finds each again), each uploaded from
@@ -452,6 +461,8 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
+void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
+                      hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

@@ -32,85 +32,36 @@ __device__ __forceinline__ void rq_finish(const RadianceArgs &Q, unsigned long l
     double *o = Q.radiance + 3ull * r;
     o[0] = color.x; o[1] = color.y; o[2] = color.z;
 }
+// ... and into a film (FilmArgs): the ray is pixel slot r of one sample, the same value as one RGBA8 word (to_byte per channel, A = 255;
+// img.rs:46-67, as write_pixel) and / or three doubles at the slot's film offset.  A slot whose offset lies behind the film writes nothing.
+__device__ __forceinline__ void film_store(const FilmArgs &Q, unsigned long long off, V3 color) {
+    if (Q.rgba) Q.rgba[off] = to_byte(color.x) | (to_byte(color.y) << 8) | (to_byte(color.z) << 16) | (255u << 24);
+    if (Q.rgb) {
+        double *o = Q.rgb + 3ull * off;
+        o[0] = color.x; o[1] = color.y; o[2] = color.z;
+    }
+}
+__device__ __forceinline__ void rq_finish(const FilmArgs &Q, unsigned long long r, V3 value) {
+    const unsigned long long off = Q.offsets ? Q.offsets[r] : r;
+    if (off >= Q.npix) return;
+    film_store(Q, off, (vzero() + value) * 1.0);
+}
 
-// W1 of level 0 (wf_trace_kernel<FAST, false, LDSS, true, PRUNE>)
+// W1 of level 0 (wf_trace_kernel<FAST, false, LDSS, true, PRUNE>): rq_closest_body.h, into radiance[] (rq_) or into a film (rf_)
 template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) rq_closest_kernel(const DParams P, const RadianceArgs Q) {
-    static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
-    static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads(); // the only workgroup-wide step; every wave reaches it before pulling tiles
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
-    Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
-    for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
-        if (tile == NO_TILE) break;
-        const unsigned long long i = (unsigned long long)tile * 64ull + lane; // the chunk's work item: index of level 0's arrays
-        const bool active = Q.base + i < Q.n;
-        unsigned long long r = 0;
-        Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
-        if (active) {
-            r = rq_ray_index<PERM>(Q, Q.base + i);
-            ray = rq_load_ray(Q, r);
-        }
-        Best b;
-        b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
-        if (active) walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
-        const bool hit = active && b.ref != NO_HIT;
-        // ---- this wave's slots in the level's hit queue (wflevel.h: dense where most lanes hit, appended otherwise)
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-        const uint32_t nhit = (uint32_t)__builtin_popcountll(mask);
-        unsigned long long h = i;
-        if (nhit < WF_FULL_MIN) {
-            P.wf_hq[i] = WF_NONE; // (every lane stands for slot i of the dense part, a ray or a slot past the last ray: the chunk's arrays hold whole tiles)
-            if (nhit != 0u) {
-                uint32_t base_v = 0u;
-                if (lane == 0u) base_v = atomicAdd(P.wf_counts + P.wf_levels, nhit);
-                h = P.wf_hit_cap + (uint32_t)__builtin_amdgcn_readfirstlane((int)base_v) + lanes_below(mask);
-            }
-        } else if (!hit) P.wf_hq[i] = WF_NONE; // a hole of a dense block
-        if (hit) {
-            P.wf_hq[h] = (uint32_t)i;
-            Shade sh;
-            shade_frame(P, ray, b, sh);
-            const unsigned long long n = P.wf_hit_stride;
-            double *f = P.frame + h;
-            f[0 * n] = sh.praw.x; f[1 * n] = sh.praw.y; f[2 * n] = sh.praw.z;
-            f[3 * n] = sh.ng.x; f[4 * n] = sh.ng.y; f[5 * n] = sh.ng.z;
-            f[6 * n] = sh.ns.x; f[7 * n] = sh.ns.y; f[8 * n] = sh.ns.z;
-            f[9 * n] = sh.ss.x; f[10 * n] = sh.ss.y; f[11 * n] = sh.ss.z;
-            f[12 * n] = (double)sh.mat;
-        } else if (active) { // integrate.rs:26-28
-            const V3 value = background(P, normalize(ray.d));
-            if (P.wf_levels == 1u) rq_finish(Q, r, value);
-            else {
-                const unsigned long long n = P.wf_cap;
-                P.wf_out[i] = value.x; P.wf_out[n + i] = value.y; P.wf_out[2 * n + i] = value.z;
-                P.wf_child[i] = WF_MISS;
-            }
-        }
-    }
+#include "rq_closest_body.h"
+}
+template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
+__global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) rf_closest_kernel(const DParams P, const FilmArgs Q) {
+#include "rq_closest_body.h"
 }
 
 // W3 of level 0 (wf_shade_kernel<KIND, true>).  KIND 0: the scene has no recursion at all, li = output + 0 + 0 is the ray's radiance;
 // KIND 1: there is a level below, the specular children are appended to its ray queue (integrate.rs:69-77).
 // The grid covers the chunk's dense tiles AND the most hits that can be appended behind them, one wave per tile, no loop.
-template <int KIND, bool PERM>
-__global__ void __launch_bounds__(LG_BLOCK, 3) rq_shade_kernel(const DParams P, const RadianceArgs Q) {
+template <int KIND, bool PERM, class ARGS>
+__device__ __forceinline__ void rq_shade_body(const DParams &P, const ARGS &Q) {
     const HitSlots hs = hit_slots(P, 0u, 64u);
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const unsigned long long t = (unsigned long long)blockIdx.x * (LG_BLOCK / 64u) + wave;
@@ -174,10 +125,12 @@ __global__ void __launch_bounds__(LG_BLOCK, 3) rq_shade_kernel(const DParams P, 
         q[0 * nn] = sh.pm.x; q[1 * nn] = sh.pm.y; q[2 * nn] = sh.pm.z; q[3 * nn] = st.wi.x; q[4 * nn] = st.wi.y; q[5 * nn] = st.wi.z;
     }
 }
+template <int KIND, bool PERM> __global__ void __launch_bounds__(LG_BLOCK, 3) rq_shade_kernel(const DParams P, const RadianceArgs Q) { rq_shade_body<KIND, PERM>(P, Q); }
+template <int KIND, bool PERM> __global__ void __launch_bounds__(LG_BLOCK, 3) rf_shade_kernel(const DParams P, const FilmArgs Q) { rq_shade_body<KIND, PERM>(P, Q); }
 
 // W4 of level 0 (wf_combine_kernel at level 0): li of the query's rays from their children's (integrate.rs:79, 103, 129), finished
-template <bool PERM>
-__global__ void __launch_bounds__(LG_BLOCK) rq_combine_kernel(const DParams P, const RadianceArgs Q) {
+template <bool PERM, class ARGS>
+__device__ __forceinline__ void rq_combine_body(const DParams &P, const ARGS &Q) {
     const unsigned long long n_work = (unsigned long long)P.ntiles * 64ull;
     const unsigned long long n = P.wf_cap, nn = P.wf_cap_next;
     for (unsigned long long j = (unsigned long long)blockIdx.x * LG_BLOCK + threadIdx.x; j < n_work; j += (unsigned long long)gridDim.x * LG_BLOCK) {
@@ -201,21 +154,51 @@ __global__ void __launch_bounds__(LG_BLOCK) rq_combine_kernel(const DParams P, c
         rq_finish(Q, rq_ray_index<PERM>(Q, Q.base + j), value);
     }
 }
+template <bool PERM> __global__ void __launch_bounds__(LG_BLOCK) rq_combine_kernel(const DParams P, const RadianceArgs Q) { rq_combine_body<PERM>(P, Q); }
+template <bool PERM> __global__ void __launch_bounds__(LG_BLOCK) rf_combine_kernel(const DParams P, const FilmArgs Q) { rq_combine_body<PERM>(P, Q); }
+
+// The resolve pass of a ray film of several samples per pixel slot (lg_capture_rays*, samples > 1): every ray's li is parked ray-indexed
+// in `li` by the radiance forms above -- so neither the chunks' boundaries nor the sorted order touch it --, and one lane per slot g sums
+// li[g*S .. g*S+S) in that order from zero, scales by 1 / S and writes the pixel: integrate.rs:16-20, as wf_resolve_kernel does it.
+// (A parked value is (0 + li) * 1: the sum from zero gives the same bits from it as from li itself.)
+__global__ void __launch_bounds__(LG_BLOCK) rf_resolve_kernel(const FilmArgs Q, const double *li, unsigned long long slots, uint32_t S) {
+    const double weight = 1. / (double)S;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * LG_BLOCK + threadIdx.x; g < slots; g += (unsigned long long)gridDim.x * LG_BLOCK) {
+        const unsigned long long off = Q.offsets ? Q.offsets[g] : g;
+        if (off >= Q.npix) continue;
+        const double *p = li + 3ull * (g * S);
+        V3 color = vzero();
+        for (uint32_t s = 0; s < S; ++s, p += 3) color = color + V3{p[0], p[1], p[2]};
+        film_store(Q, off, color * weight);
+    }
+}
 
 // ---- host-callable launchers (launch.cpp, enqueue_radiance).  The closest pass in the (FAST, LDSS, PRUNE) forms of wf_trace_kernel, its
-// LDS sized as launch_wf_trace sizes it; Q.perm != nullptr: the PERM forms
-hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+// LDS sized as launch_wf_trace sizes it; Q.perm != nullptr: the PERM forms.  A RadianceArgs launches the rq_ kernels, a FilmArgs the rf_ ones.
+template <bool F, bool L, bool Z, bool PERM> static void rq_launch_closest(const DParams &P, const RadianceArgs &Q, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, PERM>), dim3(blocks), dim3(block), lds, stream, P, Q);
+}
+template <bool F, bool L, bool Z, bool PERM> static void rq_launch_closest(const DParams &P, const FilmArgs &Q, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL((rf_closest_kernel<F, L, Z, PERM>), dim3(blocks), dim3(block), lds, stream, P, Q);
+}
+template <class ARGS> static hipError_t launch_closest_of(const DParams &P, const ARGS &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
     const bool ldss = P.lds_image && !fast;
     const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
     const uint32_t depth = fast ? stack_depth : P.stack_depth;
     const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_RQ(F, L, Z) do { if (Q.perm) hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, true>), dim3(blocks), dim3(block), lds, stream, P, Q); \
-                            else hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, false>), dim3(blocks), dim3(block), lds, stream, P, Q); } while (0)
+#define LG_RQ(F, L, Z) do { if (Q.perm) rq_launch_closest<F, L, Z, true>(P, Q, blocks, block, lds, stream); \
+                            else rq_launch_closest<F, L, Z, false>(P, Q, blocks, block, lds, stream); } while (0)
     if (fast) LG_RQ(true, false, false);
     else if (P.prune) { if (ldss) LG_RQ(false, true, true); else LG_RQ(false, false, true); }
     else { if (ldss) LG_RQ(false, true, false); else LG_RQ(false, false, false); }
 #undef LG_RQ
     return hipGetLastError();
+}
+hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    return launch_closest_of(P, Q, fast, blocks, stack_depth, stream);
+}
+hipError_t launch_rf_closest(const DParams &P, const FilmArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    return launch_closest_of(P, Q, fast, blocks, stack_depth, stream);
 }
 hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
     if (P.wf_levels == 1u) {
@@ -227,14 +210,34 @@ hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blo
     }
     return hipGetLastError();
 }
+hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream) {
+    if (P.wf_levels == 1u) {
+        if (Q.perm) hipLaunchKernelGGL((rf_shade_kernel<0, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+        else hipLaunchKernelGGL((rf_shade_kernel<0, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    } else {
+        if (Q.perm) hipLaunchKernelGGL((rf_shade_kernel<1, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+        else hipLaunchKernelGGL((rf_shade_kernel<1, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    }
+    return hipGetLastError();
+}
 hipError_t launch_rq_combine(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
     if (Q.perm) hipLaunchKernelGGL((rq_combine_kernel<true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
     else hipLaunchKernelGGL((rq_combine_kernel<false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
     return hipGetLastError();
 }
+hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream) {
+    if (Q.perm) hipLaunchKernelGGL((rf_combine_kernel<true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    else hipLaunchKernelGGL((rf_combine_kernel<false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
+    return hipGetLastError();
+}
+hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(rf_resolve_kernel, dim3(blocks), dim3(LG_BLOCK), 0, stream, Q, li, slots, samples);
+    return hipGetLastError();
+}
 // raise the dynamic-LDS limit of the closest pass to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
 template <bool FAST, bool LDSS, bool PRUNE> static hipError_t rq_lds_limit_of(int bytes) {
-    const void *fns[] = {reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, true>)};
+    const void *fns[] = {reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, true>),
+                         reinterpret_cast<const void *>(rf_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rf_closest_kernel<FAST, LDSS, PRUNE, true>)};
     for (const void *f : fns) {
         const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         if (e != hipSuccess) return e;

@@ -191,14 +191,15 @@ struct ChunkPlan {
 
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
 // (`rq`: the launch is a radiance query's -- its level 0 is k_radiance.hip's)
-static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr) {
+static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr) {
     const unsigned long long n0 = plan.n0();
     const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull), flat_cap = a.cus * 16u; // (level 0: one thread per work item)
     for (uint32_t d = plan.levels - 1; d-- > 0;) {
         P.wf_level = d;
         P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
         P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-        if (d == 0 && rq) timed(a, 1, s, [&] { return launch_rq_combine(P, *rq, flat_blocks0, s); });
+        if (d == 0 && rf) timed(a, 1, s, [&] { return launch_rf_combine(P, *rf, flat_blocks0, s); });
+        else if (d == 0 && rq) timed(a, 1, s, [&] { return launch_rq_combine(P, *rq, flat_blocks0, s); });
         else timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
     }
 }
@@ -246,8 +247,8 @@ struct WfChunk {
         }
     }
     // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
-    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's.
-    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr) const {
+    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms).
+    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr) const {
         const bool ldss = P.lds_image != nullptr;
         const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
         const uint32_t trace_cap = ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks), flat_cap = a.cus * 16u;
@@ -269,19 +270,21 @@ struct WfChunk {
             // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
             // every deeper level may exceed only in waves, never in work per wave)
             const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
-            const bool rq0 = rq && d == 0;
+            const bool rq0 = rq && d == 0, rf0 = rf && d == 0;
             level_params(d);
-            if (rq0) timed(a, 0, ls, [&] { return launch_rq_closest(P, *rq, a.fast, tb, depth, ls); });
+            if (rf0) timed(a, 0, ls, [&] { return launch_rf_closest(P, *rf, a.fast, tb, depth, ls); });
+            else if (rq0) timed(a, 0, ls, [&] { return launch_rq_closest(P, *rq, a.fast, tb, depth, ls); });
             else timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
             if (P.nlights > 0) {
                 level_params(d);
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
             }
             level_params(d);
-            if (rq0) timed(a, 3, ls, [&] { return launch_rq_shade(P, *rq, fb, ls); });
+            if (rf0) timed(a, 3, ls, [&] { return launch_rf_shade(P, *rf, fb, ls); });
+            else if (rq0) timed(a, 3, ls, [&] { return launch_rq_shade(P, *rq, fb, ls); });
             else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
-        combine_levels(a, P, L, plan, ls, rq);
+        combine_levels(a, P, L, plan, ls, rq, rf);
     }
 };
 
@@ -364,7 +367,11 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
 // whatever the scene's camera supersamples; always this organisation, whatever lg_accel_set_streaming says: nothing is measured or
 // remembered for it.  Caller holds a.mtx, has made the accel's device current and has checked the buffers and that the scene can go
 // level by level (radiance_possible).
-void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
+// `film` (lg_capture_rays* of one sample per pixel slot): ray r is pixel slot r and level 0 finishes it into the film (FilmArgs) instead of
+// radiance[] -- the same chunks, the same launches with the film forms of the three level-0 kernels in place of the radiance forms.
+// `label` / `tail`: what LASGUN_DEBUG calls the query, and what is enqueued behind its chunks inside the profiled span (a film's resolve pass).
+static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n, double *radiance, const FilmArgs *film, const uint32_t *perm, lg_accel::LaunchCtx &c,
+                                 hipStream_t stream, const char *label, const std::function<void()> &tail = nullptr) {
     DParams P0 = base_params(a, 1, 1);
     P0.ss_root = 1; // (the scene's camera may be supersampled; a query is not)
     P0.ntiles = (uint32_t)((n + 63) / 64);
@@ -377,8 +384,8 @@ void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *r
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
     if (std::getenv("LASGUN_DEBUG"))
-        std::fprintf(stderr, "[lasgun] radiance query: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", levels, (unsigned long long)P0.ntiles, chunk_tiles,
-                     plan.need() / 1048576.0, perm ? "sorted order" : "as given");
+        std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", label, levels, (unsigned long long)P0.ntiles,
+                     chunk_tiles, plan.need() / 1048576.0, perm ? "sorted order" : "as given");
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
@@ -386,9 +393,35 @@ void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *r
         P.ss_par = 1u;
         K.params(a, P, ldss);
         const RadianceArgs Q{rays, radiance, perm, (unsigned long long)n, t0 * 64ull};
-        K.run(a, P, stream, &Q);
+        if (film) {
+            FilmArgs F = *film;
+            static_cast<RadianceArgs &>(F) = Q;
+            K.run(a, P, stream, &Q, &F);
+        } else K.run(a, P, stream, &Q);
     }
+    if (tail) tail();
     if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
+}
+void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    enqueue_level0_query(a, rays, n, radiance, nullptr, perm, c, stream, "radiance query");
+}
+// A ray film (query.cpp, lg_capture_rays*): `slots` pixel slots of `samples` rays each, slot g's rays [g*samples, (g+1)*samples), into
+// film.rgba / film.rgb at film.offsets[g] (or g).  One sample: the film forms of level 0 finish every ray where the radiance forms finish
+// it, as its pixel.  Several: every ray's li is parked RAY-INDEXED in the context's film_li (24 bytes a ray; the radiance forms write it) --
+// chunks are 64-ray tiles that a pixel's samples straddle (9 does not divide 64) and the sorted order scatters them, and neither
+// matters to an array indexed by the ray --, then one resolve pass, a lane per slot, sums them in order (k_radiance.hip,
+// rf_resolve_kernel; credited to lg_profile_read_kinds as a combine pass, kind 1, as the render's resolve is).  Growing film_li is the one
+// step that is more than an enqueue (a device-wide synchronise first, as for the level arrays).
+void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
+                      hipStream_t stream) {
+    const size_t n = slots * samples;
+    if (samples == 1) { enqueue_level0_query(a, rays, n, nullptr, &film, perm, c, stream, "ray film"); return; }
+    if (c.film_li.n < n * 3) { HIP_TRY(hipDeviceSynchronize()); c.film_li.alloc(n * 3); }
+    const double *li = c.film_li.p;
+    enqueue_level0_query(a, rays, n, c.film_li.p, nullptr, perm, c, stream, "ray film", [&] {
+        const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)slots + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
+        timed(a, 1, stream, [&] { return launch_rf_resolve(film, li, slots, samples, blocks, stream); });
+    });
 }
 
 // The queue organisation (k_queue.hip): per chunk of the film and per supersample ONE persistent launch that runs every recursion

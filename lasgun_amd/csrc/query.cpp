@@ -20,7 +20,7 @@ static constexpr size_t SORT_MIN_RAYS = 65;
 
 // A caller's device buffer: not NULL, aligned, device memory of the accel's device, and `bytes` long within its allocation -- checked
 // before anything is enqueued (a pageable host pointer or another device's memory would fault the card, not fail the call).
-static void check_device_buffer(const lg_accel &a, const void *p, size_t bytes, size_t align, const char *what) {
+static void check_device_buffer(int device, const void *p, size_t bytes, size_t align, const char *what) {
     if (!p) throw Error(std::string(what) + " is NULL");
     if ((uintptr_t)p % align) throw Error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
     hipPointerAttribute_t at{};
@@ -29,13 +29,14 @@ static void check_device_buffer(const lg_accel &a, const void *p, size_t bytes, 
         throw Error(std::string(what) + " is not device memory (hipPointerGetAttributes)");
     }
     if (at.type != hipMemoryTypeDevice) throw Error(std::string(what) + " is not device memory (hipPointerGetAttributes)");
-    if (at.device != a.device) throw Error(std::string(what) + " lives on device " + std::to_string(at.device) + ", the accel on device " + std::to_string(a.device));
+    if (at.device != device) throw Error(std::string(what) + " lives on device " + std::to_string(at.device) + ", the accel on device " + std::to_string(device));
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) == hipSuccess) {
         if ((const char *)p + bytes > (const char *)base + size) throw Error(std::string(what) + " ends beyond its allocation");
     } else (void)hipGetLastError();
 }
+static void check_device_buffer(const lg_accel &a, const void *p, size_t bytes, size_t align, const char *what) { check_device_buffer(a.device, p, bytes, align, what); }
 
 // The scene's world bounds for the key (raykey.h): the root accel's box, its corners taken to world space
 static KeyBounds world_key_bounds(const lg_accel &a) {
@@ -183,6 +184,107 @@ static int radiance_device(const lg_accel *a, const double *dev_rays, size_t n, 
     });
 }
 
+// ---- ray films: a film from the caller's rays (lg_capture_rays*; launch.cpp, enqueue_ray_film; k_radiance.hip, the film forms)
+// pixels * samples as a ray count lg_radiance accepts
+static size_t film_ray_count(const lg_accel &a, size_t pixels, uint32_t samples) {
+    if (samples == 0) throw Error("samples is 0: a pixel slot has at least one ray");
+    if (pixels > MAX_RAYS / samples) throw Error("too many rays in one query (pixels * samples)");
+    const size_t n = pixels * (size_t)samples;
+    if (a.query_order == 1 && n > MAX_SORTED_RAYS) throw Error("too many rays in one query for the sorted order (lg_accel_set_query_order): at most 2^32 - 1");
+    return n;
+}
+// One film query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the counts and the buffers)
+static void enqueue_film_query(const lg_accel &a, const double *rays, size_t pixels, uint32_t samples, const unsigned long long *offsets, unsigned long long npix,
+                               uint32_t *rgba, double *rgb, hipStream_t stream) {
+    check_queue_error(a);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const size_t n = pixels * (size_t)samples;
+    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
+    FilmArgs F{};
+    F.offsets = offsets; F.npix = npix; F.rgba = rgba; F.rgb = rgb;
+    enqueue_ray_film(a, rays, pixels, samples, F, perm, c, stream);
+}
+// Host form: the rays go up, the slots' pixels come back COMPACT (slot g at g: pixels * 4 and / or pixels * 24 bytes, nothing else is
+// copied) and are placed at their offsets here -- so a pixel no slot names is never touched, and a slot behind the film is dropped.
+static int capture_rays_host(const lg_accel *a, const double *rays, size_t pixels, uint32_t samples, const uint64_t *offsets, lg_film *film, double *rgb,
+                             uint32_t w, uint32_t h) {
+    return guarded([&] {
+        if (pixels == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (!rays) throw Error("rays is NULL");
+        if (!film && !rgb) throw Error("film and rgb are both NULL: at least one output");
+        if (film && (film->w != w || film->h != h)) throw Error("film is " + std::to_string(film->w) + " x " + std::to_string(film->h) + ", not width x height");
+        std::lock_guard<std::mutex> g(a->mtx);
+        const size_t n = film_ray_count(*a, pixels, samples);
+        radiance_possible(*a);
+        use_device(a->device);
+        const unsigned long long npix = (unsigned long long)w * h;
+        DevBuf<double> drays, drgb;
+        DevBuf<uint32_t> drgba;
+        drays.alloc(n * 6);
+        if (film) drgba.alloc(pixels);
+        if (rgb) drgb.alloc(pixels * 3);
+        std::vector<uint32_t> hrgba(film && offsets ? pixels : 0);
+        std::vector<double> hrgb(rgb && offsets ? pixels * 3 : 0);
+        const size_t direct = (size_t)std::min<unsigned long long>(pixels, npix); // no offsets: slot g is pixel g
+        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_film_query(*a, drays.p, pixels, samples, nullptr, pixels, film ? drgba.p : nullptr, rgb ? drgb.p : nullptr, a->stream);
+        if (film) HIP_TRY(hipMemcpyAsync(offsets ? (void *)hrgba.data() : (void *)film->px, drgba.p, (offsets ? pixels : direct) * 4, hipMemcpyDeviceToHost, a->stream));
+        if (rgb) HIP_TRY(hipMemcpyAsync(offsets ? hrgb.data() : rgb, drgb.p, (offsets ? pixels : direct) * 3 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+        if (!offsets) return;
+        for (size_t s = 0; s < pixels; ++s) {
+            const uint64_t off = offsets[s];
+            if (off >= npix) continue;
+            if (film) std::memcpy(film->px + 4 * off, &hrgba[s], 4);
+            if (rgb) std::memcpy(rgb + 3 * off, &hrgb[3 * s], 3 * sizeof(double));
+        }
+    });
+}
+static int capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_offsets, uint32_t w, uint32_t h,
+                               void *dev_rgba, double *dev_rgb, void *hip_stream) {
+    return guarded([&] {
+        if (pixels == 0) return;
+        if (!a) throw Error("accel is NULL");
+        if (!dev_rgba && !dev_rgb) throw Error("dev_rgba and dev_rgb are both NULL: at least one output");
+        std::lock_guard<std::mutex> g(a->mtx);
+        const size_t n = film_ray_count(*a, pixels, samples);
+        radiance_possible(*a);
+        use_device(a->device);
+        const unsigned long long npix = (unsigned long long)w * h;
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        if (dev_offsets) check_device_buffer(*a, dev_offsets, pixels * sizeof(uint64_t), 8, "pixel_offsets");
+        if (dev_rgba) check_device_buffer(*a, dev_rgba, npix * 4, 4, "rgba");
+        if (dev_rgb) check_device_buffer(*a, dev_rgb, npix * 3 * sizeof(double), 8, "rgb");
+        if (npix == 0) return; // an empty film: every slot lies behind it
+        enqueue_film_query(*a, dev_rays, pixels, samples, reinterpret_cast<const unsigned long long *>(dev_offsets), npix, reinterpret_cast<uint32_t *>(dev_rgba), dev_rgb,
+                           (hipStream_t)hip_stream);
+    });
+}
+
+// ---- lens rays (lg_lens_rays*; k_lens.hip)
+static_assert(sizeof(lg_lens) == 112 && sizeof(DLens) == 112 && offsetof(lg_lens, origin) == 8 && offsetof(lg_lens, right) == 32 && offsetof(lg_lens, up) == 56 &&
+                  offsetof(lg_lens, forward) == 80 && offsetof(lg_lens, fov_deg) == 104 && offsetof(DLens, fov_deg) == 104,
+              "lg_lens: 112 bytes, no padding, the layout k_lens.hip reads");
+static unsigned long long lens_ray_count(const lg_lens *lens, uint32_t w, uint32_t h, uint32_t root, const uint64_t *offsets, size_t pixels) {
+    if (!lens) throw Error("lens is NULL");
+    if (lens->kind != 0 && lens->kind != 1) throw Error("lens kind " + std::to_string(lens->kind) + ": 0 (equirectangular) or 1 (equidistant fisheye)");
+    if (lens->reserved != 0) throw Error("lens: reserved must be 0");
+    if (w == 0 || h == 0) throw Error("lens rays: an empty film");
+    if (root == 0) throw Error("samples_root is 0");
+    if (!offsets && pixels != (size_t)w * h) throw Error("lens rays: without pixel_offsets, pixels must be width * height");
+    const unsigned long long S = (unsigned long long)root * root;
+    if (pixels > MAX_RAYS / S) throw Error("too many lens rays (pixels * samples_root^2)");
+    return pixels * S;
+}
+static void enqueue_lens_rays(const lg_lens *lens, uint32_t w, uint32_t h, uint32_t root, const uint64_t *dev_offsets, unsigned long long n, double *dev_rays,
+                              hipStream_t stream) {
+    DLens L;
+    std::memcpy(&L, lens, sizeof L);
+    const uint32_t blocks = (uint32_t)std::min<unsigned long long>((n + 255) / 256, 16384ull);
+    HIP_TRY(launch_lens_rays(L, w, h, root, reinterpret_cast<const unsigned long long *>(dev_offsets), n, dev_rays, blocks, stream));
+}
+
 // the rectangle's rays: (x1-x0) * (y1-y0) * supersamples; 0 for an empty rectangle
 static unsigned long long camera_ray_count(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     if (w == 0 || h == 0 || x0 > x1 || y0 > y1 || x1 > w || y1 > h) throw Error("rectangle outside the film");
@@ -211,6 +313,40 @@ int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint
 int lg_radiance(const lg_accel *a, const double *rays, size_t n, double *radiance) { return radiance_host(a, rays, n, radiance); }
 int lg_radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
     return radiance_device(a, dev_rays, n, dev_radiance, hip_stream);
+}
+
+int lg_capture_rays(const lg_accel *a, const double *rays, size_t pixels, uint32_t samples, const uint64_t *pixel_offsets, lg_film *film, double *rgb, uint32_t width,
+                    uint32_t height) {
+    return capture_rays_host(a, rays, pixels, samples, pixel_offsets, film, rgb, width, height);
+}
+int lg_capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_pixel_offsets, uint32_t width, uint32_t height,
+                           void *dev_rgba, double *dev_rgb, void *hip_stream) {
+    return capture_rays_device(a, dev_rays, pixels, samples, dev_pixel_offsets, width, height, dev_rgba, dev_rgb, hip_stream);
+}
+int lg_lens_rays(const lg_lens *lens, uint32_t width, uint32_t height, uint32_t samples_root, const uint64_t *pixel_offsets, size_t pixels, double *rays) {
+    return guarded([&] {
+        if (pixels == 0) return;
+        const unsigned long long n = lens_ray_count(lens, width, height, samples_root, pixel_offsets, pixels);
+        if (!rays) throw Error("rays is NULL");
+        use_device();
+        DevBuf<double> d;
+        DevBuf<uint64_t> doff;
+        d.alloc(n * 6);
+        if (pixel_offsets) { doff.alloc(pixels); HIP_TRY(hipMemcpy(doff.p, pixel_offsets, pixels * sizeof(uint64_t), hipMemcpyHostToDevice)); }
+        enqueue_lens_rays(lens, width, height, samples_root, pixel_offsets ? doff.p : nullptr, n, d.p, nullptr);
+        HIP_TRY(hipMemcpy(rays, d.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost)); // (the default stream: the copy follows the kernel and blocks)
+    });
+}
+int lg_lens_rays_device(int device, const lg_lens *lens, uint32_t width, uint32_t height, uint32_t samples_root, const uint64_t *dev_pixel_offsets, size_t pixels,
+                        double *dev_rays, void *hip_stream) {
+    return guarded([&] {
+        if (pixels == 0) return;
+        const unsigned long long n = lens_ray_count(lens, width, height, samples_root, dev_pixel_offsets, pixels);
+        use_device(device);
+        check_device_buffer(device, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        if (dev_pixel_offsets) check_device_buffer(device, dev_pixel_offsets, pixels * sizeof(uint64_t), 8, "pixel_offsets");
+        enqueue_lens_rays(lens, width, height, samples_root, dev_pixel_offsets, n, dev_rays, (hipStream_t)hip_stream);
+    });
 }
 
 int lg_accel_set_query_order(const lg_accel *a, int order) {

@@ -12,9 +12,13 @@ Radiance queries (lg_radiance_device) -- rows r / rs / r8: the radiance of (a)'s
 tiles, under --order 0|1 (both without it) -- beside the row they are measured against, "frame": lg_capture_rows_device of the same film at
 one sample per pixel with lg_accel_set_streaming(2), the same rays through the same passes, and "hbm": lg_probe_rate(0) in GB/s.
 --rows radiance measures these rows alone, --rows frame the frame row alone (any build of the library has it).
+Ray films (lg_capture_rays_device) -- rows f8 / fr: the film of (a)'s rays into RGBA8, in 8 x 8 pixel tiles with their offsets and in row-major
+order without, beside r8 and frame; and f9: a 1024^2 film of 9 samples per pixel (the camera's rays at supersampling 2), with the share of the
+call that lg_profile_read_kinds credits to kind 1 (the combine passes and the resolve pass).  --rows film measures frame, hbm and these;
+--rows takes a comma-separated list (--rows radiance,film).
 Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16; --repeats R measures
 everything R times (rows carry "repeat").
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -122,7 +126,7 @@ def measure(name, builder, size, calls, seed, order=None):
     return out
 
 
-def measure_radiance(name, builder, size, calls, seed, order=None, frame_only=False):
+def measure_radiance(name, builder, size, calls, seed, order=None, frame_only=False, film_rows=False, radiance_rows=True):
     """Rows frame / hbm / r / rs / r8 of one scene (module docstring)."""
     scene = builder(G)
     accel = G.Accel.from_scene(scene)
@@ -145,7 +149,20 @@ def measure_radiance(name, builder, size, calls, seed, order=None, frame_only=Fa
         key = ((pix // size // 8) * (size // 8) + (pix % size) // 8) * 64 + ((pix // size) % 8) * 8 + (pix % size) % 8
         tile_order = torch.argsort(key)
         del pix, key
-        for mode in ((0, 1) if order is None else (order,)):
+        if film_rows:
+            rgba = torch.empty((n * 4,), dtype=torch.uint8, device="cuda")
+            for mode in ((0, 1) if order is None else (order,)):
+                G.set_query_order(accel, mode)
+                other = rays[tile_order].contiguous()
+                ms = timed(lambda: G.capture_rays_device(accel, n, other.data_ptr(), size, size, offsets_ptr=tile_order.data_ptr(), rgba_ptr=rgba.data_ptr(), stream=s), calls)
+                rows.append(("f8: ray film RGBA8, 8x8 pixel tiles with offsets", n, ms, mode))
+                del other
+                ms = timed(lambda: G.capture_rays_device(accel, n, rays.data_ptr(), size, size, rgba_ptr=rgba.data_ptr(), stream=s), calls)
+                rows.append(("fr: ray film RGBA8, row-major", n, ms, mode))
+            G.set_query_order(accel, 0)
+            del rgba
+            rows += film_nine_samples(builder, calls, s)
+        for mode in ((0, 1) if order is None else (order,)) if radiance_rows else ():
             G.set_query_order(accel, mode)
             ms = timed(lambda: G.radiance_device(accel, n, rays.data_ptr(), out.data_ptr(), stream=s), calls)
             rows.append(("r: radiance, camera order", n, ms, mode))
@@ -160,6 +177,26 @@ def measure_radiance(name, builder, size, calls, seed, order=None, frame_only=Fa
     return [{"scene": name, "row": row, "order": mode, "film": [size, size], "rays": int(nr), "ms": round(ms, 4) if nr else None,
              "mrays_per_s": round(nr / ms / 1e3, 1) if nr else None, "gbps": None if nr else round(ms, 1), "calls": calls,
              "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, nr, ms, mode in rows]
+
+
+def film_nine_samples(builder, calls, s, size=1024):
+    """Row f9: a size^2 film of 9 samples per pixel, and the share of its kernels' time in kind 1 (combine + resolve passes)."""
+    scene = builder(G)
+    scene.camera.set_supersampling(2)
+    accel = G.Accel.from_scene(scene)
+    n = size * size
+    rays = torch.empty((n * 9, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rgba = torch.empty((n * 4,), dtype=torch.uint8, device="cuda")
+    call = lambda: G.capture_rays_device(accel, n, rays.data_ptr(), size, size, samples=9, rgba_ptr=rgba.data_ptr(), stream=s)  # noqa: E731
+    ms = timed(call, calls)
+    G.profile_enable(accel, True)
+    call()
+    kinds = G.profile_read_kinds(accel)
+    G.profile_enable(accel, False)
+    total = sum(ms_k for ms_k, _ in kinds.values())
+    share = kinds["combine"][0] / total if total > 0 else None
+    return [("f9: ray film RGBA8, %d^2 x 9 samples (kind-1 share %s)" % (size, "%.3f" % share if share is not None else "n/a"), n * 9, ms, 0)]
 
 
 def once(size):
@@ -191,7 +228,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", choices=("all", "queries", "radiance", "frame"), default="all")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -199,13 +236,17 @@ def main():
     if args.once:
         once(args.size)
         return
+    want = set(args.rows.split(","))
+    if not want or want - {"all", "queries", "radiance", "frame", "film"}:
+        ap.error("--rows: all, queries, radiance, frame, film")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
         for name, builder in SCENES:
-            got = measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order) if args.rows in ("all", "queries") else []
-            if args.rows != "queries":
-                got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=args.rows == "frame")
+            got = measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order) if want & {"all", "queries"} else []
+            if want - {"queries"}:
+                got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
+                                        film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
                 r["repeat"] = repeat
                 print(json.dumps(r), flush=True)
