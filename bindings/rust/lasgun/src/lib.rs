@@ -286,6 +286,32 @@ impl<'s> Accel<'s> {
         if rc != 0 { panic!("lasgun: {}", last_error()) }
         occ.into_iter().map(|b| b != 0).collect()
     }
+    /// Visibility matrix of two point sets (`lg_visibility`): (bits, blocked) -- `from.len()` rows of ceil(to.len() / 8) bytes, bit j of row
+    /// i (`(bits[i * row_bytes + (j >> 3)] >> (j & 7)) & 1`) set iff the segment from[i] -> to[j] is blocked, the test `occluded` makes for
+    /// the ray (from[i], to[j] - from[i]); blocked[i] = the number of set bits of row i.  The segments are made on the device.
+    pub fn visibility(&self, from: &[[f64; 3]], to: &[[f64; 3]]) -> (Vec<u8>, Vec<u32>) {
+        let row_bytes = (to.len() + 7) / 8;
+        let (mut bits, mut blocked) = (vec![0u8; from.len() * row_bytes], vec![0u32; from.len()]);
+        if from.is_empty() || to.is_empty() { return (bits, blocked) }
+        let rc = unsafe {
+            sys::lg_visibility(self.ptr, from.as_ptr() as *const f64, from.len(), to.as_ptr() as *const f64, to.len(), bits.as_mut_ptr(), row_bytes,
+                               blocked.as_mut_ptr())
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        (bits, blocked)
+    }
+    /// `visibility` for points in device memory (3 doubles each), enqueued on a HIP stream: n_from rows of `row_bytes` bytes at `dev_bits`
+    /// and / or n_from u32 at `dev_blocked` (either may be null, not both)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of those sizes (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn visibility_device(&self, dev_from: *const f64, n_from: usize, dev_to: *const f64, n_to: usize, dev_bits: *mut u8, row_bytes: usize,
+                                    dev_blocked: *mut u32, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_visibility_device(self.ptr, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
     /// Radiance along every ray (origin xyz, direction xyz): what the reference's `integrate` leaves for a pixel whose one sample is that
     /// ray (integrate.rs:16-20, 23-132) -- lights, shadows, ambient, specular recursion, background on a miss --, f64 RGB before quantisation.
     /// For rays no camera of the scene generates: probes, panoramas, bakes, a second view of one accel.

@@ -158,7 +158,7 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
-    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_radiance): rays are origin xyz, direction xyz
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_radiance): rays are origin xyz, direction xyz
     std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<lg_hit> hits(rays.size());
         if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
@@ -168,6 +168,18 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         std::vector<uint8_t> occ(rays.size());
         if (lg_occluded(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), occ.data())) throw Error(lg_last_error());
         return std::vector<bool>(occ.begin(), occ.end());
+    }
+    // visibility matrix (lg_visibility): bit j of row i -- (bits[i * row_bytes + (j >> 3)] >> (j & 7)) & 1, row_bytes = ceil(to.size() / 8) --
+    // is 1 iff the segment from[i] -> to[j] is blocked; *blocked (if asked for): the number of set bits of every row
+    std::vector<uint8_t> visibility(const std::vector<std::array<double, 3>> &from, const std::vector<std::array<double, 3>> &to,
+                                    std::vector<uint32_t> *blocked = nullptr) const {
+        const size_t row_bytes = (to.size() + 7) / 8;
+        std::vector<uint8_t> bits(from.size() * row_bytes);
+        if (blocked) blocked->assign(from.size(), 0u);
+        if (lg_visibility(h_, from.empty() ? nullptr : from[0].data(), from.size(), to.empty() ? nullptr : to[0].data(), to.size(),
+                          bits.empty() ? nullptr : bits.data(), row_bytes, blocked && !blocked->empty() ? blocked->data() : nullptr))
+            throw Error(lg_last_error());
+        return bits;
     }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {

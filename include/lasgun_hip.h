@@ -392,6 +392,33 @@ int lg_occluded(const lg_accel *, const double *rays, size_t n, uint8_t *occlude
  * anything else is an error before any launch.  n == 0 is a successful no-op. */
 int lg_intersect_device(const lg_accel *, const double *dev_rays, size_t n, lg_hit *dev_hits, void *hip_stream);
 int lg_occluded_device(const lg_accel *, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream);
+/* Visibility matrices: occlusion between two point sets, bit-packed -- "which of these n_from points see which of those n_to points"
+ * (surface samples against lights or sky samples for a bake, patch against patch for form factors, sensors against targets) without
+ * the caller writing n_from * n_to rays of 48 bytes: the segments are made in the kernel, as the render makes its shadow rays.
+ * from is n_from x 3 doubles, to is n_to x 3 doubles; any f64 is accepted as it is, NaN and infinities included.
+ * Segment (i, j) is the ray with origin from[i] and direction to[j] - from[i] -- three separate f64 subtractions, no contraction -- and it
+ * is occluded iff lg_occluded answers 1 for that ray: the shadow test of point.rs:49 (t < 1) run through the any-hit walk.  Traversal is
+ * the accel's mode exactly as for the other queries (reference, pruned, LDS-resident scene, fast mode); no switch of its own.
+ * lg_accel_set_query_order plays no part: there is no ray array to sort.  A wave walks an 8 x 8 block of the matrix -- 8 consecutive from
+ * points against 8 consecutive to points --, so callers who want coherence order their points so that neighbours in the array are
+ * neighbours in space.
+ * bits: n_from rows of row_bytes bytes, row_bytes >= ceil(n_to / 8).  Bit j of row i is (bits[i*row_bytes + (j >> 3)] >> (j & 7)) & 1,
+ * 1 iff segment (i, j) is occluded: least significant bit first, numpy's packbits(..., bitorder="little") per row.  The padding bits of
+ * a row's last used byte are written as 0; bytes of a row beyond ceil(n_to / 8) are never touched.
+ * blocked (may be NULL): blocked[i] = the number of set bits of row i.  It is WRITTEN, NOT ACCUMULATED: whatever the buffer held before is
+ * gone.  bits may be NULL when blocked is given; both NULL is an error.
+ * n_from == 0 or n_to == 0 is a successful no-op that writes nothing.  ceil(n_from / 8) * ceil(n_to / 8) > 2^32 - 1 is an error before
+ * any launch (8 x 8 blocks are counted in 32 bits, as the other queries' tiles are).
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel, a NULL point set with a non-zero count, both
+ * outputs NULL, row_bytes too small; in the device form also a pointer that is not device memory of the accel's device or is misaligned
+ * (dev_from and dev_to 8-byte aligned, dev_blocked 4, dev_bits 1), or a buffer that ends beyond its allocation.
+ * Device form: it only enqueues on hip_stream (the zeroing of dev_blocked that precedes the kernel included); one stream at a time per
+ * accel.  Host form (synchronous): the points go up, the rows come back compact and are placed into the caller's stride, so the bytes of a
+ * row behind its used part stay untouched; blocked comes back.  No counterpart in the reference. */
+int lg_visibility(const lg_accel *, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes,
+                  uint32_t *blocked);                                                             /* host arrays; synchronous */
+int lg_visibility_device(const lg_accel *, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits,
+                         size_t row_bytes, uint32_t *dev_blocked, void *hip_stream);
 /* Radiance along every ray: the third query, for rays no camera of the scene generates (a fisheye or panorama, a light probe or cube
  * map, a lightmap bake from surface points, a caller's own path continuation, a second view of an accel without rebuilding it).
  * radiance[3*i ..] = what integrate() leaves for a pixel whose one sample is ray i: (Color::zero() + li(root, ray_i, depth 0)) * 1.0

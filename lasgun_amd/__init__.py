@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, CLens  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, CLens  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -89,6 +89,7 @@ _EXTRA = {
     **QUERY_ORDER_SIGNATURES,
     **RADIANCE_SIGNATURES,
     **RAY_FILM_SIGNATURES,
+    **VISIBILITY_SIGNATURES,
 }
 
 
@@ -491,6 +492,49 @@ class HipApi(Api):
         if self.call("occluded_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(occluded_ptr)), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- visibility matrices (include/lasgun_hip.h, lg_visibility*): occlusion between two point sets, the segments made on the device
+    @staticmethod
+    def _points(pts, what):
+        p = _np.ascontiguousarray(pts, dtype=_np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("%s: an (n, 3) array of points" % what)
+        return p
+
+    def visibility(self, accel, from_pts, to_pts, counts=False, row_bytes=None, into=None):
+        """Which segments from_pts[i] -> to_pts[j] are blocked: an (n_from, ceil(n_to / 8)) uint8 array, bit j of row i
+        ((bits[i, j >> 3] >> (j & 7)) & 1, numpy's packbits(bitorder="little") per row) set iff lg_occluded answers 1 for the ray
+        (from_pts[i], to_pts[j] - from_pts[i]).  counts=True: (bits, blocked), blocked[i] the uint32 number of set bits of row i;
+        counts="only": blocked alone (no bit matrix is made).  row_bytes: a wider row stride (the array returned is then (n_from, row_bytes));
+        into = (bits array or None, blocked array or None): C-contiguous buffers written in place -- bytes behind a row's used part keep their value.
+        Also `accel.visibility(from_pts, to_pts, counts=False)`."""
+        f, t = self._points(from_pts, "from_pts"), self._points(to_pts, "to_pts")
+        used = (t.shape[0] + 7) // 8
+        stride = used if row_bytes is None else int(row_bytes)
+        if into is not None:
+            bits, blocked = into
+        else:
+            bits = None if counts == "only" else _np.zeros((f.shape[0], stride), dtype=_np.uint8)
+            blocked = _np.zeros(f.shape[0], dtype=_np.uint32) if counts else None
+        for arr, dt in ((bits, _np.uint8), (blocked, _np.uint32)):
+            if arr is not None and (arr.dtype != dt or not arr.flags["C_CONTIGUOUS"]):
+                raise ValueError("into: C-contiguous uint8 bits and uint32 blocked")
+        if self.call("visibility", accel.h, f.ctypes.data if f.size else None, f.shape[0], t.ctypes.data if t.size else None, t.shape[0],
+                     bits.ctypes.data if bits is not None and bits.size else None, stride,
+                     blocked.ctypes.data if blocked is not None and blocked.size else None):
+            raise LasgunError(self.last_error())
+        if bits is not None and blocked is not None:
+            return bits, blocked
+        return bits if bits is not None else blocked
+
+    def visibility_device(self, accel, n_from, from_ptr, n_to, to_ptr, bits_ptr=None, row_bytes=None, blocked_ptr=None, stream=None):
+        """Enqueue the visibility matrix of n_from x n_to points (device memory, 3 doubles each) into n_from rows of row_bytes bytes at bits_ptr
+        (default ceil(n_to / 8)) and / or n_from uint32 row counts at blocked_ptr."""
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        stride = (int(n_to) + 7) // 8 if row_bytes is None else int(row_bytes)
+        if self.call("visibility_device", accel.h, ptr(from_ptr), int(n_from), ptr(to_ptr), int(n_to), ptr(bits_ptr), stride, ptr(blocked_ptr),
+                     self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     def radiance(self, accel, rays):
         """Radiance along every ray of an (n, 6) float64 array (origin, direction): (n, 3) float64 RGB, li() as the render computes it
         -- lights, shadows, ambient, specular recursion, background on a miss -- before quantisation (include/lasgun_hip.h, lg_radiance)."""
@@ -672,6 +716,7 @@ def _share_torch_hip_runtime():
 
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
+api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

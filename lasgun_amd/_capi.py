@@ -138,6 +138,13 @@ RAY_FILM_SIGNATURES = {
     "lens_rays_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# Visibility matrices (include/lasgun_hip.h, lg_visibility / lg_visibility_device): occlusion between two point sets, bit-packed; the GPU
+# library's alone.
+VISIBILITY_SIGNATURES = {
+    "visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "visibility_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+
 
 class CLens(C.Structure):  # lg_lens: 112 bytes, no padding
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("origin", _D3), ("right", _D3), ("up", _D3), ("forward", _D3),

@@ -60,6 +60,12 @@ hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
 // k_lens.hip: the rays of a lens camera (lg_lens_rays*)
 hipError_t launch_lens_rays(const DLens &L, uint32_t w, uint32_t h, uint32_t root, const unsigned long long *offsets, unsigned long long n, double *rays,
                             uint32_t blocks, hipStream_t stream);
+// k_visibility.hip: visibility matrices (lg_visibility*) -- the any-hit walk of the segments from[i] -> to[j], an 8 x 8 block of the matrix
+// per wave; bit j of bits[i * row_bytes ..] and / or the row's count in blocked[i] (zeroed by the caller ahead of the launch)
+hipError_t launch_visibility(const DParams &P, const double *from, unsigned long long n_from, const double *to, unsigned long long n_to, uint8_t *bits,
+                             unsigned long long row_bytes, uint32_t *blocked, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t visibility_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
+hipError_t visibility_set_lds_limit(size_t bytes, bool ldss);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t queue_occupancy(uint32_t stack_depth, size_t extra_lds, int *blocks_per_cu);

@@ -1,0 +1,106 @@
+// lasgun_amd/csrc/k_visibility.hip -- visibility matrices (include/lasgun_hip.h, lg_visibility*): occlusion between two point sets, the
+// segments made in registers as the render's shadow pass makes its own (k_wavefront.hip: hit point and light position), the answer bit-packed.
+//
+// The grid, the tile claim, the per-lane LDS stack, the scene / accel image in LDS and the walk are query_kernel's (k_query.hip), any-hit:
+// walk<LDSS, FAST, PRUNE>(.., any = true, ..), unchanged.  What differs is the work item: an 8 x 8 BLOCK of the matrix.  Lane l of the wave
+// that claimed block (ti, tj) walks the segment from[8 ti + (l >> 3)] -> to[8 tj + (l & 7)]: a wave reads 8 + 8 points (384 bytes) where
+// lg_occluded reads 64 rays (3 KiB), and its 64 segments share 8 origins and 8 targets.  Blocks are numbered row-major (tile = ti * tiles_j
+// + tj): consecutive tiles keep their origins and step through the targets.  Lanes outside the matrix walk nothing and vote 0.
+//
+// One ballot of the verdict per wave; in each of the block's 8 rows the lane with (l & 7) == 0 takes its row's byte out of the mask and
+// stores it at bits[row * row_bytes + tj] -- every used byte is written exactly once, padding bits 0 (the lanes behind n_to voted 0), no
+// atomics and no pre-clear -- and adds the byte's popcount to blocked[row] (zeroed on the same stream ahead of the launch, query.cpp;
+// integer addition: the counts do not depend on the order the blocks finish in).
+#include "shade.h"
+
+namespace lg {
+
+struct VisibilityArgs {
+    const double *from;            // [n_from][3]
+    const double *to;              // [n_to][3]
+    unsigned long long n_from, n_to;
+    uint8_t *bits;                 // [n_from][row_bytes], may be nullptr
+    unsigned long long row_bytes;
+    uint32_t *blocked;             // [n_from], zeroed before the launch; may be nullptr
+    uint32_t tiles_j;              // ceil(n_to / 8): blocks per row of blocks (ntiles = ceil(n_from / 8) * tiles_j, DParams)
+};
+
+template <bool FAST, bool LDSS, bool PRUNE>
+__global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) visibility_kernel(const DParams P, const VisibilityArgs Q) {
+    static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
+    static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t ntiles = P.ntiles;
+    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
+    uint32_t *stack = lds_stack + tid;
+    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint4 *scn = nullptr;
+    if (LDSS) {
+        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
+        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
+        __syncthreads();
+        scn = dst;
+    }
+    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
+    if (!wave_has_work(ntiles)) return;
+    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
+    for (bool final = false; !final;) {
+        uint32_t tile;
+        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
+        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        if (tile == NO_TILE) break;
+        const uint32_t ti = tile / Q.tiles_j, tj = tile - ti * Q.tiles_j;
+        const unsigned long long row = 8ull * ti + (lane >> 3), col = 8ull * tj + (lane & 7u);
+        const bool active = row < Q.n_from && col < Q.n_to;
+        Best b;
+        b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
+        if (active) {
+            const double *f = Q.from + 3ull * row, *t = Q.to + 3ull * col;
+            const V3 o{f[0], f[1], f[2]};
+            const Ray ray = ray_new(o, V3{t[0] - o.x, t[1] - o.y, t[2] - o.z}); // the segment from -> to: three subtractions, direction as it comes out
+            walk<LDSS, FAST, PRUNE>(P, ray, true, stack, stride, b, scn, cnt, arec);
+        }
+        const unsigned long long mask = __builtin_amdgcn_ballot_w64(active && b.t < 1.0); // point.rs:49
+        if ((lane & 7u) != 0u || row >= Q.n_from) continue;
+        const uint32_t byte = (uint32_t)(mask >> (lane & 56u)) & 0xFFu;
+        if (Q.bits) Q.bits[row * Q.row_bytes + tj] = (uint8_t)byte;
+        if (Q.blocked && byte) atomicAdd(Q.blocked + row, (uint32_t)__builtin_popcount(byte));
+    }
+}
+
+// ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as query_kernel, LDS sized as launch_query sizes it.
+hipError_t launch_visibility(const DParams &P, const double *from, unsigned long long n_from, const double *to, unsigned long long n_to, uint8_t *bits,
+                             unsigned long long row_bytes, uint32_t *blocked, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    const VisibilityArgs Q{from, to, n_from, n_to, bits, row_bytes, blocked, (uint32_t)((n_to + 7ull) / 8ull)};
+    const bool ldss = P.lds_image && !fast;
+    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint32_t depth = fast ? stack_depth : P.stack_depth;
+    const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
+#define LG_V(F, L, Z) hipLaunchKernelGGL((visibility_kernel<F, L, Z>), dim3(blocks), dim3(block), lds, stream, P, Q)
+    if (fast) LG_V(true, false, false);
+    else if (P.prune) { if (ldss) LG_V(false, true, true); else LG_V(false, false, true); }
+    else { if (ldss) LG_V(false, true, false); else LG_V(false, false, false); }
+#undef LG_V
+    return hipGetLastError();
+}
+// workgroups per CU of the 256-lane forms
+hipError_t visibility_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
+    const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
+    const void *fn = fast ? reinterpret_cast<const void *>(visibility_kernel<true, false, false>)
+                          : prune ? reinterpret_cast<const void *>(visibility_kernel<false, false, true>) : reinterpret_cast<const void *>(visibility_kernel<false, false, false>);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, LG_BLOCK, lds);
+}
+// raise the dynamic-LDS limit of this file's kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
+hipError_t visibility_set_lds_limit(size_t bytes, bool ldss) {
+    const void *resident[] = {reinterpret_cast<const void *>(visibility_kernel<false, true, false>), reinterpret_cast<const void *>(visibility_kernel<false, true, true>)};
+    const void *plain[] = {reinterpret_cast<const void *>(visibility_kernel<false, false, false>), reinterpret_cast<const void *>(visibility_kernel<false, false, true>),
+                           reinterpret_cast<const void *>(visibility_kernel<true, false, false>)};
+    for (size_t i = 0; i < (ldss ? 2u : 3u); ++i) {
+        const hipError_t e = hipFuncSetAttribute(ldss ? resident[i] : plain[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+} // namespace lg

@@ -1,4 +1,4 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_radiance*, lg_camera_rays*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_radiance*, lg_camera_rays*,
 // lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
@@ -131,6 +131,92 @@ static int query_device(const lg_accel *a, const double *dev_rays, size_t n, voi
         check_device_buffer(*a, dev_out, n * (any ? 1u : sizeof(lg_hit)), any ? 1 : 16, any ? "occluded" : "hits");
         enqueue_query(*a, dev_rays, n, any ? nullptr : reinterpret_cast<lg_hit *>(dev_out), any ? reinterpret_cast<uint8_t *>(dev_out) : nullptr,
                       (hipStream_t)hip_stream);
+    });
+}
+
+// ---- visibility matrices (lg_visibility*; k_visibility.hip): the segments from[i] -> to[j] made in the kernel, one bit each
+static size_t visibility_used_bytes(size_t n_to) { return n_to / 8 + (n_to % 8 ? 1 : 0); }
+// What both forms refuse before anything is allocated or enqueued (counts are not 0 here)
+static void check_visibility(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, const uint8_t *bits, size_t row_bytes,
+                             const uint32_t *blocked) {
+    if (!a) throw Error("accel is NULL");
+    if (!from) throw Error("from is NULL");
+    if (!to) throw Error("to is NULL");
+    if (!bits && !blocked) throw Error("bits and blocked are both NULL: at least one output");
+    const size_t used = visibility_used_bytes(n_to);
+    if (bits && row_bytes < used) throw Error("row_bytes is " + std::to_string(row_bytes) + ", a row of " + std::to_string(n_to) + " bits takes " + std::to_string(used));
+    const unsigned long long ti = (unsigned long long)(n_from / 8 + (n_from % 8 ? 1 : 0));
+    if (ti > 0xFFFFFFFFull / used) throw Error("too many segments in one visibility matrix: 8 x 8 blocks are counted in 32 bits");
+    if (bits && n_from > 1 && row_bytes > (SIZE_MAX - used) / (n_from - 1)) throw Error("bits: n_from rows of row_bytes bytes do not fit the address space");
+}
+// One matrix enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): grid and
+// launch context as enqueue_query's, a tile being an 8 x 8 block
+static void enqueue_visibility(const lg_accel &a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked,
+                               hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    if (ldss) {
+        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
+        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+    }
+    P.ntiles = (uint32_t)(((n_from + 7) / 8) * visibility_used_bytes(n_to));
+    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
+    uint32_t cap = a.ldss_blocks;
+    if (!ldss) {
+        int per_cu = 0;
+        HIP_TRY(visibility_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
+        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
+    }
+    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
+    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    P.tile_counter = c.tile_counter.p;
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    if (blocked) HIP_TRY(hipMemsetAsync(blocked, 0, n_from * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
+    HIP_TRY(launch_visibility(P, from, n_from, to, n_to, bits, row_bytes, blocked, a.fast, blocks, depth, stream));
+}
+// Host form: the points go up, the rows come back COMPACT (ceil(n_to / 8) bytes each) and are placed into the caller's stride here -- the
+// bytes of a row behind its used part are never written
+static int visibility_host(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked) {
+    return guarded([&] {
+        if (n_from == 0 || n_to == 0) return;
+        check_visibility(a, from, n_from, to, n_to, bits, row_bytes, blocked);
+        const size_t used = visibility_used_bytes(n_to);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        DevBuf<double> dfrom, dto;
+        DevBuf<uint8_t> dbits;
+        DevBuf<uint32_t> dblocked;
+        dfrom.alloc(n_from * 3);
+        dto.alloc(n_to * 3);
+        if (bits) dbits.alloc(n_from * used);
+        if (blocked) dblocked.alloc(n_from);
+        std::vector<uint8_t> rows(bits && row_bytes != used ? n_from * used : 0);
+        std::vector<uint32_t> counts(blocked ? n_from : 0); // (staged: an error on the way leaves the caller's array as it was)
+        HIP_TRY(hipMemcpyAsync(dfrom.p, from, n_from * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(dto.p, to, n_to * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_visibility(*a, dfrom.p, n_from, dto.p, n_to, bits ? dbits.p : nullptr, used, blocked ? dblocked.p : nullptr, a->stream);
+        if (bits) HIP_TRY(hipMemcpyAsync(row_bytes != used ? rows.data() : bits, dbits.p, n_from * used, hipMemcpyDeviceToHost, a->stream));
+        if (blocked) HIP_TRY(hipMemcpyAsync(counts.data(), dblocked.p, n_from * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+        if (bits && row_bytes != used)
+            for (size_t i = 0; i < n_from; ++i) std::memcpy(bits + i * row_bytes, rows.data() + i * used, used);
+        if (blocked) std::memcpy(blocked, counts.data(), n_from * sizeof(uint32_t));
+    });
+}
+static int visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
+                             uint32_t *dev_blocked, void *hip_stream) {
+    return guarded([&] {
+        if (n_from == 0 || n_to == 0) return;
+        check_visibility(a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_from, n_from * 3 * sizeof(double), 8, "from");
+        check_device_buffer(*a, dev_to, n_to * 3 * sizeof(double), 8, "to");
+        if (dev_bits) check_device_buffer(*a, dev_bits, (n_from - 1) * row_bytes + visibility_used_bytes(n_to), 1, "bits");
+        if (dev_blocked) check_device_buffer(*a, dev_blocked, n_from * sizeof(uint32_t), 4, "blocked");
+        enqueue_visibility(*a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, (hipStream_t)hip_stream);
     });
 }
 
@@ -308,6 +394,14 @@ int lg_intersect_device(const lg_accel *a, const double *dev_rays, size_t n, lg_
 }
 int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream) {
     return query_device(a, dev_rays, n, dev_occluded, true, hip_stream);
+}
+
+int lg_visibility(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked) {
+    return visibility_host(a, from, n_from, to, n_to, bits, row_bytes, blocked);
+}
+int lg_visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
+                         uint32_t *dev_blocked, void *hip_stream) {
+    return visibility_device(a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, hip_stream);
 }
 
 int lg_radiance(const lg_accel *a, const double *rays, size_t n, double *radiance) { return radiance_host(a, rays, n, radiance); }

@@ -16,9 +16,14 @@ Ray films (lg_capture_rays_device) -- rows f8 / fr: the film of (a)'s rays into 
 order without, beside r8 and frame; and f9: a 1024^2 film of 9 samples per pixel (the camera's rays at supersampling 2), with the share of the
 call that lg_profile_read_kinds credits to kind 1 (the combine passes and the resolve pass).  --rows film measures frame, hbm and these;
 --rows takes a comma-separated list (--rows radiance,film).
+Visibility matrices (lg_visibility_device) -- --rows visibility: 4096 from points (the first hits of a camera grid, in 8 x 8 tiles of the grid,
+pushed out along ng by the shading offset) against 4096 to points (64 rings of 64 points on the sphere around the bounds of what the camera
+sees), 16.7 M segments.  Row x8: lg_occluded_device on those segments written out as 48-byte rays in the matrix's 8 x 8 block order (the
+yardstick: this row needs nothing the parent commit's library does not have, so the same file measures it there); row v8: the bit matrix
+from the two point sets; row v8c: the bit matrix and the row counts.  Where both run, v8's bits are checked against x8's bytes.
 Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16; --repeats R measures
 everything R times (rows carry "repeat").
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -199,6 +204,68 @@ def film_nine_samples(builder, calls, s, size=1024):
     return [("f9: ray film RGBA8, %d^2 x 9 samples (kind-1 share %s)" % (size, "%.3f" % share if share is not None else "n/a"), n * 9, ms, 0)]
 
 
+def visibility_points(accel, s, n=4096):
+    """(from, to): n first hits of a camera grid in 8 x 8 tiles of the grid (the grid grown from 64 x 64 until it has n hits), pushed out along
+    ng; n points on the sphere around the hits' bounds, 64 equal-area rings of n / 64 points, neighbours in the array neighbours on a ring."""
+    g = 64
+    while True:
+        rays = torch.empty((g * g, 6), dtype=torch.float64, device="cuda")
+        G.camera_rays_device(accel, g, g, 0, 0, g, g, rays.data_ptr(), stream=s)
+        hits = torch.empty((g * g * 96,), dtype=torch.uint8, device="cuda")
+        G.intersect_device(accel, g * g, rays.data_ptr(), hits.data_ptr(), stream=s)
+        pix = torch.arange(g * g, device="cuda")
+        key = ((pix // g // 8) * (g // 8) + (pix % g) // 8) * 64 + ((pix // g) % 8) * 8 + (pix % g) % 8
+        tiled = hits.view(-1, 96)[torch.argsort(key)].contiguous()
+        f = tiled.view(torch.float64).view(-1, 12)
+        f = f[tiled.view(torch.int32).view(-1, 24)[:, 20] != 0]
+        if f.shape[0] >= n:
+            break
+        g += 8
+    p = f[:, 1:4]
+    lo, hi = p.min(dim=0).values, p.max(dim=0).values
+    frm = (p[:n] + f[:n, 4:7] * ERR).contiguous()
+    rings = 64
+    k = torch.arange(n, device="cuda")
+    z = 1.0 - 2.0 * ((k // (n // rings)).double() + 0.5) / rings
+    phi = 2.0 * torch.pi * ((k % (n // rings)).double() + 0.5) / (n // rings)
+    r = torch.sqrt(1.0 - z * z)
+    to = (0.5 * (lo + hi) + 0.5 * torch.linalg.norm(hi - lo) * torch.stack([r * torch.cos(phi), r * torch.sin(phi), z], dim=1)).contiguous()
+    return frm, to, g
+
+
+def measure_visibility(name, builder, calls, n=4096):
+    """Rows x8 / v8 / v8c of one scene (module docstring)."""
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    frm, to, grid = visibility_points(accel, s, n)
+    b = n // 8
+    o = frm.view(b, 1, 8, 1, 3).expand(b, b, 8, 8, 3)
+    segs = torch.cat([o, to.view(1, b, 1, 8, 3).expand(b, b, 8, 8, 3) - o], dim=4).contiguous().view(-1, 6)  # block (ti, tj), then row, then column
+    del o
+    occ = torch.empty((n * n,), dtype=torch.uint8, device="cuda")
+    rows = []
+    ms = timed(lambda: G.occluded_device(accel, n * n, segs.data_ptr(), occ.data_ptr(), stream=s), calls)
+    rows.append(("x8: occluded, the matrix's segments as rays in 8x8 block order", ms, 48.0 + 1.0))
+    fraction = round(float(occ.float().mean()), 4)
+    del segs
+    if hasattr(G, "visibility_device"):
+        bits = torch.empty((n, n // 8), dtype=torch.uint8, device="cuda")
+        blocked = torch.empty((n,), dtype=torch.int32, device="cuda")
+        ms = timed(lambda: G.visibility_device(accel, n, frm.data_ptr(), n, to.data_ptr(), bits.data_ptr(), n // 8, None, stream=s), calls)
+        rows.append(("v8: visibility, bit matrix of %d x %d points" % (n, n), ms, 2.0 * n * 24.0 / (n * n) + 0.125))
+        ms = timed(lambda: G.visibility_device(accel, n, frm.data_ptr(), n, to.data_ptr(), bits.data_ptr(), n // 8, blocked.data_ptr(), stream=s), calls)
+        rows.append(("v8c: visibility, bit matrix and row counts", ms, 2.0 * n * 24.0 / (n * n) + 0.125 + 4.0 / n))
+        torch.cuda.synchronize()
+        want = occ.view(b, b, 8, 8).permute(0, 2, 1, 3).reshape(n, b, 8).int()  # [row][byte][bit]
+        want = (want << torch.arange(8, device="cuda", dtype=torch.int32)).sum(dim=2).to(torch.uint8)
+        assert torch.equal(bits, want), "v8's bits are not x8's bytes"
+        assert torch.equal(blocked, occ.view(b, b, 8, 8).permute(0, 2, 1, 3).reshape(n, n).sum(dim=1).int())
+    return [{"scene": name, "row": row, "from": n, "to": n, "rays": n * n, "camera_grid": grid, "ms": round(ms, 4), "mrays_per_s": round(n * n / ms / 1e3, 1),
+             "bytes_per_segment": round(bps, 4), "occluded_fraction": fraction, "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2",
+             "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, bps in rows]
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -228,7 +295,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -237,14 +304,16 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film"}:
-        ap.error("--rows: all, queries, radiance, frame, film")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
         for name, builder in SCENES:
             got = measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order) if want & {"all", "queries"} else []
-            if want - {"queries"}:
+            if want & {"all", "visibility"}:
+                got += measure_visibility(name, builder, max(args.calls, 20))
+            if want - {"queries", "visibility"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
