@@ -228,6 +228,7 @@ impl Img for Film {
 /// An equirectangular panorama (kind 0) or an equidistant fisheye (kind 1; `fov_deg` across the film's shorter side) around `origin`;
 /// the basis is used as given.
 pub use sys::lg_lens as Lens;
+pub use sys::lg_features as Features;
 
 /// The rays of a lens over a width x height film, row-major pixels (or over the pixel slots `offsets` names), samples_root^2 per slot in
 /// idx = i*samples_root + j order: the layout `Accel::capture_rays` takes.  Generated on the current device.
@@ -356,6 +357,45 @@ impl<'s> Accel<'s> {
     pub unsafe fn capture_rays_device(&self, dev_rays: *const f64, pixels: usize, samples: u32, dev_offsets: *const u64, width: u32, height: u32,
                                       dev_rgba: *mut std::ffi::c_void, dev_rgb: *mut f64, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_capture_rays_device(self.ptr, dev_rays, pixels, samples, dev_offsets, width, height, dev_rgba, dev_rgb, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
+    /// The number of materials of the accel's tables (`lg_accel_material_count`): the rows of `capture_features`' `material_rgb`.
+    pub fn material_count(&self) -> usize { unsafe { sys::lg_accel_material_count(self.ptr) } }
+    /// Feature buffers of the scene's own camera view (`lg_capture_features`): first-hit depth, shading normal, albedo, coverage and ids of
+    /// the pixels [x0,x1) x [y0,y1) of a width x height film, the rays made on the device in the render's 8 x 8 tiles.  Every plane given is
+    /// width*height long and addressed like the film (y*width + x); pixels outside the rectangle keep their values.  Normal and albedo are
+    /// means over all the pixel's samples (premultiplied by coverage), depth the mean over the samples that hit (+inf: none), id sample 0's
+    /// kind, prim, instance, material.  `material_rgb`: `material_count()` colours, summed per hit material (required with albedo).
+    #[allow(clippy::too_many_arguments)]
+    pub fn capture_features(&self, width: u32, height: u32, rect: (u32, u32, u32, u32), depth: Option<&mut [f32]>, normal: Option<&mut [[f32; 3]]>,
+                            albedo: Option<&mut [[f32; 3]]>, coverage: Option<&mut [f32]>, id: Option<&mut [[u32; 4]]>, material_rgb: Option<&[[f64; 3]]>) {
+        let area = (width as usize) * (height as usize);
+        assert!(depth.as_ref().map_or(true, |p| p.len() == area) && normal.as_ref().map_or(true, |p| p.len() == area)
+                && albedo.as_ref().map_or(true, |p| p.len() == area) && coverage.as_ref().map_or(true, |p| p.len() == area)
+                && id.as_ref().map_or(true, |p| p.len() == area), "capture_features: planes of width * height pixels");
+        assert!(material_rgb.map_or(true, |m| m.len() == self.material_count()), "capture_features: material_count() colours");
+        let out = sys::lg_features {
+            depth: depth.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            normal: normal.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            albedo: albedo.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            coverage: coverage.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            id: id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+        };
+        let rc = unsafe {
+            sys::lg_capture_features(self.ptr, width, height, rect.0, rect.1, rect.2, rect.3, &out, material_rgb.map_or(std::ptr::null(), |m| m.as_ptr() as *const f64))
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `capture_features` into device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device, width*height pixels a plane and `material_count()` * 3 doubles (the
+    /// library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn capture_features_device(&self, width: u32, height: u32, rect: (u32, u32, u32, u32), dev_out: &sys::lg_features, dev_material_rgb: *const f64,
+                                          hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_capture_features_device(self.ptr, width, height, rect.0, rect.1, rect.2, rect.3, dev_out, dev_material_rgb, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
     }

@@ -200,6 +200,36 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                             rgb && !rgb->empty() ? (*rgb)[0].data() : nullptr, film.w(), film.h()))
             throw Error(lg_last_error());
     }
+    // feature buffers of the scene's own camera view (lg_capture_features): first-hit depth, shading normal, albedo, coverage and ids of the
+    // pixels [x0,x1) x [y0,y1) of a width x height film, every plane addressed like the film (pixel y*width + x) and sized here when it is
+    // too small; pixels outside the rectangle keep what the vectors held.  A null vector pointer = that plane is not asked for.
+    // material_rgb: material_count() colours, summed per hit material into albedo (required with it).
+    struct Features {
+        std::vector<float> *depth = nullptr;                  // [width*height]
+        std::vector<std::array<float, 3>> *normal = nullptr;  // mean over all samples: premultiplied by coverage
+        std::vector<std::array<float, 3>> *albedo = nullptr;
+        std::vector<float> *coverage = nullptr;
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;   // sample 0's kind, prim, instance, material
+    };
+    size_t material_count() const { return lg_accel_material_count(h_); }
+    void capture_features(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const Features &out,
+                          const std::vector<std::array<double, 3>> *material_rgb = nullptr) const {
+        const size_t n = (size_t)width * height;
+        if (material_rgb && material_rgb->size() != material_count()) throw Error("capture_features: material_count() colours");
+        auto sized = [n](auto *v) { if (v && v->size() < n) v->resize(n); return v && n ? &(*v)[0] : nullptr; };
+        lg_features f{};
+        f.depth = sized(out.depth); f.coverage = sized(out.coverage);
+        if (auto *p = sized(out.normal)) f.normal = p->data();
+        if (auto *p = sized(out.albedo)) f.albedo = p->data();
+        if (auto *p = sized(out.id)) f.id = p->data();
+        if (lg_capture_features(h_, width, height, x0, y0, x1, y1, &f, material_rgb && !material_rgb->empty() ? (*material_rgb)[0].data() : nullptr))
+            throw Error(lg_last_error());
+    }
+    // the same planes enqueued into device memory on hip_stream (lg_capture_features_device): dev_out's members are device pointers
+    void capture_features_device(uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features &dev_out,
+                                 const double *dev_material_rgb, void *hip_stream) const {
+        if (lg_capture_features_device(h_, width, height, x0, y0, x1, y1, &dev_out, dev_material_rgb, hip_stream)) throw Error(lg_last_error());
+    }
     // the order a query's rays are walked in (lg_accel_set_query_order): 0 as given (default), 1 sorted on the device by a coherence key
     void set_query_order(int order) const {
         if (lg_accel_set_query_order(h_, order)) throw Error(lg_last_error());

@@ -477,6 +477,48 @@ int lg_capture_rays(const lg_accel *, const double *rays, size_t pixels, uint32_
                     double *rgb, uint32_t width, uint32_t height);
 int lg_capture_rays_device(const lg_accel *, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_pixel_offsets,
                            uint32_t width, uint32_t height, void *dev_rgba, double *dev_rgb, void *hip_stream);
+/* Feature buffers: the auxiliary images of the scene's own camera view -- first-hit depth, shading normal, albedo, coverage and object
+ * ids, what a denoiser, a compositor, an edge-aware upsampler or a picking UI asks a renderer for -- without the caller writing
+ * lg_camera_rays' rays (48 bytes each) and lg_intersect's hits (96 bytes each) and reducing the samples itself: the rays are made in the
+ * kernel, in the render's 8 x 8-pixel tiles, and at most 48 bytes a pixel are written.  An EXTRA: the contract below is this library's own,
+ * nothing of the reference is mirrored. */
+typedef struct lg_features {
+    float    *depth;     /* [width*height]     */
+    float    *normal;    /* [width*height][3]  */
+    float    *albedo;    /* [width*height][3]  */
+    float    *coverage;  /* [width*height]     */
+    uint32_t *id;        /* [width*height][4]: kind, prim, instance, material -- the last 16 bytes of an lg_hit */
+} lg_features;           /* 40 bytes; each pointer may be NULL, all NULL is an error */
+/* lg_features itself is always a host struct; in the device form its members are device pointers.
+ * Pixels: [x0,x1) x [y0,y1) of a width x height film.  Every plane is addressed like the film: pixel y*width + x.  A pixel outside the
+ * rectangle is never touched.
+ * Rays: the rays of a pixel are the S = lg_camera_samples rays of lg_camera_rays for it, s = 0 .. S-1 in camera order.  Sample s's hit is
+ * what lg_intersect returns for that ray, bit for bit, in the accel's traversal mode (reference, pruned, LDS-resident scene, fast mode);
+ * no switch of its own.  lg_accel_set_query_order plays no part (there is no ray array to sort), and neither do the interleave, subset
+ * and organisation settings of the captures.
+ * Hit: sample s is a hit iff lg_intersect reports kind != 0 for it.
+ * Accumulators: all f64, no contraction.  nhit counts the hits; tsum, nsum[3] and asum[3] start at +0.0.  For s ascending, a hit adds t to
+ * tsum, ns (lg_hit::ns, per component) to nsum, and material_rgb[3*material + c] to asum[c].  A miss adds nothing.
+ * material_rgb: lg_accel_material_count x 3 doubles, the caller's colour per material; required iff albedo is requested and ignored
+ * otherwise.  A hit whose material is outside 0 .. count-1 adds nothing to asum -- which this library's tables cannot produce: every hit's
+ * material is an index lg_accel_material accepts (the one shading itself reads); the rule is kept for a negative or stale index all the same.
+ * Outputs: with inv = 1.0 / (double)S,
+ *   normal[c] = (float)(nsum[c] * inv);  albedo[c] = (float)(asum[c] * inv);  coverage = (float)((double)nhit * inv);
+ *   depth = nhit ? (float)(tsum * (1.0 / (double)nhit)) : +INFINITY;
+ * (float) rounds to nearest even, as numpy's astype(float32).  Normal and albedo are therefore premultiplied by coverage; depth is the
+ * mean over the samples that hit.
+ * id: sample 0's kind, prim, instance, material exactly as lg_hit has them (0, ~0, ~0, -1 on a miss), written as one 16-byte store.
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel or out; all five planes NULL; albedo without
+ * material_rgb; a bad rectangle, with lg_capture_rect's rule; more 8 x 8 tiles than 2^32 - 1 (or x1 / y1 above 2^32 - 8: a tile's pixel coordinates are 32-bit); in the device form a plane or table that is
+ * not device memory of the accel's device, is misaligned (id 16-byte aligned, material_rgb 8, the float planes 4) or ends beyond its
+ * allocation.  An empty rectangle is a successful no-op.
+ * Host form (synchronous): the table goes up and the rectangle's pixels come back compact; the host places them at their film offsets, so
+ * nothing outside the rectangle is read or written.  Device form: it only enqueues on hip_stream; one stream at a time per accel. */
+int lg_capture_features(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                        const lg_features *out, const double *material_rgb);                       /* host arrays; synchronous */
+int lg_capture_features_device(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1,
+                               const lg_features *dev_out, const double *dev_material_rgb, void *hip_stream);
+size_t lg_accel_material_count(const lg_accel *);   /* indices 0 .. count-1 are valid for lg_accel_material */
 /* Lens rays: the rays of two cameras the reference does not have, generated on the device in the layout lg_capture_rays takes.  An EXTRA:
  * every expression below is this library's own, nothing of the reference is mirrored. */
 typedef struct lg_lens {

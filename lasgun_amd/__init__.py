@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, CLens  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -90,6 +90,7 @@ _EXTRA = {
     **RADIANCE_SIGNATURES,
     **RAY_FILM_SIGNATURES,
     **VISIBILITY_SIGNATURES,
+    **FEATURES_SIGNATURES,
 }
 
 
@@ -102,6 +103,10 @@ HIT_DTYPE = _np.dtype(Hit)  # the numpy mirror of lg_hit: what HipApi.intersect 
 assert _C.sizeof(Hit) == 96 and HIT_DTYPE.itemsize == 96, "lg_hit is 96 bytes"
 LENS_EQUIRECTANGULAR, LENS_FISHEYE = 0, 1  # lg_lens::kind
 assert _C.sizeof(CLens) == 112, "lg_lens is 112 bytes"
+assert _C.sizeof(CFeatures) == 40, "lg_features is 40 bytes"
+FEATURE_PLANES = ("depth", "normal", "albedo", "coverage", "id")  # lg_features' members, in its order
+_FEATURE_SHAPE = {"depth": ((), _np.float32), "normal": ((3,), _np.float32), "albedo": ((3,), _np.float32), "coverage": ((), _np.float32),
+                  "id": ((4,), _np.uint32)}
 
 
 def Lens(kind, origin, right, up, forward, fov_deg=180.0):
@@ -535,6 +540,63 @@ class HipApi(Api):
                      self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of the camera's primary hits
+    def material_count(self, accel):
+        """The number of materials of the accel's tables: indices 0 .. count-1 are valid for accel_material and name the rows of material_rgb."""
+        return int(self.call("accel_material_count", accel.h))
+
+    def default_albedo_table(self, accel):
+        """(material_count, 3) float64: per material kd for matte and plastic, kr for mirror, kt for glass and (1, 1, 1) for metal -- the
+        material_rgb capture_features uses when none is given.  A convention of this WRAPPER, not of the C contract (lg_capture_features
+        takes whatever colours the caller passes)."""
+        out = _np.ones((self.material_count(accel), 3), dtype=_np.float64)
+        for i in range(out.shape[0]):
+            m = self.accel_material(accel, i)
+            if m["kind"] in (0, 1, 4):    # matte / plastic: kd; mirror: kr
+                out[i] = m["p"][0:3]
+            elif m["kind"] == 3:          # glass: kt
+                out[i] = m["p"][3:6]
+        return out
+
+    def capture_features(self, accel, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None, into=None):
+        """The feature buffers of the pixels rect = (x0, y0, x1, y1) (default: the whole film) of the accel's own camera view of a w x h film:
+        a dict of the planes asked for (any of "depth", "normal", "albedo", "coverage", "id"), each addressed like the film -- float32
+        (h, w) depth and coverage, float32 (h, w, 3) normal and albedo, uint32 (h, w, 4) id = kind, prim, instance, material of sample 0.
+        Normal and albedo are means over ALL the pixel's samples (premultiplied by coverage), depth the mean over those that hit (+inf: none).
+        material_rgb: (material_count, 3) float64, the colour summed per hit material; default default_albedo_table(accel).
+        `into`: a dict of C-contiguous arrays of those shapes, written in place -- pixels outside rect keep their bytes; new arrays are zero there."""
+        x0, y0, x1, y1 = (0, 0, w, h) if rect is None else rect
+        planes = tuple(planes)
+        if any(p not in FEATURE_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (FEATURE_PLANES,))
+        out = {}
+        for p in planes:
+            shape, dt = _FEATURE_SHAPE[p]
+            arr = into[p] if into is not None else _np.zeros((h, w) + shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != (h, w) + shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, (h, w) + shape))
+            out[p] = arr
+        table = None
+        if "albedo" in out:
+            table = _np.ascontiguousarray(self.default_albedo_table(accel) if material_rgb is None else material_rgb, dtype=_np.float64)
+            if table.shape != (self.material_count(accel), 3):
+                raise ValueError("material_rgb: a (material_count, 3) array")
+        f = CFeatures(*[out[p].ctypes.data if p in out and out[p].size else None for p in FEATURE_PLANES])
+        if self.call("capture_features", accel.h, int(w), int(h), int(x0), int(y0), int(x1), int(y1), _C.addressof(f),
+                     table.ctypes.data if table is not None and table.size else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def capture_features_device(self, accel, w, h, rect=None, depth_ptr=None, normal_ptr=None, albedo_ptr=None, coverage_ptr=None, id_ptr=None,
+                                material_rgb_ptr=None, stream=None):
+        """Enqueue the same planes into device memory: each pointer w*h elements of its plane, addressed like the film (id 16-byte aligned),
+        or None; material_rgb_ptr: material_count * 3 doubles in device memory, required with albedo_ptr."""
+        x0, y0, x1, y1 = (0, 0, w, h) if rect is None else rect
+        f = CFeatures(*[int(p) if p is not None else None for p in (depth_ptr, normal_ptr, albedo_ptr, coverage_ptr, id_ptr)])
+        if self.call("capture_features_device", accel.h, int(w), int(h), int(x0), int(y0), int(x1), int(y1), _C.addressof(f),
+                     _C.c_void_p(int(material_rgb_ptr)) if material_rgb_ptr is not None else None, self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     def radiance(self, accel, rays):
         """Radiance along every ray of an (n, 6) float64 array (origin, direction): (n, 3) float64 RGB, li() as the render computes it
         -- lights, shadows, ambient, specular recursion, background on a miss -- before quantisation (include/lasgun_hip.h, lg_radiance)."""
@@ -716,6 +778,7 @@ def _share_torch_hip_runtime():
 
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
+api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None: api.capture_features(self, w, h, rect, planes, material_rgb)  # accel.features(w, h)
 api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`

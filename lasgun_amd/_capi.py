@@ -145,6 +145,18 @@ VISIBILITY_SIGNATURES = {
     "visibility_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# Feature buffers (include/lasgun_hip.h, lg_capture_features* / lg_accel_material_count): depth, normal, albedo, coverage and ids of the
+# camera's primary hits; the GPU library's alone.
+FEATURES_SIGNATURES = {
+    "capture_features": (C.c_int, [C.c_void_p] + [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p]),
+    "capture_features_device": (C.c_int, [C.c_void_p] + [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "accel_material_count": (C.c_size_t, [C.c_void_p]),
+}
+
+
+class CFeatures(C.Structure):  # lg_features: five plane pointers, 40 bytes; NULL = not asked for
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]
+
 
 class CLens(C.Structure):  # lg_lens: 112 bytes, no padding
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("origin", _D3), ("right", _D3), ("up", _D3), ("forward", _D3),

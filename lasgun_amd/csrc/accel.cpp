@@ -94,7 +94,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         }
         const size_t extra_lds = (size_t)a->accel_image_n16 * 16;
         size_t lds = (size_t)std::max(a->stack_depth, a->stack_depth_fast1) * 256 * 4 + extra_lds;
-        if (lds > 64 * 1024) { HIP_TRY(mega_set_lds_limit(lds, false)); HIP_TRY(wf_set_lds_limit(lds, false)); HIP_TRY(queue_set_lds_limit(lds, false)); HIP_TRY(query_set_lds_limit(lds, false)); HIP_TRY(rq_set_lds_limit(lds, false)); HIP_TRY(visibility_set_lds_limit(lds, false)); }
+        if (lds > 64 * 1024) { HIP_TRY(mega_set_lds_limit(lds, false)); HIP_TRY(wf_set_lds_limit(lds, false)); HIP_TRY(queue_set_lds_limit(lds, false)); HIP_TRY(query_set_lds_limit(lds, false)); HIP_TRY(rq_set_lds_limit(lds, false)); HIP_TRY(visibility_set_lds_limit(lds, false)); HIP_TRY(features_set_lds_limit(lds, false)); }
         int per_cu = 0, cus = 0;
         HIP_TRY(trace_occupancy(a->stack_depth, false, extra_lds, &per_cu));
         int per_cu_fast = 0;
@@ -190,7 +190,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                 }
                 stage.add(a->lds_image, img);
                 a->lds_image_n16 = (uint32_t)n16;
-                HIP_TRY(mega_set_lds_limit(LDS_MAX, true)); HIP_TRY(wf_set_lds_limit(LDS_MAX, true)); HIP_TRY(queue_set_lds_limit(LDS_MAX, true)); HIP_TRY(query_set_lds_limit(LDS_MAX, true)); HIP_TRY(rq_set_lds_limit(LDS_MAX, true)); HIP_TRY(visibility_set_lds_limit(LDS_MAX, true));
+                HIP_TRY(mega_set_lds_limit(LDS_MAX, true)); HIP_TRY(wf_set_lds_limit(LDS_MAX, true)); HIP_TRY(queue_set_lds_limit(LDS_MAX, true)); HIP_TRY(query_set_lds_limit(LDS_MAX, true)); HIP_TRY(rq_set_lds_limit(LDS_MAX, true)); HIP_TRY(visibility_set_lds_limit(LDS_MAX, true)); HIP_TRY(features_set_lds_limit(LDS_MAX, true));
                 a->ldss_blocks = (uint32_t)cus;
             }
             stage.add(a->accels, fm.accels); // with the compact bases

@@ -1,0 +1,132 @@
+// lasgun_amd/csrc/k_features.hip -- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of
+// the primary hits of the scene's own camera, the rays made in registers as the render makes them (camera_ray) and never written anywhere.
+//
+// The grid, the tile claim, the per-lane LDS stack, the scene / accel image in LDS and the walk are query_kernel's (k_query.hip), closest
+// hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged.  What differs is the work item: a tile is an 8 x 8 block of the rectangle
+// (pixel_of, mode 0, as the render's tiles) and a lane is one PIXEL.  The lane loops over the pixel's samples s = 0 .. S-1, so the whole
+// wave walks sample s together (64 neighbouring rays, as a render's wave) and each pixel's sums come out in sample order with no
+// cross-lane step: seven f64 accumulators, a hit count and sample 0's identity stay in registers across the walks.
+//
+// Out: only the planes asked for.  depth and coverage are one f32 a pixel (a tile row is 32 contiguous bytes); normal and albedo are
+// three f32 at a 12-byte pitch, written as three 4-byte stores -- a 16-byte store would reach into the neighbouring pixel, which may lie
+// outside the rectangle and is never touched (a tile row's 8 lanes still cover 96 contiguous bytes); id is one 16-byte store.  At most
+// 48 bytes a pixel, whatever S is.  Lanes outside the rectangle walk nothing and write nothing.
+#include "shade.h"
+
+namespace lg {
+
+struct FeatureArgs {
+    float *depth;               // [pixels]
+    float *normal;              // [pixels][3]
+    float *albedo;              // [pixels][3]
+    float *coverage;            // [pixels]
+    uint4 *id;                  // [pixels]: kind, prim, instance, material
+    const double *material_rgb; // [nmat][3], read only where albedo is asked for
+    uint32_t nmat;
+    const uint32_t *tri_base;   // per accel: its mesh's first triangle in the triangle tables (k_query.hip)
+};
+
+template <bool FAST, bool LDSS, bool PRUNE>
+__global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) features_kernel(const DParams P, const FeatureArgs Q) {
+    static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
+    static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t ntiles = P.ntiles;
+    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
+    uint32_t *stack = lds_stack + tid;
+    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint4 *scn = nullptr;
+    if (LDSS) {
+        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
+        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
+        __syncthreads();
+        scn = dst;
+    }
+    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
+    if (!wave_has_work(ntiles)) return;
+    const uint32_t S = P.ss_root * P.ss_root;
+    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
+    for (bool final = false; !final;) {
+        uint32_t tile;
+        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
+        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        if (tile == NO_TILE) break;
+        const Pixel px = pixel_of(P, tile, lane);
+        double tsum = 0.0;
+        V3 nsum{0.0, 0.0, 0.0}, asum{0.0, 0.0, 0.0};
+        uint32_t nhit = 0u;
+        uint4 id0 = make_uint4(0u, NO_HIT, NO_HIT, 0xFFFFFFFFu); // kind 0, prim / instance ~0, material -1: lg_hit's miss
+        for (uint32_t s = 0u; s < S; ++s) {
+            Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
+            if (px.active) ray = camera_ray(P, px.x, px.y, s);
+            Best b;
+            b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
+            if (px.active) walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+            if (!px.active || b.ref == NO_HIT) continue;
+            Shade sh;
+            shade_frame(P, ray, b, sh);
+            nhit += 1u;
+            tsum = tsum + b.t;
+            nsum = nsum + sh.ns;
+            if (Q.albedo && (uint32_t)sh.mat < Q.nmat) { // (an index outside the table, a negative one included, adds nothing)
+                const double *c = Q.material_rgb + 3ull * (uint32_t)sh.mat;
+                asum = asum + V3{c[0], c[1], c[2]};
+            }
+            if (s == 0u) {
+                const uint32_t pk = b.ref >> 30, idx = b.ref & PRIM_INDEX_MASK;
+                id0 = make_uint4(pk + 1u, pk == PK_TRIANGLE ? idx - Q.tri_base[b.accel] : idx, b.accel, (uint32_t)sh.mat);
+            }
+        }
+        if (!px.active) continue;
+        const double inv = 1.0 / (double)S;
+        const unsigned long long pix = px.pix;
+        if (Q.depth) Q.depth[pix] = nhit ? (float)(tsum * (1.0 / (double)nhit)) : INFINITY;
+        if (Q.normal) {
+            float *o = Q.normal + 3ull * pix;
+            o[0] = (float)(nsum.x * inv); o[1] = (float)(nsum.y * inv); o[2] = (float)(nsum.z * inv);
+        }
+        if (Q.albedo) {
+            float *o = Q.albedo + 3ull * pix;
+            o[0] = (float)(asum.x * inv); o[1] = (float)(asum.y * inv); o[2] = (float)(asum.z * inv);
+        }
+        if (Q.coverage) Q.coverage[pix] = (float)((double)nhit * inv);
+        if (Q.id) Q.id[pix] = id0;
+    }
+}
+
+// ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as query_kernel, LDS sized as launch_query sizes it.
+hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,
+                           const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    const FeatureArgs Q{depth, normal, albedo, coverage, reinterpret_cast<uint4 *>(id), material_rgb, nmat, tri_base};
+    const bool ldss = P.lds_image && !fast;
+    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
+    const uint32_t depth_words = fast ? stack_depth : P.stack_depth;
+    const size_t lds = (size_t)depth_words * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
+#define LG_F(F, L, Z) hipLaunchKernelGGL((features_kernel<F, L, Z>), dim3(blocks), dim3(block), lds, stream, P, Q)
+    if (fast) LG_F(true, false, false);
+    else if (P.prune) { if (ldss) LG_F(false, true, true); else LG_F(false, false, true); }
+    else { if (ldss) LG_F(false, true, false); else LG_F(false, false, false); }
+#undef LG_F
+    return hipGetLastError();
+}
+// workgroups per CU of the 256-lane forms
+hipError_t features_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
+    const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
+    const void *fn = fast ? reinterpret_cast<const void *>(features_kernel<true, false, false>)
+                          : prune ? reinterpret_cast<const void *>(features_kernel<false, false, true>) : reinterpret_cast<const void *>(features_kernel<false, false, false>);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, LG_BLOCK, lds);
+}
+// raise the dynamic-LDS limit of this file's kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
+hipError_t features_set_lds_limit(size_t bytes, bool ldss) {
+    const void *resident[] = {reinterpret_cast<const void *>(features_kernel<false, true, false>), reinterpret_cast<const void *>(features_kernel<false, true, true>)};
+    const void *plain[] = {reinterpret_cast<const void *>(features_kernel<false, false, false>), reinterpret_cast<const void *>(features_kernel<false, false, true>),
+                           reinterpret_cast<const void *>(features_kernel<true, false, false>)};
+    for (size_t i = 0; i < (ldss ? 2u : 3u); ++i) {
+        const hipError_t e = hipFuncSetAttribute(ldss ? resident[i] : plain[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+} // namespace lg

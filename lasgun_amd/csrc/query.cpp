@@ -1,11 +1,12 @@
 // lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_radiance*, lg_camera_rays*,
-// lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
+// lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.
 #include <cstddef>
 
+#include "features_host.h"
 #include "internal.h"
 
 static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hit, ng) == 32 && offsetof(lg_hit, ns) == 56 &&
@@ -348,6 +349,87 @@ static int capture_rays_device(const lg_accel *a, const double *dev_rays, size_t
     });
 }
 
+// ---- feature buffers (lg_capture_features*; k_features.hip): depth, normal, albedo, coverage and ids of the camera's primary hits.  The
+// struct handling that needs no device is features_host.h's.
+// One capture enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the rectangle and the buffers):
+// grid and launch context as enqueue_query's, a tile being an 8 x 8 block of the rectangle.  compact: the planes hold the rectangle's pixels
+// alone, row-major (the host form's staging); otherwise they are addressed like the film
+static void enqueue_features(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features &out, const double *material_rgb,
+                             bool compact, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, w, h);
+    set_rect(P, x0, y0, x1, y1);
+    if (compact) { P.out_row0 = y0; P.out_x0 = x0; P.out_pitch = x1 - x0; }
+    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    if (ldss) {
+        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
+        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+    }
+    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
+    uint32_t cap = a.ldss_blocks;
+    if (!ldss) {
+        int per_cu = 0;
+        HIP_TRY(features_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
+        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
+    }
+    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
+    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    P.tile_counter = c.tile_counter.p;
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(launch_features(P, out.depth, out.normal, out.albedo, out.coverage, out.id, out.albedo ? material_rgb : nullptr, (uint32_t)a.flat.material_pods.size(),
+                            a.accel_tri_base.p, a.fast, blocks, depth, stream));
+}
+// Host form: the table goes up, the rectangle's pixels come back COMPACT into staging and are placed at their film offsets here -- nothing
+// outside the rectangle is read or written, and an error on the way leaves the caller's planes as they were
+static int features_host(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *material_rgb) {
+    return guarded([&] {
+        const size_t pixels = check_features(a, out, w, h, x0, y0, x1, y1, material_rgb);
+        if (pixels == 0) return;
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        const size_t nmat = a->flat.material_pods.size();
+        FeatureStaging st(*out, pixels);
+        DevBuf<float> ddepth, dnormal, dalbedo, dcoverage;
+        DevBuf<uint32_t> did;
+        DevBuf<double> dtable;
+        lg_features dev{};
+        if (out->depth) { ddepth.alloc(pixels); dev.depth = ddepth.p; }
+        if (out->normal) { dnormal.alloc(pixels * 3); dev.normal = dnormal.p; }
+        if (out->albedo) { dalbedo.alloc(pixels * 3); dev.albedo = dalbedo.p; }
+        if (out->coverage) { dcoverage.alloc(pixels); dev.coverage = dcoverage.p; }
+        if (out->id) { did.alloc(pixels * 4); dev.id = did.p; }
+        if (out->albedo) {
+            dtable.alloc(std::max<size_t>(nmat * 3, 1));
+            if (nmat) HIP_TRY(hipMemcpyAsync(dtable.p, material_rgb, nmat * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        }
+        enqueue_features(*a, w, h, x0, y0, x1, y1, dev, dtable.p, true, a->stream);
+        if (out->depth) HIP_TRY(hipMemcpyAsync(st.depth.data(), ddepth.p, pixels * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->normal) HIP_TRY(hipMemcpyAsync(st.normal.data(), dnormal.p, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->albedo) HIP_TRY(hipMemcpyAsync(st.albedo.data(), dalbedo.p, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->coverage) HIP_TRY(hipMemcpyAsync(st.coverage.data(), dcoverage.p, pixels * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->id) HIP_TRY(hipMemcpyAsync(st.id.data(), did.p, pixels * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+        place_features(*out, st, w, x0, y0, x1, y1);
+    });
+}
+static int features_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *dev_material_rgb,
+                           void *hip_stream) {
+    return guarded([&] {
+        if (check_features(a, out, w, h, x0, y0, x1, y1, dev_material_rgb) == 0) return;
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        const size_t npix = (size_t)w * h, nmat = a->flat.material_pods.size();
+        if (out->depth) check_device_buffer(*a, out->depth, npix * sizeof(float), 4, "depth");
+        if (out->normal) check_device_buffer(*a, out->normal, npix * 3 * sizeof(float), 4, "normal");
+        if (out->albedo) check_device_buffer(*a, out->albedo, npix * 3 * sizeof(float), 4, "albedo");
+        if (out->coverage) check_device_buffer(*a, out->coverage, npix * sizeof(float), 4, "coverage");
+        if (out->id) check_device_buffer(*a, out->id, npix * 4 * sizeof(uint32_t), 16, "id");
+        if (out->albedo) check_device_buffer(*a, dev_material_rgb, nmat * 3 * sizeof(double), 8, "material_rgb");
+        enqueue_features(*a, w, h, x0, y0, x1, y1, *out, dev_material_rgb, false, (hipStream_t)hip_stream);
+    });
+}
+
 // ---- lens rays (lg_lens_rays*; k_lens.hip)
 static_assert(sizeof(lg_lens) == 112 && sizeof(DLens) == 112 && offsetof(lg_lens, origin) == 8 && offsetof(lg_lens, right) == 32 && offsetof(lg_lens, up) == 56 &&
                   offsetof(lg_lens, forward) == 80 && offsetof(lg_lens, fov_deg) == 104 && offsetof(DLens, fov_deg) == 104,
@@ -416,6 +498,19 @@ int lg_capture_rays(const lg_accel *a, const double *rays, size_t pixels, uint32
 int lg_capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_pixel_offsets, uint32_t width, uint32_t height,
                            void *dev_rgba, double *dev_rgb, void *hip_stream) {
     return capture_rays_device(a, dev_rays, pixels, samples, dev_pixel_offsets, width, height, dev_rgba, dev_rgb, hip_stream);
+}
+int lg_capture_features(const lg_accel *a, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out,
+                        const double *material_rgb) {
+    return features_host(a, width, height, x0, y0, x1, y1, out, material_rgb);
+}
+int lg_capture_features_device(const lg_accel *a, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *dev_out,
+                               const double *dev_material_rgb, void *hip_stream) {
+    return features_device(a, width, height, x0, y0, x1, y1, dev_out, dev_material_rgb, hip_stream);
+}
+size_t lg_accel_material_count(const lg_accel *a) {
+    if (!a) return 0;
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->flat.material_pods.size();
 }
 int lg_lens_rays(const lg_lens *lens, uint32_t width, uint32_t height, uint32_t samples_root, const uint64_t *pixel_offsets, size_t pixels, double *rays) {
     return guarded([&] {

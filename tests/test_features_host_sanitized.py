@@ -1,0 +1,24 @@
+"""The struct-handling host code of lg_capture_features* (lasgun_amd/csrc/features_host.h: argument validation, staging of the compact
+planes, their placement at the film's offsets, a NULL plane in every position) under AddressSanitizer and UBSan on the CPU: a stand-alone
+program with its own main (tools/features_host_check.cpp) that includes exactly the text query.cpp includes, with the launch stubbed out."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
+    cxx = shutil.which(os.environ.get("CXX", "g++")) or shutil.which("g++")
+    if cxx is None:
+        pytest.fail("no C++ compiler: the library itself could not have been built")
+    exe = str(tmp_path / "features_host_check")
+    subprocess.check_call([cxx, "-std=c++17", "-g", "-O1", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "features_host_check.cpp"), "-o", exe])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    run = subprocess.run([exe], capture_output=True, text=True, env=env)
+    assert run.returncode == 0 and "features_host_check: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
+    query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
+    assert '#include "features_host.h"' in query and "check_features(a, out," in query and "place_features(*out, st," in query, "query.cpp runs the text that was checked"

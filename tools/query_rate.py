@@ -23,7 +23,12 @@ yardstick: this row needs nothing the parent commit's library does not have, so 
 from the two point sets; row v8c: the bit matrix and the row counts.  Where both run, v8's bits are checked against x8's bytes.
 Each row: rays, ms per call (device events, mean over >= 20 timed calls after warm-up), Mrays/s, device_source_sha16; --repeats R measures
 everything R times (rows carry "repeat").
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility[,...]] [--out profiles/r08_query_order.jsonl]
+Feature buffers (lg_capture_features_device) -- --rows features, on the film of --size: row g8, all five planes (at most 48 bytes a pixel); row
+g8d, depth + id alone (20 bytes); beside them, in the same session, the route to the same information without them: row x8c,
+lg_camera_rays_device + lg_intersect_device on preallocated buffers (144 bytes a ray written, the per-pixel reduction still to do), and
+the closest-hit query alone on those rays in camera order (a) and in 8 x 8 pixel tiles (a8).  With one sample a pixel g8's depth and ids
+are checked against the hits.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -266,6 +271,49 @@ def measure_visibility(name, builder, calls, n=4096):
              "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, bps in rows]
 
 
+def measure_features(name, builder, size, calls):
+    """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    S_ = G.camera_samples(accel)
+    npix = size * size
+    n = npix * S_
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    rows = []
+    ms = timed(lambda: (G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s),
+                        G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s)), calls)
+    rows.append(("x8c: camera rays + closest on preallocated buffers (the two-call route, no reduction)", ms, 144.0 * S_))
+    ms = timed(lambda: G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s), calls)
+    rows.append(("a: closest, camera order", ms, 144.0 * S_))
+    if S_ == 1 and size % 8 == 0:
+        tiled = rays.view(size // 8, 8, size // 8, 8, 6).permute(0, 2, 1, 3, 4).contiguous().view(n, 6)
+        hits_b = torch.empty_like(hits)
+        ms = timed(lambda: G.intersect_device(accel, n, tiled.data_ptr(), hits_b.data_ptr(), stream=s), calls)
+        rows.append(("a8: closest, 8x8 pixel tiles", ms, 144.0 * S_))
+        del tiled, hits_b
+    if hasattr(G, "capture_features_device"):
+        depth, coverage = (torch.empty((npix,), dtype=torch.float32, device="cuda") for _ in range(2))
+        normal, albedo = (torch.empty((npix, 3), dtype=torch.float32, device="cuda") for _ in range(2))
+        ident = torch.empty((npix, 4), dtype=torch.int32, device="cuda")
+        table = torch.from_numpy(G.default_albedo_table(accel)).cuda()
+        ms = timed(lambda: G.capture_features_device(accel, size, size, None, depth.data_ptr(), normal.data_ptr(), albedo.data_ptr(), coverage.data_ptr(),
+                                                     ident.data_ptr(), table.data_ptr(), stream=s), calls)
+        rows.append(("g8: features, all five planes", ms, 48.0))
+        depth2, ident2 = torch.empty_like(depth), torch.empty_like(ident)
+        ms = timed(lambda: G.capture_features_device(accel, size, size, None, depth_ptr=depth2.data_ptr(), id_ptr=ident2.data_ptr(), stream=s), calls)
+        rows.append(("g8d: features, depth + id", ms, 20.0))
+        torch.cuda.synchronize()
+        assert torch.equal(depth, depth2) and torch.equal(ident, ident2), "g8d's planes are not g8's"
+        if S_ == 1:  # one sample: depth is (float)t and id the hit's last 16 bytes
+            assert torch.equal(ident, hits.view(torch.int32).view(-1, 24)[:, 20:24]), "g8's ids are not lg_intersect's"
+            assert torch.equal(depth, hits.view(torch.float64).view(-1, 12)[:, 0].float()), "g8's depth is not lg_intersect's t"
+    return [{"scene": name, "row": row, "film": [size, size], "samples": S_, "rays": n, "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1),
+             "bytes_per_pixel": bpp, "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel),
+             "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, bpp in rows]
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -295,7 +343,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -304,8 +352,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -313,7 +361,9 @@ def main():
             got = measure(name, builder, args.size, max(args.calls, 20), args.seed, args.order) if want & {"all", "queries"} else []
             if want & {"all", "visibility"}:
                 got += measure_visibility(name, builder, max(args.calls, 20))
-            if want - {"queries", "visibility"}:
+            if want & {"all", "features"}:
+                got += measure_features(name, builder, args.size, max(args.calls, 20))
+            if want - {"queries", "visibility", "features"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
