@@ -2,6 +2,13 @@
 // grids and budgets from the device's occupancy, one upload; and the tables once more with what was left out of them (fast trees, leaf records).
 #include "internal.h"
 
+// raise the dynamic-LDS limit of the traversal kernels of EVERY kernel file (ldss: their LDS-resident-scene forms; otherwise the 256-lane
+// forms): a kernel file with such kernels adds itself here
+static void set_lds_limits(size_t bytes, bool ldss) {
+    for (auto set : {mega_set_lds_limit, wf_set_lds_limit, queue_set_lds_limit, query_set_lds_limit, rq_set_lds_limit, visibility_set_lds_limit, features_set_lds_limit})
+        HIP_TRY(set(bytes, ldss));
+}
+
 static void build_and_upload(lg_accel *a, bool with_fast) {
     a->ldss_blocks = 0; a->lds_image_n16 = 0; a->fast_available = true;
         static const bool times = std::getenv("LASGUN_DEBUG_TIMES") != nullptr; // (where lg_accel_from's time goes: flatten / upload / derived)
@@ -94,7 +101,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         }
         const size_t extra_lds = (size_t)a->accel_image_n16 * 16;
         size_t lds = (size_t)std::max(a->stack_depth, a->stack_depth_fast1) * 256 * 4 + extra_lds;
-        if (lds > 64 * 1024) { HIP_TRY(mega_set_lds_limit(lds, false)); HIP_TRY(wf_set_lds_limit(lds, false)); HIP_TRY(queue_set_lds_limit(lds, false)); HIP_TRY(query_set_lds_limit(lds, false)); HIP_TRY(rq_set_lds_limit(lds, false)); HIP_TRY(visibility_set_lds_limit(lds, false)); HIP_TRY(features_set_lds_limit(lds, false)); }
+        if (lds > 64 * 1024) set_lds_limits(lds, false);
         int per_cu = 0, cus = 0;
         HIP_TRY(trace_occupancy(a->stack_depth, false, extra_lds, &per_cu));
         int per_cu_fast = 0;
@@ -190,7 +197,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                 }
                 stage.add(a->lds_image, img);
                 a->lds_image_n16 = (uint32_t)n16;
-                HIP_TRY(mega_set_lds_limit(LDS_MAX, true)); HIP_TRY(wf_set_lds_limit(LDS_MAX, true)); HIP_TRY(queue_set_lds_limit(LDS_MAX, true)); HIP_TRY(query_set_lds_limit(LDS_MAX, true)); HIP_TRY(rq_set_lds_limit(LDS_MAX, true)); HIP_TRY(visibility_set_lds_limit(LDS_MAX, true)); HIP_TRY(features_set_lds_limit(LDS_MAX, true));
+                set_lds_limits(LDS_MAX, true);
                 a->ldss_blocks = (uint32_t)cus;
             }
             stage.add(a->accels, fm.accels); // with the compact bases

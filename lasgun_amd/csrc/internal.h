@@ -44,7 +44,8 @@ size_t sort_scratch_bytes(unsigned long long n);
 hipError_t launch_query_order(const double *rays, unsigned long long n, const KeyBounds &B, void *scratch, uint32_t *keys_out, uint32_t *perm_out,
                               const uint32_t **perm, uint32_t grid_cap, hipStream_t stream);
 hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long n, uint32_t blocks, hipStream_t stream);
-hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
+// (the *_occupancy of the query kernels: workgroups per CU of the 256-lane form that P, without an LDS-resident scene, takes -- travform.h)
+hipError_t query_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t query_set_lds_limit(size_t bytes, bool ldss);
 hipError_t launch_wf_resolve(const DParams &P, uint32_t blocks, hipStream_t stream);
 // k_radiance.hip: level 0 of the level-by-level pipeline for a radiance query's rays (launch.cpp, enqueue_radiance)
@@ -64,13 +65,13 @@ hipError_t launch_lens_rays(const DLens &L, uint32_t w, uint32_t h, uint32_t roo
 // per wave; bit j of bits[i * row_bytes ..] and / or the row's count in blocked[i] (zeroed by the caller ahead of the launch)
 hipError_t launch_visibility(const DParams &P, const double *from, unsigned long long n_from, const double *to, unsigned long long n_to, uint8_t *bits,
                              unsigned long long row_bytes, uint32_t *blocked, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
-hipError_t visibility_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
+hipError_t visibility_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t visibility_set_lds_limit(size_t bytes, bool ldss);
 // k_features.hip: feature buffers (lg_capture_features*) -- the closest-hit walk of the camera's own rays, an 8 x 8 tile of the rectangle per
 // wave and a pixel per lane; only the planes that are not nullptr are written, at DParams' output addressing (out_row0 / out_x0 / out_pitch)
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,
                            const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
-hipError_t features_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu);
+hipError_t features_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t features_set_lds_limit(size_t bytes, bool ldss);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
@@ -470,6 +471,7 @@ lg_accel::LaunchCtx &ctx_for(const lg_accel &a, hipStream_t stream);
 void check_queue_error(const lg_accel &a);
 void sync_checked(const lg_accel &a);
 DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);
+void set_lds_scene(const lg_accel &a, DParams &P);
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);

@@ -1,17 +1,18 @@
 // lasgun_amd/csrc/k_features.hip -- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of
 // the primary hits of the scene's own camera, the rays made in registers as the render makes them (camera_ray) and never written anywhere.
 //
-// The grid, the tile claim, the per-lane LDS stack, the scene / accel image in LDS and the walk are query_kernel's (k_query.hip), closest
-// hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged.  What differs is the work item: a tile is an 8 x 8 block of the rectangle
-// (pixel_of, mode 0, as the render's tiles) and a lane is one PIXEL.  The lane loops over the pixel's samples s = 0 .. S-1, so the whole
-// wave walks sample s together (64 neighbouring rays, as a render's wave) and each pixel's sums come out in sample order with no
-// cross-lane step: seven f64 accumulators, a hit count and sample 0's identity stay in registers across the walks.
+// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
+// launched through travform.h.  The walk is closest hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged.  What differs is the work
+// item: a tile is an 8 x 8 block of the rectangle (pixel_of, mode 0, as the render's tiles) and a lane is one PIXEL.  The lane loops over
+// the pixel's samples s = 0 .. S-1, so the whole wave walks sample s together (64 neighbouring rays, as a render's wave) and each pixel's
+// sums come out in sample order with no cross-lane step: seven f64 accumulators, a hit count and sample 0's identity stay in registers
+// across the walks.
 //
 // Out: only the planes asked for.  depth and coverage are one f32 a pixel (a tile row is 32 contiguous bytes); normal and albedo are
 // three f32 at a 12-byte pitch, written as three 4-byte stores -- a 16-byte store would reach into the neighbouring pixel, which may lie
 // outside the rectangle and is never touched (a tile row's 8 lanes still cover 96 contiguous bytes); id is one 16-byte store.  At most
 // 48 bytes a pixel, whatever S is.  Lanes outside the rectangle walk nothing and write nothing.
-#include "shade.h"
+#include "travform.h"
 
 namespace lg {
 
@@ -95,38 +96,18 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
     }
 }
 
-// ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as query_kernel, LDS sized as launch_query sizes it.
+// ---- host-callable launchers (query.cpp): the forms and their three operations are travform.h's
+template <bool F, bool L, bool Z> struct FeatureKernels {
+    static constexpr int variants = 1;
+    static const void *kernel(int) { return reinterpret_cast<const void *>(features_kernel<F, L, Z>); }
+};
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,
                            const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
     const FeatureArgs Q{depth, normal, albedo, coverage, reinterpret_cast<uint4 *>(id), material_rgb, nmat, tri_base};
-    const bool ldss = P.lds_image && !fast;
-    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint32_t depth_words = fast ? stack_depth : P.stack_depth;
-    const size_t lds = (size_t)depth_words * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_F(F, L, Z) hipLaunchKernelGGL((features_kernel<F, L, Z>), dim3(blocks), dim3(block), lds, stream, P, Q)
-    if (fast) LG_F(true, false, false);
-    else if (P.prune) { if (ldss) LG_F(false, true, true); else LG_F(false, false, true); }
-    else { if (ldss) LG_F(false, true, false); else LG_F(false, false, false); }
-#undef LG_F
-    return hipGetLastError();
+    void *args[] = {const_cast<DParams *>(&P), const_cast<FeatureArgs *>(&Q)};
+    return trav_launch<FeatureKernels>(P, fast, 0, blocks, stack_depth, args, stream);
 }
-// workgroups per CU of the 256-lane forms
-hipError_t features_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
-    const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
-    const void *fn = fast ? reinterpret_cast<const void *>(features_kernel<true, false, false>)
-                          : prune ? reinterpret_cast<const void *>(features_kernel<false, false, true>) : reinterpret_cast<const void *>(features_kernel<false, false, false>);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, LG_BLOCK, lds);
-}
-// raise the dynamic-LDS limit of this file's kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
-hipError_t features_set_lds_limit(size_t bytes, bool ldss) {
-    const void *resident[] = {reinterpret_cast<const void *>(features_kernel<false, true, false>), reinterpret_cast<const void *>(features_kernel<false, true, true>)};
-    const void *plain[] = {reinterpret_cast<const void *>(features_kernel<false, false, false>), reinterpret_cast<const void *>(features_kernel<false, false, true>),
-                           reinterpret_cast<const void *>(features_kernel<true, false, false>)};
-    for (size_t i = 0; i < (ldss ? 2u : 3u); ++i) {
-        const hipError_t e = hipFuncSetAttribute(ldss ? resident[i] : plain[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+hipError_t features_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu) { return trav_occupancy<FeatureKernels>(P, fast, stack_depth, blocks_per_cu); }
+hipError_t features_set_lds_limit(size_t bytes, bool ldss) { return trav_set_lds_limit<FeatureKernels>(bytes, ldss); }
 
 } // namespace lg

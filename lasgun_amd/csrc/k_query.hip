@@ -10,7 +10,7 @@
 // PERM (lg_accel_set_query_order(1)): the tiles are cut from the SORTED order of the rays (k_sort.hip) -- slot s = tile * 64 + lane walks
 // ray i = perm[s], read from rays[6i] and answered in hits[6i] / occluded[i]: no gathered copy of the rays, no scatter pass over the hits
 // (either would move ~144 bytes a ray more).  perm is a permutation of 0 .. n-1, so every slot of the caller's arrays is written once.
-#include "shade.h"
+#include "travform.h"
 
 namespace lg {
 
@@ -102,71 +102,27 @@ __global__ void __launch_bounds__(LG_BLOCK) camera_rays_kernel(const DParams P, 
     }
 }
 
-// ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as wf_trace_kernel, LDS sized as launch_wf_trace sizes it.
-// perm != nullptr: the PERM forms
+// ---- host-callable launchers (query.cpp): the forms and their three operations are travform.h's.  Variants: ANY x PERM
+template <bool F, bool L, bool Z> struct QueryKernels {
+    static constexpr int variants = 4;
+    static const void *kernel(int v) {
+        const void *k[variants] = {reinterpret_cast<const void *>(query_kernel<F, L, Z, false, false>), reinterpret_cast<const void *>(query_kernel<F, L, Z, true, false>),
+                                   reinterpret_cast<const void *>(query_kernel<F, L, Z, false, true>), reinterpret_cast<const void *>(query_kernel<F, L, Z, true, true>)};
+        return k[v];
+    }
+};
+// occluded != nullptr: the any-hit variants; perm != nullptr: the PERM variants
 hipError_t launch_query(const DParams &P, const double *rays, unsigned long long n, void *hits, uint8_t *occluded, const uint32_t *tri_base,
                         const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
     const QueryArgs Q{rays, n, reinterpret_cast<uint4 *>(hits), occluded, tri_base, perm};
-    const bool any = occluded != nullptr;
-    const bool ldss = P.lds_image && !fast;
-    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint32_t depth = fast ? stack_depth : P.stack_depth;
-    const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_QP(F, L, Z, A) do { if (perm) hipLaunchKernelGGL((query_kernel<F, L, Z, A, true>), dim3(blocks), dim3(block), lds, stream, P, Q); \
-                               else hipLaunchKernelGGL((query_kernel<F, L, Z, A, false>), dim3(blocks), dim3(block), lds, stream, P, Q); } while (0)
-#define LG_Q(F, L, Z) do { if (any) LG_QP(F, L, Z, true); else LG_QP(F, L, Z, false); } while (0)
-    if (fast) LG_Q(true, false, false);
-    else if (P.prune) { if (ldss) LG_Q(false, true, true); else LG_Q(false, false, true); }
-    else { if (ldss) LG_Q(false, true, false); else LG_Q(false, false, false); }
-#undef LG_Q
-#undef LG_QP
-    return hipGetLastError();
+    void *args[] = {const_cast<DParams *>(&P), const_cast<QueryArgs *>(&Q)};
+    return trav_launch<QueryKernels>(P, fast, (occluded ? 1 : 0) + (perm ? 2 : 0), blocks, stack_depth, args, stream);
 }
 hipError_t launch_camera_rays(const DParams &P, double *rays, unsigned long long n, uint32_t blocks, hipStream_t stream) {
     hipLaunchKernelGGL(camera_rays_kernel, dim3(blocks), dim3(LG_BLOCK), 0, stream, P, rays, n);
     return hipGetLastError();
 }
-// workgroups per CU of the 256-lane forms (the smallest of closest and any-hit, as given and permuted)
-template <bool FAST, bool PRUNE> static hipError_t query_occupancy_of(size_t lds, int *blocks_per_cu) {
-    const void *fns[] = {reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, false, false>), reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, true, false>),
-                         reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, false, true>), reinterpret_cast<const void *>(query_kernel<FAST, false, PRUNE, true, true>)};
-    int least = 0;
-    for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
-        int v = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fns[i], LG_BLOCK, lds);
-        if (e != hipSuccess) return e;
-        if (i == 0 || v < least) least = v;
-    }
-    *blocks_per_cu = least;
-    return hipSuccess;
-}
-hipError_t query_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
-    const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
-    if (fast) return query_occupancy_of<true, false>(lds, blocks_per_cu);
-    if (prune) return query_occupancy_of<false, true>(lds, blocks_per_cu);
-    return query_occupancy_of<false, false>(lds, blocks_per_cu);
-}
-// raise the dynamic-LDS limit of this file's traversal kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
-template <bool FAST, bool LDSS, bool PRUNE> static hipError_t query_lds_limit_of(int bytes) {
-    const void *fns[] = {reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, false, false>), reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, true, false>),
-                         reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, false, true>), reinterpret_cast<const void *>(query_kernel<FAST, LDSS, PRUNE, true, true>)};
-    for (const void *f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-hipError_t query_set_lds_limit(size_t bytes, bool ldss) {
-    hipError_t e;
-    if (ldss) {
-        e = query_lds_limit_of<false, true, false>((int)bytes);
-        if (e == hipSuccess) e = query_lds_limit_of<false, true, true>((int)bytes);
-        return e;
-    }
-    e = query_lds_limit_of<false, false, false>((int)bytes);
-    if (e == hipSuccess) e = query_lds_limit_of<false, false, true>((int)bytes);
-    if (e == hipSuccess) e = query_lds_limit_of<true, false, false>((int)bytes);
-    return e;
-}
+hipError_t query_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu) { return trav_occupancy<QueryKernels>(P, fast, stack_depth, blocks_per_cu); }
+hipError_t query_set_lds_limit(size_t bytes, bool ldss) { return trav_set_lds_limit<QueryKernels>(bytes, ldss); }
 
 } // namespace lg

@@ -14,6 +14,7 @@
 //   * a finished ray is radiance[3r ..] = (0 + li) * 1.0, what integrate() leaves for a pixel of one sample (integrate.rs:16-20): no
 //     Pixel, no sample accumulator, no resolve pass.  Every r is written exactly once (perm is a permutation of 0 .. n-1).
 #include "wflevel.h"
+#include "travform.h"
 
 namespace lg {
 
@@ -173,32 +174,23 @@ __global__ void __launch_bounds__(LG_BLOCK) rf_resolve_kernel(const FilmArgs Q, 
     }
 }
 
-// ---- host-callable launchers (launch.cpp, enqueue_radiance).  The closest pass in the (FAST, LDSS, PRUNE) forms of wf_trace_kernel, its
-// LDS sized as launch_wf_trace sizes it; Q.perm != nullptr: the PERM forms.  A RadianceArgs launches the rq_ kernels, a FilmArgs the rf_ ones.
-template <bool F, bool L, bool Z, bool PERM> static void rq_launch_closest(const DParams &P, const RadianceArgs &Q, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((rq_closest_kernel<F, L, Z, PERM>), dim3(blocks), dim3(block), lds, stream, P, Q);
-}
-template <bool F, bool L, bool Z, bool PERM> static void rq_launch_closest(const DParams &P, const FilmArgs &Q, uint32_t blocks, uint32_t block, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((rf_closest_kernel<F, L, Z, PERM>), dim3(blocks), dim3(block), lds, stream, P, Q);
-}
-template <class ARGS> static hipError_t launch_closest_of(const DParams &P, const ARGS &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
-    const bool ldss = P.lds_image && !fast;
-    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint32_t depth = fast ? stack_depth : P.stack_depth;
-    const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_RQ(F, L, Z) do { if (Q.perm) rq_launch_closest<F, L, Z, true>(P, Q, blocks, block, lds, stream); \
-                            else rq_launch_closest<F, L, Z, false>(P, Q, blocks, block, lds, stream); } while (0)
-    if (fast) LG_RQ(true, false, false);
-    else if (P.prune) { if (ldss) LG_RQ(false, true, true); else LG_RQ(false, false, true); }
-    else { if (ldss) LG_RQ(false, true, false); else LG_RQ(false, false, false); }
-#undef LG_RQ
-    return hipGetLastError();
-}
+// ---- host-callable launchers (launch.cpp, enqueue_radiance).  The closest pass: the forms and their operations are travform.h's.
+// Variants: into radiance[] (rq_, a RadianceArgs) / into a film (rf_, a FilmArgs) x PERM (Q.perm != nullptr)
+template <bool F, bool L, bool Z> struct ClosestKernels {
+    static constexpr int variants = 4;
+    static const void *kernel(int v) {
+        const void *k[variants] = {reinterpret_cast<const void *>(rq_closest_kernel<F, L, Z, false>), reinterpret_cast<const void *>(rq_closest_kernel<F, L, Z, true>),
+                                   reinterpret_cast<const void *>(rf_closest_kernel<F, L, Z, false>), reinterpret_cast<const void *>(rf_closest_kernel<F, L, Z, true>)};
+        return k[v];
+    }
+};
 hipError_t launch_rq_closest(const DParams &P, const RadianceArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
-    return launch_closest_of(P, Q, fast, blocks, stack_depth, stream);
+    void *args[] = {const_cast<DParams *>(&P), const_cast<RadianceArgs *>(&Q)};
+    return trav_launch<ClosestKernels>(P, fast, Q.perm ? 1 : 0, blocks, stack_depth, args, stream);
 }
 hipError_t launch_rf_closest(const DParams &P, const FilmArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
-    return launch_closest_of(P, Q, fast, blocks, stack_depth, stream);
+    void *args[] = {const_cast<DParams *>(&P), const_cast<FilmArgs *>(&Q)};
+    return trav_launch<ClosestKernels>(P, fast, Q.perm ? 3 : 2, blocks, stack_depth, args, stream);
 }
 hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
     if (P.wf_levels == 1u) {
@@ -234,27 +226,6 @@ hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long 
     hipLaunchKernelGGL(rf_resolve_kernel, dim3(blocks), dim3(LG_BLOCK), 0, stream, Q, li, slots, samples);
     return hipGetLastError();
 }
-// raise the dynamic-LDS limit of the closest pass to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
-template <bool FAST, bool LDSS, bool PRUNE> static hipError_t rq_lds_limit_of(int bytes) {
-    const void *fns[] = {reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rq_closest_kernel<FAST, LDSS, PRUNE, true>),
-                         reinterpret_cast<const void *>(rf_closest_kernel<FAST, LDSS, PRUNE, false>), reinterpret_cast<const void *>(rf_closest_kernel<FAST, LDSS, PRUNE, true>)};
-    for (const void *f : fns) {
-        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-hipError_t rq_set_lds_limit(size_t bytes, bool ldss) {
-    hipError_t e;
-    if (ldss) {
-        e = rq_lds_limit_of<false, true, false>((int)bytes);
-        if (e == hipSuccess) e = rq_lds_limit_of<false, true, true>((int)bytes);
-        return e;
-    }
-    e = rq_lds_limit_of<false, false, false>((int)bytes);
-    if (e == hipSuccess) e = rq_lds_limit_of<false, false, true>((int)bytes);
-    if (e == hipSuccess) e = rq_lds_limit_of<true, false, false>((int)bytes);
-    return e;
-}
+hipError_t rq_set_lds_limit(size_t bytes, bool ldss) { return trav_set_lds_limit<ClosestKernels>(bytes, ldss); }
 
 } // namespace lg

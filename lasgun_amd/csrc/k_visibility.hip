@@ -1,17 +1,18 @@
 // lasgun_amd/csrc/k_visibility.hip -- visibility matrices (include/lasgun_hip.h, lg_visibility*): occlusion between two point sets, the
 // segments made in registers as the render's shadow pass makes its own (k_wavefront.hip: hit point and light position), the answer bit-packed.
 //
-// The grid, the tile claim, the per-lane LDS stack, the scene / accel image in LDS and the walk are query_kernel's (k_query.hip), any-hit:
-// walk<LDSS, FAST, PRUNE>(.., any = true, ..), unchanged.  What differs is the work item: an 8 x 8 BLOCK of the matrix.  Lane l of the wave
-// that claimed block (ti, tj) walks the segment from[8 ti + (l >> 3)] -> to[8 tj + (l & 7)]: a wave reads 8 + 8 points (384 bytes) where
-// lg_occluded reads 64 rays (3 KiB), and its 64 segments share 8 origins and 8 targets.  Blocks are numbered row-major (tile = ti * tiles_j
-// + tj): consecutive tiles keep their origins and step through the targets.  Lanes outside the matrix walk nothing and vote 0.
+// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
+// launched through travform.h.  The walk is any-hit: walk<LDSS, FAST, PRUNE>(.., any = true, ..), unchanged.  What differs is the work
+// item: an 8 x 8 BLOCK of the matrix.  Lane l of the wave that claimed block (ti, tj) walks the segment from[8 ti + (l >> 3)] ->
+// to[8 tj + (l & 7)]: a wave reads 8 + 8 points (384 bytes) where lg_occluded reads 64 rays (3 KiB), and its 64 segments share 8 origins
+// and 8 targets.  Blocks are numbered row-major (tile = ti * tiles_j + tj): consecutive tiles keep their origins and step through the
+// targets.  Lanes outside the matrix walk nothing and vote 0.
 //
 // One ballot of the verdict per wave; in each of the block's 8 rows the lane with (l & 7) == 0 takes its row's byte out of the mask and
 // stores it at bits[row * row_bytes + tj] -- every used byte is written exactly once, padding bits 0 (the lanes behind n_to voted 0), no
 // atomics and no pre-clear -- and adds the byte's popcount to blocked[row] (zeroed on the same stream ahead of the launch, query.cpp;
 // integer addition: the counts do not depend on the order the blocks finish in).
-#include "shade.h"
+#include "travform.h"
 
 namespace lg {
 
@@ -69,38 +70,18 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
     }
 }
 
-// ---- host-callable launchers (query.cpp).  The same (FAST, LDSS, PRUNE) forms as query_kernel, LDS sized as launch_query sizes it.
+// ---- host-callable launchers (query.cpp): the forms and their three operations are travform.h's
+template <bool F, bool L, bool Z> struct VisibilityKernels {
+    static constexpr int variants = 1;
+    static const void *kernel(int) { return reinterpret_cast<const void *>(visibility_kernel<F, L, Z>); }
+};
 hipError_t launch_visibility(const DParams &P, const double *from, unsigned long long n_from, const double *to, unsigned long long n_to, uint8_t *bits,
                              unsigned long long row_bytes, uint32_t *blocked, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
     const VisibilityArgs Q{from, to, n_from, n_to, bits, row_bytes, blocked, (uint32_t)((n_to + 7ull) / 8ull)};
-    const bool ldss = P.lds_image && !fast;
-    const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint32_t depth = fast ? stack_depth : P.stack_depth;
-    const size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
-#define LG_V(F, L, Z) hipLaunchKernelGGL((visibility_kernel<F, L, Z>), dim3(blocks), dim3(block), lds, stream, P, Q)
-    if (fast) LG_V(true, false, false);
-    else if (P.prune) { if (ldss) LG_V(false, true, true); else LG_V(false, false, true); }
-    else { if (ldss) LG_V(false, true, false); else LG_V(false, false, false); }
-#undef LG_V
-    return hipGetLastError();
+    void *args[] = {const_cast<DParams *>(&P), const_cast<VisibilityArgs *>(&Q)};
+    return trav_launch<VisibilityKernels>(P, fast, 0, blocks, stack_depth, args, stream);
 }
-// workgroups per CU of the 256-lane forms
-hipError_t visibility_occupancy(uint32_t stack_depth, bool fast, bool prune, size_t extra_lds, int *blocks_per_cu) {
-    const size_t lds = (size_t)stack_depth * LG_BLOCK * sizeof(uint32_t) + (fast ? 0u : extra_lds);
-    const void *fn = fast ? reinterpret_cast<const void *>(visibility_kernel<true, false, false>)
-                          : prune ? reinterpret_cast<const void *>(visibility_kernel<false, false, true>) : reinterpret_cast<const void *>(visibility_kernel<false, false, false>);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, LG_BLOCK, lds);
-}
-// raise the dynamic-LDS limit of this file's kernels to `bytes` (ldss: the LDS-resident-scene forms; otherwise the 256-lane forms)
-hipError_t visibility_set_lds_limit(size_t bytes, bool ldss) {
-    const void *resident[] = {reinterpret_cast<const void *>(visibility_kernel<false, true, false>), reinterpret_cast<const void *>(visibility_kernel<false, true, true>)};
-    const void *plain[] = {reinterpret_cast<const void *>(visibility_kernel<false, false, false>), reinterpret_cast<const void *>(visibility_kernel<false, false, true>),
-                           reinterpret_cast<const void *>(visibility_kernel<true, false, false>)};
-    for (size_t i = 0; i < (ldss ? 2u : 3u); ++i) {
-        const hipError_t e = hipFuncSetAttribute(ldss ? resident[i] : plain[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+hipError_t visibility_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu) { return trav_occupancy<VisibilityKernels>(P, fast, stack_depth, blocks_per_cu); }
+hipError_t visibility_set_lds_limit(size_t bytes, bool ldss) { return trav_set_lds_limit<VisibilityKernels>(bytes, ldss); }
 
 } // namespace lg

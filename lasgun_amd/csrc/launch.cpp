@@ -89,6 +89,12 @@ void ensure_aux_streams(const lg_accel &a, unsigned n) {
     if (!a.aux_fork) HIP_TRY(hipEventCreateWithFlags(&a.aux_fork, hipEventDisableTiming));
 }
 
+// the LDS-resident scene into a launch's parameters: the kernels then run in their 1024-lane forms and read the tables from LDS
+void set_lds_scene(const lg_accel &a, DParams &P) {
+    P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
+    P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+}
+
 // ---- the two organisations that keep every recursion level's rays in arrays of their own (k_wavefront.hip, k_queue.hip) -------------
 static uint32_t levels_of(const lg_accel &a, const DParams &P) { return (a.flat.has_specular && P.recursion > 0) ? P.recursion + 1u : 1u; }
 constexpr size_t WF_FULL_MIN_HOST = 48; // == WF_FULL_MIN of k_wavefront.hip
@@ -241,10 +247,7 @@ struct WfChunk {
         P.wf_levels = levels;
         P.wf_counts = counters;
         P.wf_hit_cap = hit_cap(); P.wf_hit_stride = hit_len(); P.wf_hq = hq; P.frame = frame; P.vis = vis;
-        if (ldss) {
-            P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-            P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-        }
+        if (ldss) set_lds_scene(a, P);
     }
     // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
     // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms).
@@ -483,10 +486,7 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
         P.q_units = (P.q_seq_len + P.q_unit_tiles - 1u) / P.q_unit_tiles;
         for (uint32_t d = 0; d < levels; ++d) { P.q_rays[d] = K.q[d]; P.q_out[d] = K.out[d]; P.q_spec[d] = K.spec[d]; P.q_child[d] = K.child[d]; }
         P.stash = c.stash.p; P.frame_threads = threads;
-        if (ldss) {
-            P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-            P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-        }
+        if (ldss) set_lds_scene(a, P);
         const uint32_t blocks = ldss ? blocks_cap : std::min(blocks_cap, (P.q_units + 3u) / 4u);
         for (uint32_t sidx = 0; sidx < nsamples / (S / parts); ++sidx) {
             P.sample_index = sidx;
@@ -579,8 +579,7 @@ static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, 
     if (blocks > cap) blocks = cap;
     uint32_t maxb = a.max_blocks > a.max_blocks_fast ? a.max_blocks : a.max_blocks_fast;
     if (!stats && !a.fast && a.lds_scene && a.ldss_blocks) { // scene tables resident in LDS: one 1024-lane workgroup per CU
-        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+        set_lds_scene(a, P);
         P.mega_lanes = a.mega_narrow ? 768u : 1024u; // (k_mega.hip: three waves per SIMD and 168 registers where shading weighs more than walking)
         blocks = a.ldss_blocks;
     }

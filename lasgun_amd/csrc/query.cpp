@@ -67,31 +67,43 @@ static const uint32_t *enqueue_query_order(const lg_accel &a, lg_accel::LaunchCt
     return perm;
 }
 
+// ... for a query of `n` rays where the accel walks its queries in sorted order; nullptr: as given
+static const uint32_t *query_order_of(const lg_accel &a, lg_accel::LaunchCtx &c, const double *rays, size_t n, hipStream_t stream) {
+    return a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
+}
+
+// The grid of a tiled traversal launch of P.ntiles tiles, a wave each (k_query.hip, k_visibility.hip, k_features.hip), sized like the render's
+// level-by-level traversal passes: the scene resident in LDS -> its tables into P and one 1024-lane workgroup per CU; otherwise as many
+// 256-lane workgroups as the kernel family's `occupancy` lets a CU hold; never more workgroups than the tiles fill with waves.  P gets the
+// context's tile counter, cleared on `stream` here.  `depth`: the stack depth the launcher is told.
+struct TraversalGrid { uint32_t blocks, depth; };
+static TraversalGrid traversal_grid(const lg_accel &a, DParams &P, hipError_t (*occupancy)(const DParams &, bool, uint32_t, int *), lg_accel::LaunchCtx &c,
+                                    hipStream_t stream) {
+    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
+    uint32_t cap = a.ldss_blocks;
+    if (ldss) set_lds_scene(a, P);
+    else {
+        int per_cu = 0;
+        HIP_TRY(occupancy(P, a.fast, depth, &per_cu));
+        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
+    }
+    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
+    P.tile_counter = c.tile_counter.p;
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    return {std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block)), depth};
+}
+
 // One query enqueued on `stream` (caller holds a.mtx and has made the accel's device current): hits != nullptr for closest hits,
 // occluded != nullptr for the any-hit walk
 static void enqueue_query(const lg_accel &a, const double *rays, size_t n, lg_hit *hits, uint8_t *occluded, hipStream_t stream) {
     check_queue_error(a);
     DParams P = base_params(a, 1, 1);
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    if (ldss) {
-        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-    }
     P.ntiles = (uint32_t)((n + 63) / 64);
-    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
-    uint32_t cap = a.ldss_blocks;
-    if (!ldss) {
-        int per_cu = 0;
-        HIP_TRY(query_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
-        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
-    }
-    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
-    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    P.tile_counter = c.tile_counter.p;
-    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
-    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
-    HIP_TRY(launch_query(P, rays, n, hits, occluded, a.accel_tri_base.p, perm, a.fast, blocks, depth, stream));
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream); // (ahead of the counter's memset on the stream)
+    const TraversalGrid g = traversal_grid(a, P, query_occupancy, c, stream);
+    HIP_TRY(launch_query(P, rays, n, hits, occluded, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
 }
 
 static void check_sorted_count(const lg_accel &a, size_t n) {
@@ -150,36 +162,20 @@ static void check_visibility(const lg_accel *a, const double *from, size_t n_fro
     if (ti > 0xFFFFFFFFull / used) throw Error("too many segments in one visibility matrix: 8 x 8 blocks are counted in 32 bits");
     if (bits && n_from > 1 && row_bytes > (SIZE_MAX - used) / (n_from - 1)) throw Error("bits: n_from rows of row_bytes bytes do not fit the address space");
 }
-// One matrix enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): grid and
-// launch context as enqueue_query's, a tile being an 8 x 8 block
+// One matrix enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): a tile is
+// an 8 x 8 block
 static void enqueue_visibility(const lg_accel &a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked,
                                hipStream_t stream) {
     check_queue_error(a);
     DParams P = base_params(a, 1, 1);
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    if (ldss) {
-        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-    }
     P.ntiles = (uint32_t)(((n_from + 7) / 8) * visibility_used_bytes(n_to));
-    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
-    uint32_t cap = a.ldss_blocks;
-    if (!ldss) {
-        int per_cu = 0;
-        HIP_TRY(visibility_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
-        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
-    }
-    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
-    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
-    lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    P.tile_counter = c.tile_counter.p;
-    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    const TraversalGrid g = traversal_grid(a, P, visibility_occupancy, ctx_for(a, stream), stream);
     if (blocked) HIP_TRY(hipMemsetAsync(blocked, 0, n_from * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
-    HIP_TRY(launch_visibility(P, from, n_from, to, n_to, bits, row_bytes, blocked, a.fast, blocks, depth, stream));
+    HIP_TRY(launch_visibility(P, from, n_from, to, n_to, bits, row_bytes, blocked, a.fast, g.blocks, g.depth, stream));
 }
 // Host form: the points go up, the rows come back COMPACT (ceil(n_to / 8) bytes each) and are placed into the caller's stride here -- the
 // bytes of a row behind its used part are never written
-static int visibility_host(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked) {
+extern "C" int lg_visibility(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked) {
     return guarded([&] {
         if (n_from == 0 || n_to == 0) return;
         check_visibility(a, from, n_from, to, n_to, bits, row_bytes, blocked);
@@ -206,7 +202,7 @@ static int visibility_host(const lg_accel *a, const double *from, size_t n_from,
         if (blocked) std::memcpy(blocked, counts.data(), n_from * sizeof(uint32_t));
     });
 }
-static int visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
+extern "C" int lg_visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
                              uint32_t *dev_blocked, void *hip_stream) {
     return guarded([&] {
         if (n_from == 0 || n_to == 0) return;
@@ -233,10 +229,10 @@ static void radiance_possible(const lg_accel &a) {
 static void enqueue_radiance_query(const lg_accel &a, const double *rays, size_t n, double *radiance, hipStream_t stream) {
     check_queue_error(a);
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream);
     enqueue_radiance(a, rays, n, radiance, perm, c, stream);
 }
-static int radiance_host(const lg_accel *a, const double *rays, size_t n, double *radiance) {
+extern "C" int lg_radiance(const lg_accel *a, const double *rays, size_t n, double *radiance) {
     return guarded([&] {
         if (n == 0) return;
         if (!a) throw Error("accel is NULL");
@@ -256,7 +252,7 @@ static int radiance_host(const lg_accel *a, const double *rays, size_t n, double
         sync_checked(*a);
     });
 }
-static int radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
+extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
     return guarded([&] {
         if (n == 0) return;
         if (!a) throw Error("accel is NULL");
@@ -277,7 +273,7 @@ static size_t film_ray_count(const lg_accel &a, size_t pixels, uint32_t samples)
     if (samples == 0) throw Error("samples is 0: a pixel slot has at least one ray");
     if (pixels > MAX_RAYS / samples) throw Error("too many rays in one query (pixels * samples)");
     const size_t n = pixels * (size_t)samples;
-    if (a.query_order == 1 && n > MAX_SORTED_RAYS) throw Error("too many rays in one query for the sorted order (lg_accel_set_query_order): at most 2^32 - 1");
+    check_sorted_count(a, n);
     return n;
 }
 // One film query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the counts and the buffers)
@@ -286,14 +282,14 @@ static void enqueue_film_query(const lg_accel &a, const double *rays, size_t pix
     check_queue_error(a);
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
     const size_t n = pixels * (size_t)samples;
-    const uint32_t *perm = a.query_order == 1 && n >= SORT_MIN_RAYS ? enqueue_query_order(a, c, rays, n, nullptr, nullptr, stream) : nullptr;
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream);
     FilmArgs F{};
     F.offsets = offsets; F.npix = npix; F.rgba = rgba; F.rgb = rgb;
     enqueue_ray_film(a, rays, pixels, samples, F, perm, c, stream);
 }
 // Host form: the rays go up, the slots' pixels come back COMPACT (slot g at g: pixels * 4 and / or pixels * 24 bytes, nothing else is
 // copied) and are placed at their offsets here -- so a pixel no slot names is never touched, and a slot behind the film is dropped.
-static int capture_rays_host(const lg_accel *a, const double *rays, size_t pixels, uint32_t samples, const uint64_t *offsets, lg_film *film, double *rgb,
+extern "C" int lg_capture_rays(const lg_accel *a, const double *rays, size_t pixels, uint32_t samples, const uint64_t *offsets, lg_film *film, double *rgb,
                              uint32_t w, uint32_t h) {
     return guarded([&] {
         if (pixels == 0) return;
@@ -328,7 +324,7 @@ static int capture_rays_host(const lg_accel *a, const double *rays, size_t pixel
         }
     });
 }
-static int capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_offsets, uint32_t w, uint32_t h,
+extern "C" int lg_capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_offsets, uint32_t w, uint32_t h,
                                void *dev_rgba, double *dev_rgb, void *hip_stream) {
     return guarded([&] {
         if (pixels == 0) return;
@@ -352,7 +348,7 @@ static int capture_rays_device(const lg_accel *a, const double *dev_rays, size_t
 // ---- feature buffers (lg_capture_features*; k_features.hip): depth, normal, albedo, coverage and ids of the camera's primary hits.  The
 // struct handling that needs no device is features_host.h's.
 // One capture enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the rectangle and the buffers):
-// grid and launch context as enqueue_query's, a tile being an 8 x 8 block of the rectangle.  compact: the planes hold the rectangle's pixels
+// a tile is an 8 x 8 block of the rectangle (set_rect).  compact: the planes hold the rectangle's pixels
 // alone, row-major (the host form's staging); otherwise they are addressed like the film
 static void enqueue_features(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features &out, const double *material_rgb,
                              bool compact, hipStream_t stream) {
@@ -360,29 +356,13 @@ static void enqueue_features(const lg_accel &a, uint32_t w, uint32_t h, uint32_t
     DParams P = base_params(a, w, h);
     set_rect(P, x0, y0, x1, y1);
     if (compact) { P.out_row0 = y0; P.out_x0 = x0; P.out_pitch = x1 - x0; }
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    if (ldss) {
-        P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
-        P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
-    }
-    const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
-    uint32_t cap = a.ldss_blocks;
-    if (!ldss) {
-        int per_cu = 0;
-        HIP_TRY(features_occupancy(depth, a.fast, P.prune != 0, P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u, &per_cu));
-        cap = (uint32_t)(per_cu < 1 ? 1 : per_cu) * a.cus;
-    }
-    const uint32_t waves_per_block = (ldss ? 1024u : 256u) / 64u;
-    const uint32_t blocks = std::max(1u, std::min(cap, (P.ntiles + waves_per_block - 1u) / waves_per_block));
-    lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    P.tile_counter = c.tile_counter.p;
-    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    const TraversalGrid g = traversal_grid(a, P, features_occupancy, ctx_for(a, stream), stream);
     HIP_TRY(launch_features(P, out.depth, out.normal, out.albedo, out.coverage, out.id, out.albedo ? material_rgb : nullptr, (uint32_t)a.flat.material_pods.size(),
-                            a.accel_tri_base.p, a.fast, blocks, depth, stream));
+                            a.accel_tri_base.p, a.fast, g.blocks, g.depth, stream));
 }
 // Host form: the table goes up, the rectangle's pixels come back COMPACT into staging and are placed at their film offsets here -- nothing
 // outside the rectangle is read or written, and an error on the way leaves the caller's planes as they were
-static int features_host(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *material_rgb) {
+extern "C" int lg_capture_features(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *material_rgb) {
     return guarded([&] {
         const size_t pixels = check_features(a, out, w, h, x0, y0, x1, y1, material_rgb);
         if (pixels == 0) return;
@@ -413,7 +393,7 @@ static int features_host(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0,
         place_features(*out, st, w, x0, y0, x1, y1);
     });
 }
-static int features_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *dev_material_rgb,
+extern "C" int lg_capture_features_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *dev_material_rgb,
                            void *hip_stream) {
     return guarded([&] {
         if (check_features(a, out, w, h, x0, y0, x1, y1, dev_material_rgb) == 0) return;
@@ -477,36 +457,8 @@ int lg_intersect_device(const lg_accel *a, const double *dev_rays, size_t n, lg_
 int lg_occluded_device(const lg_accel *a, const double *dev_rays, size_t n, uint8_t *dev_occluded, void *hip_stream) {
     return query_device(a, dev_rays, n, dev_occluded, true, hip_stream);
 }
+// (lg_visibility*, lg_radiance*, lg_capture_rays* and lg_capture_features* are defined in their sections above)
 
-int lg_visibility(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, uint8_t *bits, size_t row_bytes, uint32_t *blocked) {
-    return visibility_host(a, from, n_from, to, n_to, bits, row_bytes, blocked);
-}
-int lg_visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
-                         uint32_t *dev_blocked, void *hip_stream) {
-    return visibility_device(a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, hip_stream);
-}
-
-int lg_radiance(const lg_accel *a, const double *rays, size_t n, double *radiance) { return radiance_host(a, rays, n, radiance); }
-int lg_radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
-    return radiance_device(a, dev_rays, n, dev_radiance, hip_stream);
-}
-
-int lg_capture_rays(const lg_accel *a, const double *rays, size_t pixels, uint32_t samples, const uint64_t *pixel_offsets, lg_film *film, double *rgb, uint32_t width,
-                    uint32_t height) {
-    return capture_rays_host(a, rays, pixels, samples, pixel_offsets, film, rgb, width, height);
-}
-int lg_capture_rays_device(const lg_accel *a, const double *dev_rays, size_t pixels, uint32_t samples, const uint64_t *dev_pixel_offsets, uint32_t width, uint32_t height,
-                           void *dev_rgba, double *dev_rgb, void *hip_stream) {
-    return capture_rays_device(a, dev_rays, pixels, samples, dev_pixel_offsets, width, height, dev_rgba, dev_rgb, hip_stream);
-}
-int lg_capture_features(const lg_accel *a, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out,
-                        const double *material_rgb) {
-    return features_host(a, width, height, x0, y0, x1, y1, out, material_rgb);
-}
-int lg_capture_features_device(const lg_accel *a, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *dev_out,
-                               const double *dev_material_rgb, void *hip_stream) {
-    return features_device(a, width, height, x0, y0, x1, y1, dev_out, dev_material_rgb, hip_stream);
-}
 size_t lg_accel_material_count(const lg_accel *a) {
     if (!a) return 0;
     std::lock_guard<std::mutex> g(a->mtx);

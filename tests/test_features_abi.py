@@ -118,7 +118,8 @@ def test_the_kernel_is_a_device_kernel_of_its_own():
     assert "atomic" not in src.replace("claim_tile", ""), "the sums need no cross-lane or cross-wave step"
     assert "k_features.o" in read("lasgun_amd", "csrc", "Makefile")
     host = read("lasgun_amd", "csrc", "query.cpp")
-    body = host[host.index("static void enqueue_features("):host.index("static int features_host(")]
+    body = host[host.index("static void enqueue_features("):host.index('extern "C" int lg_capture_features(')]
     assert "set_rect(P, x0, y0, x1, y1)" in body and "P.out_row0 = y0; P.out_x0 = x0; P.out_pitch = x1 - x0;" in body
-    assert body.index("hipMemsetAsync(c.tile_counter.p, 0,") < body.index("launch_features(")
+    grid = host[host.index("static TraversalGrid traversal_grid("):host.index("static void enqueue_query(")]  # the one place that sizes a query-style launch
+    assert "hipMemsetAsync(c.tile_counter.p, 0," in grid and body.index("traversal_grid(") < body.index("launch_features(")
     assert "launch_query(" not in body and "launch_camera_rays(" not in body

@@ -92,6 +92,6 @@ def test_the_kernel_is_a_device_kernel_of_its_own():
     assert "claim_tile(" in src and "claim_tile_single(" in src and "__builtin_amdgcn_ballot_w64(" in src
     assert "k_visibility.o" in read("lasgun_amd", "csrc", "Makefile")
     host = read("lasgun_amd", "csrc", "query.cpp")
-    body = host[host.index("static void enqueue_visibility("):host.index("static int visibility_host(")]
+    body = host[host.index("static void enqueue_visibility("):host.index('extern "C" int lg_visibility(')]
     assert body.index("hipMemsetAsync(blocked, 0,") < body.index("launch_visibility(")
     assert "lg_occluded" not in body and "launch_query(" not in body
