@@ -242,6 +242,11 @@ int lg_accel_set_mode(const lg_accel *, int mode);
  * the accel build: profiles/r05_prune_threshold.jsonl -- rounds 3-5 had 256), off otherwise; 0 / 1: off / on (1 on an accel whose
  * tables were built without the leaf records builds them then). */
 int lg_accel_set_prune(const lg_accel *, int enabled);
+/* Level-by-level pipeline: the closest pass flags the hits at which no light can contribute whether or not it is visible -- BSDF::f is
+ * exactly zero when the light and the viewer are on opposite sides of the geometric normal, so the light's term is +-0 either way -- and
+ * the shadow pass does not walk them.  Exact; applies to scenes of 1 .. 32 lights of finite intensity.  1 (default):
+ * on; 0: every hit's shadow rays are walked (A/B, tests; LASGUN_SHADOW_SKIP=0 does the same for every accel).  Same bytes either way. */
+int lg_accel_set_shadow_skip(const lg_accel *, int enabled);
 int lg_accel_get_prune(const lg_accel *); /* the effective setting (accel default, LASGUN_PRUNE, lg_accel_set_prune, fast mode): 0 / 1 */
 
 /* Kernel organisation (same arithmetic, same bytes either way).  1 (default): the organisation of a launch is MEASURED -- the SECOND

@@ -39,6 +39,7 @@ _EXTRA = {
     "accel_stream": (_C.c_void_p, [_C.c_void_p]),
     "accel_set_mode": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_prune": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_set_shadow_skip": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
     "accel_last_organisation": (_C.c_int, [_C.c_void_p]),
@@ -150,6 +151,12 @@ class HipApi(Api):
         """Pruned form of the reference traversal: None / -1 = the accel's default (on for scenes with a mesh of >= 4096
         triangles), False / True = off / on (include/lasgun_hip.h, lg_accel_set_prune)."""
         if self.call("accel_set_prune", accel.h, -1 if enabled is None or enabled == -1 else (1 if enabled else 0)):
+            raise LasgunError(self.last_error())
+
+    def set_shadow_skip(self, accel, enabled):
+        """Level-by-level pipeline: skip the shadow walks of hits at which no light's term depends on its visibility (default on; same bytes
+        either way; include/lasgun_hip.h, lg_accel_set_shadow_skip)."""
+        if self.call("accel_set_shadow_skip", accel.h, 1 if enabled else 0):
             raise LasgunError(self.last_error())
 
     def last_organisation(self, accel):

@@ -706,6 +706,12 @@ int lg_accel_set_prune(const lg_accel *a, int enabled) {
     }
     return 0;
 }
+int lg_accel_set_shadow_skip(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("shadow skip must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->shadow_skip = enabled == 1;
+    return 0;
+}
 int lg_accel_set_mode(const lg_accel *a, int mode) {
     if (mode != 0 && mode != 1) return fail("mode must be 0 (reference traversal) or 1 (fast)");
     std::lock_guard<std::mutex> g(a->mtx);

@@ -29,6 +29,9 @@ enum PrimKind : uint32_t { PK_SPHERE = 0, PK_CUBOID = 1, PK_TRIANGLE = 2, PK_ACC
 constexpr uint32_t PRIM_INDEX_MASK = 0x3FFFFFFFu;
 constexpr uint32_t NO_HIT = 0xFFFFFFFFu;
 constexpr uint32_t WF_NONE = 0xFFFFFFFFu, WF_MISS = 0xFFFFFFFEu; // wavefront pipeline: no such child / the ray hit nothing
+// ... and in a hit's wf_hq word, above the ray index (the host keeps a level-by-level chunk's ray indices below 2^31 - 16): no light's term
+// at this hit depends on the light being visible -- the shadow pass skips the hit, its visibility word is 0 (DParams::shadow_skip)
+constexpr uint32_t WF_SKIP = 0x80000000u;
 constexpr int MAX_CHAIN = 8;      // scene-graph nesting levels (root = 1)
 // tile counters of a persistent kernel (kcommon.h, claim_tile): word [0] the single-head forms' next tile, word [TILE_GONE] one bit per XCD band
 // that is known to be exhausted (a line no claim touches), then one head word per XCD band from [TILE_HEAD0] on, 128 bytes -- one L2 line -- apart
@@ -331,6 +334,10 @@ struct DParams {
     unsigned long long *stamp_counts; // diagnostic build (-DLG_STAMPS) only
     uint32_t stats_filter;      // counting variant: 0 = all traversals, 1 = closest-hit (primary/secondary) only, 2 = shadow only
     uint32_t audit;             // counting variant: also audit what the pruned walk skips (walk.h, audit_prim)
+    // level-by-level pipeline: the closest pass flags the hits at which no light's term can depend on its visibility (shade.h,
+    // shadow_skippable; WF_SKIP in the hit's wf_hq word) and the shadow pass does not walk them.  Set by the host when the switch is on
+    // (lg_accel_set_shadow_skip, LASGUN_SHADOW_SKIP), the scene has 1 .. 32 lights and PI * intensity is finite for every one of them.
+    uint32_t shadow_skip;
 };
 
 // A radiance query's level 0 (k_radiance.hip), beside the DParams of its chunk: the caller's buffers and where the chunk starts

@@ -85,7 +85,8 @@ struct ShadowRefill {
             const uint32_t rank = lanes_below(m);
             if (need && rank < take) {
                 unsigned long long hh;
-                if (hit_of(P, hs, tile, slot + rank, hh)) { // (a hole of a dense block, a slot past the count: the lane asks again)
+                bool skip;
+                if (hit_of(P, hs, tile, slot + rank, hh, skip) && !skip) { // (a hole of a dense block, a slot past the count, a hit the closest pass flagged: the lane asks again)
                     h = hh;
                     const unsigned long long n = P.wf_hit_stride;
                     // interaction.p + p_err, recomputed from the parked frame exactly as stash_get does
@@ -196,9 +197,12 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
                 }
             } else if (!hit && mine) P.wf_hq[i] = WF_NONE; // a hole of a dense block
             if (hit) {
-                P.wf_hq[h] = (uint32_t)i;
                 Shade sh;
                 shade_frame(P, ray, b, sh);
+                // no light's term at this hit depends on the light being visible (shade.h): the shadow pass will not walk it
+                const bool skip = P.shadow_skip && shadow_skippable(P, sh);
+                P.wf_hq[h] = skip ? (uint32_t)i | WF_SKIP : (uint32_t)i;
+                if (skip) P.vis[h] = 0u;
                 const unsigned long long n = P.wf_hit_stride;
                 double *f = P.frame + h;
                 f[0 * n] = sh.praw.x; f[1 * n] = sh.praw.y; f[2 * n] = sh.praw.z;
@@ -217,7 +221,8 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             }
         } else {
             unsigned long long h;
-            if (!hit_of(P, hs, tile, lane, h)) continue;
+            bool skip;
+            if (!hit_of(P, hs, tile, lane, h, skip) || skip) continue; // (a tile of flagged hits alone: the wave claims its next tile at once)
             const unsigned long long n = P.wf_hit_stride;
             // interaction.p + p_err, recomputed from the parked frame exactly as stash_get does
             V3 praw{P.frame[0 * n + h], P.frame[1 * n + h], P.frame[2 * n + h]};
@@ -263,7 +268,7 @@ __global__ void __launch_bounds__(LG_BLOCK, 3) wf_shade_kernel(const DParams P) 
         Shade sh;
         V3 output = vzero();
         if (valid) {
-            j = P.wf_hq[h];
+            j = hq_ray(P.wf_hq[h]);
             Ray ray;
             if (L0) {
                 uint32_t sample;

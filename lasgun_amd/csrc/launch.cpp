@@ -62,6 +62,14 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
         const bool dflt = env_default < 0 ? a.prune_default : env_default != 0;
         P.prune = !a.fast && (a.prune < 0 ? dflt : a.prune != 0) ? 1u : 0u;
     }
+    {   // LASGUN_SHADOW_SKIP=0 / lg_accel_set_shadow_skip(0) (A/B, tests): every hit's shadow rays are walked.  The flag's argument (shade.h,
+        // light_irrelevant) needs PI * intensity finite for every light; the visibility word holds 32 lights.
+        static const bool skip_env = [] { const char *e = std::getenv("LASGUN_SHADOW_SKIP"); return !(e && e[0] == '0'); }();
+        bool ok = skip_env && a.shadow_skip && !a.flat.lights.empty() && a.flat.lights.size() <= 32;
+        for (const DLight &L : a.flat.lights)
+            for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(PI * L.intensity[k]);
+        P.shadow_skip = ok ? 1u : 0u;
+    }
     P.cam_origin = s.camera.origin; P.cam_view = s.camera.view; P.cam_up = s.camera.up; P.cam_aux = s.camera.aux;
     P.image_plane_height = s.camera.image_plane_height;
     P.pixel_separation = s.camera.pixel_separation;
@@ -136,7 +144,7 @@ struct ChunkPlan {
         }
         if (*budget == 0) *budget = budget_from_free_memory();
         chunk_tiles = *budget / (per_item * S * 64);
-        const unsigned long long cap_limit = ((queue ? 0xFFFFFF00ull : 0xFFFFFFF0ull) >> (levels - 1)) / (64ull * S); // ray indices are 32-bit
+        const unsigned long long cap_limit = ((queue ? 0xFFFFFF00ull : 0x7FFFFFF0ull) >> (levels - 1)) / (64ull * S); // ray indices are 32-bit (level by level, a render and a radiance query alike: 31, WF_SKIP sits above them -- rq_closest_body.h stores bare indices and relies on it)
         if (chunk_tiles > cap_limit) chunk_tiles = cap_limit;
         if (chunk_tiles < 1) chunk_tiles = 1;
         if (chunk_tiles > P0.ntiles) chunk_tiles = P0.ntiles;

@@ -51,6 +51,9 @@
             }
         } else if (!hit) P.wf_hq[i] = WF_NONE; // a hole of a dense block
         if (hit) {
+            // A bare ray index: bit 31 of this word is WF_SKIP to the shadow pass (wflevel.h, hit_of), which would then neither walk the hit nor write
+            // its vis word.  i stays below 2^31 because a query's chunks come from the same ChunkPlan as a render's (launch.cpp: cap_limit,
+            // 0x7FFFFFF0 rays for the level-by-level pipeline) -- raise that cap for queries and this store has to mask or flag like k_wavefront.hip's.
             P.wf_hq[h] = (uint32_t)i;
             Shade sh;
             shade_frame(P, ray, b, sh);

@@ -62,7 +62,9 @@ __device__ __forceinline__ double tr_lambda(double ax, double ay, V3 w) { // mic
     return (sqrt(1.0 + a2t2) - 1.0) / 2.0;
 }
 // microfacet::Reflection::f (microfacet.rs:101-115); conductor selects Substance::Conductor(1, eta, k)
-__device__ __forceinline__ V3 microfacet_f(V3 r, bool conductor, double d_eta_i, double d_eta_t, V3 c_eta, V3 c_k, double ax, double ay, V3 wo, V3 wi) {
+// `pre`: `lambda_o` = tr_lambda(ax, ay, wo), a term of wo alone, was computed by a caller that evaluates several wi for one wo (WoTerms
+// below); otherwise it is computed here, where it is needed, behind the early returns
+__device__ __forceinline__ V3 microfacet_f(V3 r, bool conductor, double d_eta_i, double d_eta_t, V3 c_eta, V3 c_k, double ax, double ay, V3 wo, V3 wi, bool pre, double lambda_o) {
     double cos_o = abs_cos_theta(wo), cos_i = abs_cos_theta(wi);
     V3 wh = wi + wo;
     if (cos_i == 0.0 || cos_o == 0.0) return vzero();
@@ -70,7 +72,7 @@ __device__ __forceinline__ V3 microfacet_f(V3 r, bool conductor, double d_eta_i,
     wh = normalize(wh);
     double ci = dot(wi, wh);
     V3 spectrum = conductor ? fr_conductor(ci, splat(1.0), c_eta, c_k) : splat(fr_dielectric(ci, d_eta_i, d_eta_t));
-    double g = 1.0 / (1.0 + tr_lambda(ax, ay, wo) + tr_lambda(ax, ay, wi));
+    double g = 1.0 / (1.0 + (pre ? lambda_o : tr_lambda(ax, ay, wo)) + tr_lambda(ax, ay, wi));
     return mul_ew(r * tr_d(ax, ay, wh) * g, spectrum) / (4.0 * cos_i * cos_o);
 }
 __device__ __forceinline__ V3 oren_nayar_f(V3 r, double sigma_deg, V3 wo, V3 wi) { // diffuse.rs:29-56
@@ -99,10 +101,29 @@ struct Shade {
     int32_t mat;
 };
 
+// BSDF::f's `reflect` (bsdf.rs:77): wi and wo on the same side of the geometric normal.  ONE expression for every site that asks
+// (bsdf_f, and light_term for the closest pass's shadow-skip flag), so that the same inputs give the same answer at each.
+__device__ __forceinline__ bool bsdf_reflect(const Shade &sh, V3 wo, V3 wi) { return dot(wi, sh.ng) * dot(wo, sh.ng) > 0.0; }
+// What BSDF::f needs of wo alone, computed once for all the wi of a hit (every light, then the ambient term): wo in shading space and the
+// microfacet model's Lambda(wo) (three square roots and three divisions).  The same expressions on the same inputs as inside
+// bsdf_f / microfacet_f, so the same bits.
+struct WoTerms {
+    V3 wo_l;
+    bool pre;        // lambda_o is set (a caller with ONE wi leaves it to microfacet_f, which may never need it)
+    double lambda_o;
+};
+__device__ __forceinline__ WoTerms wo_terms(const DMaterial &m, const Shade &sh, V3 wo) {
+    WoTerms t;
+    t.wo_l = V3{dot(wo, sh.ss), dot(wo, sh.ts), dot(wo, sh.ns)};
+    t.pre = true;
+    t.lambda_o = 0.0;
+    if (m.kind == MAT_PLASTIC) t.lambda_o = tr_lambda(m.p[6], m.p[6], t.wo_l);
+    else if (m.kind == MAT_METAL) t.lambda_o = tr_lambda(m.p[6], m.p[7], t.wo_l);
+    return t;
+}
 // BSDF::f (bsdf.rs:73-92) with the BxDF list of Material::scattering (material/*.rs) inlined
-__device__ __forceinline__ V3 bsdf_f(const DMaterial &m, const Shade &sh, V3 wo, V3 wi) {
-    bool reflect = dot(wi, sh.ng) * dot(wo, sh.ng) > 0.0;
-    V3 wo_l{dot(wo, sh.ss), dot(wo, sh.ts), dot(wo, sh.ns)};
+__device__ __forceinline__ V3 bsdf_f(const DMaterial &m, const Shade &sh, const WoTerms &wt, V3 wi, bool reflect) {
+    const V3 wo_l = wt.wo_l;
     V3 wi_l{dot(wi, sh.ss), dot(wi, sh.ts), dot(wi, sh.ns)};
     if (wo_l.z == 0.0) return vzero();
     V3 f = vzero();
@@ -118,14 +139,14 @@ __device__ __forceinline__ V3 bsdf_f(const DMaterial &m, const Shade &sh, V3 wo,
         if (reflect) {
             V3 kd{m.p[0], m.p[1], m.p[2]}, ks{m.p[3], m.p[4], m.p[5]};
             if (vne(kd, vzero())) f = f + kd * FRAC_1_PI;
-            if (vne(ks, vzero())) f = f + microfacet_f(ks, false, 1.0, 1.5, vzero(), vzero(), m.p[6], m.p[6], wo_l, wi_l);
+            if (vne(ks, vzero())) f = f + microfacet_f(ks, false, 1.0, 1.5, vzero(), vzero(), m.p[6], m.p[6], wo_l, wi_l, wt.pre, wt.lambda_o);
         }
         break;
     }
     case MAT_METAL: { // metal.rs:17-26
         if (reflect) {
             V3 eta{m.p[0], m.p[1], m.p[2]}, k{m.p[3], m.p[4], m.p[5]};
-            f = f + microfacet_f(splat(1.0), true, 0.0, 0.0, eta, k, m.p[6], m.p[7], wo_l, wi_l);
+            f = f + microfacet_f(splat(1.0), true, 0.0, 0.0, eta, k, m.p[6], m.p[7], wo_l, wi_l, wt.pre, wt.lambda_o);
         }
         break;
     }
@@ -140,6 +161,10 @@ __device__ __forceinline__ V3 bsdf_f(const DMaterial &m, const Shade &sh, V3 wo,
         break;
     }
     return f;
+}
+__device__ __forceinline__ V3 bsdf_f(const DMaterial &m, const Shade &sh, V3 wo, V3 wi) { // one wi for this wo (the megakernel's call)
+    const WoTerms wt{V3{dot(wo, sh.ss), dot(wo, sh.ts), dot(wo, sh.ns)}, false, 0.0};
+    return bsdf_f(m, sh, wt, wi, bsdf_reflect(sh, wo, wi));
 }
 
 struct Sample { // bxdf::LightSample
@@ -390,25 +415,53 @@ __device__ __forceinline__ void finish_pixel(const DParams &P, const Pixel &px, 
     color = color * weight;
     write_pixel(P, px, color);
 }
+// What a hit sees of point light L (integrate.rs:53-62, bsdf.rs:77): the direction to it, the attenuation, the cosine, and whether BSDF::f
+// counts the light as reflected.  shade_lights evaluates the light's term from it; the closest pass asks light_irrelevant of the SAME
+// function on the same frame, so both sites hold the same bits.
+struct LightTerm {
+    V3 wi;
+    double f_att, wi_dot_n;
+    bool reflect;
+};
+__device__ __forceinline__ LightTerm light_term(const DLight &L, const Shade &sh) {
+    LightTerm t;
+    V3 wi = V3{L.pos[0], L.pos[1], L.pos[2]} - sh.p;
+    double d = magnitude(wi);
+    t.f_att = L.falloff[0] + L.falloff[1] * d + L.falloff[2] * d * d;
+    t.wi = normalize(wi);
+    t.wi_dot_n = dot(t.wi, sh.ns);
+    t.reflect = bsdf_reflect(sh, sh.wo, t.wi);
+    return t;
+}
+// The light's term of li() is +-0 in every channel WHETHER OR NOT the light is visible: BSDF::f is exactly zero for every material when
+// `reflect` is false (bsdf_f above: nothing, or only vzero(), is ever added), and (PI * intensity * 0) * wi_dot_n / f_att stays a zero
+// while the intensity (DParams::shadow_skip, tested once on the host) and wi_dot_n are finite and f_att is not NaN (f_att == 0 skips
+// the light altogether).  The running sum starts at +0 and adding +-0 to it changes no bit, so the hit's shadow ray decides nothing.
+__device__ __forceinline__ bool light_irrelevant(const LightTerm &t) {
+    return !t.reflect && isfinite(t.wi_dot_n) && !isnan(t.f_att);
+}
+// Every light of the scene is irrelevant at this hit: its shadow walks can be skipped (DParams::shadow_skip; at most 32 lights).
+__device__ __forceinline__ bool shadow_skippable(const DParams &P, const Shade &sh) {
+    bool all = true;
+    for (uint32_t l = 0; l < P.nlights; ++l) all = all && light_irrelevant(light_term(P.lights[l], sh));
+    return all;
+}
 // li() of a hit up to its specular children: the lights in order, then the ambient term (integrate.rs:47-67).  `vis` bit l:
 // light l is visible from the hit (PointLight::sample, point.rs:49).  Shared by the level-by-level shade pass and the queue kernel.
 __device__ __forceinline__ V3 shade_lights(const DParams &P, const DMaterial &m, const Shade &sh, const uint32_t vis) {
     V3 output = vzero();
     const V3 nrm = sh.ns;
+    const WoTerms wt = wo_terms(m, sh, sh.wo);
     for (uint32_t l = 0; l < P.nlights; ++l) { // integrate.rs:47-66
         if (!((vis >> l) & 1u)) continue;
         const DLight L = P.lights[l];
-        V3 wi = V3{L.pos[0], L.pos[1], L.pos[2]} - sh.p;
-        double d = magnitude(wi);
-        double f_att = L.falloff[0] + L.falloff[1] * d + L.falloff[2] * d * d;
-        if (f_att == 0.0) continue;
-        wi = normalize(wi);
-        double wi_dot_n = dot(wi, nrm);
-        V3 fr = bsdf_f(m, sh, sh.wo, wi);
+        const LightTerm t = light_term(L, sh);
+        if (t.f_att == 0.0) continue;
+        V3 fr = bsdf_f(m, sh, wt, t.wi, t.reflect);
         V3 li_col{L.intensity[0], L.intensity[1], L.intensity[2]};
-        output = output + (mul_ew(PI * li_col, fr) * wi_dot_n / f_att);
+        output = output + (mul_ew(PI * li_col, fr) * t.wi_dot_n / t.f_att);
     }
-    return output + mul_ew(P.ambient, bsdf_f(m, sh, sh.wo, nrm)); // integrate.rs:67
+    return output + mul_ew(P.ambient, bsdf_f(m, sh, wt, nrm, bsdf_reflect(sh, sh.wo, nrm))); // integrate.rs:67
 }
 
 // Camera::sample for sample `sidx` of pixel (x, y) (camera.rs:113-146)

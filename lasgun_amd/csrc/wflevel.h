@@ -62,5 +62,24 @@ __device__ __forceinline__ bool hit_of(const DParams &P, const HitSlots &s, uint
     h = P.wf_hit_cap + k;
     return k < s.n_part;
 }
+// ... for the shadow pass: `skip` = the closest pass flagged the hit (WF_SKIP) -- it has no shadow ray to walk and its visibility is written
+__device__ __forceinline__ bool hit_of(const DParams &P, const HitSlots &s, uint32_t tile, uint32_t lane, unsigned long long &h, bool &skip) {
+    skip = false;
+    if (lane >= s.lpt) return false;
+    uint32_t word = WF_NONE;
+    if (tile < s.tiles_dense) {
+        h = (unsigned long long)tile * s.lpt + lane;
+        if (h < s.n_rays) word = P.wf_hq[h];
+    } else {
+        const unsigned long long k = (unsigned long long)(tile - s.tiles_dense) * s.lpt + lane;
+        h = P.wf_hit_cap + k;
+        if (k < s.n_part) word = P.wf_hq[h];
+    }
+    if (word == WF_NONE) return false; // (an appended hit's word is its ray index, never WF_NONE)
+    skip = (word & WF_SKIP) != 0u;
+    return true;
+}
+// the ray index of a hit's wf_hq word
+__device__ __forceinline__ uint32_t hq_ray(uint32_t word) { return word & ~WF_SKIP; }
 
 } // namespace lg
