@@ -247,6 +247,12 @@ int lg_accel_set_prune(const lg_accel *, int enabled);
  * the shadow pass does not walk them.  Exact; applies to scenes of 1 .. 32 lights of finite intensity.  1 (default):
  * on; 0: every hit's shadow rays are walked (A/B, tests; LASGUN_SHADOW_SKIP=0 does the same for every accel).  Same bytes either way. */
 int lg_accel_set_shadow_skip(const lg_accel *, int enabled);
+/* Exact walk, where a ray reaches a nested accel (a group or a mesh): bit 0 -- one row of the accel's inverse transform and one axis of
+ * its root box are tried first, and a ray that has that whole slab behind it does not enter (the root box's own test would say so); bit 1 --
+ * a group that holds one untransformed mesh and nothing else is walked as one level with it.  Both exact; the
+ * counting forms (lg_capture_stats*, lg_trace_pixel*) and the fast mode never take them.  3 (default): both; 0 .. 3: as given (A/B, tests;
+ * LASGUN_LEVEL_DOOR=0..3 masks every accel's setting).  Same bytes, hit records and visibility bits with every mask. */
+int lg_accel_set_level_door(const lg_accel *, int mask);
 int lg_accel_get_prune(const lg_accel *); /* the effective setting (accel default, LASGUN_PRUNE, lg_accel_set_prune, fast mode): 0 / 1 */
 
 /* Kernel organisation (same arithmetic, same bytes either way).  1 (default): the organisation of a launch is MEASURED -- the SECOND

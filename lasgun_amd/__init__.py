@@ -40,6 +40,7 @@ _EXTRA = {
     "accel_set_mode": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_prune": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_shadow_skip": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_set_level_door": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
     "accel_last_organisation": (_C.c_int, [_C.c_void_p]),
@@ -157,6 +158,12 @@ class HipApi(Api):
         """Level-by-level pipeline: skip the shadow walks of hits at which no light's term depends on its visibility (default on; same bytes
         either way; include/lasgun_hip.h, lg_accel_set_shadow_skip)."""
         if self.call("accel_set_shadow_skip", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def set_level_door(self, accel, mask):
+        """Exact walk, entering a nested accel: bit 0 = the one-axis probe at its door, bit 1 = a lone mesh and its group as one level
+        (default 3; same results with every mask; include/lasgun_hip.h, lg_accel_set_level_door)."""
+        if self.call("accel_set_level_door", accel.h, int(mask)):
             raise LasgunError(self.last_error())
 
     def last_organisation(self, accel):

@@ -91,7 +91,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
             }
         }
         if (!a->fast_available) a->stack_depth_fast1 = a->stack_depth;
-        // Scenes whose tables stay in L2: the accel records (13 x 16 bytes each) go into LDS behind the stacks of the 256-lane
+        // Scenes whose tables stay in L2: the accel records (LDS_ACCEL_UNITS x 16 bytes each) go into LDS behind the stacks of the 256-lane
         // kernels when that keeps four workgroups on a CU -- entering and leaving nested accels is a chain of dependent fetches of
         // these records (37 % of the walk's cycles on config 4m when they come from L2)
         a->accel_image_n16 = 0;
@@ -191,9 +191,10 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                     std::memcpy(rec, &A.minv, 96);
                     rec[24] = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
                     rec[25] = A.lprim_base; rec[26] = A.prim_base - A.lprim_base; rec[27] = A.flags;
-                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain;
+                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain; rec[30] = A.lone;
                     for (int k = 0; k < MAX_CHAIN; ++k) rec[32 + k] = A.chain[k];
                     std::memcpy(rec + 40, A.prune, sizeof A.prune);
+                    std::memcpy(rec + LDS_ACCEL_DOOR * 4, A.door, sizeof A.door);
                 }
                 stage.add(a->lds_image, img);
                 a->lds_image_n16 = (uint32_t)n16;
@@ -208,9 +209,10 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                     uint32_t *rec = &img[i * LDS_ACCEL_UNITS * 4];
                     std::memcpy(rec, &A.minv, 96);
                     rec[24] = A.node_base; rec[25] = A.prim_base; rec[26] = 0u; rec[27] = A.flags;
-                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain;
+                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain; rec[30] = A.lone;
                     for (int k = 0; k < MAX_CHAIN; ++k) rec[32 + k] = A.chain[k];
                     std::memcpy(rec + 40, A.prune, sizeof A.prune);
+                    std::memcpy(rec + LDS_ACCEL_DOOR * 4, A.door, sizeof A.door);
                 }
                 stage.add(a->accel_image, img);
             }

@@ -712,6 +712,12 @@ int lg_accel_set_shadow_skip(const lg_accel *a, int enabled) {
     a->shadow_skip = enabled == 1;
     return 0;
 }
+int lg_accel_set_level_door(const lg_accel *a, int mask) {
+    if (mask < 0 || mask > 3) return fail("level door mask must be 0 .. 3 (bit 0: the probe, bit 1: the lone-mesh level)");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->level_door = (uint32_t)mask;
+    return 0;
+}
 int lg_accel_set_mode(const lg_accel *a, int mode) {
     if (mode != 0 && mode != 1) return fail("mode must be 0 (reference traversal) or 1 (fast)");
     std::lock_guard<std::mutex> g(a->mtx);

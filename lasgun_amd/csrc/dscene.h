@@ -59,7 +59,12 @@ constexpr uint32_t LDS_NODE_STRIDE = 5u;
 // base, leaf_soup slot delta, flags}, [7] {parent, nchain, -, -}, [8..9] chain[8].  Entering and leaving nested accels is
 // a chain of DEPENDENT fetches of these fields; from LDS each link costs ~64 cycles instead of an L2 round trip.
 // [10..12] the pruned walk's constants of the level: {centre x, y}, {centre z, size}, {e0, e2} (DAccel::prune).
-constexpr uint32_t LDS_ACCEL_UNITS = 13u;
+// [13..15] the door record (DAccel::door); word [30] of unit [7]: DAccel::lone.
+constexpr uint32_t LDS_ACCEL_UNITS = 16u;
+constexpr uint32_t LDS_ACCEL_DOOR = 13u;
+// lg_accel_set_level_door / LASGUN_LEVEL_DOOR (DParams::level_door): bit 0 the probe at a nested accel's door, bit 1 a lone mesh and
+// its group walked as one level (walk.h, the ST_ENTER block)
+constexpr uint32_t LEVEL_DOOR_PROBE = 1u, LEVEL_DOOR_LONE = 2u;
 
 struct alignas(64) DNode {
     double bmin[3];
@@ -169,8 +174,15 @@ struct alignas(16) DAccel {
     uint32_t fprim_base;
     uint32_t lnode_base; // reference tree again, in the compact numbering of the LDS-resident scene image (DParams::lds_image)
     uint32_t lprim_base;
-    uint32_t pad[2];
+    // a group that holds one identity-transform mesh accel and nothing else, under a root box that is the mesh's bit for bit: that
+    // mesh accel's id (the walk may take the two as one level: walk.h, ST_ENTER); NO_HIT otherwise
+    uint32_t lone;
+    uint32_t pad;
     double prune[6]; // pruned walk: centre of the root box (3), sum of its extents, e0, e2 (e0 = +inf: this level is never pruned)
+    // door record, for the axis k on which this accel's node-0 box is thinnest: minv's row k -- the four coefficients xf_point /
+    // xf_vector use for component k -- then bmin[k], bmax[k] of node 0.  One matrix row, one division and two products prove most of
+    // the misses at node 0 before the whole local ray is formed (walk.h, ST_ENTER).
+    double door[6];
 };
 
 // Control words of the queue organisation (DParams::q_ctl).  Every word that many waves hammer sits on a 128-byte line of its own
@@ -338,6 +350,7 @@ struct DParams {
     // shadow_skippable; WF_SKIP in the hit's wf_hq word) and the shadow pass does not walk them.  Set by the host when the switch is on
     // (lg_accel_set_shadow_skip, LASGUN_SHADOW_SKIP), the scene has 1 .. 32 lights and PI * intensity is finite for every one of them.
     uint32_t shadow_skip;
+    uint32_t level_door; // LEVEL_DOOR_* bits (lg_accel_set_level_door, LASGUN_LEVEL_DOOR; default: both)
 };
 
 // A radiance query's level 0 (k_radiance.hip), beside the DParams of its chunk: the caller's buffers and where the chunk starts

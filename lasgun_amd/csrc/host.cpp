@@ -1478,6 +1478,33 @@ static void anyhit_range(FlatScene &out) {
     out.ah_dmax = ok ? dmax : 0.0;
 }
 
+// Door records and lone-mesh marks of every accel (dscene.h, DAccel::door / DAccel::lone; the walk's use of them: walk.h, ST_ENTER).
+// The door's axis is the one on which the accel's node-0 box is thinnest (the lowest such axis; an extent that is NaN never wins):
+// any axis would be exact, the thinnest slab is the one a ray is most often wholly in front of.
+void level_door_records(FlatScene &out) {
+    for (DAccel &A : out.accels) {
+        const DNode &n0 = out.nodes[A.node_base];
+        int k = 0;
+        for (int i = 1; i < 3; ++i)
+            if (n0.bmax[i] - n0.bmin[i] < n0.bmax[k] - n0.bmin[k]) k = i;
+        for (int c = 0; c < 4; ++c) A.door[c] = A.minv.c[c][k];
+        A.door[4] = n0.bmin[k]; A.door[5] = n0.bmax[k];
+        A.lone = NO_HIT;
+    }
+    for (DAccel &G : out.accels) {
+        if (G.flags & AF_MESH) continue;
+        const DNode &g0 = out.nodes[G.node_base];
+        if (!(g0.meta & NODE_LEAF) || (g0.meta & 0xFFFFu) != 1u) continue; // node 0 a leaf of one slot: the group holds exactly one primitive
+        const uint32_t ref = out.primref[G.prim_base + g0.link];
+        if ((ref >> 30) != PK_ACCEL) continue;
+        const uint32_t m = ref & PRIM_INDEX_MASK;
+        const DAccel &M = out.accels[m];
+        if ((M.flags & (AF_MESH | AF_IDENTITY)) != (AF_MESH | AF_IDENTITY)) continue;
+        if (std::memcmp(&g0, &out.nodes[M.node_base], 48) != 0) continue; // bmin[3], bmax[3]: the same 48 bytes (a signed zero that differs: not lone)
+        G.lone = m;
+    }
+}
+
 void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with_records) {
     out = FlatScene();
     Flattener fl{scene, out, {}, with_fast};
@@ -1510,6 +1537,7 @@ void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with
         for (int k = 0; k < 3; ++k) // finite AND ordered: slab_intersects_sg takes the near / far plane from the ray's sign, which is the reference's min / max only for bmin <= bmax
             out.boxes_finite = out.boxes_finite && std::isfinite(nd.bmin[k]) && std::isfinite(nd.bmax[k]) && nd.bmin[k] <= nd.bmax[k];
     anyhit_range(out);
+    level_door_records(out);
     out.sphere_ref_leaf.resize(out.spheres.size(), NO_HIT);
     out.cuboid_ref_leaf.resize(out.cuboids.size(), NO_HIT);
     out.tri_ref_leaf.resize(out.tri_v.size() / 3, NO_HIT);

@@ -150,5 +150,7 @@ struct FlatScene {
 // (with_records: the culling records and strips of the pruned walk's mesh leaves -- a third to a half of a mesh accel's build; without them
 // every mesh leaf is walked in the reference's order, pruned walk or not)
 void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast = false, bool with_records = true); // throws Error
+// the last step of flatten_scene: every accel's door record and lone-mesh mark (DAccel::door, DAccel::lone) from the finished tables
+void level_door_records(FlatScene &out);
 
 } // namespace lg

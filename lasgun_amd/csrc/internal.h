@@ -447,6 +447,7 @@ struct lg_accel {
     mutable int prune = -1;    // lg_accel_set_prune: -1 = prune_default
     bool prune_default = false; // the scene carries a mesh with fat leaves
     mutable bool shadow_skip = true; // lg_accel_set_shadow_skip: the level-by-level closest pass flags hits whose shadow rays decide nothing
+    mutable uint32_t level_door = 3u; // lg_accel_set_level_door: LEVEL_DOOR_* bits of the exact walk's enter block (walk.h, ST_ENTER)
     bool fast_available = true;
     std::string fast_refusal = "fast mode unavailable: its tree is too deep for the LDS stack";
     mutable std::vector<std::pair<hipEvent_t, hipEvent_t>> events;

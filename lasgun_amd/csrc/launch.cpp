@@ -70,6 +70,11 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
             for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(PI * L.intensity[k]);
         P.shadow_skip = ok ? 1u : 0u;
     }
+    {   // LASGUN_LEVEL_DOOR=0..3 / lg_accel_set_level_door (A/B, tests): which shortcuts the exact walk takes where it enters a nested accel --
+        // bit 0 the probe at the door, bit 1 a lone mesh and its group as one level.  Same results with every mask.
+        static const uint32_t door_env = [] { const char *e = std::getenv("LASGUN_LEVEL_DOOR"); return e && e[0] >= '0' && e[0] <= '3' && !e[1] ? (uint32_t)(e[0] - '0') : 3u; }();
+        P.level_door = door_env & a.level_door;
+    }
     P.cam_origin = s.camera.origin; P.cam_view = s.camera.view; P.cam_up = s.camera.up; P.cam_aux = s.camera.aux;
     P.image_plane_height = s.camera.image_plane_height;
     P.pixel_separation = s.camera.pixel_separation;

@@ -600,6 +600,7 @@ __device__ __forceinline__ uint32_t neg_mask_x(const Ray &r) {
 }
 template <int N> struct IntC { static constexpr int value = N; };
 constexpr uint32_t FRAME_SAME_RAY = 0x80000000u; // level frame, third word: the level was entered without changing the ray
+constexpr uint32_t FRAME_LONE = 0x40000000u;     // ... the level is a lone mesh entered together with its group: the frame returns to the group's parent (traverse_ref)
 
 struct Lvl { // the accel level a lane is walking
     uint32_t accel, node_base, prim_base, soup_delta, flags;
@@ -1337,20 +1338,67 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
         if (wave_any(state == ST_LEVEL_DONE)) stamp_cnt[4] += 1;
 #endif
         if (state == ST_ENTER) {
-            lvl_set<LDSS, FAST>(P, arec, L, enter);
-            const bool same = (L.flags & AF_IDENTITY) != 0u && ray_plain(ray);
-            stk[sp * stride] = li; stk[(sp + 1u) * stride] = le; stk[(sp + 2u) * stride] = base | (same ? FRAME_SAME_RAY : 0u);
-            sp += 3u; base = sp;
-            if (!same) {
-                ray = accel_local_ray<LDSS>(P, arec, enter, ray);
-                dd = dot(ray.d, ray.d);
-                four_a = 4.0 * dd;
-                negmask = neg_mask_x(ray);
+            // The probe at the door (not the counting forms, whose event order is the reference's, nor the fast trees): component k
+            // of the local ray alone -- k the axis on which the accel's node-0 box is thinnest (DAccel::door) -- by the very expressions of
+            // xf_point / xf_vector, and that axis's two plane parameters as the slab test forms them.  m = fmax(t1, t2) <= 0: in every form of
+            // the slab test tfar is the fmin chain over the per-axis fmax(t1, t2), and fmin ignores a NaN operand, so tfar <= m <= 0 and
+            // !(tfar <= 0.0) is false -- node 0 misses whatever the other axes say (the pruned walk only ever turns a hit into a miss), and with
+            // an empty level stack the level is exhausted.  The lane then does not enter: its state becomes what phase C makes it after that
+            // miss, from the parent's li / le / sp / base, which are still in registers; no frame is pushed, L, ray, dd, four_a and negmask stay.
+            // Both t NaN: m is NaN, the comparison is false, the lane enters as before.  An AF_IDENTITY accel whose entry keeps a plain ray:
+            // ((1*x + 0*y) + 0*z) + 0*w below IS the ray's own component k, bit for bit (see `same`), so the same expressions serve it.
+            bool shut = false;
+            if (!FAST && !COUNT && (P.level_door & LEVEL_DOOR_PROBE)) {
+                double2 ma, mb, bx;
+                if (LDSS || arec) {
+                    const uint4 *q = arec + (enter * LDS_ACCEL_UNITS + LDS_ACCEL_DOOR);
+                    ma = lds_d2(q); mb = lds_d2(q + 1); bx = lds_d2(q + 2);
+                } else {
+                    const double *q = P.accels[enter].door;
+                    ma = double2{q[0], q[1]}; mb = double2{q[2], q[3]}; bx = double2{q[4], q[5]};
+                }
+                const bool o_finite = __builtin_isfinite(ray.o.x) && __builtin_isfinite(ray.o.y) && __builtin_isfinite(ray.o.z); // (xf_point: else NaN)
+                const double ok = ((ma.x * ray.o.x + ma.y * ray.o.y) + mb.x * ray.o.z) + mb.y * 1.0;
+                const double dk = ((ma.x * ray.d.x + ma.y * ray.d.y) + mb.x * ray.d.z) + mb.y * 0.0;
+                const double inv = 1.0 / dk; // ray_new
+                const double m = fmax_((bx.x - ok) * inv, (bx.y - ok) * inv);
+                shut = o_finite && m <= 0.0;
             }
-            if (FAST && (L.flags & AF_MESH)) tri = tri_setup(ray);
-            if (PRUNE) prune_level();
-            cur = L.node_base;
-            state = ST_NODE; // node 0 is tested when visited (bvh.rs:472-473)
+            if (shut) {
+                if (li < le) state = ST_LEAF;
+                else if (sp != base) { --sp; cur = stk[sp * stride]; state = ST_NODE; }
+                else state = ST_LEVEL_DONE; // the parent level is exhausted as well
+            } else {
+                lvl_set<LDSS, FAST>(P, arec, L, enter);
+                const bool same = (L.flags & AF_IDENTITY) != 0u && ray_plain(ray);
+                uint32_t fflags = same ? FRAME_SAME_RAY : 0u;
+                if (!same) {
+                    ray = accel_local_ray<LDSS>(P, arec, enter, ray);
+                    dd = dot(ray.d, ray.d);
+                    four_a = 4.0 * dd;
+                    negmask = neg_mask_x(ray);
+                }
+                // A lone mesh and its group as one level: the group's node 0 is a leaf whose one slot is an AF_IDENTITY mesh
+                // accel under the same 48 bytes of box (DAccel::lone, checked by the host).  The group's node-0 test and the mesh's are then one
+                // operation on the same bits, the group's leaf loop has that one slot, and the mesh's entry keeps a plain ray: the lane goes
+                // on as the mesh's level, under ONE frame whose return lands in the group's parent (FRAME_LONE).  A local ray that is not
+                // plain takes both levels as before (the identity matrix turns a -0 into +0 and with it the sign of dinv).
+                if (!FAST && !COUNT && (P.level_door & LEVEL_DOOR_LONE)) {
+                    uint32_t lone;
+                    if (LDSS || arec) lone = lds_u4(arec + (enter * LDS_ACCEL_UNITS + 7u)).z;
+                    else lone = P.accels[enter].lone;
+                    if (lone != NO_HIT && ray_plain(ray)) {
+                        lvl_set<LDSS, FAST>(P, arec, L, lone);
+                        fflags |= FRAME_LONE;
+                    }
+                }
+                stk[sp * stride] = li; stk[(sp + 1u) * stride] = le; stk[(sp + 2u) * stride] = base | fflags;
+                sp += 3u; base = sp;
+                if (FAST && (L.flags & AF_MESH)) tri = tri_setup(ray);
+                if (PRUNE) prune_level();
+                cur = L.node_base;
+                state = ST_NODE; // node 0 is tested when visited (bvh.rs:472-473)
+            }
         }
         LG_STAMP(4);
         // ---- phase C: this nested BVHAccel is exhausted: resume the parent's leaf loop (bvh.rs:483-488)
@@ -1366,14 +1414,16 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
             else {
                 const uint32_t w2 = stk[(sp - 1u) * stride];
                 le = stk[(sp - 2u) * stride]; li = stk[(sp - 3u) * stride];
-                sp -= 3u; base = w2 & ~FRAME_SAME_RAY;
+                sp -= 3u; base = w2 & ~(FRAME_SAME_RAY | FRAME_LONE);
                 if (COUNT) dbg_event(P, 5.0, (double)L.accel, (double)li, (double)le);
                 uint32_t parent, nchain;
                 if (LDSS || arec) {
                     parent = lds_u4(arec + (L.accel * LDS_ACCEL_UNITS + 7u)).x;
+                    if (!FAST && !COUNT && (w2 & FRAME_LONE)) parent = lds_u4(arec + (parent * LDS_ACCEL_UNITS + 7u)).x; // a lone mesh's frame returns past its group
                     nchain = lds_u4(arec + (parent * LDS_ACCEL_UNITS + 7u)).y;
                 } else {
                     parent = (uint32_t)P.accels[L.accel].parent;
+                    if (!FAST && !COUNT && (w2 & FRAME_LONE)) parent = (uint32_t)P.accels[parent].parent;
                     nchain = P.accels[parent].nchain;
                 }
                 LG_RSTAMP(1);
