@@ -313,6 +313,34 @@ impl<'s> Accel<'s> {
             panic!("lasgun: {}", last_error())
         }
     }
+    /// Open directions above points (`lg_open_directions`): (bits, open, above) -- `points.len()` rows of ceil(dirs.len() / 8) bytes, bit k of
+    /// row i (`(bits[i * row_bytes + (k >> 3)] >> (k & 7)) & 1`) set iff dirs[k] is above the horizon of points[i]
+    /// (`(n.x*d.x + n.y*d.y) + n.z*d.z > 0.0`; every direction when `normals` is None) and `occluded` answers false for the ray
+    /// (points[i], dirs[k]); open[i] / above[i] = the numbers of open directions and of directions above.  The rays are made on the device.
+    pub fn open_directions(&self, points: &[[f64; 3]], normals: Option<&[[f64; 3]]>, dirs: &[[f64; 3]]) -> (Vec<u8>, Vec<u32>, Vec<u32>) {
+        let row_bytes = (dirs.len() + 7) / 8;
+        let (mut bits, mut open, mut above) = (vec![0u8; points.len() * row_bytes], vec![0u32; points.len()], vec![0u32; points.len()]);
+        if points.is_empty() || dirs.is_empty() { return (bits, open, above) }
+        if let Some(n) = normals { assert_eq!(n.len(), points.len(), "open_directions: one normal per point") }
+        let rc = unsafe {
+            sys::lg_open_directions(self.ptr, points.as_ptr() as *const f64, normals.map_or(std::ptr::null(), |n| n.as_ptr() as *const f64), points.len(),
+                                    dirs.as_ptr() as *const f64, dirs.len(), bits.as_mut_ptr(), row_bytes, open.as_mut_ptr(), above.as_mut_ptr())
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        (bits, open, above)
+    }
+    /// `open_directions` for tables in device memory (3 doubles a vector), enqueued on a HIP stream: n_points rows of `row_bytes` bytes at
+    /// `dev_bits` and / or n_points u32 at `dev_open` and `dev_above` (each may be null, not all three); `dev_normals` may be null
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of those sizes (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn open_directions_device(&self, dev_points: *const f64, dev_normals: *const f64, n_points: usize, dev_dirs: *const f64, n_dirs: usize,
+                                         dev_bits: *mut u8, row_bytes: usize, dev_open: *mut u32, dev_above: *mut u32, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_open_directions_device(self.ptr, dev_points, dev_normals, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
     /// Radiance along every ray (origin xyz, direction xyz): what the reference's `integrate` leaves for a pixel whose one sample is that
     /// ray (integrate.rs:16-20, 23-132) -- lights, shadows, ambient, specular recursion, background on a miss --, f64 RGB before quantisation.
     /// For rays no camera of the scene generates: probes, panoramas, bakes, a second view of one accel.

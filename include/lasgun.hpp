@@ -158,7 +158,7 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
-    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_radiance): rays are origin xyz, direction xyz
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_open_directions / lg_radiance): rays are origin xyz, direction xyz
     std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<lg_hit> hits(rays.size());
         if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
@@ -178,6 +178,23 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         if (blocked) blocked->assign(from.size(), 0u);
         if (lg_visibility(h_, from.empty() ? nullptr : from[0].data(), from.size(), to.empty() ? nullptr : to[0].data(), to.size(),
                           bits.empty() ? nullptr : bits.data(), row_bytes, blocked && !blocked->empty() ? blocked->data() : nullptr))
+            throw Error(lg_last_error());
+        return bits;
+    }
+    // direction set (lg_open_directions): bit k of row i -- (bits[i * row_bytes + (k >> 3)] >> (k & 7)) & 1, row_bytes = ceil(dirs.size() / 8) --
+    // is 1 iff dirs[k] is above the horizon of points[i] ((n.x*d.x + n.y*d.y) + n.z*d.z > 0.0; every direction without normals) and the ray
+    // (points[i], dirs[k]) is not occluded; *open / *above (if asked for): the numbers of open directions and of directions above per point
+    std::vector<uint8_t> open_directions(const std::vector<std::array<double, 3>> &points, const std::vector<std::array<double, 3>> &dirs,
+                                         const std::vector<std::array<double, 3>> *normals = nullptr, std::vector<uint32_t> *open = nullptr,
+                                         std::vector<uint32_t> *above = nullptr) const {
+        if (normals && normals->size() != points.size()) throw Error("open_directions: one normal per point");
+        const size_t row_bytes = (dirs.size() + 7) / 8;
+        std::vector<uint8_t> bits(points.size() * row_bytes);
+        if (open) open->assign(points.size(), 0u);
+        if (above) above->assign(points.size(), 0u);
+        if (lg_open_directions(h_, points.empty() ? nullptr : points[0].data(), normals && !normals->empty() ? (*normals)[0].data() : nullptr, points.size(),
+                               dirs.empty() ? nullptr : dirs[0].data(), dirs.size(), bits.empty() ? nullptr : bits.data(), row_bytes,
+                               open && !open->empty() ? open->data() : nullptr, above && !above->empty() ? above->data() : nullptr))
             throw Error(lg_last_error());
         return bits;
     }

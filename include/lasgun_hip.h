@@ -430,6 +430,45 @@ int lg_visibility(const lg_accel *, const double *from, size_t n_from, const dou
                   uint32_t *blocked);                                                             /* host arrays; synchronous */
 int lg_visibility_device(const lg_accel *, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits,
                          size_t row_bytes, uint32_t *dev_blocked, void *hip_stream);
+/* Direction sets: which of n_dirs shared directions are open above each of n_points points -- ambient occlusion, sky visibility and
+ * sky-light bakes, sun hours (the directions are the sun's positions over a year), hemispherical form factors, antenna line of sight --
+ * without the caller writing n_points * n_dirs rays of 48 bytes: n_points + n_dirs vectors describe all of them.  An EXTRA; no
+ * counterpart in the reference.
+ * points is n_points x 3 doubles; normals is n_points x 3 doubles and MAY BE NULL; dirs is n_dirs x 3 doubles.  Any f64 is accepted as it
+ * is, NaN and infinities included.
+ * Pair (i, k) is the ray with origin points[i] and direction dirs[k], both bit for bit as given: no arithmetic makes the ray.  The
+ * direction's length is the reach: as for lg_occluded the segment p -> p + d is what is tested (t < 1), so the caller scales the directions
+ * by the AO radius, or by more than the scene's diameter for "sky".  The library does not offset the origin: a caller starting from
+ * surface hits offsets them as shading does, p + ng * 2^-36.
+ * above(i, k): true for every pair when normals is NULL; otherwise s = (n.x*d.x + n.y*d.y) + n.z*d.z in f64, in this order, with no
+ * contraction, and above = s > 0.0 -- a NaN s, a zero direction and a perpendicular direction are therefore not above.
+ * open(i, k) = above(i, k) and lg_occluded answers 0 for the pair's ray, in the accel's traversal mode exactly as for the other queries
+ * (reference, pruned, LDS-resident scene, fast mode); no switch of its own.  lg_accel_set_query_order plays no part: there is no ray
+ * array to sort.  A pair that is not above is NOT WALKED.  A wave walks 64 consecutive points against 8 consecutive directions, one
+ * direction at a time -- 64 parallel rays --, so callers who want coherence order their points so that neighbours in the array are
+ * neighbours in space (with similar normals).
+ * Outputs; each may be NULL, all three NULL is an error:
+ * bits: n_points rows of row_bytes bytes, row_bytes >= ceil(n_dirs / 8).  Bit k of row i is (bits[i*row_bytes + (k >> 3)] >> (k & 7)) & 1,
+ * 1 iff open(i, k): least significant bit first, numpy's packbits(..., bitorder="little") per row.  The padding bits of a row's last used
+ * byte are written as 0; bytes of a row beyond ceil(n_dirs / 8) are never touched.
+ * open: open[i] = the number of open directions at point i.  above: above[i] = the number of directions above, n_dirs when normals is
+ * NULL.  Both counts are WRITTEN, NOT ACCUMULATED: whatever the buffers held before is gone.  open[i] / above[i] is the ambient-occlusion
+ * value for a uniform direction set, the cosine-weighted one for cosine-distributed directions.
+ * n_points == 0 or n_dirs == 0 is a successful no-op that writes nothing.
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel; NULL points or dirs with non-zero counts; all
+ * outputs NULL; row_bytes too small; n_dirs > 2^32 - 1; ceil(n_points / 64) * ceil(n_dirs / 8) > 2^32 - 1 (tiles of 64 points x 8
+ * directions are counted in 32 bits, as the other queries' tiles are); bits rows that do not fit the address space -- all checked before
+ * any HIP call --; in the device form also a pointer that is not device memory of the accel's device or is misaligned (dev_points,
+ * dev_normals and dev_dirs 8-byte aligned, dev_open and dev_above 4, dev_bits 1), or a buffer that ends beyond its allocation.
+ * Device form: it only enqueues on hip_stream (the zeroing of dev_open and dev_above that precedes the kernel included); one stream at a
+ * time per accel.  Host form (synchronous): the tables go up, the rows come back compact and are placed into the caller's stride, so the
+ * bytes of a row behind its used part stay untouched; rows and counts are staged, so an error on the way leaves the caller's arrays as
+ * they were. */
+int lg_open_directions(const lg_accel *, const double *points, const double *normals, size_t n_points, const double *dirs, size_t n_dirs,
+                       uint8_t *bits, size_t row_bytes, uint32_t *open, uint32_t *above);       /* host arrays; synchronous */
+int lg_open_directions_device(const lg_accel *, const double *dev_points, const double *dev_normals, size_t n_points,
+                              const double *dev_dirs, size_t n_dirs, uint8_t *dev_bits, size_t row_bytes, uint32_t *dev_open,
+                              uint32_t *dev_above, void *hip_stream);
 /* Radiance along every ray: the third query, for rays no camera of the scene generates (a fisheye or panorama, a light probe or cube
  * map, a lightmap bake from surface points, a caller's own path continuation, a second view of an accel without rebuilding it).
  * radiance[3*i ..] = what integrate() leaves for a pixel whose one sample is ray i: (Color::zero() + li(root, ray_i, depth 0)) * 1.0

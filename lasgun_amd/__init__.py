@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -92,6 +92,7 @@ _EXTRA = {
     **RADIANCE_SIGNATURES,
     **RAY_FILM_SIGNATURES,
     **VISIBILITY_SIGNATURES,
+    **DIRECTIONS_SIGNATURES,
     **FEATURES_SIGNATURES,
 }
 
@@ -554,6 +555,59 @@ class HipApi(Api):
                      self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- direction sets (include/lasgun_hip.h, lg_open_directions*): which of K shared directions are open above each of N points
+    def open_directions(self, accel, points, dirs, normals=None, counts=False, row_bytes=None, into=None):
+        """Which directions dirs[k] are open at points[i]: an (n_points, ceil(n_dirs / 8)) uint8 array, bit k of row i
+        ((bits[i, k >> 3] >> (k & 7)) & 1, numpy's packbits(bitorder="little") per row) set iff the direction is above the point's horizon
+        ((n.x*d.x + n.y*d.y) + n.z*d.z > 0.0; every direction when normals is None) and lg_occluded answers 0 for the ray (points[i], dirs[k]).
+        The direction's length is the reach; the origin is used as given.  counts=True: (bits, open, above), the uint32 numbers of open
+        directions and of directions above per point; counts="only": (open, above) alone (no bit matrix is made).  row_bytes: a wider row
+        stride (the array returned is then (n_points, row_bytes)); into = (bits array or None, open array or None, above array or None):
+        C-contiguous buffers of those shapes written in place -- bytes behind a row's used part keep their value; the outputs are then the
+        arrays given, whatever `counts` says.
+        Also `accel.open_directions(points, dirs, normals=None, counts=False)`."""
+        p, d = self._points(points, "points"), self._points(dirs, "dirs")
+        n = None if normals is None else self._points(normals, "normals")
+        if n is not None and n.shape != p.shape:
+            raise ValueError("normals: one per point")
+        used = (d.shape[0] + 7) // 8
+        stride = used if row_bytes is None else int(row_bytes)
+        if into is not None:
+            bits, nopen, above = into
+        else:
+            bits = None if counts == "only" else _np.zeros((p.shape[0], stride), dtype=_np.uint8)
+            nopen = _np.zeros(p.shape[0], dtype=_np.uint32) if counts else None
+            above = _np.zeros(p.shape[0], dtype=_np.uint32) if counts else None
+        for arr, dt in ((bits, _np.uint8), (nopen, _np.uint32), (above, _np.uint32)):
+            if arr is not None and (arr.dtype != dt or not arr.flags["C_CONTIGUOUS"]):
+                raise ValueError("into: C-contiguous uint8 bits, uint32 open and above")
+        if bits is not None and (bits.ndim != 2 or bits.shape[0] != p.shape[0] or bits.shape[1] != stride):
+            raise ValueError("into: bits of shape (n_points, row_bytes)")
+        for arr in (nopen, above):
+            if arr is not None and arr.shape != (p.shape[0],):
+                raise ValueError("into: open and above of shape (n_points,)")
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        if self.call("open_directions", accel.h, data(p), data(n), p.shape[0], data(d), d.shape[0], data(bits), stride, data(nopen), data(above)):
+            raise LasgunError(self.last_error())
+        out = tuple(a for a in (bits, nopen, above) if a is not None)
+        return out[0] if len(out) == 1 else out
+
+    def open_directions_device(self, accel, n_points, points_ptr, normals_ptr, n_dirs, dirs_ptr, bits_ptr=None, row_bytes=None, open_ptr=None, above_ptr=None,
+                               stream=None):
+        """Enqueue the open directions of n_points points (device memory, 3 doubles each; normals_ptr may be None) against n_dirs directions
+        into n_points rows of row_bytes bytes at bits_ptr (default ceil(n_dirs / 8)) and / or n_points uint32 counts at open_ptr and above_ptr."""
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        stride = (int(n_dirs) + 7) // 8 if row_bytes is None else int(row_bytes)
+        if self.call("open_directions_device", accel.h, ptr(points_ptr), ptr(normals_ptr), int(n_points), ptr(dirs_ptr), int(n_dirs), ptr(bits_ptr), stride,
+                     ptr(open_ptr), ptr(above_ptr), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def ambient_occlusion(self, accel, points, normals, k=64, radius=1.0):
+        """open / max(above, 1) per point, float64, for `k` Fibonacci directions (sphere_directions) of length `radius`: the share of the
+        hemisphere above each point that is unblocked within `radius`.  A convention of this WRAPPER, not of the C contract."""
+        nopen, above = self.open_directions(accel, points, sphere_directions(k, radius), normals, counts="only")
+        return nopen.astype(_np.float64) / _np.maximum(above, 1).astype(_np.float64)
+
     # ---- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of the camera's primary hits
     def material_count(self, accel):
         """The number of materials of the accel's tables: indices 0 .. count-1 are valid for accel_material and name the rows of material_rgb."""
@@ -790,10 +844,21 @@ def _share_torch_hip_runtime():
         _C.CDLL(bundled, mode=_C.RTLD_GLOBAL)
 
 
+def sphere_directions(k, length=1.0):
+    """(k, 3) float64: a Fibonacci lattice of k directions spread evenly over the sphere, each of length `length` (the reach of
+    open_directions).  A convention of this WRAPPER, not of the C contract."""
+    i = _np.arange(int(k), dtype=_np.float64) + 0.5
+    z = 1.0 - 2.0 * i / max(int(k), 1)
+    phi = i * (_np.pi * (3.0 - _np.sqrt(5.0)))
+    d = _np.stack([_np.sqrt(1.0 - z * z) * _np.cos(phi), _np.sqrt(1.0 - z * z) * _np.sin(phi), z], axis=1)
+    return _np.ascontiguousarray(d * (float(length) / _np.linalg.norm(d, axis=1))[:, None])
+
+
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
 api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None: api.capture_features(self, w, h, rect, planes, material_rgb)  # accel.features(w, h)
 api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
+api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

@@ -145,6 +145,14 @@ VISIBILITY_SIGNATURES = {
     "visibility_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# Direction sets (include/lasgun_hip.h, lg_open_directions / lg_open_directions_device): which of K shared directions are open above each of
+# N points, bit-packed and counted; the GPU library's alone.
+DIRECTIONS_SIGNATURES = {
+    "open_directions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "open_directions_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+}
+
 # Feature buffers (include/lasgun_hip.h, lg_capture_features* / lg_accel_material_count): depth, normal, albedo, coverage and ids of the
 # camera's primary hits; the GPU library's alone.
 FEATURES_SIGNATURES = {

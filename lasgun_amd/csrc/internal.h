@@ -67,6 +67,14 @@ hipError_t launch_visibility(const DParams &P, const double *from, unsigned long
                              unsigned long long row_bytes, uint32_t *blocked, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t visibility_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t visibility_set_lds_limit(size_t bytes, bool ldss);
+// k_directions.hip: direction sets (lg_open_directions*) -- the any-hit walk of the rays (points[i], dirs[k]) that are above the point's
+// horizon, 64 points x 8 directions per wave; bit k of bits[i * row_bytes ..] set iff open, and / or the counts in open[i] and above[i]
+// (both zeroed by the caller ahead of the launch); normals may be nullptr (every pair above)
+hipError_t launch_open_directions(const DParams &P, const double *points, const double *normals, unsigned long long n_points, const double *dirs,
+                                  unsigned long long n_dirs, uint8_t *bits, unsigned long long row_bytes, uint32_t *open, uint32_t *above, bool fast,
+                                  uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t open_directions_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t open_directions_set_lds_limit(size_t bytes, bool ldss);
 // k_features.hip: feature buffers (lg_capture_features*) -- the closest-hit walk of the camera's own rays, an 8 x 8 tile of the rectangle per
 // wave and a pixel per lane; only the planes that are not nullptr are written, at DParams' output addressing (out_row0 / out_x0 / out_pitch)
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,

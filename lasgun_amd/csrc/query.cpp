@@ -1,4 +1,4 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_radiance*, lg_camera_rays*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_radiance*, lg_camera_rays*,
 // lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
@@ -214,6 +214,87 @@ extern "C" int lg_visibility_device(const lg_accel *a, const double *dev_from, s
         if (dev_bits) check_device_buffer(*a, dev_bits, (n_from - 1) * row_bytes + visibility_used_bytes(n_to), 1, "bits");
         if (dev_blocked) check_device_buffer(*a, dev_blocked, n_from * sizeof(uint32_t), 4, "blocked");
         enqueue_visibility(*a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- direction sets (lg_open_directions*; k_directions.hip): the rays (points[i], dirs[k]) made in the kernel, one bit each, walked only
+// where the direction is above the point's horizon
+// What both forms refuse before anything is allocated or enqueued (counts are not 0 here)
+static void check_open_directions(const lg_accel *a, const double *points, size_t n_points, const double *dirs, size_t n_dirs, const uint8_t *bits, size_t row_bytes,
+                                  const uint32_t *open, const uint32_t *above) {
+    if (!a) throw Error("accel is NULL");
+    if (!points) throw Error("points is NULL");
+    if (!dirs) throw Error("dirs is NULL");
+    if (!bits && !open && !above) throw Error("bits, open and above are all NULL: at least one output");
+    if ((unsigned long long)n_dirs > 0xFFFFFFFFull) throw Error("too many directions in one set: at most 2^32 - 1 (tiles of 64 points x 8 directions are counted in 32 bits)");
+    const size_t used = visibility_used_bytes(n_dirs);
+    if (bits && row_bytes < used) throw Error("row_bytes is " + std::to_string(row_bytes) + ", a row of " + std::to_string(n_dirs) + " bits takes " + std::to_string(used));
+    const unsigned long long pb = (unsigned long long)(n_points / 64 + (n_points % 64 ? 1 : 0));
+    if (pb > 0xFFFFFFFFull / used) throw Error("too many pairs in one direction set: tiles of 64 points x 8 directions are counted in 32 bits");
+    if (bits && n_points > 1 && row_bytes > (SIZE_MAX - used) / (n_points - 1)) throw Error("bits: n_points rows of row_bytes bytes do not fit the address space");
+}
+// One direction set enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): a
+// tile is 64 points x 8 directions
+static void enqueue_open_directions(const lg_accel &a, const double *points, const double *normals, size_t n_points, const double *dirs, size_t n_dirs, uint8_t *bits,
+                                    size_t row_bytes, uint32_t *open, uint32_t *above, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    P.ntiles = (uint32_t)(((n_points + 63) / 64) * visibility_used_bytes(n_dirs));
+    const TraversalGrid g = traversal_grid(a, P, open_directions_occupancy, ctx_for(a, stream), stream);
+    if (open) HIP_TRY(hipMemsetAsync(open, 0, n_points * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
+    if (above) HIP_TRY(hipMemsetAsync(above, 0, n_points * sizeof(uint32_t), stream));
+    HIP_TRY(launch_open_directions(P, points, normals, n_points, dirs, n_dirs, bits, row_bytes, open, above, a.fast, g.blocks, g.depth, stream));
+}
+// Host form: the tables go up, the rows come back COMPACT (ceil(n_dirs / 8) bytes each) and are placed into the caller's stride here -- the
+// bytes of a row behind its used part are never written; rows and counts are staged
+extern "C" int lg_open_directions(const lg_accel *a, const double *points, const double *normals, size_t n_points, const double *dirs, size_t n_dirs, uint8_t *bits,
+                                  size_t row_bytes, uint32_t *open, uint32_t *above) {
+    return guarded([&] {
+        if (n_points == 0 || n_dirs == 0) return;
+        check_open_directions(a, points, n_points, dirs, n_dirs, bits, row_bytes, open, above);
+        const size_t used = visibility_used_bytes(n_dirs);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        DevBuf<double> dpoints, dnormals, ddirs;
+        DevBuf<uint8_t> dbits;
+        DevBuf<uint32_t> dopen, dabove;
+        dpoints.alloc(n_points * 3);
+        if (normals) dnormals.alloc(n_points * 3);
+        ddirs.alloc(n_dirs * 3);
+        if (bits) dbits.alloc(n_points * used);
+        if (open) dopen.alloc(n_points);
+        if (above) dabove.alloc(n_points);
+        std::vector<uint8_t> rows(bits ? n_points * used : 0); // (staged like the counts: an error on the way leaves the caller's arrays as they were)
+        std::vector<uint32_t> nopen(open ? n_points : 0), nabove(above ? n_points : 0);
+        HIP_TRY(hipMemcpyAsync(dpoints.p, points, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        if (normals) HIP_TRY(hipMemcpyAsync(dnormals.p, normals, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(ddirs.p, dirs, n_dirs * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_open_directions(*a, dpoints.p, normals ? dnormals.p : nullptr, n_points, ddirs.p, n_dirs, bits ? dbits.p : nullptr, used, open ? dopen.p : nullptr,
+                                above ? dabove.p : nullptr, a->stream);
+        if (bits) HIP_TRY(hipMemcpyAsync(rows.data(), dbits.p, n_points * used, hipMemcpyDeviceToHost, a->stream));
+        if (open) HIP_TRY(hipMemcpyAsync(nopen.data(), dopen.p, n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        if (above) HIP_TRY(hipMemcpyAsync(nabove.data(), dabove.p, n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+        if (bits)
+            for (size_t i = 0; i < n_points; ++i) std::memcpy(bits + i * row_bytes, rows.data() + i * used, used);
+        if (open) std::memcpy(open, nopen.data(), n_points * sizeof(uint32_t));
+        if (above) std::memcpy(above, nabove.data(), n_points * sizeof(uint32_t));
+    });
+}
+extern "C" int lg_open_directions_device(const lg_accel *a, const double *dev_points, const double *dev_normals, size_t n_points, const double *dev_dirs, size_t n_dirs,
+                                         uint8_t *dev_bits, size_t row_bytes, uint32_t *dev_open, uint32_t *dev_above, void *hip_stream) {
+    return guarded([&] {
+        if (n_points == 0 || n_dirs == 0) return;
+        check_open_directions(a, dev_points, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_points, n_points * 3 * sizeof(double), 8, "points");
+        if (dev_normals) check_device_buffer(*a, dev_normals, n_points * 3 * sizeof(double), 8, "normals");
+        check_device_buffer(*a, dev_dirs, n_dirs * 3 * sizeof(double), 8, "dirs");
+        if (dev_bits) check_device_buffer(*a, dev_bits, (n_points - 1) * row_bytes + visibility_used_bytes(n_dirs), 1, "bits");
+        if (dev_open) check_device_buffer(*a, dev_open, n_points * sizeof(uint32_t), 4, "open");
+        if (dev_above) check_device_buffer(*a, dev_above, n_points * sizeof(uint32_t), 4, "above");
+        enqueue_open_directions(*a, dev_points, dev_normals, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above, (hipStream_t)hip_stream);
     });
 }
 

@@ -28,7 +28,12 @@ g8d, depth + id alone (20 bytes); beside them, in the same session, the route to
 lg_camera_rays_device + lg_intersect_device on preallocated buffers (144 bytes a ray written, the per-pixel reduction still to do), and
 the closest-hit query alone on those rays in camera order (a) and in 8 x 8 pixel tiles (a8).  With one sample a pixel g8's depth and ids
 are checked against the hits.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features[,...]] [--out profiles/r08_query_order.jsonl]
+Direction sets (lg_open_directions_device) -- --rows directions (not part of "all"): the first hits of a 1024^2 camera frame in 8 x 8 tile
+order, pushed out along ng, normals ng, against 64 Fibonacci directions of length a quarter of the hit bounds' diagonal.  Row o64: the bit
+matrix and both counts from the N + 64 vectors; row ox: lg_occluded_device (the parent commit's library has it) on the explicit rays of the
+ABOVE pairs only, ordered as the kernel walks them (per block of 64 points, direction-major) -- the best the two-call route can do, the
+rays' construction not timed; row op: the same rays point-major.  o64's bits and counts are checked against op's bytes.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -271,6 +276,62 @@ def measure_visibility(name, builder, calls, n=4096):
              "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, bps in rows]
 
 
+def measure_directions(name, builder, calls, size=1024, k=64):
+    """Rows o64 / ox / op of one scene (module docstring)."""
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    assert G.camera_samples(accel) == 1 and size % 8 == 0
+    rays = torch.empty((size * size, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rays = rays.view(size // 8, 8, size // 8, 8, 6).permute(0, 2, 1, 3, 4).contiguous().view(-1, 6)  # 8 x 8 pixel tiles
+    hits = torch.empty((size * size * 96,), dtype=torch.uint8, device="cuda")
+    G.intersect_device(accel, size * size, rays.data_ptr(), hits.data_ptr(), stream=s)
+    f = hits.view(torch.float64).view(-1, 12)
+    f = f[hits.view(torch.int32).view(-1, 24)[:, 20] != 0]
+    del rays, hits
+    n = f.shape[0]
+    pts, nrm = (f[:, 1:4] + f[:, 4:7] * ERR).contiguous(), f[:, 4:7].contiguous()
+    lo, hi = f[:, 1:4].min(dim=0).values, f[:, 1:4].max(dim=0).values
+    dirs = torch.from_numpy(la.sphere_directions(k, 0.25 * float(torch.linalg.norm(hi - lo)))).cuda()
+    above = (nrm[:, None, 0] * dirs[None, :, 0] + nrm[:, None, 1] * dirs[None, :, 1]) + nrm[:, None, 2] * dirs[None, :, 2] > 0.0  # [n][k], the header's order
+    nb = (n + 63) // 64
+    padded = torch.zeros((nb * 64, k), dtype=torch.bool, device="cuda")
+    padded[:n] = above
+    b, j, l = padded.view(nb, 64, k).permute(0, 2, 1).nonzero(as_tuple=True)  # per block of 64 points, direction-major: the kernel's order
+    walked = torch.cat([pts[b * 64 + l], dirs[j]], dim=1).contiguous()
+    del padded, b, j, l
+    i, j = above.nonzero(as_tuple=True)
+    by_point = torch.cat([pts[i], dirs[j]], dim=1).contiguous()
+    m = walked.shape[0]
+    assert by_point.shape[0] == m
+    occ = torch.empty((m,), dtype=torch.uint8, device="cuda")
+    rows = []
+    ms = timed(lambda: G.occluded_device(accel, m, walked.data_ptr(), occ.data_ptr(), stream=s), calls)
+    rows.append(("ox: occluded, the above pairs as rays, per 64-point block direction-major", ms, m, 48.0 + 1.0))
+    del walked
+    ms = timed(lambda: G.occluded_device(accel, m, by_point.data_ptr(), occ.data_ptr(), stream=s), calls)
+    rows.append(("op: occluded, the above pairs as rays, point-major", ms, m, 48.0 + 1.0))
+    fraction = round(float(occ.float().mean()), 4)
+    del by_point
+    if hasattr(G, "open_directions_device"):
+        bits = torch.empty((n, k // 8), dtype=torch.uint8, device="cuda")
+        nopen, nabove = (torch.empty((n,), dtype=torch.int32, device="cuda") for _ in range(2))
+        ms = timed(lambda: G.open_directions_device(accel, n, pts.data_ptr(), nrm.data_ptr(), k, dirs.data_ptr(), bits.data_ptr(), k // 8, nopen.data_ptr(),
+                                                    nabove.data_ptr(), stream=s), calls)
+        rows.append(("o64: open directions, bit matrix and both counts of %d points x %d directions" % (n, k), ms, m, (2.0 * n * 24.0 + k * 24.0) / m + (k / 8 + 8.0) * n / m))
+        torch.cuda.synchronize()
+        opened = torch.zeros((n, k), dtype=torch.bool, device="cuda")
+        opened[i, j] = occ == 0
+        want = (opened.view(n, k // 8, 8).int() << torch.arange(8, device="cuda", dtype=torch.int32)).sum(dim=2).to(torch.uint8)
+        assert torch.equal(bits, want), "o64's bits are not op's bytes"
+        assert torch.equal(nopen, opened.sum(dim=1).int()) and torch.equal(nabove, above.sum(dim=1).int())
+    return [{"scene": name, "row": row, "points": n, "dirs": k, "pairs": n * k, "rays": walked_rays, "ms": round(ms, 4), "mrays_per_s": round(walked_rays / ms / 1e3, 1),
+             "bytes_per_walked_ray": round(bpr, 4), "above_fraction": round(m / (n * k), 4), "occluded_fraction_of_above": fraction, "calls": calls,
+             "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+             "gpu": torch.cuda.get_device_name(0)} for row, ms, walked_rays, bpr in rows]
+
+
 def measure_features(name, builder, size, calls):
     """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
     accel = G.Accel.from_scene(builder(G))
@@ -343,7 +404,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -352,8 +413,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -363,7 +424,9 @@ def main():
                 got += measure_visibility(name, builder, max(args.calls, 20))
             if want & {"all", "features"}:
                 got += measure_features(name, builder, args.size, max(args.calls, 20))
-            if want - {"queries", "visibility", "features"}:
+            if "directions" in want:
+                got += measure_directions(name, builder, max(args.calls, 20))
+            if want - {"queries", "visibility", "features", "directions"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
