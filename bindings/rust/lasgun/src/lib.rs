@@ -229,6 +229,10 @@ impl Img for Film {
 /// the basis is used as given.
 pub use sys::lg_lens as Lens;
 pub use sys::lg_features as Features;
+pub use sys::lg_scan_out as ScanOut;
+/// The work item a range scan of these counts would use (`lg_range_scan_lanes`): 1 beam lanes, 2 pose lanes; `lanes` 0 asks for the
+/// stated default (pose lanes iff n_poses >= n_beams); -1 for a bad `lanes`.  No device is touched.
+pub fn range_scan_lanes(n_poses: usize, n_beams: usize, lanes: i32) -> i32 { unsafe { sys::lg_range_scan_lanes(n_poses, n_beams, lanes) } }
 
 /// The rays of a lens over a width x height film, row-major pixels (or over the pixel slots `offsets` names), samples_root^2 per slot in
 /// idx = i*samples_root + j order: the layout `Accel::capture_rays` takes.  Generated on the current device.
@@ -338,6 +342,47 @@ impl<'s> Accel<'s> {
     pub unsafe fn open_directions_device(&self, dev_points: *const f64, dev_normals: *const f64, n_points: usize, dev_dirs: *const f64, n_dirs: usize,
                                          dev_bits: *mut u8, row_bytes: usize, dev_open: *mut u32, dev_above: *mut u32, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_open_directions_device(self.ptr, dev_points, dev_normals, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
+    /// Range scan (`lg_range_scan`): the first hits along `beams[k]` from `origins[i]`, ray (i, k) at `i * beams.len() + k` of every plane
+    /// given (`None` = not asked for; not all six).  `frames`: one row-major 3 x 3 matrix per pose whose columns are the sensor's axes in
+    /// world space, `d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z`; `None`: the beams are the directions, bit for bit.  range = the hit's t
+    /// (+inf: a miss), normal = the geometric normal faced toward the sensor, id = kind, prim, instance, material; `hits[i]` = the beams of
+    /// pose i that hit, `nearest[i]` = its smallest non-negative finite range (+inf: none).  `lanes`: 0 auto, 1 beam lanes, 2 pose lanes.
+    #[allow(clippy::too_many_arguments)]
+    pub fn range_scan(&self, origins: &[[f64; 3]], frames: Option<&[[f64; 9]]>, beams: &[[f64; 3]], lanes: i32, range: Option<&mut [f32]>,
+                      point: Option<&mut [[f32; 3]]>, normal: Option<&mut [[f32; 3]]>, id: Option<&mut [[u32; 4]]>, hits: Option<&mut [u32]>,
+                      nearest: Option<&mut [f32]>) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_scan_out>() == 48);
+        let pairs = origins.len().checked_mul(beams.len()).expect("range_scan: origins.len() * beams.len() overflows usize");
+        assert!(frames.map_or(true, |m| m.len() == origins.len()), "range_scan: one frame per pose");
+        assert!(range.as_ref().map_or(true, |p| p.len() == pairs) && point.as_ref().map_or(true, |p| p.len() == pairs)
+                && normal.as_ref().map_or(true, |p| p.len() == pairs) && id.as_ref().map_or(true, |p| p.len() == pairs)
+                && hits.as_ref().map_or(true, |p| p.len() == origins.len()) && nearest.as_ref().map_or(true, |p| p.len() == origins.len()),
+                "range_scan: planes of origins.len() * beams.len() elements, hits and nearest of origins.len()");
+        let out = sys::lg_scan_out {
+            range: range.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            point: point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            normal: normal.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            id: id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+            hits: hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            nearest: nearest.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+        };
+        let rc = unsafe {
+            sys::lg_range_scan(self.ptr, origins.as_ptr() as *const f64, frames.map_or(std::ptr::null(), |m| m.as_ptr() as *const f64), origins.len(),
+                               beams.as_ptr() as *const f64, beams.len(), lanes, &out)
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `range_scan` for tables in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `range_scan` states (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn range_scan_device(&self, dev_origins: *const f64, dev_frames: *const f64, n_poses: usize, dev_beams: *const f64, n_beams: usize, lanes: i32,
+                                    dev_out: &sys::lg_scan_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_range_scan_device(self.ptr, dev_origins, dev_frames, n_poses, dev_beams, n_beams, lanes, dev_out, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
     }

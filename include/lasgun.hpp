@@ -158,7 +158,7 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
-    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_open_directions / lg_radiance): rays are origin xyz, direction xyz
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_open_directions / lg_range_scan / lg_radiance): rays are origin xyz, direction xyz
     std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<lg_hit> hits(rays.size());
         if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
@@ -197,6 +197,39 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                                open && !open->empty() ? open->data() : nullptr, above && !above->empty() ? above->data() : nullptr))
             throw Error(lg_last_error());
         return bits;
+    }
+    // range scan (lg_range_scan): the first hits along beams[k] from origins[i], ray (i, k) at i * beams.size() + k of every plane asked for
+    // (a null member is not asked for; not all six).  frames: one row-major 3 x 3 matrix per pose whose columns are the sensor's axes in
+    // world space -- d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z --, or null: the beams are the directions, bit for bit.  range = the
+    // hit's t (+inf: a miss); normal = the geometric normal faced toward the sensor; id = kind, prim, instance, material; hits[i] = the
+    // beams of pose i that hit; nearest[i] = its smallest non-negative finite range (+inf: none).  lanes: 0 auto, 1 beam lanes, 2 pose lanes
+    struct Scan {
+        std::vector<float> *range = nullptr;                  // [poses*beams]
+        std::vector<std::array<float, 3>> *point = nullptr;
+        std::vector<std::array<float, 3>> *normal = nullptr;
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;
+        std::vector<uint32_t> *hits = nullptr;                // [poses]
+        std::vector<float> *nearest = nullptr;
+    };
+    void range_scan(const std::vector<std::array<double, 3>> &origins, const std::vector<std::array<double, 3>> &beams, const Scan &out,
+                    const std::vector<std::array<double, 9>> *frames = nullptr, int lanes = 0) const {
+        static_assert(sizeof(lg_scan_out) == 48, "lg_scan_out: six pointers");
+        if (frames && frames->size() != origins.size()) throw Error("range_scan: one frame per pose");
+        const size_t n = origins.size() * beams.size();
+        lg_scan_out o{};
+        if (out.range) { out.range->assign(n, 0.0f); o.range = out.range->data(); }
+        if (out.point) { out.point->assign(n, {0.0f, 0.0f, 0.0f}); o.point = n ? (*out.point)[0].data() : nullptr; }
+        if (out.normal) { out.normal->assign(n, {0.0f, 0.0f, 0.0f}); o.normal = n ? (*out.normal)[0].data() : nullptr; }
+        if (out.id) { out.id->assign(n, {0u, 0u, 0u, 0u}); o.id = n ? (*out.id)[0].data() : nullptr; }
+        if (out.hits) { out.hits->assign(origins.size(), 0u); o.hits = out.hits->data(); }
+        if (out.nearest) { out.nearest->assign(origins.size(), 0.0f); o.nearest = out.nearest->data(); }
+        if (lg_range_scan(h_, origins.empty() ? nullptr : origins[0].data(), frames && !frames->empty() ? (*frames)[0].data() : nullptr, origins.size(),
+                          beams.empty() ? nullptr : beams[0].data(), beams.size(), lanes, &o))
+            throw Error(lg_last_error());
+    }
+    void range_scan_device(const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_beams, size_t n_beams, int lanes,
+                           const lg_scan_out &dev_out, void *hip_stream) const {
+        if (lg_range_scan_device(h_, dev_origins, dev_frames, n_poses, dev_beams, n_beams, lanes, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {

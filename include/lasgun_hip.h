@@ -469,6 +469,66 @@ int lg_open_directions(const lg_accel *, const double *points, const double *nor
 int lg_open_directions_device(const lg_accel *, const double *dev_points, const double *dev_normals, size_t n_points,
                               const double *dev_dirs, size_t n_dirs, uint8_t *dev_bits, size_t row_bytes, uint32_t *dev_open,
                               uint32_t *dev_above, void *hip_stream);
+/* Range scans: the first hits along n_beams shared beams from each of n_poses sensor poses -- a simulated lidar or depth sensor, a probe
+ * grid that samples clearance for a distance-field bake, a cube-map depth pass, a height field -- without the caller writing
+ * n_poses * n_beams rays of 48 bytes and reading back lg_hit records of 96: n_poses + n_beams vectors describe all the rays, and only the
+ * planes asked for come back.  An EXTRA; no counterpart in the reference.
+ * Inputs: origins is n_poses x 3 doubles; frames is n_poses x 9 doubles, a row-major 3 x 3 matrix M per pose whose columns are the
+ * sensor's axes in world space, and MAY BE NULL; beams is n_beams x 3 doubles, shared by all poses.  Any f64 is accepted as it is, NaN and
+ * infinities included.
+ * Ray (i, k): the origin is origins[i] bit for bit.  With frames == NULL the direction is beams[k] bit for bit: no arithmetic makes the
+ * ray.  Otherwise, with M = frames + 9*i and b = beams[k], d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z for c = 0, 1, 2, in f64, in
+ * this order, with no contraction.  An identity frame is therefore NOT the same as NULL for -0.0, infinite and NaN beam components:
+ * -0.0 comes out as +0.0 unless both other products are -0.0 too, an infinite component makes the other two components of d NaN (0 * inf), and a
+ * NaN component all three.
+ * The direction is not normalised: range is the hit's parameter t, which is the distance when the beams are unit vectors and the frames
+ * rotations.
+ * Hit: what lg_intersect returns for that ray, bit for bit, in the accel's traversal mode exactly as for the other queries (reference,
+ * pruned, LDS-resident scene, fast mode); no switch of its own.  lg_accel_set_query_order plays no part: there is no ray array to sort.
+ * Planes (lg_scan_out): element (i, k) is at i*n_beams + k.  range = (float)t, +INF on a miss.  point[c] = (float)p[c].  normal[c] =
+ * (float)ng[c]: the geometric normal faced toward the sensor, the one an incidence angle wants -- not ns.  id is as in lg_features: kind,
+ * prim, instance, material in one 16-byte store, 0, ~0, ~0, -1 on a miss.  point and normal are zeros on a miss, as lg_hit has them.
+ * (float) rounds to nearest even.
+ * Per-pose reductions, both WRITTEN, NOT ACCUMULATED: whatever the buffers held before is gone.  hits[i] = the number of beams with
+ * kind != 0.  nearest[i] = the f32 range of pose i whose bit pattern, read as uint32, is smallest among the pose's hits; +INF where no
+ * hit's pattern is below +INF's.  In words: the smallest non-negative finite range -- a hit whose range is NaN, negative or has overflowed
+ * to +INF never wins.  It is an integer atomicMin on the bit pattern into a buffer pre-filled with 0x7F800000 (hits: an integer add into
+ * zeros), both pre-fills on the same stream ahead of the kernel; integer minima and sums do not depend on the order tiles finish in.
+ * lanes: the work item.  1: beam lanes -- a tile is one pose x 64 consecutive beams, a beam per lane; the rays share an origin, like a
+ * camera's; the form for few poses and many beams.  2: pose lanes -- a tile is 64 consecutive poses x 8 consecutive beams, a pose per
+ * lane and the beams in a loop, the direction sets' work item; with NULL frames the 64 rays are parallel.  0: auto -- pose lanes iff
+ * n_poses >= n_beams, else beam lanes; a stated default, not a measured optimum.  Any other value is an error.  Every output is the same
+ * bytes in either form.  Callers who want coherence order poses (pose lanes) or beams (beam lanes) so that neighbours in the array are
+ * neighbours in space.
+ * Limits, all checked before any HIP call: n_beams > 2^32 - 1 is an error; more tiles than 2^32 - 1 in the form chosen is an error:
+ * n_poses * ceil(n_beams / 64) > 2^32 - 1 for beam lanes, ceil(n_poses / 64) * ceil(n_beams / 8) > 2^32 - 1 for pose lanes (tiles are
+ * counted in 32 bits, as the other queries' are); planes that do not fit the address space are an error.  n_poses == 0 or n_beams == 0 is
+ * a successful no-op that writes nothing, and it is answered BEFORE every other check: with an empty set a NULL accel or out, NULL
+ * tables and a bad lanes are not looked at (as for the other structured queries).
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched), for non-zero counts: a NULL accel or out; NULL origins or beams
+ * with non-zero counts; all six outputs NULL; a bad lanes; the limits above; in the device form also a pointer that is not device memory
+ * of the accel's device or is misaligned (dev_origins, dev_frames and dev_beams 8-byte aligned, id 16, the float planes, hits and nearest
+ * 4), or a buffer that ends beyond its allocation.
+ * Device form: dev_out is a HOST struct of device pointers; it only enqueues on hip_stream (the two pre-fills that precede the kernel
+ * included); one stream at a time per accel.  Host form (synchronous): the tables go up, the planes come back into staging and are
+ * copied out at the end, so an error on the way leaves the caller's arrays as they were.
+ * Out of scope: there is no maximum range inside the walk -- the caller thresholds range; no noise or intensity model; no multi-device
+ * split.
+ * lg_range_scan_lanes: the work item a call with these counts and this `lanes` would use -- 1 or 2; -1 for a bad `lanes`; no device is
+ * touched. */
+typedef struct lg_scan_out {
+    float    *range;    /* [n_poses*n_beams]     */
+    float    *point;    /* [n_poses*n_beams][3]  */
+    float    *normal;   /* [n_poses*n_beams][3]  */
+    uint32_t *id;       /* [n_poses*n_beams][4]: kind, prim, instance, material -- the last 16 bytes of an lg_hit */
+    uint32_t *hits;     /* [n_poses]             */
+    float    *nearest;  /* [n_poses]             */
+} lg_scan_out;          /* 48 bytes; each pointer may be NULL, all NULL is an error */
+int lg_range_scan(const lg_accel *, const double *origins, const double *frames, size_t n_poses, const double *beams, size_t n_beams,
+                  int lanes, const lg_scan_out *out);                      /* host arrays; synchronous */
+int lg_range_scan_device(const lg_accel *, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_beams,
+                         size_t n_beams, int lanes, const lg_scan_out *dev_out, void *hip_stream);
+int lg_range_scan_lanes(size_t n_poses, size_t n_beams, int lanes);        /* the work item a call would use: 1 or 2; -1 for a bad `lanes`; no device */
 /* Radiance along every ray: the third query, for rays no camera of the scene generates (a fisheye or panorama, a light probe or cube
  * map, a lightmap bake from surface points, a caller's own path continuation, a second view of an accel without rebuilding it).
  * radiance[3*i ..] = what integrate() leaves for a pixel whose one sample is ray i: (Color::zero() + li(root, ray_i, depth 0)) * 1.0

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures, CScanOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -93,6 +93,7 @@ _EXTRA = {
     **RAY_FILM_SIGNATURES,
     **VISIBILITY_SIGNATURES,
     **DIRECTIONS_SIGNATURES,
+    **RANGE_SCAN_SIGNATURES,
     **FEATURES_SIGNATURES,
 }
 
@@ -108,6 +109,11 @@ LENS_EQUIRECTANGULAR, LENS_FISHEYE = 0, 1  # lg_lens::kind
 assert _C.sizeof(CLens) == 112, "lg_lens is 112 bytes"
 assert _C.sizeof(CFeatures) == 40, "lg_features is 40 bytes"
 FEATURE_PLANES = ("depth", "normal", "albedo", "coverage", "id")  # lg_features' members, in its order
+assert _C.sizeof(CScanOut) == 48, "lg_scan_out is 48 bytes"
+SCAN_PLANES = ("range", "point", "normal", "id", "hits", "nearest")  # lg_scan_out's members, in its order
+_SCAN_SHAPE = {"range": ((), _np.float32, True), "point": ((3,), _np.float32, True), "normal": ((3,), _np.float32, True), "id": ((4,), _np.uint32, True),
+               "hits": ((), _np.uint32, False), "nearest": ((), _np.float32, False)}  # (trailing shape, dtype, per pair -- else per pose)
+SCAN_LANES = {"auto": 0, "beam": 1, "pose": 2}
 _FEATURE_SHAPE = {"depth": ((), _np.float32), "normal": ((3,), _np.float32), "albedo": ((3,), _np.float32), "coverage": ((), _np.float32),
                   "id": ((4,), _np.uint32)}
 
@@ -608,6 +614,59 @@ class HipApi(Api):
         nopen, above = self.open_directions(accel, points, sphere_directions(k, radius), normals, counts="only")
         return nopen.astype(_np.float64) / _np.maximum(above, 1).astype(_np.float64)
 
+    # ---- range scans (include/lasgun_hip.h, lg_range_scan*): the first hits along K shared beams from N sensor poses
+    @staticmethod
+    def _scan_lanes(lanes):
+        return SCAN_LANES[lanes] if isinstance(lanes, str) else int(lanes)
+
+    def range_scan_lanes(self, n_poses, n_beams, lanes=0):
+        """The work item a scan of these counts would use: 1 beam lanes (one pose x 64 beams a wave), 2 pose lanes (64 poses x 8 beams);
+        -1 for a bad `lanes`.  lanes: 0 / "auto" (pose lanes iff n_poses >= n_beams), 1 / "beam", 2 / "pose".  No device is touched."""
+        return int(self.call("range_scan_lanes", int(n_poses), int(n_beams), self._scan_lanes(lanes)))
+
+    def range_scan(self, accel, origins, beams, frames=None, planes=("range",), lanes=0, into=None):
+        """The first hits along beams[k] from origins[i]: a dict of the planes asked for (any of "range", "point", "normal", "id", "hits",
+        "nearest") -- float32 (n_poses, n_beams) range = the hit's t (+inf: a miss), float32 (n_poses, n_beams, 3) point and normal (the
+        geometric normal faced toward the sensor; zeros on a miss), uint32 (n_poses, n_beams, 4) id = kind, prim, instance, material (0, ~0,
+        ~0, -1 on a miss), uint32 (n_poses,) hits = the beams that hit, float32 (n_poses,) nearest = the smallest non-negative finite range
+        (+inf: none).  frames: (n_poses, 3, 3) or (n_poses, 9) float64, row-major matrices whose columns are the sensor's axes in world space,
+        d[c] = (M[c,0]*b.x + M[c,1]*b.y) + M[c,2]*b.z; None: the beams are the directions, bit for bit.  The directions are not normalised.
+        lanes: range_scan_lanes' (the outputs do not depend on it).  `into`: a dict of C-contiguous arrays of those shapes, written in place.
+        Also `accel.range_scan(origins, beams, frames=None, planes=("range",), lanes=0)`."""
+        o, b = self._points(origins, "origins"), self._points(beams, "beams")
+        m = None
+        if frames is not None:
+            m = _np.ascontiguousarray(frames, dtype=_np.float64)
+            if m.shape not in ((o.shape[0], 3, 3), (o.shape[0], 9)):
+                raise ValueError("frames: one 3 x 3 matrix per pose")
+        planes = tuple(planes)
+        if any(p not in SCAN_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (SCAN_PLANES,))
+        out = {}
+        for p in planes:
+            tail, dt, per_pair = _SCAN_SHAPE[p]
+            shape = ((o.shape[0], b.shape[0]) if per_pair else (o.shape[0],)) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CScanOut(*[data(out.get(p)) for p in SCAN_PLANES])
+        if self.call("range_scan", accel.h, data(o), data(m), o.shape[0], data(b), b.shape[0], self._scan_lanes(lanes), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def range_scan_device(self, accel, n_poses, origins_ptr, frames_ptr, n_beams, beams_ptr, range_ptr=None, point_ptr=None, normal_ptr=None, id_ptr=None,
+                          hits_ptr=None, nearest_ptr=None, lanes=0, stream=None):
+        """Enqueue the scan of n_poses poses (device memory, 3 doubles an origin; frames_ptr 9 doubles a pose or None) along n_beams beams
+        (3 doubles each) into device memory: n_poses * n_beams elements at range_ptr (f32), point_ptr and normal_ptr (3 f32), id_ptr (4 u32,
+        16-byte aligned), n_poses elements at hits_ptr (u32) and nearest_ptr (f32); each may be None, not all."""
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        f = CScanOut(*[int(p) if p is not None else None for p in (range_ptr, point_ptr, normal_ptr, id_ptr, hits_ptr, nearest_ptr)])
+        if self.call("range_scan_device", accel.h, ptr(origins_ptr), ptr(frames_ptr), int(n_poses), ptr(beams_ptr), int(n_beams), self._scan_lanes(lanes),
+                     _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of the camera's primary hits
     def material_count(self, accel):
         """The number of materials of the accel's tables: indices 0 .. count-1 are valid for accel_material and name the rows of material_rgb."""
@@ -854,11 +913,25 @@ def sphere_directions(k, length=1.0):
     return _np.ascontiguousarray(d * (float(length) / _np.linalg.norm(d, axis=1))[:, None])
 
 
+def spinning_lidar_beams(rings, azimuths, elev_lo_deg, elev_hi_deg):
+    """(rings * azimuths, 3) float64 unit beams of a spinning lidar in the sensor's frame (x forward, y left, z up): `rings` elevations
+    spread evenly over [elev_lo_deg, elev_hi_deg] (one ring: their mean), `azimuths` steps of a full turn.  RING-MAJOR -- beam
+    r * azimuths + a -- so that 64 consecutive beams are neighbours: a stretch of one ring.  A convention of this WRAPPER, not of the C
+    contract."""
+    rings, azimuths = int(rings), int(azimuths)
+    elev = _np.deg2rad(_np.linspace(float(elev_lo_deg), float(elev_hi_deg), rings) if rings > 1 else _np.array([0.5 * (float(elev_lo_deg) + float(elev_hi_deg))]))
+    az = _np.arange(azimuths, dtype=_np.float64) * (2.0 * _np.pi / max(azimuths, 1))
+    e, a = _np.meshgrid(elev, az, indexing="ij")
+    d = _np.stack([_np.cos(e) * _np.cos(a), _np.cos(e) * _np.sin(a), _np.sin(e)], axis=-1).reshape(-1, 3)
+    return _np.ascontiguousarray(d / _np.linalg.norm(d, axis=1)[:, None])
+
+
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
 api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None: api.capture_features(self, w, h, rect, planes, material_rgb)  # accel.features(w, h)
 api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
 api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
+api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

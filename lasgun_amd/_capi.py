@@ -153,6 +153,14 @@ DIRECTIONS_SIGNATURES = {
                                          C.c_void_p]),
 }
 
+# Range scans (include/lasgun_hip.h, lg_range_scan / lg_range_scan_device / lg_range_scan_lanes): the first hits along K shared beams from N
+# sensor poses, as planes and per-pose reductions; the GPU library's alone.
+RANGE_SCAN_SIGNATURES = {
+    "range_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "range_scan_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "range_scan_lanes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int]),
+}
+
 # Feature buffers (include/lasgun_hip.h, lg_capture_features* / lg_accel_material_count): depth, normal, albedo, coverage and ids of the
 # camera's primary hits; the GPU library's alone.
 FEATURES_SIGNATURES = {
@@ -164,6 +172,10 @@ FEATURES_SIGNATURES = {
 
 class CFeatures(C.Structure):  # lg_features: five plane pointers, 40 bytes; NULL = not asked for
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]
+
+
+class CScanOut(C.Structure):  # lg_scan_out: six pointers, 48 bytes; NULL = not asked for
+    _fields_ = [("range", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p), ("hits", C.c_void_p), ("nearest", C.c_void_p)]
 
 
 class CLens(C.Structure):  # lg_lens: 112 bytes, no padding

@@ -75,6 +75,14 @@ hipError_t launch_open_directions(const DParams &P, const double *points, const 
                                   uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t open_directions_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t open_directions_set_lds_limit(size_t bytes, bool ldss);
+// k_scan.hip: range scans (lg_range_scan*) -- the closest-hit walk of the rays (origins[i], frames[i] * beams[k]), one pose x 64 beams
+// (beam lanes) or 64 poses x 8 beams (pose_lanes) per wave; only the outputs that are not nullptr are written, element (i, k) at
+// i * n_beams + k; hits and nearest are pre-filled by the caller ahead of the launch (0 and 0x7F800000); frames may be nullptr
+hipError_t launch_range_scan(const DParams &P, const double *origins, const double *frames, unsigned long long n_poses, const double *beams,
+                             unsigned long long n_beams, bool pose_lanes, float *range, float *point, float *normal, void *id, uint32_t *hits, uint32_t *nearest,
+                             const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t range_scan_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t range_scan_set_lds_limit(size_t bytes, bool ldss);
 // k_features.hip: feature buffers (lg_capture_features*) -- the closest-hit walk of the camera's own rays, an 8 x 8 tile of the rectangle per
 // wave and a pixel per lane; only the planes that are not nullptr are written, at DParams' output addressing (out_row0 / out_x0 / out_pitch)
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,

@@ -1,5 +1,6 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_radiance*, lg_camera_rays*,
-// lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of k_query.hip on the caller's stream, sized like
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_camera_rays*,
+// lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
+// k_visibility.hip, k_directions.hip, k_scan.hip and k_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
@@ -7,6 +8,7 @@
 #include <cstddef>
 
 #include "features_host.h"
+#include "scan_host.h"
 #include "internal.h"
 
 static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hit, ng) == 32 && offsetof(lg_hit, ns) == 56 &&
@@ -295,6 +297,82 @@ extern "C" int lg_open_directions_device(const lg_accel *a, const double *dev_po
         if (dev_open) check_device_buffer(*a, dev_open, n_points * sizeof(uint32_t), 4, "open");
         if (dev_above) check_device_buffer(*a, dev_above, n_points * sizeof(uint32_t), 4, "above");
         enqueue_open_directions(*a, dev_points, dev_normals, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- range scans (lg_range_scan*; k_scan.hip): the rays (origins[i], frames[i] * beams[k]) made in the kernel, their first hits written
+// as planes and reduced per pose.  The arithmetic that needs no device -- the lane rule, the tile counts, the sizes, the NULL and
+// alignment rules, the staging -- is scan_host.h's.
+extern "C" int lg_range_scan_lanes(size_t n_poses, size_t n_beams, int lanes) { return scan_lanes(n_poses, n_beams, lanes); }
+// One scan enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): the two
+// pre-fills, then the kernel in the shape's form
+static void enqueue_range_scan(const lg_accel &a, const double *origins, const double *frames, size_t n_poses, const double *beams, size_t n_beams, const ScanShape &shape,
+                               const lg_scan_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    P.ntiles = shape.tiles;
+    const TraversalGrid g = traversal_grid(a, P, range_scan_occupancy, ctx_for(a, stream), stream);
+    if (out.hits) HIP_TRY(hipMemsetAsync(out.hits, 0, n_poses * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
+    if (out.nearest) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out.nearest, 0x7F800000, n_poses, stream)); // ... and takes minima below +INF
+    HIP_TRY(launch_range_scan(P, origins, frames, n_poses, beams, n_beams, shape.form == SCAN_POSE_LANES, out.range, out.point, out.normal, out.id, out.hits,
+                              reinterpret_cast<uint32_t *>(out.nearest), a.accel_tri_base.p, a.fast, g.blocks, g.depth, stream));
+}
+// Host form: the tables go up, the planes come back into staging and are copied out at the end
+extern "C" int lg_range_scan(const lg_accel *a, const double *origins, const double *frames, size_t n_poses, const double *beams, size_t n_beams, int lanes,
+                             const lg_scan_out *out) {
+    return guarded([&] {
+        if (n_poses == 0 || n_beams == 0) return;
+        const ScanShape shape = check_scan(a, origins, n_poses, beams, n_beams, lanes, out);
+        const size_t pairs = shape.pairs;
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        ScanStaging st(*out, n_poses, pairs);
+        DevBuf<double> dorigins, dframes, dbeams;
+        DevBuf<float> drange, dpoint, dnormal, dnearest;
+        DevBuf<uint32_t> did, dhits;
+        lg_scan_out dev{};
+        dorigins.alloc(n_poses * 3);
+        if (frames) dframes.alloc(n_poses * 9);
+        dbeams.alloc(n_beams * 3);
+        if (out->range) { drange.alloc(pairs); dev.range = drange.p; }
+        if (out->point) { dpoint.alloc(pairs * 3); dev.point = dpoint.p; }
+        if (out->normal) { dnormal.alloc(pairs * 3); dev.normal = dnormal.p; }
+        if (out->id) { did.alloc(pairs * 4); dev.id = did.p; }
+        if (out->hits) { dhits.alloc(n_poses); dev.hits = dhits.p; }
+        if (out->nearest) { dnearest.alloc(n_poses); dev.nearest = dnearest.p; }
+        HIP_TRY(hipMemcpyAsync(dorigins.p, origins, n_poses * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        if (frames) HIP_TRY(hipMemcpyAsync(dframes.p, frames, n_poses * 9 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        HIP_TRY(hipMemcpyAsync(dbeams.p, beams, n_beams * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
+        enqueue_range_scan(*a, dorigins.p, frames ? dframes.p : nullptr, n_poses, dbeams.p, n_beams, shape, dev, a->stream);
+        if (out->range) HIP_TRY(hipMemcpyAsync(st.range.data(), drange.p, pairs * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->point) HIP_TRY(hipMemcpyAsync(st.point.data(), dpoint.p, pairs * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->normal) HIP_TRY(hipMemcpyAsync(st.normal.data(), dnormal.p, pairs * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        if (out->id) HIP_TRY(hipMemcpyAsync(st.id.data(), did.p, pairs * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        if (out->hits) HIP_TRY(hipMemcpyAsync(st.hits.data(), dhits.p, n_poses * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
+        if (out->nearest) HIP_TRY(hipMemcpyAsync(st.nearest.data(), dnearest.p, n_poses * sizeof(float), hipMemcpyDeviceToHost, a->stream));
+        sync_checked(*a);
+        place_scan(*out, st);
+    });
+}
+extern "C" int lg_range_scan_device(const lg_accel *a, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_beams, size_t n_beams,
+                                    int lanes, const lg_scan_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n_poses == 0 || n_beams == 0) return;
+        const ScanShape shape = check_scan(a, dev_origins, n_poses, dev_beams, n_beams, lanes, dev_out);
+        check_scan_alignment(dev_origins, dev_frames, dev_beams, *dev_out);
+        const size_t pairs = shape.pairs;
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_origins, n_poses * 3 * sizeof(double), 8, "origins");
+        if (dev_frames) check_device_buffer(*a, dev_frames, n_poses * 9 * sizeof(double), 8, "frames");
+        check_device_buffer(*a, dev_beams, n_beams * 3 * sizeof(double), 8, "beams");
+        if (dev_out->range) check_device_buffer(*a, dev_out->range, pairs * sizeof(float), 4, "range");
+        if (dev_out->point) check_device_buffer(*a, dev_out->point, pairs * 3 * sizeof(float), 4, "point");
+        if (dev_out->normal) check_device_buffer(*a, dev_out->normal, pairs * 3 * sizeof(float), 4, "normal");
+        if (dev_out->id) check_device_buffer(*a, dev_out->id, pairs * 4 * sizeof(uint32_t), 16, "id");
+        if (dev_out->hits) check_device_buffer(*a, dev_out->hits, n_poses * sizeof(uint32_t), 4, "hits");
+        if (dev_out->nearest) check_device_buffer(*a, dev_out->nearest, n_poses * sizeof(float), 4, "nearest");
+        enqueue_range_scan(*a, dev_origins, dev_frames, n_poses, dev_beams, n_beams, shape, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

@@ -1,0 +1,105 @@
+// lasgun_amd/csrc/scan_host.h -- the part of lg_range_scan* (query.cpp) that touches no device: the lane rule, the two tile counts with
+// their 32-bit limit, the planes' byte sizes, the NULL and alignment rules of the caller's lg_scan_out, and the host form's staging.
+// Everything here is arithmetic on size_t that can overflow, so it is kept free of HIP: tools/scan_host_check.cpp runs exactly this text
+// under AddressSanitizer / UBSan on the CPU, and lg_range_scan_lanes and both entry points call it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/lasgun_hip.h"
+
+namespace lg {
+
+static_assert(sizeof(lg_scan_out) == 48 && offsetof(lg_scan_out, range) == 0 && offsetof(lg_scan_out, point) == 8 && offsetof(lg_scan_out, normal) == 16 &&
+                  offsetof(lg_scan_out, id) == 24 && offsetof(lg_scan_out, hits) == 32 && offsetof(lg_scan_out, nearest) == 40,
+              "lg_scan_out: six pointers, 48 bytes");
+
+constexpr int SCAN_BEAM_LANES = 1, SCAN_POSE_LANES = 2;
+constexpr unsigned long long SCAN_MAX_TILES = 0xFFFFFFFFull; // tiles are counted in 32 bits, as the other queries' are
+constexpr unsigned long long SCAN_MAX_BEAMS = 0xFFFFFFFFull;
+
+// The work item a call takes: 1 beam lanes, 2 pose lanes; 0 asks for the stated default, pose lanes iff n_poses >= n_beams; -1: a bad `lanes`
+inline int scan_lanes(size_t n_poses, size_t n_beams, int lanes) {
+    if (lanes == SCAN_BEAM_LANES || lanes == SCAN_POSE_LANES) return lanes;
+    if (lanes != 0) return -1;
+    return n_poses >= n_beams ? SCAN_POSE_LANES : SCAN_BEAM_LANES;
+}
+
+inline unsigned long long scan_ceil_div(size_t n, unsigned d) { return (unsigned long long)(n / d) + (n % d ? 1u : 0u); }
+// The tiles of a scan in `form` (1 or 2): n_poses * ceil(n_beams / 64) of one pose x 64 beams, or ceil(n_poses / 64) * ceil(n_beams / 8) of
+// 64 poses x 8 beams.  false: more than 2^32 - 1 (the product itself is never formed where it could overflow)
+inline bool scan_tiles(size_t n_poses, size_t n_beams, int form, unsigned long long *tiles) {
+    const unsigned long long a = form == SCAN_POSE_LANES ? scan_ceil_div(n_poses, 64) : (unsigned long long)n_poses;
+    const unsigned long long b = form == SCAN_POSE_LANES ? scan_ceil_div(n_beams, 8) : scan_ceil_div(n_beams, 64);
+    if (a == 0 || b == 0) { *tiles = 0; return true; }
+    if (a > SCAN_MAX_TILES / b) return false;
+    *tiles = a * b;
+    return true;
+}
+// count * bytes_each as a size_t, refused where it does not fit the address space
+inline size_t scan_bytes(size_t count, size_t bytes_each, const char *what) {
+    if (bytes_each && count > SIZE_MAX / bytes_each) throw std::runtime_error(std::string(what) + " does not fit the address space");
+    return count * bytes_each;
+}
+
+// What a checked call is: its form, its tiles and its pairs
+struct ScanShape {
+    int form;        // SCAN_BEAM_LANES or SCAN_POSE_LANES
+    uint32_t tiles;
+    size_t pairs;    // n_poses * n_beams
+};
+// Everything the contract calls an error that needs no device, thrown here; the counts are not 0 (an empty set is answered before this)
+inline ScanShape check_scan(const void *accel, const double *origins, size_t n_poses, const double *beams, size_t n_beams, int lanes, const lg_scan_out *out) {
+    if (!accel) throw std::runtime_error("accel is NULL");
+    if (!out) throw std::runtime_error("out is NULL");
+    if (!origins) throw std::runtime_error("origins is NULL");
+    if (!beams) throw std::runtime_error("beams is NULL");
+    if (!out->range && !out->point && !out->normal && !out->id && !out->hits && !out->nearest) throw std::runtime_error("every plane of out is NULL: at least one output");
+    const int form = scan_lanes(n_poses, n_beams, lanes);
+    if (form < 0) throw std::runtime_error("lanes is " + std::to_string(lanes) + ": 0 (auto), 1 (beam lanes) or 2 (pose lanes)");
+    if ((unsigned long long)n_beams > SCAN_MAX_BEAMS) throw std::runtime_error("too many beams in one scan: at most 2^32 - 1");
+    unsigned long long tiles = 0;
+    if (!scan_tiles(n_poses, n_beams, form, &tiles))
+        throw std::runtime_error(form == SCAN_POSE_LANES ? "too many pairs in one scan: tiles of 64 poses x 8 beams are counted in 32 bits"
+                                                         : "too many pairs in one scan: tiles of one pose x 64 beams are counted in 32 bits");
+    if (n_poses > SIZE_MAX / n_beams) throw std::runtime_error("n_poses * n_beams does not fit the address space");
+    const size_t pairs = n_poses * n_beams;
+    (void)scan_bytes(n_poses, 9 * sizeof(double), "frames");
+    (void)scan_bytes(pairs, 4 * sizeof(uint32_t), "a plane of n_poses * n_beams elements"); // id, the widest: range 4, point and normal 12 bytes an element
+    return {form, (uint32_t)tiles, pairs};
+}
+// The device form's alignment rule: the inputs 8 bytes, id 16, the float planes, hits and nearest 4
+inline void check_scan_alignment(const double *origins, const double *frames, const double *beams, const lg_scan_out &out) {
+    const struct { const void *p; size_t align; const char *what; } rule[] = {
+        {origins, 8, "origins"}, {frames, 8, "frames"}, {beams, 8, "beams"}, {out.range, 4, "range"}, {out.point, 4, "point"},
+        {out.normal, 4, "normal"}, {out.id, 16, "id"}, {out.hits, 4, "hits"}, {out.nearest, 4, "nearest"}};
+    for (const auto &r : rule)
+        if (r.p && (uintptr_t)r.p % r.align) throw std::runtime_error(std::string(r.what) + " is not " + std::to_string(r.align) + "-byte aligned");
+}
+
+// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
+struct ScanStaging {
+    std::vector<float> range, point, normal;
+    std::vector<uint32_t> id, hits;
+    std::vector<float> nearest;
+    ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs)
+        : range(out.range ? pairs : 0), point(out.point ? pairs * 3 : 0), normal(out.normal ? pairs * 3 : 0), id(out.id ? pairs * 4 : 0), hits(out.hits ? n_poses : 0),
+          nearest(out.nearest ? n_poses : 0) {}
+};
+template <class T> inline void place_scan_plane(T *to, const std::vector<T> &from) {
+    if (to && !from.empty()) std::memcpy(to, from.data(), from.size() * sizeof(T));
+}
+inline void place_scan(const lg_scan_out &out, const ScanStaging &st) {
+    place_scan_plane(out.range, st.range);
+    place_scan_plane(out.point, st.point);
+    place_scan_plane(out.normal, st.normal);
+    place_scan_plane(out.id, st.id);
+    place_scan_plane(out.hits, st.hits);
+    place_scan_plane(out.nearest, st.nearest);
+}
+
+} // namespace lg

@@ -33,7 +33,14 @@ order, pushed out along ng, normals ng, against 64 Fibonacci directions of lengt
 matrix and both counts from the N + 64 vectors; row ox: lg_occluded_device (the parent commit's library has it) on the explicit rays of the
 ABOVE pairs only, ordered as the kernel walks them (per block of 64 points, direction-major) -- the best the two-call route can do, the
 rays' construction not timed; row op: the same rays point-major.  o64's bits and counts are checked against op's bytes.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions[,...]] [--out profiles/r08_query_order.jsonl]
+Range scans (lg_range_scan_device) -- --rows scan (not part of "all"), two shapes a scene, each in both lane forms.  Shape a: the first hits
+of a 1024^2 camera frame in 8 x 8 tile order, pushed out along ng, as poses without frames x 64 unit Fibonacci beams.  Shape b: 1024 poses
+along the camera's view axis, each with a rotation frame (the sensor yawed about the camera's up by a full turn over the poses) x the
+64 rings x 1024 azimuths of spinning_lidar_beams(-25 .. 15 degrees).  Rows s1 / s2: range, hits and nearest in beam lanes / pose lanes; rows
+s1a / s2a: all six outputs.  Beside them lg_intersect_device (the parent commit's library has it) on the explicit rays of the same pairs,
+their construction not timed: row sx1, pose-major, which is beam lanes' own order and the caller's natural one; row sx2, per block of 64
+poses beam-major, pose lanes' own order.  Every scan's range, hits and nearest are checked against sx1's records.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -332,6 +339,98 @@ def measure_directions(name, builder, calls, size=1024, k=64):
              "gpu": torch.cuda.get_device_name(0)} for row, ms, walked_rays, bpr in rows]
 
 
+def scan_shapes(accel, builder, s, size=1024, k=64):
+    """[(shape, poses, frames or None, beams)] of one scene, device tensors (module docstring)."""
+    assert G.camera_samples(accel) == 1 and size % 8 == 0
+    rays = torch.empty((size * size, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rays = rays.view(size // 8, 8, size // 8, 8, 6).permute(0, 2, 1, 3, 4).contiguous().view(-1, 6)  # 8 x 8 pixel tiles
+    hits = torch.empty((size * size * 96,), dtype=torch.uint8, device="cuda")
+    G.intersect_device(accel, size * size, rays.data_ptr(), hits.data_ptr(), stream=s)
+    f = hits.view(torch.float64).view(-1, 12)
+    f = f[hits.view(torch.int32).view(-1, 24)[:, 20] != 0]
+    shape_a = ("a", (f[:, 1:4] + f[:, 4:7] * ERR).contiguous(), None, torch.from_numpy(la.sphere_directions(k, 1.0)).cuda())
+    del rays, hits, f
+    cam = builder(pyref.Api).camera
+    eye, view, up, aux = (torch.tensor(v, dtype=torch.float64, device="cuda") for v in (cam.origin, cam.view, cam.up, cam.aux))
+    n = 1024
+    poses = (eye[None, :] + torch.linspace(0.0, 1.0, n, dtype=torch.float64, device="cuda")[:, None] * view[None, :]).contiguous()
+    yaw = torch.arange(n, dtype=torch.float64, device="cuda") * (2.0 * torch.pi / n)
+    fwd, left = view / torch.linalg.norm(view), -aux
+    x = torch.cos(yaw)[:, None] * fwd + torch.sin(yaw)[:, None] * left   # the sensor's axes in world space: the columns of M
+    y = -torch.sin(yaw)[:, None] * fwd + torch.cos(yaw)[:, None] * left
+    frames = torch.stack([x, y, up[None, :].expand(n, 3)], dim=2).contiguous().view(n, 9)  # row-major: M[c][axis]
+    return [shape_a, ("b", poses, frames, torch.from_numpy(la.spinning_lidar_beams(64, 1024, -25.0, 15.0)).cuda())]
+
+
+def measure_scan(name, builder, calls):
+    """Rows sx1 / sx2 / s1 / s2 / s1a / s2a of one scene, per shape (module docstring)."""
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    out = []
+    for shape, poses, frames, beams in scan_shapes(accel, builder, s):
+        n, k = poses.shape[0], beams.shape[0]
+        if frames is None:
+            d = beams[None, :, :].expand(n, k, 3)
+        else:  # the header's expression: three products, two sums in the stated order (separate kernels: nothing fused)
+            M = frames.view(n, 1, 9)
+            d = torch.stack([(M[..., 3 * c] * beams[None, :, 0] + M[..., 3 * c + 1] * beams[None, :, 1]) + M[..., 3 * c + 2] * beams[None, :, 2] for c in range(3)], dim=2)
+        by_pose = torch.cat([poses[:, None, :].expand(n, k, 3), d], dim=2).contiguous().view(-1, 6)
+        del d
+        nb = (n + 63) // 64
+        pi = (torch.arange(nb, device="cuda")[:, None, None] * 64 + torch.arange(64, device="cuda")[None, None, :]).expand(nb, k, 64)
+        valid = pi < n
+        src = (pi * k + torch.arange(k, device="cuda")[None, :, None])[valid]  # per block of 64 poses, beam-major: pose lanes' own order
+        by_block = by_pose[src].contiguous()
+        del pi, valid, src
+        m = n * k
+        hits = torch.empty((m * 96,), dtype=torch.uint8, device="cuda")
+        rows = []
+        ms = timed(lambda: G.intersect_device(accel, m, by_block.data_ptr(), hits.data_ptr(), stream=s), calls)
+        rows.append(("sx2: closest, the pairs as rays, per 64-pose block beam-major (pose lanes' own order)", ms, 144.0))
+        del by_block
+        ms = timed(lambda: G.intersect_device(accel, m, by_pose.data_ptr(), hits.data_ptr(), stream=s), calls)
+        rows.append(("sx1: closest, the pairs as rays, pose-major (beam lanes' own order)", ms, 144.0))
+        del by_pose
+        torch.cuda.synchronize()
+        kind = hits.view(torch.int32).view(-1, 24)[:, 20].view(n, k)
+        want_range = hits.view(torch.float64).view(-1, 12)[:, 0].float().view(n, k)
+        want_hits = (kind != 0).sum(dim=1).int()
+        bits = want_range.view(torch.int32)
+        want_nearest = torch.where((kind != 0) & (bits >= 0), bits, torch.full_like(bits, 0x7F800000)).min(dim=1).values.clamp(max=0x7F800000)  # (a NaN range never wins)
+        fraction = round(float((kind != 0).float().mean()), 4)
+        del hits
+        if hasattr(G, "range_scan_device"):
+            rng = torch.empty((n, k), dtype=torch.float32, device="cuda")
+            nhit, near = torch.empty((n,), dtype=torch.int32, device="cuda"), torch.empty((n,), dtype=torch.float32, device="cuda")
+            point, normal = (torch.empty((n, k, 3), dtype=torch.float32, device="cuda") for _ in range(2))
+            ident = torch.empty((n, k, 4), dtype=torch.int32, device="cuda")
+            fp = frames.data_ptr() if frames is not None else None
+            inputs = (n * (24.0 + (72.0 if frames is not None else 0.0)) + k * 24.0) / m
+            for lanes in (1, 2):
+                form = "beam lanes" if lanes == 1 else "pose lanes"
+                ms = timed(lambda: G.range_scan_device(accel, n, poses.data_ptr(), fp, k, beams.data_ptr(), range_ptr=rng.data_ptr(), hits_ptr=nhit.data_ptr(),
+                                                       nearest_ptr=near.data_ptr(), lanes=lanes, stream=s), calls)
+                rows.append(("s%d: range scan, %s, range + hits + nearest" % (lanes, form), ms, inputs + 4.0 + 8.0 / k))
+                torch.cuda.synchronize()
+                assert torch.equal(rng.view(torch.int32), bits), "the scan's range is not sx1's t"
+                assert torch.equal(nhit, want_hits) and torch.equal(near.view(torch.int32), want_nearest), "the scan's reductions are not sx1's"
+                ms = timed(lambda: G.range_scan_device(accel, n, poses.data_ptr(), fp, k, beams.data_ptr(), rng.data_ptr(), point.data_ptr(), normal.data_ptr(),
+                                                       ident.data_ptr(), nhit.data_ptr(), near.data_ptr(), lanes=lanes, stream=s), calls)
+                rows.append(("s%da: range scan, %s, all six outputs" % (lanes, form), ms, inputs + 44.0 + 8.0 / k))
+                torch.cuda.synchronize()
+                assert torch.equal(ident[..., 0], kind), "the scan's ids are not sx1's"
+            del rng, point, normal, ident
+        out += [{"scene": name, "shape": shape, "row": row, "poses": n, "beams": k, "frames": frames is not None, "rays": m, "ms": round(ms, 4),
+                 "mrays_per_s": round(m / ms / 1e3, 1), "bytes_per_pair": round(bpp, 4), "hit_fraction": fraction,
+                 "auto_lanes": G.range_scan_lanes(n, k) if hasattr(G, "range_scan_lanes") else None, "calls": calls,
+                 "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+                 "gpu": torch.cuda.get_device_name(0)} for row, ms, bpp in rows]
+        del want_range, bits, kind
+    return out
+
+
 def measure_features(name, builder, size, calls):
     """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
     accel = G.Accel.from_scene(builder(G))
@@ -404,7 +503,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -413,8 +512,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -426,7 +525,9 @@ def main():
                 got += measure_features(name, builder, args.size, max(args.calls, 20))
             if "directions" in want:
                 got += measure_directions(name, builder, max(args.calls, 20))
-            if want - {"queries", "visibility", "features", "directions"}:
+            if "scan" in want:
+                got += measure_scan(name, builder, max(args.calls, 20))
+            if want - {"queries", "visibility", "features", "directions", "scan"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
