@@ -4,9 +4,12 @@
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
-// its tiles from the sorted order; lg_query_order* return that order.
+// its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
+// lg_features is, is scan_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
+#include <deque>
 
+#include "bitrows_host.h"
 #include "features_host.h"
 #include "scan_host.h"
 #include "internal.h"
@@ -112,7 +115,58 @@ static void check_sorted_count(const lg_accel &a, size_t n) {
     if (a.query_order == 1 && n > MAX_SORTED_RAYS) throw Error("too many rays in one query for the sorted order (lg_accel_set_query_order): at most 2^32 - 1");
 }
 
-// Both host forms: copy the rays in, enqueue on the accel's stream, copy the results out, synchronise (as lg_capture_pixels)
+// One host form's round trip on the accel's stream (caller holds a.mtx): a device buffer is allocated as its array is named, then run() copies
+// the inputs up, enqueues, copies the outputs down, synchronises and places what was staged, all in that order.  An output is DIRECT (out: the
+// copy lands in the caller's memory), STAGED (staged: it lands in a buffer of this call's and reaches the caller's array after the synchronise:
+// an error on the way leaves that array as it was) or HELD (held: staged, and the form places it).  A NULL array is one not asked for: NULL.
+class RoundTrip {
+    struct Copy { void *to; const void *from; size_t bytes; };
+    const lg_accel &a;
+    std::deque<DevBuf<uint8_t>> mem;
+    std::deque<std::vector<uint8_t>> stage;
+    std::vector<Copy> up, down, place;
+    template <class T> T *device(size_t n) { mem.emplace_back(); mem.back().alloc(std::max<size_t>(n, 1) * sizeof(T)); return reinterpret_cast<T *>(mem.back().p); }
+
+  public:
+    explicit RoundTrip(const lg_accel &accel) : a(accel) { use_device(a.device); }
+    // n elements of `host` on the device (none: an element to point at, nothing copied)
+    template <class T> const T *in(const T *host, size_t n) {
+        if (!host) return nullptr;
+        T *d = device<T>(n);
+        if (n) up.push_back({d, host, n * sizeof(T)});
+        return d;
+    }
+    // n elements for the kernel to write, the first `back` of which come back to `host` (asked for whatever `host` is)
+    template <class T> T *out(T *host, size_t n, size_t back) {
+        T *d = device<T>(n);
+        down.push_back({host, d, back * sizeof(T)});
+        return d;
+    }
+    template <class T> T *out(T *host, size_t n) { return host ? out(host, n, n) : nullptr; }
+    template <class T> T *held(size_t n, const T **staged) {
+        stage.emplace_back(n * sizeof(T));
+        *staged = reinterpret_cast<const T *>(stage.back().data());
+        return out(reinterpret_cast<T *>(stage.back().data()), n, n);
+    }
+    template <class T> T *staged(T *host, size_t n) {
+        if (!host) return nullptr;
+        const T *s = nullptr;
+        T *d = held(n, &s);
+        place.push_back({host, s, n * sizeof(T)});
+        return d;
+    }
+    // a copy down from device memory that is not this call's, for the enqueue to ask for (it precedes the outputs')
+    void download(void *host, const void *dev, size_t bytes) { HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, a.stream)); }
+    template <class Enqueue> void run(Enqueue &&enqueue) {
+        for (const Copy &c : up) HIP_TRY(hipMemcpyAsync(c.to, c.from, c.bytes, hipMemcpyHostToDevice, a.stream));
+        enqueue();
+        for (const Copy &c : down) download(c.to, c.from, c.bytes);
+        sync_checked(a);
+        for (const Copy &c : place) std::memcpy(c.to, c.from, c.bytes);
+    }
+};
+
+// Both host forms: the rays up, the query on the accel's stream, the results straight back (as lg_capture_pixels)
 static int query_host(const lg_accel *a, const double *rays, size_t n, void *out, bool any) {
     return guarded([&] {
         if (n == 0) return;
@@ -123,15 +177,10 @@ static int query_host(const lg_accel *a, const double *rays, size_t n, void *out
         const size_t out_bytes = n * (any ? 1u : sizeof(lg_hit));
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
-        use_device(a->device);
-        DevBuf<double> drays;
-        DevBuf<uint8_t> dout;
-        drays.alloc(n * 6);
-        dout.alloc(out_bytes);
-        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_query(*a, drays.p, n, any ? nullptr : reinterpret_cast<lg_hit *>(dout.p), any ? dout.p : nullptr, a->stream);
-        HIP_TRY(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        RoundTrip trip(*a);
+        const double *drays = trip.in(rays, n * 6);
+        uint8_t *dout = trip.out(static_cast<uint8_t *>(out), out_bytes);
+        trip.run([&] { enqueue_query(*a, drays, n, any ? nullptr : reinterpret_cast<lg_hit *>(dout), any ? dout : nullptr, a->stream); });
     });
 }
 static int query_device(const lg_accel *a, const double *dev_rays, size_t n, void *dev_out, bool any, void *hip_stream) {
@@ -150,7 +199,6 @@ static int query_device(const lg_accel *a, const double *dev_rays, size_t n, voi
 }
 
 // ---- visibility matrices (lg_visibility*; k_visibility.hip): the segments from[i] -> to[j] made in the kernel, one bit each
-static size_t visibility_used_bytes(size_t n_to) { return n_to / 8 + (n_to % 8 ? 1 : 0); }
 // What both forms refuse before anything is allocated or enqueued (counts are not 0 here)
 static void check_visibility(const lg_accel *a, const double *from, size_t n_from, const double *to, size_t n_to, const uint8_t *bits, size_t row_bytes,
                              const uint32_t *blocked) {
@@ -158,11 +206,7 @@ static void check_visibility(const lg_accel *a, const double *from, size_t n_fro
     if (!from) throw Error("from is NULL");
     if (!to) throw Error("to is NULL");
     if (!bits && !blocked) throw Error("bits and blocked are both NULL: at least one output");
-    const size_t used = visibility_used_bytes(n_to);
-    if (bits && row_bytes < used) throw Error("row_bytes is " + std::to_string(row_bytes) + ", a row of " + std::to_string(n_to) + " bits takes " + std::to_string(used));
-    const unsigned long long ti = (unsigned long long)(n_from / 8 + (n_from % 8 ? 1 : 0));
-    if (ti > 0xFFFFFFFFull / used) throw Error("too many segments in one visibility matrix: 8 x 8 blocks are counted in 32 bits");
-    if (bits && n_from > 1 && row_bytes > (SIZE_MAX - used) / (n_from - 1)) throw Error("bits: n_from rows of row_bytes bytes do not fit the address space");
+    check_bit_rows(n_from, n_to, 8, bits, row_bytes, "too many segments in one visibility matrix: 8 x 8 blocks are counted in 32 bits", "n_from");
 }
 // One matrix enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): a tile is
 // an 8 x 8 block
@@ -170,7 +214,7 @@ static void enqueue_visibility(const lg_accel &a, const double *from, size_t n_f
                                hipStream_t stream) {
     check_queue_error(a);
     DParams P = base_params(a, 1, 1);
-    P.ntiles = (uint32_t)(((n_from + 7) / 8) * visibility_used_bytes(n_to));
+    P.ntiles = (uint32_t)(((n_from + 7) / 8) * bit_row_used_bytes(n_to));
     const TraversalGrid g = traversal_grid(a, P, visibility_occupancy, ctx_for(a, stream), stream);
     if (blocked) HIP_TRY(hipMemsetAsync(blocked, 0, n_from * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
     HIP_TRY(launch_visibility(P, from, n_from, to, n_to, bits, row_bytes, blocked, a.fast, g.blocks, g.depth, stream));
@@ -181,27 +225,16 @@ extern "C" int lg_visibility(const lg_accel *a, const double *from, size_t n_fro
     return guarded([&] {
         if (n_from == 0 || n_to == 0) return;
         check_visibility(a, from, n_from, to, n_to, bits, row_bytes, blocked);
-        const size_t used = visibility_used_bytes(n_to);
+        const size_t used = bit_row_used_bytes(n_to);
+        const bool strided = bits && row_bytes != used; // compact rows are the caller's layout already: they come straight back
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
-        DevBuf<double> dfrom, dto;
-        DevBuf<uint8_t> dbits;
-        DevBuf<uint32_t> dblocked;
-        dfrom.alloc(n_from * 3);
-        dto.alloc(n_to * 3);
-        if (bits) dbits.alloc(n_from * used);
-        if (blocked) dblocked.alloc(n_from);
-        std::vector<uint8_t> rows(bits && row_bytes != used ? n_from * used : 0);
-        std::vector<uint32_t> counts(blocked ? n_from : 0); // (staged: an error on the way leaves the caller's array as it was)
-        HIP_TRY(hipMemcpyAsync(dfrom.p, from, n_from * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(dto.p, to, n_to * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_visibility(*a, dfrom.p, n_from, dto.p, n_to, bits ? dbits.p : nullptr, used, blocked ? dblocked.p : nullptr, a->stream);
-        if (bits) HIP_TRY(hipMemcpyAsync(row_bytes != used ? rows.data() : bits, dbits.p, n_from * used, hipMemcpyDeviceToHost, a->stream));
-        if (blocked) HIP_TRY(hipMemcpyAsync(counts.data(), dblocked.p, n_from * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
-        if (bits && row_bytes != used)
-            for (size_t i = 0; i < n_from; ++i) std::memcpy(bits + i * row_bytes, rows.data() + i * used, used);
-        if (blocked) std::memcpy(blocked, counts.data(), n_from * sizeof(uint32_t));
+        RoundTrip trip(*a);
+        const double *dfrom = trip.in(from, n_from * 3), *dto = trip.in(to, n_to * 3);
+        const uint8_t *rows = nullptr;
+        uint8_t *dbits = strided ? trip.held(n_from * used, &rows) : trip.out(bits, n_from * used);
+        uint32_t *dblocked = trip.staged(blocked, n_from);
+        trip.run([&] { enqueue_visibility(*a, dfrom, n_from, dto, n_to, dbits, used, dblocked, a->stream); });
+        if (strided) place_bit_rows(bits, row_bytes, rows, n_from, used);
     });
 }
 extern "C" int lg_visibility_device(const lg_accel *a, const double *dev_from, size_t n_from, const double *dev_to, size_t n_to, uint8_t *dev_bits, size_t row_bytes,
@@ -213,7 +246,7 @@ extern "C" int lg_visibility_device(const lg_accel *a, const double *dev_from, s
         use_device(a->device);
         check_device_buffer(*a, dev_from, n_from * 3 * sizeof(double), 8, "from");
         check_device_buffer(*a, dev_to, n_to * 3 * sizeof(double), 8, "to");
-        if (dev_bits) check_device_buffer(*a, dev_bits, (n_from - 1) * row_bytes + visibility_used_bytes(n_to), 1, "bits");
+        if (dev_bits) check_device_buffer(*a, dev_bits, bit_rows_extent(n_from, row_bytes, bit_row_used_bytes(n_to)), 1, "bits");
         if (dev_blocked) check_device_buffer(*a, dev_blocked, n_from * sizeof(uint32_t), 4, "blocked");
         enqueue_visibility(*a, dev_from, n_from, dev_to, n_to, dev_bits, row_bytes, dev_blocked, (hipStream_t)hip_stream);
     });
@@ -229,11 +262,7 @@ static void check_open_directions(const lg_accel *a, const double *points, size_
     if (!dirs) throw Error("dirs is NULL");
     if (!bits && !open && !above) throw Error("bits, open and above are all NULL: at least one output");
     if ((unsigned long long)n_dirs > 0xFFFFFFFFull) throw Error("too many directions in one set: at most 2^32 - 1 (tiles of 64 points x 8 directions are counted in 32 bits)");
-    const size_t used = visibility_used_bytes(n_dirs);
-    if (bits && row_bytes < used) throw Error("row_bytes is " + std::to_string(row_bytes) + ", a row of " + std::to_string(n_dirs) + " bits takes " + std::to_string(used));
-    const unsigned long long pb = (unsigned long long)(n_points / 64 + (n_points % 64 ? 1 : 0));
-    if (pb > 0xFFFFFFFFull / used) throw Error("too many pairs in one direction set: tiles of 64 points x 8 directions are counted in 32 bits");
-    if (bits && n_points > 1 && row_bytes > (SIZE_MAX - used) / (n_points - 1)) throw Error("bits: n_points rows of row_bytes bytes do not fit the address space");
+    check_bit_rows(n_points, n_dirs, 64, bits, row_bytes, "too many pairs in one direction set: tiles of 64 points x 8 directions are counted in 32 bits", "n_points");
 }
 // One direction set enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): a
 // tile is 64 points x 8 directions
@@ -241,7 +270,7 @@ static void enqueue_open_directions(const lg_accel &a, const double *points, con
                                     size_t row_bytes, uint32_t *open, uint32_t *above, hipStream_t stream) {
     check_queue_error(a);
     DParams P = base_params(a, 1, 1);
-    P.ntiles = (uint32_t)(((n_points + 63) / 64) * visibility_used_bytes(n_dirs));
+    P.ntiles = (uint32_t)(((n_points + 63) / 64) * bit_row_used_bytes(n_dirs));
     const TraversalGrid g = traversal_grid(a, P, open_directions_occupancy, ctx_for(a, stream), stream);
     if (open) HIP_TRY(hipMemsetAsync(open, 0, n_points * sizeof(uint32_t), stream)); // written, not accumulated: the kernel adds to zero
     if (above) HIP_TRY(hipMemsetAsync(above, 0, n_points * sizeof(uint32_t), stream));
@@ -254,33 +283,15 @@ extern "C" int lg_open_directions(const lg_accel *a, const double *points, const
     return guarded([&] {
         if (n_points == 0 || n_dirs == 0) return;
         check_open_directions(a, points, n_points, dirs, n_dirs, bits, row_bytes, open, above);
-        const size_t used = visibility_used_bytes(n_dirs);
+        const size_t used = bit_row_used_bytes(n_dirs);
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
-        DevBuf<double> dpoints, dnormals, ddirs;
-        DevBuf<uint8_t> dbits;
-        DevBuf<uint32_t> dopen, dabove;
-        dpoints.alloc(n_points * 3);
-        if (normals) dnormals.alloc(n_points * 3);
-        ddirs.alloc(n_dirs * 3);
-        if (bits) dbits.alloc(n_points * used);
-        if (open) dopen.alloc(n_points);
-        if (above) dabove.alloc(n_points);
-        std::vector<uint8_t> rows(bits ? n_points * used : 0); // (staged like the counts: an error on the way leaves the caller's arrays as they were)
-        std::vector<uint32_t> nopen(open ? n_points : 0), nabove(above ? n_points : 0);
-        HIP_TRY(hipMemcpyAsync(dpoints.p, points, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        if (normals) HIP_TRY(hipMemcpyAsync(dnormals.p, normals, n_points * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(ddirs.p, dirs, n_dirs * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_open_directions(*a, dpoints.p, normals ? dnormals.p : nullptr, n_points, ddirs.p, n_dirs, bits ? dbits.p : nullptr, used, open ? dopen.p : nullptr,
-                                above ? dabove.p : nullptr, a->stream);
-        if (bits) HIP_TRY(hipMemcpyAsync(rows.data(), dbits.p, n_points * used, hipMemcpyDeviceToHost, a->stream));
-        if (open) HIP_TRY(hipMemcpyAsync(nopen.data(), dopen.p, n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        if (above) HIP_TRY(hipMemcpyAsync(nabove.data(), dabove.p, n_points * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
-        if (bits)
-            for (size_t i = 0; i < n_points; ++i) std::memcpy(bits + i * row_bytes, rows.data() + i * used, used);
-        if (open) std::memcpy(open, nopen.data(), n_points * sizeof(uint32_t));
-        if (above) std::memcpy(above, nabove.data(), n_points * sizeof(uint32_t));
+        RoundTrip trip(*a);
+        const double *dpoints = trip.in(points, n_points * 3), *dnormals = trip.in(normals, n_points * 3), *ddirs = trip.in(dirs, n_dirs * 3);
+        const uint8_t *rows = nullptr;
+        uint8_t *dbits = bits ? trip.held(n_points * used, &rows) : nullptr; // (held whatever the stride, like the counts)
+        uint32_t *dopen = trip.staged(open, n_points), *dabove = trip.staged(above, n_points);
+        trip.run([&] { enqueue_open_directions(*a, dpoints, dnormals, n_points, ddirs, n_dirs, dbits, used, dopen, dabove, a->stream); });
+        if (bits) place_bit_rows(bits, row_bytes, rows, n_points, used);
     });
 }
 extern "C" int lg_open_directions_device(const lg_accel *a, const double *dev_points, const double *dev_normals, size_t n_points, const double *dev_dirs, size_t n_dirs,
@@ -293,7 +304,7 @@ extern "C" int lg_open_directions_device(const lg_accel *a, const double *dev_po
         check_device_buffer(*a, dev_points, n_points * 3 * sizeof(double), 8, "points");
         if (dev_normals) check_device_buffer(*a, dev_normals, n_points * 3 * sizeof(double), 8, "normals");
         check_device_buffer(*a, dev_dirs, n_dirs * 3 * sizeof(double), 8, "dirs");
-        if (dev_bits) check_device_buffer(*a, dev_bits, (n_points - 1) * row_bytes + visibility_used_bytes(n_dirs), 1, "bits");
+        if (dev_bits) check_device_buffer(*a, dev_bits, bit_rows_extent(n_points, row_bytes, bit_row_used_bytes(n_dirs)), 1, "bits");
         if (dev_open) check_device_buffer(*a, dev_open, n_points * sizeof(uint32_t), 4, "open");
         if (dev_above) check_device_buffer(*a, dev_above, n_points * sizeof(uint32_t), 4, "above");
         enqueue_open_directions(*a, dev_points, dev_normals, n_points, dev_dirs, n_dirs, dev_bits, row_bytes, dev_open, dev_above, (hipStream_t)hip_stream);
@@ -325,32 +336,12 @@ extern "C" int lg_range_scan(const lg_accel *a, const double *origins, const dou
         const ScanShape shape = check_scan(a, origins, n_poses, beams, n_beams, lanes, out);
         const size_t pairs = shape.pairs;
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
+        RoundTrip trip(*a);
         ScanStaging st(*out, n_poses, pairs);
-        DevBuf<double> dorigins, dframes, dbeams;
-        DevBuf<float> drange, dpoint, dnormal, dnearest;
-        DevBuf<uint32_t> did, dhits;
-        lg_scan_out dev{};
-        dorigins.alloc(n_poses * 3);
-        if (frames) dframes.alloc(n_poses * 9);
-        dbeams.alloc(n_beams * 3);
-        if (out->range) { drange.alloc(pairs); dev.range = drange.p; }
-        if (out->point) { dpoint.alloc(pairs * 3); dev.point = dpoint.p; }
-        if (out->normal) { dnormal.alloc(pairs * 3); dev.normal = dnormal.p; }
-        if (out->id) { did.alloc(pairs * 4); dev.id = did.p; }
-        if (out->hits) { dhits.alloc(n_poses); dev.hits = dhits.p; }
-        if (out->nearest) { dnearest.alloc(n_poses); dev.nearest = dnearest.p; }
-        HIP_TRY(hipMemcpyAsync(dorigins.p, origins, n_poses * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        if (frames) HIP_TRY(hipMemcpyAsync(dframes.p, frames, n_poses * 9 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        HIP_TRY(hipMemcpyAsync(dbeams.p, beams, n_beams * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_range_scan(*a, dorigins.p, frames ? dframes.p : nullptr, n_poses, dbeams.p, n_beams, shape, dev, a->stream);
-        if (out->range) HIP_TRY(hipMemcpyAsync(st.range.data(), drange.p, pairs * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->point) HIP_TRY(hipMemcpyAsync(st.point.data(), dpoint.p, pairs * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->normal) HIP_TRY(hipMemcpyAsync(st.normal.data(), dnormal.p, pairs * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->id) HIP_TRY(hipMemcpyAsync(st.id.data(), did.p, pairs * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        if (out->hits) HIP_TRY(hipMemcpyAsync(st.hits.data(), dhits.p, n_poses * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        if (out->nearest) HIP_TRY(hipMemcpyAsync(st.nearest.data(), dnearest.p, n_poses * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        const double *dorigins = trip.in(origins, n_poses * 3), *dframes = trip.in(frames, n_poses * 9), *dbeams = trip.in(beams, n_beams * 3);
+        lg_scan_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        scan_planes(dev, n_poses, pairs, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        trip.run([&] { enqueue_range_scan(*a, dorigins, dframes, n_poses, dbeams, n_beams, shape, dev, a->stream); });
         place_scan(*out, st);
     });
 }
@@ -366,12 +357,7 @@ extern "C" int lg_range_scan_device(const lg_accel *a, const double *dev_origins
         check_device_buffer(*a, dev_origins, n_poses * 3 * sizeof(double), 8, "origins");
         if (dev_frames) check_device_buffer(*a, dev_frames, n_poses * 9 * sizeof(double), 8, "frames");
         check_device_buffer(*a, dev_beams, n_beams * 3 * sizeof(double), 8, "beams");
-        if (dev_out->range) check_device_buffer(*a, dev_out->range, pairs * sizeof(float), 4, "range");
-        if (dev_out->point) check_device_buffer(*a, dev_out->point, pairs * 3 * sizeof(float), 4, "point");
-        if (dev_out->normal) check_device_buffer(*a, dev_out->normal, pairs * 3 * sizeof(float), 4, "normal");
-        if (dev_out->id) check_device_buffer(*a, dev_out->id, pairs * 4 * sizeof(uint32_t), 16, "id");
-        if (dev_out->hits) check_device_buffer(*a, dev_out->hits, n_poses * sizeof(uint32_t), 4, "hits");
-        if (dev_out->nearest) check_device_buffer(*a, dev_out->nearest, n_poses * sizeof(float), 4, "nearest");
+        scan_planes(*dev_out, n_poses, pairs, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
         enqueue_range_scan(*a, dev_origins, dev_frames, n_poses, dev_beams, n_beams, shape, *dev_out, (hipStream_t)hip_stream);
     });
 }
@@ -401,14 +387,10 @@ extern "C" int lg_radiance(const lg_accel *a, const double *rays, size_t n, doub
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         radiance_possible(*a);
-        use_device(a->device);
-        DevBuf<double> drays, dout;
-        drays.alloc(n * 6);
-        dout.alloc(n * 3);
-        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_radiance_query(*a, drays.p, n, dout.p, a->stream);
-        HIP_TRY(hipMemcpyAsync(radiance, dout.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        RoundTrip trip(*a);
+        const double *drays = trip.in(rays, n * 6);
+        double *dout = trip.out(radiance, n * 3);
+        trip.run([&] { enqueue_radiance_query(*a, drays, n, dout, a->stream); });
     });
 }
 extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream) {
@@ -459,27 +441,21 @@ extern "C" int lg_capture_rays(const lg_accel *a, const double *rays, size_t pix
         std::lock_guard<std::mutex> g(a->mtx);
         const size_t n = film_ray_count(*a, pixels, samples);
         radiance_possible(*a);
-        use_device(a->device);
+        RoundTrip trip(*a);
         const unsigned long long npix = (unsigned long long)w * h;
-        DevBuf<double> drays, drgb;
-        DevBuf<uint32_t> drgba;
-        drays.alloc(n * 6);
-        if (film) drgba.alloc(pixels);
-        if (rgb) drgb.alloc(pixels * 3);
-        std::vector<uint32_t> hrgba(film && offsets ? pixels : 0);
-        std::vector<double> hrgb(rgb && offsets ? pixels * 3 : 0);
-        const size_t direct = (size_t)std::min<unsigned long long>(pixels, npix); // no offsets: slot g is pixel g
-        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        enqueue_film_query(*a, drays.p, pixels, samples, nullptr, pixels, film ? drgba.p : nullptr, rgb ? drgb.p : nullptr, a->stream);
-        if (film) HIP_TRY(hipMemcpyAsync(offsets ? (void *)hrgba.data() : (void *)film->px, drgba.p, (offsets ? pixels : direct) * 4, hipMemcpyDeviceToHost, a->stream));
-        if (rgb) HIP_TRY(hipMemcpyAsync(offsets ? hrgb.data() : rgb, drgb.p, (offsets ? pixels : direct) * 3 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        const size_t direct = (size_t)std::min<unsigned long long>(pixels, npix); // no offsets: slot g is pixel g, and those of the film come straight back
+        const double *drays = trip.in(rays, n * 6);
+        const uint8_t *hrgba = nullptr; // with offsets: every slot is held and placed below
+        const double *hrgb = nullptr;
+        uint8_t *drgba = !film ? nullptr : offsets ? trip.held(pixels * 4, &hrgba) : trip.out(film->px, pixels * 4, direct * 4);
+        double *drgb = !rgb ? nullptr : offsets ? trip.held(pixels * 3, &hrgb) : trip.out(rgb, pixels * 3, direct * 3);
+        trip.run([&] { enqueue_film_query(*a, drays, pixels, samples, nullptr, pixels, reinterpret_cast<uint32_t *>(drgba), drgb, a->stream); });
         if (!offsets) return;
         for (size_t s = 0; s < pixels; ++s) {
             const uint64_t off = offsets[s];
             if (off >= npix) continue;
-            if (film) std::memcpy(film->px + 4 * off, &hrgba[s], 4);
-            if (rgb) std::memcpy(rgb + 3 * off, &hrgb[3 * s], 3 * sizeof(double));
+            if (film) std::memcpy(film->px + 4 * off, hrgba + 4 * s, 4);
+            if (rgb) std::memcpy(rgb + 3 * off, hrgb + 3 * s, 3 * sizeof(double));
         }
     });
 }
@@ -526,29 +502,13 @@ extern "C" int lg_capture_features(const lg_accel *a, uint32_t w, uint32_t h, ui
         const size_t pixels = check_features(a, out, w, h, x0, y0, x1, y1, material_rgb);
         if (pixels == 0) return;
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
-        const size_t nmat = a->flat.material_pods.size();
+        RoundTrip trip(*a);
         FeatureStaging st(*out, pixels);
-        DevBuf<float> ddepth, dnormal, dalbedo, dcoverage;
-        DevBuf<uint32_t> did;
-        DevBuf<double> dtable;
-        lg_features dev{};
-        if (out->depth) { ddepth.alloc(pixels); dev.depth = ddepth.p; }
-        if (out->normal) { dnormal.alloc(pixels * 3); dev.normal = dnormal.p; }
-        if (out->albedo) { dalbedo.alloc(pixels * 3); dev.albedo = dalbedo.p; }
-        if (out->coverage) { dcoverage.alloc(pixels); dev.coverage = dcoverage.p; }
-        if (out->id) { did.alloc(pixels * 4); dev.id = did.p; }
-        if (out->albedo) {
-            dtable.alloc(std::max<size_t>(nmat * 3, 1));
-            if (nmat) HIP_TRY(hipMemcpyAsync(dtable.p, material_rgb, nmat * 3 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        }
-        enqueue_features(*a, w, h, x0, y0, x1, y1, dev, dtable.p, true, a->stream);
-        if (out->depth) HIP_TRY(hipMemcpyAsync(st.depth.data(), ddepth.p, pixels * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->normal) HIP_TRY(hipMemcpyAsync(st.normal.data(), dnormal.p, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->albedo) HIP_TRY(hipMemcpyAsync(st.albedo.data(), dalbedo.p, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->coverage) HIP_TRY(hipMemcpyAsync(st.coverage.data(), dcoverage.p, pixels * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-        if (out->id) HIP_TRY(hipMemcpyAsync(st.id.data(), did.p, pixels * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        lg_features dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        feature_planes(dev, [&](auto *&p, auto plane, size_t per_pixel, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), pixels * per_pixel); });
+        // the table for albedo alone (a scene without materials: an element to point at, nothing copied)
+        const double *dtable = out->albedo ? trip.in(material_rgb, a->flat.material_pods.size() * 3) : nullptr;
+        trip.run([&] { enqueue_features(*a, w, h, x0, y0, x1, y1, dev, dtable, true, a->stream); });
         place_features(*out, st, w, x0, y0, x1, y1);
     });
 }
@@ -559,11 +519,7 @@ extern "C" int lg_capture_features_device(const lg_accel *a, uint32_t w, uint32_
         std::lock_guard<std::mutex> g(a->mtx);
         use_device(a->device);
         const size_t npix = (size_t)w * h, nmat = a->flat.material_pods.size();
-        if (out->depth) check_device_buffer(*a, out->depth, npix * sizeof(float), 4, "depth");
-        if (out->normal) check_device_buffer(*a, out->normal, npix * 3 * sizeof(float), 4, "normal");
-        if (out->albedo) check_device_buffer(*a, out->albedo, npix * 3 * sizeof(float), 4, "albedo");
-        if (out->coverage) check_device_buffer(*a, out->coverage, npix * sizeof(float), 4, "coverage");
-        if (out->id) check_device_buffer(*a, out->id, npix * 4 * sizeof(uint32_t), 16, "id");
+        feature_planes(*out, [&](auto *p, auto, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, npix * per_pixel * sizeof *p, align, what); });
         if (out->albedo) check_device_buffer(*a, dev_material_rgb, nmat * 3 * sizeof(double), 8, "material_rgb");
         enqueue_features(*a, w, h, x0, y0, x1, y1, *out, dev_material_rgb, false, (hipStream_t)hip_stream);
     });
@@ -670,16 +626,12 @@ int lg_query_order(const lg_accel *a, const double *rays, size_t n, uint32_t *pe
         if (!perm) throw Error("perm is NULL");
         if (n > MAX_SORTED_RAYS) throw Error("too many rays to order: at most 2^32 - 1");
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
-        DevBuf<double> drays;
-        DevBuf<uint32_t> dkeys;
-        drays.alloc(n * 6);
-        if (keys) dkeys.alloc(n);
-        HIP_TRY(hipMemcpyAsync(drays.p, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        const uint32_t *dperm = enqueue_query_order(*a, ctx_for(*a, a->stream), drays.p, n, keys ? dkeys.p : nullptr, nullptr, a->stream);
-        HIP_TRY(hipMemcpyAsync(perm, dperm, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        if (keys) HIP_TRY(hipMemcpyAsync(keys, dkeys.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        RoundTrip trip(*a);
+        const double *drays = trip.in(rays, n * 6);
+        uint32_t *dkeys = trip.out(keys, n);
+        trip.run([&] { // (the permutation is left in the context's scratch: it comes back from there)
+            trip.download(perm, enqueue_query_order(*a, ctx_for(*a, a->stream), drays, n, dkeys, nullptr, a->stream), n * sizeof(uint32_t));
+        });
     });
 }
 int lg_query_order_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t *dev_perm, uint32_t *dev_keys, void *hip_stream) {
@@ -704,12 +656,9 @@ int lg_camera_rays(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint3
         if (n == 0) return;
         if (!rays) throw Error("rays is NULL");
         std::lock_guard<std::mutex> g(a->mtx);
-        use_device(a->device);
-        DevBuf<double> d;
-        d.alloc(n * 6);
-        enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, d.p, n, a->stream);
-        HIP_TRY(hipMemcpyAsync(rays, d.p, n * 6 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
-        sync_checked(*a);
+        RoundTrip trip(*a);
+        double *d = trip.out(rays, n * 6);
+        trip.run([&] { enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, d, n, a->stream); });
     });
 }
 int lg_camera_rays_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *dev_rays, void *hip_stream) {

@@ -1,7 +1,7 @@
 // lasgun_amd/csrc/scan_host.h -- the part of lg_range_scan* (query.cpp) that touches no device: the lane rule, the two tile counts with
-// their 32-bit limit, the planes' byte sizes, the NULL and alignment rules of the caller's lg_scan_out, and the host form's staging.
-// Everything here is arithmetic on size_t that can overflow, so it is kept free of HIP: tools/scan_host_check.cpp runs exactly this text
-// under AddressSanitizer / UBSan on the CPU, and lg_range_scan_lanes and both entry points call it.
+// their 32-bit limit, the planes' byte sizes, and the one table of lg_scan_out's planes (scan_planes) with what follows from it: the NULL and
+// alignment rules, the host form's staging and its placement.  Arithmetic on size_t that can overflow, so kept free of HIP:
+// tools/scan_host_check.cpp runs exactly this text under AddressSanitizer / UBSan on the CPU, and lg_range_scan_lanes and both entry points call it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -46,6 +46,25 @@ inline size_t scan_bytes(size_t count, size_t bytes_each, const char *what) {
     return count * bytes_each;
 }
 
+// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
+struct ScanStaging {
+    std::vector<float> range, point, normal;
+    std::vector<uint32_t> id, hits;
+    std::vector<float> nearest;
+    ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs);
+};
+// The six planes of lg_scan_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, the
+// plane's staging, its elements, its alignment in bytes, its name) in the struct's order.  The alignment and NULL rules, the staging's
+// sizes, the host form's device buffers and copies, the device form's buffer checks and the placement all go through here.
+template <class Out, class F> inline void scan_planes(Out &out, size_t n_poses, size_t pairs, F &&f) {
+    f(out.range, &ScanStaging::range, pairs, 4, "range");
+    f(out.point, &ScanStaging::point, pairs * 3, 4, "point");
+    f(out.normal, &ScanStaging::normal, pairs * 3, 4, "normal");
+    f(out.id, &ScanStaging::id, pairs * 4, 16, "id");
+    f(out.hits, &ScanStaging::hits, n_poses, 4, "hits");
+    f(out.nearest, &ScanStaging::nearest, n_poses, 4, "nearest");
+}
+
 // What a checked call is: its form, its tiles and its pairs
 struct ScanShape {
     int form;        // SCAN_BEAM_LANES or SCAN_POSE_LANES
@@ -58,7 +77,9 @@ inline ScanShape check_scan(const void *accel, const double *origins, size_t n_p
     if (!out) throw std::runtime_error("out is NULL");
     if (!origins) throw std::runtime_error("origins is NULL");
     if (!beams) throw std::runtime_error("beams is NULL");
-    if (!out->range && !out->point && !out->normal && !out->id && !out->hits && !out->nearest) throw std::runtime_error("every plane of out is NULL: at least one output");
+    bool any = false;
+    scan_planes(*out, 0, 0, [&](auto *p, auto, size_t, size_t, const char *) { any = any || p; });
+    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
     const int form = scan_lanes(n_poses, n_beams, lanes);
     if (form < 0) throw std::runtime_error("lanes is " + std::to_string(lanes) + ": 0 (auto), 1 (beam lanes) or 2 (pose lanes)");
     if ((unsigned long long)n_beams > SCAN_MAX_BEAMS) throw std::runtime_error("too many beams in one scan: at most 2^32 - 1");
@@ -69,37 +90,26 @@ inline ScanShape check_scan(const void *accel, const double *origins, size_t n_p
     if (n_poses > SIZE_MAX / n_beams) throw std::runtime_error("n_poses * n_beams does not fit the address space");
     const size_t pairs = n_poses * n_beams;
     (void)scan_bytes(n_poses, 9 * sizeof(double), "frames");
-    (void)scan_bytes(pairs, 4 * sizeof(uint32_t), "a plane of n_poses * n_beams elements"); // id, the widest: range 4, point and normal 12 bytes an element
+    (void)scan_bytes(pairs, 4 * sizeof(uint32_t), "a plane of n_poses * n_beams elements"); // 16 bytes an element, the widest (id): no count or size of scan_planes wraps
     return {form, (uint32_t)tiles, pairs};
 }
-// The device form's alignment rule: the inputs 8 bytes, id 16, the float planes, hits and nearest 4
-inline void check_scan_alignment(const double *origins, const double *frames, const double *beams, const lg_scan_out &out) {
-    const struct { const void *p; size_t align; const char *what; } rule[] = {
-        {origins, 8, "origins"}, {frames, 8, "frames"}, {beams, 8, "beams"}, {out.range, 4, "range"}, {out.point, 4, "point"},
-        {out.normal, 4, "normal"}, {out.id, 16, "id"}, {out.hits, 4, "hits"}, {out.nearest, 4, "nearest"}};
-    for (const auto &r : rule)
-        if (r.p && (uintptr_t)r.p % r.align) throw std::runtime_error(std::string(r.what) + " is not " + std::to_string(r.align) + "-byte aligned");
-}
-
-// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
-struct ScanStaging {
-    std::vector<float> range, point, normal;
-    std::vector<uint32_t> id, hits;
-    std::vector<float> nearest;
-    ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs)
-        : range(out.range ? pairs : 0), point(out.point ? pairs * 3 : 0), normal(out.normal ? pairs * 3 : 0), id(out.id ? pairs * 4 : 0), hits(out.hits ? n_poses : 0),
-          nearest(out.nearest ? n_poses : 0) {}
-};
-template <class T> inline void place_scan_plane(T *to, const std::vector<T> &from) {
-    if (to && !from.empty()) std::memcpy(to, from.data(), from.size() * sizeof(T));
+inline ScanStaging::ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs) {
+    scan_planes(out, n_poses, pairs, [&](auto *p, auto plane, size_t count, size_t, const char *) { if (p) (this->*plane).resize(count); });
 }
 inline void place_scan(const lg_scan_out &out, const ScanStaging &st) {
-    place_scan_plane(out.range, st.range);
-    place_scan_plane(out.point, st.point);
-    place_scan_plane(out.normal, st.normal);
-    place_scan_plane(out.id, st.id);
-    place_scan_plane(out.hits, st.hits);
-    place_scan_plane(out.nearest, st.nearest);
+    scan_planes(out, 0, 0, [&](auto *p, auto plane, size_t, size_t, const char *) {
+        if (p && !(st.*plane).empty()) std::memcpy(p, (st.*plane).data(), (st.*plane).size() * sizeof *p);
+    });
+}
+// The device form's alignment rule: the inputs 8 bytes, the planes theirs (id 16, the others 4)
+inline void check_alignment(const void *p, size_t align, const char *what) {
+    if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
+}
+inline void check_scan_alignment(const double *origins, const double *frames, const double *beams, const lg_scan_out &out) {
+    check_alignment(origins, 8, "origins");
+    check_alignment(frames, 8, "frames");
+    check_alignment(beams, 8, "beams");
+    scan_planes(out, 0, 0, [](auto *p, auto, size_t, size_t align, const char *what) { check_alignment(p, align, what); });
 }
 
 } // namespace lg
