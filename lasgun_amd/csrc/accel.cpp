@@ -18,8 +18,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         // triangles in a mesh (below: on), when LASGUN_PRUNE=1 or lg_accel_set_prune(1) ask for it (rebuild_tables).
         size_t big_mesh_tris = 0;
         for (const auto &m : a->scene->meshes) if (m && m->tri.size() / 3 > big_mesh_tris) big_mesh_tris = m->tri.size() / 3;
-        static const int prune_env = [] { const char *e = std::getenv("LASGUN_PRUNE"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1; }();
-        const bool with_records = a->prune == 1 || (a->prune < 0 && (prune_env == 1 || (prune_env < 0 && big_mesh_tris >= PRUNE_MIN_TRIS)));
+        const bool with_records = a->prune == 1 || (a->prune < 0 && (prune_env() == 1 || (prune_env() < 0 && big_mesh_tris >= PRUNE_MIN_TRIS)));
         flatten_scene(*a->scene, a->flat, with_fast, with_records); // host HLBVH build + flatten (throws on what the reference would panic on)
         const auto t_flat = std::chrono::steady_clock::now();
         use_device(a->device);

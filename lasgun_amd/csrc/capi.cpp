@@ -1,6 +1,7 @@
 // lasgun_amd/csrc/capi.cpp -- the C ABI of include/lasgun_hip.h over the host-side units (internal.h): host objects, captures, switches,
 // measurement and test hooks.  No torch types, no C++ exceptions across the boundary, no CPU render path.
 #include "internal.h"
+#include "choice.h"
 
 // ============================================================================================
 extern "C" {
@@ -25,7 +26,7 @@ size_t lg_tune_export(lg_tune_entry *out, size_t capacity) {
 int lg_tune_import(const lg_tune_entry *entries, size_t count) {
     if (count != 0 && !entries) return fail("lg_tune_import: entries is NULL");
     for (size_t i = 0; i < count; ++i) { // (a choice is checked against the launch when it is used: one the launch cannot take falls back to the rule's)
-        if (entries[i].choice < 0 || entries[i].choice >= 256 || (entries[i].choice & 15) > 2 /* the queue organisation */) return fail("lg_tune_import: entry " + std::to_string(i) + " holds no choice this library makes");
+        if (!choice_well_formed(entries[i].choice)) return fail("lg_tune_import: entry " + std::to_string(i) + " holds no choice this library makes");
     }
     for (size_t i = 0; i < count; ++i) {
         lg::tune::Key k;
@@ -687,7 +688,7 @@ int lg_accel_set_sample_order(const lg_accel *a, int order) { // a supersampled 
     a->sample_order = order;
     return 0;
 }
-int lg_accel_last_organisation(const lg_accel *a) { // what the accel's last launch ran as: 0 megakernel, 1 level by level, 2 queue, + 16 when its tiles were claimed bottom-up; -1 before the first
+int lg_accel_last_organisation(const lg_accel *a) { // what the accel's last launch ran as, encoded (choice.h); -1 before the first
     std::lock_guard<std::mutex> g(a->mtx);
     return a->last_org;
 }

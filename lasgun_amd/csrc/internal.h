@@ -124,6 +124,15 @@ inline int fail(const std::string &msg) {
 void use_device(int dev); // devmem.cpp
 void use_device();
 
+// A switch of the environment that is on unless its value begins with '0' (callers keep the answer in a static: once per process)
+inline bool env_on(const char *name) { const char *e = std::getenv(name); return !(e && e[0] == '0'); }
+// LASGUN_PRUNE=0|1 replaces the scene-dependent DEFAULT of the pruned walk (test suites run whole under either; -1: not set), for the launch
+// (launch.cpp, base_params) and for the records the accel is built with (accel.cpp) alike; lg_accel_set_prune still wins
+inline int prune_env() {
+    static const int v = [] { const char *e = std::getenv("LASGUN_PRUNE"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1; }();
+    return v;
+}
+
 // Device allocations of 1 KiB and more are recycled through a small per-process pool (at most 4 GiB parked per
 // device): capture() builds and drops an accel -- film staging, per-pixel state -- for every frame, like the
 // reference, and hipMalloc / hipFree of those buffers would otherwise cost about a millisecond of each frame.
@@ -223,6 +232,10 @@ template <class T> struct DevBuf {
     }
     ~DevBuf() { release(); }
 };
+// A launch's buffer that is too small is allocated anew -- after a device-wide synchronise: nothing may still use the old one
+template <class T> void grow(DevBuf<T> &buf, size_t need) {
+    if (buf.n < need) { HIP_TRY(hipDeviceSynchronize()); buf.alloc(need); }
+}
 
 // The scene tables of an accel go to the device in ONE allocation and ONE copy: capture() builds an accel for every frame like the
 // reference (lib.rs:64), and two dozen hipMalloc + hipMemcpy pairs of a few kilobytes each were a third of lg_accel_from's millisecond
@@ -431,7 +444,7 @@ struct lg_accel {
     uint32_t queue_blocks = 1;                    // grid of the queue organisation's persistent kernel (256-lane form)
     mutable uint32_t *q_err = nullptr;            // the queue organisation's sticky error word (pinned host memory, g_err_words): taken at its first launch
     mutable int queue = -1;                       // lg_accel_set_streaming(3) forces the queue organisation, (0..2) rule it out; -1 = queue_default
-    mutable int last_org = -1;                    // what the last launch ran as: 0 megakernel, 1 level by level, 2 queue, + 16 with its tiles claimed bottom-up (lg_accel_last_organisation)
+    mutable int last_org = -1;                    // what the last launch ran as, encoded (choice.h); -1 before the first (lg_accel_last_organisation)
     mutable int tile_parts = -1;                  // lg_accel_set_tile_parts: the megakernel hands a tile out whole (1) or in 2 / 4 / 8 parts; -1 = whole unless the measured choice says quarters
     mutable int sample_order = -1;                // lg_accel_set_sample_order: 0 a pixel's samples side by side, 1 one after the other, -1 = side by side (megakernel: rule / measured)
     mutable int query_order = 0;                  // lg_accel_set_query_order: 0 a query's rays are walked as given, 1 sorted on the device by a coherence key (k_sort.hip)
@@ -479,6 +492,9 @@ struct lg_accel {
         g_err_words.give(q_err);
     }
 };
+
+// the scene's tables are resident in LDS for this accel's launches (the reference walk; the kernels' 1024-lane forms)
+inline bool lds_resident(const lg_accel &a) { return !a.fast && a.lds_scene && a.ldss_blocks; }
 
 constexpr size_t MAX_LAUNCH_CTXS = 8;
 constexpr unsigned MAX_WF_BANDS = 4; // bands of a big wavefront launch on internal streams (lg_accel_set_wf_split)

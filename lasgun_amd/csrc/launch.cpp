@@ -2,6 +2,7 @@
 // (level by level, queue, megakernel), the fitted rule and the measured choice between them (tune.cpp does the measuring), and the
 // addressing modes of capture_subset (strided subsets, batches, lattice tiling).
 #include "internal.h"
+#include "choice.h"
 
 // The launch context of `stream` (at most MAX_LAUNCH_CTXS are kept; the least recently used one is recycled after a
 // device-wide synchronise).  Caller holds a.mtx and has made the accel's device current.
@@ -54,17 +55,16 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
     P.default_material = a.flat.default_material;
     P.stack_depth = a.stack_depth;
     {   // LASGUN_ACCEL_LDS=0 (A/B): the accel records from the DAccel table in L2
-        static const bool accel_lds = [] { const char *e = std::getenv("LASGUN_ACCEL_LDS"); return !(e && e[0] == '0'); }();
+        static const bool accel_lds = env_on("LASGUN_ACCEL_LDS");
         P.accel_image = a.accel_image_n16 && accel_lds ? a.accel_image.p : nullptr; P.accel_image_n16 = a.accel_image_n16;
     }
-    {   // LASGUN_PRUNE=0|1 replaces the scene-dependent DEFAULT (test suites run whole under either); lg_accel_set_prune still wins
-        static const int env_default = [] { const char *e = std::getenv("LASGUN_PRUNE"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1; }();
-        const bool dflt = env_default < 0 ? a.prune_default : env_default != 0;
+    {   // LASGUN_PRUNE=0|1 replaces the scene-dependent DEFAULT (prune_env); lg_accel_set_prune still wins
+        const bool dflt = prune_env() < 0 ? a.prune_default : prune_env() != 0;
         P.prune = !a.fast && (a.prune < 0 ? dflt : a.prune != 0) ? 1u : 0u;
     }
     {   // LASGUN_SHADOW_SKIP=0 / lg_accel_set_shadow_skip(0) (A/B, tests): every hit's shadow rays are walked.  The flag's argument (shade.h,
         // light_irrelevant) needs PI * intensity finite for every light; the visibility word holds 32 lights.
-        static const bool skip_env = [] { const char *e = std::getenv("LASGUN_SHADOW_SKIP"); return !(e && e[0] == '0'); }();
+        static const bool skip_env = env_on("LASGUN_SHADOW_SKIP");
         bool ok = skip_env && a.shadow_skip && !a.flat.lights.empty() && a.flat.lights.size() <= 32;
         for (const DLight &L : a.flat.lights)
             for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(PI * L.intensity[k]);
@@ -81,7 +81,7 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
     P.ss_distance = s.camera.ss_distance;
     P.ss_root = s.camera.ss_root;
     {   // LASGUN_SLAB_SIGNS=0: the reference's slab formula as written in every node step (A/B, tests)
-        static const bool signs = [] { const char *e = std::getenv("LASGUN_SLAB_SIGNS"); return !(e && e[0] == '0'); }();
+        static const bool signs = env_on("LASGUN_SLAB_SIGNS");
         P.boxes_finite = a.flat.boxes_finite && signs ? 1u : 0u;
     }
     P.ah_omax = a.flat.ah_omax; P.ah_dmin = a.flat.ah_dmin; P.ah_dmax = a.flat.ah_dmax;
@@ -112,13 +112,25 @@ void set_lds_scene(const lg_accel &a, DParams &P) {
 static uint32_t levels_of(const lg_accel &a, const DParams &P) { return (a.flat.has_specular && P.recursion > 0) ? P.recursion + 1u : 1u; }
 constexpr size_t WF_FULL_MIN_HOST = 48; // == WF_FULL_MIN of k_wavefront.hip
 constexpr uint32_t MEGA_SPLIT = 4;      // the parts a small launch's tiles are handed out in where the measured choice found that faster (enqueue_mega, enqueue_queue)
+// the parts a launch's tiles are handed out in -- lg_accel_set_tile_parts, or the measured choice's candidate (`split`) -- and DParams::split_shift for them
+static std::pair<uint32_t, uint32_t> tile_parts(const lg_accel &a, bool split) {
+    const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split ? MEGA_SPLIT : 1u;
+    return {parts, parts == 8u ? 3u : parts == 4u ? 2u : parts == 2u ? 1u : 0u};
+}
 
-// HIP events around ONE kernel on its launch stream
+// A profiled span of a stream: two HIP events around what is enqueued on it between the span's declaration and end(), which hands the pair
+// over (lg_profile_read* reads and destroys it).  Profiling off: no HIP call.  An enqueue that throws in between: the events are destroyed.
+struct Span {
+    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } e0, e1;
+    hipStream_t s;
+    Span(const lg_accel &a, hipStream_t stream) : s(stream) { if (a.profiling) { HIP_TRY(hipEventCreate(&e0.e)); HIP_TRY(hipEventCreate(&e1.e)); HIP_TRY(hipEventRecord(e0.e, s)); } }
+    void end(std::vector<std::pair<hipEvent_t, hipEvent_t>> &into) { if (e0.e) { HIP_TRY(hipEventRecord(e1.e, s)); into.emplace_back(e0.e, e1.e); e0.e = e1.e = nullptr; } }
+};
+// ... around ONE kernel on its launch stream
 template <class F> static void timed(const lg_accel &a, int kind, hipStream_t s, F &&launch) {
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    if (a.profiling) { HIP_TRY(hipEventCreate(&k0)); HIP_TRY(hipEventCreate(&k1)); HIP_TRY(hipEventRecord(k0, s)); }
+    Span span(a, s);
     HIP_TRY(launch());
-    if (a.profiling) { HIP_TRY(hipEventRecord(k1, s)); a.kind_events[kind].emplace_back(k0, k1); }
+    span.end(a.kind_events[kind]);
 }
 
 // A chunk's level arrays, carved from a launch context's wf_mem
@@ -244,8 +256,8 @@ struct WfChunk {
     size_t hit_cap() const { return (size_t)plan.n0() << (levels - 1); }
     size_t hit_len() const { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); } // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
     void carve(lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk, grown if they have to be
-        if (cx.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); cx.wf_mem.alloc(plan.need()); }
-        if (cx.wf_counters.n < CL * (1 + nlaunch)) { HIP_TRY(hipDeviceSynchronize()); cx.wf_counters.alloc(CL * (1 + nlaunch)); }
+        grow(cx.wf_mem, plan.need());
+        grow(cx.wf_counters, CL * (1 + nlaunch));
         L = plan.carve(cx.wf_mem.p, [&](auto &take) {
             hq = (uint32_t *)take(hit_len() * 4);
             frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
@@ -254,13 +266,13 @@ struct WfChunk {
         counters = cx.wf_counters.p;
     }
     // what every launch of the chunk is told (P.ntiles = level 0's work tiles is the caller's)
-    void params(const lg_accel &a, DParams &P, bool ldss) const {
+    void params(const lg_accel &a, DParams &P) const {
         P.n_items = plan.n0(); // stride of the sample accumulator
         P.accum = L.accum;
         P.wf_levels = levels;
         P.wf_counts = counters;
         P.wf_hit_cap = hit_cap(); P.wf_hit_stride = hit_len(); P.wf_hq = hq; P.frame = frame; P.vis = vis;
-        if (ldss) set_lds_scene(a, P);
+        if (lds_resident(a)) set_lds_scene(a, P);
     }
     // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
     // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms).
@@ -340,9 +352,8 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
         for (unsigned j = 0; j < nstreams; ++j) HIP_TRY(hipStreamWaitEvent(a.aux_streams[j], a.aux_fork, 0));
     }
 
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    const bool ldss = lds_resident(a);
+    Span span(a, stream);
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] wavefront: levels %u, %llu tiles in chunks of %llu on %u stream(s) (%.1f MiB per context), trace grid %u x %u, stack %u, max_blocks %u\n", levels,
                      (unsigned long long)P0.ntiles, chunk_tiles, nstreams ? nstreams : 1u, plan.need() / 1048576.0, ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks),
@@ -359,7 +370,7 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
         const uint32_t pixel_tiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ntiles = pixel_tiles * S; // level 0's work tiles
         P.ss_par = S;
-        K.params(a, P, ldss);
+        K.params(a, P);
 #ifdef LG_STAMPS
         P.stats = a.stats.p;
         P.stamp_counts = reinterpret_cast<unsigned long long *>(a.stats.p + 1);
@@ -374,7 +385,7 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
         HIP_TRY(hipEventRecord(a.aux_done[j], a.aux_streams[j]));
         HIP_TRY(hipStreamWaitEvent(stream, a.aux_done[j], 0));
     }
-    if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
+    span.end(a.events);
 }
 
 // A radiance query (query.cpp, lg_radiance*): li() of `n` caller-supplied rays through the same chain, on the caller's stream alone (no
@@ -396,9 +407,7 @@ static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n
     WfChunk K(plan);
     plan.fit([&] { K.carve(c); });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    Span span(a, stream);
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", label, levels, (unsigned long long)P0.ntiles,
                      chunk_tiles, plan.need() / 1048576.0, perm ? "sorted order" : "as given");
@@ -407,7 +416,7 @@ static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n
         P.tile0 = (uint32_t)t0;
         P.ntiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ss_par = 1u;
-        K.params(a, P, ldss);
+        K.params(a, P);
         const RadianceArgs Q{rays, radiance, perm, (unsigned long long)n, t0 * 64ull};
         if (film) {
             FilmArgs F = *film;
@@ -416,7 +425,7 @@ static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n
         } else K.run(a, P, stream, &Q);
     }
     if (tail) tail();
-    if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
+    span.end(a.events);
 }
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
     enqueue_level0_query(a, rays, n, radiance, nullptr, perm, c, stream, "radiance query");
@@ -432,7 +441,7 @@ void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint3
                       hipStream_t stream) {
     const size_t n = slots * samples;
     if (samples == 1) { enqueue_level0_query(a, rays, n, nullptr, &film, perm, c, stream, "ray film"); return; }
-    if (c.film_li.n < n * 3) { HIP_TRY(hipDeviceSynchronize()); c.film_li.alloc(n * 3); }
+    grow(c.film_li, n * 3);
     const double *li = c.film_li.p;
     enqueue_level0_query(a, rays, n, c.film_li.p, nullptr, perm, c, stream, "ray film", [&] {
         const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)slots + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
@@ -449,7 +458,7 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
     const uint32_t nsamples = P0.ss_root * P0.ss_root;
     // level 0's tiles in parts (enqueue_mega, DParams::split_shift): the children's packets are then as narrow as their parents -- a small
     // launch's recursion chains are walked by four times the waves, 16 lanes each
-    const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split ? MEGA_SPLIT : 1u, split_shift = parts == 8u ? 3u : parts == 4u ? 2u : parts == 2u ? 1u : 0u;
+    const auto [parts, split_shift] = tile_parts(a, split);
     const uint32_t S = (nsamples > 1 && a.sample_order != 1 ? nsamples : 1u) * parts; // samples side by side (enqueue_wavefront) x parts: level-0 tiles per pixel tile
     // (+ 1 byte per level-0 work item, as the organisation was first written: nothing is carved for it.  It stands in for the packets'
     // ready words, which live in wf_counters -- 4 bytes per 64-ray packet of the levels >= 1, 7/8 of a byte per item at four levels.)
@@ -462,21 +471,20 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
     // claim counter (config 4 / 4m / 5: 39.4 / 16.7 / 63.7 against 38.4 / 16.0 / 64.8 ms): which tiles are in flight together does not
     // move these kernels, as round 3 found for the other organisations
     static const bool order_blocks = [] { const char *e = std::getenv("LASGUN_QUEUE_ORDER"); return e && e[0] == '1'; }();
-    const bool ldss = a.lds_scene && a.ldss_blocks;
+    const bool ldss = lds_resident(a); // (never in fast mode: org_possible rules the queue organisation out there, wherever one is picked)
     const uint32_t blocks_cap = ldss ? a.ldss_blocks : a.queue_blocks;
     const unsigned long long threads = (unsigned long long)blocks_cap * (ldss ? 1024ull : 256ull);
     // one word per packet of the levels >= 1, + slack per level
     auto nready = [&] { return (size_t)plan.chunk_tiles * S * ((1ull << levels) - 2ull) + (size_t)levels * QR_SLACK; };
     plan.fit([&] {
-        if (c.wf_mem.n < plan.need()) { HIP_TRY(hipDeviceSynchronize()); c.wf_mem.alloc(plan.need()); }
-        if (c.wf_counters.n < QC_WORDS + nready()) { HIP_TRY(hipDeviceSynchronize()); c.wf_counters.alloc(QC_WORDS + nready()); }
-        if (P0.nlights > 0 && c.stash.n < (size_t)threads * STASH_DOUBLES) { HIP_TRY(hipDeviceSynchronize()); c.stash.alloc((size_t)threads * STASH_DOUBLES); }
+        grow(c.wf_mem, plan.need());
+        grow(c.wf_counters, QC_WORDS + nready());
+        if (P0.nlights > 0) grow(c.stash, (size_t)threads * STASH_DOUBLES);
     });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
     const LevelArrays K = plan.carve(c.wf_mem.p, [](auto &) {});
     if (!a.q_err) a.q_err = g_err_words.take();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (a.profiling) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    Span span(a, stream);
     if (std::getenv("LASGUN_DEBUG"))
         std::fprintf(stderr, "[lasgun] queue: levels %u, %llu tiles in chunks of %llu (%.1f MiB), grid %u x %u, stack %u\n", levels,
                      (unsigned long long)P0.ntiles, chunk_tiles, plan.need() / 1048576.0, blocks_cap, ldss ? 1024u : 256u, a.stack_depth);
@@ -509,11 +517,10 @@ static void enqueue_queue(const lg_accel &a, DParams &P0, lg_accel::LaunchCtx &c
         }
         if (S / parts > 1) resolve_samples(a, P, pixel_tiles, stream);
     }
-    if (a.profiling) { HIP_TRY(hipEventRecord(e1, stream)); a.events.emplace_back(e0, e1); }
+    span.end(a.events);
 }
 
 // ---- which organisation renders a launch -----------------------------------------------------------------
-enum Org : int { ORG_MEGA = 0, ORG_WAVEFRONT = 1, ORG_QUEUE = 2 };
 // what each organisation can take: the queue organisation the reference traversal with <= 32 lights and <= 8 recursion levels, the
 // level-by-level pipeline any scene with <= 32 lights; neither the counting variant
 static bool org_possible(const lg_accel &a, const DParams &P, bool stats, Org org) {
@@ -532,13 +539,13 @@ static bool org_possible(const lg_accel &a, const DParams &P, bool stats, Org or
 static Org org_by_rule(const lg_accel &a, const DParams &P, bool stats) {
     const unsigned long long items = (unsigned long long)P.ntiles * 64ull;
     if (org_possible(a, P, stats, ORG_QUEUE) && a.streaming && a.queue_default && items >= a.queue_min_items) return ORG_QUEUE;
-    const bool lds_resident = !a.fast && a.lds_scene && a.ldss_blocks, specular = a.flat.has_specular && P.recursion > 0;
+    const bool resident = lds_resident(a), specular = a.flat.has_specular && P.recursion > 0;
     // (level 0's work items: with a pixel's samples side by side -- round 5 -- a 9-sample frame is nine times as wide as its film;
     // profiles/r05_ss_par.jsonl: Cornell glass at 9 spp goes level by level at 256^2 and in the megakernel from 512^2, like its
     // one-sample frames of nine times the pixels; simple.rs at 16 spp level by level at every size)
     const unsigned long long work = items * (a.sample_order != 1 ? (unsigned long long)P.ss_root * P.ss_root : 1ull);
-    const bool small_specular = lds_resident && specular && work <= a.specular_small_items;
-    const bool light_scene = lds_resident && !specular && !a.streaming_pays && (P.ss_root == 1u || a.sample_order != 1) && work >= (1ull << 18);
+    const bool small_specular = resident && specular && work <= a.specular_small_items;
+    const bool light_scene = resident && !specular && !a.streaming_pays && (P.ss_root == 1u || a.sample_order != 1) && work >= (1ull << 18);
     if (a.streaming && org_possible(a, P, stats, ORG_WAVEFRONT) && (small_specular || light_scene || (a.streaming_pays && work >= a.streaming_min_items)))
         return ORG_WAVEFRONT;
     return ORG_MEGA;
@@ -558,8 +565,7 @@ static bool mega_par_possible(const DParams &P, bool stats) {
 }
 // the waves of the megakernel's grid (its LDS-resident form: one 1024- or 768-lane workgroup per CU)
 static unsigned long long mega_grid_waves(const lg_accel &a) {
-    const bool lds_form = !a.fast && a.lds_scene && a.ldss_blocks;
-    return lds_form ? (unsigned long long)a.ldss_blocks * (a.mega_narrow ? 12u : 16u) : (unsigned long long)(a.fast ? a.max_blocks_fast : a.max_blocks) * 4ull;
+    return lds_resident(a) ? (unsigned long long)a.ldss_blocks * (a.mega_narrow ? 12u : 16u) : (unsigned long long)(a.fast ? a.max_blocks_fast : a.max_blocks) * 4ull;
 }
 static bool mega_par_by_rule(const lg_accel &a, const DParams &P, bool stats) {
     if (!mega_par_possible(P, stats) || a.sample_order == 1) return false;
@@ -580,41 +586,29 @@ static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, 
     par = par && mega_par_possible(P, stats);
     if (par) {
         const size_t n_items = (size_t)P.ntiles * 64ull * nsamples, need = n_items * 3 * 8;
-        if (c.wf_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); c.wf_mem.alloc(need); }
+        grow(c.wf_mem, need);
         P.accum = reinterpret_cast<double *>(c.wf_mem.p); P.n_items = n_items; P.ss_par = nsamples; P.ntiles *= nsamples;
     }
-    { // tiles handed out in parts: lg_accel_set_tile_parts, or the measured choice's candidate
-        const uint32_t parts = a.tile_parts >= 1 ? (uint32_t)a.tile_parts : split ? MEGA_SPLIT : 1u;
-        if (parts > 1u && !stats && (unsigned long long)P.ntiles * parts < (1ull << 31)) { P.split_shift = parts == 2u ? 1u : parts == 4u ? 2u : 3u; P.ntiles *= parts; }
-    }
+    const auto [parts, shift] = tile_parts(a, split);
+    if (parts > 1u && !stats && (unsigned long long)P.ntiles * parts < (1ull << 31)) { P.split_shift = shift; P.ntiles *= parts; }
     uint32_t cap = a.fast ? a.max_blocks_fast : a.max_blocks;
     uint32_t blocks = (P.ntiles + 3u) / 4u;
     if (blocks > cap) blocks = cap;
     uint32_t maxb = a.max_blocks > a.max_blocks_fast ? a.max_blocks : a.max_blocks_fast;
-    if (!stats && !a.fast && a.lds_scene && a.ldss_blocks) { // scene tables resident in LDS: one 1024-lane workgroup per CU
+    if (!stats && lds_resident(a)) { // scene tables resident in LDS: one 1024-lane workgroup per CU
         set_lds_scene(a, P);
         P.mega_lanes = a.mega_narrow ? 768u : 1024u; // (k_mega.hip: three waves per SIMD and 168 registers where shading weighs more than walking)
         blocks = a.ldss_blocks;
     }
     if (maxb < a.ldss_blocks * 4u) maxb = a.ldss_blocks * 4u; // per-lane slots below: 1024 lanes per LDS-scene workgroup
-    // Whitted frames: one slot per resident lane and recursion level, only for glass / mirror scenes
-    if (a.flat.has_specular && P.recursion > 0) {
-        unsigned long long threads = (unsigned long long)maxb * 256ull;
-        size_t need = (size_t)threads * P.recursion * FRAME_DOUBLES;
-        if (c.frames.n < need) {
-            HIP_TRY(hipDeviceSynchronize()); // (re)allocation: nothing may still use the old buffer
-            c.frames.alloc(need);
-        }
+    const unsigned long long threads = (unsigned long long)maxb * 256ull;
+    if (a.flat.has_specular && P.recursion > 0) { // Whitted frames: one slot per resident lane and recursion level, only for glass / mirror scenes
+        grow(c.frames, (size_t)threads * P.recursion * FRAME_DOUBLES);
         P.frames = c.frames.p;
         P.frame_threads = threads;
     }
     if (P.nlights > 0) { // shading frame parked across the shadow traversals
-        unsigned long long threads = (unsigned long long)maxb * 256ull;
-        size_t need = (size_t)threads * STASH_DOUBLES;
-        if (c.stash.n < need) {
-            HIP_TRY(hipDeviceSynchronize()); // (re)allocation: nothing may still use the old buffer
-            c.stash.alloc(need);
-        }
+        grow(c.stash, (size_t)threads * STASH_DOUBLES);
         P.stash = c.stash.p;
         P.frame_threads = threads;
     }
@@ -623,11 +617,7 @@ static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, 
         HIP_TRY(hipMemsetAsync(a.stats.p, 0, sizeof(DStats), stream));
     }
     HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (a.profiling) {
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, stream));
-    }
+    Span span(a, stream);
 #ifdef LG_QIDLE // diagnostic build: the waves' start / exit times of this launch (k_mega.hip), read by lg_debug_stats
     if (!stats) { P.stats = a.stats.p; HIP_TRY(hipMemsetAsync(a.stats.p, 0, sizeof(DStats), stream)); }
 #endif
@@ -637,17 +627,14 @@ static void enqueue_mega(const lg_accel &a, DParams &P, lg_accel::LaunchCtx &c, 
         R.ntiles = (P.ntiles >> P.split_shift) / nsamples; R.tile_rev = 0u; R.split_shift = 0u;
         HIP_TRY(launch_wf_resolve(R, (uint32_t)(((unsigned long long)R.ntiles * 64ull + 255ull) / 256ull), stream));
     }
-    if (a.profiling) {
-        HIP_TRY(hipEventRecord(e1, stream));
-        a.events.emplace_back(e0, e1);
-    }
+    span.end(a.events);
 }
-static void enqueue_org(const lg_accel &a, DParams P, lg_accel::LaunchCtx &c, Org org, int dir, bool ss_serial, bool split, bool stats, hipStream_t stream) { // (P by value: an organisation fills in its own fields)
+static void enqueue_choice(const lg_accel &a, DParams P, lg_accel::LaunchCtx &c, Choice ch, bool stats, hipStream_t stream) { // (P by value: an organisation fills in its own fields)
     P.tile_counter = c.tile_counter.p;
-    P.tile_rev = org != ORG_WAVEFRONT ? (uint32_t)dir : 0u; // 0 top-down, 1 bottom-up, 2 from the middle outwards (the level-by-level passes are short and alike: one direction)
-    if (org == ORG_QUEUE) enqueue_queue(a, P, c, split, stream);
-    else if (org == ORG_WAVEFRONT) enqueue_wavefront(a, P, c, stream);
-    else enqueue_mega(a, P, c, !ss_serial, split, stats, stream);
+    P.tile_rev = ch.org != ORG_WAVEFRONT ? (uint32_t)ch.dir : 0u; // (the level-by-level passes are short and alike: one direction)
+    if (ch.org == ORG_QUEUE) enqueue_queue(a, P, c, ch.split, stream);
+    else if (ch.org == ORG_WAVEFRONT) enqueue_wavefront(a, P, c, stream);
+    else enqueue_mega(a, P, c, !ch.serial, ch.split, stats, stream);
 }
 
 // The MEASURED choice (round 5; the rule above was a fit to eight scenes and wrong by 6-22 % on the first scene that was not among
@@ -670,17 +657,8 @@ static void enqueue_org(const lg_accel &a, DParams P, lg_accel::LaunchCtx &c, Or
 // lg_tune_export / lg_tune_import / lg_tune_clear read, pin and forget choices.
 namespace {
 using TuneKey = lg::tune::Key;
-constexpr int TUNE_REV = 16;    // a remembered choice: organisation | TUNE_REV when the tiles go bottom-up
-constexpr int TUNE_MID = 64;    //   | TUNE_MID when they go from the middle row outwards
-static int dir_bits(int dir) { return dir == 1 ? TUNE_REV : dir == 2 ? TUNE_MID : 0; }
-static int dir_of(int choice) { return (choice & TUNE_REV) ? 1 : (choice & TUNE_MID) ? 2 : 0; }
-// The direction a launch's tiles are claimed in when nothing is forced or measured: from the middle row outwards.  What a frame shows
-// tends to sit in its middle, and a launch should END on cheap tiles: config 4 in the megakernel 36.2 -> 32.8 ms, 4m 13.1 -> 12.7,
-// simple.rs 0.55 -> 0.53, nothing slower among the configs (profiles/r05_ab_tile_middle.jsonl).
-constexpr int DIR_DEFAULT = 2;
+// the direction a launch's tiles are claimed in when nothing is measured (choice.h: DIR_DEFAULT unless lg_accel_set_tile_order says otherwise)
 static int dir_unmeasured(const lg_accel &a, Org org) { return org == ORG_WAVEFRONT ? 0 : a.tile_order >= 0 ? a.tile_order : DIR_DEFAULT; }
-constexpr int TUNE_SPLIT = 128; //   | TUNE_SPLIT when the megakernel hands a small launch's tiles out in quarters (enqueue_mega)
-constexpr int TUNE_SERIAL = 32; //   | TUNE_SERIAL when the megakernel takes a pixel's samples one after the other (enqueue_mega)
 // LASGUN_AUTOTUNE (tune.cpp: mode()): 0 = never measure (the fitted rule), 1 (default) = measure a kind at the second API CALL that
 // launches it, 2 = at the first.  A program that renders one frame and exits (every example of the reference) gets the rule's choice at no
 // cost -- timing seven candidates three times over costs 30-50 frames' worth; whatever renders a kind twice (an animation, the progressive
@@ -724,74 +702,64 @@ static TuneKey tune_key(const lg_accel &a, const DParams &P) {
 }
 // a remembered choice (measured here, or pinned by lg_tune_import for a kind this build may see differently) that the launch cannot take
 // falls back to the rule's
-static int rule_choice(const lg_accel &a, const DParams &P) {
+static Choice rule_choice(const lg_accel &a, const DParams &P) {
     const Org rule = org_by_rule(a, P, false);
-    return (int)rule | dir_bits(P.ntiles < 2u ? 0 : dir_unmeasured(a, rule)) | (rule == ORG_MEGA && !mega_par_by_rule(a, P, false) ? TUNE_SERIAL : 0);
+    return Choice{rule, P.ntiles < 2u ? 0 : dir_unmeasured(a, rule), rule == ORG_MEGA && !mega_par_by_rule(a, P, false), false};
 }
-static bool choice_possible(const lg_accel &a, const DParams &P, int choice) {
-    const int org = choice & (TUNE_REV - 1);
-    if (org < 0 || org > (int)ORG_QUEUE || !org_possible(a, P, false, (Org)org)) return false;
-    if ((choice & TUNE_SPLIT) && !mega_split_possible(a, P, false)) return false;
-    if (org == (int)ORG_MEGA && !(choice & TUNE_SERIAL) && P.ss_root > 1 && !mega_par_possible(P, false)) return false;
+static bool choice_possible(const lg_accel &a, const DParams &P, Choice ch) {
+    if (ch.org < ORG_MEGA || ch.org > ORG_QUEUE || !org_possible(a, P, false, ch.org)) return false;
+    if (ch.split && !mega_split_possible(a, P, false)) return false;
+    if (ch.org == ORG_MEGA && !ch.serial && P.ss_root > 1 && !mega_par_possible(P, false)) return false;
     return true;
 }
-static int tuned_choice(const lg_accel &a, const DParams &P, lg_accel::LaunchCtx &c, hipStream_t stream) {
+static Choice tuned_choice(const lg_accel &a, const DParams &P, lg_accel::LaunchCtx &c, hipStream_t stream) {
     const Org rule = org_by_rule(a, P, false);
     const TuneKey key = tune_key(a, P);
     int known;
-    if (lg::tune::lookup(key, &known)) return choice_possible(a, P, known) ? known : rule_choice(a, P);
+    if (lg::tune::lookup(key, &known)) return choice_possible(a, P, decode(known)) ? decode(known) : rule_choice(a, P);
     if (lg::tune::mode() == 1 && lg::tune::first_call_of_kind(key, g_call_serial.load())) return rule_choice(a, P); // the first call that launches the kind: the rule's choice, at no cost
     {   // a stream that is being captured into a graph cannot be waited on: no race there (the next plain launch of the kind measures)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();
         else if (cs != hipStreamCaptureStatusNone) return rule_choice(a, P);
     }
-    // candidates: [organisation][samples side by side, one after the other (megakernel only)][top-down, bottom-up, middle-out]
-    constexpr int NC = 20, K_SPLIT = 18, K_QSPLIT = 19; // (+ the megakernel / the queue organisation with their tiles in quarters: sample order by the rule, middle-out)
-    lg::tune::Candidate cand[NC];
+    // the candidates (choice.h) and which of them can take this launch
+    Choice slot[RACE_SLOTS];
+    race_slots(!mega_par_by_rule(a, P, false), slot);
+    lg::tune::Candidate cand[RACE_SLOTS];
     const unsigned long long items = (unsigned long long)P.ntiles * 64ull;
-    for (int k = 0; k < NC; ++k) {
-        if (k == K_SPLIT) {
-            cand[k].choice = (int)ORG_MEGA | dir_bits(DIR_DEFAULT) | (!mega_par_by_rule(a, P, false) ? TUNE_SERIAL : 0) | TUNE_SPLIT;
-            cand[k].in_race = mega_split_possible(a, P, false) && a.tile_parts < 0 && (a.tile_order < 0 || a.tile_order == DIR_DEFAULT);
-            continue;
-        }
-        if (k == K_QSPLIT) {
-            cand[k].choice = (int)ORG_QUEUE | dir_bits(DIR_DEFAULT) | TUNE_SPLIT;
-            cand[k].in_race = org_possible(a, P, false, ORG_QUEUE) && items >= 4096ull && mega_split_possible(a, P, false) && a.tile_parts < 0 && (a.tile_order < 0 || a.tile_order == DIR_DEFAULT);
-            continue;
-        }
-        const int org = k / 6, ser = (k / 3) & 1, dir = k % 3;
-        cand[k].choice = org | dir_bits(dir) | (ser ? TUNE_SERIAL : 0);
-        cand[k].in_race = org_possible(a, P, false, (Org)org) &&
-                     (ser ? org == ORG_MEGA : (org != ORG_MEGA || mega_par_possible(P, false))) &&
-                     !(org == ORG_MEGA && mega_par_possible(P, false) && a.sample_order >= 0 && ser != a.sample_order) && // (lg_accel_set_sample_order) // (one form of the megakernel for a frame of one sample per pixel: the serial one)
-                     !(org == ORG_QUEUE && items < 4096ull && rule != ORG_QUEUE) && // (a persistent scheduler for a handful of tiles: never ahead)
-                     !(dir != 0 && (org == ORG_WAVEFRONT || P.ntiles < 2u)) &&      // (one direction for the level-by-level passes and for a single tile)
-                     (a.tile_order < 0 || org == ORG_WAVEFRONT || dir == a.tile_order); // (lg_accel_set_tile_order: only the organisations race)
+    const bool par = mega_par_possible(P, false);
+    for (int k = 0; k < RACE_SLOTS; ++k) {
+        const Choice s = slot[k];
+        cand[k].choice = encode(s);
+        // (tiles in parts: a small launch with nothing forced by lg_accel_set_tile_parts or lg_accel_set_tile_order; the queue organisation where it is possible, from 4096 pixels)
+        cand[k].in_race = s.split
+            ? (s.org == ORG_MEGA || (org_possible(a, P, false, ORG_QUEUE) && items >= 4096ull)) && mega_split_possible(a, P, false) && a.tile_parts < 0 && (a.tile_order < 0 || a.tile_order == DIR_DEFAULT)
+            : org_possible(a, P, false, s.org) &&
+              (s.serial ? s.org == ORG_MEGA : (s.org != ORG_MEGA || par)) &&
+              !(s.org == ORG_MEGA && par && a.sample_order >= 0 && (int)s.serial != a.sample_order) && // (lg_accel_set_sample_order) // (one form of the megakernel for a frame of one sample per pixel: the serial one)
+              !(s.org == ORG_QUEUE && items < 4096ull && rule != ORG_QUEUE) && // (a persistent scheduler for a handful of tiles: never ahead)
+              !(s.dir != 0 && (s.org == ORG_WAVEFRONT || P.ntiles < 2u)) &&      // (one direction for the level-by-level passes and for a single tile)
+              (a.tile_order < 0 || s.org == ORG_WAVEFRONT || s.dir == a.tile_order); // (lg_accel_set_tile_order: only the organisations race)
     }
-    const int rule_k = (int)rule * 6 + (rule == ORG_MEGA && !mega_par_by_rule(a, P, false) ? 3 : 0) + (P.ntiles < 2u ? 0 : dir_unmeasured(a, rule));
-    float best_ms[NC];
+    float best_ms[RACE_SLOTS];
     for (float &m : best_ms) m = INFINITY;
-    const bool was_profiling = a.profiling;
+    struct Restore { const lg_accel &a; bool was; ~Restore() { a.profiling = was; } } restore{a, a.profiling};
     a.profiling = false; // (the measurement's launches are not the caller's: lg_profile_read must not count them)
-    struct Restore { const lg_accel &a; bool was; ~Restore() { a.profiling = was; } } restore{a, was_profiling};
     // (LASGUN_TUNE_FAIL=<organisation 0..2>: test hook -- every candidate of that organisation throws in the race, as one whose buffers do not fit would)
     static const int fail_org = [] { const char *e = std::getenv("LASGUN_TUNE_FAIL"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : -1; }();
-    const int choice = lg::tune::race(key, cand, NC, rule_k, stream, [&](int k) {
-        if (fail_org >= 0 && (cand[k].choice & (TUNE_REV - 1)) == fail_org) throw Error("LASGUN_TUNE_FAIL: injected failure of a candidate");
-        if (k == K_SPLIT) enqueue_org(a, P, c, ORG_MEGA, DIR_DEFAULT, !mega_par_by_rule(a, P, false), true, false, stream);
-        else if (k == K_QSPLIT) enqueue_org(a, P, c, ORG_QUEUE, DIR_DEFAULT, false, true, false, stream);
-        else enqueue_org(a, P, c, (Org)(k / 6), k % 3, ((k / 3) & 1) != 0, false, false, stream);
+    const int raced = lg::tune::race(key, cand, RACE_SLOTS, slot_of(slot, rule_choice(a, P)), stream, [&](int k) {
+        if ((int)slot[k].org == fail_org) throw Error("LASGUN_TUNE_FAIL: injected failure of a candidate");
+        enqueue_choice(a, P, c, slot[k], false, stream);
     }, best_ms);
     check_queue_error(a);
     if (std::getenv("LASGUN_DEBUG")) {
         std::fprintf(stderr, "[lasgun] measured for %llu pixels (top-down / bottom-up / middle-out): megakernel %.3f / %.3f / %.3f ms (samples in a row: %.3f / %.3f / %.3f), level by level %.3f ms, queue %.3f / %.3f / %.3f ms -> choice %d (rule: %d)\n",
                      items, best_ms[0], best_ms[1], best_ms[2], best_ms[3], best_ms[4], best_ms[5], best_ms[6], best_ms[12], best_ms[13], best_ms[14], // (one sample per pixel: "in a row" is the megakernel)
-                     choice, (int)rule);
-        if (std::isfinite(best_ms[K_SPLIT]) || std::isfinite(best_ms[K_QSPLIT])) std::fprintf(stderr, "[lasgun]   (tiles in quarters: megakernel %.3f ms, queue %.3f ms)\n", best_ms[K_SPLIT], best_ms[K_QSPLIT]);
+                     raced, (int)rule);
+        if (std::isfinite(best_ms[SLOT_MEGA_PARTS]) || std::isfinite(best_ms[SLOT_QUEUE_PARTS])) std::fprintf(stderr, "[lasgun]   (tiles in quarters: megakernel %.3f ms, queue %.3f ms)\n", best_ms[SLOT_MEGA_PARTS], best_ms[SLOT_QUEUE_PARTS]);
     }
-    return choice_possible(a, P, choice) ? choice : rule_choice(a, P);
+    return choice_possible(a, P, decode(raced)) ? decode(raced) : rule_choice(a, P);
 }
 
 // Enqueue one render on `stream`.  Caller holds a.mtx.
@@ -799,28 +767,20 @@ void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream) {
     if (P.ntiles == 0) return;
     check_queue_error(a); // (an earlier launch on a caller's stream that stalled: reported here at the latest)
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    Org org;
-    int dir = -1; // lg_accel_set_tile_order; -1: from the middle outwards unless measured otherwise (dir_unmeasured)
-    bool ss_serial = !mega_par_by_rule(a, P, stats); // the megakernel's samples: by the rule unless measured
-    bool split = false;                              // its tiles in quarters: only as measured
-    if (stats) { org = ORG_MEGA; dir = 0; }                                                      // the counting variant
-    else if (a.queue == 1) org = org_possible(a, P, stats, ORG_QUEUE) ? ORG_QUEUE : org_by_rule(a, P, stats); // lg_accel_set_streaming(3)
-    else if (!a.streaming) org = ORG_MEGA;                                                       // lg_accel_set_streaming(0)
-    else if (a.streaming_forced) org = org_possible(a, P, stats, ORG_WAVEFRONT) ? ORG_WAVEFRONT : ORG_MEGA; // lg_accel_set_streaming(2)
-    else if (a.queue == 0 || !autotune_enabled()) {                                              // the fitted rule (queue ruled out by set_streaming(0 .. 2))
-        org = org_by_rule(a, P, stats);
-        if (a.queue == 0 && org == ORG_QUEUE) org = ORG_MEGA;
-    } else {
-        const int choice = tuned_choice(a, P, c, stream);
-        org = (Org)(choice & (TUNE_REV - 1));
-        dir = dir_of(choice);
-        ss_serial = (choice & TUNE_SERIAL) != 0;
-        split = (choice & TUNE_SPLIT) != 0;
-    }
-    if (dir < 0) dir = P.ntiles < 2u ? 0 : dir_unmeasured(a, org);
-    if (org == ORG_WAVEFRONT) dir = 0;
-    a.last_org = (int)org | dir_bits(dir) | (org == ORG_MEGA && ss_serial && P.ss_root > 1 ? TUNE_SERIAL : 0) | (org != ORG_WAVEFRONT && (split || a.tile_parts > 1) ? TUNE_SPLIT : 0);
-    enqueue_org(a, P, c, org, dir, ss_serial, split, stats, stream);
+    Choice ch{ORG_MEGA, -1, !mega_par_by_rule(a, P, stats), false}; // (dir -1: dir_unmeasured, below; the megakernel's samples by the rule; tiles in parts only as measured)
+    if (stats) ch.dir = 0;                                                                          // the counting variant
+    else if (a.queue == 1) ch.org = org_possible(a, P, stats, ORG_QUEUE) ? ORG_QUEUE : org_by_rule(a, P, stats); // lg_accel_set_streaming(3)
+    else if (!a.streaming) ch.org = ORG_MEGA;                                                       // lg_accel_set_streaming(0)
+    else if (a.streaming_forced) ch.org = org_possible(a, P, stats, ORG_WAVEFRONT) ? ORG_WAVEFRONT : ORG_MEGA; // lg_accel_set_streaming(2)
+    else if (a.queue == 0 || !autotune_enabled()) {                                                 // the fitted rule (queue ruled out by set_streaming(0 .. 2))
+        ch.org = org_by_rule(a, P, stats);
+        if (a.queue == 0 && ch.org == ORG_QUEUE) ch.org = ORG_MEGA;
+    } else ch = tuned_choice(a, P, c, stream);
+    if (ch.dir < 0) ch.dir = P.ntiles < 2u ? 0 : dir_unmeasured(a, ch.org);
+    if (ch.org == ORG_WAVEFRONT) ch.dir = 0;
+    // (what is reported: samples in a row only where the megakernel has several; parts also where lg_accel_set_tile_parts forces them, never for level by level)
+    a.last_org = encode(Choice{ch.org, ch.dir, ch.org == ORG_MEGA && ch.serial && P.ss_root > 1, ch.org != ORG_WAVEFRONT && (ch.split || a.tile_parts > 1)});
+    enqueue_choice(a, P, c, ch, stats, stream);
 }
 
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
@@ -860,6 +820,8 @@ static const DRowTab *lattice_rows(const lg_accel &a, hipStream_t stream, uint32
     r->w = w; r->h = h; r->n = n; r->last_use = ++c.rowtab_clock;
     return r->buf.p;
 }
+// LASGUN_SUBSET_LATTICE=0 (A/B): a strided subset and a batch of them are never tiled by lattice column (set_subset, set_subsets)
+static bool subset_lattice() { static const bool on = env_on("LASGUN_SUBSET_LATTICE"); return on; }
 // the pixels of the subset {k + i*n} of an `area`-pixel film (k < area, n > 0), without forming area - k + n - 1 (which wraps for n near SIZE_MAX)
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n) { return k < area ? 1ull + (area - 1ull - k) / n : 0ull; }
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h) {
@@ -869,9 +831,8 @@ void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, siz
     P.ntiles = (uint32_t)((P.sub_count + 63ull) / 64ull);
     // The subset tile by lattice column (mode 4, shade.h: 64 rows x <= n pixels per tile instead of 64 consecutive i) where that is the denser
     // window: a period shorter than the film's width and longer than a tile's 64 pixels in a row would be.  LASGUN_SUBSET_LATTICE=0: never (A/B).
-    static const bool lattice = [] { const char *e = std::getenv("LASGUN_SUBSET_LATTICE"); return !(e && e[0] == '0'); }();
     const unsigned long long cols = (w + n - 1) / n, tiles4 = ((unsigned long long)h + 63ull) / 64ull * cols;
-    if (lattice && P.sub_count != 0 && n >= 8 && n <= w && h >= 16 && area < (1ull << 32) && tiles4 < (1ull << 31) && tiles4 <= 2ull * P.ntiles + 8ull) {
+    if (subset_lattice() && P.sub_count != 0 && n >= 8 && n <= w && h >= 16 && area < (1ull << 32) && tiles4 < (1ull << 31) && tiles4 <= 2ull * P.ntiles + 8ull) {
         P.mode = 4; P.sub_cols = (uint32_t)cols; P.sub_rows = 64u; P.ntiles = (uint32_t)tiles4;
         P.sub_kk = (uint32_t)(k % n); P.sub_kdiv = (uint32_t)(k / n);
         P.sub_rowtab = lattice_rows(a, stream, w, h, n);
@@ -918,10 +879,9 @@ void set_subsets(const lg_accel &a, DParams &P, const SubsetBatch &b, hipStream_
     P.ntiles = (uint32_t)((b.items + 63ull) / 64ull);
     // the batch tile by lattice column (mode 5, shade.h: 64 / m rows x <= n pixels per tile instead of 64 consecutive work items -- 64 / m
     // periods of one row) where that wastes few lanes; LASGUN_SUBSET_LATTICE=0: never (A/B)
-    static const bool lattice = [] { const char *e = std::getenv("LASGUN_SUBSET_LATTICE"); return !(e && e[0] == '0'); }();
     const unsigned long long m = b.ks.size(), rows = m != 0 && m <= 64 ? 64ull / m : 0ull, cols = (P.w + b.n - 1) / b.n;
     const unsigned long long tiles5 = rows ? ((unsigned long long)P.h + rows - 1ull) / rows * cols : ~0ull;
-    if (lattice && rows >= 2 && b.n >= 8 && b.n <= P.w && (unsigned long long)P.w * P.h < (1ull << 32) && tiles5 < (1ull << 31) && tiles5 * 3ull <= (unsigned long long)P.ntiles * 4ull + 24ull) {
+    if (subset_lattice() && rows >= 2 && b.n >= 8 && b.n <= P.w && (unsigned long long)P.w * P.h < (1ull << 32) && tiles5 < (1ull << 31) && tiles5 * 3ull <= (unsigned long long)P.ntiles * 4ull + 24ull) {
         P.mode = 5; P.sub_cols = (uint32_t)cols; P.sub_rows = (uint32_t)rows; P.ntiles = (uint32_t)tiles5;
         P.sub_rowtab = lattice_rows(a, stream, P.w, P.h, b.n);
     }

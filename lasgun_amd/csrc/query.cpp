@@ -66,7 +66,7 @@ static KeyBounds world_key_bounds(const lg_accel &a) {
 static const uint32_t *enqueue_query_order(const lg_accel &a, lg_accel::LaunchCtx &c, const double *rays, size_t n, uint32_t *keys_out, uint32_t *perm_out,
                                            hipStream_t stream) {
     const size_t need = sort_scratch_bytes(n);
-    if (c.sort_mem.n < need) { HIP_TRY(hipDeviceSynchronize()); c.sort_mem.alloc(need); }
+    grow(c.sort_mem, need);
     const uint32_t *perm = nullptr;
     HIP_TRY(launch_query_order(rays, n, world_key_bounds(a), c.sort_mem.p, keys_out, perm_out, &perm, a.cus * 8u, stream));
     return perm;

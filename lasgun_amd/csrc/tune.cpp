@@ -1,6 +1,7 @@
 // lasgun_amd/csrc/tune.cpp -- see tune.h.  (Round 6: moved out of capi.cpp; the race no longer fails the caller's render when a
 // candidate cannot run, counts API calls instead of launches, and its table can be exported, imported and cleared.)
 #include "tune.h"
+#include "choice.h"
 
 #include <algorithm>
 #include <cmath>
@@ -48,7 +49,7 @@ void load_file_locked() { // caller holds g_mtx
             ok = std::sscanf(p, "%llx%n", &v, &n) == 1;
             k.v[i] = v; p += ok ? n : 0;
         }
-        ok = ok && std::sscanf(p, "%d%n", &choice, &used) == 1 && choice >= 0 && choice < 256 && (choice & 15) <= 2;
+        ok = ok && std::sscanf(p, "%d%n", &choice, &used) == 1 && choice_well_formed(choice);
         if (ok) g_tuned.emplace(k, choice); // (a choice made in this process already wins)
     }
     std::fclose(f);

@@ -862,6 +862,38 @@ def test_the_table_of_measured_choices_can_be_exported_pinned_and_cleared():
     G.tune_clear()
 
 
+PINNED_CHOICES = [(0, "megakernel"), (16, "megakernel, bottom-up"), (64, "megakernel, middle-out"), (80, "megakernel, bottom-up"),
+                  (32, "megakernel, samples in a row"), (96, "megakernel, middle-out, samples in a row"), (192, "megakernel, middle-out, tiles in parts"),
+                  (1, "wavefront"), (17, "wavefront"), (2, "queue"), (18, "queue, bottom-up"), (194, "queue, middle-out, tiles in parts")]
+
+
+def test_a_pinned_choice_runs_as_its_bits_say():
+    """Every bit of a remembered choice (csrc/choice.h: organisation, + 16 bottom-up, + 64 middle-out, + 32 samples in a row, + 128 tiles in
+    parts), pinned by lg_tune_import and run: the oracle's bytes and exactly what lg_accel_last_organisation reports for it.  16 + 64 is
+    bottom-up; level by level has one direction and no parts.  Cornell glass at four samples per pixel on a 64 x 64 film: 64 tiles (parts are
+    possible), four samples that fit side by side (so "in a row" is a choice)."""
+    w, h = 64, 64
+    o = oracle()
+    build = lambda api: S.cornell_scene(api, "glass", supersampling=2)
+    want = o.render(build(o), (w, h)).pixels()
+    G.tune_clear()
+    acc = G.Accel(build(G))
+    for _ in range(3):  # (measured at the kind's first or second call, LASGUN_AUTOTUNE=2 or 1)
+        film = G.Film(w, h)
+        G.capture_subset(0, 1, acc, film)
+        assert np.array_equal(film.pixels(), want)
+    table = G.tune_export()
+    assert len(table) >= 1
+    for choice, ran_as in PINNED_CHOICES:
+        G.tune_clear()
+        G.tune_import([(k, choice) for k, _ in table])
+        film = G.Film(w, h)
+        G.capture_subset(0, 1, acc, film)
+        assert np.array_equal(film.pixels(), want), choice
+        assert G.last_organisation(acc) == ran_as, (choice, ran_as, G.last_organisation(acc))
+    G.tune_clear()
+
+
 TUNE_FAIL_CHILD = r"""
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)

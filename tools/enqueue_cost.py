@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host time to ENQUEUE a frame (the library's launches, memsets and bookkeeping, no synchronisation) beside the frame's device time:
-python tools/enqueue_cost.py [glass|plastic|readme|spheres] [size] -- is a small frame bound by the host's launch calls?"""
+python tools/enqueue_cost.py [glass|plastic|readme|spheres] [size] [frames] -- is a small frame bound by the host's launch calls?"""
 import os
 import sys
 import time
@@ -12,6 +12,7 @@ G = la.api; S = la.scenes
 G.set_device(0)
 which = sys.argv[1] if len(sys.argv) > 1 else "glass"
 size = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+n = int(sys.argv[3]) if len(sys.argv) > 3 else 50  # timed frames per organisation
 scene = S.readme_scene(G) if which == "readme" else S.spheres_scene(G) if which == "spheres" else S.cornell_scene(G, which)
 for org, st in (("default", 1), ("megakernel", 0), ("wavefront", 2), ("queue", 3)):
     acc = G.Accel(scene)
@@ -21,7 +22,6 @@ for org, st in (("default", 1), ("megakernel", 0), ("wavefront", 2), ("queue", 3
     for _ in range(5):
         G.capture_rows_device(acc, size, size, 0, size, film.data_ptr(), row0=0, stream=stream)
     torch.cuda.synchronize()
-    n = 50
     t0 = time.perf_counter()
     for _ in range(n):
         G.capture_rows_device(acc, size, size, 0, size, film.data_ptr(), row0=0, stream=stream)
