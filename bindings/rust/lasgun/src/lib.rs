@@ -233,6 +233,10 @@ pub use sys::lg_scan_out as ScanOut;
 /// The work item a range scan of these counts would use (`lg_range_scan_lanes`): 1 beam lanes, 2 pose lanes; `lanes` 0 asks for the
 /// stated default (pose lanes iff n_poses >= n_beams); -1 for a bad `lanes`.  No device is touched.
 pub fn range_scan_lanes(n_poses: usize, n_beams: usize, lanes: i32) -> i32 { unsafe { sys::lg_range_scan_lanes(n_poses, n_beams, lanes) } }
+pub use sys::lg_gather_out as GatherOut;
+/// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
+/// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
+pub fn radiance_gather_lanes(n_poses: usize, n_dirs: usize, lanes: i32) -> i32 { unsafe { sys::lg_radiance_gather_lanes(n_poses, n_dirs, lanes) } }
 
 /// The rays of a lens over a width x height film, row-major pixels (or over the pixel slots `offsets` names), samples_root^2 per slot in
 /// idx = i*samples_root + j order: the layout `Accel::capture_rays` takes.  Generated on the current device.
@@ -395,6 +399,43 @@ impl<'s> Accel<'s> {
         let rc = unsafe { sys::lg_radiance(self.ptr, rays.as_ptr() as *const f64, rays.len(), out.as_mut_ptr() as *mut f64) };
         if rc != 0 { panic!("lasgun: {}", last_error()) }
         out
+    }
+    /// Radiance gather (`lg_radiance_gather`): li() along `dirs[k]` from `origins[i]`, what `radiance` returns for that ray, at
+    /// `i * dirs.len() + k` of `radiance`, and / or reduced per pose into `sums`: `sums[i * n_weights + c]` = the sum over k, in order from
+    /// +0.0, of radiance(i, k) * `weights[k * n_weights + c]` (one product, one sum a step).  `None` = not asked for; not both.  `weights`:
+    /// `dirs.len() * n_weights` doubles, k-major, looked at only with `sums`.  `frames`: one row-major 3 x 3 matrix per pose,
+    /// `d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z`; `None`: the directions are used bit for bit.  `lanes`: 0 auto, 1 direction lanes, 2 pose lanes.
+    #[allow(clippy::too_many_arguments)]
+    pub fn radiance_gather(&self, origins: &[[f64; 3]], frames: Option<&[[f64; 9]]>, dirs: &[[f64; 3]], weights: Option<&[f64]>, n_weights: usize, lanes: i32,
+                           radiance: Option<&mut [[f64; 3]]>, sums: Option<&mut [[f64; 3]]>) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_gather_out>() == 16);
+        let pairs = origins.len().checked_mul(dirs.len()).expect("radiance_gather: origins.len() * dirs.len() overflows usize");
+        assert!(frames.map_or(true, |m| m.len() == origins.len()), "radiance_gather: one frame per pose");
+        assert!(radiance.as_ref().map_or(true, |p| p.len() == pairs), "radiance_gather: radiance of origins.len() * dirs.len() elements");
+        if let Some(s) = sums.as_ref() {
+            assert!(s.len() == origins.len() * n_weights && weights.map_or(false, |w| w.len() == dirs.len() * n_weights),
+                    "radiance_gather: sums of origins.len() * n_weights elements, weights of dirs.len() * n_weights");
+        }
+        let out = sys::lg_gather_out {
+            radiance: radiance.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            sums: sums.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+        };
+        let rc = unsafe {
+            sys::lg_radiance_gather(self.ptr, origins.as_ptr() as *const f64, frames.map_or(std::ptr::null(), |m| m.as_ptr() as *const f64), origins.len(),
+                                    dirs.as_ptr() as *const f64, dirs.len(), weights.map_or(std::ptr::null(), |w| w.as_ptr()), n_weights, lanes, &out)
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `radiance_gather` for tables in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `radiance_gather` states (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn radiance_gather_device(&self, dev_origins: *const f64, dev_frames: *const f64, n_poses: usize, dev_dirs: *const f64, n_dirs: usize,
+                                         dev_weights: *const f64, n_weights: usize, lanes: i32, dev_out: &sys::lg_gather_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_radiance_gather_device(self.ptr, dev_origins, dev_frames, n_poses, dev_dirs, n_dirs, dev_weights, n_weights, lanes, dev_out, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
     }
     /// `radiance` for rays in device memory (6 doubles each), enqueued on a HIP stream: 3 n doubles at `dev_radiance`
     ///

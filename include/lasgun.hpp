@@ -158,7 +158,7 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     Accel(Accel &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
     ~Accel() { if (h_) lg_accel_free(h_); }
     const lg_accel *handle() const { return h_; }
-    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_open_directions / lg_range_scan / lg_radiance): rays are origin xyz, direction xyz
+    // ray queries (lasgun_hip.h, lg_intersect / lg_occluded / lg_visibility / lg_open_directions / lg_range_scan / lg_radiance / lg_radiance_gather): rays are origin xyz, direction xyz
     std::vector<lg_hit> intersect(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<lg_hit> hits(rays.size());
         if (lg_intersect(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), hits.data())) throw Error(lg_last_error());
@@ -236,6 +236,32 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
         std::vector<std::array<double, 3>> out(rays.size());
         if (lg_radiance(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
         return out;
+    }
+    // radiance gather (lg_radiance_gather): li() along dirs[k] from origins[i], what radiance() returns for that ray, at i * dirs.size() + k of
+    // *out.radiance, and / or reduced per pose into *out.sums: sums[i * n_weights + c] = the sum over k, in order from +0.0, of
+    // radiance(i, k) * weights[k * n_weights + c] (one product, one sum a step).  A null member is not asked for; not both.  weights:
+    // dirs.size() * n_weights doubles, k-major; looked at only with sums.  frames: one row-major 3 x 3 matrix per pose --
+    // d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z --, or null: the directions are used bit for bit.  lanes: 0 auto, 1 direction lanes, 2 pose lanes
+    struct Gather {
+        std::vector<std::array<double, 3>> *radiance = nullptr;  // [poses*dirs]
+        std::vector<std::array<double, 3>> *sums = nullptr;      // [poses*n_weights]
+    };
+    void radiance_gather(const std::vector<std::array<double, 3>> &origins, const std::vector<std::array<double, 3>> &dirs, const Gather &out,
+                         const std::vector<double> *weights = nullptr, size_t n_weights = 0, const std::vector<std::array<double, 9>> *frames = nullptr,
+                         int lanes = 0) const {
+        static_assert(sizeof(lg_gather_out) == 16, "lg_gather_out: two pointers");
+        if (frames && frames->size() != origins.size()) throw Error("radiance_gather: one frame per pose");
+        if (out.sums && (!weights || weights->size() != dirs.size() * n_weights)) throw Error("radiance_gather: dirs.size() * n_weights weights");
+        lg_gather_out o{};
+        if (out.radiance) { out.radiance->assign(origins.size() * dirs.size(), {0.0, 0.0, 0.0}); o.radiance = out.radiance->empty() ? nullptr : (*out.radiance)[0].data(); }
+        if (out.sums) { out.sums->assign(origins.size() * n_weights, {0.0, 0.0, 0.0}); o.sums = out.sums->empty() ? nullptr : (*out.sums)[0].data(); }
+        if (lg_radiance_gather(h_, origins.empty() ? nullptr : origins[0].data(), frames && !frames->empty() ? (*frames)[0].data() : nullptr, origins.size(),
+                               dirs.empty() ? nullptr : dirs[0].data(), dirs.size(), weights && !weights->empty() ? weights->data() : nullptr, n_weights, lanes, &o))
+            throw Error(lg_last_error());
+    }
+    void radiance_gather_device(const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_dirs, size_t n_dirs, const double *dev_weights,
+                                size_t n_weights, int lanes, const lg_gather_out &dev_out, void *hip_stream) const {
+        if (lg_radiance_gather_device(h_, dev_origins, dev_frames, n_poses, dev_dirs, n_dirs, dev_weights, n_weights, lanes, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
     // a film from the caller's rays (lg_capture_rays): pixel slot g's rays are [g*samples, (g+1)*samples), summed in that order, scaled by
     // 1 / samples, quantised and written at film offset offsets[g] (y*width + x), or g without offsets; *rgb (if asked for): width*height

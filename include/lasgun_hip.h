@@ -549,6 +549,60 @@ int lg_range_scan_lanes(size_t n_poses, size_t n_beams, int lanes);        /* th
  * synchronise.  One stream at a time per accel. */
 int lg_radiance(const lg_accel *, const double *rays, size_t n, double *radiance);                         /* host arrays; synchronous */
 int lg_radiance_device(const lg_accel *, const double *dev_rays, size_t n, double *dev_radiance, void *hip_stream);
+/* Radiance gathers: li() along n_dirs shared directions from each of n_poses poses, reduced per pose by the caller's weights -- an
+ * irradiance volume of SH probes, a cube map per probe, a lightmap final gather from surface points -- without the caller writing
+ * n_poses * n_dirs rays of 48 bytes and reading back 24 bytes of radiance for each: n_poses + n_dirs vectors describe all the rays, and
+ * n_weights RGB sums a pose come back.  The radiance half of what lg_open_directions is for occlusion.  An EXTRA; no counterpart in the
+ * reference.
+ * Inputs: origins is n_poses x 3 doubles; frames is n_poses x 9 doubles, a row-major 3 x 3 matrix M per pose, and MAY BE NULL; dirs is
+ * n_dirs x 3 doubles, shared by all poses; weights is n_dirs x n_weights doubles, k-major: W[k*n_weights + c].  Any f64 is accepted as it
+ * is, NaN and infinities included.
+ * Ray (i, k): exactly the range scans' rule.  The origin is origins[i] bit for bit.  With frames == NULL the direction is dirs[k] bit for
+ * bit.  Otherwise, with M = frames + 9*i and b = dirs[k], d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z for c = 0, 1, 2, in f64, in this
+ * order, with no contraction (so an identity frame is NOT the same as NULL for -0.0, infinite and NaN components, as for lg_range_scan).
+ * The direction is not normalised.
+ * Radiance: L(i,k) is what lg_radiance returns for that ray, bit for bit: (0 + li) * 1.0, in the accel's traversal mode exactly as for
+ * the other queries; no switch of its own.  lg_accel_set_query_order plays no part: there is no ray array to sort.  lg_radiance's
+ * refusals hold: a scene with more than 32 lights, or a recursion depth of 20 or more, is an error before any launch.
+ * Outputs (lg_gather_out), both WRITTEN, NOT ACCUMULATED: radiance[i*n_dirs + k] = L(i,k), three doubles.
+ * sums[(i*n_weights + c)*3 + ch]: acc = +0.0; for k = 0 .. n_dirs-1 in that order acc = acc + L(i,k)[ch] * W[k*n_weights + c]; each step
+ * is one f64 product then one f64 sum, nothing fused.  NaN and infinite weights and radiances follow IEEE (0 * inf is NaN); a zero weight
+ * is not skipped.  Every element is written by exactly one lane; there are no atomics, so nothing depends on the order tiles finish in.
+ * weights and n_weights are looked at only where sums is asked for.
+ * lanes: the work item.  1: direction lanes -- a tile is one pose x 64 consecutive directions, tile = pose * ceil(n_dirs/64) + block; the
+ * rays share an origin, like a camera's.  2: pose lanes -- a tile is 64 consecutive poses x one direction, tile = pose_block * n_dirs + k;
+ * with NULL frames the 64 rays are parallel.  0: auto -- pose lanes iff n_poses >= n_dirs, else direction lanes; a stated default, not a
+ * measured optimum.  Any other value is an error.  Every output is the same bytes in either form.
+ * Limits, all checked before any HIP call: n_dirs > 2^32 - 1 is an error; more tiles than 2^32 - 1 in the form chosen is an error
+ * (n_poses * ceil(n_dirs/64) for direction lanes, ceil(n_poses/64) * n_dirs for pose lanes); each of n_poses*n_dirs*24, n_poses*72 and,
+ * with sums, n_dirs*n_weights*8 and n_poses*n_weights*24 bytes must fit size_t.  n_poses == 0 or n_dirs == 0 is a successful no-op that
+ * writes nothing, and it is answered BEFORE every other check, as for the scans.
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched), for non-zero counts: a NULL accel, out, origins or dirs; both
+ * outputs NULL; sums given with weights == NULL or n_weights == 0; a bad lanes; the limits above; lg_radiance's two refusals; in the
+ * device form also any pointer that is not 8-byte aligned device memory of the accel's device, or that ends beyond its allocation.
+ * Where li lives: with radiance given, li IS the caller's plane and the whole call is one level-0 query of the level-by-level pipeline
+ * (cut into chunks by LASGUN_WF_BUDGET_MB, as lg_radiance is), then one reduction.  With sums alone, li is parked in a buffer of the
+ * launch context: the call is cut into batches of whole consecutive poses that park at most LASGUN_GATHER_PARK_MB MiB each (read once;
+ * default 1024, a stated default; never fewer than one pose a batch), and each batch is reduced before the next.  Batching cannot change
+ * a bit: a sum never crosses a pose.  lg_profile_read_kinds credits the reduction as a combine pass, kind 1.
+ * Device form: dev_out is a HOST struct of device pointers.  It only enqueues on hip_stream, with lg_radiance_device's exception: growing
+ * the launch context's level arrays or the parked buffer synchronises the device first.  One stream at a time per accel.  Host form
+ * (synchronous): the tables go up, the outputs come back into staging and are copied out at the end, so an error on the way leaves the
+ * caller's arrays as they were.
+ * Out of scope: a multi-device split, a sorted order, per-pose direction sets or weights, any other summation order, normal-dependent
+ * culling of directions (callers use lg_open_directions' `above` rule, or zero weights).
+ * lg_radiance_gather_lanes: the work item a call with these counts and this `lanes` would use -- 1 or 2; -1 for a bad `lanes`; no device
+ * is touched. */
+typedef struct lg_gather_out {
+    double *radiance;  /* [n_poses*n_dirs][3], element (i,k) at i*n_dirs + k; may be NULL */
+    double *sums;      /* [n_poses][n_weights][3]; may be NULL */
+} lg_gather_out;       /* 16 bytes; both NULL is an error */
+int lg_radiance_gather(const lg_accel *, const double *origins, const double *frames, size_t n_poses, const double *dirs, size_t n_dirs,
+                       const double *weights, size_t n_weights, int lanes, const lg_gather_out *out);      /* host arrays; synchronous */
+int lg_radiance_gather_device(const lg_accel *, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_dirs,
+                              size_t n_dirs, const double *dev_weights, size_t n_weights, int lanes, const lg_gather_out *dev_out,
+                              void *hip_stream);
+int lg_radiance_gather_lanes(size_t n_poses, size_t n_dirs, int lanes);   /* the work item a call would use: 1 or 2; -1 for a bad `lanes`; no device */
 /* The rays the render traces for the pixels [x0,x1) x [y0,y1) of a width x height film: row-major pixels and, per pixel, the camera's
  * samples in camera.rs order (idx = i*dim + j, camera.rs:137-146), 6 doubles each: (x1-x0) * (y1-y0) * supersamples rays. */
 int lg_camera_rays(const lg_accel *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays);

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures, CScanOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures, CScanOut, CGatherOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -94,6 +94,7 @@ _EXTRA = {
     **VISIBILITY_SIGNATURES,
     **DIRECTIONS_SIGNATURES,
     **RANGE_SCAN_SIGNATURES,
+    **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
 }
 
@@ -114,6 +115,9 @@ SCAN_PLANES = ("range", "point", "normal", "id", "hits", "nearest")  # lg_scan_o
 _SCAN_SHAPE = {"range": ((), _np.float32, True), "point": ((3,), _np.float32, True), "normal": ((3,), _np.float32, True), "id": ((4,), _np.uint32, True),
                "hits": ((), _np.uint32, False), "nearest": ((), _np.float32, False)}  # (trailing shape, dtype, per pair -- else per pose)
 SCAN_LANES = {"auto": 0, "beam": 1, "pose": 2}
+assert _C.sizeof(CGatherOut) == 16, "lg_gather_out is 16 bytes"
+GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
+GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
 _FEATURE_SHAPE = {"depth": ((), _np.float32), "normal": ((3,), _np.float32), "albedo": ((3,), _np.float32), "coverage": ((), _np.float32),
                   "id": ((4,), _np.uint32)}
 
@@ -667,6 +671,66 @@ class HipApi(Api):
                      _C.addressof(f), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- radiance gathers (include/lasgun_hip.h, lg_radiance_gather*): li() along K shared directions from N poses, reduced per pose
+    @staticmethod
+    def _gather_lanes(lanes):
+        return GATHER_LANES[lanes] if isinstance(lanes, str) else int(lanes)
+
+    def radiance_gather_lanes(self, n_poses, n_dirs, lanes=0):
+        """The work item a gather of these counts would use: 1 direction lanes (one pose x 64 directions a wave), 2 pose lanes (64 poses x
+        one direction); -1 for a bad `lanes`.  lanes: 0 / "auto" (pose lanes iff n_poses >= n_dirs), 1 / "direction", 2 / "pose".  No device
+        is touched."""
+        return int(self.call("radiance_gather_lanes", int(n_poses), int(n_dirs), self._gather_lanes(lanes)))
+
+    def radiance_gather(self, accel, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0, into=None):
+        """li() along dirs[k] from origins[i], what `radiance` returns for that ray: a dict of the planes asked for (any of "radiance",
+        "sums") -- float64 (n_poses, n_dirs, 3) radiance, and float64 (n_poses, n_weights, 3) sums[i, c] = the sum over k, in order from
+        +0.0, of radiance[i, k] * weights[k, c] (one product, one sum a step).  weights: (n_dirs, n_weights) float64, or (n_dirs,) for one
+        column; needed for "sums" alone.  frames: (n_poses, 3, 3) or (n_poses, 9) float64, row-major, d[c] = (M[c,0]*b.x + M[c,1]*b.y) +
+        M[c,2]*b.z; None: the directions are used bit for bit.  The directions are not normalised.  lanes: radiance_gather_lanes' (the
+        outputs do not depend on it).  `into`: a dict of C-contiguous arrays of those shapes, written in place.
+        Also `accel.radiance_gather(origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0)`."""
+        o, b = self._points(origins, "origins"), self._points(dirs, "dirs")
+        m = None
+        if frames is not None:
+            m = _np.ascontiguousarray(frames, dtype=_np.float64)
+            if m.shape not in ((o.shape[0], 3, 3), (o.shape[0], 9)):
+                raise ValueError("frames: one 3 x 3 matrix per pose")
+        planes = tuple(planes)
+        if any(p not in GATHER_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (GATHER_PLANES,))
+        wt, n_weights = None, 0
+        if weights is not None:
+            wt = _np.ascontiguousarray(weights, dtype=_np.float64)
+            if wt.ndim == 1:
+                wt = wt.reshape(-1, 1)
+            if wt.ndim != 2 or wt.shape[0] != b.shape[0]:
+                raise ValueError("weights: (n_dirs, n_weights), one row per direction")
+            n_weights = wt.shape[1]
+        shapes = {"radiance": (o.shape[0], b.shape[0], 3), "sums": (o.shape[0], n_weights, 3)}
+        out = {}
+        for p in planes:
+            arr = into[p] if into is not None else _np.zeros(shapes[p], dtype=_np.float64)
+            if arr.dtype != _np.float64 or arr.shape != shapes[p] or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous float64 array of shape %s" % (p, shapes[p]))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CGatherOut(*[data(out.get(p)) for p in GATHER_PLANES])
+        if self.call("radiance_gather", accel.h, data(o), data(m), o.shape[0], data(b), b.shape[0], data(wt), n_weights, self._gather_lanes(lanes), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def radiance_gather_device(self, accel, n_poses, origins_ptr, frames_ptr, n_dirs, dirs_ptr, weights_ptr=None, n_weights=0, radiance_ptr=None, sums_ptr=None,
+                               lanes=0, stream=None):
+        """Enqueue the gather of n_poses poses (device memory, 3 doubles an origin; frames_ptr 9 doubles a pose or None) along n_dirs
+        directions (3 doubles each) into device memory: n_poses * n_dirs * 3 doubles at radiance_ptr and / or, with n_dirs * n_weights
+        doubles at weights_ptr, n_poses * n_weights * 3 doubles at sums_ptr; each output may be None, not both."""
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        f = CGatherOut(*[int(p) if p is not None else None for p in (radiance_ptr, sums_ptr)])
+        if self.call("radiance_gather_device", accel.h, ptr(origins_ptr), ptr(frames_ptr), int(n_poses), ptr(dirs_ptr), int(n_dirs), ptr(weights_ptr), int(n_weights),
+                     self._gather_lanes(lanes), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of the camera's primary hits
     def material_count(self, accel):
         """The number of materials of the accel's tables: indices 0 .. count-1 are valid for accel_material and name the rows of material_rgb."""
@@ -926,12 +990,61 @@ def spinning_lidar_beams(rings, azimuths, elev_lo_deg, elev_hi_deg):
     return _np.ascontiguousarray(d / _np.linalg.norm(d, axis=1)[:, None])
 
 
+def cosine_directions(k):
+    """(k, 3) float64: k unit directions about +z whose density is proportional to the cosine of the angle to +z (a Fibonacci spiral on the
+    unit disk, lifted to the hemisphere), so that the mean of li over them estimates irradiance / pi.  For j = 0 .. k-1: u = (j + 0.5) / k,
+    r = sqrt(u), phi = j * pi * (3 - sqrt(5)), d = (r cos phi, r sin phi, sqrt(1 - u)).  A convention of this WRAPPER, not of the C contract."""
+    j = _np.arange(int(k), dtype=_np.float64)
+    u = (j + 0.5) / max(int(k), 1)
+    r, phi = _np.sqrt(u), j * (_np.pi * (3.0 - _np.sqrt(5.0)))
+    return _np.ascontiguousarray(_np.stack([r * _np.cos(phi), r * _np.sin(phi), _np.sqrt(1.0 - u)], axis=1))
+
+
+def sh_weights(dirs, bands=3):
+    """(K, bands^2) float64 weights for radiance_gather that project a pose's radiance onto the real spherical harmonics: column l*l + l + m
+    of row k is Y_lm(d_k / |d_k|) * 4 pi / K, the Monte-Carlo weight of K directions spread evenly over the sphere (sphere_directions).
+    bands 1 .. 3, with (x, y, z) = d / |d|:  Y_00 = 0.28209479177387814;  Y_1,-1 = 0.4886025119029199 y,  Y_10 = 0.4886025119029199 z,
+    Y_11 = 0.4886025119029199 x;  Y_2,-2 = 1.0925484305920792 x y,  Y_2,-1 = 1.0925484305920792 y z,  Y_20 = 0.31539156525252005 (3 z z - 1),
+    Y_21 = 1.0925484305920792 x z,  Y_22 = 0.5462742152960396 (x x - y y).  No Condon-Shortley sign.  A convention of this WRAPPER, not of
+    the C contract."""
+    bands = int(bands)
+    if not 1 <= bands <= 3:
+        raise ValueError("bands: 1, 2 or 3")
+    d = _np.ascontiguousarray(dirs, dtype=_np.float64).reshape(-1, 3)
+    n = d / _np.linalg.norm(d, axis=1)[:, None]
+    x, y, z = n[:, 0], n[:, 1], n[:, 2]
+    cols = [_np.full(d.shape[0], 0.28209479177387814)]
+    if bands >= 2:
+        cols += [0.4886025119029199 * y, 0.4886025119029199 * z, 0.4886025119029199 * x]
+    if bands >= 3:
+        cols += [1.0925484305920792 * (x * y), 1.0925484305920792 * (y * z), 0.31539156525252005 * (3.0 * (z * z) - 1.0), 1.0925484305920792 * (x * z),
+                 0.5462742152960396 * (x * x - y * y)]
+    return _np.ascontiguousarray(_np.stack(cols, axis=1) * (4.0 * _np.pi / max(d.shape[0], 1)))
+
+
+def frames_from_normals(normals):
+    """(N, 3, 3) float64 frames for radiance_gather / range_scan: per point a row-major matrix whose columns t, s, n are an orthonormal
+    basis with n = normal / |normal| as the THIRD column, so that a direction (0, 0, 1) leaves along the normal.  Branch-free (Duff et al.,
+    "Building an Orthonormal Basis, Revisited", 2017): sg = copysign(1, n.z), a = -1 / (sg + n.z), b = n.x * n.y * a,
+    t = (1 + sg * n.x * n.x * a, sg * b, -sg * n.x), s = (b, sg + n.y * n.y * a, -n.y).  A convention of this WRAPPER, not of the C contract."""
+    v = _np.ascontiguousarray(normals, dtype=_np.float64).reshape(-1, 3)
+    n = v / _np.linalg.norm(v, axis=1)[:, None]
+    x, y, z = n[:, 0], n[:, 1], n[:, 2]
+    sg = _np.copysign(1.0, z)
+    a = -1.0 / (sg + z)
+    b = x * y * a
+    t = _np.stack([1.0 + sg * x * x * a, sg * b, -sg * x], axis=1)
+    s = _np.stack([b, sg + y * y * a, -y], axis=1)
+    return _np.ascontiguousarray(_np.stack([t, s, n], axis=2))
+
+
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
 api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None: api.capture_features(self, w, h, rect, planes, material_rgb)  # accel.features(w, h)
 api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
 api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
+api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

@@ -161,6 +161,15 @@ RANGE_SCAN_SIGNATURES = {
     "range_scan_lanes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int]),
 }
 
+# Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
+# directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
+GATHER_SIGNATURES = {
+    "radiance_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "radiance_gather_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
+    "radiance_gather_lanes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int]),
+}
+
 # Feature buffers (include/lasgun_hip.h, lg_capture_features* / lg_accel_material_count): depth, normal, albedo, coverage and ids of the
 # camera's primary hits; the GPU library's alone.
 FEATURES_SIGNATURES = {
@@ -176,6 +185,10 @@ class CFeatures(C.Structure):  # lg_features: five plane pointers, 40 bytes; NUL
 
 class CScanOut(C.Structure):  # lg_scan_out: six pointers, 48 bytes; NULL = not asked for
     _fields_ = [("range", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p), ("hits", C.c_void_p), ("nearest", C.c_void_p)]
+
+
+class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for
+    _fields_ = [("radiance", C.c_void_p), ("sums", C.c_void_p)]
 
 
 class CLens(C.Structure):  # lg_lens: 112 bytes, no padding

@@ -371,6 +371,19 @@ struct FilmArgs : RadianceArgs {
     double *rgb;                       // f64 RGB before quantisation, 3 per pixel; may be nullptr
 };
 
+// A radiance gather's level 0 (k_gather.hip; lg_radiance_gather*), beside the DParams of its chunk: the two tables the rays are made from,
+// where li goes, and where the chunk starts.  A batch of a call is a call of its own here: its poses' tables, its own li.
+struct GatherArgs {
+    const double *origins;         // [n_poses][3]
+    const double *frames;          // [n_poses][9], row-major 3 x 3; nullptr: the directions are used as given
+    const double *dirs;            // [n_dirs][3]
+    double *li;                    // [n_poses * n_dirs][3]: ray (i, k) at i * n_dirs + k
+    unsigned long long n_poses, n_dirs;
+    unsigned long long base_tile;  // the chunk's first tile: work item i of the chunk belongs to tile base_tile + i / 64
+    uint32_t tiles_per;            // tiles per pose (direction lanes: ceil(n_dirs / 64)) or per block of 64 poses (pose lanes: n_dirs)
+    uint32_t pose_lanes;           // 0: a tile is one pose x 64 directions; 1: 64 poses x one direction
+};
+
 // A lens camera (k_lens.hip; include/lasgun_hip.h, lg_lens -- the same 112 bytes)
 struct DLens {
     int32_t kind, reserved;          // 0 equirectangular panorama, 1 equidistant fisheye

@@ -58,6 +58,14 @@ hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks,
 hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream);
 hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
+// k_gather.hip: level 0 a third time, for the rays of a radiance gather (launch.cpp, enqueue_radiance_gather), and its reduction:
+// sums[(i*n_weights + c)*3 ..] = the sequential weighted sum of pose i's li over the directions
+hipError_t launch_gather_closest(const DParams &P, const GatherArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_gather_shade(const DParams &P, const GatherArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_gather_combine(const DParams &P, const GatherArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_gather_resolve(const double *li, const double *weights, double *sums, unsigned long long n_poses, unsigned long long n_dirs, unsigned long long n_weights,
+                                 uint32_t blocks, hipStream_t stream);
+hipError_t gather_set_lds_limit(size_t bytes, bool ldss);
 // k_lens.hip: the rays of a lens camera (lg_lens_rays*)
 hipError_t launch_lens_rays(const DLens &L, uint32_t w, uint32_t h, uint32_t root, const unsigned long long *offsets, unsigned long long n, double *rays,
                             uint32_t blocks, hipStream_t stream);
@@ -406,6 +414,7 @@ struct lg_accel {
         DevBuf<uint8_t> wf_mem;                                // wavefront pipeline: every per-level array of a chunk, carved from one allocation
         DevBuf<uint32_t> wf_counters;                          // its queue counts and per-launch tile counters
         DevBuf<double> film_li;                                // ray films of several samples per pixel (lg_capture_rays*): every ray's li, 24 bytes a ray, until the resolve pass; grown on demand
+        DevBuf<double> gather_li;                              // radiance gathers without a radiance plane (lg_radiance_gather*): a batch's li, 24 bytes a ray, until its resolve pass; grown on demand
         DevBuf<uint8_t> sort_mem;                              // ray queries in sorted order (k_sort.hip): ping-pong keys and indices, histograms; grown on demand
         // strided subsets by lattice column (shade.h, modes 4 / 5): (floor(y*w / n), (y*w) mod n) per film row -- one table per (w, h, n), the
         // last MAX_ROW_TABLES of them kept (a caller that alternates periods or films on one stream finds each again), each uploaded from
@@ -511,6 +520,15 @@ void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream);
+// One checked lg_radiance_gather* call on device tables (query.cpp; gather_host.h): batch_poses = n_poses where radiance is given
+struct GatherCall {
+    const double *origins, *frames, *dirs, *weights; // frames may be nullptr; weights where sums is given
+    size_t n_poses, n_dirs, n_weights;
+    bool pose_lanes;
+    double *radiance, *sums;                         // either may be nullptr
+    size_t batch_poses;                              // whole poses whose li is parked at a time (sums alone)
+};
+void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::LaunchCtx &c, hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

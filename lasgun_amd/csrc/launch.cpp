@@ -221,15 +221,17 @@ struct ChunkPlan {
 };
 
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
-// (`rq`: the launch is a radiance query's -- its level 0 is k_radiance.hip's)
-static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr) {
+// (`rq`: the launch is a radiance query's -- its level 0 is k_radiance.hip's; `rf`: a ray film's; `rg`: a radiance gather's, k_gather.hip's)
+static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr,
+                           const GatherArgs *rg = nullptr) {
     const unsigned long long n0 = plan.n0();
     const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull), flat_cap = a.cus * 16u; // (level 0: one thread per work item)
     for (uint32_t d = plan.levels - 1; d-- > 0;) {
         P.wf_level = d;
         P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
         P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-        if (d == 0 && rf) timed(a, 1, s, [&] { return launch_rf_combine(P, *rf, flat_blocks0, s); });
+        if (d == 0 && rg) timed(a, 1, s, [&] { return launch_gather_combine(P, *rg, flat_blocks0, s); });
+        else if (d == 0 && rf) timed(a, 1, s, [&] { return launch_rf_combine(P, *rf, flat_blocks0, s); });
         else if (d == 0 && rq) timed(a, 1, s, [&] { return launch_rq_combine(P, *rq, flat_blocks0, s); });
         else timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
     }
@@ -275,8 +277,9 @@ struct WfChunk {
         if (lds_resident(a)) set_lds_scene(a, P);
     }
     // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
-    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms).
-    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr) const {
+    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms);
+    // `rg`: ... a radiance gather's, made in the kernel from two tables (k_gather.hip).
+    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr, const GatherArgs *rg = nullptr) const {
         const bool ldss = P.lds_image != nullptr;
         const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
         const uint32_t trace_cap = ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks), flat_cap = a.cus * 16u;
@@ -298,9 +301,10 @@ struct WfChunk {
             // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
             // every deeper level may exceed only in waves, never in work per wave)
             const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
-            const bool rq0 = rq && d == 0, rf0 = rf && d == 0;
+            const bool rq0 = rq && d == 0, rf0 = rf && d == 0, rg0 = rg && d == 0;
             level_params(d);
-            if (rf0) timed(a, 0, ls, [&] { return launch_rf_closest(P, *rf, a.fast, tb, depth, ls); });
+            if (rg0) timed(a, 0, ls, [&] { return launch_gather_closest(P, *rg, a.fast, tb, depth, ls); });
+            else if (rf0) timed(a, 0, ls, [&] { return launch_rf_closest(P, *rf, a.fast, tb, depth, ls); });
             else if (rq0) timed(a, 0, ls, [&] { return launch_rq_closest(P, *rq, a.fast, tb, depth, ls); });
             else timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
             if (P.nlights > 0) {
@@ -308,11 +312,12 @@ struct WfChunk {
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
             }
             level_params(d);
-            if (rf0) timed(a, 3, ls, [&] { return launch_rf_shade(P, *rf, fb, ls); });
+            if (rg0) timed(a, 3, ls, [&] { return launch_gather_shade(P, *rg, fb, ls); });
+            else if (rf0) timed(a, 3, ls, [&] { return launch_rf_shade(P, *rf, fb, ls); });
             else if (rq0) timed(a, 3, ls, [&] { return launch_rq_shade(P, *rq, fb, ls); });
             else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
-        combine_levels(a, P, L, plan, ls, rq, rf);
+        combine_levels(a, P, L, plan, ls, rq, rf, rg);
     }
 };
 
@@ -396,12 +401,25 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
 // level by level (radiance_possible).
 // `film` (lg_capture_rays* of one sample per pixel slot): ray r is pixel slot r and level 0 finishes it into the film (FilmArgs) instead of
 // radiance[] -- the same chunks, the same launches with the film forms of the three level-0 kernels in place of the radiance forms.
-// `label` / `tail`: what LASGUN_DEBUG calls the query, and what is enqueued behind its chunks inside the profiled span (a film's resolve pass).
-static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n, double *radiance, const FilmArgs *film, const uint32_t *perm, lg_accel::LaunchCtx &c,
-                                 hipStream_t stream, const char *label, const std::function<void()> &tail = nullptr) {
+// `gather` (lg_radiance_gather*): there is no ray array -- level 0's work items are the gather's `gather_tiles` tiles, whose rays its own
+// forms of the three kernels make from two tables (k_gather.hip) and finish into gather->li; a chunk is told its first tile.
+// `label` / `note`: what LASGUN_DEBUG calls the query and how it ends its line (a query's rays: the order they are walked in); `tail`: what
+// is enqueued behind the chunks inside the profiled span (a film's or a gather's resolve pass).
+struct Level0Source {
+    const double *rays = nullptr;       // a radiance query or a ray film: n rays ...
+    size_t n = 0;
+    double *radiance = nullptr;         // ... into radiance[] ...
+    const FilmArgs *film = nullptr;     // ... or into a film
+    const uint32_t *perm = nullptr;
+    const GatherArgs *gather = nullptr; // a radiance gather (base_tile is the chunk's to set)
+    uint32_t gather_tiles = 0;
+    const char *label = "";
+    std::string note;
+};
+static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_accel::LaunchCtx &c, hipStream_t stream, const std::function<void()> &tail = nullptr) {
     DParams P0 = base_params(a, 1, 1);
     P0.ss_root = 1; // (the scene's camera may be supersampled; a query is not)
-    P0.ntiles = (uint32_t)((n + 63) / 64);
+    P0.ntiles = src.gather ? src.gather_tiles : (uint32_t)((src.n + 63) / 64);
     const uint32_t levels = levels_of(a, P0);
     ChunkPlan plan(a, P0, false, 1u, WfChunk::extra_per_item(levels));
     WfChunk K(plan);
@@ -409,17 +427,23 @@ static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n
     const unsigned long long chunk_tiles = plan.chunk_tiles;
     Span span(a, stream);
     if (std::getenv("LASGUN_DEBUG"))
-        std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", label, levels, (unsigned long long)P0.ntiles,
-                     chunk_tiles, plan.need() / 1048576.0, perm ? "sorted order" : "as given");
+        std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", src.label, levels, (unsigned long long)P0.ntiles,
+                     chunk_tiles, plan.need() / 1048576.0, src.note.c_str());
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
         P.ntiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
         P.ss_par = 1u;
         K.params(a, P);
-        const RadianceArgs Q{rays, radiance, perm, (unsigned long long)n, t0 * 64ull};
-        if (film) {
-            FilmArgs F = *film;
+        if (src.gather) {
+            GatherArgs G = *src.gather;
+            G.base_tile = t0;
+            K.run(a, P, stream, nullptr, nullptr, &G);
+            continue;
+        }
+        const RadianceArgs Q{src.rays, src.radiance, src.perm, (unsigned long long)src.n, t0 * 64ull};
+        if (src.film) {
+            FilmArgs F = *src.film;
             static_cast<RadianceArgs &>(F) = Q;
             K.run(a, P, stream, &Q, &F);
         } else K.run(a, P, stream, &Q);
@@ -427,8 +451,44 @@ static void enqueue_level0_query(const lg_accel &a, const double *rays, size_t n
     if (tail) tail();
     span.end(a.events);
 }
+// the rays of a radiance query or a ray film as level 0's source
+static Level0Source ray_source(const double *rays, size_t n, double *radiance, const FilmArgs *film, const uint32_t *perm, const char *label) {
+    Level0Source src;
+    src.rays = rays; src.n = n; src.radiance = radiance; src.film = film; src.perm = perm; src.label = label;
+    src.note = perm ? "sorted order" : "as given";
+    return src;
+}
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
-    enqueue_level0_query(a, rays, n, radiance, nullptr, perm, c, stream, "radiance query");
+    enqueue_level0_query(a, ray_source(rays, n, radiance, nullptr, perm, "radiance query"), c, stream);
+}
+// A radiance gather (query.cpp, lg_radiance_gather*; the call checked there and in gather_host.h): batch after batch of g.batch_poses whole
+// consecutive poses, each a level-0 query of its own over the batch's tiles -- its poses' rows of the tables, its own li -- with the
+// reduction (k_gather.hip, gather_resolve_kernel; credited to lg_profile_read_kinds as a combine pass, kind 1, as a film's resolve is) as
+// its tail where sums is asked for.  li is the caller's radiance plane (then the call is ONE batch) or the context's gather_li, which the
+// next batch overwrites: the stream orders a batch's reduction ahead of the next batch's level 0.  Growing gather_li is the one step that
+// is more than an enqueue (a device-wide synchronise first, as for the level arrays).  A sum never crosses a pose, so the batches cannot
+// change a bit.
+void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    const size_t batch_poses = std::min(g.batch_poses, g.n_poses);
+    const size_t nbatches = (g.n_poses + batch_poses - 1) / batch_poses;
+    if (!g.radiance) grow(c.gather_li, batch_poses * g.n_dirs * 3);
+    for (size_t p0 = 0, batch = 0; p0 < g.n_poses; p0 += batch_poses, ++batch) {
+        const size_t np = std::min(batch_poses, g.n_poses - p0);
+        double *li = g.radiance ? g.radiance + 3 * (p0 * g.n_dirs) : c.gather_li.p;
+        const uint32_t tiles_per = g.pose_lanes ? (uint32_t)g.n_dirs : (uint32_t)((g.n_dirs + 63) / 64);
+        const GatherArgs G{g.origins + 3 * p0, g.frames ? g.frames + 9 * p0 : nullptr, g.dirs, li, np, g.n_dirs, 0ull, tiles_per, g.pose_lanes ? 1u : 0u};
+        Level0Source src;
+        src.gather = &G;
+        src.gather_tiles = (uint32_t)((g.pose_lanes ? (np + 63) / 64 : np) * tiles_per); // (at most the call's tiles: 32 bits)
+        src.label = "radiance gather";
+        src.note = "batch " + std::to_string(batch + 1) + " of " + std::to_string(nbatches) + ", " + (g.pose_lanes ? "pose lanes" : "direction lanes");
+        double *sums = g.sums ? g.sums + 3 * (p0 * g.n_weights) : nullptr;
+        enqueue_level0_query(a, src, c, stream, [&] {
+            if (!sums) return;
+            const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)np * g.n_weights + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
+            timed(a, 1, stream, [&] { return launch_gather_resolve(li, g.weights, sums, np, g.n_dirs, g.n_weights, blocks, stream); });
+        });
+    }
 }
 // A ray film (query.cpp, lg_capture_rays*): `slots` pixel slots of `samples` rays each, slot g's rays [g*samples, (g+1)*samples), into
 // film.rgba / film.rgb at film.offsets[g] (or g).  One sample: the film forms of level 0 finish every ray where the radiance forms finish
@@ -440,10 +500,10 @@ void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *r
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream) {
     const size_t n = slots * samples;
-    if (samples == 1) { enqueue_level0_query(a, rays, n, nullptr, &film, perm, c, stream, "ray film"); return; }
+    if (samples == 1) { enqueue_level0_query(a, ray_source(rays, n, nullptr, &film, perm, "ray film"), c, stream); return; }
     grow(c.film_li, n * 3);
     const double *li = c.film_li.p;
-    enqueue_level0_query(a, rays, n, c.film_li.p, nullptr, perm, c, stream, "ray film", [&] {
+    enqueue_level0_query(a, ray_source(rays, n, c.film_li.p, nullptr, perm, "ray film"), c, stream, [&] {
         const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)slots + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
         timed(a, 1, stream, [&] { return launch_rf_resolve(film, li, slots, samples, blocks, stream); });
     });

@@ -1,4 +1,4 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_camera_rays*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*,
 // lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
 // k_visibility.hip, k_directions.hip, k_scan.hip and k_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
@@ -11,6 +11,7 @@
 
 #include "bitrows_host.h"
 #include "features_host.h"
+#include "gather_host.h"
 #include "scan_host.h"
 #include "internal.h"
 
@@ -405,6 +406,57 @@ extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, siz
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         check_device_buffer(*a, dev_radiance, n * 3 * sizeof(double), 8, "radiance");
         enqueue_radiance_query(*a, dev_rays, n, dev_radiance, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- radiance gathers (lg_radiance_gather*; launch.cpp, enqueue_radiance_gather; k_gather.hip): li() of the rays (origins[i], frames[i] *
+// dirs[k]) made in the kernel, written as a plane and / or reduced per pose by the caller's weights.  The arithmetic that needs no device --
+// the lane rule, the tile counts, the sizes, the NULL and alignment rules, the batch, the staging -- is gather_host.h's.
+extern "C" int lg_radiance_gather_lanes(size_t n_poses, size_t n_dirs, int lanes) { return gather_lanes(n_poses, n_dirs, lanes); }
+// One gather enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts, scene and buffers)
+static void enqueue_gather(const lg_accel &a, const double *origins, const double *frames, size_t n_poses, const double *dirs, size_t n_dirs, const double *weights,
+                           size_t n_weights, const GatherShape &shape, const lg_gather_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    static const size_t park_bytes = gather_park_bytes(std::getenv("LASGUN_GATHER_PARK_MB")); // (read once)
+    const size_t batch = out.radiance ? n_poses : gather_batch_poses(n_poses, n_dirs, shape.form, park_bytes);
+    const GatherCall g{origins, frames, dirs, out.sums ? weights : nullptr, n_poses, n_dirs, out.sums ? n_weights : 0, shape.form == GATHER_POSE_LANES, out.radiance, out.sums, batch};
+    enqueue_radiance_gather(a, g, ctx_for(a, stream), stream);
+}
+// Host form: the tables go up, the outputs come back into staging and are copied out at the end
+extern "C" int lg_radiance_gather(const lg_accel *a, const double *origins, const double *frames, size_t n_poses, const double *dirs, size_t n_dirs, const double *weights,
+                                  size_t n_weights, int lanes, const lg_gather_out *out) {
+    return guarded([&] {
+        if (n_poses == 0 || n_dirs == 0) return;
+        const GatherShape shape = check_gather(a, origins, n_poses, dirs, n_dirs, weights, n_weights, lanes, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        radiance_possible(*a);
+        RoundTrip trip(*a);
+        GatherStaging st(*out, shape.pairs, n_poses, n_weights);
+        const double *dorigins = trip.in(origins, n_poses * 3), *dframes = trip.in(frames, n_poses * 9), *ddirs = trip.in(dirs, n_dirs * 3);
+        const double *dweights = out->sums ? trip.in(weights, n_dirs * n_weights) : nullptr;
+        lg_gather_out dev = *out; // ... where an output asked for becomes its device buffer, which comes back into its staging
+        if (dev.radiance) dev.radiance = trip.out(st.radiance.data(), st.radiance.size());
+        if (dev.sums) dev.sums = trip.out(st.sums.data(), st.sums.size());
+        trip.run([&] { enqueue_gather(*a, dorigins, dframes, n_poses, ddirs, n_dirs, dweights, n_weights, shape, dev, a->stream); });
+        place_gather(*out, st);
+    });
+}
+extern "C" int lg_radiance_gather_device(const lg_accel *a, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_dirs, size_t n_dirs,
+                                         const double *dev_weights, size_t n_weights, int lanes, const lg_gather_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n_poses == 0 || n_dirs == 0) return;
+        const GatherShape shape = check_gather(a, dev_origins, n_poses, dev_dirs, n_dirs, dev_weights, n_weights, lanes, dev_out);
+        check_gather_alignment(dev_origins, dev_frames, dev_dirs, dev_weights, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        radiance_possible(*a);
+        use_device(a->device);
+        check_device_buffer(*a, dev_origins, n_poses * 3 * sizeof(double), 8, "origins");
+        if (dev_frames) check_device_buffer(*a, dev_frames, n_poses * 9 * sizeof(double), 8, "frames");
+        check_device_buffer(*a, dev_dirs, n_dirs * 3 * sizeof(double), 8, "dirs");
+        if (dev_out->sums) check_device_buffer(*a, dev_weights, n_dirs * n_weights * sizeof(double), 8, "weights");
+        if (dev_out->radiance) check_device_buffer(*a, dev_out->radiance, shape.pairs * 3 * sizeof(double), 8, "radiance");
+        if (dev_out->sums) check_device_buffer(*a, dev_out->sums, n_poses * n_weights * 3 * sizeof(double), 8, "sums");
+        enqueue_gather(*a, dev_origins, dev_frames, n_poses, dev_dirs, n_dirs, dev_weights, n_weights, shape, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

@@ -40,7 +40,16 @@ along the camera's view axis, each with a rotation frame (the sensor yawed about
 s1a / s2a: all six outputs.  Beside them lg_intersect_device (the parent commit's library has it) on the explicit rays of the same pairs,
 their construction not timed: row sx1, pose-major, which is beam lanes' own order and the caller's natural one; row sx2, per block of 64
 poses beam-major, pose lanes' own order.  Every scan's range, hits and nearest are checked against sx1's records.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan[,...]] [--out profiles/r08_query_order.jsonl]
+Radiance gathers (lg_radiance_gather_device) -- --rows gather (not part of "all"), two shapes a scene, each in both lane forms, sums alone (li
+parked).  Shape a: the first hits of a 1024^2 camera frame in 8 x 8 tile order, pushed out along ng, as poses with frames_from_normals(ng) x
+the 64 cosine_directions, one weight column of 1 / 64 (a lightmap's irradiance / pi).  Shape b: 4096 probes, a 16^3 grid in the hits' bounds,
+without frames x the 6144 sphere_directions with sh_weights (9 columns: an SH9 probe grid).  Rows g1 / g2: direction lanes / pose lanes.
+Beside them lg_radiance_device (the parent commit's library has it) on the explicit rays of the same pairs, their construction not timed: row
+gx1, pose-major, which is direction lanes' own order and the caller's natural one; row gx2, per block of 64 poses direction-major, pose
+lanes' own order.  Every gather's sums are checked against the sequential sum of gx1's radiance (torch: a product and a sum a step).  Each row
+carries kind1_ms, what lg_profile_read_kinds credits to kind 1 in one profiled call (the level combine passes, and for g1 / g2 the resolve);
+resolve_ms = a g row's kind1_ms minus its yardstick's is the resolve's own time.  These rows time --calls calls as given (at least 3), not 20.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -431,6 +440,96 @@ def measure_scan(name, builder, calls):
     return out
 
 
+def gather_shapes(accel, s, size=1024):
+    """[(shape, poses, frames or None, dirs, weights)] of one scene, device tensors (module docstring)."""
+    assert G.camera_samples(accel) == 1 and size % 8 == 0
+    rays = torch.empty((size * size, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rays = rays.view(size // 8, 8, size // 8, 8, 6).permute(0, 2, 1, 3, 4).contiguous().view(-1, 6)  # 8 x 8 pixel tiles
+    hits = torch.empty((size * size * 96,), dtype=torch.uint8, device="cuda")
+    G.intersect_device(accel, size * size, rays.data_ptr(), hits.data_ptr(), stream=s)
+    f = hits.view(torch.float64).view(-1, 12)
+    f = f[hits.view(torch.int32).view(-1, 24)[:, 20] != 0]
+    p, ng = f[:, 1:4], f[:, 4:7]
+    lo, hi = p.min(dim=0).values, p.max(dim=0).values
+    frames = torch.from_numpy(la.frames_from_normals(ng.cpu().numpy())).cuda().view(-1, 9).contiguous()
+    shape_a = ("a", (p + ng * ERR).contiguous(), frames, torch.from_numpy(la.cosine_directions(64)).cuda(), torch.full((64, 1), 1.0 / 64.0, dtype=torch.float64, device="cuda"))
+    t = (torch.arange(16, dtype=torch.float64, device="cuda") + 0.5) / 16.0
+    grid = torch.stack(torch.meshgrid(t, t, t, indexing="ij"), dim=3).view(-1, 3)
+    dirs = la.sphere_directions(6144)
+    shape_b = ("b", (lo + grid * (hi - lo)).contiguous(), None, torch.from_numpy(dirs).cuda(), torch.from_numpy(la.sh_weights(dirs)).cuda())
+    return [shape_a, shape_b]
+
+
+def measure_gather(name, builder, calls):
+    """Rows gx1 / gx2 / g1 / g2 of one scene, per shape (module docstring)."""
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    calls = max(calls, 3)
+
+    def kind1(fn):
+        G.profile_enable(accel, True)
+        fn()
+        torch.cuda.synchronize()
+        kinds = G.profile_read_kinds(accel)
+        G.profile_enable(accel, False)
+        return kinds["combine"][0]
+
+    out = []
+    for shape, poses, frames, dirs, weights in gather_shapes(accel, s):
+        n, k, c = poses.shape[0], dirs.shape[0], weights.shape[1]
+        if frames is None:
+            d = dirs[None, :, :].expand(n, k, 3)
+        else:  # the header's expression: three products, two sums in the stated order (separate kernels: nothing fused)
+            M = frames.view(n, 1, 9)
+            d = torch.stack([(M[..., 3 * a] * dirs[None, :, 0] + M[..., 3 * a + 1] * dirs[None, :, 1]) + M[..., 3 * a + 2] * dirs[None, :, 2] for a in range(3)], dim=2)
+        by_pose = torch.cat([poses[:, None, :].expand(n, k, 3), d], dim=2).contiguous().view(-1, 6)
+        del d
+        nb = (n + 63) // 64
+        pi = (torch.arange(nb, device="cuda")[:, None, None] * 64 + torch.arange(64, device="cuda")[None, None, :]).expand(nb, k, 64)
+        src = (pi * k + torch.arange(k, device="cuda")[None, :, None])[pi < n]  # per block of 64 poses, direction-major: pose lanes' own order
+        by_block = by_pose[src].contiguous()
+        del pi, src
+        m = n * k
+        rad = torch.empty((m, 3), dtype=torch.float64, device="cuda")
+        rows = []
+        call = lambda: G.radiance_device(accel, m, by_block.data_ptr(), rad.data_ptr(), stream=s)  # noqa: E731
+        rows.append(("gx2: radiance, the pairs as rays, per 64-pose block direction-major (pose lanes' own order)", timed(call, calls, 2), kind1(call), 72.0))
+        del by_block
+        call = lambda: G.radiance_device(accel, m, by_pose.data_ptr(), rad.data_ptr(), stream=s)  # noqa: E731
+        rows.append(("gx1: radiance, the pairs as rays, pose-major (direction lanes' own order)", timed(call, calls, 2), kind1(call), 72.0))
+        del by_pose
+        torch.cuda.synchronize()
+        L = rad.view(n, k, 3)
+        want = torch.zeros((n, c, 3), dtype=torch.float64, device="cuda")
+        for j in range(k):  # the contract's sum: one product, one sum a step, in order
+            want = want + L[:, j, None, :] * weights[j, :, None]
+        del rad, L
+        if hasattr(G, "radiance_gather_device"):
+            sums = torch.empty((n, c, 3), dtype=torch.float64, device="cuda")
+            fp = frames.data_ptr() if frames is not None else None
+            bpp = (n * (24.0 + (72.0 if frames is not None else 0.0)) + k * 24.0 + k * c * 8.0 + n * c * 24.0) / m
+            for lanes in (1, 2):
+                call = lambda: G.radiance_gather_device(accel, n, poses.data_ptr(), fp, k, dirs.data_ptr(), weights.data_ptr(), c, sums_ptr=sums.data_ptr(),  # noqa: E731
+                                                        lanes=lanes, stream=s)
+                sums.fill_(float("nan"))
+                ms = timed(call, calls, 2)
+                rows.append(("g%d: radiance gather, %s, sums" % (lanes, "direction lanes" if lanes == 1 else "pose lanes"), ms, kind1(call), bpp))
+                torch.cuda.synchronize()
+                assert torch.equal(sums.view(torch.int64), want.view(torch.int64)), "the gather's sums are not the sequential sum of gx1's radiance"
+            del sums
+        yard = {"g1": rows[1][2], "g2": rows[0][2]}
+        out += [{"scene": name, "shape": shape, "row": row, "poses": n, "dirs": k, "weights": c, "frames": frames is not None, "rays": m, "ms": round(ms, 4),
+                 "mrays_per_s": round(m / ms / 1e3, 1), "bytes_per_pair": round(bpp, 4), "kind1_ms": round(k1, 4),
+                 "resolve_ms": round(k1 - yard[row[:2]], 4) if row[:2] in yard else None,
+                 "auto_lanes": G.radiance_gather_lanes(n, k) if hasattr(G, "radiance_gather_lanes") else None, "calls": calls,
+                 "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+                 "gpu": torch.cuda.get_device_name(0)} for row, ms, k1, bpp in rows]
+        del want
+    return out
+
+
 def measure_features(name, builder, size, calls):
     """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
     accel = G.Accel.from_scene(builder(G))
@@ -503,7 +602,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -512,8 +611,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -527,7 +626,9 @@ def main():
                 got += measure_directions(name, builder, max(args.calls, 20))
             if "scan" in want:
                 got += measure_scan(name, builder, max(args.calls, 20))
-            if want - {"queries", "visibility", "features", "directions", "scan"}:
+            if "gather" in want:
+                got += measure_gather(name, builder, args.calls)
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
