@@ -237,6 +237,23 @@ pub use sys::lg_gather_out as GatherOut;
 /// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
 /// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
 pub fn radiance_gather_lanes(n_poses: usize, n_dirs: usize, lanes: i32) -> i32 { unsafe { sys::lg_radiance_gather_lanes(n_poses, n_dirs, lanes) } }
+/// A camera as the kernels read it (`lg_view`, 120 bytes): what `Accel::capture_views` renders from.
+pub use sys::lg_view as View;
+/// The view of a look-at camera (`lg_view_look_at`): what a scene's own camera holds after `set_perspective_camera(param)` (or
+/// `set_orthographic_camera(param)` with `perspective` false), `look_at` and `set_supersampling`, byte for byte.  No device is touched.
+pub fn view_look_at(perspective: bool, param: f64, origin: [f64; 3], look: [f64; 3], up: [f64; 3], supersampling: u8) -> View {
+    const _: () = assert!(std::mem::size_of::<sys::lg_view>() == 120);
+    let mut v: View = unsafe { std::mem::zeroed() };
+    let rc = unsafe { sys::lg_view_look_at(&mut v, perspective as i32, param, &origin, &look, &up, supersampling) };
+    if rc != 0 { panic!("lasgun: {}", last_error()) }
+    v
+}
+/// The scene's own camera as a view (`lg_scene_view`).  No device is touched.
+pub fn scene_view(scene: &Scene) -> View {
+    let mut v: View = unsafe { std::mem::zeroed() };
+    if unsafe { sys::lg_scene_view(scene.ptr, &mut v) } != 0 { panic!("lasgun: {}", last_error()) }
+    v
+}
 
 /// The rays of a lens over a width x height film, row-major pixels (or over the pixel slots `offsets` names), samples_root^2 per slot in
 /// idx = i*samples_root + j order: the layout `Accel::capture_rays` takes.  Generated on the current device.
@@ -473,6 +490,48 @@ impl<'s> Accel<'s> {
         if sys::lg_capture_rays_device(self.ptr, dev_rays, pixels, samples, dev_offsets, width, height, dev_rgba, dev_rgb, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
+    }
+    /// The camera of the scene this accel was built from, as a view (`lg_accel_view`): `capture_views` of it is `capture`'s film.
+    pub fn view(&self) -> View {
+        let mut v: View = unsafe { std::mem::zeroed() };
+        if unsafe { sys::lg_accel_view(self.ptr, &mut v) } != 0 { panic!("lasgun: {}", last_error()) }
+        v
+    }
+    /// `camera_rays` with `view` in the camera's place (`lg_view_rays`): the pixels [x0,x1) x [y0,y1) of a width x height film, row-major,
+    /// samples_root^2 rays a pixel in camera order.
+    pub fn view_rays(&self, view: &View, width: u32, height: u32, rect: (u32, u32, u32, u32)) -> Vec<[f64; 6]> {
+        let (x0, y0, x1, y1) = rect;
+        let n = (x1.saturating_sub(x0) as usize) * (y1.saturating_sub(y0) as usize) * (view.samples_root as usize) * (view.samples_root as usize);
+        let mut out = vec![[0f64; 6]; n];
+        let rc = unsafe { sys::lg_view_rays(self.ptr, view, width, height, x0, y0, x1, y1, if n == 0 { std::ptr::null_mut() } else { out.as_mut_ptr() as *mut f64 }) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        out
+    }
+    /// `view_rays` into device memory, enqueued on a HIP stream
+    ///
+    /// # Safety
+    /// `dev_rays` must be device memory of the accel's device holding the rectangle's rays, 6 doubles each.
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn view_rays_device(&self, view: &View, width: u32, height: u32, rect: (u32, u32, u32, u32), dev_rays: *mut f64, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_view_rays_device(self.ptr, view, width, height, rect.0, rect.1, rect.2, rect.3, dev_rays, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// This accel from K cameras into K width x height films in ONE call (`lg_capture_views`): film v is `pixels[v*width*height ..]`, its
+    /// f64 RGB before quantisation `rgb[v*width*height ..]`.  The views share samples_root.  Either output may be absent, not both.
+    pub fn capture_views(&self, views: &[View], width: u32, height: u32, pixels: Option<&mut [Pixel]>, rgb: Option<&mut [[f64; 3]]>) {
+        let n = views.len().checked_mul((width as usize) * (height as usize)).expect("capture_views: views.len() * width * height overflows usize");
+        assert!(pixels.as_ref().map_or(true, |p| p.len() == n) && rgb.as_ref().map_or(true, |r| r.len() == n), "capture_views: views.len() * width * height pixels");
+        let rc = unsafe {
+            sys::lg_capture_views(self.ptr, views.as_ptr(), views.len(), width, height, pixels.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u8),
+                                  rgb.map_or(std::ptr::null_mut(), |r| r.as_mut_ptr() as *mut f64))
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `capture_views` for films in device memory, enqueued on a HIP stream; `views` stays a host slice, copied before the call returns
+    ///
+    /// # Safety
+    /// `dev_rgba` / `dev_rgb` must be null or device memory of the accel's device holding views.len() * width * height RGBA8 words / RGB triples.
+    pub unsafe fn capture_views_device(&self, views: &[View], width: u32, height: u32, dev_rgba: *mut std::ffi::c_void, dev_rgb: *mut f64, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_capture_views_device(self.ptr, views.as_ptr(), views.len(), width, height, dev_rgba, dev_rgb, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     /// The number of materials of the accel's tables (`lg_accel_material_count`): the rows of `capture_features`' `material_rgb`.
     pub fn material_count(&self) -> usize { unsafe { sys::lg_accel_material_count(self.ptr) } }

@@ -276,6 +276,33 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                             rgb && !rgb->empty() ? (*rgb)[0].data() : nullptr, film.w(), film.h()))
             throw Error(lg_last_error());
     }
+    // views (lg_view, lg_capture_views): this accel from K cameras into K width x height films in ONE call -- film v at rgba[v*width*height*4],
+    // its f64 RGB before quantisation at (*rgb)[v*width*height]; the views share samples_root.  view(): the scene's own camera, whose film is
+    // capture()'s; lg_view_look_at makes others (View::look_at below).
+    lg_view view() const {
+        lg_view v{};
+        if (lg_accel_view(h_, &v)) throw Error(lg_last_error());
+        return v;
+    }
+    std::vector<std::array<double, 6>> view_rays(const lg_view &v, uint32_t width, uint32_t height) const {
+        static_assert(sizeof(lg_view) == 120, "lg_view: 15 doubles and two words, no padding");
+        std::vector<std::array<double, 6>> out((size_t)width * height * v.samples_root * v.samples_root);
+        if (lg_view_rays(h_, &v, width, height, 0, 0, width, height, out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
+        return out;
+    }
+    void view_rays_device(const lg_view &v, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *dev_rays, void *hip_stream) const {
+        if (lg_view_rays_device(h_, &v, width, height, x0, y0, x1, y1, dev_rays, hip_stream)) throw Error(lg_last_error());
+    }
+    void capture_views(const std::vector<lg_view> &views, uint32_t width, uint32_t height, std::vector<uint8_t> *rgba, std::vector<std::array<double, 3>> *rgb = nullptr) const {
+        const size_t n = views.size() * (size_t)width * height;
+        if (rgba) rgba->resize(n * 4);
+        if (rgb) rgb->resize(n);
+        if (lg_capture_views(h_, views.data(), views.size(), width, height, rgba && n ? rgba->data() : nullptr, rgb && n ? (*rgb)[0].data() : nullptr)) throw Error(lg_last_error());
+    }
+    // the same films enqueued into device memory on hip_stream (lg_capture_views_device); `views` stays a host array, copied before the call returns
+    void capture_views_device(const std::vector<lg_view> &views, uint32_t width, uint32_t height, void *dev_rgba, double *dev_rgb, void *hip_stream) const {
+        if (lg_capture_views_device(h_, views.data(), views.size(), width, height, dev_rgba, dev_rgb, hip_stream)) throw Error(lg_last_error());
+    }
     // feature buffers of the scene's own camera view (lg_capture_features): first-hit depth, shading normal, albedo, coverage and ids of the
     // pixels [x0,x1) x [y0,y1) of a width x height film, every plane addressed like the film (pixel y*width + x) and sized here when it is
     // too small; pixels outside the rectangle keep what the vectors held.  A null vector pointer = that plane is not asked for.
@@ -322,6 +349,22 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
   private:
     explicit Accel(lg_accel *a) : h_(a) {}
     lg_accel *h_;
+};
+
+// A view for Accel::capture_views from a look-at camera (lg_view_look_at): what a scene's own camera holds after set_perspective_camera(fov) /
+// set_orthographic_camera(scale), look_at and set_supersampling, byte for byte
+struct View {
+    static lg_view look_at(bool perspective, double param, Vec3 origin, Vec3 look, Vec3 up, uint8_t supersampling = 0) {
+        lg_view v{};
+        const double o[3] = {origin[0], origin[1], origin[2]}, l[3] = {look[0], look[1], look[2]}, u[3] = {up[0], up[1], up[2]};
+        if (lg_view_look_at(&v, perspective ? 1 : 0, param, o, l, u, supersampling)) throw Error(lg_last_error());
+        return v;
+    }
+    static lg_view of(const Scene &scene) {
+        lg_view v{};
+        if (lg_scene_view(scene.handle(), &v)) throw Error(lg_last_error());
+        return v;
+    }
 };
 
 // A lens camera the reference does not have (lg_lens, lg_lens_rays): an equirectangular panorama (kind 0) or an equidistant fisheye (kind 1)

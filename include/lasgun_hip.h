@@ -713,6 +713,61 @@ int lg_lens_rays(const lg_lens *, uint32_t width, uint32_t height, uint32_t samp
                  double *rays);
 int lg_lens_rays_device(int device, const lg_lens *, uint32_t width, uint32_t height, uint32_t samples_root,
                         const uint64_t *dev_pixel_offsets, size_t pixels, double *dev_rays, void *hip_stream);
+/* Views: one accel seen from other cameras than its scene's, K of them into K films in one call -- an orbit, a stereo pair, the six faces
+ * of a cube map, a light field, thumbnails -- without rebuilding the scene and the accel per camera and without writing 48 bytes a ray
+ * that a kernel makes from 15 doubles a view.  An EXTRA: no counterpart in the reference. */
+typedef struct lg_view {            /* a camera as the kernels read it: Camera's derived fields (camera.rs:6-37), used AS GIVEN */
+    double origin[3], view[3], up[3], aux[3];
+    double image_plane_height, pixel_separation;
+    uint32_t samples_root;          /* supersampling base + 1: samples per pixel = samples_root^2; 1 .. 256 */
+    uint32_t reserved;              /* must be 0 */
+} lg_view;                          /* 120 bytes, no padding */
+/* lg_view_look_at: the scene camera's own host code -- Camera::init(perspective, param), Camera::look_at(origin, look, up),
+ * Camera::set_supersampling(supersampling) -- run on a camera of its own; param is the fov in degrees for a perspective view and the
+ * scale for an orthographic one.  The result is, byte for byte, what lg_scene_view reports for a scene that received
+ * lg_scene_set_perspective_camera / lg_scene_set_orthographic_camera, lg_camera_look_at and lg_camera_set_supersampling, in this order,
+ * with the same arguments.  (The aperture radius is stored by the scene and used by nothing: a view has none.)  Device-free; an error
+ * (non-zero, lg_last_error) only for a NULL pointer.
+ * lg_scene_view / lg_accel_view: the scene's own camera as a view (of the scene the accel was built from); device-free.
+ * lg_view_rays*: lg_camera_rays* with the view in the camera's place -- the same pixel and sample order, the same 6 doubles, the same
+ * errors, and a samples_root of 0 or above 256 or reserved != 0; (x1-x0) * (y1-y0) * samples_root^2 rays.
+ * lg_capture_views*: film v starts at rgba + v*width*height*4 and its doubles at rgb + v*width*height*3; either output may be NULL, both
+ * NULL is an error.  The ray of (v, x, y, s) is Camera::sample's expression (camera.rs:113-146) over view v's fields, all f64, nothing
+ * contracted, in this order -- with winv = 1.0 / (double)width, hinv = 1.0 / (double)height, aspect = (double)width / (double)height
+ * (film.rs:40-42) and ss_distance = 1.0 / (double)samples_root:
+ *   plane_w = image_plane_height * aspect;  pixel = image_plane_height * hinv;  sep = ss_distance * pixel;
+ *   sox = ((double)x * winv - 0.5) * plane_w;  soy = (0.5 - (double)(y + 1) * hinv) * image_plane_height;
+ *   o = (origin + ((soy * pixel_separation) * up)) + ((sox * pixel_separation) * aux);
+ *   d = (view + (soy * up)) + (sox * aux);  updiff = up * sep;  auxdiff = aux * sep;  half = updiff * 0.5 + auxdiff * 0.5;
+ *   i = s / samples_root;  j = s % samples_root;  direction = ((d + ((double)j * updiff)) + ((double)i * auxdiff)) + half;  origin = o.
+ * A pixel's value is integrate()'s (integrate.rs:16-20): the samples' li() summed from zero in camera order (s = 0 .. S-1, S =
+ * samples_root^2), then multiplied by 1.0 / (double)S, then to_byte per channel with A = 255 (img.rs:65-67) and / or the three doubles
+ * before quantisation.  li() is lg_radiance's value for that ray, in the accel's traversal mode.  So for lg_accel_view's view the film is
+ * lg_capture's and the doubles are lg_capture_radiance(0, 1, ..)'s, bit for bit; for lg_view_look_at's view they are those of a scene
+ * rebuilt with that camera.  Non-finite fields are accepted as they are.  Every pixel of every film is written exactly once; nothing
+ * outside n_views*width*height elements is touched.
+ * views is a HOST array in both forms: it is copied before the call returns (through pinned staging, on the stream).
+ * Everything else is lg_capture_rays' contract: always the level-by-level pipeline, LASGUN_WF_BUDGET_MB chunks (of whole 8 x 8 pixel
+ * tiles x S; with S > 1 each chunk parks its samples and resolves them itself), one stream at a time per accel, the device form only
+ * enqueues, bar the usual growth of scratch.  lg_accel_set_query_order plays no part: there is no ray array.  n_views == 0 is a
+ * successful no-op.
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel; NULL views with n_views > 0; both outputs NULL;
+ * width or height 0; a samples_root of 0 or above 256; reserved != 0; views of one call that differ in samples_root (the uniform-samples
+ * rule); n_views * ceil(width/8) * ceil(height/8) * S > 2^32 - 1 (work tiles are counted in 32 bits, as the other queries' are); a byte
+ * size beyond SIZE_MAX; MORE THAN 32 LIGHTS or a recursion depth of 20 or more.  The device form adds: a pointer that is not device
+ * memory of the accel's device, dev_rgba not 4-byte aligned, dev_rgb not 8-byte aligned, a buffer that ends beyond its allocation. */
+int lg_view_look_at(lg_view *out, int perspective, double param, const double origin[3], const double look[3],
+                    const double up[3], uint8_t supersampling);
+int lg_scene_view(const lg_scene *, lg_view *out);     /* the scene's own camera as a view; device-free */
+int lg_accel_view(const lg_accel *, lg_view *out);     /* ... of the scene the accel was built from */
+int lg_view_rays(const lg_accel *, const lg_view *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t x1,
+                 uint32_t y1, double *rays);
+int lg_view_rays_device(const lg_accel *, const lg_view *, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0,
+                        uint32_t x1, uint32_t y1, double *dev_rays, void *hip_stream);
+int lg_capture_views(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
+                     uint8_t *rgba, double *rgb);                                   /* host arrays; synchronous */
+int lg_capture_views_device(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
+                            void *dev_rgba, double *dev_rgb, void *hip_stream);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.
  * Results are identical bytes either way, in the caller's order. Any other value: non-zero return, lg_last_error.
  * The walk keeps a wave's 64 rays in step; rays that arrive in no particular order (collision probes, visibility between arbitrary

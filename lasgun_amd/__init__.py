@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, CLens, CFeatures, CScanOut, CGatherOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, CView, CLens, CFeatures, CScanOut, CGatherOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -96,6 +96,7 @@ _EXTRA = {
     **RANGE_SCAN_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
+    **VIEWS_SIGNATURES,
 }
 
 
@@ -126,6 +127,18 @@ def Lens(kind, origin, right, up, forward, fov_deg=180.0):
     """An lg_lens: kind LENS_EQUIRECTANGULAR or LENS_FISHEYE, a basis used as given, and (fisheye) the full angle across the shorter side."""
     three = lambda v: (_C.c_double * 3)(*[float(c) for c in v])  # noqa: E731
     return CLens(int(kind), 0, three(origin), three(right), three(up), three(forward), float(fov_deg))
+
+
+View = CView  # lg_view (include/lasgun_hip.h): a camera as the kernels read it, 120 bytes -- view_look_at / api.scene_view / api.accel_view make them
+
+
+def _views(views):
+    """A sequence of View (or one View) as a contiguous ctypes array of them."""
+    vs = [views] if isinstance(views, CView) else list(views)
+    for v in vs:
+        if not isinstance(v, CView):
+            raise TypeError("views: View records (lasgun_amd.View)")
+    return (CView * len(vs))(*vs)
 
 
 def tile_order_offsets(w, h, tile=8):
@@ -905,6 +918,74 @@ class HipApi(Api):
         if self.call("camera_rays_device", accel.h, w, h, x0, y0, x1, y1, _C.c_void_p(int(rays_ptr)), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- views (include/lasgun_hip.h, lg_view_look_at .. lg_capture_views_device): one accel from K cameras into K films in one call
+    def view_look_at(self, origin, look, up, fov=None, scale=None, supersampling=0):
+        """The View of a perspective camera of `fov` degrees (or an orthographic one of `scale`) at `origin` looking at `look`: what a scene's
+        own camera holds after set_perspective_camera(fov) / set_orthographic_camera(scale), look_at and set_supersampling, byte for byte."""
+        if (fov is None) == (scale is None):
+            raise ValueError("view_look_at: fov (perspective) or scale (orthographic), one of them")
+        from ._capi import _v3
+        v = CView()
+        if self.call("view_look_at", _C.addressof(v), 1 if fov is not None else 0, float(fov if fov is not None else scale), _v3(origin), _v3(look), _v3(up),
+                     int(supersampling)):
+            raise LasgunError(self.last_error())
+        return v
+
+    def scene_view(self, scene):
+        """The scene's own camera as a View (no device is touched)."""
+        v = CView()
+        if self.call("scene_view", scene.h, _C.addressof(v)):
+            raise LasgunError(self.last_error())
+        return v
+
+    def accel_view(self, accel):
+        """The camera of the scene the accel was built from, as a View: capture_views(accel, [accel_view(accel)], w, h) is capture's film."""
+        v = CView()
+        if self.call("accel_view", accel.h, _C.addressof(v)):
+            raise LasgunError(self.last_error())
+        return v
+
+    def view_rays(self, accel, view, w, h, x0=0, y0=0, x1=None, y1=None):
+        """camera_rays with `view` in the camera's place: ((y1-y0) * (x1-x0) * samples_root^2, 6) float64, the same pixel and sample order."""
+        x1 = w if x1 is None else x1
+        y1 = h if y1 is None else y1
+        n = max(x1 - x0, 0) * max(y1 - y0, 0) * int(view.samples_root) ** 2
+        out = _np.zeros((n, 6), dtype=_np.float64)
+        if self.call("view_rays", accel.h, _C.addressof(view), w, h, x0, y0, x1, y1, out.ctypes.data if n else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def view_rays_device(self, accel, view, w, h, x0, y0, x1, y1, rays_ptr, stream=None):
+        if self.call("view_rays_device", accel.h, _C.addressof(view), w, h, x0, y0, x1, y1, _C.c_void_p(int(rays_ptr)), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def capture_views(self, accel, views, w, h, rgba=True, rgb=False, into=None):
+        """The accel's scene from K Views into K w x h films in ONE call: the (K, h, w, 4) uint8 films and / or the (K, h, w, 3) float64
+        radiance before quantisation (both: a pair).  The views share samples_root.  `into` = (films array or None, rgb array or None):
+        C-contiguous buffers of those shapes, written in place."""
+        tab = _views(views)
+        k = len(tab)
+        out_a, out_d = into if into is not None else (_np.zeros((k, h, w, 4), dtype=_np.uint8) if rgba else None,
+                                                      _np.zeros((k, h, w, 3), dtype=_np.float64) if rgb else None)
+        for o, dt, c in ((out_a, _np.uint8, 4), (out_d, _np.float64, 3)):
+            if o is not None and (o.dtype != dt or o.size != k * h * w * c or not o.flags["C_CONTIGUOUS"]):
+                raise ValueError("into: C-contiguous (K, h, w, 4) uint8 / (K, h, w, 3) float64")
+        if self.call("capture_views", accel.h, _C.addressof(tab) if k else None, k, int(w), int(h), out_a.ctypes.data if out_a is not None else None,
+                     out_d.ctypes.data if out_d is not None else None):
+            raise LasgunError(self.last_error())
+        if out_a is not None and out_d is not None:
+            return out_a, out_d
+        return out_a if out_a is not None else out_d
+
+    def capture_views_device(self, accel, views, w, h, rgba_ptr=None, rgb_ptr=None, stream=None):
+        """Enqueue the same K films into K*w*h RGBA8 words at rgba_ptr and / or K*w*h*3 doubles at rgb_ptr (device memory); `views` stays a
+        host sequence of View and is copied before the call returns."""
+        tab = _views(views)
+        ptr = lambda p: _C.c_void_p(int(p)) if p is not None else None  # noqa: E731
+        if self.call("capture_views_device", accel.h, _C.addressof(tab) if len(tab) else None, len(tab), int(w), int(h), ptr(rgba_ptr), ptr(rgb_ptr),
+                     self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     def camera_samples(self, accel):
         """Rays per pixel of lg_camera_rays (the camera's supersamples)."""
         return int(self.call("camera_samples", accel.h))
@@ -1038,6 +1119,41 @@ def frames_from_normals(normals):
     return _np.ascontiguousarray(_np.stack([t, s, n], axis=2))
 
 
+def view_look_at(origin, look, up, fov=None, scale=None, supersampling=0):
+    """api.view_look_at at package level: a View from a look-at camera (perspective `fov` degrees, or orthographic `scale`)."""
+    return api.view_look_at(origin, look, up, fov=fov, scale=scale, supersampling=supersampling)
+
+
+CUBE_FACES = (((1, 0, 0), (0, -1, 0)), ((-1, 0, 0), (0, -1, 0)), ((0, 1, 0), (0, 0, 1)), ((0, -1, 0), (0, 0, -1)), ((0, 0, 1), (0, -1, 0)), ((0, 0, -1), (0, -1, 0)))
+
+
+def cube_map_views(origin, supersampling=0):
+    """The six faces of a cube map around `origin`, in the order +X -X +Y -Y +Z -Z: face f is the perspective view of fov 90 degrees
+    view_look_at(origin, look=origin + axis_f, up=up_f), with the axes (1,0,0) (-1,0,0) (0,1,0) (0,-1,0) (0,0,1) (0,0,-1) and the ups
+    (0,-1,0) (0,-1,0) (0,0,1) (0,0,-1) (0,-1,0) (0,-1,0).  A convention of this WRAPPER, not of the C contract."""
+    o = [float(c) for c in origin]
+    return [view_look_at(o, [o[c] + float(axis[c]) for c in range(3)], up, fov=90.0, supersampling=supersampling) for axis, up in CUBE_FACES]
+
+
+def orbit_views(center, radius, elevation_deg, n, fov, up=(0, 1, 0), supersampling=0):
+    """n perspective views of `fov` degrees looking at `center` from eyes on a circle about the axis `up` through it: with u = up / |up|,
+    (t, s) = the first two columns of frames_from_normals(u) (so t, s, u is an orthonormal basis), e = radians(elevation_deg) and
+    a_k = 2 pi k / n, eye_k = center + radius * (cos(e) * (cos(a_k) * t + sin(a_k) * s) + sin(e) * u) and view k is
+    view_look_at(eye_k, center, up, fov=fov).  A convention of this WRAPPER, not of the C contract."""
+    c = _np.asarray(center, dtype=_np.float64).reshape(3)
+    u = _np.asarray(up, dtype=_np.float64).reshape(3)
+    u = u / _np.linalg.norm(u)
+    f = frames_from_normals(u)[0]
+    t, s = f[:, 0], f[:, 1]
+    e = _np.radians(float(elevation_deg))
+    views = []
+    for k in range(int(n)):
+        a = 2.0 * _np.pi * k / int(n)
+        eye = c + float(radius) * (_np.cos(e) * (_np.cos(a) * t + _np.sin(a) * s) + _np.sin(e) * u)
+        views.append(view_look_at(eye, c, up, fov=float(fov), supersampling=supersampling))
+    return views
+
+
 _share_torch_hip_runtime()
 api = HipApi(_C.CDLL(LIB_PATH), "lg_", _EXTRA)
 api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, material_rgb=None: api.capture_features(self, w, h, rect, planes, material_rgb)  # accel.features(w, h)
@@ -1045,6 +1161,7 @@ api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibili
 api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
+api.Accel.views = lambda self, views, w, h, rgba=True, rgb=False: api.capture_views(self, views, w, h, rgba, rgb)  # accel.views(views, w, h)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

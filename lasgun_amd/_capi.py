@@ -178,6 +178,23 @@ FEATURES_SIGNATURES = {
     "accel_material_count": (C.c_size_t, [C.c_void_p]),
 }
 
+# Views (include/lasgun_hip.h, lg_view_look_at .. lg_capture_views_device): one accel from K cameras into K films in one call; the GPU
+# library's alone.
+VIEWS_SIGNATURES = {
+    "view_look_at": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _D3, _D3, _D3, C.c_uint8]),
+    "scene_view": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "accel_view": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "view_rays": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + [C.c_void_p]),
+    "view_rays_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p]),
+    "capture_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "capture_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
+class CView(C.Structure):  # lg_view: 120 bytes, no padding
+    _fields_ = [("origin", _D3), ("view", _D3), ("up", _D3), ("aux", _D3), ("image_plane_height", C.c_double), ("pixel_separation", C.c_double),
+                ("samples_root", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 class CFeatures(C.Structure):  # lg_features: five plane pointers, 40 bytes; NULL = not asked for
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]

@@ -384,6 +384,26 @@ struct GatherArgs {
     uint32_t pose_lanes;           // 0: a tile is one pose x 64 directions; 1: 64 poses x one direction
 };
 
+// A view batch's level 0 (k_views.hip; lg_capture_views*).  DView: a camera as camera_ray() reads one (include/lasgun_hip.h, lg_view, plus
+// the ss_distance the host derives from samples_root: views_host.h) -- 16 doubles' worth, read through a wave-uniform index in the closest pass.
+struct DView {
+    V3 origin, view, up, aux;
+    double image_plane_height, pixel_separation, ss_distance;
+    uint32_t ss_root, pad;
+};
+// ... beside the DParams of its chunk (which carries the film size, winv / hinv / aspect, ss_root and ss_par): the table, the tiling of a
+// film, where the chunk starts and where the K films go.  Global pixel tile G = v * tiles_per_view + t; t an 8 x 8 tile of film v in row order.
+struct ViewArgs {
+    const DView *views;            // [n_views]
+    unsigned long long n_views;
+    uint32_t w, h;                 // every film's size
+    uint32_t tiles_x;              // ceil(w / 8)
+    uint32_t tiles_per_view;       // tiles_x * ceil(h / 8)
+    unsigned long long base_tile;  // the chunk's first global pixel tile: pixel tile t of the chunk is G = base_tile + t
+    uint32_t *rgba;                // K RGBA8 films, film v at v * w * h words; may be nullptr
+    double *rgb;                   // K films of 3 doubles a pixel, film v at v * w * h * 3; may be nullptr
+};
+
 // A lens camera (k_lens.hip; include/lasgun_hip.h, lg_lens -- the same 112 bytes)
 struct DLens {
     int32_t kind, reserved;          // 0 equirectangular panorama, 1 equidistant fisheye

@@ -66,6 +66,13 @@ hipError_t launch_gather_combine(const DParams &P, const GatherArgs &Q, uint32_t
 hipError_t launch_gather_resolve(const double *li, const double *weights, double *sums, unsigned long long n_poses, unsigned long long n_dirs, unsigned long long n_weights,
                                  uint32_t blocks, hipStream_t stream);
 hipError_t gather_set_lds_limit(size_t bytes, bool ldss);
+// k_views.hip: level 0 a fourth time, for the cameras of a view batch (launch.cpp, enqueue_view_batch), and the resolve pass of its chunks
+// (P.ntiles = the chunk's pixel tiles) where a pixel has several samples
+hipError_t launch_view_closest(const DParams &P, const ViewArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_view_shade(const DParams &P, const ViewArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_view_combine(const DParams &P, const ViewArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_view_resolve(const DParams &P, const ViewArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t view_set_lds_limit(size_t bytes, bool ldss);
 // k_lens.hip: the rays of a lens camera (lg_lens_rays*)
 hipError_t launch_lens_rays(const DLens &L, uint32_t w, uint32_t h, uint32_t root, const unsigned long long *offsets, unsigned long long n, double *rays,
                             uint32_t blocks, hipStream_t stream);
@@ -529,6 +536,9 @@ struct GatherCall {
     size_t batch_poses;                              // whole poses whose li is parked at a time (sums alone)
 };
 void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::LaunchCtx &c, hipStream_t stream);
+// One checked lg_capture_views* call (query.cpp; views_host.h): `views` is the HOST table, copied through pinned staging into a device table of
+// the call's own on `stream` before its launches; V.views and V.base_tile are set here
+void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

@@ -220,19 +220,35 @@ struct ChunkPlan {
     }
 };
 
+// Whose forms of level 0's three passes a chain of the level-by-level pipeline runs.  At most one is set: `rq` a radiance query's rays
+// (k_radiance.hip), `rf` a ray film's (its film forms), `rg` a radiance gather's, made in the kernel from two tables (k_gather.hip), `rv` a view
+// batch's, made in the kernel from a table of cameras (k_views.hip).  None: the scene's own camera (k_wavefront.hip) -- a render.
+struct Level0 {
+    const RadianceArgs *rq = nullptr;
+    const FilmArgs *rf = nullptr;
+    const GatherArgs *rg = nullptr;
+    const ViewArgs *rv = nullptr;
+    bool own() const { return rq || rf || rg || rv; }
+    hipError_t closest(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const {
+        return rv ? launch_view_closest(P, *rv, fast, blocks, depth, s) : rg ? launch_gather_closest(P, *rg, fast, blocks, depth, s) : rf ? launch_rf_closest(P, *rf, fast, blocks, depth, s)
+                                                                                                                                : launch_rq_closest(P, *rq, fast, blocks, depth, s);
+    }
+    hipError_t shade(const DParams &P, uint32_t blocks, hipStream_t s) const {
+        return rv ? launch_view_shade(P, *rv, blocks, s) : rg ? launch_gather_shade(P, *rg, blocks, s) : rf ? launch_rf_shade(P, *rf, blocks, s) : launch_rq_shade(P, *rq, blocks, s);
+    }
+    hipError_t combine(const DParams &P, uint32_t blocks, hipStream_t s) const {
+        return rv ? launch_view_combine(P, *rv, blocks, s) : rg ? launch_gather_combine(P, *rg, blocks, s) : rf ? launch_rf_combine(P, *rf, blocks, s) : launch_rq_combine(P, *rq, blocks, s);
+    }
+};
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
-// (`rq`: the launch is a radiance query's -- its level 0 is k_radiance.hip's; `rf`: a ray film's; `rg`: a radiance gather's, k_gather.hip's)
-static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr,
-                           const GatherArgs *rg = nullptr) {
+static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const Level0 &l0 = Level0()) {
     const unsigned long long n0 = plan.n0();
     const uint32_t flat_blocks0 = (uint32_t)(((unsigned long long)P.ntiles * 64ull + 255ull) / 256ull), flat_cap = a.cus * 16u; // (level 0: one thread per work item)
     for (uint32_t d = plan.levels - 1; d-- > 0;) {
         P.wf_level = d;
         P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
         P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-        if (d == 0 && rg) timed(a, 1, s, [&] { return launch_gather_combine(P, *rg, flat_blocks0, s); });
-        else if (d == 0 && rf) timed(a, 1, s, [&] { return launch_rf_combine(P, *rf, flat_blocks0, s); });
-        else if (d == 0 && rq) timed(a, 1, s, [&] { return launch_rq_combine(P, *rq, flat_blocks0, s); });
+        if (d == 0 && l0.own()) timed(a, 1, s, [&] { return l0.combine(P, flat_blocks0, s); });
         else timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
     }
 }
@@ -277,9 +293,8 @@ struct WfChunk {
         if (lds_resident(a)) set_lds_scene(a, P);
     }
     // One chain of launches on `ls`: the counters cleared, levels 0 .. L-1 top-down (closest, shadow, shade), the combine passes
-    // bottom-up.  `rq`: level 0's rays are a radiance query's (k_radiance.hip) instead of the camera's; `rf`: ... a ray film's (its film forms);
-    // `rg`: ... a radiance gather's, made in the kernel from two tables (k_gather.hip).
-    void run(const lg_accel &a, DParams &P, hipStream_t ls, const RadianceArgs *rq = nullptr, const FilmArgs *rf = nullptr, const GatherArgs *rg = nullptr) const {
+    // bottom-up.  `l0`: whose forms level 0's three passes take (Level0; none: the camera's).
+    void run(const lg_accel &a, DParams &P, hipStream_t ls, const Level0 &l0 = Level0()) const {
         const bool ldss = P.lds_image != nullptr;
         const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
         const uint32_t trace_cap = ldss ? a.ldss_blocks : (a.fast ? a.wf_blocks_fast : a.wf_blocks), flat_cap = a.cus * 16u;
@@ -301,23 +316,19 @@ struct WfChunk {
             // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
             // every deeper level may exceed only in waves, never in work per wave)
             const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
-            const bool rq0 = rq && d == 0, rf0 = rf && d == 0, rg0 = rg && d == 0;
+            const bool own0 = d == 0 && l0.own();
             level_params(d);
-            if (rg0) timed(a, 0, ls, [&] { return launch_gather_closest(P, *rg, a.fast, tb, depth, ls); });
-            else if (rf0) timed(a, 0, ls, [&] { return launch_rf_closest(P, *rf, a.fast, tb, depth, ls); });
-            else if (rq0) timed(a, 0, ls, [&] { return launch_rq_closest(P, *rq, a.fast, tb, depth, ls); });
+            if (own0) timed(a, 0, ls, [&] { return l0.closest(P, a.fast, tb, depth, ls); });
             else timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
             if (P.nlights > 0) {
                 level_params(d);
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
             }
             level_params(d);
-            if (rg0) timed(a, 3, ls, [&] { return launch_gather_shade(P, *rg, fb, ls); });
-            else if (rf0) timed(a, 3, ls, [&] { return launch_rf_shade(P, *rf, fb, ls); });
-            else if (rq0) timed(a, 3, ls, [&] { return launch_rq_shade(P, *rq, fb, ls); });
+            if (own0) timed(a, 3, ls, [&] { return l0.shade(P, fb, ls); });
             else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
-        combine_levels(a, P, L, plan, ls, rq, rf, rg);
+        combine_levels(a, P, L, plan, ls, l0);
     }
 };
 
@@ -403,6 +414,10 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
 // radiance[] -- the same chunks, the same launches with the film forms of the three level-0 kernels in place of the radiance forms.
 // `gather` (lg_radiance_gather*): there is no ray array -- level 0's work items are the gather's `gather_tiles` tiles, whose rays its own
 // forms of the three kernels make from two tables (k_gather.hip) and finish into gather->li; a chunk is told its first tile.
+// `views` (lg_capture_views*): there is no ray array either -- level 0's work items are the batch's `view_tiles` global pixel tiles x S samples
+// side by side, as a render's (enqueue_wavefront): the film size and samples_root go into the chunk's DParams, a chunk holds whole pixel tiles
+// x S and is told its first pixel tile, and with S > 1 each chunk's parked samples are resolved behind its chain (k_views.hip,
+// view_resolve_kernel; a combine pass, kind 1, as the render's resolve is).
 // `label` / `note`: what LASGUN_DEBUG calls the query and how it ends its line (a query's rays: the order they are walked in); `tail`: what
 // is enqueued behind the chunks inside the profiled span (a film's or a gather's resolve pass).
 struct Level0Source {
@@ -413,15 +428,18 @@ struct Level0Source {
     const uint32_t *perm = nullptr;
     const GatherArgs *gather = nullptr; // a radiance gather (base_tile is the chunk's to set)
     uint32_t gather_tiles = 0;
+    const ViewArgs *views = nullptr;    // a view batch (base_tile is the chunk's to set)
+    uint32_t view_tiles = 0, samples_root = 1;
     const char *label = "";
     std::string note;
 };
 static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_accel::LaunchCtx &c, hipStream_t stream, const std::function<void()> &tail = nullptr) {
-    DParams P0 = base_params(a, 1, 1);
-    P0.ss_root = 1; // (the scene's camera may be supersampled; a query is not)
-    P0.ntiles = src.gather ? src.gather_tiles : (uint32_t)((src.n + 63) / 64);
+    DParams P0 = src.views ? base_params(a, src.views->w, src.views->h) : base_params(a, 1, 1);
+    P0.ss_root = src.samples_root; // (the scene's camera may be supersampled; a query is not, and a view batch has its own samples_root)
+    const uint32_t S = P0.ss_root * P0.ss_root; // level-0 work items per pixel (views alone: > 1)
+    P0.ntiles = src.views ? src.view_tiles : src.gather ? src.gather_tiles : (uint32_t)((src.n + 63) / 64);
     const uint32_t levels = levels_of(a, P0);
-    ChunkPlan plan(a, P0, false, 1u, WfChunk::extra_per_item(levels));
+    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels));
     WfChunk K(plan);
     plan.fit([&] { K.carve(c); });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
@@ -432,21 +450,40 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
-        P.ntiles = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
-        P.ss_par = 1u;
+        const uint32_t chunk = (uint32_t)std::min<unsigned long long>(chunk_tiles, P0.ntiles - t0);
+        P.ntiles = chunk * S; // level 0's work tiles (at most the call's: 32 bits, views_host.h)
+        P.ss_par = S;
         K.params(a, P);
+        if (src.views) {
+            ViewArgs V = *src.views;
+            V.base_tile = t0;
+            Level0 l0;
+            l0.rv = &V;
+            K.run(a, P, stream, l0);
+            if (S > 1) {
+                DParams R = P;
+                R.ntiles = chunk;
+                timed(a, 1, stream, [&] { return launch_view_resolve(R, V, (uint32_t)(((unsigned long long)chunk * 64ull + 255ull) / 256ull), stream); });
+            }
+            continue;
+        }
         if (src.gather) {
             GatherArgs G = *src.gather;
             G.base_tile = t0;
-            K.run(a, P, stream, nullptr, nullptr, &G);
+            Level0 l0;
+            l0.rg = &G;
+            K.run(a, P, stream, l0);
             continue;
         }
         const RadianceArgs Q{src.rays, src.radiance, src.perm, (unsigned long long)src.n, t0 * 64ull};
+        Level0 l0;
+        FilmArgs F;
         if (src.film) {
-            FilmArgs F = *src.film;
+            F = *src.film;
             static_cast<RadianceArgs &>(F) = Q;
-            K.run(a, P, stream, &Q, &F);
-        } else K.run(a, P, stream, &Q);
+            l0.rf = &F;
+        } else l0.rq = &Q;
+        K.run(a, P, stream, l0);
     }
     if (tail) tail();
     span.end(a.events);
@@ -489,6 +526,44 @@ void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::L
             timed(a, 1, stream, [&] { return launch_gather_resolve(li, g.weights, sums, np, g.n_dirs, g.n_weights, blocks, stream); });
         });
     }
+}
+// A small host table on its way to the device for the launches a call enqueues next on `stream`: a buffer and pinned staging of its own in
+// the stream's launch context, released once the event that subsets_enqueued() records behind those launches is through (a call that
+// fails before that: subsets_abandoned()).  Tables whose launch is through go back to the pools here.
+static lg_accel::LaunchCtx::KsTable &live_table(lg_accel::LaunchCtx &c) {
+    for (size_t i = 0; i < c.ks_live.size();) {
+        if (c.ks_live[i]->done && hipEventQuery(c.ks_live[i]->done) == hipSuccess) {
+            (void)hipEventDestroy(c.ks_live[i]->done);
+            c.ks_live.erase(c.ks_live.begin() + (long)i);
+        } else ++i;
+    }
+    (void)hipGetLastError(); // (hipEventQuery's "not ready" is not an error of this call)
+    c.ks_live.emplace_back(new lg_accel::LaunchCtx::KsTable());
+    return *c.ks_live.back();
+}
+// A view batch (query.cpp, lg_capture_views*; the call checked there and in views_host.h): the K records go from the caller's host array
+// through pinned staging into a table of the call's own on the stream -- so the call only enqueues and the caller's array may be freed when
+// it returns --, then one level-0 query over the batch's pixel tiles.
+void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    static_assert(sizeof(DView) % sizeof(unsigned long long) == 0, "the table is staged as 64-bit words");
+    const size_t bytes = (size_t)V.n_views * sizeof(DView);
+    try {
+        lg_accel::LaunchCtx::KsTable &t = live_table(c);
+        t.stage.need(bytes);
+        std::memcpy(t.stage.p, views, bytes);
+        t.buf.alloc(std::max<size_t>(bytes / sizeof(unsigned long long), 128));
+        HIP_TRY(hipMemcpyAsync(t.buf.p, t.stage.p, bytes, hipMemcpyHostToDevice, stream));
+        V.views = reinterpret_cast<const DView *>(t.buf.p);
+        V.base_tile = 0;
+        Level0Source src;
+        src.views = &V;
+        src.view_tiles = (uint32_t)V.n_views * V.tiles_per_view; // (at most the call's work tiles: 32 bits)
+        src.samples_root = samples_root;
+        src.label = "view batch";
+        src.note = std::to_string(V.n_views) + " views of " + std::to_string(V.tiles_per_view) + " tiles x " + std::to_string(samples_root * samples_root) + " samples";
+        enqueue_level0_query(a, src, c, stream);
+        subsets_enqueued(a, stream);
+    } catch (...) { subsets_abandoned(a, stream); throw; }
 }
 // A ray film (query.cpp, lg_capture_rays*): `slots` pixel slots of `samples` rays each, slot g's rays [g*samples, (g+1)*samples), into
 // film.rgba / film.rgb at film.offsets[g] (or g).  One sample: the film forms of level 0 finish every ray where the radiance forms finish
@@ -918,17 +993,9 @@ SubsetBatch make_batch(const size_t *ks, size_t count, size_t n, uint32_t w, uin
 // the batch as addressing mode 3 on `stream` (its k table lives in the stream's launch context).  Caller holds a.mtx.
 void set_subsets(const lg_accel &a, DParams &P, const SubsetBatch &b, hipStream_t stream) {
     lg_accel::LaunchCtx &c = ctx_for(a, stream);
-    for (size_t i = 0; i < c.ks_live.size();) { // tables whose launch is through go back to the pool
-        if (c.ks_live[i]->done && hipEventQuery(c.ks_live[i]->done) == hipSuccess) {
-            (void)hipEventDestroy(c.ks_live[i]->done);
-            c.ks_live.erase(c.ks_live.begin() + (long)i);
-        } else ++i;
-    }
-    (void)hipGetLastError(); // (hipEventQuery's "not ready" is not an error of this call)
     // (a table whose launch was never enqueued -- the call failed between set_subsets and subsets_enqueued -- has no event to wait for:
     // subsets_abandoned() below takes it out again on that path)
-    c.ks_live.emplace_back(new lg_accel::LaunchCtx::KsTable());
-    lg_accel::LaunchCtx::KsTable &t = *c.ks_live.back();
+    lg_accel::LaunchCtx::KsTable &t = live_table(c);
     const size_t m_ = b.ks.size();
     t.stage.need(2 * m_ * sizeof(unsigned long long));
     unsigned long long *tab = static_cast<unsigned long long *>(t.stage.p); // the m values of k, then (k mod n) | (k / n) << 32 of each (the lattice form, shade.h mode 5)

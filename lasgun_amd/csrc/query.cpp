@@ -1,4 +1,4 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
 // k_visibility.hip, k_directions.hip, k_scan.hip and k_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
@@ -13,6 +13,7 @@
 #include "features_host.h"
 #include "gather_host.h"
 #include "scan_host.h"
+#include "views_host.h"
 #include "internal.h"
 
 static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hit, ng) == 32 && offsetof(lg_hit, ns) == 56 &&
@@ -532,6 +533,126 @@ extern "C" int lg_capture_rays_device(const lg_accel *a, const double *dev_rays,
     });
 }
 
+// the rectangle's rays: (x1-x0) * (y1-y0) * supersamples (the scene camera's, or a view's `root`^2); 0 for an empty rectangle
+static unsigned long long camera_ray_count(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t root = 0) {
+    if (w == 0 || h == 0 || x0 > x1 || y0 > y1 || x1 > w || y1 > h) throw Error("rectangle outside the film");
+    if (root == 0) root = a.scene->camera.ss_root;
+    return (unsigned long long)(x1 - x0) * (y1 - y0) * ((unsigned long long)root * root);
+}
+// (`view`: its fields in the camera's place -- camera_rays_kernel takes its camera from DParams)
+static void enqueue_camera_rays(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays,
+                                unsigned long long n, hipStream_t stream, const DView *view = nullptr) {
+    DParams P = base_params(a, w, h);
+    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
+    if (view) {
+        P.cam_origin = view->origin; P.cam_view = view->view; P.cam_up = view->up; P.cam_aux = view->aux;
+        P.image_plane_height = view->image_plane_height; P.pixel_separation = view->pixel_separation;
+        P.ss_distance = view->ss_distance; P.ss_root = view->ss_root;
+    }
+    const uint32_t blocks = (uint32_t)std::min<unsigned long long>((n + 255) / 256, (unsigned long long)a.cus * 64ull);
+    HIP_TRY(launch_camera_rays(P, rays, n, blocks, stream));
+}
+
+// ---- views (lg_view_look_at, lg_scene_view, lg_accel_view, lg_view_rays*, lg_capture_views*; launch.cpp, enqueue_view_batch; k_views.hip):
+// one accel from K cameras into K films.  The arithmetic that needs no device -- the tile count, the sizes, what a valid view is, the NULL
+// and alignment rules, lg_view -> DView -- is views_host.h's.
+static lg_view view_of(const Camera &c) {
+    lg_view v;
+    std::memset(&v, 0, sizeof v);
+    const V3 *from[4] = {&c.origin, &c.view, &c.up, &c.aux};
+    double *to[4] = {v.origin, v.view, v.up, v.aux};
+    for (int k = 0; k < 4; ++k) { to[k][0] = from[k]->x; to[k][1] = from[k]->y; to[k][2] = from[k]->z; }
+    v.image_plane_height = c.image_plane_height; v.pixel_separation = c.pixel_separation;
+    v.samples_root = c.ss_root;
+    return v;
+}
+extern "C" int lg_view_look_at(lg_view *out, int perspective, double param, const double origin[3], const double look[3], const double up[3], uint8_t supersampling) {
+    return guarded([&] {
+        if (!out || !origin || !look || !up) throw Error("view look_at: a NULL pointer");
+        Camera c; // the scene camera's own code, in the order a scene receives the three calls
+        c.init(perspective != 0, param);
+        c.look_at(V3{origin[0], origin[1], origin[2]}, V3{look[0], look[1], look[2]}, V3{up[0], up[1], up[2]});
+        c.set_supersampling(supersampling);
+        *out = view_of(c);
+    });
+}
+extern "C" int lg_scene_view(const lg_scene *s, lg_view *out) {
+    return guarded([&] {
+        if (!s || !out) throw Error("scene / out is NULL");
+        *out = view_of(s->s.camera);
+    });
+}
+extern "C" int lg_accel_view(const lg_accel *a, lg_view *out) {
+    return guarded([&] {
+        if (!a || !out) throw Error("accel / out is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        *out = view_of(a->scene->camera);
+    });
+}
+extern "C" int lg_view_rays(const lg_accel *a, const lg_view *view, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        if (!view) throw Error("view is NULL");
+        check_view(*view, 0);
+        const unsigned long long n = camera_ray_count(*a, w, h, x0, y0, x1, y1, view->samples_root);
+        if (n == 0) return;
+        if (!rays) throw Error("rays is NULL");
+        const DView dv = to_dview(*view);
+        std::lock_guard<std::mutex> g(a->mtx);
+        RoundTrip trip(*a);
+        double *d = trip.out(rays, n * 6);
+        trip.run([&] { enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, d, n, a->stream, &dv); });
+    });
+}
+extern "C" int lg_view_rays_device(const lg_accel *a, const lg_view *view, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *dev_rays,
+                                   void *hip_stream) {
+    return guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        if (!view) throw Error("view is NULL");
+        check_view(*view, 0);
+        const unsigned long long n = camera_ray_count(*a, w, h, x0, y0, x1, y1, view->samples_root);
+        if (n == 0) return;
+        const DView dv = to_dview(*view);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        enqueue_camera_rays(*a, w, h, x0, y0, x1, y1, dev_rays, n, (hipStream_t)hip_stream, &dv);
+    });
+}
+// One batch enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call, the scene and the buffers)
+static void enqueue_views(const lg_accel &a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, const ViewShape &shape, uint32_t *rgba, double *rgb, hipStream_t stream) {
+    check_queue_error(a);
+    const std::vector<DView> table = to_dviews(views, n_views);
+    const ViewArgs V{nullptr, (unsigned long long)n_views, w, h, shape.tiles_x, shape.tiles_per_view, 0ull, rgba, rgb};
+    enqueue_view_batch(a, table.data(), V, shape.samples_root, ctx_for(a, stream), stream);
+}
+// Host form: the K films come back into staging and reach the caller's arrays after the synchronise (an error on the way leaves them as they were)
+extern "C" int lg_capture_views(const lg_accel *a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, uint8_t *rgba, double *rgb) {
+    return guarded([&] {
+        if (n_views == 0) return;
+        const ViewShape shape = check_views(a, views, n_views, w, h, rgba, rgb);
+        std::lock_guard<std::mutex> g(a->mtx);
+        radiance_possible(*a);
+        RoundTrip trip(*a);
+        uint8_t *drgba = trip.staged(rgba, shape.pixels * 4);
+        double *drgb = trip.staged(rgb, shape.pixels * 3);
+        trip.run([&] { enqueue_views(*a, views, n_views, w, h, shape, reinterpret_cast<uint32_t *>(drgba), drgb, a->stream); });
+    });
+}
+extern "C" int lg_capture_views_device(const lg_accel *a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, void *dev_rgba, double *dev_rgb, void *hip_stream) {
+    return guarded([&] {
+        if (n_views == 0) return;
+        const ViewShape shape = check_views(a, views, n_views, w, h, dev_rgba, dev_rgb);
+        check_views_alignment(dev_rgba, dev_rgb);
+        std::lock_guard<std::mutex> g(a->mtx);
+        radiance_possible(*a);
+        use_device(a->device);
+        if (dev_rgba) check_device_buffer(*a, dev_rgba, shape.pixels * 4, 4, "rgba");
+        if (dev_rgb) check_device_buffer(*a, dev_rgb, shape.pixels * 3 * sizeof(double), 8, "rgb");
+        enqueue_views(*a, views, n_views, w, h, shape, reinterpret_cast<uint32_t *>(dev_rgba), dev_rgb, (hipStream_t)hip_stream);
+    });
+}
+
 // ---- feature buffers (lg_capture_features*; k_features.hip): depth, normal, albedo, coverage and ids of the camera's primary hits.  The
 // struct handling that needs no device is features_host.h's.
 // One capture enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the rectangle and the buffers):
@@ -598,20 +719,6 @@ static void enqueue_lens_rays(const lg_lens *lens, uint32_t w, uint32_t h, uint3
     std::memcpy(&L, lens, sizeof L);
     const uint32_t blocks = (uint32_t)std::min<unsigned long long>((n + 255) / 256, 16384ull);
     HIP_TRY(launch_lens_rays(L, w, h, root, reinterpret_cast<const unsigned long long *>(dev_offsets), n, dev_rays, blocks, stream));
-}
-
-// the rectangle's rays: (x1-x0) * (y1-y0) * supersamples; 0 for an empty rectangle
-static unsigned long long camera_ray_count(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
-    if (w == 0 || h == 0 || x0 > x1 || y0 > y1 || x1 > w || y1 > h) throw Error("rectangle outside the film");
-    const unsigned long long S = (unsigned long long)a.scene->camera.ss_root * a.scene->camera.ss_root;
-    return (unsigned long long)(x1 - x0) * (y1 - y0) * S;
-}
-static void enqueue_camera_rays(const lg_accel &a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, double *rays,
-                                unsigned long long n, hipStream_t stream) {
-    DParams P = base_params(a, w, h);
-    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
-    const uint32_t blocks = (uint32_t)std::min<unsigned long long>((n + 255) / 256, (unsigned long long)a.cus * 64ull);
-    HIP_TRY(launch_camera_rays(P, rays, n, blocks, stream));
 }
 
 extern "C" {

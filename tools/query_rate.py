@@ -49,7 +49,13 @@ gx1, pose-major, which is direction lanes' own order and the caller's natural on
 lanes' own order.  Every gather's sums are checked against the sequential sum of gx1's radiance (torch: a product and a sum a step).  Each row
 carries kind1_ms, what lg_profile_read_kinds credits to kind 1 in one profiled call (the level combine passes, and for g1 / g2 the resolve);
 resolve_ms = a g row's kind1_ms minus its yardstick's is the resolve's own time.  These rows time --calls calls as given (at least 3), not 20.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather[,...]] [--out profiles/r08_query_order.jsonl]
+View batches (lg_capture_views_device) -- --rows views (not part of "all"), two shapes a scene, RGBA8 films.  Shape A: 64 orbit_views of 128 x 128
+at one sample -- the scene's own eye and 63 more on the circle through it about the camera's up, looking at the camera's look point with its
+field of view.  Shape B: the scene's own view at 4096 x 4096.  Row v: the batch, one call.  Beside it, both the parent commit's own
+capabilities: row vk, lg_capture_subset_device(0, 1, ..) on K accels rebuilt per camera, K render chains on one stream (the K scene + accel
+builds are timed apart, host wall clock: build_ms); row vx8, lg_capture_rays_device on the views' rays written out in 8 x 8-tile order through
+pixel_offsets (the rays' construction not timed).  Every row's films are checked against row v's bytes.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -530,6 +536,71 @@ def measure_gather(name, builder, calls):
     return out
 
 
+_VIEW_ACCELS = {}  # scene name -> (the K rebuilt accels of shape A, their build's wall-clock ms): built once, whatever --repeats says
+
+
+def measure_views(name, builder, calls):
+    """Rows v / vk / vx8 of one scene in both shapes (module docstring)."""
+    import math
+    import numpy as np
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    own = G.accel_view(accel)
+    eye, view, up = (np.array(v[:]) for v in (own.origin, own.view, own.up))
+    center, radius = eye + view, float(np.linalg.norm(view))
+    fov = math.degrees(2.0 * math.atan(own.image_plane_height / (2.0 * radius)))
+    K = 64
+    orbit = [la.view_look_at(eye, center, up, fov=fov)] + la.orbit_views(center, radius, 0.0, K, fov, up=up)[1:]
+    if name not in _VIEW_ACCELS:
+        t0 = time.time()
+        accels = []
+        for v in orbit:
+            scene = builder(G)
+            scene.set_perspective_camera(fov).look_at(list(v.origin[:]), list(center), list(up))
+            accels.append(G.Accel.from_scene(scene))
+        _VIEW_ACCELS[name] = (accels, (time.time() - t0) * 1e3)
+    rebuilt, build_ms = _VIEW_ACCELS[name]
+    out = []
+    for shape, views, w, h, chain in (("A: 64 orbit views x 128 x 128", orbit, 128, 128, rebuilt), ("B: 1 view x 4096 x 4096", [own], 4096, 4096, [accel])):
+        k, npix = len(views), w * h
+        S_ = int(views[0].samples_root) ** 2
+        films = torch.zeros((k * npix * 4,), dtype=torch.uint8, device="cuda")
+        rows = []
+        call = lambda: G.capture_views_device(accel, views, w, h, rgba_ptr=films.data_ptr(), stream=s)  # noqa: E731
+        rows.append(("v: view batch, one call", timed(call, calls, 2), None))
+        torch.cuda.synchronize()
+        want = films.clone()
+        # K render chains on K accels rebuilt per camera (the organisation each accel's own choice picks)
+        call = lambda: [G.capture_subset_device(0, 1, a, w, h, films.data_ptr() + 4 * npix * i, stream=s) for i, a in enumerate(chain)]  # noqa: E731
+        films.zero_()
+        ms = timed(call, calls, 8)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(films, want))
+        orgs = sorted({str(G.last_organisation(a)) for a in chain})
+        rows.append(("vk: lg_capture_subset_device on K rebuilt accels, K render chains", ms, {"build_ms": round(build_ms, 1) if k > 1 else None, "organisations": orgs,
+                                                                                           "same_bytes": same}))
+        # the views' rays written out in 8 x 8-tile order, one ray film over the K films stacked
+        n = k * npix * S_
+        rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+        for i, v in enumerate(views):
+            G.view_rays_device(accel, v, w, h, 0, 0, w, h, rays.data_ptr() + 48 * npix * S_ * i, stream=s)
+        tiles = torch.from_numpy(la.tile_order_offsets(w, h).view(np.int64)).cuda()
+        offs = (torch.arange(k, device="cuda")[:, None] * npix + tiles[None, :]).contiguous().view(-1)
+        tiled = rays.view(k * npix, S_, 6)[offs].contiguous().view(n, 6)
+        del rays
+        films.zero_()
+        call = lambda: G.capture_rays_device(accel, k * npix, tiled.data_ptr(), w, h * k, samples=S_, offsets_ptr=offs.data_ptr(), rgba_ptr=films.data_ptr(), stream=s)  # noqa: E731
+        ms = timed(call, calls, 2)
+        torch.cuda.synchronize()
+        rows.append(("vx8: lg_capture_rays_device on the views' rays in 8x8-tile order with pixel_offsets", ms, {"same_bytes": bool(torch.equal(films, want))}))
+        del tiled, offs, films, want
+        out += [{"scene": name, "shape": shape, "row": row, "views": k, "film": [w, h], "samples": S_, "rays": n, "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1),
+                 **(extra or {}), "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel),
+                 "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, extra in rows]
+    return out
+
+
 def measure_features(name, builder, size, calls):
     """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
     accel = G.Accel.from_scene(builder(G))
@@ -602,7 +673,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -611,8 +682,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -628,7 +699,9 @@ def main():
                 got += measure_scan(name, builder, max(args.calls, 20))
             if "gather" in want:
                 got += measure_gather(name, builder, args.calls)
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather"}:
+            if "views" in want:
+                got += measure_views(name, builder, max(args.calls, 3))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
