@@ -253,6 +253,17 @@ int lg_accel_set_shadow_skip(const lg_accel *, int enabled);
  * counting forms (lg_capture_stats*, lg_trace_pixel*) and the fast mode never take them.  3 (default): both; 0 .. 3: as given (A/B, tests;
  * LASGUN_LEVEL_DOOR=0..3 masks every accel's setting).  Same bytes, hit records and visibility bits with every mask. */
 int lg_accel_set_level_door(const lg_accel *, int mask);
+/* Level-by-level pipeline, level 0's closest pass over an LDS-resident scene: every ray of a perspective camera leaves from the same point,
+ * so the workgroup that has copied the scene into LDS subtracts that point from the node boxes and sphere centres once, in LDS, instead of
+ * every lane at every test -- the same subtraction on the same bits.  Taken only where that holds in every bit: a
+ * perspective camera (pixel_separation == 0) whose origin, and whose origin in every accel's local space, is finite with no -0 component,
+ * finite up / aux, at most 16 accels, the plain exact walk.  1 (default): on; 0: the absolute form (A/B, tests; LASGUN_L0_RELATIVE=0 does
+ * the same for every accel).  Same bytes either way.  lg_accel_last_l0_relative: the form the last such launch took (1 / 0; -1 before the
+ * first).  lg_scene_l0_relative_origins: the device-free part of the gate for a scene and its own camera -- returns the number of accels and
+ * writes the camera's origin in each accel's local space to origins[3 * accel ..] (at most `cap` accels), 0 where the gate says no, -1 on an error. */
+int lg_accel_set_l0_relative(const lg_accel *, int enabled);
+int lg_accel_last_l0_relative(const lg_accel *);
+int lg_scene_l0_relative_origins(const lg_scene *, double *origins, int cap);
 int lg_accel_get_prune(const lg_accel *); /* the effective setting (accel default, LASGUN_PRUNE, lg_accel_set_prune, fast mode): 0 / 1 */
 
 /* Kernel organisation (same arithmetic, same bytes either way).  1 (default): the organisation of a launch is MEASURED -- the SECOND

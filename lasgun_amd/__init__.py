@@ -41,6 +41,9 @@ _EXTRA = {
     "accel_set_prune": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_shadow_skip": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_set_level_door": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_set_l0_relative": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_last_l0_relative": (_C.c_int, [_C.c_void_p]),
+    "scene_l0_relative_origins": (_C.c_int, [_C.c_void_p, _C.POINTER(_C.c_double), _C.c_int]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
     "accel_last_organisation": (_C.c_int, [_C.c_void_p]),
@@ -189,6 +192,27 @@ class HipApi(Api):
         (default 3; same results with every mask; include/lasgun_hip.h, lg_accel_set_level_door)."""
         if self.call("accel_set_level_door", accel.h, int(mask)):
             raise LasgunError(self.last_error())
+
+    def set_l0_relative(self, accel, enabled):
+        """Level-by-level pipeline, level 0's closest pass over an LDS-resident scene: node boxes and sphere slots held relative to the camera's
+        origin where every ray of the launch shares it (default on; same bytes either way; include/lasgun_hip.h, lg_accel_set_l0_relative)."""
+        if self.call("accel_set_l0_relative", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def last_l0_relative(self, accel):
+        """The form the last level-0 closest launch of the level-by-level pipeline took: True origin-relative, False absolute; None before the first."""
+        v = self.call("accel_last_l0_relative", accel.h)
+        return None if v < 0 else bool(v)
+
+    def l0_relative_origins(self, scene):
+        """The device-free part of that form's gate for a scene and its camera: the camera's origin in every accel's local space, (accels, 3)
+        float64, or None where the gate says no (include/lasgun_hip.h, lg_scene_l0_relative_origins)."""
+        import numpy as np
+        out = np.zeros((64, 3), dtype=np.float64)
+        n = self.call("scene_l0_relative_origins", scene.h, out.ctypes.data_as(_C.POINTER(_C.c_double)), 64)
+        if n < 0:
+            raise LasgunError(self.last_error())
+        return out[:n].copy() if n else None
 
     def last_organisation(self, accel):
         """What the accel's last launch ran as: "megakernel", "wavefront" (level by level), "queue"; None before the first."""

@@ -139,23 +139,39 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
             uint32_t nn = 0, np = 0;
             // compact numbering: the non-mesh accels first (their slots get a leaf record in the image), then the meshes
             uint32_t np_soup = 0; // slots of the non-mesh accels
-            for (int pass = 0; pass < 2; ++pass) {
-              if (pass == 1) np_soup = np;
-              for (DAccel &A : fm.accels) {
-                if (((A.flags & AF_MESH) != 0u) != (pass == 1)) continue;
-                auto fn = std::find_if(nruns.begin(), nruns.end(), [&](auto &r) { return r.first == A.node_base; });
-                if (fn == nruns.end()) { nruns.emplace_back(A.node_base, nn); A.lnode_base = nn; nn += extent(nb, A.node_base, fm.nodes.size()); }
-                else A.lnode_base = fn->second;
-                auto fp = std::find_if(pruns.begin(), pruns.end(), [&](auto &r) { return r.first == A.prim_base; });
-                if (fp == pruns.end()) { pruns.emplace_back(A.prim_base, np); A.lprim_base = np; np += extent(pb, A.prim_base, fm.primref.size()); }
-                else A.lprim_base = fp->second;
-              }
-            }
             const size_t stack_bytes = (size_t)a->stack_depth * 1024 * 4; // per-lane stacks of the private walks
-            const size_t prim16 = ((size_t)np + 3) / 4;
-            // image: [nodes, LDS_NODE_STRIDE units each][primrefs][leaf records, 3 units per slot][accel records]
             const size_t accel16 = fm.accels.size() * LDS_ACCEL_UNITS;
-            const size_t n16 = (size_t)nn * LDS_NODE_STRIDE + prim16 + (size_t)np_soup * 3 + accel16;
+            // image: [nodes, LDS_NODE_STRIDE units each][primrefs][leaf records, 3 units per slot][accel records]
+            // `own_trees`: every accel gets node records of its own -- instances of one mesh (the five walls of the Cornell shell are one
+            // two-triangle plane) otherwise share a tree, and the level-0 closest pass's origin-relative form (k_wavefront.hip, l0_rewrite)
+            // rewrites a tree relative to ITS accel's local origin, which differs from instance to instance.  Same records, same walk words
+            // up to each copy's own base; the primrefs stay shared (a mesh's slots are triangles: never rewritten).
+            auto number = [&](bool own_trees) {
+                nruns.clear(); pruns.clear(); nn = np = np_soup = 0;
+                for (int pass = 0; pass < 2; ++pass) {
+                  if (pass == 1) np_soup = np;
+                  for (DAccel &A : fm.accels) {
+                    if (((A.flags & AF_MESH) != 0u) != (pass == 1)) continue;
+                    auto fn = own_trees ? nruns.end() : std::find_if(nruns.begin(), nruns.end(), [&](auto &r) { return r.first == A.node_base; });
+                    if (fn == nruns.end()) { nruns.emplace_back(A.node_base, nn); A.lnode_base = nn; nn += extent(nb, A.node_base, fm.nodes.size()); }
+                    else A.lnode_base = fn->second;
+                    auto fp = std::find_if(pruns.begin(), pruns.end(), [&](auto &r) { return r.first == A.prim_base; });
+                    if (fp == pruns.end()) { pruns.emplace_back(A.prim_base, np); A.lprim_base = np; np += extent(pb, A.prim_base, fm.primref.size()); }
+                    else A.lprim_base = fp->second;
+                  }
+                }
+                return (size_t)nn * LDS_NODE_STRIDE + ((size_t)np + 3) / 4 + (size_t)np_soup * 3 + accel16;
+            };
+            size_t n16 = number(false);
+            // The copies are paid by every launch of every LDS-resident kernel (each workgroup copies the image once per launch), so they are
+            // made only where they are small change: at most 1/16 on top of the shared image, and only for a scene the form can serve at all.
+            if (fm.accels.size() <= L0_REL_MAX_ACCELS && nruns.size() < fm.accels.size()) {
+                const size_t shared16 = n16, own16 = number(true);
+                if (stack_bytes + own16 * 16 > LDS_MAX || (own16 - shared16) * 16 > shared16) n16 = number(false);
+                else n16 = own16;
+            }
+            const size_t prim16 = ((size_t)np + 3) / 4;
+            a->l0_rel.clear();
             if (stack_bytes + n16 * 16 <= LDS_MAX) {
                 std::vector<uint32_t> img(n16 * 4, 0u);
                 a->lds_node_off = 0;
@@ -195,6 +211,25 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
                     for (int k = 0; k < MAX_CHAIN; ++k) rec[32 + k] = A.chain[k];
                     std::memcpy(rec + 40, A.prune, sizeof A.prune);
                     std::memcpy(rec + LDS_ACCEL_DOOR * 4, A.door, sizeof A.door);
+                }
+                // the origin-relative form's ranges (DRelAccel): offered only when no record would be rewritten for two accels
+                if (fm.accels.size() <= L0_REL_MAX_ACCELS) {
+                    bool own = true;
+                    for (size_t i = 0; i < fm.accels.size(); ++i)
+                        for (size_t j = 0; j < i; ++j) {
+                            const DAccel &A = fm.accels[i], &B = fm.accels[j];
+                            own = own && A.lnode_base != B.lnode_base && (((A.flags | B.flags) & AF_MESH) != 0u || A.lprim_base != B.lprim_base);
+                        }
+                    for (const DAccel &A : fm.accels) {
+                        DRelAccel r{};
+                        r.node_off = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
+                        r.node_n = extent(nb, A.node_base, fm.nodes.size());
+                        r.slot0 = A.lprim_base;
+                        r.slot_n = (A.flags & AF_MESH) ? 0u : extent(pb, A.prim_base, fm.primref.size());
+                        own = own && (size_t)r.node_off + (size_t)r.node_n * LDS_NODE_STRIDE * 16u <= (size_t)a->lds_prim_off * 16u && r.slot0 + r.slot_n <= np_soup;
+                        a->l0_rel.push_back(r);
+                    }
+                    if (!own) a->l0_rel.clear();
                 }
                 stage.add(a->lds_image, img);
                 a->lds_image_n16 = (uint32_t)n16;
@@ -274,7 +309,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.lds_image, y.lds_image); swap(x.accel_image, y.accel_image); swap(x.accel_image_n16, y.accel_image_n16);
     swap(x.lds_image_n16, y.lds_image_n16); swap(x.lds_node_off, y.lds_node_off); swap(x.lds_prim_off, y.lds_prim_off);
     swap(x.lds_soup_off, y.lds_soup_off); swap(x.lds_accel_off, y.lds_accel_off);
-    swap(x.ldss_blocks, y.ldss_blocks); swap(x.cus, y.cus);
+    swap(x.ldss_blocks, y.ldss_blocks); swap(x.cus, y.cus); swap(x.l0_rel, y.l0_rel);
     swap(x.stack_depth, y.stack_depth); swap(x.stack_depth_fast1, y.stack_depth_fast1); swap(x.max_blocks, y.max_blocks); swap(x.max_blocks_fast, y.max_blocks_fast);
     swap(x.wf_blocks, y.wf_blocks); swap(x.wf_blocks_fast, y.wf_blocks_fast); swap(x.queue_blocks, y.queue_blocks);
     swap(x.queue_default, y.queue_default); swap(x.prune_default, y.prune_default); swap(x.queue_min_items, y.queue_min_items); swap(x.specular_small_items, y.specular_small_items);

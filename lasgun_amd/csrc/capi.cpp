@@ -719,6 +719,32 @@ int lg_accel_set_level_door(const lg_accel *a, int mask) {
     a->level_door = (uint32_t)mask;
     return 0;
 }
+int lg_accel_set_l0_relative(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("l0 relative must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->l0_relative = enabled == 1;
+    return 0;
+}
+int lg_accel_last_l0_relative(const lg_accel *a) { // the form the last level-0 closest launch of the level-by-level pipeline took: 1 origin-relative, 0 absolute; -1 before the first
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->last_l0_relative;
+}
+// The device-free part of that form's gate for a scene and its own camera (host.cpp, l0_relative_camera / l0_relative_origins): the number
+// of accels, and the camera's origin in each accel's local space in origins[3 * accel ..] (at most `cap` accels are written), when the
+// camera's rays share one origin that is the same bits in every accel's frame of every lane; 0 when they do not; -1 on an error.
+int lg_scene_l0_relative_origins(const lg_scene *s, double *origins, int cap) {
+    int n = 0;
+    int rc = guarded([&] {
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        const Camera &c = s->s.camera;
+        std::vector<V3> local;
+        if (!l0_relative_camera(c.origin, c.up, c.aux, c.pixel_separation) || !l0_relative_origins(f, c.origin, local)) return;
+        n = (int)local.size();
+        for (int i = 0; i < n && i < cap && origins; ++i) { origins[3 * i] = local[(size_t)i].x; origins[3 * i + 1] = local[(size_t)i].y; origins[3 * i + 2] = local[(size_t)i].z; }
+    });
+    return rc ? -1 : n;
+}
 int lg_accel_set_mode(const lg_accel *a, int mode) {
     if (mode != 0 && mode != 1) return fail("mode must be 0 (reference traversal) or 1 (fast)");
     std::lock_guard<std::mutex> g(a->mtx);

@@ -214,6 +214,18 @@ constexpr int STASH_DOUBLES = 13; // p(3) ng(3) ns(3) ss(3) material id
 
 struct DRowTab { uint32_t base, rem; }; // a film row's floor(y*w / n) and (y*w) mod n (strided subsets by lattice column: shade.h, modes 4 / 5)
 
+// The level-0 closest pass in its origin-relative form (k_wavefront.hip, l0_rewrite; walk.h, traverse_ref<.., REL>): one
+// record per accel of a scene of at most L0_REL_MAX_ACCELS -- the accel's own node records and (non-mesh accels) leaf slots in the LDS
+// image, and the camera's origin in the accel's local space, which is the same bits for every ray of the launch (host.cpp, l0_relative_table).
+constexpr uint32_t L0_REL_MAX_ACCELS = 16u;
+struct DRelAccel {
+    double o[3];       // local origin of every level-0 ray in this accel
+    uint32_t node_off; // byte offset of its first node record in the image
+    uint32_t node_n;   // its node records
+    uint32_t slot0;    // its first leaf slot (compact numbering), ...
+    uint32_t slot_n;   // ... and how many carry a 48-byte leaf record (0 for a mesh accel: triangles stay absolute)
+};
+
 struct DParams {
     // ---- scene tables
     const DNode *nodes;
@@ -351,7 +363,12 @@ struct DParams {
     // (lg_accel_set_shadow_skip, LASGUN_SHADOW_SKIP), the scene has 1 .. 32 lights and PI * intensity is finite for every one of them.
     uint32_t shadow_skip;
     uint32_t level_door; // LEVEL_DOOR_* bits (lg_accel_set_level_door, LASGUN_LEVEL_DOOR; default: both)
+    // level-0 closest pass of the level-by-level pipeline, LDS-resident scene: the number of accels when the launch takes the
+    // origin-relative form, 0 for the absolute form (launch.cpp, l0_relative: the gate); set for that one launch alone
+    uint32_t l0_rel_n;
+    DRelAccel l0_rel[L0_REL_MAX_ACCELS];
 };
+static_assert(sizeof(DParams) <= 4096, "DParams is passed by value: a kernel's arguments are at most 4 KB");
 
 // A radiance query's level 0 (k_radiance.hip), beside the DParams of its chunk: the caller's buffers and where the chunk starts
 struct RadianceArgs {

@@ -1505,6 +1505,39 @@ void level_door_records(FlatScene &out) {
     }
 }
 
+// ---- the level-0 closest pass's origin-relative form: what the host can say without a device (host.h)
+// finite and not -0: the values x for which x + (+-0) is x and ((1*x + 0*y) + 0*z) + 0*1 is x, bit for bit
+static bool l0_plain(double x) { return std::isfinite(x) && !(x == 0.0 && std::signbit(x)); }
+static bool l0_plain(const V3 &v) { return l0_plain(v.x) && l0_plain(v.y) && l0_plain(v.z); }
+// camera_ray (shade.h): cam_o = origin + ((soy * pixel_separation) * up) + ((sox * pixel_separation) * aux), soy and sox finite.  With
+// pixel_separation == 0 (a perspective camera) and finite up / aux both products are vectors of zeros of either sign, and x + (+-0) is x
+// for every x but -0 ((-0) + (+0) = +0: such an origin would differ from pixel to pixel).
+bool l0_relative_camera(const V3 &origin, const V3 &up, const V3 &aux, double pixel_separation) {
+    const bool finite = std::isfinite(up.x) && std::isfinite(up.y) && std::isfinite(up.z) && std::isfinite(aux.x) && std::isfinite(aux.y) && std::isfinite(aux.z);
+    return pixel_separation == 0.0 && finite && l0_plain(origin);
+}
+// The walk enters accel c of a chain with ray_to_local(minv[c], ray) -- origin: xf_point -- unless the accel is AF_IDENTITY and the lane's
+// ray is plain (walk.h, ray_plain: that depends on the lane's DIRECTION too), in which case it keeps the ray.  The two agree in every bit of
+// the origin exactly when no component is -0, so every origin on the way has to be plain; the kept form is compared as well.
+bool l0_relative_origins(const FlatScene &f, const V3 &origin, std::vector<V3> &local) {
+    local.assign(f.accels.size(), origin);
+    if (!l0_plain(origin)) return false;
+    for (size_t i = 0; i < f.accels.size(); ++i) {
+        const DAccel &A = f.accels[i];
+        if (A.nchain < 1u || A.nchain > (uint32_t)MAX_CHAIN || A.chain[A.nchain - 1u] != i) return false;
+        V3 o = origin;
+        for (uint32_t k = 0; k < A.nchain; ++k) {
+            const DAccel &C = f.accels[A.chain[k]];
+            const V3 moved = xf_point(C.minv, o);
+            if (!l0_plain(moved)) return false;
+            if ((C.flags & AF_IDENTITY) && std::memcmp(&moved, &o, sizeof o) != 0) return false;
+            o = moved;
+        }
+        local[i] = o;
+    }
+    return true;
+}
+
 void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast, bool with_records) {
     out = FlatScene();
     Flattener fl{scene, out, {}, with_fast};

@@ -152,5 +152,11 @@ struct FlatScene {
 void flatten_scene(const Scene &scene, FlatScene &out, bool with_fast = false, bool with_records = true); // throws Error
 // the last step of flatten_scene: every accel's door record and lone-mesh mark (DAccel::door, DAccel::lone) from the finished tables
 void level_door_records(FlatScene &out);
+// The gate of the level-0 closest pass's origin-relative form, the part that needs no device (launch.cpp, l0_relative adds the
+// launch's own conditions).  true: every ray camera_ray() (shade.h) makes from this camera leaves from the same bits `origin`, and in every
+// accel of the scene the walk's local ray (walk.h: accel_local_ray along DAccel::chain, or the kept ray of an AF_IDENTITY accel) has the
+// origin local[accel], whichever way the lane took -- the very expressions of xf_point, one accel of the chain after the other.
+bool l0_relative_camera(const V3 &origin, const V3 &up, const V3 &aux, double pixel_separation);
+bool l0_relative_origins(const FlatScene &f, const V3 &origin, std::vector<V3> &local);
 
 } // namespace lg

@@ -474,6 +474,11 @@ struct lg_accel {
     DevBuf<uint32_t> accel_image;     // scenes in L2: the accel records alone, in their LDS layout (DParams::accel_image); empty: too many accels
     uint32_t accel_image_n16 = 0;
     uint32_t lds_image_n16 = 0, lds_node_off = 0, lds_prim_off = 0, lds_soup_off = 0, lds_accel_off = 0;
+    // the level-0 closest pass's origin-relative form (dscene.h, DRelAccel): every accel's own node records and leaf slots in the image, origins
+    // zero (launch.cpp fills them per launch); empty: more than L0_REL_MAX_ACCELS accels, or two accels share records (accel.cpp)
+    std::vector<DRelAccel> l0_rel;
+    mutable bool l0_relative = true;  // lg_accel_set_l0_relative
+    mutable int last_l0_relative = -1; // the last level-0 closest launch of the level-by-level pipeline: 1 origin-relative, 0 absolute; -1 before the first
     uint32_t ldss_blocks = 0;         // one 1024-lane workgroup per CU; 0 = variant unavailable for this scene
     uint32_t cus = 1;                 // compute units of the accel's device
     mutable bool lds_scene = true;    // lg_accel_set_lds_scene

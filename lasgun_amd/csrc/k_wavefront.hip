@@ -106,10 +106,51 @@ struct ShadowRefill {
     }
 };
 
+// The origin-relative form of the level-0 closest pass: every ray of a perspective camera leaves from the same point, so
+// bmin - o / bmax - o of a node step and l = o - cen, c = dot(l, l) - r^2 of a sphere slot are the same bits in every lane, tile and
+// frame.  The workgroup that has just copied the scene image into LDS does those subtractions ONCE, in place: every accel's node boxes and
+// sphere slots relative to the camera's origin in THAT accel's local space (DParams::l0_rel, made by the host with the walk's own
+// expressions; each accel has node records and leaf slots of its own in the image, or the host does not ask for this form).  The same
+// operations on the same operands as walk.h's absolute forms -- slab_intersects_sg / _nc, the sphere slot -- so the same bits; the image
+// in HBM, which the shadow pass shares, is untouched.  Called by every lane of the workgroup between two barriers.
+__device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_t tid) {
+    char *const img = reinterpret_cast<char *>(scn);
+    const uint32_t *const prim = reinterpret_cast<const uint32_t *>(scn + P.lds_prim_off);
+    // accel `a` by the lanes first, first + step, ...
+    auto rewrite = [&](const uint32_t a, const uint32_t first, const uint32_t step) {
+        const V3 o{P.l0_rel[a].o[0], P.l0_rel[a].o[1], P.l0_rel[a].o[2]};
+        const uint32_t node_off = P.l0_rel[a].node_off, node_n = P.l0_rel[a].node_n, slot0 = P.l0_rel[a].slot0, slot_n = P.l0_rel[a].slot_n;
+        for (uint32_t i = first; i < node_n; i += step) {
+            double *q = reinterpret_cast<double *>(img + (node_off + i * LDS_NODE_BYTES));
+            q[0] = q[0] - o.x; q[1] = q[1] - o.y; q[2] = q[2] - o.z; // bmin - o
+            q[3] = q[3] - o.x; q[4] = q[4] - o.y; q[5] = q[5] - o.z; // bmax - o
+        }
+        for (uint32_t s = first; s < slot_n; s += step) {
+            const uint32_t slot = slot0 + s;
+            if (prim[slot] >= (1u << 30)) continue; // a cuboid or a nested accel: read as it is
+            double *q = reinterpret_cast<double *>(scn + (P.lds_soup_off + slot * 3u)); // {cen.x, cen.y, cen.z, r, r * r, -}
+            const V3 l = o - V3{q[0], q[1], q[2]};
+            const double c = dot(l, l) - q[4];
+            q[0] = l.x; q[1] = l.y; q[2] = l.z; q[4] = c;
+        }
+    };
+    // A small accel (a wall: a node or two) is one WAVE's: at most 16 accels, 16 waves, so the waves fetch their records of the table side
+    // by side instead of the workgroup one after the other -- on a small frame (a 512^2 Cornell box) those dependent fetches are all this
+    // step costs.  A big one (the headline's root: 2,037 nodes, 1,088 slots) is the whole workgroup's.  Every record is rewritten once.
+    constexpr uint32_t SMALL = 256u;
+    const uint32_t lane = tid & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6)); // (a scalar: the table comes through the scalar cache)
+    for (uint32_t a = wave; a < P.l0_rel_n; a += LG_LDSS_BLOCK / 64u)
+        if (P.l0_rel[a].node_n + P.l0_rel[a].slot_n <= SMALL) rewrite(a, lane, 64u);
+    for (uint32_t a = 0; a < P.l0_rel_n; ++a)
+        if (P.l0_rel[a].node_n + P.l0_rel[a].slot_n > SMALL) rewrite(a, tid, LG_LDSS_BLOCK);
+}
+
 // W1 / W2: persistent traversal kernels of the wavefront pipeline (tile counter, per-lane LDS stack; LDSS as above).
 // L0: the launch is level 0's (rays from the camera, work items = the chunk's pixels in 8x8 tiles).
-template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false>
+// REL: level 0's closest pass with the image's node boxes and sphere slots relative to the camera's origin (l0_rewrite above).
+template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) wf_trace_kernel(const DParams P) {
+    static_assert(!REL || (!FAST && !SHADOW && LDSS && L0 && !PRUNE && !REFILL), "the origin-relative form: level 0's closest pass from LDS");
     static_assert(!REFILL || (SHADOW && LDSS && !FAST), "the refilling walk: the LDS-resident shadow pass");
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
@@ -135,6 +176,10 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         const uint4 *src = reinterpret_cast<const uint4 *>(P.lds_image);
         copy_to_lds(dst, src, P.lds_image_n16, tid, stride);
         __syncthreads(); // the only workgroup-wide step; every wave reaches it before pulling tiles
+        if (REL) { // (uniform: every lane of the workgroup is still here)
+            l0_rewrite(P, dst, tid);
+            __syncthreads();
+        }
         scn = dst;
     }
     const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
@@ -179,7 +224,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
             if (active) {
                 bool tie = false;
-                walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+                walk<LDSS, FAST, PRUNE, false, REL>(P, ray, false, stack, stride, b, scn, cnt, arec);
                 (void)tie;
             }
             const bool hit = active && b.ref != NO_HIT;
@@ -417,6 +462,7 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         static const bool refill_on = [] { const char *e = std::getenv("LASGUN_REFILL"); return e && e[0] == '1'; }();
         const bool refill = refill_on && shadow && P.wf_level == 0u && (unsigned long long)P.ntiles >= 4ull * blocks * (block / 64u);
         if (shadow) { if (refill) hipLaunchKernelGGL((wf_trace_kernel<false, true, true, false, false, true>), dim3(blocks), dim3(block), lds, stream, P); else LG_LAUNCH(false, true, true, false); }
+        else if (l0 && P.l0_rel_n) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, true>), dim3(blocks), dim3(block), lds, stream, P); // (launch.cpp, l0_relative: the gate)
         else if (l0) LG_LAUNCH(false, false, true, true); else LG_LAUNCH(false, false, true, false);
     }
     else { if (shadow) LG_LAUNCH(false, true, false, false); else if (l0) LG_LAUNCH(false, false, false, true); else LG_LAUNCH(false, false, false, false); }
@@ -461,7 +507,8 @@ hipError_t wf_set_lds_limit(size_t bytes, bool ldss) {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, true>),
-        reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, true>)};
+        reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true>)};
     const void *plain_fns[] = {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, false, false>),

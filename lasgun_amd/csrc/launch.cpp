@@ -259,6 +259,27 @@ static void resolve_samples(const lg_accel &a, const DParams &P, uint32_t pixel_
     timed(a, 1, s, [&] { return launch_wf_resolve(R, (uint32_t)(((unsigned long long)pixel_tiles * 64ull + 255ull) / 256ull), s); });
 }
 
+// The gate of the level-0 closest pass's origin-relative form (k_wavefront.hip, l0_rewrite).  Wrong means wrong pixels, so every
+// condition is stated: the plain exact walk over the LDS-resident scene with finite, ordered boxes; an accel whose records the form may
+// rewrite (lg_accel::l0_rel); rays that camera_ray() makes from THIS launch's parameters, all from one origin that is the same bits in every
+// lane (host.cpp, l0_relative_camera), and the same again in every accel's local space (l0_relative_origins).  LASGUN_L0_RELATIVE=0 /
+// lg_accel_set_l0_relative(0): the absolute form, the parent's code path.  Fills P.l0_rel_n / P.l0_rel; false leaves P.l0_rel_n = 0.
+static bool l0_relative(const lg_accel &a, DParams &P) {
+    static const bool env = env_on("LASGUN_L0_RELATIVE");
+    P.l0_rel_n = 0u;
+    if (!env || !a.l0_relative || a.fast || P.prune || !P.lds_image || !P.boxes_finite || P.wf_level != 0u) return false;
+    if (a.l0_rel.empty() || a.l0_rel.size() != a.flat.accels.size() || a.l0_rel.size() > L0_REL_MAX_ACCELS) return false;
+    if (!l0_relative_camera(P.cam_origin, P.cam_up, P.cam_aux, P.pixel_separation)) return false;
+    std::vector<V3> local;
+    if (!l0_relative_origins(a.flat, P.cam_origin, local)) return false;
+    for (size_t i = 0; i < a.l0_rel.size(); ++i) {
+        P.l0_rel[i] = a.l0_rel[i];
+        P.l0_rel[i].o[0] = local[i].x; P.l0_rel[i].o[1] = local[i].y; P.l0_rel[i].o[2] = local[i].z;
+    }
+    P.l0_rel_n = (uint32_t)a.l0_rel.size();
+    return true;
+}
+
 // ---- the level-by-level pipeline (k_wavefront.hip), shared by a render (enqueue_wavefront) and a radiance query (enqueue_radiance) ----
 // A chunk's arrays in a launch context: the level arrays, and beside them the hit queue, frame and visibility of the widest level (dense
 // part + appended part), the queue counts and a block of tile heads per launch
@@ -319,7 +340,11 @@ struct WfChunk {
             const bool own0 = d == 0 && l0.own();
             level_params(d);
             if (own0) timed(a, 0, ls, [&] { return l0.closest(P, a.fast, tb, depth, ls); });
-            else timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
+            else {
+                if (d == 0) a.last_l0_relative = l0_relative(a, P) ? 1 : 0; // (the camera's level 0: the form is chosen per launch, from this launch's camera)
+                timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
+                P.l0_rel_n = 0u;
+            }
             if (P.nlights > 0) {
                 level_params(d);
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });

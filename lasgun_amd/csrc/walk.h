@@ -13,6 +13,7 @@
 //   wf_trace_kernel<FAST, SHADOW, LDSS, L0, PRUNE>  wavefront pipeline, traversal only: closest hit of a level's rays (hits
 //                                             compacted, frames parked) or per-light any-hit of its hits;
 //                                             LDSS = scene tables resident in LDS, one 1024-lane workgroup per CU
+//                                             (+ REL: level 0's closest pass with the LDS records relative to the camera's origin)
 //   wf_shade_kernel<KIND, L0>, wf_combine_kernel   radiance of a level's hits, specular children queued; levels combined bottom-up
 //   queue_kernel<LDSS, PRUNE>                 every recursion level in one persistent launch (k_queue.hip)
 //   trace_pixel_kernel<FAST>                  one pixel by one lane, with an event log of the walk (lg_trace_pixel)
@@ -127,6 +128,35 @@ __device__ __forceinline__ bool slab_intersects_sg(const double bmin[3], const d
     const double fz = (((SG & 4) ? bmin[2] : bmax[2]) - r.o.z) * r.dinv.z;
     tnear = fmax_(tnear, tz);
     tfar = fmin_(tfar, fz);
+    return !(tnear > tfar) && !(tfar <= 0.0);
+}
+
+// The REL forms (the level-0 closest pass of a camera whose rays share one origin: k_wavefront.hip, l0_rewrite): the record holds
+// fl(bmin - o) and fl(bmax - o) where it held bmin and bmax -- the same subtraction on the same bits, done once by the workgroup
+// instead of per lane and node step -- and the test starts at the multiplication by dinv.  Nothing else differs from the form above.
+template <int SG>
+__device__ __forceinline__ bool slab_intersects_sg_rel(const double rmin[3], const double rmax[3], const Ray &r) {
+    const double tx = ((SG & 1) ? rmax[0] : rmin[0]) * r.dinv.x;
+    double tfar = ((SG & 1) ? rmin[0] : rmax[0]) * r.dinv.x;
+    const double ty = ((SG & 2) ? rmax[1] : rmin[1]) * r.dinv.y;
+    const double fy = ((SG & 2) ? rmin[1] : rmax[1]) * r.dinv.y;
+    double tnear = fmax_(tx, ty);
+    tfar = fmin_(tfar, fy);
+    const double tz = ((SG & 4) ? rmax[2] : rmin[2]) * r.dinv.z;
+    const double fz = ((SG & 4) ? rmin[2] : rmax[2]) * r.dinv.z;
+    tnear = fmax_(tnear, tz);
+    tfar = fmin_(tfar, fz);
+    return !(tnear > tfar) && !(tfar <= 0.0);
+}
+__device__ __forceinline__ bool slab_intersects_nc_rel(const double rmin[3], const double rmax[3], const Ray &r) { // slab_intersects_nc
+    double t1 = rmin[0] * r.dinv.x, t2 = rmax[0] * r.dinv.x;
+    double tnear = fmin_(t1, t2), tfar = fmax_(t1, t2);
+    t1 = rmin[1] * r.dinv.y; t2 = rmax[1] * r.dinv.y;
+    tnear = fmax_(tnear, fmin_(t1, t2));
+    tfar = fmin_(tfar, fmax_(t1, t2));
+    t1 = rmin[2] * r.dinv.z; t2 = rmax[2] * r.dinv.z;
+    tnear = fmax_(tnear, fmin_(t1, t2));
+    tfar = fmin_(tfar, fmax_(t1, t2));
     return !(tnear > tfar) && !(tfar <= 0.0);
 }
 
@@ -1050,11 +1080,15 @@ struct NoRefill {
     __device__ __forceinline__ uint32_t threshold() const { return 65u; }
     __device__ __forceinline__ bool next(bool, const Best &, Ray &) { return false; }
 };
-template <bool LDSS, bool FAST = false, bool PRUNE = false, bool COUNT = false, class RF = NoRefill>
+// REL (the level-0 closest pass over an LDS-resident scene whose rays share one origin: k_wavefront.hip, l0_rewrite): the node records and
+// the sphere slots of the image are held relative to their accel's local origin; everything read from the accel records or the global
+// tables -- cuboid slots, doors, entry transforms -- stays absolute and goes on using the lane's own ray.o.
+template <bool LDSS, bool FAST = false, bool PRUNE = false, bool COUNT = false, class RF = NoRefill, bool REL = false>
 __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, const bool anyhit, uint32_t *stack, const uint32_t stride,
                                              Best &best, const uint4 *scn, bool &tie, Counters &cnt, const uint4 *arec_in = nullptr,
                                              RF *rf = nullptr, const bool live = true) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
+    static_assert(!REL || (LDSS && !FAST && !PRUNE && !COUNT && !RF::enabled), "the origin-relative records: the plain exact walk from LDS");
     const uint4 *const arec = LDSS ? scn + P.lds_accel_off : (FAST ? nullptr : arec_in); // the accel records in LDS, if they are there (lvl_set)
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
 #ifdef LG_STAMPS
@@ -1183,8 +1217,10 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                     hit = hit && !(beyond && (w_meta & NODE_NOPRUNE) == 0u);
                 } else if (SG < 8) {
                     double tx, ty, tz;
-                    hit = slab_intersects_sg<SG & 7>(bmin, bmax, ray, tx, ty, tz);
-                } else hit = slab_intersects_nc(bmin, bmax, ray);
+                    if (REL) hit = slab_intersects_sg_rel<SG & 7>(bmin, bmax, ray);
+                    else hit = slab_intersects_sg<SG & 7>(bmin, bmax, ray, tx, ty, tz);
+                } else if (REL) hit = slab_intersects_nc_rel(bmin, bmax, ray);
+                else hit = slab_intersects_nc(bmin, bmax, ray);
                 if (COUNT) { cnt.nodes++; dbg_event(P, 2.0 + (hit ? 0.1 : 0.0), (double)L.accel, (double)cur, (double)w_meta); }
                 const bool leaf = (int32_t)w_meta < 0;            // n_primitives > 0 (bvh.rs:475): the builder emits no empty leaf
                 const bool neg = ((SG < 8 ? (uint32_t)SG : negmask) & w_meta) != 0u; // dir_is_neg[axis] (bvh.rs:496); w_meta carries 1 << axis, never bit 3
@@ -1279,9 +1315,9 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                 // mesh_leaf2 walks; the sphere is asked for first, with one compare on the primref: the common case passes one branch)
                 if (ref < (1u << 30)) { // PK_SPHERE: Sphere::intersect_t + quad_roots (sphere.rs:30-69, core/math.rs) == sphere_t_a
                     const V3 cen{rec_f64(g.a.x, g.a.y), rec_f64(g.a.z, g.a.w), rec_f64(g.b.x, g.b.y)};
-                    const V3 l = ray.o - cen;
+                    const V3 l = REL ? cen : ray.o - cen; // (REL: the slot holds l where it held the centre, and c where it held rad * rad)
                     const double b = 2.0 * dot(ray.d, l);
-                    const double c = dot(l, l) - rec_f64(g.c.x, g.c.y); // rad * rad, formed by the host
+                    const double c = REL ? rec_f64(g.c.x, g.c.y) : dot(l, l) - rec_f64(g.c.x, g.c.y); // rad * rad, formed by the host
                     bool has = false;
                     if (dd == 0.0) {
                         if (b != 0.0) { t = -c / b; has = true; }
@@ -1751,7 +1787,7 @@ __device__ __forceinline__ void traverse_fast(const DParams &P, const Ray &wray,
 //   * any-hit: an occluder counts if the reference tree would have tested it (the reference then finds it or one before it);
 //     "not occluded" stands unless a tie / NaN makes the reference's own answer depend on its visit order;
 // otherwise the ray is traced again with the reference walk over the tables in HBM / L2.
-template <bool LDSS, bool FAST, bool PRUNE = false, bool COUNT = false>
+template <bool LDSS, bool FAST, bool PRUNE = false, bool COUNT = false, bool REL = false>
 __device__ __forceinline__ void walk(const DParams &P, const Ray &ray, const bool anyhit, uint32_t *stack, const uint32_t stride, Best &best,
                                      const uint4 *scn, Counters &cnt, const uint4 *arec = nullptr) {
     bool tie = false;
@@ -1761,7 +1797,7 @@ __device__ __forceinline__ void walk(const DParams &P, const Ray &ray, const boo
     }
     if (FAST) traverse_fast<COUNT>(P, ray, anyhit, stack, stride, best, scn, tie, cnt);
     else
-    traverse_ref<LDSS, FAST, PRUNE, COUNT>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);
+    traverse_ref<LDSS, FAST, PRUNE, COUNT, NoRefill, REL>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);
     if (!FAST) return;
     if (COUNT) dbg_event(P, 9.0, tie ? 1.0 : 0.0, best.t, (double)best.ref);
     bool redo;
