@@ -264,6 +264,19 @@ int lg_accel_set_level_door(const lg_accel *, int mask);
 int lg_accel_set_l0_relative(const lg_accel *, int enabled);
 int lg_accel_last_l0_relative(const lg_accel *);
 int lg_scene_l0_relative_origins(const lg_scene *, double *origins, int cap);
+/* The exact walk from LDS, two boxes a trip: the LDS image of an accel whose tables fit there holds one 112-byte
+ * PAIR record per interior node -- its two children's boxes and a typed word per child -- and one root record per tree in place of the
+ * node records.  Every kernel that walks the plain exact form (not fast, not pruned) from LDS tests both children of a node in one trip and
+ * pushes only a far child that is hit: the same box tests on the same operands, each at most once per ray, the leaves in the reference's
+ * order.  1 (default): on where every tree's slot ranges fit a child word and the accel does not render pruned; 0: the node records (A/B,
+ * tests; LASGUN_NODE_PAIRS=0 does the same for every accel).  A change re-makes the image with the accel's tables.  Same bytes either way.
+ * lg_accel_last_node_pairs: the records the last launch over the LDS-resident scene read (1 pair / 0 node; -1 before the first). */
+int lg_accel_set_node_pairs(const lg_accel *, int enabled);
+int lg_accel_last_node_pairs(const lg_accel *);
+/* The LDS image lg_accel_from would make for this scene, without a device (tests): its 32-bit words into words[0 .. cap), info[8] = {16-byte
+ * units, node offset, primref offset, leaf-record offset, accel-record offset (all in units), 1 if it holds pair records, accels, node
+ * records of the flat tables}.  Returns the number of words, 0 when the tables do not fit in LDS, -1 on an error. */
+int64_t lg_scene_lds_image(const lg_scene *, int pairs, uint32_t *words, size_t cap, uint32_t *info);
 int lg_accel_get_prune(const lg_accel *); /* the effective setting (accel default, LASGUN_PRUNE, lg_accel_set_prune, fast mode): 0 / 1 */
 
 /* Kernel organisation (same arithmetic, same bytes either way).  1 (default): the organisation of a launch is MEASURED -- the SECOND

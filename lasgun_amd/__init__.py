@@ -44,6 +44,9 @@ _EXTRA = {
     "accel_set_l0_relative": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_last_l0_relative": (_C.c_int, [_C.c_void_p]),
     "scene_l0_relative_origins": (_C.c_int, [_C.c_void_p, _C.POINTER(_C.c_double), _C.c_int]),
+    "accel_set_node_pairs": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_last_node_pairs": (_C.c_int, [_C.c_void_p]),
+    "scene_lds_image": (_C.c_longlong, [_C.c_void_p, _C.c_int, _C.POINTER(_C.c_uint32), _C.c_size_t, _C.POINTER(_C.c_uint32)]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
     "accel_last_organisation": (_C.c_int, [_C.c_void_p]),
@@ -203,6 +206,31 @@ class HipApi(Api):
         """The form the last level-0 closest launch of the level-by-level pipeline took: True origin-relative, False absolute; None before the first."""
         v = self.call("accel_last_l0_relative", accel.h)
         return None if v < 0 else bool(v)
+
+    def set_node_pairs(self, accel, enabled):
+        """The exact walk from LDS over pair records, two boxes a trip (default on; same bytes either way; include/lasgun_hip.h,
+        lg_accel_set_node_pairs)."""
+        if self.call("accel_set_node_pairs", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def last_node_pairs(self, accel):
+        """The records the last launch over the LDS-resident scene read: True pair records, False node records, None before the first."""
+        v = self.call("accel_last_node_pairs", accel.h)
+        return None if v < 0 else bool(v)
+
+    def scene_lds_image(self, scene, pairs):
+        """The LDS image lg_accel_from would make for this scene, without a device: (uint32 words, info dict), or None where the tables
+        do not fit in LDS (include/lasgun_hip.h, lg_scene_lds_image)."""
+        info = (_C.c_uint32 * 8)()
+        n = self.call("scene_lds_image", scene.h, 1 if pairs else 0, None, 0, info)
+        if n < 0:
+            raise LasgunError(self.last_error())
+        if n == 0:
+            return None
+        words = _np.zeros(n, dtype=_np.uint32)
+        self.call("scene_lds_image", scene.h, 1 if pairs else 0, words.ctypes.data_as(_C.POINTER(_C.c_uint32)), n, info)
+        keys = ("units", "node_off", "prim_off", "soup_off", "accel_off", "pairs", "accels", "nodes")
+        return words, {k: int(info[i]) for i, k in enumerate(keys)}
 
     def l0_relative_origins(self, scene):
         """The device-free part of that form's gate for a scene and its camera: the camera's origin in every accel's local space, (accels, 3)

@@ -1,6 +1,7 @@
 // lasgun_amd/csrc/accel.cpp -- Accel::from (src/accelerators/bvh.rs:135-202 on the host, host.cpp) as device tables: flatten, the LDS images,
 // grids and budgets from the device's occupancy, one upload; and the tables once more with what was left out of them (fast trees, leaf records).
 #include "internal.h"
+#include "pairs_host.h"
 
 // raise the dynamic-LDS limit of the traversal kernels of EVERY kernel file (ldss: their LDS-resident-scene forms; otherwise the 256-lane
 // forms): a kernel file with such kernels adds itself here
@@ -10,8 +11,195 @@ static void set_lds_limits(size_t bytes, bool ldss) {
         HIP_TRY(set(bytes, ldss));
 }
 
+// The LDS-resident scene image of a flattened scene (a->flat; a->stack_depth, a->node_pairs and a->prune say which): the image's words into
+// `img`, the compact bases into the accel records of a->flat, the offsets, ranges and form into `a`.  Touches no device (lg_scene_lds_image
+// calls it for a scene alone).  false: the tables do not fit beside the stacks.
+constexpr size_t LDS_MAX = 160 * 1024;
+static bool make_lds_image(lg_accel *a, size_t big_mesh_tris, std::vector<uint32_t> &img) {
+    static const bool times = std::getenv("LASGUN_DEBUG_TIMES") != nullptr;
+    a->lds_image_n16 = 0; a->lds_pairs = false; a->pair_refusal.clear(); a->pair_rel.clear();
+    {
+        {
+            FlatScene &fm = a->flat;
+            std::vector<uint32_t> nb, pb; // start offsets of every tree / primref run, both kinds
+            for (const DAccel &A : fm.accels) { nb.push_back(A.node_base); nb.push_back(A.fnode_base); pb.push_back(A.prim_base); pb.push_back(A.fprim_base); }
+            std::sort(nb.begin(), nb.end()); nb.erase(std::unique(nb.begin(), nb.end()), nb.end());
+            std::sort(pb.begin(), pb.end()); pb.erase(std::unique(pb.begin(), pb.end()), pb.end());
+            auto extent = [](const std::vector<uint32_t> &starts, uint32_t b, size_t total) {
+                auto it = std::upper_bound(starts.begin(), starts.end(), b);
+                return (uint32_t)((it == starts.end() ? total : (size_t)*it) - b);
+            };
+            std::vector<std::pair<uint32_t, uint32_t>> nruns, pruns; // (global base, compact base) of each reference tree, once
+            uint32_t nn = 0, np = 0;
+            // compact numbering: the non-mesh accels first (their slots get a leaf record in the image), then the meshes
+            uint32_t np_soup = 0; // slots of the non-mesh accels
+            const size_t stack_bytes = (size_t)a->stack_depth * 1024 * 4; // per-lane stacks of the private walks
+            const size_t accel16 = fm.accels.size() * LDS_ACCEL_UNITS;
+            // image: [nodes, LDS_NODE_STRIDE units each][primrefs][leaf records, 3 units per slot][accel records]
+            // `own_trees`: every accel gets node records of its own -- instances of one mesh (the five walls of the Cornell shell are one
+            // two-triangle plane) otherwise share a tree, and the level-0 closest pass's origin-relative form (k_wavefront.hip, l0_rewrite)
+            // rewrites a tree relative to ITS accel's local origin, which differs from instance to instance.  Same records, same walk words
+            // up to each copy's own base; the primrefs stay shared (a mesh's slots are triangles: never rewritten).
+            auto number = [&](bool own_trees) {
+                nruns.clear(); pruns.clear(); nn = np = np_soup = 0;
+                for (int pass = 0; pass < 2; ++pass) {
+                  if (pass == 1) np_soup = np;
+                  for (DAccel &A : fm.accels) {
+                    if (((A.flags & AF_MESH) != 0u) != (pass == 1)) continue;
+                    auto fn = own_trees ? nruns.end() : std::find_if(nruns.begin(), nruns.end(), [&](auto &r) { return r.first == A.node_base; });
+                    if (fn == nruns.end()) { nruns.emplace_back(A.node_base, nn); A.lnode_base = nn; nn += extent(nb, A.node_base, fm.nodes.size()); }
+                    else A.lnode_base = fn->second;
+                    auto fp = std::find_if(pruns.begin(), pruns.end(), [&](auto &r) { return r.first == A.prim_base; });
+                    if (fp == pruns.end()) { pruns.emplace_back(A.prim_base, np); A.lprim_base = np; np += extent(pb, A.prim_base, fm.primref.size()); }
+                    else A.lprim_base = fp->second;
+                  }
+                }
+                return (size_t)nn * LDS_NODE_STRIDE + ((size_t)np + 3) / 4 + (size_t)np_soup * 3 + accel16;
+            };
+            size_t n16 = number(false);
+            // The copies are paid by every launch of every LDS-resident kernel (each workgroup copies the image once per launch), so they are
+            // made only where they are small change: at most 1/16 on top of the shared image, and only for a scene the form can serve at all.
+            if (fm.accels.size() <= L0_REL_MAX_ACCELS && nruns.size() < fm.accels.size()) {
+                const size_t shared16 = n16, own16 = number(true);
+                if (stack_bytes + own16 * 16 > LDS_MAX || (own16 - shared16) * 16 > shared16) n16 = number(false);
+                else n16 = own16;
+            }
+            const size_t prim16 = ((size_t)np + 3) / 4;
+            a->l0_rel.clear();
+            if (stack_bytes + n16 * 16 <= LDS_MAX) {
+                img.assign(n16 * 4, 0u);
+                a->lds_node_off = 0;
+                for (auto &r : nruns)
+                    for (uint32_t i = 0, e = extent(nb, r.first, fm.nodes.size()); i < e; ++i) {
+                        uint32_t *rec = &img[((size_t)(r.second + i) * LDS_NODE_STRIDE) * 4];
+                        std::memcpy(rec, &fm.nodes[r.first + i], 56);
+                    }
+                a->lds_prim_off = nn * LDS_NODE_STRIDE;
+                a->lds_soup_off = a->lds_prim_off + (uint32_t)prim16;
+                for (auto &r : pruns)
+                    for (uint32_t i = 0, e = extent(pb, r.first, fm.primref.size()); i < e; ++i) {
+                        img[(size_t)a->lds_prim_off * 4 + r.second + i] = fm.primref[r.first + i];
+                        if (r.second + i < np_soup)
+                            std::memcpy(&img[((size_t)a->lds_soup_off + (size_t)(r.second + i) * 3) * 4], &fm.leaf_soup[r.first + i], 48);
+                    }
+                // walk words of every record (words 16..19; walk.h, traverse_ref): the second formulation of the reference walk
+                // addresses nodes by their byte offset in the image and takes a leaf's slot range ready-made
+                for (const DAccel &A : fm.accels) {
+                    const uint32_t tree0 = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
+                    for (uint32_t i = 0, e = extent(nb, A.node_base, fm.nodes.size()); i < e; ++i) {
+                        uint32_t *rec = &img[((size_t)(A.lnode_base + i) * LDS_NODE_STRIDE) * 4];
+                        const DNode &nd = fm.nodes[A.node_base + i];
+                        if (nd.meta & NODE_LEAF) { rec[16] = A.lprim_base + nd.link; rec[17] = NODE_LEAF; rec[18] = rec[16] + (nd.meta & 0xFFFFu); rec[19] = nd.pad; }
+                        else { rec[16] = tree0 + nd.link * LDS_NODE_STRIDE * 16u; rec[17] = 1u << (nd.meta & 3u); rec[18] = 0u; }
+                        rec[17] |= nd.meta & NODE_NOPRUNE;
+                    }
+                }
+                a->lds_accel_off = a->lds_soup_off + np_soup * 3u;
+                for (size_t i = 0; i < fm.accels.size(); ++i) {
+                    const DAccel &A = fm.accels[i];
+                    uint32_t *rec = &img[((size_t)a->lds_accel_off + i * LDS_ACCEL_UNITS) * 4];
+                    std::memcpy(rec, &A.minv, 96);
+                    rec[24] = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
+                    rec[25] = A.lprim_base; rec[26] = A.prim_base - A.lprim_base; rec[27] = A.flags;
+                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain; rec[30] = A.lone;
+                    for (int k = 0; k < MAX_CHAIN; ++k) rec[32 + k] = A.chain[k];
+                    std::memcpy(rec + 40, A.prune, sizeof A.prune);
+                    std::memcpy(rec + LDS_ACCEL_DOOR * 4, A.door, sizeof A.door);
+                }
+                // the origin-relative form's ranges (DRelAccel): offered only when no record would be rewritten for two accels
+                if (fm.accels.size() <= L0_REL_MAX_ACCELS) {
+                    bool own = true;
+                    for (size_t i = 0; i < fm.accels.size(); ++i)
+                        for (size_t j = 0; j < i; ++j) {
+                            const DAccel &A = fm.accels[i], &B = fm.accels[j];
+                            own = own && A.lnode_base != B.lnode_base && (((A.flags | B.flags) & AF_MESH) != 0u || A.lprim_base != B.lprim_base);
+                        }
+                    for (const DAccel &A : fm.accels) {
+                        DRelAccel r{};
+                        r.node_off = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
+                        r.node_n = extent(nb, A.node_base, fm.nodes.size());
+                        r.slot0 = A.lprim_base;
+                        r.slot_n = (A.flags & AF_MESH) ? 0u : extent(pb, A.prim_base, fm.primref.size());
+                        own = own && (size_t)r.node_off + (size_t)r.node_n * LDS_NODE_STRIDE * 16u <= (size_t)a->lds_prim_off * 16u && r.slot0 + r.slot_n <= np_soup;
+                        a->l0_rel.push_back(r);
+                    }
+                    if (!own) a->l0_rel.clear();
+                }
+                // The pair form of the image (pairs_host.h; walk.h, traverse_ref<.., PAIR>), made IN PLACE of the node form where the switch asks for it
+                // (lg_accel_set_node_pairs, LASGUN_NODE_PAIRS; not beside the REFILL experiment, which reads node records): [pair records of
+                // every tree][root records][primrefs][leaf records][accel records] -- everything behind the node records copied as it is, the
+                // accel records' unit [6].x pointing at the tree's root record.  2 * pairs + roots == node records (pair_size_ok): the pair
+                // records hold the 56 payload bytes of every node record but the roots', so the image grows by nothing but the root records
+                // (and shrinks against the 80-byte LDS node records).  A tree whose slot ranges do not fit a child word, or instances of one
+                // tree with different slot bases: the node form stays, and pair_refusal says why (LASGUN_DEBUG_TIMES prints it).
+                static const bool pairs_env = env_on("LASGUN_NODE_PAIRS");
+                static const bool refill_env = [] { const char *e = std::getenv("LASGUN_REFILL"); return e && e[0] == '1'; }();
+                // (an accel whose renders take the pruned walk keeps the node form, which that walk reads from LDS; lg_accel_set_prune(1) on an accel
+                // that holds pair records sends its pruned launches to the L2 tables instead: internal.h, lds_resident)
+                const int prune_set = a->image_prune != -2 ? a->image_prune : a->prune;
+                const bool pruned_now = prune_set < 0 ? (prune_env() < 0 ? big_mesh_tris >= PRUNE_MIN_TRIS : prune_env() != 0) : prune_set != 0;
+                if (a->node_pairs && pairs_env && !refill_env && !pruned_now) {
+                    std::vector<uint32_t> run_pair(nruns.size(), 0u), run_n(nruns.size(), 0u), run_lprim(nruns.size(), 0u); // first pair record of each tree, its pair records, its slot base
+                    size_t pairs = 0;
+                    for (size_t r = 0; r < nruns.size(); ++r) {
+                        run_pair[r] = (uint32_t)pairs;
+                        run_n[r] = (uint32_t)pair_interior_count(&fm.nodes[nruns[r].first], extent(nb, nruns[r].first, fm.nodes.size()));
+                        pairs += run_n[r];
+                    }
+                    const size_t pair16 = pairs * (PAIR_REC_BYTES / 16u), root16 = nruns.size() * (PAIR_ROOT_BYTES / 16u), tail16 = n16 - a->lds_prim_off;
+                    const size_t p16 = pair16 + root16 + tail16;
+                    std::vector<uint32_t> pimg(p16 * 4, 0u);
+                    std::string why;
+                    bool ok = pair_size_ok(pairs, nruns.size(), nn) && stack_bytes + p16 * 16 <= LDS_MAX;
+                    if (!ok) why = "the trees are not binary, or the pair form does not fit beside the stacks";
+                    std::memcpy(&pimg[(pair16 + root16) * 4], &img[(size_t)a->lds_prim_off * 4], tail16 * 16);
+                    const uint32_t shift = (uint32_t)(pair16 + root16) - a->lds_prim_off; // what every offset behind the node records moves by (mod 2^32)
+                    std::vector<bool> built(nruns.size(), false);
+                    for (size_t i = 0; ok && i < fm.accels.size(); ++i) {
+                        const DAccel &A = fm.accels[i];
+                        const size_t r = (size_t)(std::find_if(nruns.begin(), nruns.end(), [&](auto &q) { return q.second == A.lnode_base; }) - nruns.begin());
+                        if (r >= nruns.size()) { ok = false; why = "an accel without a tree in the image"; break; }
+                        const size_t pair_off = (size_t)run_pair[r] * PAIR_REC_BYTES, root_off = pair16 * 16u + r * PAIR_ROOT_BYTES;
+                        if (!built[r]) {
+                            ok = pair_build_tree(&fm.nodes[nruns[r].first], extent(nb, nruns[r].first, fm.nodes.size()), A.lprim_base, pair_off, root_off,
+                                                 reinterpret_cast<unsigned char *>(pimg.data()), (pair16 + root16) * 16u, &why);
+                            built[r] = true; run_lprim[r] = A.lprim_base;
+                        } else if (run_lprim[r] != A.lprim_base) { ok = false; why = "instances of one tree with different slot bases"; } // (a leaf word carries absolute slots)
+                        pimg[((size_t)(a->lds_accel_off + shift) + i * LDS_ACCEL_UNITS) * 4 + 24] = (uint32_t)root_off;
+                        a->pair_rel.push_back({(uint32_t)root_off, (uint32_t)pair_off, run_n[r]});
+                    }
+                    if (ok) {
+                        a->lds_prim_off += shift; a->lds_soup_off += shift; a->lds_accel_off += shift;
+                        img.swap(pimg); n16 = p16;
+                        a->lds_pairs = true;
+                    } else {
+                        a->pair_rel.clear(); a->pair_refusal = why;
+                        if (times) std::fprintf(stderr, "[lasgun] accel build: no pair form of the LDS image (%s): the node form serves every kernel\n", why.c_str());
+                    }
+                }
+                a->lds_image_n16 = (uint32_t)n16;
+                return true;
+            }
+        }
+    }
+    return false;
+}
+// the image builder for a scene alone (lg_scene_lds_image): what lg_accel_from would copy into LDS, without a device
+bool scene_lds_image(const Scene &scene, bool pairs, std::vector<uint32_t> &img, uint32_t info[8]) {
+    lg_accel a;
+    a.scene = &scene;
+    a.node_pairs = pairs;
+    a.prune = 0;
+    flatten_scene(scene, a.flat, false, false);
+    a.stack_depth = a.flat.max_stack + 2;
+    if (!make_lds_image(&a, 0, img)) return false;
+    info[0] = a.lds_image_n16; info[1] = a.lds_node_off; info[2] = a.lds_prim_off; info[3] = a.lds_soup_off; info[4] = a.lds_accel_off;
+    info[5] = a.lds_pairs ? 1u : 0u; info[6] = (uint32_t)a.flat.accels.size(); info[7] = (uint32_t)a.flat.nodes.size();
+    return true;
+}
+
 static void build_and_upload(lg_accel *a, bool with_fast) {
-    a->ldss_blocks = 0; a->lds_image_n16 = 0; a->fast_available = true;
+    a->ldss_blocks = 0; a->lds_image_n16 = 0; a->lds_pairs = false; a->pair_refusal.clear(); a->pair_rel.clear(); a->fast_available = true;
         static const bool times = std::getenv("LASGUN_DEBUG_TIMES") != nullptr; // (where lg_accel_from's time goes: flatten / upload / derived)
         const auto t_begin = std::chrono::steady_clock::now();
         // The culling records and strips of the pruned walk's mesh leaves are built when that walk will run: by default from PRUNE_MIN_TRIS
@@ -41,9 +229,10 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         if (!a->stream) a->stream = g_streams.take(a->device);
         // per-lane LDS stack: worst case of this scene graph, +2 guard entries
         a->stack_depth = f.max_stack + 2;
+        // (the pair form of the walk -- walk.h, traverse_ref<.., PAIR> -- keeps this depth: per level its stack holds the far children that are HIT of the
+        // interior nodes on the lane's path, the node form's every far child of those nodes -- a subset, entry for entry; frames and guard entries are the same)
         // the fast kernel falls back to the reference traversal on exact ties, so its stack must hold either
         a->stack_depth_fast1 = (f.max_stack > f.max_stack_fast1 ? f.max_stack : f.max_stack_fast1) + 2;
-        const size_t LDS_MAX = 160 * 1024;
         if ((size_t)a->stack_depth * 256 * 4 > LDS_MAX)
             throw Error("BVH too deep for the LDS traversal stack (" + std::to_string(a->stack_depth) + " entries per lane; the reference panics beyond 64 per level, bvh.rs:497)");
         a->fast_available = (size_t)a->stack_depth_fast1 * 256 * 4 <= LDS_MAX;
@@ -126,116 +315,13 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         // stacks, all within one CU's LDS.  The flat tables interleave reference and fast trees per
         // accel, so the image renumbers the reference trees compactly (DAccel::lnode_base / lprim_base).
         {
-            FlatScene &fm = a->flat;
-            std::vector<uint32_t> nb, pb; // start offsets of every tree / primref run, both kinds
-            for (const DAccel &A : fm.accels) { nb.push_back(A.node_base); nb.push_back(A.fnode_base); pb.push_back(A.prim_base); pb.push_back(A.fprim_base); }
-            std::sort(nb.begin(), nb.end()); nb.erase(std::unique(nb.begin(), nb.end()), nb.end());
-            std::sort(pb.begin(), pb.end()); pb.erase(std::unique(pb.begin(), pb.end()), pb.end());
-            auto extent = [](const std::vector<uint32_t> &starts, uint32_t b, size_t total) {
-                auto it = std::upper_bound(starts.begin(), starts.end(), b);
-                return (uint32_t)((it == starts.end() ? total : (size_t)*it) - b);
-            };
-            std::vector<std::pair<uint32_t, uint32_t>> nruns, pruns; // (global base, compact base) of each reference tree, once
-            uint32_t nn = 0, np = 0;
-            // compact numbering: the non-mesh accels first (their slots get a leaf record in the image), then the meshes
-            uint32_t np_soup = 0; // slots of the non-mesh accels
-            const size_t stack_bytes = (size_t)a->stack_depth * 1024 * 4; // per-lane stacks of the private walks
-            const size_t accel16 = fm.accels.size() * LDS_ACCEL_UNITS;
-            // image: [nodes, LDS_NODE_STRIDE units each][primrefs][leaf records, 3 units per slot][accel records]
-            // `own_trees`: every accel gets node records of its own -- instances of one mesh (the five walls of the Cornell shell are one
-            // two-triangle plane) otherwise share a tree, and the level-0 closest pass's origin-relative form (k_wavefront.hip, l0_rewrite)
-            // rewrites a tree relative to ITS accel's local origin, which differs from instance to instance.  Same records, same walk words
-            // up to each copy's own base; the primrefs stay shared (a mesh's slots are triangles: never rewritten).
-            auto number = [&](bool own_trees) {
-                nruns.clear(); pruns.clear(); nn = np = np_soup = 0;
-                for (int pass = 0; pass < 2; ++pass) {
-                  if (pass == 1) np_soup = np;
-                  for (DAccel &A : fm.accels) {
-                    if (((A.flags & AF_MESH) != 0u) != (pass == 1)) continue;
-                    auto fn = own_trees ? nruns.end() : std::find_if(nruns.begin(), nruns.end(), [&](auto &r) { return r.first == A.node_base; });
-                    if (fn == nruns.end()) { nruns.emplace_back(A.node_base, nn); A.lnode_base = nn; nn += extent(nb, A.node_base, fm.nodes.size()); }
-                    else A.lnode_base = fn->second;
-                    auto fp = std::find_if(pruns.begin(), pruns.end(), [&](auto &r) { return r.first == A.prim_base; });
-                    if (fp == pruns.end()) { pruns.emplace_back(A.prim_base, np); A.lprim_base = np; np += extent(pb, A.prim_base, fm.primref.size()); }
-                    else A.lprim_base = fp->second;
-                  }
-                }
-                return (size_t)nn * LDS_NODE_STRIDE + ((size_t)np + 3) / 4 + (size_t)np_soup * 3 + accel16;
-            };
-            size_t n16 = number(false);
-            // The copies are paid by every launch of every LDS-resident kernel (each workgroup copies the image once per launch), so they are
-            // made only where they are small change: at most 1/16 on top of the shared image, and only for a scene the form can serve at all.
-            if (fm.accels.size() <= L0_REL_MAX_ACCELS && nruns.size() < fm.accels.size()) {
-                const size_t shared16 = n16, own16 = number(true);
-                if (stack_bytes + own16 * 16 > LDS_MAX || (own16 - shared16) * 16 > shared16) n16 = number(false);
-                else n16 = own16;
-            }
-            const size_t prim16 = ((size_t)np + 3) / 4;
-            a->l0_rel.clear();
-            if (stack_bytes + n16 * 16 <= LDS_MAX) {
-                std::vector<uint32_t> img(n16 * 4, 0u);
-                a->lds_node_off = 0;
-                for (auto &r : nruns)
-                    for (uint32_t i = 0, e = extent(nb, r.first, fm.nodes.size()); i < e; ++i) {
-                        uint32_t *rec = &img[((size_t)(r.second + i) * LDS_NODE_STRIDE) * 4];
-                        std::memcpy(rec, &fm.nodes[r.first + i], 56);
-                    }
-                a->lds_prim_off = nn * LDS_NODE_STRIDE;
-                a->lds_soup_off = a->lds_prim_off + (uint32_t)prim16;
-                for (auto &r : pruns)
-                    for (uint32_t i = 0, e = extent(pb, r.first, fm.primref.size()); i < e; ++i) {
-                        img[(size_t)a->lds_prim_off * 4 + r.second + i] = fm.primref[r.first + i];
-                        if (r.second + i < np_soup)
-                            std::memcpy(&img[((size_t)a->lds_soup_off + (size_t)(r.second + i) * 3) * 4], &fm.leaf_soup[r.first + i], 48);
-                    }
-                // walk words of every record (words 16..19; walk.h, traverse_ref): the second formulation of the reference walk
-                // addresses nodes by their byte offset in the image and takes a leaf's slot range ready-made
-                for (const DAccel &A : fm.accels) {
-                    const uint32_t tree0 = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
-                    for (uint32_t i = 0, e = extent(nb, A.node_base, fm.nodes.size()); i < e; ++i) {
-                        uint32_t *rec = &img[((size_t)(A.lnode_base + i) * LDS_NODE_STRIDE) * 4];
-                        const DNode &nd = fm.nodes[A.node_base + i];
-                        if (nd.meta & NODE_LEAF) { rec[16] = A.lprim_base + nd.link; rec[17] = NODE_LEAF; rec[18] = rec[16] + (nd.meta & 0xFFFFu); rec[19] = nd.pad; }
-                        else { rec[16] = tree0 + nd.link * LDS_NODE_STRIDE * 16u; rec[17] = 1u << (nd.meta & 3u); rec[18] = 0u; }
-                        rec[17] |= nd.meta & NODE_NOPRUNE;
-                    }
-                }
-                a->lds_accel_off = a->lds_soup_off + np_soup * 3u;
-                for (size_t i = 0; i < fm.accels.size(); ++i) {
-                    const DAccel &A = fm.accels[i];
-                    uint32_t *rec = &img[((size_t)a->lds_accel_off + i * LDS_ACCEL_UNITS) * 4];
-                    std::memcpy(rec, &A.minv, 96);
-                    rec[24] = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
-                    rec[25] = A.lprim_base; rec[26] = A.prim_base - A.lprim_base; rec[27] = A.flags;
-                    rec[28] = (uint32_t)A.parent; rec[29] = A.nchain; rec[30] = A.lone;
-                    for (int k = 0; k < MAX_CHAIN; ++k) rec[32 + k] = A.chain[k];
-                    std::memcpy(rec + 40, A.prune, sizeof A.prune);
-                    std::memcpy(rec + LDS_ACCEL_DOOR * 4, A.door, sizeof A.door);
-                }
-                // the origin-relative form's ranges (DRelAccel): offered only when no record would be rewritten for two accels
-                if (fm.accels.size() <= L0_REL_MAX_ACCELS) {
-                    bool own = true;
-                    for (size_t i = 0; i < fm.accels.size(); ++i)
-                        for (size_t j = 0; j < i; ++j) {
-                            const DAccel &A = fm.accels[i], &B = fm.accels[j];
-                            own = own && A.lnode_base != B.lnode_base && (((A.flags | B.flags) & AF_MESH) != 0u || A.lprim_base != B.lprim_base);
-                        }
-                    for (const DAccel &A : fm.accels) {
-                        DRelAccel r{};
-                        r.node_off = a->lds_node_off * 16u + A.lnode_base * LDS_NODE_STRIDE * 16u;
-                        r.node_n = extent(nb, A.node_base, fm.nodes.size());
-                        r.slot0 = A.lprim_base;
-                        r.slot_n = (A.flags & AF_MESH) ? 0u : extent(pb, A.prim_base, fm.primref.size());
-                        own = own && (size_t)r.node_off + (size_t)r.node_n * LDS_NODE_STRIDE * 16u <= (size_t)a->lds_prim_off * 16u && r.slot0 + r.slot_n <= np_soup;
-                        a->l0_rel.push_back(r);
-                    }
-                    if (!own) a->l0_rel.clear();
-                }
+            std::vector<uint32_t> img;
+            if (make_lds_image(a, big_mesh_tris, img)) {
                 stage.add(a->lds_image, img);
-                a->lds_image_n16 = (uint32_t)n16;
                 set_lds_limits(LDS_MAX, true);
                 a->ldss_blocks = (uint32_t)cus;
             }
+            FlatScene &fm = a->flat;
             stage.add(a->accels, fm.accels); // with the compact bases
             if (a->accel_image_n16) { // the accel records alone, global bases in unit [6] (the LDS-resident image carries compact ones)
                 std::vector<uint32_t> img((size_t)a->accel_image_n16 * 4, 0u);
@@ -310,6 +396,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.lds_image_n16, y.lds_image_n16); swap(x.lds_node_off, y.lds_node_off); swap(x.lds_prim_off, y.lds_prim_off);
     swap(x.lds_soup_off, y.lds_soup_off); swap(x.lds_accel_off, y.lds_accel_off);
     swap(x.ldss_blocks, y.ldss_blocks); swap(x.cus, y.cus); swap(x.l0_rel, y.l0_rel);
+    swap(x.lds_pairs, y.lds_pairs); swap(x.pair_refusal, y.pair_refusal); swap(x.pair_rel, y.pair_rel);
     swap(x.stack_depth, y.stack_depth); swap(x.stack_depth_fast1, y.stack_depth_fast1); swap(x.max_blocks, y.max_blocks); swap(x.max_blocks_fast, y.max_blocks_fast);
     swap(x.wf_blocks, y.wf_blocks); swap(x.wf_blocks_fast, y.wf_blocks_fast); swap(x.queue_blocks, y.queue_blocks);
     swap(x.queue_default, y.queue_default); swap(x.prune_default, y.prune_default); swap(x.queue_min_items, y.queue_min_items); swap(x.specular_small_items, y.specular_small_items);
@@ -325,6 +412,8 @@ void rebuild_tables(const lg_accel *ca, bool fast) {
     next->scene = a->scene;
     next->device = a->device;
     next->prune = a->prune == 1 || a->flat.has_records ? 1 : a->prune; // (what the tables hold stays in them)
+    next->node_pairs = a->node_pairs; // (the LDS image in the form the switch asks for now)
+    next->image_prune = a->prune;     // (... by the caller's own setting of the pruned walk, not by what the tables must hold)
     build_and_upload(next.get(), fast || a->flat.has_fast); // throws: `a` is untouched
     next->prune = a->prune;
     // (bit patterns, not values: a NaN bound of a degenerate scene equals itself here)

@@ -729,6 +729,36 @@ int lg_accel_last_l0_relative(const lg_accel *a) { // the form the last level-0 
     std::lock_guard<std::mutex> g(a->mtx);
     return a->last_l0_relative;
 }
+// The LDS image lg_accel_from would make for this scene, without a device (accel.cpp, scene_lds_image): its 32-bit words into `words` (at most
+// `cap` of them), info = {16-byte units, node offset, primref offset, leaf-record offset, accel-record offset (units), 1 if pair records,
+// accels, node records of the flat tables}.  Returns the number of words, 0 when the tables do not fit in LDS, -1 on an error.
+int64_t lg_scene_lds_image(const lg_scene *s, int pairs, uint32_t *words, size_t cap, uint32_t *info) {
+    long long n = 0;
+    int rc = guarded([&] {
+        std::vector<uint32_t> img;
+        uint32_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (!scene_lds_image(s->s, pairs != 0, img, inf)) return;
+        n = (long long)img.size();
+        for (size_t i = 0; words && i < img.size() && i < cap; ++i) words[i] = img[i];
+        for (int i = 0; info && i < 8; ++i) info[i] = inf[i];
+    });
+    return rc ? -1 : n;
+}
+int lg_accel_set_node_pairs(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("node pairs must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    const bool before = a->node_pairs;
+    a->node_pairs = enabled == 1;
+    if (a->node_pairs != before && a->ldss_blocks) { // the LDS image is re-made in the other form (with every other table: one path, one upload)
+        int rc = guarded([&] { rebuild_tables(a, false); });
+        if (rc) { a->node_pairs = before; return rc; }
+    }
+    return 0;
+}
+int lg_accel_last_node_pairs(const lg_accel *a) { // the records the last launch over the LDS-resident scene walked: 1 pair records, 0 node records; -1 before the first
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->last_node_pairs;
+}
 // The device-free part of that form's gate for a scene and its own camera (host.cpp, l0_relative_camera / l0_relative_origins): the number
 // of accels, and the camera's origin in each accel's local space in origins[3 * accel ..] (at most `cap` accels are written), when the
 // camera's rays share one origin that is the same bits in every accel's frame of every lane; 0 when they do not; -1 on an error.

@@ -61,6 +61,13 @@ constexpr uint32_t LDS_NODE_STRIDE = 5u;
 // [10..12] the pruned walk's constants of the level: {centre x, y}, {centre z, size}, {e0, e2} (DAccel::prune).
 // [13..15] the door record (DAccel::door); word [30] of unit [7]: DAccel::lone.
 constexpr uint32_t LDS_ACCEL_UNITS = 16u;
+// The pair form of the image (pairs_host.h has the builder and the words' range checks): a 112-byte pair record per interior node -- two
+// boxes, then {first child's word, second child's word, 1 << split axis, 0} -- and a 64-byte slot per tree for its root record (node 0's
+// box, then its word).  A child word: an interior child = the byte offset of its own pair record; a leaf child = PAIR_LEAF | first slot
+// (PAIR_SLOT_BITS bits) | slot count << PAIR_SLOT_BITS (PAIR_COUNT_BITS bits).
+constexpr uint32_t PAIR_REC_BYTES = 112u, PAIR_ROOT_BYTES = 64u, PAIR_WORDS_OFF = 96u, PAIR_ROOT_WORD_OFF = 48u;
+constexpr uint32_t PAIR_LEAF = 0x80000000u, PAIR_SLOT_BITS = 16u, PAIR_COUNT_BITS = 15u;
+constexpr uint32_t PAIR_SLOT_MAX = (1u << PAIR_SLOT_BITS) - 1u, PAIR_COUNT_MAX = (1u << PAIR_COUNT_BITS) - 1u;
 constexpr uint32_t LDS_ACCEL_DOOR = 13u;
 // lg_accel_set_level_door / LASGUN_LEVEL_DOOR (DParams::level_door): bit 0 the probe at a nested accel's door, bit 1 a lone mesh and
 // its group walked as one level (walk.h, the ST_ENTER block)
@@ -367,8 +374,16 @@ struct DParams {
     // origin-relative form, 0 for the absolute form (launch.cpp, l0_relative: the gate); set for that one launch alone
     uint32_t l0_rel_n;
     DRelAccel l0_rel[L0_REL_MAX_ACCELS];
+    // The pair form of the LDS image (pairs_host.h; walk.h, traverse_ref<.., PAIR>): lds_pairs != 0 says that lds_image holds
+    // PAIR records -- the two children's boxes of every interior node, 112 bytes -- and one root record per tree in place of the node
+    // records; an accel record's unit [6].x is then its ROOT record's byte offset.  Every kernel that walks the plain exact form from LDS
+    // takes the pair step then (walk.h, walk<>); the pruned walk is launched from the L2 tables while the accel holds this form.
+    uint32_t lds_pairs;
+    struct { uint32_t root_off, pair_off, pair_n, pad; } pair_rel[L0_REL_MAX_ACCELS]; // l0_rel's node ranges in the pair form: bytes, bytes, records
 };
 static_assert(sizeof(DParams) <= 4096, "DParams is passed by value: a kernel's arguments are at most 4 KB");
+// does a closest / shadow pass of the level-by-level pipeline launched with these parameters walk the pair form of the LDS image?  (the plain exact walk from LDS alone)
+inline bool wf_takes_pairs(const DParams &P, bool fast) { return P.lds_image && P.lds_pairs && !fast && !P.prune; }
 
 // A radiance query's level 0 (k_radiance.hip), beside the DParams of its chunk: the caller's buffers and where the chunk starts
 struct RadianceArgs {

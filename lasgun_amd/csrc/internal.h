@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -479,6 +480,14 @@ struct lg_accel {
     std::vector<DRelAccel> l0_rel;
     mutable bool l0_relative = true;  // lg_accel_set_l0_relative
     mutable int last_l0_relative = -1; // the last level-0 closest launch of the level-by-level pipeline: 1 origin-relative, 0 absolute; -1 before the first
+    // the pair form of that image (dscene.h, DParams::lds_pairs; pairs_host.h): lds_image holds pair records in place of the node records --
+    // where the switch asks for them and every tree's ranges fit a child word (pair_refusal: why not, when the builder said no)
+    bool lds_pairs = false;
+    int image_prune = -2;             // rebuild_tables: the caller's lg_accel_set_prune setting while `prune` says which records the tables must hold (-2: `prune` itself)
+    std::string pair_refusal;
+    std::vector<std::array<uint32_t, 3>> pair_rel; // per accel: root record's byte offset, first pair record's, pair records (DParams::pair_rel)
+    mutable bool node_pairs = true;   // lg_accel_set_node_pairs (a change re-makes the image: rebuild_tables)
+    mutable int last_node_pairs = -1; // the last launch over the LDS-resident scene: 1 pair records, 0 node records; -1 before the first
     uint32_t ldss_blocks = 0;         // one 1024-lane workgroup per CU; 0 = variant unavailable for this scene
     uint32_t cus = 1;                 // compute units of the accel's device
     mutable bool lds_scene = true;    // lg_accel_set_lds_scene
@@ -515,7 +524,13 @@ struct lg_accel {
 };
 
 // the scene's tables are resident in LDS for this accel's launches (the reference walk; the kernels' 1024-lane forms)
-inline bool lds_resident(const lg_accel &a) { return !a.fast && a.lds_scene && a.ldss_blocks; }
+// the effective setting of the pruned walk (launch.cpp, base_params): LASGUN_PRUNE=0|1 replaces the scene-dependent default, lg_accel_set_prune wins
+inline bool prune_effective(const lg_accel &a) {
+    const bool dflt = prune_env() < 0 ? a.prune_default : prune_env() != 0;
+    return !a.fast && (a.prune < 0 ? dflt : a.prune != 0);
+}
+// (an image of pair records serves the plain exact walk alone: while the accel holds one, the pruned walk is launched from the L2 tables)
+inline bool lds_resident(const lg_accel &a) { return !a.fast && a.lds_scene && a.ldss_blocks && !(a.lds_pairs && prune_effective(a)); }
 
 constexpr size_t MAX_LAUNCH_CTXS = 8;
 constexpr unsigned MAX_WF_BANDS = 4; // bands of a big wavefront launch on internal streams (lg_accel_set_wf_split)
@@ -527,6 +542,7 @@ void check_queue_error(const lg_accel &a);
 void sync_checked(const lg_accel &a);
 DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);
 void set_lds_scene(const lg_accel &a, DParams &P);
+bool scene_lds_image(const Scene &scene, bool pairs, std::vector<uint32_t> &img, uint32_t info[8]); // accel.cpp: the LDS image of a scene alone, no device
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);

@@ -113,6 +113,8 @@ struct ShadowRefill {
 // expressions; each accel has node records and leaf slots of its own in the image, or the host does not ask for this form).  The same
 // operations on the same operands as walk.h's absolute forms -- slab_intersects_sg / _nc, the sphere slot -- so the same bits; the image
 // in HBM, which the shadow pass shares, is untouched.  Called by every lane of the workgroup between two barriers.
+// PAIR (the pair form of the image, pairs_host.h): both boxes of every pair record and the box of the root record, by the same subtractions.
+template <bool PAIR>
 __device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_t tid) {
     char *const img = reinterpret_cast<char *>(scn);
     const uint32_t *const prim = reinterpret_cast<const uint32_t *>(scn + P.lds_prim_off);
@@ -120,6 +122,18 @@ __device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_
     auto rewrite = [&](const uint32_t a, const uint32_t first, const uint32_t step) {
         const V3 o{P.l0_rel[a].o[0], P.l0_rel[a].o[1], P.l0_rel[a].o[2]};
         const uint32_t node_off = P.l0_rel[a].node_off, node_n = P.l0_rel[a].node_n, slot0 = P.l0_rel[a].slot0, slot_n = P.l0_rel[a].slot_n;
+        if (PAIR) { // records 0 .. pair_n - 1: the pair records (two boxes each); record pair_n: the root record
+            const uint32_t pair_off = P.pair_rel[a].pair_off, pair_n = P.pair_rel[a].pair_n, root_off = P.pair_rel[a].root_off;
+            for (uint32_t i = first; i <= pair_n; i += step) {
+                double *q = reinterpret_cast<double *>(img + (i < pair_n ? pair_off + i * PAIR_REC_BYTES : root_off));
+                q[0] = q[0] - o.x; q[1] = q[1] - o.y; q[2] = q[2] - o.z; // bmin - o
+                q[3] = q[3] - o.x; q[4] = q[4] - o.y; q[5] = q[5] - o.z; // bmax - o
+                if (i < pair_n) {
+                    q[6] = q[6] - o.x; q[7] = q[7] - o.y; q[8] = q[8] - o.z;
+                    q[9] = q[9] - o.x; q[10] = q[10] - o.y; q[11] = q[11] - o.z;
+                }
+            }
+        } else
         for (uint32_t i = first; i < node_n; i += step) {
             double *q = reinterpret_cast<double *>(img + (node_off + i * LDS_NODE_BYTES));
             q[0] = q[0] - o.x; q[1] = q[1] - o.y; q[2] = q[2] - o.z; // bmin - o
@@ -148,8 +162,10 @@ __device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_
 // W1 / W2: persistent traversal kernels of the wavefront pipeline (tile counter, per-lane LDS stack; LDSS as above).
 // L0: the launch is level 0's (rays from the camera, work items = the chunk's pixels in 8x8 tiles).
 // REL: level 0's closest pass with the image's node boxes and sphere slots relative to the camera's origin (l0_rewrite above).
-template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false>
+// PAIR: the image this launch copies holds pair records (P.lds_pairs).
+template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false, bool PAIR = false>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) wf_trace_kernel(const DParams P) {
+    static_assert(!PAIR || (!FAST && LDSS && !PRUNE && !REFILL), "the pair records: the plain exact walk from LDS");
     static_assert(!REL || (!FAST && !SHADOW && LDSS && L0 && !PRUNE && !REFILL), "the origin-relative form: level 0's closest pass from LDS");
     static_assert(!REFILL || (SHADOW && LDSS && !FAST), "the refilling walk: the LDS-resident shadow pass");
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
@@ -177,7 +193,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         copy_to_lds(dst, src, P.lds_image_n16, tid, stride);
         __syncthreads(); // the only workgroup-wide step; every wave reaches it before pulling tiles
         if (REL) { // (uniform: every lane of the workgroup is still here)
-            l0_rewrite(P, dst, tid);
+            l0_rewrite<PAIR>(P, dst, tid);
             __syncthreads();
         }
         scn = dst;
@@ -224,7 +240,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
             if (active) {
                 bool tie = false;
-                walk<LDSS, FAST, PRUNE, false, REL>(P, ray, false, stack, stride, b, scn, cnt, arec);
+                walk<LDSS, FAST, PRUNE, false, REL, PAIR ? 1 : 0>(P, ray, false, stack, stride, b, scn, cnt, arec);
                 (void)tie;
             }
             const bool hit = active && b.ref != NO_HIT;
@@ -280,7 +296,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
                 Ray sray = ray_new(hit_p, V3{L.pos[0], L.pos[1], L.pos[2]} - hit_p); // point.rs:43-44
                 Best b;
                 bool tie = false;
-                walk<LDSS, FAST, PRUNE>(P, sray, true, stack, stride, b, scn, cnt, arec);
+                walk<LDSS, FAST, PRUNE, false, false, PAIR ? 1 : 0>(P, sray, true, stack, stride, b, scn, cnt, arec);
                 (void)tie;
                 if (!(b.t < 1.0)) vis |= 1u << l; // point.rs:49
             }
@@ -440,6 +456,7 @@ hipError_t launch_wf_resolve(const DParams &P, uint32_t blocks, hipStream_t stre
     return hipGetLastError();
 }
 hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t blocks, uint32_t stack_depth, hipStream_t stream) {
+    const bool pairs = wf_takes_pairs(P, fast); // the image holds pair records: the plain exact walk from LDS in its pair form
     const bool ldss = P.lds_image && !fast; // LDS-resident scene: `blocks` = one workgroup per CU
     const bool l0 = !shadow && P.wf_level == 0u;
     const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
@@ -460,10 +477,17 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         // wave-uniform phases live on the lanes of a wave being at the SAME phase: 64 rays that start together through one tile stay roughly in
         // step, lanes restarted at the root while their neighbours are deep in the tree do not, and every phase then runs for a few lanes.
         static const bool refill_on = [] { const char *e = std::getenv("LASGUN_REFILL"); return e && e[0] == '1'; }();
-        const bool refill = refill_on && shadow && P.wf_level == 0u && (unsigned long long)P.ntiles >= 4ull * blocks * (block / 64u);
+        const bool refill = refill_on && !pairs && shadow && P.wf_level == 0u && (unsigned long long)P.ntiles >= 4ull * blocks * (block / 64u);
+#define LG_LAUNCH_PAIR(S, Z, R) hipLaunchKernelGGL((wf_trace_kernel<false, S, true, Z, false, false, R, true>), dim3(blocks), dim3(block), lds, stream, P)
+        if (pairs) {
+            if (shadow) LG_LAUNCH_PAIR(true, false, false);
+            else if (l0 && P.l0_rel_n) LG_LAUNCH_PAIR(false, true, true);
+            else if (l0) LG_LAUNCH_PAIR(false, true, false); else LG_LAUNCH_PAIR(false, false, false);
+        } else
         if (shadow) { if (refill) hipLaunchKernelGGL((wf_trace_kernel<false, true, true, false, false, true>), dim3(blocks), dim3(block), lds, stream, P); else LG_LAUNCH(false, true, true, false); }
         else if (l0 && P.l0_rel_n) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, true>), dim3(blocks), dim3(block), lds, stream, P); // (launch.cpp, l0_relative: the gate)
         else if (l0) LG_LAUNCH(false, false, true, true); else LG_LAUNCH(false, false, true, false);
+#undef LG_LAUNCH_PAIR
     }
     else { if (shadow) LG_LAUNCH(false, true, false, false); else if (l0) LG_LAUNCH(false, false, false, true); else LG_LAUNCH(false, false, false, false); }
 #undef LG_LAUNCH
@@ -508,7 +532,11 @@ hipError_t wf_set_lds_limit(size_t bytes, bool ldss) {
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, true>),
-        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true>)};
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, false, false, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, false, false, false, true>)};
     const void *plain_fns[] = {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, false, false>),

@@ -59,8 +59,7 @@ DParams base_params(const lg_accel &a, uint32_t w, uint32_t h) {
         P.accel_image = a.accel_image_n16 && accel_lds ? a.accel_image.p : nullptr; P.accel_image_n16 = a.accel_image_n16;
     }
     {   // LASGUN_PRUNE=0|1 replaces the scene-dependent DEFAULT (prune_env); lg_accel_set_prune still wins
-        const bool dflt = prune_env() < 0 ? a.prune_default : prune_env() != 0;
-        P.prune = !a.fast && (a.prune < 0 ? dflt : a.prune != 0) ? 1u : 0u;
+        P.prune = prune_effective(a) ? 1u : 0u;
     }
     {   // LASGUN_SHADOW_SKIP=0 / lg_accel_set_shadow_skip(0) (A/B, tests): every hit's shadow rays are walked.  The flag's argument (shade.h,
         // light_irrelevant) needs PI * intensity finite for every light; the visibility word holds 32 lights.
@@ -106,6 +105,15 @@ void ensure_aux_streams(const lg_accel &a, unsigned n) {
 void set_lds_scene(const lg_accel &a, DParams &P) {
     P.lds_image = a.lds_image.p; P.lds_image_n16 = a.lds_image_n16;
     P.lds_node_off = a.lds_node_off; P.lds_prim_off = a.lds_prim_off; P.lds_soup_off = a.lds_soup_off; P.lds_accel_off = a.lds_accel_off;
+    // ... which holds pair records in place of the node records when lds_pairs says so (dscene.h; never for a pruned launch: lds_resident)
+    const bool pairs = a.lds_pairs;
+    P.lds_pairs = pairs ? 1u : 0u;
+    a.last_node_pairs = pairs ? 1 : 0;
+    for (size_t i = 0; i < L0_REL_MAX_ACCELS; ++i) {
+        const bool have = pairs && a.pair_rel.size() <= L0_REL_MAX_ACCELS && i < a.pair_rel.size();
+        P.pair_rel[i].root_off = have ? a.pair_rel[i][0] : 0u; P.pair_rel[i].pair_off = have ? a.pair_rel[i][1] : 0u; P.pair_rel[i].pair_n = have ? a.pair_rel[i][2] : 0u;
+        P.pair_rel[i].pad = 0u;
+    }
 }
 
 // ---- the two organisations that keep every recursion level's rays in arrays of their own (k_wavefront.hip, k_queue.hip) -------------

@@ -86,7 +86,7 @@ static const uint32_t *query_order_of(const lg_accel &a, lg_accel::LaunchCtx &c,
 struct TraversalGrid { uint32_t blocks, depth; };
 static TraversalGrid traversal_grid(const lg_accel &a, DParams &P, hipError_t (*occupancy)(const DParams &, bool, uint32_t, int *), lg_accel::LaunchCtx &c,
                                     hipStream_t stream) {
-    const bool ldss = !a.fast && a.lds_scene && a.ldss_blocks;
+    const bool ldss = lds_resident(a);
     const uint32_t depth = a.fast ? a.stack_depth_fast1 : a.stack_depth;
     uint32_t cap = a.ldss_blocks;
     if (ldss) set_lds_scene(a, P);

@@ -1083,12 +1083,19 @@ struct NoRefill {
 // REL (the level-0 closest pass over an LDS-resident scene whose rays share one origin: k_wavefront.hip, l0_rewrite): the node records and
 // the sphere slots of the image are held relative to their accel's local origin; everything read from the accel records or the global
 // tables -- cuboid slots, doors, entry transforms -- stays absolute and goes on using the lane's own ray.o.
-template <bool LDSS, bool FAST = false, bool PRUNE = false, bool COUNT = false, class RF = NoRefill, bool REL = false>
+// PAIR (the plain exact walk over the pair form of the LDS image: pairs_host.h): ST_NODE means "`cur` is the pair record of an
+// interior node whose own box is known to be hit".  A trip tests BOTH children's boxes -- the reference never culls a node by t (cuboid.rs:120),
+// so every child of a hit interior node has its box tested sooner or later, by the same operations on the same operands -- and goes to
+// the near one that is hit (pushing the far one if it is hit too), to the far one, or pops.  A missed child is never pushed: a stack entry,
+// like a child word of a record, is a hit child, typed (PAIR_LEAF: its slot range; otherwise its own pair record).  Node 0 of a level
+// has no parent: it is tested once, on entering the level, from the level's root record.
+template <bool LDSS, bool FAST = false, bool PRUNE = false, bool COUNT = false, class RF = NoRefill, bool REL = false, bool PAIR = false>
 __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, const bool anyhit, uint32_t *stack, const uint32_t stride,
                                              Best &best, const uint4 *scn, bool &tie, Counters &cnt, const uint4 *arec_in = nullptr,
                                              RF *rf = nullptr, const bool live = true) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!REL || (LDSS && !FAST && !PRUNE && !COUNT && !RF::enabled), "the origin-relative records: the plain exact walk from LDS");
+    static_assert(!PAIR || (LDSS && !FAST && !PRUNE && !COUNT && !RF::enabled), "the pair records: the plain exact walk from LDS");
     const uint4 *const arec = LDSS ? scn + P.lds_accel_off : (FAST ? nullptr : arec_in); // the accel records in LDS, if they are there (lvl_set)
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
 #ifdef LG_STAMPS
@@ -1148,6 +1155,24 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
         prune_limits(anyhit ? 1.0 : best.t);
     };
     if (PRUNE) prune_level();
+    // PAIR: a typed word -- a child word of a pair record, a stack entry -- becomes the lane's place
+    auto take_word = [&](const uint32_t w) __attribute__((always_inline)) {
+        cur = w; // (an interior child's pair record; read in ST_NODE only)
+        li = w & PAIR_SLOT_MAX; le = li + ((w >> PAIR_SLOT_BITS) & PAIR_COUNT_MAX); // (a leaf child's slots; read in ST_LEAF only)
+        state = (int32_t)w < 0 ? ST_LEAF : ST_NODE;
+    };
+    // PAIR: node 0 of level L (bvh.rs:472-473), once, from the level's root record; a miss with the level's stack empty exhausts the level
+    auto pair_root = [&]() __attribute__((always_inline)) {
+        const char *rec = reinterpret_cast<const char *>(scn) + L.node_base;
+        const double2 *q = reinterpret_cast<const double2 *>(rec);
+        const double2 a = q[0], b = q[1], c = q[2];
+        const uint32_t w = *reinterpret_cast<const uint32_t *>(rec + PAIR_ROOT_WORD_OFF);
+        const double bmin[3] = {a.x, a.y, b.x}, bmax[3] = {b.y, c.x, c.y};
+        const bool hit = REL ? slab_intersects_nc_rel(bmin, bmax, ray) : slab_intersects_nc(bmin, bmax, ray);
+        if (hit) take_word(w);
+        else state = ST_LEVEL_DONE;
+    };
+    if (PAIR) pair_root();
     LG_STAMP(0);
     for (;;) {
         // ---- phase A: interior nodes (bvh.rs:471-505), until no lane of the wave is at a node
@@ -1167,6 +1192,34 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
 #ifdef LG_STAMPS
             stamp_cnt[5] += (unsigned long long)__builtin_popcountll(__builtin_amdgcn_ballot_w64(state == ST_NODE));
 #endif
+            if constexpr (PAIR) {
+              if (at_node_l) {
+                // one pair record: seven ds_read_b128 -- both children's boxes, their words, 1 << split axis -- and two independent slab tests
+                const char *rec = reinterpret_cast<const char *>(scn) + cur;
+                const double2 *q = reinterpret_cast<const double2 *>(rec);
+                const double2 a0 = q[0], a1 = q[1], a2 = q[2], b0 = q[3], b1 = q[4], b2 = q[5];
+                const uint4 w = *reinterpret_cast<const uint4 *>(rec + PAIR_WORDS_OFF);
+                const uint32_t popped = stk[(int)(sp - 1u) * (int)stride];
+                const double amin[3] = {a0.x, a0.y, a1.x}, amax[3] = {a1.y, a2.x, a2.y}, bmin[3] = {b0.x, b0.y, b1.x}, bmax[3] = {b1.y, b2.x, b2.y};
+                bool hit_a, hit_b;
+                if (SG < 8) {
+                    double tx, ty, tz;
+                    if (REL) { hit_a = slab_intersects_sg_rel<SG & 7>(amin, amax, ray); hit_b = slab_intersects_sg_rel<SG & 7>(bmin, bmax, ray); }
+                    else { hit_a = slab_intersects_sg<SG & 7>(amin, amax, ray, tx, ty, tz); hit_b = slab_intersects_sg<SG & 7>(bmin, bmax, ray, tx, ty, tz); }
+                } else if (REL) { hit_a = slab_intersects_nc_rel(amin, amax, ray); hit_b = slab_intersects_nc_rel(bmin, bmax, ray); }
+                else { hit_a = slab_intersects_nc(amin, amax, ray); hit_b = slab_intersects_nc(bmin, bmax, ray); }
+                const bool neg = ((SG < 8 ? (uint32_t)SG : negmask) & w.z) != 0u; // dir_is_neg[axis] (bvh.rs:496)
+                const uint32_t near_w = neg ? w.y : w.x, far_w = neg ? w.x : w.y;
+                const bool near_hit = neg ? hit_b : hit_a, far_hit = neg ? hit_a : hit_b;
+                const bool both = near_hit && far_hit, any = near_hit || far_hit, can_pop = sp != base;
+                stk[sp * stride] = far_w; // counts only if sp advances: both hit (bvh.rs:493-504)
+                const uint32_t next = near_hit ? near_w : far_hit ? far_w : popped;
+                sp = sp + (both ? 1u : 0u) - (!any && can_pop ? 1u : 0u);
+                cur = next;
+                li = next & PAIR_SLOT_MAX; le = li + ((next >> PAIR_SLOT_BITS) & PAIR_COUNT_MAX);
+                state = (!any && !can_pop) ? ST_LEVEL_DONE : (int32_t)next < 0 ? ST_LEAF : ST_NODE;
+              }
+            } else
             if (at_node_l) {
                 // the record's walk words: interior -> (second child's cursor, 1 << split axis, -), leaf -> (first slot, NODE_LEAF, last slot + 1)
                 double bmin[3], bmax[3];
@@ -1289,11 +1342,12 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
             if (FAST) limit = prune_limit(best.t, anyhit);
             if (PRUNE && !anyhit) prune_limits(best.t);
             if (done) state = ST_DONE;
-            else if (sp != base) { --sp; cur = stk[sp * stride]; state = ST_NODE; }
+            else if (sp != base) { --sp; if (PAIR) take_word(stk[sp * stride]); else { cur = stk[sp * stride]; state = ST_NODE; } }
             else state = ST_LEVEL_DONE;
         }
         LG_STAMP(2);
-        bool at_slot_l = state == ST_LEAF; // (carried like at_node_l above)
+        // (PAIR: an entry popped at the end of a mesh leaf may be a leaf itself -- the next trip of the outer loop walks it, not the slot loop)
+        bool at_slot_l = state == ST_LEAF && !(PAIR && mesh); // (carried like at_node_l above)
         bool more_prims = wave_any(at_slot_l);
         while (more_prims) {
 #ifdef LG_STAMPS
@@ -1357,11 +1411,11 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                     if (early && t < 1.0) state = ST_DONE; // occluded: point.rs:49 only asks isect.t < 1.0
                 }
                 if (state == ST_LEAF && li >= le) { // leaf exhausted: next pending node of this level, or the level is done
-                    if (sp != base) { --sp; cur = popped; state = ST_NODE; }
+                    if (sp != base) { --sp; if (PAIR) take_word(popped); else { cur = popped; state = ST_NODE; } }
                     else state = ST_LEVEL_DONE;
                 }
             }
-            at_slot_l = state == ST_LEAF;
+            at_slot_l = state == ST_LEAF && !(PAIR && mesh);
             more_prims = wave_any(at_slot_l);
 #ifdef LG_STAMPS
             stamp_cnt[2] += 1;
@@ -1402,7 +1456,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
             }
             if (shut) {
                 if (li < le) state = ST_LEAF;
-                else if (sp != base) { --sp; cur = stk[sp * stride]; state = ST_NODE; }
+                else if (sp != base) { --sp; if (PAIR) take_word(stk[sp * stride]); else { cur = stk[sp * stride]; state = ST_NODE; } }
                 else state = ST_LEVEL_DONE; // the parent level is exhausted as well
             } else {
                 lvl_set<LDSS, FAST>(P, arec, L, enter);
@@ -1434,6 +1488,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                 if (PRUNE) prune_level();
                 cur = L.node_base;
                 state = ST_NODE; // node 0 is tested when visited (bvh.rs:472-473)
+                if (PAIR) pair_root(); // ... or here, from the level's root record
             }
         }
         LG_STAMP(4);
@@ -1486,7 +1541,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                 if (PRUNE) prune_level();
                 LG_RSTAMP(4);
                 if (li < le) state = ST_LEAF;
-                else if (sp != base) { --sp; cur = stk[sp * stride]; state = ST_NODE; }
+                else if (sp != base) { --sp; if (PAIR) take_word(stk[sp * stride]); else { cur = stk[sp * stride]; state = ST_NODE; } }
                 else state = ST_LEVEL_DONE; // the parent level is exhausted as well
                 LG_RSTAMP(5);
 #ifdef LG_STAMPS
@@ -1787,7 +1842,9 @@ __device__ __forceinline__ void traverse_fast(const DParams &P, const Ray &wray,
 //   * any-hit: an occluder counts if the reference tree would have tested it (the reference then finds it or one before it);
 //     "not occluded" stands unless a tie / NaN makes the reference's own answer depend on its visit order;
 // otherwise the ray is traced again with the reference walk over the tables in HBM / L2.
-template <bool LDSS, bool FAST, bool PRUNE = false, bool COUNT = false, bool REL = false>
+// PAIRSEL: which records the plain exact walk from LDS reads -- 0 node records, 1 pair records (a kernel that is compiled in both forms says
+// so), 2 what the image holds (P.lds_pairs, the same for every lane of the launch: one scalar branch per walk).  Every other form: node records.
+template <bool LDSS, bool FAST, bool PRUNE = false, bool COUNT = false, bool REL = false, int PAIRSEL = 2>
 __device__ __forceinline__ void walk(const DParams &P, const Ray &ray, const bool anyhit, uint32_t *stack, const uint32_t stride, Best &best,
                                      const uint4 *scn, Counters &cnt, const uint4 *arec = nullptr) {
     bool tie = false;
@@ -1797,6 +1854,11 @@ __device__ __forceinline__ void walk(const DParams &P, const Ray &ray, const boo
     }
     if (FAST) traverse_fast<COUNT>(P, ray, anyhit, stack, stride, best, scn, tie, cnt);
     else
+    if (LDSS && !FAST && !PRUNE && !COUNT && PAIRSEL != 0) {
+        constexpr bool CAN = LDSS && !FAST && !PRUNE && !COUNT; // (so that the pair form is only ever instantiated where it exists)
+        if (PAIRSEL == 1 || P.lds_pairs != 0u) traverse_ref<LDSS, FAST, PRUNE, COUNT, NoRefill, REL, CAN>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);
+        else traverse_ref<LDSS, FAST, PRUNE, COUNT, NoRefill, REL>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);
+    } else
     traverse_ref<LDSS, FAST, PRUNE, COUNT, NoRefill, REL>(P, ray, anyhit, stack, stride, best, scn, tie, cnt, arec);
     if (!FAST) return;
     if (COUNT) dbg_event(P, 9.0, tie ? 1.0 : 0.0, best.t, (double)best.ref);
