@@ -239,6 +239,8 @@ pub use sys::lg_gather_out as GatherOut;
 pub fn radiance_gather_lanes(n_poses: usize, n_dirs: usize, lanes: i32) -> i32 { unsafe { sys::lg_radiance_gather_lanes(n_poses, n_dirs, lanes) } }
 /// A camera as the kernels read it (`lg_view`, 120 bytes): what `Accel::capture_views` renders from.
 pub use sys::lg_view as View;
+/// The planes of `Accel::capture_view_features_device` (`lg_view_features`, 48 bytes): `Features`' five and the world-space hit point.
+pub use sys::lg_view_features as ViewFeatures;
 /// The view of a look-at camera (`lg_view_look_at`): what a scene's own camera holds after `set_perspective_camera(param)` (or
 /// `set_orthographic_camera(param)` with `perspective` false), `look_at` and `set_supersampling`, byte for byte.  No device is touched.
 pub fn view_look_at(perspective: bool, param: f64, origin: [f64; 3], look: [f64; 3], up: [f64; 3], supersampling: u8) -> View {
@@ -569,6 +571,46 @@ impl<'s> Accel<'s> {
     pub unsafe fn capture_features_device(&self, width: u32, height: u32, rect: (u32, u32, u32, u32), dev_out: &sys::lg_features, dev_material_rgb: *const f64,
                                           hip_stream: *mut std::ffi::c_void) {
         if sys::lg_capture_features_device(self.ptr, width, height, rect.0, rect.1, rect.2, rect.3, dev_out, dev_material_rgb, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
+    /// View features (`lg_capture_view_features`): `capture_features`' planes and the world-space hit point for K views in ONE call, K whole
+    /// films.  Every plane given is views.len()*width*height long, the element of (v, x, y) at v*width*height + y*width + x.  depth and
+    /// point are means over the samples that hit (+inf and (0, 0, 0): none); point is what reprojects a pixel of one view into another.
+    /// The views share `samples_root`.  `material_rgb`: `material_count()` colours, summed per hit material (required with albedo).
+    #[allow(clippy::too_many_arguments)]
+    pub fn capture_view_features(&self, views: &[View], width: u32, height: u32, depth: Option<&mut [f32]>, normal: Option<&mut [[f32; 3]]>,
+                                 albedo: Option<&mut [[f32; 3]]>, coverage: Option<&mut [f32]>, id: Option<&mut [[u32; 4]]>, point: Option<&mut [[f32; 3]]>,
+                                 material_rgb: Option<&[[f64; 3]]>) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_view_features>() == 48);
+        let n = views.len().checked_mul((width as usize) * (height as usize)).expect("capture_view_features: views.len() * width * height overflows usize");
+        assert!(depth.as_ref().map_or(true, |p| p.len() == n) && normal.as_ref().map_or(true, |p| p.len() == n)
+                && albedo.as_ref().map_or(true, |p| p.len() == n) && coverage.as_ref().map_or(true, |p| p.len() == n)
+                && id.as_ref().map_or(true, |p| p.len() == n) && point.as_ref().map_or(true, |p| p.len() == n),
+                "capture_view_features: planes of views.len() * width * height pixels");
+        assert!(material_rgb.map_or(true, |m| m.len() == self.material_count()), "capture_view_features: material_count() colours");
+        let out = sys::lg_view_features {
+            depth: depth.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            normal: normal.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            albedo: albedo.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+            coverage: coverage.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            id: id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+            point: point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f32),
+        };
+        let rc = unsafe {
+            sys::lg_capture_view_features(self.ptr, views.as_ptr(), views.len(), width, height, &out, material_rgb.map_or(std::ptr::null(), |m| m.as_ptr() as *const f64))
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `capture_view_features` into device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked
+    /// for); `views` stays a host slice, copied before the call returns
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device, views.len()*width*height pixels a plane and `material_count()` * 3
+    /// doubles (the library checks what HIP can tell it).
+    pub unsafe fn capture_view_features_device(&self, views: &[View], width: u32, height: u32, dev_out: &sys::lg_view_features, dev_material_rgb: *const f64,
+                                               hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_capture_view_features_device(self.ptr, views.as_ptr(), views.len(), width, height, dev_out, dev_material_rgb, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
     }

@@ -333,6 +333,33 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                                  const double *dev_material_rgb, void *hip_stream) const {
         if (lg_capture_features_device(h_, width, height, x0, y0, x1, y1, &dev_out, dev_material_rgb, hip_stream)) throw Error(lg_last_error());
     }
+    // view features (lg_capture_view_features): the same planes and the world-space hit point for K views in ONE call, K whole films -- the
+    // element of (v, x, y) at v*width*height + y*width + x, every vector sized here to n_views*width*height.  A null vector pointer = that
+    // plane is not asked for.  depth and point are means over the samples that hit (+inf and (0, 0, 0): none); the views share samples_root.
+    struct ViewFeatures : Features {
+        std::vector<std::array<float, 3>> *point = nullptr;   // reprojects a pixel of one view into another
+    };
+    void capture_view_features(const std::vector<lg_view> &views, uint32_t width, uint32_t height, const ViewFeatures &out,
+                               const std::vector<std::array<double, 3>> *material_rgb = nullptr) const {
+        static_assert(sizeof(lg_view_features) == 48, "lg_view_features: six pointers");
+        const size_t n = views.size() * (size_t)width * height;
+        if (material_rgb && material_rgb->size() != material_count()) throw Error("capture_view_features: material_count() colours");
+        auto sized = [n](auto *v) { if (v) v->resize(n); return v && n ? &(*v)[0] : nullptr; };
+        lg_view_features f{};
+        f.depth = sized(out.depth); f.coverage = sized(out.coverage);
+        if (auto *p = sized(out.normal)) f.normal = p->data();
+        if (auto *p = sized(out.albedo)) f.albedo = p->data();
+        if (auto *p = sized(out.id)) f.id = p->data();
+        if (auto *p = sized(out.point)) f.point = p->data();
+        if (lg_capture_view_features(h_, views.data(), views.size(), width, height, &f, material_rgb && !material_rgb->empty() ? (*material_rgb)[0].data() : nullptr))
+            throw Error(lg_last_error());
+    }
+    // the same planes enqueued into device memory on hip_stream (lg_capture_view_features_device): dev_out's members are device pointers;
+    // `views` stays a host array, copied before the call returns
+    void capture_view_features_device(const std::vector<lg_view> &views, uint32_t width, uint32_t height, const lg_view_features &dev_out,
+                                      const double *dev_material_rgb, void *hip_stream) const {
+        if (lg_capture_view_features_device(h_, views.data(), views.size(), width, height, &dev_out, dev_material_rgb, hip_stream)) throw Error(lg_last_error());
+    }
     // the order a query's rays are walked in (lg_accel_set_query_order): 0 as given (default), 1 sorted on the device by a coherence key
     void set_query_order(int order) const {
         if (lg_accel_set_query_order(h_, order)) throw Error(lg_last_error());

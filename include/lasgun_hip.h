@@ -792,6 +792,51 @@ int lg_capture_views(const lg_accel *, const lg_view *views, size_t n_views, uin
                      uint8_t *rgba, double *rgb);                                   /* host arrays; synchronous */
 int lg_capture_views_device(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
                             void *dev_rgba, double *dev_rgb, void *hip_stream);
+/* View features: lg_capture_features' planes for the K cameras of a view batch in one call -- first-hit depth, shading normal, albedo,
+ * coverage and ids beside every film of lg_capture_views, for a denoiser, a compositor, a segmentation label --, and one plane more that
+ * only matters once there is more than one view: the world-space hit POINT, which is what reprojects a pixel of view A into view B
+ * (temporal and multi-view denoising, stereo consistency, label transfer).  Without rebuilding the scene and the accel per camera and
+ * without writing lg_view_rays' rays (48 bytes each) and lg_intersect's hits (96 bytes each): the rays are made in the kernel and at most
+ * 60 bytes a pixel are written.  An EXTRA: no counterpart in the reference.  It is the two contracts above joined; nothing in it is new
+ * arithmetic except point. */
+typedef struct lg_view_features {
+    float    *depth;     /* [n_views*width*height]     */
+    float    *normal;    /* [n_views*width*height][3]  */
+    float    *albedo;    /* [n_views*width*height][3]  */
+    float    *coverage;  /* [n_views*width*height]     */
+    uint32_t *id;        /* [n_views*width*height][4]: kind, prim, instance, material -- the last 16 bytes of an lg_hit */
+    float    *point;     /* [n_views*width*height][3]: world space */
+} lg_view_features;      /* 48 bytes; each pointer may be NULL, all NULL is an error */
+/* lg_view_features itself is always a host struct; in the device form its members are device pointers.
+ * Addressing: the element of (v, x, y) is at v*width*height + y*width + x, times the plane's elements per pixel -- whole films, as
+ * lg_capture_views has them; there is no rectangle.  Every pixel of every requested plane is written exactly once; nothing outside
+ * n_views*width*height elements is touched; a plane that is not requested is not touched.
+ * Rays: the S = samples_root^2 rays of (v, x, y) are lg_view_rays' rays for view v and that pixel, s = 0 .. S-1 in camera order: the
+ * expression spelled out under lg_capture_views.
+ * Hit: sample s's hit is what lg_intersect returns for that ray, bit for bit, in the accel's traversal mode (reference, pruned,
+ * LDS-resident scene, fast mode); a hit iff kind != 0.  lg_accel_set_query_order plays no part (there is no ray array to sort), and neither
+ * do the interleave, subset and organisation settings of the captures.
+ * depth, normal, albedo, coverage, id: lg_capture_features' accumulators, order and roundings word for word -- all f64, from +0.0, s
+ * ascending, a miss adds nothing; inv = 1.0 / (double)S; depth the mean over the hits and +INFINITY where there are none; id sample 0's.
+ * material_rgb follows the same rule (lg_accel_material_count x 3 doubles; required iff albedo is requested, ignored otherwise).  For
+ * lg_accel_view's view these five planes are lg_capture_features' bytes for the full film.
+ * point: psum[3] starts at +0.0; a hit adds lg_hit::p per component, the value lg_intersect reports.
+ *   point[c] = nhit ? (float)(psum[c] * (1.0 / (double)nhit)) : 0.0f
+ * -- depth's divisor, and lg_hit's zeros on a miss.
+ * views is a HOST array in both forms: it is copied before the call returns (through pinned staging, on the stream).
+ * Host form (synchronous): the planes come back into staging and reach the caller's arrays after the synchronise, so an error on the way
+ * leaves them as they were.  Device form: it only enqueues on hip_stream, ONE launch whatever the size; one stream at a time per accel.
+ * n_views == 0 is a successful no-op, answered before every other check.
+ * Errors (non-zero, lg_last_error, nothing launched, no output touched): a NULL accel, views or out; all six planes NULL; albedo without
+ * material_rgb; width or height 0, or above 2^32 - 8 (a tile's pixel coordinates are 32-bit); a samples_root of 0 or above 256;
+ * reserved != 0; views of one call that differ in samples_root (the uniform-samples rule); n_views * ceil(width/8) * ceil(height/8) >
+ * 2^32 - 1 (8 x 8 pixel tiles are counted in 32 bits; the samples run in a loop and do not count); a plane's byte size beyond SIZE_MAX;
+ * in the device form a plane or table that is not device memory of the accel's device, is misaligned (id 16-byte aligned, material_rgb 8,
+ * the float planes 4) or ends beyond its allocation.  More than 32 lights or a deep recursion is NOT an error here: nothing is shaded. */
+int lg_capture_view_features(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
+                             const lg_view_features *out, const double *material_rgb);          /* host arrays; synchronous */
+int lg_capture_view_features_device(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
+                                    const lg_view_features *dev_out, const double *dev_material_rgb, void *hip_stream);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.
  * Results are identical bytes either way, in the caller's order. Any other value: non-zero return, lg_last_error.
  * The walk keeps a wave's 64 rays in step; rays that arrive in no particular order (collision probes, visibility between arbitrary

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, CView, CLens, CFeatures, CScanOut, CGatherOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CGatherOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -103,6 +103,7 @@ _EXTRA = {
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
     **VIEWS_SIGNATURES,
+    **VIEW_FEATURES_SIGNATURES,
 }
 
 
@@ -127,6 +128,9 @@ GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
 GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
 _FEATURE_SHAPE = {"depth": ((), _np.float32), "normal": ((3,), _np.float32), "albedo": ((3,), _np.float32), "coverage": ((), _np.float32),
                   "id": ((4,), _np.uint32)}
+assert _C.sizeof(CViewFeatures) == 48, "lg_view_features is 48 bytes"
+VIEW_FEATURE_PLANES = FEATURE_PLANES + ("point",)  # lg_view_features' members, in its order
+_VIEW_FEATURE_SHAPE = dict(_FEATURE_SHAPE, point=((3,), _np.float32))
 
 
 def Lens(kind, origin, right, up, forward, fov_deg=180.0):
@@ -1038,6 +1042,49 @@ class HipApi(Api):
                      self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- view features (include/lasgun_hip.h, lg_capture_view_features*): the feature planes and the hit point for K views in one call
+    def capture_view_features(self, accel, views, w, h, planes=VIEW_FEATURE_PLANES, material_rgb=None, into=None):
+        """The feature planes of the accel's scene seen from K Views, K whole w x h films in ONE call: a dict of the planes asked for (any of
+        "depth", "normal", "albedo", "coverage", "id", "point"), plane p of view v at out[p][v] -- float32 (K, h, w) depth and coverage,
+        float32 (K, h, w, 3) normal, albedo and point, uint32 (K, h, w, 4) id = kind, prim, instance, material of sample 0.  Normal and
+        albedo are means over ALL the pixel's samples (premultiplied by coverage); depth and the world-space point are means over those
+        that hit (+inf and (0, 0, 0): none).  The views share samples_root.
+        material_rgb: (material_count, 3) float64, the colour summed per hit material; default default_albedo_table(accel).
+        `into`: a dict of C-contiguous arrays of those shapes, written in place."""
+        tab = _views(views)
+        k = len(tab)
+        planes = tuple(planes)
+        if any(p not in VIEW_FEATURE_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (VIEW_FEATURE_PLANES,))
+        out = {}
+        for p in planes:
+            shape, dt = _VIEW_FEATURE_SHAPE[p]
+            arr = into[p] if into is not None else _np.zeros((k, h, w) + shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != (k, h, w) + shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, (k, h, w) + shape))
+            out[p] = arr
+        table = None
+        if "albedo" in out:
+            table = _np.ascontiguousarray(self.default_albedo_table(accel) if material_rgb is None else material_rgb, dtype=_np.float64)
+            if table.shape != (self.material_count(accel), 3):
+                raise ValueError("material_rgb: a (material_count, 3) array")
+        f = CViewFeatures(*[out[p].ctypes.data if p in out and out[p].size else None for p in VIEW_FEATURE_PLANES])
+        if self.call("capture_view_features", accel.h, _C.addressof(tab) if k else None, k, int(w), int(h), _C.addressof(f),
+                     table.ctypes.data if table is not None and table.size else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def capture_view_features_device(self, accel, views, w, h, depth_ptr=None, normal_ptr=None, albedo_ptr=None, coverage_ptr=None, id_ptr=None,
+                                     point_ptr=None, material_rgb_ptr=None, stream=None):
+        """Enqueue the same planes into device memory: each pointer K*w*h elements of its plane, film after film (id 16-byte aligned), or
+        None; material_rgb_ptr: material_count * 3 doubles in device memory, required with albedo_ptr.  `views` stays a host sequence of
+        View and is copied before the call returns."""
+        tab = _views(views)
+        f = CViewFeatures(*[int(p) if p is not None else None for p in (depth_ptr, normal_ptr, albedo_ptr, coverage_ptr, id_ptr, point_ptr)])
+        if self.call("capture_view_features_device", accel.h, _C.addressof(tab) if len(tab) else None, len(tab), int(w), int(h), _C.addressof(f),
+                     _C.c_void_p(int(material_rgb_ptr)) if material_rgb_ptr is not None else None, self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     def camera_samples(self, accel):
         """Rays per pixel of lg_camera_rays (the camera's supersamples)."""
         return int(self.call("camera_samples", accel.h))
@@ -1214,6 +1261,7 @@ api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=Fals
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
 api.Accel.views = lambda self, views, w, h, rgba=True, rgb=False: api.capture_views(self, views, w, h, rgba, rgb)  # accel.views(views, w, h)
+api.Accel.view_features = lambda self, views, w, h, planes=VIEW_FEATURE_PLANES, material_rgb=None: api.capture_view_features(self, views, w, h, planes, material_rgb)  # accel.view_features(views, w, h)
 
 # reference-shaped names at package level: `from lasgun_amd import Scene, Material, capture`
 Scene, Aggregate, Material, Camera, Film, Accel = api.Scene, api.Aggregate, api.Material, api.Camera, api.Film, api.Accel

@@ -190,6 +190,13 @@ VIEWS_SIGNATURES = {
     "capture_views_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# View features (include/lasgun_hip.h, lg_capture_view_features*): lg_capture_features' planes and the hit point for the K cameras of a
+# view batch in one call; the GPU library's alone.
+VIEW_FEATURES_SIGNATURES = {
+    "capture_view_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "capture_view_features_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 class CView(C.Structure):  # lg_view: 120 bytes, no padding
     _fields_ = [("origin", _D3), ("view", _D3), ("up", _D3), ("aux", _D3), ("image_plane_height", C.c_double), ("pixel_separation", C.c_double),
@@ -198,6 +205,10 @@ class CView(C.Structure):  # lg_view: 120 bytes, no padding
 
 class CFeatures(C.Structure):  # lg_features: five plane pointers, 40 bytes; NULL = not asked for
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p)]
+
+
+class CViewFeatures(C.Structure):  # lg_view_features: six plane pointers, 48 bytes; NULL = not asked for
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("coverage", C.c_void_p), ("id", C.c_void_p), ("point", C.c_void_p)]
 
 
 class CScanOut(C.Structure):  # lg_scan_out: six pointers, 48 bytes; NULL = not asked for

@@ -105,6 +105,13 @@ hipError_t launch_features(const DParams &P, float *depth, float *normal, float 
                            const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t features_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t features_set_lds_limit(size_t bytes, bool ldss);
+// k_view_features.hip: view features (lg_capture_view_features*) -- features_kernel over the K cameras of a table: global pixel tile
+// G = v * tiles_per_view + t per wave, a pixel per lane; only the planes that are not nullptr are written, film v's pixel at v * w * h + y * w + x
+// (V.rgba / V.rgb are not used)
+hipError_t launch_view_features(const DParams &P, const ViewArgs &V, float *depth, float *normal, float *albedo, float *coverage, void *id, float *point,
+                                const double *material_rgb, uint32_t nmat, const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t view_features_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t view_features_set_lds_limit(size_t bytes, bool ldss);
 hipError_t wf_trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, int *blocks_per_cu);
 hipError_t launch_queue(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t queue_occupancy(uint32_t stack_depth, size_t extra_lds, int *blocks_per_cu);
@@ -560,6 +567,9 @@ void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::L
 // One checked lg_capture_views* call (query.cpp; views_host.h): `views` is the HOST table, copied through pinned staging into a device table of
 // the call's own on `stream` before its launches; V.views and V.base_tile are set here
 void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream);
+// ... and the staging alone, for a call that launches a kernel of its own over the table (lg_capture_view_features*): the device table
+// of this call, released by subsets_enqueued() behind the launch or by subsets_abandoned() where the call fails before it
+const DView *stage_view_table(const DView *views, size_t n_views, lg_accel::LaunchCtx &c, hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

@@ -574,19 +574,24 @@ static lg_accel::LaunchCtx::KsTable &live_table(lg_accel::LaunchCtx &c) {
     c.ks_live.emplace_back(new lg_accel::LaunchCtx::KsTable());
     return *c.ks_live.back();
 }
-// A view batch (query.cpp, lg_capture_views*; the call checked there and in views_host.h): the K records go from the caller's host array
-// through pinned staging into a table of the call's own on the stream -- so the call only enqueues and the caller's array may be freed when
-// it returns --, then one level-0 query over the batch's pixel tiles.
-void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream) {
+// The K view records of a call (lg_capture_views*, lg_capture_view_features*) from the caller's host array through pinned staging into a
+// table of the call's own on the stream (live_table) -- so the call only enqueues and the caller's array may be freed when it returns.
+// The caller ends with subsets_enqueued() behind its launches, or subsets_abandoned() where it fails before them.
+const DView *stage_view_table(const DView *views, size_t n_views, lg_accel::LaunchCtx &c, hipStream_t stream) {
     static_assert(sizeof(DView) % sizeof(unsigned long long) == 0, "the table is staged as 64-bit words");
-    const size_t bytes = (size_t)V.n_views * sizeof(DView);
+    const size_t bytes = n_views * sizeof(DView);
+    lg_accel::LaunchCtx::KsTable &t = live_table(c);
+    t.stage.need(bytes);
+    std::memcpy(t.stage.p, views, bytes);
+    t.buf.alloc(std::max<size_t>(bytes / sizeof(unsigned long long), 128));
+    HIP_TRY(hipMemcpyAsync(t.buf.p, t.stage.p, bytes, hipMemcpyHostToDevice, stream));
+    return reinterpret_cast<const DView *>(t.buf.p);
+}
+// A view batch (query.cpp, lg_capture_views*; the call checked there and in views_host.h): the table, then one level-0 query over the
+// batch's pixel tiles.
+void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream) {
     try {
-        lg_accel::LaunchCtx::KsTable &t = live_table(c);
-        t.stage.need(bytes);
-        std::memcpy(t.stage.p, views, bytes);
-        t.buf.alloc(std::max<size_t>(bytes / sizeof(unsigned long long), 128));
-        HIP_TRY(hipMemcpyAsync(t.buf.p, t.stage.p, bytes, hipMemcpyHostToDevice, stream));
-        V.views = reinterpret_cast<const DView *>(t.buf.p);
+        V.views = stage_view_table(views, (size_t)V.n_views, c, stream);
         V.base_tile = 0;
         Level0Source src;
         src.views = &V;

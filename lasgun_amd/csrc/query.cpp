@@ -1,6 +1,6 @@
 // lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
-// lg_capture_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip and k_features.hip for the structured queries) on the caller's stream, sized like
+// lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
@@ -14,6 +14,7 @@
 #include "gather_host.h"
 #include "scan_host.h"
 #include "views_host.h"
+#include "view_features_host.h"
 #include "internal.h"
 
 static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hit, ng) == 32 && offsetof(lg_hit, ns) == 56 &&
@@ -695,6 +696,57 @@ extern "C" int lg_capture_features_device(const lg_accel *a, uint32_t w, uint32_
         feature_planes(*out, [&](auto *p, auto, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, npix * per_pixel * sizeof *p, align, what); });
         if (out->albedo) check_device_buffer(*a, dev_material_rgb, nmat * 3 * sizeof(double), 8, "material_rgb");
         enqueue_features(*a, w, h, x0, y0, x1, y1, *out, dev_material_rgb, false, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- view features (lg_capture_view_features*; k_view_features.hip): depth, normal, albedo, coverage, ids and hit points of the primary
+// hits of K cameras, K whole films' planes in one launch.  What needs no device -- the plane table, the NULL and alignment rules, the
+// film's limits, the tile count, the sizes -- is view_features_host.h's (and views_host.h's below it).
+// One capture enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers): the
+// K records through the launch context's pinned staging into a table of the call's own, then ONE launch over n_views * tiles_per_view
+// tiles -- no chunks: the outputs are the caller's, at most 60 bytes a pixel, and nothing is parked
+static void enqueue_view_features(const lg_accel &a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, const ViewShape &shape, const lg_view_features &out,
+                                  const double *material_rgb, hipStream_t stream) {
+    check_queue_error(a);
+    const std::vector<DView> table = to_dviews(views, n_views);
+    DParams P = base_params(a, w, h);
+    P.ss_root = shape.samples_root; // (the views' own: S = samples_root^2 walks a pixel)
+    P.ntiles = shape.pixel_tiles;
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    try {
+        const ViewArgs V{stage_view_table(table.data(), n_views, c, stream), (unsigned long long)n_views, w, h, shape.tiles_x, shape.tiles_per_view, 0ull, nullptr, nullptr};
+        const TraversalGrid g = traversal_grid(a, P, view_features_occupancy, c, stream);
+        HIP_TRY(launch_view_features(P, V, out.depth, out.normal, out.albedo, out.coverage, out.id, out.point, out.albedo ? material_rgb : nullptr,
+                                     (uint32_t)a.flat.material_pods.size(), a.accel_tri_base.p, a.fast, g.blocks, g.depth, stream));
+        subsets_enqueued(a, stream);
+    } catch (...) { subsets_abandoned(a, stream); throw; }
+}
+// Host form: the table goes up, the K films' planes come back into staging and reach the caller's arrays after the synchronise (an error
+// on the way leaves them as they were)
+extern "C" int lg_capture_view_features(const lg_accel *a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, const lg_view_features *out, const double *material_rgb) {
+    return guarded([&] {
+        if (n_views == 0) return;
+        const ViewShape shape = check_view_features(a, views, n_views, w, h, out, material_rgb);
+        std::lock_guard<std::mutex> g(a->mtx);
+        RoundTrip trip(*a);
+        lg_view_features dev = *out; // ... where a plane asked for becomes its device buffer
+        view_feature_planes(dev, [&](auto *&p, size_t per_pixel, size_t, const char *) { p = trip.staged(p, shape.pixels * per_pixel); });
+        // the table for albedo alone (a scene without materials: an element to point at, nothing copied)
+        const double *dtable = out->albedo ? trip.in(material_rgb, a->flat.material_pods.size() * 3) : nullptr;
+        trip.run([&] { enqueue_view_features(*a, views, n_views, w, h, shape, dev, dtable, a->stream); });
+    });
+}
+extern "C" int lg_capture_view_features_device(const lg_accel *a, const lg_view *views, size_t n_views, uint32_t w, uint32_t h, const lg_view_features *dev_out,
+                                               const double *dev_material_rgb, void *hip_stream) {
+    return guarded([&] {
+        if (n_views == 0) return;
+        const ViewShape shape = check_view_features(a, views, n_views, w, h, dev_out, dev_material_rgb);
+        check_view_features_alignment(*dev_out, dev_material_rgb);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        view_feature_planes(*dev_out, [&](auto *p, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, shape.pixels * per_pixel * sizeof *p, align, what); });
+        if (dev_out->albedo) check_device_buffer(*a, dev_material_rgb, a->flat.material_pods.size() * 3 * sizeof(double), 8, "material_rgb");
+        enqueue_view_features(*a, views, n_views, w, h, shape, *dev_out, dev_material_rgb, (hipStream_t)hip_stream);
     });
 }
 

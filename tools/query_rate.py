@@ -55,7 +55,13 @@ field of view.  Shape B: the scene's own view at 4096 x 4096.  Row v: the batch,
 capabilities: row vk, lg_capture_subset_device(0, 1, ..) on K accels rebuilt per camera, K render chains on one stream (the K scene + accel
 builds are timed apart, host wall clock: build_ms); row vx8, lg_capture_rays_device on the views' rays written out in 8 x 8-tile order through
 pixel_offsets (the rays' construction not timed).  Every row's films are checked against row v's bytes.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views[,...]] [--out profiles/r08_query_order.jsonl]
+View features (lg_capture_view_features_device) -- --rows viewfeatures (not part of "all"), two shapes a scene.  Shape A: the 64 orbit views of
+--rows views at 128 x 128, one sample, depth + normal + id + point.  Row f: one call.  Beside it, the two routes the parent commit offers for the
+same planes: row fi, lg_view_rays_device + lg_intersect_device per view (48 bytes a ray out, 96 bytes a hit back, no reduction counted); row fk,
+lg_capture_features_device on K accels rebuilt per camera (builds timed apart, host wall clock: build_ms; there is no point there).  Every row's
+planes are checked against row f's bytes where they coincide.  Shape B: the scene's own view at 4096 x 4096, all six planes (row f) against
+lg_capture_features_device with the same camera (row g8, five planes), measured in alternation, `round` 0 and 1.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -601,6 +607,83 @@ def measure_views(name, builder, calls):
     return out
 
 
+def measure_view_features(name, builder, calls):
+    """Rows f / fi / fk of shape A and f / g8 of shape B for one scene (module docstring)."""
+    import math
+    import numpy as np
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    own = G.accel_view(accel)
+    assert own.samples_root == 1, "the shapes are one sample a pixel"
+    eye, view, up = (np.array(v[:]) for v in (own.origin, own.view, own.up))
+    center, radius = eye + view, float(np.linalg.norm(view))
+    fov = math.degrees(2.0 * math.atan(own.image_plane_height / (2.0 * radius)))
+    K = 64
+    orbit = [la.view_look_at(eye, center, up, fov=fov)] + la.orbit_views(center, radius, 0.0, K, fov, up=up)[1:]
+    if name not in _VIEW_ACCELS:
+        t0 = time.time()
+        accels = []
+        for v in orbit:
+            scene = builder(G)
+            scene.set_perspective_camera(fov).look_at(list(v.origin[:]), list(center), list(up))
+            accels.append(G.Accel.from_scene(scene))
+        _VIEW_ACCELS[name] = (accels, (time.time() - t0) * 1e3)
+    rebuilt, build_ms = _VIEW_ACCELS[name]
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device="cuda")  # noqa: E731
+    common = {"calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+              "gpu": torch.cuda.get_device_name(0)}
+    out = []
+    # ---- shape A
+    w = h = 128
+    npix, n = w * h, K * w * h
+    depth, normal, point, ident = f32(n), f32(n, 3), f32(n, 3), torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    call = lambda: G.capture_view_features_device(accel, orbit, w, h, depth_ptr=depth.data_ptr(), normal_ptr=normal.data_ptr(), id_ptr=ident.data_ptr(),  # noqa: E731
+                                                  point_ptr=point.data_ptr(), stream=s)
+    rows = [("f: view features, depth + normal + id + point, one call", timed(call, calls, 2), 44.0, None)]
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    call = lambda: [(G.view_rays_device(accel, v, w, h, 0, 0, w, h, rays.data_ptr() + 48 * npix * i, stream=s),  # noqa: E731
+                     G.intersect_device(accel, npix, rays.data_ptr() + 48 * npix * i, hits.data_ptr() + 96 * npix * i, stream=s)) for i, v in enumerate(orbit)]
+    ms = timed(call, calls, 2)
+    torch.cuda.synchronize()
+    hf, hi = hits.view(torch.float64).view(-1, 12), hits.view(torch.int32).view(-1, 24)
+    hit = hi[:, 20] != 0
+    same = bool(torch.equal(ident, hi[:, 20:24])) and bool(torch.equal(depth, hf[:, 0].float())) and bool(torch.equal(normal, hf[:, 7:10].float())) \
+        and bool(torch.equal(point, torch.where(hit[:, None], hf[:, 1:4].float(), torch.zeros_like(point))))
+    rows.append(("fi: lg_view_rays_device + lg_intersect_device per view (no reduction)", ms, 144.0, {"same_bytes": same, "hit_share": round(float(hit.float().mean()), 4)}))
+    del rays, hits, hf, hi
+    depth2, normal2, ident2 = torch.empty_like(depth), torch.empty_like(normal), torch.empty_like(ident)
+    call = lambda: [G.capture_features_device(a, w, h, None, depth_ptr=depth2.data_ptr() + 4 * npix * i, normal_ptr=normal2.data_ptr() + 12 * npix * i,  # noqa: E731
+                                              id_ptr=ident2.data_ptr() + 16 * npix * i, stream=s) for i, a in enumerate(rebuilt)]
+    ms = timed(call, calls, 2)
+    torch.cuda.synchronize()
+    same = bool(torch.equal(depth, depth2)) and bool(torch.equal(normal, normal2)) and bool(torch.equal(ident, ident2))
+    rows.append(("fk: lg_capture_features_device on K rebuilt accels (depth + normal + id: no point there)", ms, 32.0, {"build_ms": round(build_ms, 1), "same_bytes": same}))
+    out += [{"scene": name, "shape": "A: 64 orbit views x 128 x 128", "row": row, "views": K, "film": [w, h], "samples": 1, "rays": n, "ms": round(ms, 4),
+             "mrays_per_s": round(n / ms / 1e3, 1), "bytes_per_pixel": bpp, **(extra or {}), **common} for row, ms, bpp, extra in rows]
+    del depth, normal, point, ident, depth2, normal2, ident2
+    # ---- shape B: the same camera through both entry points, in alternation
+    w = h = 4096
+    n = w * h
+    table = torch.from_numpy(G.default_albedo_table(accel)).cuda()
+    a, b = [(f32(n), f32(n, 3), f32(n, 3), f32(n), torch.empty((n, 4), dtype=torch.int32, device="cuda")) for _ in range(2)]
+    point = f32(n, 3)
+    views_call = lambda: G.capture_view_features_device(accel, [own], w, h, a[0].data_ptr(), a[1].data_ptr(), a[2].data_ptr(), a[3].data_ptr(), a[4].data_ptr(),  # noqa: E731
+                                                        point.data_ptr(), table.data_ptr(), stream=s)
+    own_call = lambda: G.capture_features_device(accel, w, h, None, b[0].data_ptr(), b[1].data_ptr(), b[2].data_ptr(), b[3].data_ptr(), b[4].data_ptr(),  # noqa: E731
+                                                 table.data_ptr(), stream=s)
+    rows = []
+    for rnd in range(2):
+        rows.append(("f: view features, all six planes", timed(views_call, calls, 2), 60.0, rnd))
+        rows.append(("g8: lg_capture_features_device, all five planes", timed(own_call, calls, 2), 48.0, rnd))
+    torch.cuda.synchronize()
+    same = all(bool(torch.equal(x, y)) for x, y in zip(a, b))
+    out += [{"scene": name, "shape": "B: 1 view x 4096 x 4096", "row": row, "views": 1, "film": [w, h], "samples": 1, "rays": n, "ms": round(ms, 4),
+             "mrays_per_s": round(n / ms / 1e3, 1), "bytes_per_pixel": bpp, "round": rnd, "same_bytes": same, **common} for row, ms, bpp, rnd in rows]
+    return out
+
+
 def measure_features(name, builder, size, calls):
     """Rows a / a8 / x8c / g8 / g8d of one scene (module docstring)."""
     accel = G.Accel.from_scene(builder(G))
@@ -673,7 +756,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -682,8 +765,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -701,7 +784,9 @@ def main():
                 got += measure_gather(name, builder, args.calls)
             if "views" in want:
                 got += measure_views(name, builder, max(args.calls, 3))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views"}:
+            if "viewfeatures" in want:
+                got += measure_view_features(name, builder, max(args.calls, 3))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
