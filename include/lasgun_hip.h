@@ -273,6 +273,18 @@ int lg_scene_l0_relative_origins(const lg_scene *, double *origins, int cap);
  * lg_accel_last_node_pairs: the records the last launch over the LDS-resident scene read (1 pair / 0 node; -1 before the first). */
 int lg_accel_set_node_pairs(const lg_accel *, int enabled);
 int lg_accel_last_node_pairs(const lg_accel *);
+/* The packet form of that walk: level 0's closest pass of the level-by-level pipeline walks the 64 rays of a wave
+ * with one cursor, one stack and one slot counter; a lane takes part at a record exactly when it hit every ancestor of it, so its own
+ * sequence of box and primitive tests is the per-lane walk's.  Taken where the launch takes the pair form, for the scene's own camera, and
+ * every nested accel is a single root record entered from the root accel (a lone mesh and its group count as one).  1 (default): on;
+ * 0: the per-lane walk (A/B, tests; LASGUN_PACKET_WALK=0 does the same for every accel).  Same bytes either way.
+ * lg_accel_last_packet_walk: the form the last such launch took (1 / 0; -1 before the first). */
+int lg_accel_set_packet_walk(const lg_accel *, int enabled);
+int lg_accel_last_packet_walk(const lg_accel *);
+/* The scene graph's part of that gate, without a device (tests): 0 where the packet form may take the scene, otherwise the reason it may
+ * not (lasgun_amd/csrc/packet_host.h, PacketRefusal: 5 the root is a mesh, 6 a nested tree with interior nodes, 7 a nested accel inside a
+ * nested accel, 8 a nested group's leaf holds another accel, 9 the root tree is deeper than the stack); -1 on an error. */
+int lg_scene_packet_walk_gate(const lg_scene *);
 /* The LDS image lg_accel_from would make for this scene, without a device (tests): its 32-bit words into words[0 .. cap), info[8] = {16-byte
  * units, node offset, primref offset, leaf-record offset, accel-record offset (all in units), 1 if it holds pair records, accels, node
  * records of the flat tables}.  Returns the number of words, 0 when the tables do not fit in LDS, -1 on an error. */

@@ -46,6 +46,9 @@ _EXTRA = {
     "scene_l0_relative_origins": (_C.c_int, [_C.c_void_p, _C.POINTER(_C.c_double), _C.c_int]),
     "accel_set_node_pairs": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_last_node_pairs": (_C.c_int, [_C.c_void_p]),
+    "accel_set_packet_walk": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_last_packet_walk": (_C.c_int, [_C.c_void_p]),
+    "scene_packet_walk_gate": (_C.c_int, [_C.c_void_p]),
     "scene_lds_image": (_C.c_longlong, [_C.c_void_p, _C.c_int, _C.POINTER(_C.c_uint32), _C.c_size_t, _C.POINTER(_C.c_uint32)]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
@@ -222,6 +225,18 @@ class HipApi(Api):
         v = self.call("accel_last_node_pairs", accel.h)
         return None if v < 0 else bool(v)
 
+    def set_packet_walk(self, accel, enabled):
+        """Level 0's closest pass of the level-by-level pipeline in the packet form: one cursor and one stack per wave
+        (default on; same bytes either way; include/lasgun_hip.h, lg_accel_set_packet_walk)."""
+        if self.call("accel_set_packet_walk", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def last_packet_walk(self, accel):
+        """The form the last level-0 closest launch of the level-by-level pipeline took: True the packet form, False the per-lane walk,
+        None before the first."""
+        v = self.call("accel_last_packet_walk", accel.h)
+        return None if v < 0 else bool(v)
+
     def scene_lds_image(self, scene, pairs):
         """The LDS image lg_accel_from would make for this scene, without a device: (uint32 words, info dict), or None where the tables
         do not fit in LDS (include/lasgun_hip.h, lg_scene_lds_image)."""
@@ -245,6 +260,14 @@ class HipApi(Api):
         if n < 0:
             raise LasgunError(self.last_error())
         return out[:n].copy() if n else None
+
+    def scene_packet_walk_gate(self, scene):
+        """The scene graph's part of the packet walk's gate, without a device: 0 where the form may take the scene, otherwise the reason it
+        may not (include/lasgun_hip.h, lg_scene_packet_walk_gate)."""
+        v = self.call("scene_packet_walk_gate", scene.h)
+        if v < 0:
+            raise LasgunError(self.last_error())
+        return int(v)
 
     def last_organisation(self, accel):
         """What the accel's last launch ran as: "megakernel", "wavefront" (level by level), "queue"; None before the first."""

@@ -402,6 +402,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.queue_default, y.queue_default); swap(x.prune_default, y.prune_default); swap(x.queue_min_items, y.queue_min_items); swap(x.specular_small_items, y.specular_small_items);
     swap(x.device_bytes, y.device_bytes); swap(x.fast_available, y.fast_available); swap(x.fast_refusal, y.fast_refusal);
     swap(x.streaming_pays, y.streaming_pays); swap(x.streaming_min_items, y.streaming_min_items); swap(x.mega_narrow, y.mega_narrow);
+    x.packet_scene = y.packet_scene = -1; // (the packet walk's gate reads the tables: asked again at the next launch)
 }
 // the tables once more, with what was left out of them: the fast mode's trees (lg_accel_set_mode(1)), the pruned walk's leaf records (lg_accel_set_prune(1), lg_audit_prune)
 void rebuild_tables(const lg_accel *ca, bool fast) {

@@ -2,6 +2,7 @@
 // measurement and test hooks.  No torch types, no C++ exceptions across the boundary, no CPU render path.
 #include "internal.h"
 #include "choice.h"
+#include "packet_host.h"
 
 // ============================================================================================
 extern "C" {
@@ -759,6 +760,16 @@ int lg_accel_last_node_pairs(const lg_accel *a) { // the records the last launch
     std::lock_guard<std::mutex> g(a->mtx);
     return a->last_node_pairs;
 }
+int lg_accel_set_packet_walk(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("packet walk must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->packet_walk = enabled == 1;
+    return 0;
+}
+int lg_accel_last_packet_walk(const lg_accel *a) { // the form the last level-0 closest launch of the level-by-level pipeline took: 1 the packet form, 0 the per-lane walk; -1 before the first
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->last_packet_walk;
+}
 // The device-free part of that form's gate for a scene and its own camera (host.cpp, l0_relative_camera / l0_relative_origins): the number
 // of accels, and the camera's origin in each accel's local space in origins[3 * accel ..] (at most `cap` accels are written), when the
 // camera's rays share one origin that is the same bits in every accel's frame of every lane; 0 when they do not; -1 on an error.
@@ -774,6 +785,17 @@ int lg_scene_l0_relative_origins(const lg_scene *s, double *origins, int cap) {
         for (int i = 0; i < n && i < cap && origins; ++i) { origins[3 * i] = local[(size_t)i].x; origins[3 * i + 1] = local[(size_t)i].y; origins[3 * i + 2] = local[(size_t)i].z; }
     });
     return rc ? -1 : n;
+}
+// The scene graph's part of the packet walk's gate, without a device (packet_host.h, packet_scene_gate over the flattened tables): 0 the
+// packet form may take the scene, otherwise the PacketRefusal that says why not; -1 on an error.
+int lg_scene_packet_walk_gate(const lg_scene *s) {
+    int v = 0;
+    int rc = guarded([&] {
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        v = (int)packet_scene_gate(f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.max_stack + 2u);
+    });
+    return rc ? -1 : v;
 }
 int lg_accel_set_mode(const lg_accel *a, int mode) {
     if (mode != 0 && mode != 1) return fail("mode must be 0 (reference traversal) or 1 (fast)");

@@ -380,6 +380,9 @@ struct DParams {
     // takes the pair step then (walk.h, walk<>); the pruned walk is launched from the L2 tables while the accel holds this form.
     uint32_t lds_pairs;
     struct { uint32_t root_off, pair_off, pair_n, pad; } pair_rel[L0_REL_MAX_ACCELS]; // l0_rel's node ranges in the pair form: bytes, bytes, records
+    // The packet form of the plain exact walk (packet.h): 1 where the level-0 closest launch of the level-by-level pipeline
+    // takes it (launch.cpp, packet_walk: the gate); 0 everywhere else
+    uint32_t packet;
 };
 static_assert(sizeof(DParams) <= 4096, "DParams is passed by value: a kernel's arguments are at most 4 KB");
 // does a closest / shadow pass of the level-by-level pipeline launched with these parameters walk the pair form of the LDS image?  (the plain exact walk from LDS alone)

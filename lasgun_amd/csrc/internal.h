@@ -495,6 +495,10 @@ struct lg_accel {
     std::vector<std::array<uint32_t, 3>> pair_rel; // per accel: root record's byte offset, first pair record's, pair records (DParams::pair_rel)
     mutable bool node_pairs = true;   // lg_accel_set_node_pairs (a change re-makes the image: rebuild_tables)
     mutable int last_node_pairs = -1; // the last launch over the LDS-resident scene: 1 pair records, 0 node records; -1 before the first
+    // the packet form of level 0's closest pass (packet.h; launch.cpp, packet_walk: the gate)
+    mutable bool packet_walk = true;   // lg_accel_set_packet_walk
+    mutable int last_packet_walk = -1; // the last level-0 closest launch of the level-by-level pipeline: 1 the packet form, 0 the per-lane walk; -1 before the first
+    mutable int packet_scene = -1;     // the scene graph's part of the gate (packet_host.h, PacketRefusal), made at the first launch that asks; -1: not yet
     uint32_t ldss_blocks = 0;         // one 1024-lane workgroup per CU; 0 = variant unavailable for this scene
     uint32_t cus = 1;                 // compute units of the accel's device
     mutable bool lds_scene = true;    // lg_accel_set_lds_scene

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "wflevel.h"
+#include "packet.h"
 
 namespace lg {
 
@@ -163,9 +164,11 @@ __device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_
 // L0: the launch is level 0's (rays from the camera, work items = the chunk's pixels in 8x8 tiles).
 // REL: level 0's closest pass with the image's node boxes and sphere slots relative to the camera's origin (l0_rewrite above).
 // PAIR: the image this launch copies holds pair records (P.lds_pairs).
-template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false, bool PAIR = false>
+// PACKET: level 0's closest pass in the packet form (packet.h): one cursor and one stack per wave; the kernel then holds no per-lane walk.
+template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false, bool PAIR = false, bool PACKET = false>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) wf_trace_kernel(const DParams P) {
     static_assert(!PAIR || (!FAST && LDSS && !PRUNE && !REFILL), "the pair records: the plain exact walk from LDS");
+    static_assert(!PACKET || (PAIR && L0), "the packet form: level 0's closest pass over the pair records");
     static_assert(!REL || (!FAST && !SHADOW && LDSS && L0 && !PRUNE && !REFILL), "the origin-relative form: level 0's closest pass from LDS");
     static_assert(!REFILL || (SHADOW && LDSS && !FAST), "the refilling walk: the LDS-resident shadow pass");
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
@@ -184,7 +187,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         ntiles = L0 ? P.ntiles : (uint32_t)((n_work + lpt - 1u) / lpt);
     }
     if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
+    uint32_t *stack = lds_stack + (PACKET ? tid & ~63u : tid); // (PACKET: the wave's slice of the stacks holds the wave's one stack)
     constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
     const uint4 *scn = nullptr;
     if (LDSS) {
@@ -238,7 +241,8 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             const bool active = px.active;
             Best b;
             b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
-            if (active) {
+            if constexpr (PACKET) packet_walk<REL>(P, ray, active, stack, stride, b, scn); // (every lane: the walk is the wave's)
+            else if (active) {
                 bool tie = false;
                 walk<LDSS, FAST, PRUNE, false, REL, PAIR ? 1 : 0>(P, ray, false, stack, stride, b, scn, cnt, arec);
                 (void)tie;
@@ -479,7 +483,9 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         static const bool refill_on = [] { const char *e = std::getenv("LASGUN_REFILL"); return e && e[0] == '1'; }();
         const bool refill = refill_on && !pairs && shadow && P.wf_level == 0u && (unsigned long long)P.ntiles >= 4ull * blocks * (block / 64u);
 #define LG_LAUNCH_PAIR(S, Z, R) hipLaunchKernelGGL((wf_trace_kernel<false, S, true, Z, false, false, R, true>), dim3(blocks), dim3(block), lds, stream, P)
-        if (pairs) {
+#define LG_LAUNCH_PACKET(R) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, R, true, true>), dim3(blocks), dim3(block), lds, stream, P)
+        if (pairs && l0 && P.packet) { if (P.l0_rel_n) LG_LAUNCH_PACKET(true); else LG_LAUNCH_PACKET(false); } // (launch.cpp, packet_walk: the gate)
+        else if (pairs) {
             if (shadow) LG_LAUNCH_PAIR(true, false, false);
             else if (l0 && P.l0_rel_n) LG_LAUNCH_PAIR(false, true, true);
             else if (l0) LG_LAUNCH_PAIR(false, true, false); else LG_LAUNCH_PAIR(false, false, false);
@@ -488,6 +494,7 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         else if (l0 && P.l0_rel_n) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, true>), dim3(blocks), dim3(block), lds, stream, P); // (launch.cpp, l0_relative: the gate)
         else if (l0) LG_LAUNCH(false, false, true, true); else LG_LAUNCH(false, false, true, false);
 #undef LG_LAUNCH_PAIR
+#undef LG_LAUNCH_PACKET
     }
     else { if (shadow) LG_LAUNCH(false, true, false, false); else if (l0) LG_LAUNCH(false, false, false, true); else LG_LAUNCH(false, false, false, false); }
 #undef LG_LAUNCH
@@ -536,7 +543,9 @@ hipError_t wf_set_lds_limit(size_t bytes, bool ldss) {
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true>),
-        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, false, false, false, true>)};
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, false, false, false, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true, true, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true, true>)};
     const void *plain_fns[] = {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, false, false>),

@@ -3,6 +3,7 @@
 // addressing modes of capture_subset (strided subsets, batches, lattice tiling).
 #include "internal.h"
 #include "choice.h"
+#include "packet_host.h"
 
 // The launch context of `stream` (at most MAX_LAUNCH_CTXS are kept; the least recently used one is recycled after a
 // device-wide synchronise).  Caller holds a.mtx and has made the accel's device current.
@@ -288,6 +289,18 @@ static bool l0_relative(const lg_accel &a, DParams &P) {
     return true;
 }
 
+// The gate of the packet form of level 0's closest pass (packet.h; the predicate is packet_host.h's).  Wrong means wrong
+// pixels: the launch takes the pair form today, it is the camera's level 0 of the level-by-level pipeline, and every nested accel is one
+// root record entered from the root accel.  LASGUN_PACKET_WALK=0 / lg_accel_set_packet_walk(0): the per-lane walk, the parent's kernel.
+static uint32_t packet_walk(const lg_accel &a, const DParams &P, bool camera_level0) {
+    static const bool env = env_on("LASGUN_PACKET_WALK");
+    if (packet_launch_gate(wf_takes_pairs(P, a.fast), camera_level0, a.packet_walk && env) != PACKET_OK) return 0u;
+    if (a.packet_scene < 0)
+        a.packet_scene = (int)packet_scene_gate(a.flat.accels.data(), a.flat.accels.size(), a.flat.nodes.data(), a.flat.nodes.size(), a.flat.primref.data(),
+                                                a.flat.primref.size(), a.stack_depth);
+    return a.packet_scene == (int)PACKET_OK ? 1u : 0u;
+}
+
 // ---- the level-by-level pipeline (k_wavefront.hip), shared by a render (enqueue_wavefront) and a radiance query (enqueue_radiance) ----
 // A chunk's arrays in a launch context: the level arrays, and beside them the hit queue, frame and visibility of the widest level (dense
 // part + appended part), the queue counts and a block of tile heads per launch
@@ -347,6 +360,8 @@ struct WfChunk {
             const uint32_t tb = d == 0 ? trace_blocks0 : trace_cap, fb = d == 0 ? shade_blocks0 : flat_cap;
             const bool own0 = d == 0 && l0.own();
             level_params(d);
+            P.packet = packet_walk(a, P, d == 0 && !own0); // (the camera's level 0 alone; every other launch of the chain: 0)
+            if (d == 0) a.last_packet_walk = (int)P.packet;
             if (own0) timed(a, 0, ls, [&] { return l0.closest(P, a.fast, tb, depth, ls); });
             else {
                 if (d == 0) a.last_l0_relative = l0_relative(a, P) ? 1 : 0; // (the camera's level 0: the form is chosen per launch, from this launch's camera)
@@ -361,6 +376,7 @@ struct WfChunk {
             if (own0) timed(a, 3, ls, [&] { return l0.shade(P, fb, ls); });
             else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
+        P.packet = 0u;
         combine_levels(a, P, L, plan, ls, l0);
     }
 };

@@ -13,7 +13,8 @@
 //   wf_trace_kernel<FAST, SHADOW, LDSS, L0, PRUNE>  wavefront pipeline, traversal only: closest hit of a level's rays (hits
 //                                             compacted, frames parked) or per-light any-hit of its hits;
 //                                             LDSS = scene tables resident in LDS, one 1024-lane workgroup per CU
-//                                             (+ REL: level 0's closest pass with the LDS records relative to the camera's origin)
+//                                             (+ REL: level 0's closest pass with the LDS records relative to the camera's origin;
+//                                             + PACKET: that pass with one cursor per wave, packet.h)
 //   wf_shade_kernel<KIND, L0>, wf_combine_kernel   radiance of a level's hits, specular children queued; levels combined bottom-up
 //   queue_kernel<LDSS, PRUNE>                 every recursion level in one persistent launch (k_queue.hip)
 //   trace_pixel_kernel<FAST>                  one pixel by one lane, with an event log of the walk (lg_trace_pixel)
@@ -116,18 +117,24 @@ __device__ __forceinline__ bool slab_intersects_nc_axes(const double bmin[3], co
 // without a NaN (inf * 0 needs dinv = 0): min(t1, t2) and max(t1, t2) of cuboid.rs:113-117 ARE (t1, t2) or (t2, t1), up to the
 // sign of a zero when both are zeros -- and tnear / tfar only ever meet comparisons, which do not see that sign.  Six of the
 // ten min / max of a node step become register names.  Also hands back the per-axis entry parameters (the pruned walk's).
+// (the _t forms hand back tnear and tfar: the packet walk, packet.h, takes a wave vote on each of the two comparisons)
 template <int SG>
-__device__ __forceinline__ bool slab_intersects_sg(const double bmin[3], const double bmax[3], const Ray &r, double &tx, double &ty, double &tz) {
+__device__ __forceinline__ void slab_sg_t(const double bmin[3], const double bmax[3], const Ray &r, double &tx, double &ty, double &tz, double &tnear, double &tfar) {
     tx = (((SG & 1) ? bmax[0] : bmin[0]) - r.o.x) * r.dinv.x;
-    double tfar = (((SG & 1) ? bmin[0] : bmax[0]) - r.o.x) * r.dinv.x;
+    tfar = (((SG & 1) ? bmin[0] : bmax[0]) - r.o.x) * r.dinv.x;
     ty = (((SG & 2) ? bmax[1] : bmin[1]) - r.o.y) * r.dinv.y;
     const double fy = (((SG & 2) ? bmin[1] : bmax[1]) - r.o.y) * r.dinv.y;
-    double tnear = fmax_(tx, ty);
+    tnear = fmax_(tx, ty);
     tfar = fmin_(tfar, fy);
     tz = (((SG & 4) ? bmax[2] : bmin[2]) - r.o.z) * r.dinv.z;
     const double fz = (((SG & 4) ? bmin[2] : bmax[2]) - r.o.z) * r.dinv.z;
     tnear = fmax_(tnear, tz);
     tfar = fmin_(tfar, fz);
+}
+template <int SG>
+__device__ __forceinline__ bool slab_intersects_sg(const double bmin[3], const double bmax[3], const Ray &r, double &tx, double &ty, double &tz) {
+    double tnear, tfar;
+    slab_sg_t<SG>(bmin, bmax, r, tx, ty, tz, tnear, tfar);
     return !(tnear > tfar) && !(tfar <= 0.0);
 }
 
@@ -135,17 +142,22 @@ __device__ __forceinline__ bool slab_intersects_sg(const double bmin[3], const d
 // fl(bmin - o) and fl(bmax - o) where it held bmin and bmax -- the same subtraction on the same bits, done once by the workgroup
 // instead of per lane and node step -- and the test starts at the multiplication by dinv.  Nothing else differs from the form above.
 template <int SG>
-__device__ __forceinline__ bool slab_intersects_sg_rel(const double rmin[3], const double rmax[3], const Ray &r) {
+__device__ __forceinline__ void slab_sg_rel_t(const double rmin[3], const double rmax[3], const Ray &r, double &tnear, double &tfar) {
     const double tx = ((SG & 1) ? rmax[0] : rmin[0]) * r.dinv.x;
-    double tfar = ((SG & 1) ? rmin[0] : rmax[0]) * r.dinv.x;
+    tfar = ((SG & 1) ? rmin[0] : rmax[0]) * r.dinv.x;
     const double ty = ((SG & 2) ? rmax[1] : rmin[1]) * r.dinv.y;
     const double fy = ((SG & 2) ? rmin[1] : rmax[1]) * r.dinv.y;
-    double tnear = fmax_(tx, ty);
+    tnear = fmax_(tx, ty);
     tfar = fmin_(tfar, fy);
     const double tz = ((SG & 4) ? rmax[2] : rmin[2]) * r.dinv.z;
     const double fz = ((SG & 4) ? rmin[2] : rmax[2]) * r.dinv.z;
     tnear = fmax_(tnear, tz);
     tfar = fmin_(tfar, fz);
+}
+template <int SG>
+__device__ __forceinline__ bool slab_intersects_sg_rel(const double rmin[3], const double rmax[3], const Ray &r) {
+    double tnear, tfar;
+    slab_sg_rel_t<SG>(rmin, rmax, r, tnear, tfar);
     return !(tnear > tfar) && !(tfar <= 0.0);
 }
 __device__ __forceinline__ bool slab_intersects_nc_rel(const double rmin[3], const double rmax[3], const Ray &r) { // slab_intersects_nc
@@ -574,6 +586,33 @@ __device__ __forceinline__ LeafRec load_rec(const DParams &P, uint32_t slot) {
 __device__ __forceinline__ double rec_f64(uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); }
 __device__ __forceinline__ double rec_f32(uint32_t w) { return (double)__uint_as_float(w); } // f32 -> f64 `.into()`
 
+// One sphere slot of a leaf of the LDS image, for a lane whose best hit so far is at best_t: Sphere::intersect_t + quad_roots (sphere.rs:30-69,
+// core/math.rs) and the reference's accept (sphere.rs:86).  dd = dot(d, d), four_a = 4.0 * dd of the lane's ray at this level.  REL: the slot
+// holds l where it held the centre, and c where it held rad * rad (k_wavefront.hip, l0_rewrite).  `t`: the root when there is one (left
+// as it was otherwise).  The one text of these expressions: the per-lane walk (traverse_ref) and the packet walk (packet.h) both call it.
+template <bool REL>
+__device__ __forceinline__ bool sphere_slot_accept(const LeafRec &g, const Ray &ray, const double dd, const double four_a, const double best_t, double &t) {
+    const V3 cen{rec_f64(g.a.x, g.a.y), rec_f64(g.a.z, g.a.w), rec_f64(g.b.x, g.b.y)};
+    const V3 l = REL ? cen : ray.o - cen;
+    const double b = 2.0 * dot(ray.d, l);
+    const double c = REL ? rec_f64(g.c.x, g.c.y) : dot(l, l) - rec_f64(g.c.x, g.c.y); // rad * rad, formed by the host
+    bool has = false;
+    if (dd == 0.0) {
+        if (b != 0.0) { t = -c / b; has = true; }
+    } else {
+        const double disc = b * b - four_a * c;
+        if (!(disc < 0.0)) {
+            const double q = -(b + signum(b) * sqrt(disc)) / 2.0;
+            const double r0 = q / dd;
+            const double r1 = (q == 0.0) ? r0 : c / q;
+            const double t0 = fmin_(r0, r1), t1 = fmax_(r0, r1);
+            t = t0 < 0.0 ? t1 : t0;
+            has = true;
+        }
+    }
+    return has && !(t < 0.0) && !(t >= best_t);
+}
+
 // ---- fast mode (opt-in; NOT the reference's traversal): the limit beyond which its walk skips a node's subtree
 __device__ __forceinline__ double prune_limit(double tbest, bool anyhit) {
     double lim = anyhit ? 1.0 : tbest;
@@ -669,6 +708,25 @@ __device__ __forceinline__ Ray accel_local_ray(const DParams &P, const uint4 *ar
         return ray_to_local(m, r);
     }
     return ray_to_local(P.accels[accel].minv, r);
+}
+// The probe at the door of nested accel `enter` for a ray of its parent's level (traverse_ref, the ST_ENTER block, has the argument; the
+// packet walk, packet.h, asks the same question with the same expressions): true = node 0 of the accel misses, whatever the other axes say.
+template <bool LDSS>
+__device__ __forceinline__ bool door_shut(const DParams &P, const uint4 *arec, const uint32_t enter, const Ray &ray) {
+    double2 ma, mb, bx;
+    if (LDSS || arec) {
+        const uint4 *q = arec + (enter * LDS_ACCEL_UNITS + LDS_ACCEL_DOOR);
+        ma = lds_d2(q); mb = lds_d2(q + 1); bx = lds_d2(q + 2);
+    } else {
+        const double *q = P.accels[enter].door;
+        ma = double2{q[0], q[1]}; mb = double2{q[2], q[3]}; bx = double2{q[4], q[5]};
+    }
+    const bool o_finite = __builtin_isfinite(ray.o.x) && __builtin_isfinite(ray.o.y) && __builtin_isfinite(ray.o.z); // (xf_point: else NaN)
+    const double ok = ((ma.x * ray.o.x + ma.y * ray.o.y) + mb.x * ray.o.z) + mb.y * 1.0;
+    const double dk = ((ma.x * ray.d.x + ma.y * ray.d.y) + mb.x * ray.d.z) + mb.y * 0.0;
+    const double inv = 1.0 / dk; // ray_new
+    const double m = fmax_((bx.x - ok) * inv, (bx.y - ok) * inv);
+    return o_finite && m <= 0.0;
 }
 // One fat mesh leaf [li, le) of the second formulation: the reference's leaf loop (bvh.rs:483-488) over the leaf-ordered
 // 48-byte f32 position records, two triangles per trip in ping-pong (while one record is tested the next is in flight and
@@ -1368,25 +1426,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
                 // (the slots of a non-mesh accel are spheres, boxes and nested accels -- triangles live in mesh accels, whose leaves
                 // mesh_leaf2 walks; the sphere is asked for first, with one compare on the primref: the common case passes one branch)
                 if (ref < (1u << 30)) { // PK_SPHERE: Sphere::intersect_t + quad_roots (sphere.rs:30-69, core/math.rs) == sphere_t_a
-                    const V3 cen{rec_f64(g.a.x, g.a.y), rec_f64(g.a.z, g.a.w), rec_f64(g.b.x, g.b.y)};
-                    const V3 l = REL ? cen : ray.o - cen; // (REL: the slot holds l where it held the centre, and c where it held rad * rad)
-                    const double b = 2.0 * dot(ray.d, l);
-                    const double c = REL ? rec_f64(g.c.x, g.c.y) : dot(l, l) - rec_f64(g.c.x, g.c.y); // rad * rad, formed by the host
-                    bool has = false;
-                    if (dd == 0.0) {
-                        if (b != 0.0) { t = -c / b; has = true; }
-                    } else {
-                        const double disc = b * b - four_a * c;
-                        if (!(disc < 0.0)) {
-                            const double q = -(b + signum(b) * sqrt(disc)) / 2.0;
-                            const double r0 = q / dd;
-                            const double r1 = (q == 0.0) ? r0 : c / q;
-                            const double t0 = fmin_(r0, r1), t1 = fmax_(r0, r1);
-                            t = t0 < 0.0 ? t1 : t0;
-                            has = true;
-                        }
-                    }
-                    accepted = has && !(t < 0.0) && !(t >= best.t);
+                    accepted = sphere_slot_accept<REL>(g, ray, dd, four_a, best.t, t);
                 } else if (ref >= (3u << 30)) { // PK_ACCEL
                     // nested BVHAccel (Group / Mesh): entered below, outside this loop -- the ray and the level are
                     // loop-invariant here, which keeps them out of the loop's register shuffles
@@ -1438,22 +1478,7 @@ __device__ __forceinline__ void traverse_ref(const DParams &P, const Ray &wray, 
             // Both t NaN: m is NaN, the comparison is false, the lane enters as before.  An AF_IDENTITY accel whose entry keeps a plain ray:
             // ((1*x + 0*y) + 0*z) + 0*w below IS the ray's own component k, bit for bit (see `same`), so the same expressions serve it.
             bool shut = false;
-            if (!FAST && !COUNT && (P.level_door & LEVEL_DOOR_PROBE)) {
-                double2 ma, mb, bx;
-                if (LDSS || arec) {
-                    const uint4 *q = arec + (enter * LDS_ACCEL_UNITS + LDS_ACCEL_DOOR);
-                    ma = lds_d2(q); mb = lds_d2(q + 1); bx = lds_d2(q + 2);
-                } else {
-                    const double *q = P.accels[enter].door;
-                    ma = double2{q[0], q[1]}; mb = double2{q[2], q[3]}; bx = double2{q[4], q[5]};
-                }
-                const bool o_finite = __builtin_isfinite(ray.o.x) && __builtin_isfinite(ray.o.y) && __builtin_isfinite(ray.o.z); // (xf_point: else NaN)
-                const double ok = ((ma.x * ray.o.x + ma.y * ray.o.y) + mb.x * ray.o.z) + mb.y * 1.0;
-                const double dk = ((ma.x * ray.d.x + ma.y * ray.d.y) + mb.x * ray.d.z) + mb.y * 0.0;
-                const double inv = 1.0 / dk; // ray_new
-                const double m = fmax_((bx.x - ok) * inv, (bx.y - ok) * inv);
-                shut = o_finite && m <= 0.0;
-            }
+            if (!FAST && !COUNT && (P.level_door & LEVEL_DOOR_PROBE)) shut = door_shut<LDSS>(P, arec, enter, ray);
             if (shut) {
                 if (li < le) state = ST_LEAF;
                 else if (sp != base) { --sp; if (PAIR) take_word(stk[sp * stride]); else { cur = stk[sp * stride]; state = ST_NODE; } }
