@@ -233,6 +233,7 @@ pub use sys::lg_scan_out as ScanOut;
 /// The work item a range scan of these counts would use (`lg_range_scan_lanes`): 1 beam lanes, 2 pose lanes; `lanes` 0 asks for the
 /// stated default (pose lanes iff n_poses >= n_beams); -1 for a bad `lanes`.  No device is touched.
 pub fn range_scan_lanes(n_poses: usize, n_beams: usize, lanes: i32) -> i32 { unsafe { sys::lg_range_scan_lanes(n_poses, n_beams, lanes) } }
+pub use sys::lg_layers_out as LayersOut;
 pub use sys::lg_gather_out as GatherOut;
 /// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
 /// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
@@ -406,6 +407,39 @@ impl<'s> Accel<'s> {
     pub unsafe fn range_scan_device(&self, dev_origins: *const f64, dev_frames: *const f64, n_poses: usize, dev_beams: *const f64, n_beams: usize, lanes: i32,
                                     dev_out: &sys::lg_scan_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_range_scan_device(self.ptr, dev_origins, dev_frames, n_poses, dev_beams, n_beams, lanes, dev_out, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
+    /// Hit layers (`lg_hit_layers`): the first `max_layers` surfaces along each ray, layer j of ray i at `j * rays.len() + i` of every layer
+    /// plane given (`None` = not asked for; not all five).  Segment j + 1 starts at layer j's `p - ng * 2^-36` and keeps the ray's direction.
+    /// hits = `intersect`'s record of the segment (the miss record behind a ray's last layer), along = t_0 + .. + t_j (+inf behind the last
+    /// layer), id = kind, prim, instance, material; `count[i]` = the layers found (== `max_layers`: the ray may have been cut short),
+    /// `inside[i]` = t_1 + t_3 + ..: the length inside material of a ray that starts outside every closed solid.
+    #[allow(clippy::too_many_arguments)]
+    pub fn hit_layers(&self, rays: &[[f64; 6]], max_layers: u32, hits: Option<&mut [sys::lg_hit]>, along: Option<&mut [f64]>, id: Option<&mut [[u32; 4]]>,
+                      count: Option<&mut [u32]>, inside: Option<&mut [f64]>) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_layers_out>() == 40);
+        let total = rays.len().checked_mul(max_layers as usize).expect("hit_layers: rays.len() * max_layers overflows usize");
+        assert!(hits.as_ref().map_or(true, |p| p.len() == total) && along.as_ref().map_or(true, |p| p.len() == total)
+                && id.as_ref().map_or(true, |p| p.len() == total) && count.as_ref().map_or(true, |p| p.len() == rays.len())
+                && inside.as_ref().map_or(true, |p| p.len() == rays.len()),
+                "hit_layers: layer planes of rays.len() * max_layers elements, count and inside of rays.len()");
+        let out = sys::lg_layers_out {
+            hits: hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            along: along.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            id: id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+            count: count.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            inside: inside.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+        };
+        let rc = unsafe { sys::lg_hit_layers(self.ptr, rays.as_ptr() as *const f64, rays.len(), max_layers, &out) };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `hit_layers` for rays in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `hit_layers` states (the library checks what HIP can tell it).
+    pub unsafe fn hit_layers_device(&self, dev_rays: *const f64, n: usize, max_layers: u32, dev_out: &sys::lg_layers_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_hit_layers_device(self.ptr, dev_rays, n, max_layers, dev_out, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
     }

@@ -231,6 +231,33 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                            const lg_scan_out &dev_out, void *hip_stream) const {
         if (lg_range_scan_device(h_, dev_origins, dev_frames, n_poses, dev_beams, n_beams, lanes, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // hit layers (lg_hit_layers): the first max_layers surfaces along each ray, layer j of ray i at j * rays.size() + i of every layer plane
+    // asked for (a null member is not asked for; not all five).  Segment j + 1 starts at layer j's p - ng * 2^-36 and keeps the ray's
+    // direction.  hits = lg_intersect's record of the segment (the miss record behind a ray's last layer); along = t_0 + .. + t_j (+inf
+    // behind the last layer); id = kind, prim, instance, material; count[i] = the layers found (== max_layers: the ray may have been cut
+    // short); inside[i] = t_1 + t_3 + ..: the length inside material of a ray that starts outside every closed solid
+    struct Layers {
+        std::vector<lg_hit> *hits = nullptr;                  // [max_layers*rays]
+        std::vector<double> *along = nullptr;
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;
+        std::vector<uint32_t> *count = nullptr;               // [rays]
+        std::vector<double> *inside = nullptr;
+    };
+    void hit_layers(const std::vector<std::array<double, 6>> &rays, uint32_t max_layers, const Layers &out) const {
+        static_assert(sizeof(lg_layers_out) == 40, "lg_layers_out: five pointers");
+        if (max_layers && rays.size() > SIZE_MAX / max_layers) throw Error("hit_layers: rays.size() * max_layers does not fit size_t");
+        const size_t n = rays.size() * max_layers;
+        lg_layers_out o{};
+        if (out.hits) { out.hits->assign(n, lg_hit{}); o.hits = out.hits->data(); }
+        if (out.along) { out.along->assign(n, 0.0); o.along = out.along->data(); }
+        if (out.id) { out.id->assign(n, {0u, 0u, 0u, 0u}); o.id = n ? (*out.id)[0].data() : nullptr; }
+        if (out.count) { out.count->assign(rays.size(), 0u); o.count = out.count->data(); }
+        if (out.inside) { out.inside->assign(rays.size(), 0.0); o.inside = out.inside->data(); }
+        if (lg_hit_layers(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), max_layers, &o)) throw Error(lg_last_error());
+    }
+    void hit_layers_device(const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out &dev_out, void *hip_stream) const {
+        if (lg_hit_layers_device(h_, dev_rays, n, max_layers, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<std::array<double, 3>> out(rays.size());

@@ -849,6 +849,52 @@ int lg_capture_view_features(const lg_accel *, const lg_view *views, size_t n_vi
                              const lg_view_features *out, const double *material_rgb);          /* host arrays; synchronous */
 int lg_capture_view_features_device(const lg_accel *, const lg_view *views, size_t n_views, uint32_t width, uint32_t height,
                                     const lg_view_features *dev_out, const double *dev_material_rgb, void *hip_stream);
+/* Hit layers: the first max_layers surfaces along each ray in one call -- an x-ray or thickness image, wall thickness for a printability
+ * check, ordered transparency and depth peeling, multi-return lidar, inside / outside of a closed solid by crossing parity, picking
+ * through a window -- without the caller's own loop of lg_intersect calls that reads back 96 bytes a ray, moves every origin to just
+ * behind its hit, compacts the rays still alive and uploads 48 bytes a ray, max_layers times over.  One launch walks each ray up to
+ * max_layers times; the ray stays in registers between the walks; only the planes asked for are written.  An EXTRA; no counterpart in
+ * the reference.
+ * Segments: ray i is 6 doubles as for lg_intersect; any f64 is accepted as it is.  Segment 0 of ray i is that ray, bit for bit.  Layer j
+ * is what lg_intersect returns for segment j, bit for bit, exact ties included, in the accel's traversal mode exactly as for the other
+ * queries (reference, pruned, LDS-resident scene, fast mode); no switch of its own.  If layer j has kind != 0 and j + 1 < max_layers,
+ * segment j+1 has the origin o'[c] = p[c] - ng[c]*0x1p-36 for c = 0, 1, 2, with p and ng layer j's lg_hit::p and lg_hit::ng: one f64
+ * product and one f64 subtraction per component, nothing fused -- the origin the render gives a glass hit's transmitted ray (the
+ * reference's N::epsilon() * 2^16 step through the surface).  Segment j+1 keeps the direction of ray i bit for bit.  If layer j is a
+ * miss, the ray is finished.
+ * Planes (lg_layers_out) are LAYER-MAJOR: element (j, i) is at j*n + i, so each layer is a plane of n -- what depth peeling calls a
+ * layer.  Every element of every plane asked for is written, whatever the buffers held before, by exactly one lane: no atomics, no
+ * pre-fill.  hits = the whole lg_hit of layer j.  id = its kind, prim, instance, material.  along = the running parameter T_j: T_0 = t_0
+ * and T_j = T_(j-1) + t_j, with t_j layer j's lg_hit::t, added sequentially in f64 -- the 2^-36 steps are NOT added, so T_j runs behind the
+ * parameter of layer j on ray i by up to j steps.  A NaN stays: where T_(j-1) is NaN, T_j is T_(j-1) bit for bit, and so for inside (IEEE
+ * leaves open which of two NaNs a sum returns).  Behind a ray's last layer: hits holds lg_intersect's miss record (t = +INF, zeros,
+ * kind 0, prim and instance ~0, material -1), id holds 0, ~0, ~0, -1, along holds +INF.  count[i] = the number of layers with kind != 0,
+ * 0 .. max_layers; count[i] == max_layers means the ray may have been cut short.  inside[i] = t_1 + t_3 + t_5 + ...: the sequential
+ * f64 sum, from +0.0, of t_j over the odd j < count[i] -- for a ray that starts outside every closed solid, the length travelled
+ * inside material, in units of |d|.
+ * lg_accel_set_query_order(1) is honoured exactly as lg_intersect honours it: the tiles are cut from the sorted order of the GIVEN rays,
+ * every answer lands in its own ray's slots, the same bytes as order 0 (a query of 64 rays or fewer is walked as given).
+ * Limits and errors: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors (non-zero,
+ * lg_last_error, nothing launched, no output touched), for n > 0: max_layers == 0; n > (2^32 - 1) * 64 (64-ray tiles are counted in 32
+ * bits), and n > 2^32 - 1 with the sorted order; n * max_layers or a plane's byte size that does not fit size_t; a NULL accel, rays or
+ * out; all five planes NULL; in the device form also a pointer that is not device memory of the accel's device or is misaligned (rays 8
+ * bytes; hits and id 16; along and inside 8; count 4), or a buffer that ends beyond its allocation.
+ * Device form: dev_out is a HOST struct of device pointers; it only enqueues on hip_stream; one stream at a time per accel.  Host form
+ * (synchronous): the rays go up, the planes come back into staging and are copied out at the end, so an error on the way leaves the
+ * caller's arrays as they were.
+ * Out of scope: no maximum range and no material filter -- the caller thresholds along and reads id; lanes are not re-packed after
+ * rays end (a wave walks while any of its rays is alive); no multi-device split.  Where |p[c]| is so large that ng[c]*2^-36 is absorbed,
+ * a segment may find the same surface again: the contract is still the loop above, and max_layers bounds it. */
+typedef struct lg_layers_out {
+    lg_hit   *hits;    /* [max_layers][n]     the whole record of layer j of ray i, at j*n + i */
+    double   *along;   /* [max_layers][n]     running parameter T_j, +INF behind the last layer */
+    uint32_t *id;      /* [max_layers][n][4]  kind, prim, instance, material: the last 16 bytes of an lg_hit */
+    uint32_t *count;   /* [n]                 layers found, 0 .. max_layers */
+    double   *inside;  /* [n]                 t_1 + t_3 + t_5 + ... */
+} lg_layers_out;       /* 40 bytes; each pointer may be NULL, all NULL is an error */
+int lg_hit_layers(const lg_accel *, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out); /* host arrays; synchronous */
+int lg_hit_layers_device(const lg_accel *, const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out *dev_out,
+                         void *hip_stream);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.
  * Results are identical bytes either way, in the caller's order. Any other value: non-zero return, lg_last_error.
  * The walk keeps a wave's 64 rays in step; rays that arrive in no particular order (collision probes, visibility between arbitrary

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CGatherOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CGatherOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -103,6 +103,7 @@ _EXTRA = {
     **VISIBILITY_SIGNATURES,
     **DIRECTIONS_SIGNATURES,
     **RANGE_SCAN_SIGNATURES,
+    **HIT_LAYERS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
     **VIEWS_SIGNATURES,
@@ -126,6 +127,10 @@ SCAN_PLANES = ("range", "point", "normal", "id", "hits", "nearest")  # lg_scan_o
 _SCAN_SHAPE = {"range": ((), _np.float32, True), "point": ((3,), _np.float32, True), "normal": ((3,), _np.float32, True), "id": ((4,), _np.uint32, True),
                "hits": ((), _np.uint32, False), "nearest": ((), _np.float32, False)}  # (trailing shape, dtype, per pair -- else per pose)
 SCAN_LANES = {"auto": 0, "beam": 1, "pose": 2}
+assert _C.sizeof(CLayersOut) == 40, "lg_layers_out is 40 bytes"
+LAYER_PLANES = ("hits", "along", "id", "count", "inside")  # lg_layers_out's members, in its order
+_LAYER_SHAPE = {"hits": ((), HIT_DTYPE, True), "along": ((), _np.float64, True), "id": ((4,), _np.uint32, True), "count": ((), _np.uint32, False),
+                "inside": ((), _np.float64, False)}  # (trailing shape, dtype, per layer and ray -- else per ray)
 assert _C.sizeof(CGatherOut) == 16, "lg_gather_out is 16 bytes"
 GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
 GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
@@ -763,6 +768,48 @@ class HipApi(Api):
                      _C.addressof(f), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- hit layers (include/lasgun_hip.h, lg_hit_layers*): the first K surfaces along each ray in one call
+    def hit_layers(self, accel, rays, max_layers, planes=("along", "id", "count"), into=None):
+        """The first max_layers surfaces along every ray of an (n, 6) float64 array: a dict of the planes asked for (any of "hits", "along",
+        "id", "count", "inside"), LAYER-MAJOR -- HIT_DTYPE (K, n) hits = lg_intersect's record of layer j of ray i at [j, i] (the miss record
+        behind a ray's last layer), float64 (K, n) along = t_0 + .. + t_j (+inf behind the last layer), uint32 (K, n, 4) id = kind, prim,
+        instance, material (0, ~0, ~0, -1 behind the last layer), uint32 (n,) count = the layers found (== K: the ray may have been cut
+        short), float64 (n,) inside = t_1 + t_3 + ..: the length inside material of a ray that starts outside every closed solid.  Segment
+        j + 1 starts at layer j's p - ng * 2**-36 and keeps the ray's direction.  `into`: a dict of C-contiguous arrays of those shapes,
+        written in place.  Also `accel.hit_layers(rays, max_layers, planes=...)`."""
+        r = self._rays(rays)
+        n, k = r.shape[0], int(max_layers)
+        planes = tuple(planes)
+        if any(p not in LAYER_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (LAYER_PLANES,))
+        if not 0 <= k <= 0xFFFFFFFF:
+            raise ValueError("max_layers: 0 .. 2^32 - 1")
+        out = {}
+        for p in planes:
+            tail, dt, per_layer = _LAYER_SHAPE[p]
+            shape = ((k, n) if per_layer else (n,)) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        # (an array without elements is not named: with k == 0 the library sees no plane and n > 0 rays, and says so)
+        f = CLayersOut(*[data(out.get(p)) for p in LAYER_PLANES])
+        if self.call("hit_layers", accel.h, data(r), n, k, _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def hit_layers_device(self, accel, n, rays_ptr, max_layers, hits_ptr=None, along_ptr=None, id_ptr=None, count_ptr=None, inside_ptr=None, stream=None):
+        """Enqueue the hit layers of n rays (device memory, 6 doubles each) into device memory, layer-major: max_layers * n elements at
+        hits_ptr (lg_hit, 16-byte aligned), along_ptr (f64) and id_ptr (4 u32, 16-byte aligned), n elements at count_ptr (u32) and inside_ptr
+        (f64); each may be None, not all.  The pointers are integers (torch: tensor.data_ptr()) or objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CLayersOut(*[ptr(p) for p in (hits_ptr, along_ptr, id_ptr, count_ptr, inside_ptr)])
+        rays = ptr(rays_ptr)
+        if self.call("hit_layers_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), int(max_layers), _C.addressof(f),
+                     self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- radiance gathers (include/lasgun_hip.h, lg_radiance_gather*): li() along K shared directions from N poses, reduced per pose
     @staticmethod
     def _gather_lanes(lanes):
@@ -1282,6 +1329,7 @@ api.Accel.features = lambda self, w, h, rect=None, planes=FEATURE_PLANES, materi
 api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibility(self, from_pts, to_pts, counts)  # accel.visibility(from_pts, to_pts)
 api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
+api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
 api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
 api.Accel.views = lambda self, views, w, h, rgba=True, rgb=False: api.capture_views(self, views, w, h, rgba, rgb)  # accel.views(views, w, h)
 api.Accel.view_features = lambda self, views, w, h, planes=VIEW_FEATURE_PLANES, material_rgb=None: api.capture_view_features(self, views, w, h, planes, material_rgb)  # accel.view_features(views, w, h)

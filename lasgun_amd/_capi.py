@@ -161,6 +161,13 @@ RANGE_SCAN_SIGNATURES = {
     "range_scan_lanes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int]),
 }
 
+# Hit layers (include/lasgun_hip.h, lg_hit_layers / lg_hit_layers_device): the first K surfaces along each ray in one call, as layer-major
+# planes; the GPU library's alone.
+HIT_LAYERS_SIGNATURES = {
+    "hit_layers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "hit_layers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+}
+
 # Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
 # directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
 GATHER_SIGNATURES = {
@@ -213,6 +220,10 @@ class CViewFeatures(C.Structure):  # lg_view_features: six plane pointers, 48 by
 
 class CScanOut(C.Structure):  # lg_scan_out: six pointers, 48 bytes; NULL = not asked for
     _fields_ = [("range", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p), ("hits", C.c_void_p), ("nearest", C.c_void_p)]
+
+
+class CLayersOut(C.Structure):  # lg_layers_out: five pointers, 40 bytes; NULL = not asked for
+    _fields_ = [("hits", C.c_void_p), ("along", C.c_void_p), ("id", C.c_void_p), ("count", C.c_void_p), ("inside", C.c_void_p)]
 
 
 class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for

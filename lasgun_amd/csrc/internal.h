@@ -99,6 +99,13 @@ hipError_t launch_range_scan(const DParams &P, const double *origins, const doub
                              const uint32_t *tri_base, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t range_scan_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t range_scan_set_lds_limit(size_t bytes, bool ldss);
+// k_layers.hip: hit layers (lg_hit_layers*) -- the closest-hit walk of the caller's rays repeated up to max_layers times a ray, the next
+// segment started at the hit's p - ng * 2^-36 (shade_frame's pm) in registers; a 64-ray tile per wave and a ray per lane; only the planes
+// that are not nullptr are written, layer-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order
+hipError_t launch_hit_layers(const DParams &P, const double *rays, unsigned long long n, uint32_t max_layers, void *hits, double *along, void *id, uint32_t *count,
+                             double *inside, const uint32_t *tri_base, const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t hit_layers_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t hit_layers_set_lds_limit(size_t bytes, bool ldss);
 // k_features.hip: feature buffers (lg_capture_features*) -- the closest-hit walk of the camera's own rays, an 8 x 8 tile of the rectangle per
 // wave and a pixel per lane; only the planes that are not nullptr are written, at DParams' output addressing (out_row0 / out_x0 / out_pitch)
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,

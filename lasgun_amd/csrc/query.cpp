@@ -1,17 +1,18 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
-// lg_features is, is scan_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
+// lg_layers_out / lg_features is, is scan_host.h's / layers_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
 
 #include "bitrows_host.h"
 #include "features_host.h"
 #include "gather_host.h"
+#include "layers_host.h"
 #include "scan_host.h"
 #include "views_host.h"
 #include "view_features_host.h"
@@ -747,6 +748,50 @@ extern "C" int lg_capture_view_features_device(const lg_accel *a, const lg_view 
         view_feature_planes(*dev_out, [&](auto *p, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, shape.pixels * per_pixel * sizeof *p, align, what); });
         if (dev_out->albedo) check_device_buffer(*a, dev_material_rgb, a->flat.material_pods.size() * 3 * sizeof(double), 8, "material_rgb");
         enqueue_view_features(*a, views, n_views, w, h, shape, *dev_out, dev_material_rgb, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- hit layers (lg_hit_layers*; k_layers.hip): the first max_layers surfaces along each of the caller's rays, the next segment made in
+// the kernel, the answer as layer-major planes.  The arithmetic that needs no device -- the limits, n * max_layers and the sizes, the NULL
+// and alignment rules, the staging -- is layers_host.h's.
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the counts and the buffers):
+// ONE launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is parked
+static void enqueue_hit_layers(const lg_accel &a, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    P.ntiles = (uint32_t)((n + 63) / 64);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream); // (ahead of the counter's memset on the stream)
+    const TraversalGrid g = traversal_grid(a, P, hit_layers_occupancy, c, stream);
+    HIP_TRY(launch_hit_layers(P, rays, n, max_layers, out.hits, out.along, out.id, out.count, out.inside, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
+}
+// Host form: the rays go up, the planes come back into staging and are copied out at the end
+extern "C" int lg_hit_layers(const lg_accel *a, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t total = check_layers(a, rays, n, max_layers, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        RoundTrip trip(*a);
+        LayersStaging st(*out, n, total);
+        const double *drays = trip.in(rays, n * 6);
+        lg_layers_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        layer_planes(dev, n, total, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        trip.run([&] { enqueue_hit_layers(*a, drays, n, max_layers, dev, a->stream); });
+        place_layers(*out, st);
+    });
+}
+extern "C" int lg_hit_layers_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t total = check_layers(a, dev_rays, n, max_layers, dev_out);
+        check_layers_alignment(dev_rays, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        layer_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        enqueue_hit_layers(*a, dev_rays, n, max_layers, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

@@ -61,7 +61,12 @@ same planes: row fi, lg_view_rays_device + lg_intersect_device per view (48 byte
 lg_capture_features_device on K accels rebuilt per camera (builds timed apart, host wall clock: build_ms; there is no point there).  Every row's
 planes are checked against row f's bytes where they coincide.  Shape B: the scene's own view at 4096 x 4096, all six planes (row f) against
 lg_capture_features_device with the same camera (row g8, five planes), measured in alternation, `round` 0 and 1.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures[,...]] [--out profiles/r08_query_order.jsonl]
+Hit layers (lg_hit_layers_device) -- --rows layers (not part of "all"): the camera's rays of a --size^2 film, 8 layers.  Row L8: one call, along +
+id + count; row LX: the same call with inside alone (the x-ray image, 8 bytes out a ray).  Beside them the route the parent commit offers: rows
+Y8 / YX, 8 rounds of lg_intersect_device with the planes pre-filled, the next origins computed and the live rays compacted by torch on the
+same stream (the compaction's size comes back to the host every round: the route needs it).  Timed L8, Y8, LX, YX, so --repeats alternates
+them; Y's planes are checked against L's bytes.  These rows time --calls calls as given (at least 4; the Y rows half as many), not 20.
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -727,6 +732,85 @@ def measure_features(name, builder, size, calls):
              "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, bpp in rows]
 
 
+def measure_layers(name, builder, size, calls, K=8):
+    """Hit layers on the camera's rays of a size^2 film, K layers.  Row L8: one lg_hit_layers_device call, along + id + count; row LX: the same
+    call with inside alone.  Rows Y8 / YX: the route without it -- K rounds of lg_intersect_device, the planes pre-filled, the next origins
+    (p - ng * 2^-36) computed and the live rays compacted by torch on the same stream -- into the same planes.  L8 / Y8 / LX / YX are timed
+    in that order, so a repeat alternates them; Y's planes are checked against L's bytes."""
+    if not hasattr(G, "hit_layers_device"):
+        return []
+    scene = builder(G)
+    accel = G.Accel.from_scene(scene)
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    n = size * size * G.camera_samples(accel)
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    inf = float("inf")
+    miss = torch.tensor([0, -1, -1, -1], dtype=torch.int32, device="cuda")
+
+    def planes():
+        return (torch.empty((K, n), dtype=torch.float64, device="cuda"), torch.empty((K, n, 4), dtype=torch.int32, device="cuda"),
+                torch.empty((n,), dtype=torch.int32, device="cuda"), torch.empty((n,), dtype=torch.float64, device="cuda"))
+
+    along, ident, count, inside = planes()
+    y_along, y_ident, y_count, y_inside = planes()
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    rounds = []
+
+    def loop(xray):
+        """The caller's own loop: lg_intersect_device, read the records, move the origins, compact; K times over."""
+        if xray:
+            y_inside.zero_()
+        else:
+            y_along.fill_(inf)
+            y_ident[:] = miss
+            y_count.zero_()
+        cur, live, T = rays, None, None
+        rounds.clear()
+        for j in range(K):
+            m = cur.shape[0]
+            if m == 0:
+                break
+            rounds.append(m)
+            G.intersect_device(accel, m, cur.data_ptr(), hits.data_ptr(), stream=s)
+            h64, h32 = hits.view(torch.float64)[:m * 12].view(m, 12), hits.view(torch.int32)[:m * 24].view(m, 24)
+            hit = h32[:, 20] != 0
+            on = hit.nonzero().squeeze(1)  # (the compaction: its size comes back to the host)
+            idx = on if live is None else live[on]
+            t = h64[on, 0]
+            if xray:
+                if j & 1:
+                    y_inside[idx] += t
+            else:
+                T = t if T is None else T[on] + t
+                y_along[j, idx] = T
+                y_ident[j, idx] = h32[on, 20:24]
+                y_count[idx] += 1
+            nxt = cur[on]
+            nxt[:, :3] = h64[on, 1:4] - h64[on, 4:7] * ERR
+            cur, live = nxt, idx
+
+    rows = []
+    ms = timed(lambda: G.hit_layers_device(accel, n, rays.data_ptr(), K, along_ptr=along.data_ptr(), id_ptr=ident.data_ptr(), count_ptr=count.data_ptr(), stream=s), calls, warmup=1)
+    rows.append(("L8: hit layers, one call, along + id + count", ms, K * 24.0 + 4.0, None))
+    ms = timed(lambda: loop(False), max(calls // 2, 2), warmup=1)
+    rows.append(("Y8: K rounds of lg_intersect_device + torch moves and compaction, along + id + count", ms, K * 24.0 + 4.0, list(rounds)))
+    torch.cuda.synchronize()
+    assert torch.equal(along.view(torch.int64), y_along.view(torch.int64)) and torch.equal(ident, y_ident) and torch.equal(count, y_count), "Y8's planes are not L8's"
+    ms = timed(lambda: G.hit_layers_device(accel, n, rays.data_ptr(), K, inside_ptr=inside.data_ptr(), stream=s), calls, warmup=1)
+    rows.append(("LX: hit layers, one call, inside alone", ms, 8.0, None))
+    ms = timed(lambda: loop(True), max(calls // 2, 2), warmup=1)
+    rows.append(("YX: K rounds of lg_intersect_device + torch moves and compaction, inside alone", ms, 8.0, list(rounds)))
+    torch.cuda.synchronize()
+    assert torch.equal(inside.view(torch.int64), y_inside.view(torch.int64)), "YX's inside is not LX's"
+    cnt = count.cpu()
+    return [{"scene": name, "row": row, "film": [size, size], "rays": n, "max_layers": K, "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1),
+             "bytes_out_per_ray": bpr, "rounds": rnd, "count_hist": torch.bincount(cnt, minlength=K + 1).tolist(), "calls": calls,
+             "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+             "gpu": torch.cuda.get_device_name(0)} for row, ms, bpr, rnd in rows]
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -756,7 +840,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -765,8 +849,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -786,7 +870,9 @@ def main():
                 got += measure_views(name, builder, max(args.calls, 3))
             if "viewfeatures" in want:
                 got += measure_view_features(name, builder, max(args.calls, 3))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures"}:
+            if "layers" in want:
+                got += measure_layers(name, builder, args.size, max(args.calls, 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
