@@ -453,6 +453,38 @@ impl<'s> Accel<'s> {
         if rc != 0 { panic!("lasgun: {}", last_error()) }
         out
     }
+    /// The scene's point lights: the mask bits a light group may use (`lg_accel_light_count`).
+    pub fn light_count(&self) -> usize {
+        let n = unsafe { sys::lg_accel_light_count(self.ptr) };
+        if n < 0 { panic!("lasgun: {}", last_error()) }
+        n as usize
+    }
+    /// Light groups (`lg_radiance_groups`): `radiance` split by subsets of the scene's lights, `groups.len()` planes from one chain of
+    /// walks, group-major: plane g of ray r at `g * rays.len() + r`.  Plane g is what `radiance` returns on an accel rebuilt with the
+    /// lights of `groups[g].lights` alone (bit l: light l in add order) and, without `sys::LG_GROUP_AMBIENT` in its flags, no ambient
+    /// term -- bit for bit.  The background belongs to every group.  At most `sys::LG_MAX_LIGHT_GROUPS` groups.
+    pub fn radiance_groups(&self, rays: &[[f64; 6]], groups: &[sys::lg_light_group]) -> Vec<[f64; 3]> {
+        const _: () = assert!(std::mem::size_of::<sys::lg_light_group>() == 8);
+        let total = rays.len().checked_mul(groups.len()).expect("radiance_groups: rays.len() * groups.len() overflows usize");
+        let mut out = vec![[0f64; 3]; total];
+        if rays.is_empty() { return out }
+        let rc = unsafe {
+            sys::lg_radiance_groups(self.ptr, rays.as_ptr() as *const f64, rays.len(), groups.as_ptr(), groups.len(), out.as_mut_ptr() as *mut f64)
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+        out
+    }
+    /// `radiance_groups` for rays in device memory, enqueued on a HIP stream; `groups` is a host slice and may be dropped on return
+    ///
+    /// # Safety
+    /// `dev_rays` (6 n doubles) and `dev_radiance` (groups.len() * n * 3 doubles) must be device memory of the accel's device (the
+    /// library checks what HIP can tell it).
+    pub unsafe fn radiance_groups_device(&self, dev_rays: *const f64, n: usize, groups: &[sys::lg_light_group], dev_radiance: *mut f64,
+                                         hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_radiance_groups_device(self.ptr, dev_rays, n, groups.as_ptr(), groups.len(), dev_radiance, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
     /// Radiance gather (`lg_radiance_gather`): li() along `dirs[k]` from `origins[i]`, what `radiance` returns for that ray, at
     /// `i * dirs.len() + k` of `radiance`, and / or reduced per pose into `sums`: `sums[i * n_weights + c]` = the sum over k, in order from
     /// +0.0, of radiance(i, k) * `weights[k * n_weights + c]` (one product, one sum a step).  `None` = not asked for; not both.  `weights`:

@@ -258,6 +258,21 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void hit_layers_device(const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out &dev_out, void *hip_stream) const {
         if (lg_hit_layers_device(h_, dev_rays, n, max_layers, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // light groups (lg_radiance_groups): radiance() split by subsets of the scene's lights, groups.size() planes from one chain of walks,
+    // group-major: plane g of ray r at g * rays.size() + r.  Plane g is what radiance() returns on an accel rebuilt with the lights of
+    // groups[g].lights alone (bit l: light l in add order) and, without LG_GROUP_AMBIENT in its flags, no ambient term -- bit for bit
+    int light_count() const { return lg_accel_light_count(h_); }
+    std::vector<std::array<double, 3>> radiance_groups(const std::vector<std::array<double, 6>> &rays, const std::vector<lg_light_group> &groups) const {
+        static_assert(sizeof(lg_light_group) == 8, "lg_light_group: two 32-bit words");
+        if (!groups.empty() && rays.size() > SIZE_MAX / groups.size()) throw Error("radiance_groups: rays.size() * groups.size() does not fit size_t");
+        std::vector<std::array<double, 3>> out(rays.size() * groups.size());
+        if (rays.empty()) return out;
+        if (lg_radiance_groups(h_, rays[0].data(), rays.size(), groups.data(), groups.size(), out.empty() ? nullptr : out[0].data())) throw Error(lg_last_error());
+        return out;
+    }
+    void radiance_groups_device(const double *dev_rays, size_t n, const std::vector<lg_light_group> &groups, double *dev_radiance, void *hip_stream) const {
+        if (lg_radiance_groups_device(h_, dev_rays, n, groups.data(), groups.size(), dev_radiance, hip_stream)) throw Error(lg_last_error());
+    }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<std::array<double, 3>> out(rays.size());

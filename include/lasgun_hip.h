@@ -895,6 +895,51 @@ typedef struct lg_layers_out {
 int lg_hit_layers(const lg_accel *, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out); /* host arrays; synchronous */
 int lg_hit_layers_device(const lg_accel *, const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out *dev_out,
                          void *hip_stream);
+/* Light groups: li() of each ray split by subsets of the scene's lights, n_groups planes from one call -- light-group AOVs for
+ * compositing, re-lighting a frame afterwards by changing intensities and colours, a light-mixing slider, a per-light contribution for
+ * light placement -- without a scene and an accel rebuilt and a render repeated per group.  Nothing a walk finds depends on which
+ * lights are counted, so every group shares ONE chain of closest-hit and shadow walks; only the sums over the lights and the combine
+ * of the specular children carry n_groups planes.  li() is linear in the lights' intensities, so the planes of single lights, of the
+ * ambient term alone and of the empty group re-light a frame without tracing again.  An EXTRA; no counterpart in the reference.
+ * Groups: bit l of `lights` names light l, in lg_scene_add_point_light order; LG_GROUP_AMBIENT in `flags` makes the scene's ambient term
+ * part of the group.  Groups may overlap, repeat and be empty.  The background belongs to every group.
+ * Output: radiance is GROUP-MAJOR, element (g, r, c) at (g*n + r)*3 + c: n_groups * n * 3 doubles.  Every element is written, whatever
+ * the buffer held before, by exactly one lane: no atomics, no pre-fill.
+ * Value: plane g is lg_radiance's value for ray r, bit for bit and in the accel's traversal mode, on an accel built from the same scene
+ * with only the lights of groups[g].lights added, in their original order, and with the ambient colour (+0, +0, +0) unless
+ * LG_GROUP_AMBIENT is set.  As arithmetic, at every hit of every recursion level: the lights' terms are added in light order from zero,
+ * a light outside the mask skipped exactly as an invisible light is; the ambient term is added last, with the ambient colour replaced
+ * by zero for a group without the flag (the product with the BSDF is still formed: a NaN there stays a NaN); a hit's li is
+ * (output + reflected) + refracted per group with the same weights; a finished ray is (0 + li) * 1.0.  So a group with ALL lights and
+ * LG_GROUP_AMBIENT holds lg_radiance's very bytes, and a group with no lights and no flag holds the "base": the background and what the
+ * specular chain carries of it.  The render's shadow-skip stays valid: a hit where every light is irrelevant is one where each subset's
+ * lights are.
+ * Shared with lg_radiance: lg_accel_set_query_order(1) and the LASGUN_WF_BUDGET_MB chunks (the chunk also carries 24 * (n_groups - 1)
+ * bytes per ray of every level of a recursive scene), always the level-by-level pipeline, lg_profile_* credit its kernels as a render's
+ * (closest 0, combine and the deepest level's spread pass 1, shade 3).
+ * Limits and errors: n == 0 is a successful no-op whatever the pointers are.  Errors (non-zero, lg_last_error, nothing launched, no
+ * output touched), for n > 0: n_groups == 0 or > LG_MAX_LIGHT_GROUPS; a `lights` bit at or above the scene's light count
+ * (lg_accel_light_count); an unknown `flags` bit; a scene with more than 32 lights or a recursion depth of 20 or more (lg_radiance's two
+ * refusals); n > (2^32 - 1) * 64, and n > 2^32 - 1 with the sorted order; n * n_groups * 24 that does not fit size_t; a NULL accel,
+ * rays, groups or radiance; in the device form also rays or radiance that is not 8-byte aligned device memory of the accel's device or
+ * ends beyond its allocation.  `groups` is a HOST array in both forms: it travels by value in the launches' arguments and may be freed
+ * when the call returns.
+ * Device form: it only enqueues on hip_stream, with lg_radiance_device's exceptions (growing the level arrays, the sort's scratch).
+ * One stream at a time per accel.  Host form (synchronous): the planes come back into staging and are copied out at the end, so an
+ * error on the way leaves the caller's array as it was.
+ * Out of scope: films per group, groups for gathers, views and the render's own entry points, more than 32 lights, a background flag. */
+typedef struct lg_light_group {
+    uint32_t lights;   /* bit l: light l, in lg_scene_add_point_light order */
+    uint32_t flags;    /* LG_GROUP_AMBIENT or 0 */
+} lg_light_group;      /* 8 bytes */
+#define LG_GROUP_AMBIENT 1u      /* the scene's ambient term is part of the group */
+#define LG_MAX_LIGHT_GROUPS 64
+int lg_radiance_groups(const lg_accel *, const double *rays, size_t n, const lg_light_group *groups, size_t n_groups,
+                       double *radiance);                                   /* host arrays; synchronous */
+int lg_radiance_groups_device(const lg_accel *, const double *dev_rays, size_t n, const lg_light_group *groups /* host */, size_t n_groups,
+                              double *dev_radiance, void *hip_stream);
+/* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
+int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.
  * Results are identical bytes either way, in the caller's order. Any other value: non-zero return, lg_last_error.
  * The walk keeps a wave's 64 rays in step; rays that arrive in no particular order (collision probes, visibility between arbitrary

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CGatherOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -104,6 +104,7 @@ _EXTRA = {
     **DIRECTIONS_SIGNATURES,
     **RANGE_SCAN_SIGNATURES,
     **HIT_LAYERS_SIGNATURES,
+    **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
     **VIEWS_SIGNATURES,
@@ -941,6 +942,42 @@ class HipApi(Api):
         if self.call("radiance_device", accel.h, _C.c_void_p(int(rays_ptr)), int(n), _C.c_void_p(int(out_ptr)), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- light groups (include/lasgun_hip.h, lg_radiance_groups*): li() of each ray split by subsets of the scene's lights
+    def light_count(self, accel):
+        """The scene's point lights: the mask bits a LightGroup may use (include/lasgun_hip.h, lg_accel_light_count)."""
+        return int(self.call("accel_light_count", accel.h))
+
+    @staticmethod
+    def _groups(groups):
+        """The groups as a C array of lg_light_group: LightGroup records or (lights, flags) pairs."""
+        items = [g if isinstance(g, CLightGroup) else LightGroup(*g) for g in groups]
+        return (CLightGroup * max(len(items), 1))(*items), len(items)
+
+    def radiance_groups(self, accel, rays, groups, into=None):
+        """Radiance along every ray of an (n, 6) float64 array split by light groups: (G, n, 3) float64, plane g what `radiance` returns on
+        an accel rebuilt with the lights of groups[g].lights alone (bit l: light l in add order) and, without GROUP_AMBIENT in its flags,
+        no ambient term -- bit for bit, from ONE chain of walks.  The background belongs to every group.  groups: LightGroup records or
+        (lights, flags) pairs, at most MAX_LIGHT_GROUPS.  `into`: a C-contiguous (G, n, 3) float64 array written in place.  Also
+        `accel.radiance_groups(rays, groups)`."""
+        r = self._rays(rays)
+        table, k = self._groups(groups)
+        shape = (k, r.shape[0], 3)
+        out = into if into is not None else _np.zeros(shape, dtype=_np.float64)
+        if out.dtype != _np.float64 or out.shape != shape or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("into: a C-contiguous float64 array of shape %s" % (shape,))
+        if self.call("radiance_groups", accel.h, r.ctypes.data, r.shape[0], _C.addressof(table), k, out.ctypes.data if out.size else None):
+            raise LasgunError(self.last_error())
+        return out
+
+    def radiance_groups_device(self, accel, n, rays_ptr, groups, out_ptr, stream=None):
+        """Enqueue the light groups of n rays (device memory, 6 doubles each) into G * n * 3 doubles at out_ptr, group-major (both 8-byte
+        aligned).  groups: a host sequence, as for radiance_groups; it may be dropped when the call returns.  The pointers are integers
+        (torch: tensor.data_ptr()) or objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else _C.c_void_p(int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p))  # noqa: E731
+        table, k = self._groups(groups)
+        if self.call("radiance_groups_device", accel.h, ptr(rays_ptr), int(n), _C.addressof(table), k, ptr(out_ptr), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- ray films (include/lasgun_hip.h, lg_capture_rays* / lg_lens_rays*): a film from the caller's rays
     def capture_rays(self, accel, rays, w, h, samples=1, offsets=None, rgba=True, rgb=False, into=None):
         """The film of (slots * samples, 6) float64 rays, slot-major: slot g's rays are summed in order, scaled by 1 / samples and written at
@@ -1288,6 +1325,50 @@ def frames_from_normals(normals):
     return _np.ascontiguousarray(_np.stack([t, s, n], axis=2))
 
 
+def LightGroup(lights=0, ambient=False, flags=None):
+    """lg_light_group (include/lasgun_hip.h): `lights` a mask (bit l: light l in add order) or an iterable of light indices; `ambient`:
+    the scene's ambient term is part of the group (GROUP_AMBIENT); `flags`: the raw word instead."""
+    if not isinstance(lights, int):
+        mask = 0
+        for l in lights:
+            if not 0 <= int(l) < 32:
+                raise ValueError("a light index is 0 .. 31")
+            mask |= 1 << int(l)
+        lights = mask
+    return CLightGroup(int(lights), int(flags) if flags is not None else (GROUP_AMBIENT if ambient else 0))
+
+
+def per_light_groups(n_lights):
+    """The groups a re-lit frame needs: [base (no lights, no ambient), the ambient term alone, light 0, light 1, ...] -- 2 + n_lights
+    groups for radiance_groups; relight() takes its planes.  A convention of this WRAPPER, not of the C contract."""
+    n = int(n_lights)
+    if not 0 <= n <= 32:
+        raise ValueError("n_lights: 0 .. 32")
+    return [LightGroup(0), LightGroup(0, ambient=True)] + [LightGroup(1 << l) for l in range(n)]
+
+
+def relight(planes, ambient_scale=1.0, light_scales=None):
+    """A frame re-lit from per_light_groups' planes without tracing again: base + a * (amb - base) + sum_i s_i * (L_i - base), with
+    planes[0] the base, planes[1] the ambient plane and planes[2 + i] light i's; a = ambient_scale, s_i = light_scales[i] (a scalar, or
+    3 values per light to change its colour; None: all 1).  li() is linear in the intensities, so this is the frame the scaled scene
+    renders up to rounding -- it is NOT bit-exact against a rebuilt render: the render sums the lights' terms in one running sum at every
+    hit, this sums whole planes.  Evaluated left to right in float64.  A convention of this WRAPPER."""
+    p = _np.asarray(planes, dtype=_np.float64)
+    if p.ndim < 2 or p.shape[0] < 2 or p.shape[-1] != 3:
+        raise ValueError("planes: (2 + n_lights, ..., 3), as radiance_groups returns for per_light_groups")
+    n = p.shape[0] - 2
+    scales = [1.0] * n if light_scales is None else list(light_scales)
+    if len(scales) != n:
+        raise ValueError("light_scales: one scalar or 3 values per light, %d lights" % n)
+    s = [_np.broadcast_to(_np.asarray(x, dtype=_np.float64), (3,)) for x in scales]
+    a = _np.broadcast_to(_np.asarray(ambient_scale, dtype=_np.float64), (3,))
+    base = p[0]
+    out = base + a * (p[1] - base)
+    for i in range(n):
+        out = out + s[i] * (p[2 + i] - base)
+    return out
+
+
 def view_look_at(origin, look, up, fov=None, scale=None, supersampling=0):
     """api.view_look_at at package level: a View from a look-at camera (perspective `fov` degrees, or orthographic `scale`)."""
     return api.view_look_at(origin, look, up, fov=fov, scale=scale, supersampling=supersampling)
@@ -1330,6 +1411,7 @@ api.Accel.visibility = lambda self, from_pts, to_pts, counts=False: api.visibili
 api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=False: api.open_directions(self, points, dirs, normals, counts)  # accel.open_directions(points, dirs)
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
+api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
 api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
 api.Accel.views = lambda self, views, w, h, rgba=True, rgb=False: api.capture_views(self, views, w, h, rgba, rgb)  # accel.views(views, w, h)
 api.Accel.view_features = lambda self, views, w, h, planes=VIEW_FEATURE_PLANES, material_rgb=None: api.capture_view_features(self, views, w, h, planes, material_rgb)  # accel.view_features(views, w, h)

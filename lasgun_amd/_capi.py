@@ -168,6 +168,16 @@ HIT_LAYERS_SIGNATURES = {
     "hit_layers_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
+# Light groups (include/lasgun_hip.h, lg_radiance_groups / lg_radiance_groups_device / lg_accel_light_count): li() of each ray split by
+# subsets of the scene's lights, group-major planes from one call; the GPU library's alone.
+LIGHT_GROUPS_SIGNATURES = {
+    "radiance_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "radiance_groups_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "accel_light_count": (C.c_int, [C.c_void_p]),
+}
+GROUP_AMBIENT = 1  # LG_GROUP_AMBIENT
+MAX_LIGHT_GROUPS = 64  # LG_MAX_LIGHT_GROUPS
+
 # Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
 # directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
 GATHER_SIGNATURES = {
@@ -224,6 +234,10 @@ class CScanOut(C.Structure):  # lg_scan_out: six pointers, 48 bytes; NULL = not 
 
 class CLayersOut(C.Structure):  # lg_layers_out: five pointers, 40 bytes; NULL = not asked for
     _fields_ = [("hits", C.c_void_p), ("along", C.c_void_p), ("id", C.c_void_p), ("count", C.c_void_p), ("inside", C.c_void_p)]
+
+
+class CLightGroup(C.Structure):  # lg_light_group: 8 bytes; bit l of `lights` = light l in add order, flags = GROUP_AMBIENT or 0
+    _fields_ = [("lights", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for

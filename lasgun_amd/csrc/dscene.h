@@ -406,6 +406,19 @@ struct FilmArgs : RadianceArgs {
     double *rgb;                       // f64 RGB before quantisation, 3 per pixel; may be nullptr
 };
 
+// Light groups (k_light_groups.hip; lg_radiance_groups*): the same query with G planes of li per ray, plane g counting the lights of
+// groups[g] alone.  Plane 0 of every level is the pipeline's own wf_out / wf_out_next; planes 1 .. G-1 of the level a launch works on are
+// `xout` (plane g, channel c, ray j at ((g-1)*3 + c) * wf_cap + j) and those of the level below `xout_next` (with wf_cap_next), both
+// set per launch by the chain.  `radiance` is [G][n][3].  The table travels by value: DParams gets no field for it.
+constexpr uint32_t MAX_LIGHT_GROUPS = 64u; // == LG_MAX_LIGHT_GROUPS
+constexpr uint32_t GROUP_AMBIENT = 1u;     // == LG_GROUP_AMBIENT
+struct DLightGroup { uint32_t lights, flags; }; // == lg_light_group
+struct GroupArgs : RadianceArgs {
+    double *xout, *xout_next;
+    uint32_t n_groups, pad;
+    DLightGroup groups[MAX_LIGHT_GROUPS];
+};
+
 // A radiance gather's level 0 (k_gather.hip; lg_radiance_gather*), beside the DParams of its chunk: the two tables the rays are made from,
 // where li goes, and where the chunk starts.  A batch of a call is a call of its own here: its poses' tables, its own li.
 struct GatherArgs {

@@ -59,6 +59,13 @@ hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks,
 hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream);
 hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
+// k_light_groups.hip: light groups (lg_radiance_groups*; launch.cpp, enqueue_radiance_groups) -- the radiance query's level-0 closest pass with
+// a GroupArgs, and the shade and combine passes of EVERY level (P.wf_level) carrying Q.n_groups planes; the spread pass of the deepest level
+hipError_t launch_lg_closest(const DParams &P, const GroupArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_lg_shade(const DParams &P, const GroupArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_lg_combine(const DParams &P, const GroupArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t launch_lg_spread(const DParams &P, const GroupArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t light_groups_set_lds_limit(size_t bytes, bool ldss);
 // k_gather.hip: level 0 a third time, for the rays of a radiance gather (launch.cpp, enqueue_radiance_gather), and its reduction:
 // sums[(i*n_weights + c)*3 ..] = the sequential weighted sum of pose i's li over the directions
 hipError_t launch_gather_closest(const DParams &P, const GatherArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
@@ -564,6 +571,9 @@ bool scene_lds_image(const Scene &scene, bool pairs, std::vector<uint32_t> &img,
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
+// One checked lg_radiance_groups* call: `groups` is the host table of n_groups entries (it travels by value in every launch's arguments)
+void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, const DLightGroup *groups, uint32_t n_groups, double *radiance, const uint32_t *perm,
+                             lg_accel::LaunchCtx &c, hipStream_t stream);
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream);
 // One checked lg_radiance_gather* call on device tables (query.cpp; gather_host.h): batch_poses = n_poses where radiance is given

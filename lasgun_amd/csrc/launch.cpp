@@ -229,24 +229,36 @@ struct ChunkPlan {
     }
 };
 
-// Whose forms of level 0's three passes a chain of the level-by-level pipeline runs.  At most one is set: `rq` a radiance query's rays
+// Whose forms the passes of a chain of the level-by-level pipeline take.  At most one is set: `rq` a radiance query's rays
 // (k_radiance.hip), `rf` a ray film's (its film forms), `rg` a radiance gather's, made in the kernel from two tables (k_gather.hip), `rv` a view
-// batch's, made in the kernel from a table of cameras (k_views.hip).  None: the scene's own camera (k_wavefront.hip) -- a render.
+// batch's, made in the kernel from a table of cameras (k_views.hip): level 0's three passes, the levels below are the render's.  `lg` light
+// groups (k_light_groups.hip): level 0's three passes AND the shade and combine passes of every level below (every_level), which carry
+// lg->n_groups planes, with a spread pass at the deepest level; `xout` then holds each level's planes 1 .. G-1 (WfChunk::xout) and level()
+// tells lg which the next launches work on.  None: the scene's own camera (k_wavefront.hip) -- a render.
 struct Level0 {
     const RadianceArgs *rq = nullptr;
     const FilmArgs *rf = nullptr;
     const GatherArgs *rg = nullptr;
     const ViewArgs *rv = nullptr;
-    bool own() const { return rq || rf || rg || rv; }
+    GroupArgs *lg = nullptr;
+    const std::vector<double *> *xout = nullptr;
+    bool own() const { return rq || rf || rg || rv || lg; }
+    bool every_level() const { return lg != nullptr; }
+    void level(uint32_t d) const {
+        if (!lg) return;
+        lg->xout = (*xout)[d];
+        lg->xout_next = d + 1 < xout->size() ? (*xout)[d + 1] : nullptr;
+    }
+    hipError_t spread(const DParams &P, uint32_t blocks, hipStream_t s) const { return launch_lg_spread(P, *lg, blocks, s); }
     hipError_t closest(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const {
-        return rv ? launch_view_closest(P, *rv, fast, blocks, depth, s) : rg ? launch_gather_closest(P, *rg, fast, blocks, depth, s) : rf ? launch_rf_closest(P, *rf, fast, blocks, depth, s)
+        return lg ? launch_lg_closest(P, *lg, fast, blocks, depth, s) : rv ? launch_view_closest(P, *rv, fast, blocks, depth, s) : rg ? launch_gather_closest(P, *rg, fast, blocks, depth, s) : rf ? launch_rf_closest(P, *rf, fast, blocks, depth, s)
                                                                                                                                 : launch_rq_closest(P, *rq, fast, blocks, depth, s);
     }
     hipError_t shade(const DParams &P, uint32_t blocks, hipStream_t s) const {
-        return rv ? launch_view_shade(P, *rv, blocks, s) : rg ? launch_gather_shade(P, *rg, blocks, s) : rf ? launch_rf_shade(P, *rf, blocks, s) : launch_rq_shade(P, *rq, blocks, s);
+        return lg ? launch_lg_shade(P, *lg, blocks, s) : rv ? launch_view_shade(P, *rv, blocks, s) : rg ? launch_gather_shade(P, *rg, blocks, s) : rf ? launch_rf_shade(P, *rf, blocks, s) : launch_rq_shade(P, *rq, blocks, s);
     }
     hipError_t combine(const DParams &P, uint32_t blocks, hipStream_t s) const {
-        return rv ? launch_view_combine(P, *rv, blocks, s) : rg ? launch_gather_combine(P, *rg, blocks, s) : rf ? launch_rf_combine(P, *rf, blocks, s) : launch_rq_combine(P, *rq, blocks, s);
+        return lg ? launch_lg_combine(P, *lg, blocks, s) : rv ? launch_view_combine(P, *rv, blocks, s) : rg ? launch_gather_combine(P, *rg, blocks, s) : rf ? launch_rf_combine(P, *rf, blocks, s) : launch_rq_combine(P, *rq, blocks, s);
     }
 };
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
@@ -257,7 +269,8 @@ static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, 
         P.wf_level = d;
         P.wf_cap = n0 << d; P.wf_cap_next = n0 << (d + 1);
         P.wf_out = K.out[d]; P.wf_spec = K.spec[d]; P.wf_child = K.child[d]; P.wf_out_next = K.out[d + 1];
-        if (d == 0 && l0.own()) timed(a, 1, s, [&] { return l0.combine(P, flat_blocks0, s); });
+        l0.level(d);
+        if (l0.own() && (d == 0 || l0.every_level())) timed(a, 1, s, [&] { return l0.combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
         else timed(a, 1, s, [&] { return launch_wf_combine(P, d == 0 ? flat_blocks0 : flat_cap, s); });
     }
 }
@@ -311,8 +324,13 @@ struct WfChunk {
     LevelArrays L;
     uint32_t *hq = nullptr, *vis = nullptr, *counters = nullptr;
     double *frame = nullptr;
-    WfChunk(const ChunkPlan &p) : plan(p), levels(p.levels), nlaunch(4 * p.levels) {}
-    static size_t extra_per_item(uint32_t levels) { return ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4; } // ChunkPlan's `extra`
+    uint32_t groups;             // light groups (Level0::lg): planes of li per ray of every level; 1 for every other chain
+    std::vector<double *> xout;  // ... planes 1 .. groups-1 of each level, where there are any (plane 0 is L.out)
+    WfChunk(const ChunkPlan &p, uint32_t groups_ = 1) : plan(p), levels(p.levels), nlaunch(4 * p.levels), groups(groups_) {}
+    // ChunkPlan's `extra`: the hit queue, frame and visibility of the widest level; and 3 * 8 * (groups - 1) bytes per ray of each level of a recursive scene
+    static size_t extra_per_item(uint32_t levels, uint32_t groups = 1) {
+        return ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4 + (levels > 1 ? (size_t)3 * 8 * (groups - 1) * (((size_t)1 << levels) - 1) : 0);
+    }
     size_t hit_cap() const { return (size_t)plan.n0() << (levels - 1); }
     size_t hit_len() const { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); } // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
     void carve(lg_accel::LaunchCtx &cx) { // this context's arrays for one chunk, grown if they have to be
@@ -322,6 +340,8 @@ struct WfChunk {
             hq = (uint32_t *)take(hit_len() * 4);
             frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
             vis = (uint32_t *)take(hit_len() * 4);
+            xout.assign(levels, nullptr);
+            for (uint32_t d = 0; levels > 1 && groups > 1 && d < levels; ++d) xout[d] = (double *)take(((size_t)plan.n0() << d) * 3 * 8 * (groups - 1));
         });
         counters = cx.wf_counters.p;
     }
@@ -353,6 +373,7 @@ struct WfChunk {
             P.wf_q_next = d + 1 < levels ? L.q[d + 1] : nullptr;
             P.wf_out_next = d + 1 < levels ? L.out[d + 1] : nullptr;
             P.tile_counter = counters + CL * (1 + launch_no++);
+            l0.level(d);
         };
         for (uint32_t d = 0; d < levels; ++d) {
             // (deeper levels: the number of rays is only known on the device; grids are sized for a full level 0, which
@@ -373,7 +394,9 @@ struct WfChunk {
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
             }
             level_params(d);
-            if (own0) timed(a, 3, ls, [&] { return l0.shade(P, fb, ls); });
+            // (light groups, the deepest level of a recursive scene: the closest pass left a miss's background in plane 0 alone)
+            if (l0.every_level() && d >= 1 && d + 1 == levels) timed(a, 1, ls, [&] { return l0.spread(P, flat_cap, ls); });
+            if (own0 || l0.every_level()) timed(a, 3, ls, [&] { return l0.shade(P, fb, ls); });
             else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
         P.packet = 0u;
@@ -475,6 +498,8 @@ struct Level0Source {
     double *radiance = nullptr;         // ... into radiance[] ...
     const FilmArgs *film = nullptr;     // ... or into a film
     const uint32_t *perm = nullptr;
+    const DLightGroup *groups = nullptr; // ... or, split by light groups, into the n_groups planes of radiance[] (host table)
+    uint32_t n_groups = 0;
     const GatherArgs *gather = nullptr; // a radiance gather (base_tile is the chunk's to set)
     uint32_t gather_tiles = 0;
     const ViewArgs *views = nullptr;    // a view batch (base_tile is the chunk's to set)
@@ -488,8 +513,9 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_
     const uint32_t S = P0.ss_root * P0.ss_root; // level-0 work items per pixel (views alone: > 1)
     P0.ntiles = src.views ? src.view_tiles : src.gather ? src.gather_tiles : (uint32_t)((src.n + 63) / 64);
     const uint32_t levels = levels_of(a, P0);
-    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels));
-    WfChunk K(plan);
+    const uint32_t G = src.groups ? src.n_groups : 1u; // planes of li per ray of every level
+    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, G));
+    WfChunk K(plan, G);
     plan.fit([&] { K.carve(c); });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
     Span span(a, stream);
@@ -527,7 +553,15 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_
         const RadianceArgs Q{src.rays, src.radiance, src.perm, (unsigned long long)src.n, t0 * 64ull};
         Level0 l0;
         FilmArgs F;
-        if (src.film) {
+        GroupArgs GA;
+        if (src.groups) {
+            std::memset(&GA, 0, sizeof GA);
+            static_cast<RadianceArgs &>(GA) = Q;
+            GA.n_groups = G;
+            std::memcpy(GA.groups, src.groups, G * sizeof(DLightGroup));
+            l0.lg = &GA;
+            l0.xout = &K.xout;
+        } else if (src.film) {
             F = *src.film;
             static_cast<RadianceArgs &>(F) = Q;
             l0.rf = &F;
@@ -546,6 +580,16 @@ static Level0Source ray_source(const double *rays, size_t n, double *radiance, c
 }
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
     enqueue_level0_query(a, ray_source(rays, n, radiance, nullptr, perm, "radiance query"), c, stream);
+}
+// Light groups (query.cpp, lg_radiance_groups*; the call checked there and in light_groups_host.h): the same query with n_groups planes of li
+// per ray at every level -- the chunk carries planes 1 .. G-1 beside the level arrays, and the chain takes the shade and combine passes of
+// every level, and a spread pass at the deepest, from k_light_groups.hip (Level0::lg).  The walks are the radiance query's.
+void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, const DLightGroup *groups, uint32_t n_groups, double *radiance, const uint32_t *perm,
+                             lg_accel::LaunchCtx &c, hipStream_t stream) {
+    Level0Source src = ray_source(rays, n, radiance, nullptr, perm, "radiance groups");
+    src.groups = groups; src.n_groups = n_groups;
+    src.note += ", " + std::to_string(n_groups) + " groups";
+    enqueue_level0_query(a, src, c, stream);
 }
 // A radiance gather (query.cpp, lg_radiance_gather*; the call checked there and in gather_host.h): batch after batch of g.batch_poses whole
 // consecutive poses, each a level-0 query of its own over the batch's tiles -- its poses' rows of the tables, its own li -- with the

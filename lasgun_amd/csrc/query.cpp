@@ -13,6 +13,7 @@
 #include "features_host.h"
 #include "gather_host.h"
 #include "layers_host.h"
+#include "light_groups_host.h"
 #include "scan_host.h"
 #include "views_host.h"
 #include "view_features_host.h"
@@ -409,6 +410,53 @@ extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, siz
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         check_device_buffer(*a, dev_radiance, n * 3 * sizeof(double), 8, "radiance");
         enqueue_radiance_query(*a, dev_rays, n, dev_radiance, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- light groups (lg_radiance_groups*; launch.cpp, enqueue_radiance_groups; k_light_groups.hip): the radiance query with n_groups planes
+// of li per ray.  What needs no device -- the limits, a group's rules, the sizes, the NULL and alignment rules, the table as it travels, the
+// host form's staging -- is light_groups_host.h's.
+static_assert(sizeof(DLightGroup) == sizeof(lg_light_group) && MAX_LIGHT_GROUPS == LG_MAX_LIGHT_GROUPS && GROUP_AMBIENT == LG_GROUP_AMBIENT, "dscene.h restates the contract's group");
+extern "C" int lg_accel_light_count(const lg_accel *a) { return a ? (int)a->flat.lights.size() : -1; }
+// One call enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers)
+static void enqueue_groups_query(const lg_accel &a, const double *rays, size_t n, const GroupTable &table, double *radiance, hipStream_t stream) {
+    check_queue_error(a);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream);
+    enqueue_radiance_groups(a, rays, n, reinterpret_cast<const DLightGroup *>(table.groups), table.n_groups, radiance, perm, c, stream);
+}
+extern "C" int lg_radiance_groups(const lg_accel *a, const double *rays, size_t n, const lg_light_group *groups, size_t n_groups, double *radiance) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        GroupTable table;
+        const GroupsShape shape = check_light_groups(a, rays, n, groups, n_groups, radiance, a->flat.lights.size(), table);
+        check_sorted_count(*a, n);
+        radiance_possible(*a);
+        RoundTrip trip(*a);
+        GroupsStaging st(shape);
+        const double *drays = trip.in(rays, shape.ray_doubles);
+        double *dout = trip.out(st.radiance.data(), shape.out_doubles);
+        trip.run([&] { enqueue_groups_query(*a, drays, n, table, dout, a->stream); });
+        place_light_groups(radiance, st);
+    });
+}
+extern "C" int lg_radiance_groups_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_light_group *groups, size_t n_groups, double *dev_radiance,
+                                         void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        if (!a) throw Error("accel is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        GroupTable table;
+        const GroupsShape shape = check_light_groups(a, dev_rays, n, groups, n_groups, dev_radiance, a->flat.lights.size(), table);
+        check_light_groups_alignment(dev_rays, dev_radiance);
+        check_sorted_count(*a, n);
+        radiance_possible(*a);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, shape.ray_doubles * sizeof(double), 8, "rays");
+        check_device_buffer(*a, dev_radiance, shape.out_doubles * sizeof(double), 8, "radiance");
+        enqueue_groups_query(*a, dev_rays, n, table, dev_radiance, (hipStream_t)hip_stream);
     });
 }
 

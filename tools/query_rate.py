@@ -66,7 +66,11 @@ id + count; row LX: the same call with inside alone (the x-ray image, 8 bytes ou
 Y8 / YX, 8 rounds of lg_intersect_device with the planes pre-filled, the next origins computed and the live rays compacted by torch on the
 same stream (the compaction's size comes back to the host every round: the route needs it).  Timed L8, Y8, LX, YX, so --repeats alternates
 them; Y's planes are checked against L's bytes.  These rows time --calls calls as given (at least 4; the Y rows half as many), not 20.
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers[,...]] [--out profiles/r08_query_order.jsonl]
+Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
+point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
+Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
+row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -811,6 +815,60 @@ def measure_layers(name, builder, size, calls, K=8):
              "gpu": torch.cuda.get_device_name(0)} for row, ms, bpr, rnd in rows]
 
 
+GROUP_LIGHTS = 4  # the builder's one light and three more (measure_groups)
+_GROUP_ACCELS = {}  # scene name -> (the accels rebuilt per group, their build's wall-clock ms): built once, whatever --repeats says
+
+
+def measure_groups(name, builder, size, calls):
+    """Light groups on the camera's rays of a size^2 film, the scene with FOUR point lights: the builder's own at L = (x, y, z) and three more
+    at L + (0.8, -0.25, 0.8), L + (-0.8, -0.25, 0.8) and L + (0, -0.25, -0.8) (the three scenes share one Cornell shell with L under its ceiling) with intensities (0.5, 0.4, 0.3), (0.3, 0.4, 0.5), (0.4, 0.5, 0.3) and falloff (1, 0, 0).  G = 6:
+    per_light_groups(4) -- base, ambient, the four lights.  Row G6: one lg_radiance_groups_device call.  Beside it, in the same session: row
+    GK, G calls of lg_radiance_device on G accels rebuilt per group (tests/light_subsets.py; the builds timed apart, host wall clock:
+    build_ms), and row R1, ONE lg_radiance_device call on the full scene -- the floor: the difference to G6 is what G planes cost.  Timed
+    G6, GK, R1, so --repeats alternates them; GK's planes are compared with G6's bytes (same_bytes)."""
+    if not hasattr(G, "radiance_groups_device"):
+        return []
+    from light_subsets import subset_scene
+    x, y, z = builder(pyref.Api).lights[0][0]
+    extra = [((x + 0.8, y - 0.25, z + 0.8), (0.5, 0.4, 0.3)), ((x - 0.8, y - 0.25, z + 0.8), (0.3, 0.4, 0.5)), ((x, y - 0.25, z - 0.8), (0.4, 0.5, 0.3))]
+
+    def four(api):
+        scene = builder(api)
+        for pos, col in extra:
+            scene.add_point_light(list(pos), list(col), [1.0, 0.0, 0.0])
+        return scene
+
+    accel = G.Accel.from_scene(four(G))
+    assert G.light_count(accel) == GROUP_LIGHTS
+    groups = la.per_light_groups(GROUP_LIGHTS)
+    k = len(groups)
+    if name not in _GROUP_ACCELS:
+        t0 = time.time()
+        rebuilt = [G.Accel.from_scene(subset_scene(G, four, g.lights, bool(g.flags & la.GROUP_AMBIENT))) for g in groups]
+        _GROUP_ACCELS[name] = (rebuilt, (time.time() - t0) * 1e3)
+    rebuilt, build_ms = _GROUP_ACCELS[name]
+    s = torch.cuda.current_stream().cuda_stream
+    for a in [accel] + rebuilt:
+        G.set_query_order(a, 0)
+    assert G.camera_samples(accel) == 1
+    n = size * size
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    planes = torch.empty((k, n, 3), dtype=torch.float64, device="cuda")
+    other = torch.empty((k, n, 3), dtype=torch.float64, device="cuda")
+    rows = []
+    ms = timed(lambda: G.radiance_groups_device(accel, n, rays.data_ptr(), groups, planes.data_ptr(), stream=s), calls, warmup=1)
+    rows.append(("G6: radiance groups, one call, base + ambient + %d lights" % GROUP_LIGHTS, ms, k, None))
+    ms = timed(lambda: [G.radiance_device(a, n, rays.data_ptr(), other.data_ptr() + 24 * n * i, stream=s) for i, a in enumerate(rebuilt)], calls, warmup=1)
+    torch.cuda.synchronize()
+    rows.append(("GK: lg_radiance_device on G accels rebuilt per group, G calls", ms, k, {"build_ms": round(build_ms, 1), "same_bytes": bool(torch.equal(planes.view(torch.int64), other.view(torch.int64)))}))
+    ms = timed(lambda: G.radiance_device(accel, n, rays.data_ptr(), other.data_ptr(), stream=s), calls, warmup=1)
+    rows.append(("R1: lg_radiance_device, the full scene, one call (the floor)", ms, 1, None))
+    return [{"scene": name, "row": row, "film": [size, size], "rays": n, "lights": GROUP_LIGHTS, "planes": p, "light_positions": [[x, y, z]] + [list(e[0]) for e in extra],
+             "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1), **(x_ or {}), "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2",
+             "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, p, x_ in rows]
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -840,7 +898,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -849,8 +907,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -872,7 +930,9 @@ def main():
                 got += measure_view_features(name, builder, max(args.calls, 3))
             if "layers" in want:
                 got += measure_layers(name, builder, args.size, max(args.calls, 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers"}:
+            if "groups" in want:
+                got += measure_groups(name, builder, args.size, max(args.calls, 3))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
