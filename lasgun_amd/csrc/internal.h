@@ -66,7 +66,7 @@ hipError_t launch_lg_shade(const DParams &P, const GroupArgs &Q, uint32_t blocks
 hipError_t launch_lg_combine(const DParams &P, const GroupArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t launch_lg_spread(const DParams &P, const GroupArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t light_groups_set_lds_limit(size_t bytes, bool ldss);
-// k_gather.hip: level 0 a third time, for the rays of a radiance gather (launch.cpp, enqueue_radiance_gather), and its reduction:
+// k_gather.hip: level 0 for the rays of a radiance gather (launch.cpp, enqueue_radiance_gather), and its reduction:
 // sums[(i*n_weights + c)*3 ..] = the sequential weighted sum of pose i's li over the directions
 hipError_t launch_gather_closest(const DParams &P, const GatherArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_gather_shade(const DParams &P, const GatherArgs &Q, uint32_t blocks, hipStream_t stream);
@@ -74,7 +74,7 @@ hipError_t launch_gather_combine(const DParams &P, const GatherArgs &Q, uint32_t
 hipError_t launch_gather_resolve(const double *li, const double *weights, double *sums, unsigned long long n_poses, unsigned long long n_dirs, unsigned long long n_weights,
                                  uint32_t blocks, hipStream_t stream);
 hipError_t gather_set_lds_limit(size_t bytes, bool ldss);
-// k_views.hip: level 0 a fourth time, for the cameras of a view batch (launch.cpp, enqueue_view_batch), and the resolve pass of its chunks
+// k_views.hip: level 0 for the cameras of a view batch (launch.cpp, enqueue_view_batch), and the resolve pass of its chunks
 // (P.ntiles = the chunk's pixel tiles) where a pixel has several samples
 hipError_t launch_view_closest(const DParams &P, const ViewArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_view_shade(const DParams &P, const ViewArgs &Q, uint32_t blocks, hipStream_t stream);

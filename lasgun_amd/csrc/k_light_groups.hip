@@ -5,7 +5,7 @@
 // weights, and the shadow pass's visibility word (one bit per light) are the same for every subset.  So the call is k_radiance.hip's
 // pipeline -- the caller's rays as level 0, the render's own wf_trace_kernels for the shadow pass of every level and the closest pass of
 // the levels below -- and only what SUMS lights carries G planes, at every level: the shade pass (lg_shade_kernel: wf_shade_kernel /
-// rq_shade_body with the group loop) and the combine pass (lg_combine_kernel: wf_combine_kernel / rq_combine_body per group).  Plane g is
+// l0_shade_body with the group loop) and the combine pass (lg_combine_kernel: wf_combine_kernel / l0_combine_body per group).  Plane g is
 // what lg_radiance returns on an accel rebuilt with the lights of groups[g].lights alone and, without LG_GROUP_AMBIENT, an ambient
 // colour of +0: shade_lights' expression where a light outside the mask is skipped as an invisible one is and P.ambient becomes
 // vzero() (the product is still formed).  Each group's additions run in light order from vzero(): groups outside, lights inside, the
@@ -18,31 +18,34 @@
 // rays into the other planes between that level's closest and shade passes (the shade pass then overwrites the hits).
 #include "wflevel.h"
 #include "travform.h"
+#include "level0.h"
 
 namespace lg {
 
 static_assert(sizeof(DLightGroup) == 8 && sizeof(GroupArgs) == sizeof(RadianceArgs) + 24 + 8 * MAX_LIGHT_GROUPS, "GroupArgs: the query, two plane pointers, the count, the table");
 static_assert(sizeof(DParams) + sizeof(GroupArgs) <= 4096, "both are passed by value: a kernel's arguments are at most 4 KB");
 
-// (k_radiance.hip's, word for word: the query's slots, rays and the finish of one value)
-template <bool PERM> __device__ __forceinline__ unsigned long long rq_ray_index(const RadianceArgs &Q, unsigned long long slot) {
-    return PERM ? (unsigned long long)Q.perm[slot] : slot;
-}
-__device__ __forceinline__ Ray rq_load_ray(const RadianceArgs &Q, unsigned long long r) {
-    const double2 *p = reinterpret_cast<const double2 *>(Q.rays + 6ull * r);
-    const double2 a = p[0], b = p[1], c = p[2];
-    return ray_new(V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}); // Ray3::new: the direction as given
-}
 // integrate() for a pixel whose one sample is this ray, into plane g: radiance[(g*n + r)*3 ..] = (0 + li) * 1.0 (integrate.rs:16-20)
 __device__ __forceinline__ void lg_finish(const GroupArgs &Q, unsigned long long r, uint32_t g, V3 value) {
-    const V3 color = (vzero() + value) * 1.0;
-    double *o = Q.radiance + ((unsigned long long)g * Q.n + r) * 3ull;
-    o[0] = color.x; o[1] = color.y; o[2] = color.z;
+    l0_finish_at(Q.radiance + ((unsigned long long)g * Q.n + r) * 3ull, value);
 }
-// a ray that missed with no recursion at all: the background belongs to every group
-__device__ __forceinline__ void rq_finish(const GroupArgs &Q, unsigned long long r, V3 value) {
-    for (uint32_t g = 0; g < Q.n_groups; ++g) lg_finish(Q, r, g, value);
-}
+// Level 0's source (level0.h) for the closest pass: work item i = tile * 64 + lane of a chunk stands for SLOT s = Q.base + i of the query,
+// active while s < Q.n; the item is the slot, and the ray's index is read where it is used, not carried across the walk.  The finish is a
+// ray that missed with no recursion at all: the background belongs to every group.
+template <bool PERM> struct GroupRaySource {
+    const GroupArgs &Q;
+    struct Item { unsigned long long slot; };
+    __device__ __forceinline__ bool work_item(const DParams &, unsigned long long j, Item &it) const {
+        it.slot = Q.base + j;
+        return it.slot < Q.n;
+    }
+    __device__ __forceinline__ bool tile_item(const DParams &P, uint32_t tile, uint32_t lane, Item &it) const { return work_item(P, (unsigned long long)tile * 64ull + lane, it); }
+    __device__ __forceinline__ Ray ray(const DParams &, const Item &it) const { return rq_load_ray(Q, rq_ray_index<PERM>(Q, it.slot)); }
+    __device__ __forceinline__ void finish(const DParams &, const Item &it, unsigned long long, V3 value) const {
+        const unsigned long long r = rq_ray_index<PERM>(Q, it.slot);
+        for (uint32_t g = 0; g < Q.n_groups; ++g) lg_finish(Q, r, g, value);
+    }
+};
 // plane g of a level's li: channel c of ray j at [c * cap + j]
 __device__ __forceinline__ double *lg_plane(double *plane0, double *xplanes, unsigned long long cap, uint32_t g) {
     return g == 0u ? plane0 : xplanes + (unsigned long long)(g - 1u) * 3ull * cap;
@@ -52,10 +55,10 @@ __device__ __forceinline__ void lg_store(double *plane, unsigned long long cap, 
 }
 __device__ __forceinline__ V3 lg_load(const double *plane, unsigned long long cap, unsigned long long j) { return V3{plane[j], plane[cap + j], plane[2 * cap + j]}; }
 
-// W1 of level 0: rq_closest_body.h a third time, Q a GroupArgs (rq_finish above writes a finished miss into all G planes)
+// W1 of level 0: level0.h's closest body over the query's rays (the source above writes a finished miss into all G planes)
 template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) lg_closest_kernel(const DParams P, const GroupArgs Q) {
-#include "rq_closest_body.h"
+    l0_closest_body<FAST, LDSS, PRUNE>(P, GroupRaySource<PERM>{Q});
 }
 
 // shade_lights (shade.h, integrate.rs:47-67) for one group: `vis` is the shadow pass's word AND the group's mask -- a light outside the

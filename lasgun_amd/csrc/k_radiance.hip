@@ -1,52 +1,21 @@
 // lasgun_amd/csrc/k_radiance.hip -- radiance queries (include/lasgun_hip.h, lg_radiance*): LEVEL 0 of the level-by-level pipeline
 // (k_wavefront.hip) for rays the caller supplies instead of the rays a camera generates for a film.
 //
-// A query is li() of n rays.  The pipeline's levels >= 1 never knew where level 0's rays came from: they read a ray queue and leave li
-// in a per-level array, so the shadow pass of every level, the closest / shade passes of the levels below and every combine above
-// level 0 are the render's own kernels.  What is welded to the camera in k_wavefront.hip is level 0 -- camera_ray() / pixel_of() /
-// finish_pixel() -- and these are its three passes again with that replaced, the walk, the hit queue, the parked frame and every
-// f64 expression kept as they are there (the two files are meant to be read side by side; the existing kernels are not touched, several
-// sit at their register budget):
+// A query is li() of n rays.  These are level 0's three passes (level0.h says what they are and what a source replaces in them) in this
+// family's OWN text: rq_closest_body.h, rq_shade_body, rq_combine_body -- the text level0.h's bodies were made from, with the query's slots,
+// rays and finish (level0.h: rq_ray_index, rq_load_ray, rq_finish, film_store) written in place:
 //   * work item i = tile * 64 + lane of a chunk stands for SLOT s = base + i of the query, active while s < n, and walks
 //     ray r = perm ? perm[s] : s (lg_accel_set_query_order(1): the chunks are cut from the sorted order, k_sort.hip);
-//   * the ray is read from the caller's AoS buffer (48 bytes, three 16-byte loads, as k_query.hip reads it) in the closest pass and
-//     again in the shade pass (wo depends on it) -- no transposed copy of the rays, no gather pass over the results;
-//   * a finished ray is radiance[3r ..] = (0 + li) * 1.0, what integrate() leaves for a pixel of one sample (integrate.rs:16-20): no
-//     Pixel, no sample accumulator, no resolve pass.  Every r is written exactly once (perm is a permutation of 0 .. n-1).
+//   * the ray is read from the caller's AoS buffer in the closest pass and again in the shade pass (wo depends on it);
+//   * a finished ray is radiance[3r ..] = (0 + li) * 1.0 (rq_) or pixel slot r of a film (rf_, FilmArgs).
+// Why not the shared bodies: measured over them against the parent's library, three alternations in one session, one radiance row and two
+// sorted-order film rows were slower by 0.2-0.5 % with ranges that did not overlap (profiles/level0_shared_ab.jsonl), so by the rule set
+// for sharing this family keeps its text, and its kernels are the code they were (profiles/level0_shared_kernel_resources_diff.txt).
 #include "wflevel.h"
 #include "travform.h"
+#include "level0.h"
 
 namespace lg {
-
-template <bool PERM> __device__ __forceinline__ unsigned long long rq_ray_index(const RadianceArgs &Q, unsigned long long slot) {
-    return PERM ? (unsigned long long)Q.perm[slot] : slot;
-}
-__device__ __forceinline__ Ray rq_load_ray(const RadianceArgs &Q, unsigned long long r) {
-    const double2 *p = reinterpret_cast<const double2 *>(Q.rays + 6ull * r);
-    const double2 a = p[0], b = p[1], c = p[2];
-    return ray_new(V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}); // Ray3::new: the direction as given
-}
-// integrate() for a pixel whose one sample is this ray: Color::zero() + li, then * weight with weight = 1 / 1 (integrate.rs:16-20).
-// (The sum is what turns a -0.0 of li into the +0.0 a rendered pixel holds; the product by one is exact.)
-__device__ __forceinline__ void rq_finish(const RadianceArgs &Q, unsigned long long r, V3 value) {
-    const V3 color = (vzero() + value) * 1.0;
-    double *o = Q.radiance + 3ull * r;
-    o[0] = color.x; o[1] = color.y; o[2] = color.z;
-}
-// ... and into a film (FilmArgs): the ray is pixel slot r of one sample, the same value as one RGBA8 word (to_byte per channel, A = 255;
-// img.rs:46-67, as write_pixel) and / or three doubles at the slot's film offset.  A slot whose offset lies behind the film writes nothing.
-__device__ __forceinline__ void film_store(const FilmArgs &Q, unsigned long long off, V3 color) {
-    if (Q.rgba) Q.rgba[off] = to_byte(color.x) | (to_byte(color.y) << 8) | (to_byte(color.z) << 16) | (255u << 24);
-    if (Q.rgb) {
-        double *o = Q.rgb + 3ull * off;
-        o[0] = color.x; o[1] = color.y; o[2] = color.z;
-    }
-}
-__device__ __forceinline__ void rq_finish(const FilmArgs &Q, unsigned long long r, V3 value) {
-    const unsigned long long off = Q.offsets ? Q.offsets[r] : r;
-    if (off >= Q.npix) return;
-    film_store(Q, off, (vzero() + value) * 1.0);
-}
 
 // W1 of level 0 (wf_trace_kernel<FAST, false, LDSS, true, PRUNE>): rq_closest_body.h, into radiance[] (rq_) or into a film (rf_)
 template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
@@ -193,34 +162,20 @@ hipError_t launch_rf_closest(const DParams &P, const FilmArgs &Q, bool fast, uin
     return trav_launch<ClosestKernels>(P, fast, Q.perm ? 3 : 2, blocks, stack_depth, args, stream);
 }
 hipError_t launch_rq_shade(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
-    if (P.wf_levels == 1u) {
-        if (Q.perm) hipLaunchKernelGGL((rq_shade_kernel<0, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-        else hipLaunchKernelGGL((rq_shade_kernel<0, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    } else {
-        if (Q.perm) hipLaunchKernelGGL((rq_shade_kernel<1, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-        else hipLaunchKernelGGL((rq_shade_kernel<1, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    }
-    return hipGetLastError();
+    static const L0Kernel<RadianceArgs> k[2][2] = {{rq_shade_kernel<0, false>, rq_shade_kernel<0, true>}, {rq_shade_kernel<1, false>, rq_shade_kernel<1, true>}};
+    return l0_launch_shade(k, P, Q, Q.perm != nullptr, blocks, stream);
 }
 hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream) {
-    if (P.wf_levels == 1u) {
-        if (Q.perm) hipLaunchKernelGGL((rf_shade_kernel<0, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-        else hipLaunchKernelGGL((rf_shade_kernel<0, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    } else {
-        if (Q.perm) hipLaunchKernelGGL((rf_shade_kernel<1, true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-        else hipLaunchKernelGGL((rf_shade_kernel<1, false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    }
-    return hipGetLastError();
+    static const L0Kernel<FilmArgs> k[2][2] = {{rf_shade_kernel<0, false>, rf_shade_kernel<0, true>}, {rf_shade_kernel<1, false>, rf_shade_kernel<1, true>}};
+    return l0_launch_shade(k, P, Q, Q.perm != nullptr, blocks, stream);
 }
 hipError_t launch_rq_combine(const DParams &P, const RadianceArgs &Q, uint32_t blocks, hipStream_t stream) {
-    if (Q.perm) hipLaunchKernelGGL((rq_combine_kernel<true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    else hipLaunchKernelGGL((rq_combine_kernel<false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    return hipGetLastError();
+    static const L0Kernel<RadianceArgs> k[2] = {rq_combine_kernel<false>, rq_combine_kernel<true>};
+    return l0_launch_combine(k, P, Q, Q.perm != nullptr, blocks, stream);
 }
 hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream) {
-    if (Q.perm) hipLaunchKernelGGL((rf_combine_kernel<true>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    else hipLaunchKernelGGL((rf_combine_kernel<false>), dim3(blocks), dim3(LG_BLOCK), 0, stream, P, Q);
-    return hipGetLastError();
+    static const L0Kernel<FilmArgs> k[2] = {rf_combine_kernel<false>, rf_combine_kernel<true>};
+    return l0_launch_combine(k, P, Q, Q.perm != nullptr, blocks, stream);
 }
 hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream) {
     hipLaunchKernelGGL(rf_resolve_kernel, dim3(blocks), dim3(LG_BLOCK), 0, stream, Q, li, slots, samples);

@@ -170,7 +170,7 @@ struct ChunkPlan {
         }
         if (*budget == 0) *budget = budget_from_free_memory();
         chunk_tiles = *budget / (per_item * S * 64);
-        const unsigned long long cap_limit = ((queue ? 0xFFFFFF00ull : 0x7FFFFFF0ull) >> (levels - 1)) / (64ull * S); // ray indices are 32-bit (level by level, a render and a radiance query alike: 31, WF_SKIP sits above them -- rq_closest_body.h stores bare indices and relies on it)
+        const unsigned long long cap_limit = ((queue ? 0xFFFFFF00ull : 0x7FFFFFF0ull) >> (levels - 1)) / (64ull * S); // ray indices are 32-bit (level by level, a render and a radiance query alike: 31, WF_SKIP sits above them -- rq_closest_body.h and level0.h's closest body store bare indices and rely on it)
         if (chunk_tiles > cap_limit) chunk_tiles = cap_limit;
         if (chunk_tiles < 1) chunk_tiles = 1;
         if (chunk_tiles > P0.ntiles) chunk_tiles = P0.ntiles;
@@ -229,20 +229,22 @@ struct ChunkPlan {
     }
 };
 
-// Whose forms the passes of a chain of the level-by-level pipeline take.  At most one is set: `rq` a radiance query's rays
-// (k_radiance.hip), `rf` a ray film's (its film forms), `rg` a radiance gather's, made in the kernel from two tables (k_gather.hip), `rv` a view
-// batch's, made in the kernel from a table of cameras (k_views.hip): level 0's three passes, the levels below are the render's.  `lg` light
-// groups (k_light_groups.hip): level 0's three passes AND the shade and combine passes of every level below (every_level), which carry
-// lg->n_groups planes, with a spread pass at the deepest level; `xout` then holds each level's planes 1 .. G-1 (WfChunk::xout) and level()
-// tells lg which the next launches work on.  None: the scene's own camera (k_wavefront.hip) -- a render.
+// The passes of a chain of the level-by-level pipeline that are not the render's own, bound to the kernel arguments `q` of whoever makes level
+// 0's rays (level0.h's sources: a radiance query's or a ray film's rays, k_radiance.hip; a radiance gather's, k_gather.hip; a view batch's,
+// k_views.hip; light groups, k_light_groups.hip): level 0's three passes, the levels below are the render's.  `resolve`: what the source
+// enqueues behind a chunk's chain (a view batch of several samples a pixel; P.ntiles = the chunk's pixel tiles).  `lg`, light groups: the shade
+// and combine passes of every level below are the source's too (every_level), they carry lg->n_groups planes, with a spread pass at the
+// deepest level; `xout` then holds each level's planes 1 .. G-1 (WfChunk::xout) and level() tells lg which the next launches work on.
+// Nothing bound: the scene's own camera (k_wavefront.hip) -- a render.
 struct Level0 {
-    const RadianceArgs *rq = nullptr;
-    const FilmArgs *rf = nullptr;
-    const GatherArgs *rg = nullptr;
-    const ViewArgs *rv = nullptr;
+    typedef hipError_t (*Closest)(const DParams &, const void *, bool, uint32_t, uint32_t, hipStream_t);
+    typedef hipError_t (*Flat)(const DParams &, const void *, uint32_t, hipStream_t);
+    const void *q = nullptr;
+    Closest closest_ = nullptr;
+    Flat shade_ = nullptr, combine_ = nullptr, resolve_ = nullptr;
     GroupArgs *lg = nullptr;
     const std::vector<double *> *xout = nullptr;
-    bool own() const { return rq || rf || rg || rv || lg; }
+    bool own() const { return q != nullptr; }
     bool every_level() const { return lg != nullptr; }
     void level(uint32_t d) const {
         if (!lg) return;
@@ -250,17 +252,26 @@ struct Level0 {
         lg->xout_next = d + 1 < xout->size() ? (*xout)[d + 1] : nullptr;
     }
     hipError_t spread(const DParams &P, uint32_t blocks, hipStream_t s) const { return launch_lg_spread(P, *lg, blocks, s); }
-    hipError_t closest(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const {
-        return lg ? launch_lg_closest(P, *lg, fast, blocks, depth, s) : rv ? launch_view_closest(P, *rv, fast, blocks, depth, s) : rg ? launch_gather_closest(P, *rg, fast, blocks, depth, s) : rf ? launch_rf_closest(P, *rf, fast, blocks, depth, s)
-                                                                                                                                : launch_rq_closest(P, *rq, fast, blocks, depth, s);
-    }
-    hipError_t shade(const DParams &P, uint32_t blocks, hipStream_t s) const {
-        return lg ? launch_lg_shade(P, *lg, blocks, s) : rv ? launch_view_shade(P, *rv, blocks, s) : rg ? launch_gather_shade(P, *rg, blocks, s) : rf ? launch_rf_shade(P, *rf, blocks, s) : launch_rq_shade(P, *rq, blocks, s);
-    }
-    hipError_t combine(const DParams &P, uint32_t blocks, hipStream_t s) const {
-        return lg ? launch_lg_combine(P, *lg, blocks, s) : rv ? launch_view_combine(P, *rv, blocks, s) : rg ? launch_gather_combine(P, *rg, blocks, s) : rf ? launch_rf_combine(P, *rf, blocks, s) : launch_rq_combine(P, *rq, blocks, s);
-    }
+    hipError_t closest(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const { return closest_(P, q, fast, blocks, depth, s); }
+    hipError_t shade(const DParams &P, uint32_t blocks, hipStream_t s) const { return shade_(P, q, blocks, s); }
+    hipError_t combine(const DParams &P, uint32_t blocks, hipStream_t s) const { return combine_(P, q, blocks, s); }
+    hipError_t resolve(const DParams &P, uint32_t blocks, hipStream_t s) const { return resolve_(P, q, blocks, s); }
 };
+// ... bound to a family's launchers (internal.h) and to its arguments, which live until the chunk's chain is enqueued
+template <class ARGS> using L0Closest = hipError_t (*)(const DParams &, const ARGS &, bool, uint32_t, uint32_t, hipStream_t);
+template <class ARGS> using L0Flat = hipError_t (*)(const DParams &, const ARGS &, uint32_t, hipStream_t);
+template <class ARGS, L0Closest<ARGS> F> static hipError_t l0_closest(const DParams &P, const void *q, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) {
+    return F(P, *static_cast<const ARGS *>(q), fast, blocks, depth, s);
+}
+template <class ARGS, L0Flat<ARGS> F> static hipError_t l0_flat(const DParams &P, const void *q, uint32_t blocks, hipStream_t s) { return F(P, *static_cast<const ARGS *>(q), blocks, s); }
+template <class ARGS, L0Closest<ARGS> CLOSEST, L0Flat<ARGS> SHADE, L0Flat<ARGS> COMBINE> static Level0 bind_level0(const ARGS &Q) {
+    Level0 l0;
+    l0.q = &Q;
+    l0.closest_ = l0_closest<ARGS, CLOSEST>;
+    l0.shade_ = l0_flat<ARGS, SHADE>;
+    l0.combine_ = l0_flat<ARGS, COMBINE>;
+    return l0;
+}
 // Bottom-up after a sample's levels: li of level d's rays from their children's (integrate.rs:79, 103, 129), shared by both organisations
 static void combine_levels(const lg_accel &a, DParams &P, const LevelArrays &K, const ChunkPlan &plan, hipStream_t s, const Level0 &l0 = Level0()) {
     const unsigned long long n0 = plan.n0();
@@ -482,46 +493,40 @@ static void enqueue_wavefront(const lg_accel &a, DParams &P0, lg_accel::LaunchCt
 // whatever the scene's camera supersamples; always this organisation, whatever lg_accel_set_streaming says: nothing is measured or
 // remembered for it.  Caller holds a.mtx, has made the accel's device current and has checked the buffers and that the scene can go
 // level by level (radiance_possible).
-// `film` (lg_capture_rays* of one sample per pixel slot): ray r is pixel slot r and level 0 finishes it into the film (FilmArgs) instead of
-// radiance[] -- the same chunks, the same launches with the film forms of the three level-0 kernels in place of the radiance forms.
-// `gather` (lg_radiance_gather*): there is no ray array -- level 0's work items are the gather's `gather_tiles` tiles, whose rays its own
-// forms of the three kernels make from two tables (k_gather.hip) and finish into gather->li; a chunk is told its first tile.
-// `views` (lg_capture_views*): there is no ray array either -- level 0's work items are the batch's `view_tiles` global pixel tiles x S samples
-// side by side, as a render's (enqueue_wavefront): the film size and samples_root go into the chunk's DParams, a chunk holds whole pixel tiles
-// x S and is told its first pixel tile, and with S > 1 each chunk's parked samples are resolved behind its chain (k_views.hip,
-// view_resolve_kernel; a combine pass, kind 1, as the render's resolve is).
-// `label` / `note`: what LASGUN_DEBUG calls the query and how it ends its line (a query's rays: the order they are walked in); `tail`: what
-// is enqueued behind the chunks inside the profiled span (a film's or a gather's resolve pass).
-struct Level0Source {
-    const double *rays = nullptr;       // a radiance query or a ray film: n rays ...
-    size_t n = 0;
-    double *radiance = nullptr;         // ... into radiance[] ...
-    const FilmArgs *film = nullptr;     // ... or into a film
-    const uint32_t *perm = nullptr;
-    const DLightGroup *groups = nullptr; // ... or, split by light groups, into the n_groups planes of radiance[] (host table)
-    uint32_t n_groups = 0;
-    const GatherArgs *gather = nullptr; // a radiance gather (base_tile is the chunk's to set)
-    uint32_t gather_tiles = 0;
-    const ViewArgs *views = nullptr;    // a view batch (base_tile is the chunk's to set)
-    uint32_t view_tiles = 0, samples_root = 1;
-    const char *label = "";
-    std::string note;
+// A call is its SHAPE (Level0Call) and a per-chunk callback `bind(t0)`: told the chunk's first tile, it sets where the chunk starts in its
+// kernel arguments (base / base_tile) and returns the passes bound to them (Level0).  The sources:
+// rays (lg_radiance*, and with `film` lg_capture_rays* of one sample per pixel slot: ray r is pixel slot r and level 0 finishes it into the film
+// (FilmArgs) instead of radiance[] -- the same chunks, the same launches with the film forms of the three level-0 kernels);
+// a gather (lg_radiance_gather*): there is no ray array -- level 0's work items are the gather's tiles, whose rays its own forms of the three
+// kernels make from two tables (k_gather.hip) and finish into its li;
+// views (lg_capture_views*): there is no ray array either -- level 0's work items are the batch's global pixel tiles x S samples side by side,
+// as a render's (enqueue_wavefront): the film size and samples_root go into the chunk's DParams, a chunk holds whole pixel tiles x S, and with
+// S > 1 each chunk's parked samples are resolved behind its chain (Level0::resolve: k_views.hip, view_resolve_kernel; a combine pass, kind 1, as
+// the render's resolve is).
+// `tail`: what is enqueued behind the chunks inside the profiled span (a film's or a gather's resolve pass).
+struct Level0Call {
+    uint32_t tiles = 0;                // level 0's tiles of 64 work items (views: pixel tiles, x samples_root^2 work tiles each)
+    uint32_t w = 1, h = 1;             // the film size the chunks' DParams are made for (views alone)
+    uint32_t samples_root = 1;         // (the scene's camera may be supersampled; a query is not, and a view batch has its own samples_root)
+    uint32_t planes = 1;               // planes of li per ray of every level (light groups alone: > 1)
+    const char *label = "";            // what LASGUN_DEBUG calls the query ...
+    std::string note;                  // ... and how it ends its line (a query's rays: the order they are walked in)
 };
-static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_accel::LaunchCtx &c, hipStream_t stream, const std::function<void()> &tail = nullptr) {
-    DParams P0 = src.views ? base_params(a, src.views->w, src.views->h) : base_params(a, 1, 1);
-    P0.ss_root = src.samples_root; // (the scene's camera may be supersampled; a query is not, and a view batch has its own samples_root)
-    const uint32_t S = P0.ss_root * P0.ss_root; // level-0 work items per pixel (views alone: > 1)
-    P0.ntiles = src.views ? src.view_tiles : src.gather ? src.gather_tiles : (uint32_t)((src.n + 63) / 64);
+template <class BIND>
+static void enqueue_level0_query(const lg_accel &a, const Level0Call &call, BIND &&bind, lg_accel::LaunchCtx &c, hipStream_t stream, const std::function<void()> &tail = nullptr) {
+    DParams P0 = base_params(a, call.w, call.h);
+    P0.ss_root = call.samples_root;
+    const uint32_t S = P0.ss_root * P0.ss_root; // level-0 work items per pixel
+    P0.ntiles = call.tiles;
     const uint32_t levels = levels_of(a, P0);
-    const uint32_t G = src.groups ? src.n_groups : 1u; // planes of li per ray of every level
-    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, G));
-    WfChunk K(plan, G);
+    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, call.planes));
+    WfChunk K(plan, call.planes);
     plan.fit([&] { K.carve(c); });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
     Span span(a, stream);
     if (std::getenv("LASGUN_DEBUG"))
-        std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", src.label, levels, (unsigned long long)P0.ntiles,
-                     chunk_tiles, plan.need() / 1048576.0, src.note.c_str());
+        std::fprintf(stderr, "[lasgun] %s: levels %u, %llu tiles in chunks of %llu (%.1f MiB), %s\n", call.label, levels, (unsigned long long)P0.ntiles,
+                     chunk_tiles, plan.need() / 1048576.0, call.note.c_str());
     for (unsigned long long t0 = 0; t0 < P0.ntiles; t0 += chunk_tiles) {
         DParams P = P0;
         P.tile0 = (uint32_t)t0;
@@ -529,67 +534,65 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Source &src, lg_
         P.ntiles = chunk * S; // level 0's work tiles (at most the call's: 32 bits, views_host.h)
         P.ss_par = S;
         K.params(a, P);
-        if (src.views) {
-            ViewArgs V = *src.views;
-            V.base_tile = t0;
-            Level0 l0;
-            l0.rv = &V;
-            K.run(a, P, stream, l0);
-            if (S > 1) {
-                DParams R = P;
-                R.ntiles = chunk;
-                timed(a, 1, stream, [&] { return launch_view_resolve(R, V, (uint32_t)(((unsigned long long)chunk * 64ull + 255ull) / 256ull), stream); });
-            }
-            continue;
-        }
-        if (src.gather) {
-            GatherArgs G = *src.gather;
-            G.base_tile = t0;
-            Level0 l0;
-            l0.rg = &G;
-            K.run(a, P, stream, l0);
-            continue;
-        }
-        const RadianceArgs Q{src.rays, src.radiance, src.perm, (unsigned long long)src.n, t0 * 64ull};
-        Level0 l0;
-        FilmArgs F;
-        GroupArgs GA;
-        if (src.groups) {
-            std::memset(&GA, 0, sizeof GA);
-            static_cast<RadianceArgs &>(GA) = Q;
-            GA.n_groups = G;
-            std::memcpy(GA.groups, src.groups, G * sizeof(DLightGroup));
-            l0.lg = &GA;
-            l0.xout = &K.xout;
-        } else if (src.film) {
-            F = *src.film;
-            static_cast<RadianceArgs &>(F) = Q;
-            l0.rf = &F;
-        } else l0.rq = &Q;
+        Level0 l0 = bind(t0);
+        l0.xout = &K.xout; // (light groups: where the chunk carved planes 1 .. G-1 of each level)
         K.run(a, P, stream, l0);
+        if (l0.resolve_) {
+            DParams R = P;
+            R.ntiles = chunk;
+            timed(a, 1, stream, [&] { return l0.resolve(R, (uint32_t)(((unsigned long long)chunk * 64ull + 255ull) / 256ull), stream); });
+        }
     }
     if (tail) tail();
     span.end(a.events);
 }
-// the rays of a radiance query or a ray film as level 0's source
-static Level0Source ray_source(const double *rays, size_t n, double *radiance, const FilmArgs *film, const uint32_t *perm, const char *label) {
-    Level0Source src;
-    src.rays = rays; src.n = n; src.radiance = radiance; src.film = film; src.perm = perm; src.label = label;
-    src.note = perm ? "sorted order" : "as given";
-    return src;
+// The rays of a radiance query, a ray film (`film`) or light groups (`groups`) as level 0's source: work item i of the chunk at tile t0 is
+// slot 64 t0 + i of the query
+static void enqueue_ray_query(const lg_accel &a, const double *rays, size_t n, double *radiance, const FilmArgs *film, const DLightGroup *groups, uint32_t n_groups,
+                              const uint32_t *perm, const char *label, lg_accel::LaunchCtx &c, hipStream_t stream, const std::function<void()> &tail = nullptr) {
+    Level0Call call;
+    call.tiles = (uint32_t)((n + 63) / 64);
+    call.label = label;
+    call.note = perm ? "sorted order" : "as given";
+    const RadianceArgs Q{rays, radiance, perm, (unsigned long long)n, 0ull};
+    if (groups) {
+        call.planes = n_groups;
+        call.note += ", " + std::to_string(n_groups) + " groups";
+        GroupArgs GA;
+        std::memset(&GA, 0, sizeof GA);
+        static_cast<RadianceArgs &>(GA) = Q;
+        GA.n_groups = n_groups;
+        std::memcpy(GA.groups, groups, n_groups * sizeof(DLightGroup));
+        enqueue_level0_query(a, call, [&](unsigned long long t0) {
+            GA.base = t0 * 64ull;
+            Level0 l0 = bind_level0<GroupArgs, launch_lg_closest, launch_lg_shade, launch_lg_combine>(GA);
+            l0.lg = &GA;
+            return l0;
+        }, c, stream, tail);
+    } else if (film) {
+        FilmArgs F = *film;
+        static_cast<RadianceArgs &>(F) = Q;
+        enqueue_level0_query(a, call, [&](unsigned long long t0) {
+            F.base = t0 * 64ull;
+            return bind_level0<FilmArgs, launch_rf_closest, launch_rf_shade, launch_rf_combine>(F);
+        }, c, stream, tail);
+    } else {
+        RadianceArgs R = Q;
+        enqueue_level0_query(a, call, [&](unsigned long long t0) {
+            R.base = t0 * 64ull;
+            return bind_level0<RadianceArgs, launch_rq_closest, launch_rq_shade, launch_rq_combine>(R);
+        }, c, stream, tail);
+    }
 }
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
-    enqueue_level0_query(a, ray_source(rays, n, radiance, nullptr, perm, "radiance query"), c, stream);
+    enqueue_ray_query(a, rays, n, radiance, nullptr, nullptr, 0, perm, "radiance query", c, stream);
 }
 // Light groups (query.cpp, lg_radiance_groups*; the call checked there and in light_groups_host.h): the same query with n_groups planes of li
 // per ray at every level -- the chunk carries planes 1 .. G-1 beside the level arrays, and the chain takes the shade and combine passes of
 // every level, and a spread pass at the deepest, from k_light_groups.hip (Level0::lg).  The walks are the radiance query's.
 void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, const DLightGroup *groups, uint32_t n_groups, double *radiance, const uint32_t *perm,
                              lg_accel::LaunchCtx &c, hipStream_t stream) {
-    Level0Source src = ray_source(rays, n, radiance, nullptr, perm, "radiance groups");
-    src.groups = groups; src.n_groups = n_groups;
-    src.note += ", " + std::to_string(n_groups) + " groups";
-    enqueue_level0_query(a, src, c, stream);
+    enqueue_ray_query(a, rays, n, radiance, nullptr, groups, n_groups, perm, "radiance groups", c, stream);
 }
 // A radiance gather (query.cpp, lg_radiance_gather*; the call checked there and in gather_host.h): batch after batch of g.batch_poses whole
 // consecutive poses, each a level-0 query of its own over the batch's tiles -- its poses' rows of the tables, its own li -- with the
@@ -606,14 +609,17 @@ void enqueue_radiance_gather(const lg_accel &a, const GatherCall &g, lg_accel::L
         const size_t np = std::min(batch_poses, g.n_poses - p0);
         double *li = g.radiance ? g.radiance + 3 * (p0 * g.n_dirs) : c.gather_li.p;
         const uint32_t tiles_per = g.pose_lanes ? (uint32_t)g.n_dirs : (uint32_t)((g.n_dirs + 63) / 64);
-        const GatherArgs G{g.origins + 3 * p0, g.frames ? g.frames + 9 * p0 : nullptr, g.dirs, li, np, g.n_dirs, 0ull, tiles_per, g.pose_lanes ? 1u : 0u};
-        Level0Source src;
-        src.gather = &G;
-        src.gather_tiles = (uint32_t)((g.pose_lanes ? (np + 63) / 64 : np) * tiles_per); // (at most the call's tiles: 32 bits)
-        src.label = "radiance gather";
-        src.note = "batch " + std::to_string(batch + 1) + " of " + std::to_string(nbatches) + ", " + (g.pose_lanes ? "pose lanes" : "direction lanes");
+        GatherArgs G{g.origins + 3 * p0, g.frames ? g.frames + 9 * p0 : nullptr, g.dirs, li, np, g.n_dirs, 0ull, tiles_per, g.pose_lanes ? 1u : 0u};
+        Level0Call call;
+        call.tiles = (uint32_t)((g.pose_lanes ? (np + 63) / 64 : np) * tiles_per); // (at most the call's tiles: 32 bits)
+        call.label = "radiance gather";
+        call.note = "batch " + std::to_string(batch + 1) + " of " + std::to_string(nbatches) + ", " + (g.pose_lanes ? "pose lanes" : "direction lanes");
         double *sums = g.sums ? g.sums + 3 * (p0 * g.n_weights) : nullptr;
-        enqueue_level0_query(a, src, c, stream, [&] {
+        auto bind = [&](unsigned long long t0) {
+            G.base_tile = t0;
+            return bind_level0<GatherArgs, launch_gather_closest, launch_gather_shade, launch_gather_combine>(G);
+        };
+        enqueue_level0_query(a, call, bind, c, stream, [&] {
             if (!sums) return;
             const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)np * g.n_weights + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
             timed(a, 1, stream, [&] { return launch_gather_resolve(li, g.weights, sums, np, g.n_dirs, g.n_weights, blocks, stream); });
@@ -653,13 +659,18 @@ void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint3
     try {
         V.views = stage_view_table(views, (size_t)V.n_views, c, stream);
         V.base_tile = 0;
-        Level0Source src;
-        src.views = &V;
-        src.view_tiles = (uint32_t)V.n_views * V.tiles_per_view; // (at most the call's work tiles: 32 bits)
-        src.samples_root = samples_root;
-        src.label = "view batch";
-        src.note = std::to_string(V.n_views) + " views of " + std::to_string(V.tiles_per_view) + " tiles x " + std::to_string(samples_root * samples_root) + " samples";
-        enqueue_level0_query(a, src, c, stream);
+        Level0Call call;
+        call.tiles = (uint32_t)V.n_views * V.tiles_per_view; // (at most the call's work tiles: 32 bits)
+        call.w = V.w; call.h = V.h;
+        call.samples_root = samples_root;
+        call.label = "view batch";
+        call.note = std::to_string(V.n_views) + " views of " + std::to_string(V.tiles_per_view) + " tiles x " + std::to_string(samples_root * samples_root) + " samples";
+        enqueue_level0_query(a, call, [&](unsigned long long t0) {
+            V.base_tile = t0;
+            Level0 l0 = bind_level0<ViewArgs, launch_view_closest, launch_view_shade, launch_view_combine>(V);
+            if (samples_root > 1) l0.resolve_ = l0_flat<ViewArgs, launch_view_resolve>;
+            return l0;
+        }, c, stream);
         subsets_enqueued(a, stream);
     } catch (...) { subsets_abandoned(a, stream); throw; }
 }
@@ -673,10 +684,10 @@ void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint3
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream) {
     const size_t n = slots * samples;
-    if (samples == 1) { enqueue_level0_query(a, ray_source(rays, n, nullptr, &film, perm, "ray film"), c, stream); return; }
+    if (samples == 1) { enqueue_ray_query(a, rays, n, nullptr, &film, nullptr, 0, perm, "ray film", c, stream); return; }
     grow(c.film_li, n * 3);
     const double *li = c.film_li.p;
-    enqueue_level0_query(a, ray_source(rays, n, c.film_li.p, nullptr, perm, "ray film"), c, stream, [&] {
+    enqueue_ray_query(a, rays, n, c.film_li.p, nullptr, nullptr, 0, perm, "ray film", c, stream, [&] {
         const uint32_t blocks = (uint32_t)std::min<unsigned long long>(((unsigned long long)slots + 255ull) / 256ull, (unsigned long long)a.cus * 64ull);
         timed(a, 1, stream, [&] { return launch_rf_resolve(film, li, slots, samples, blocks, stream); });
     });

@@ -1,7 +1,6 @@
 // lasgun_amd/csrc/rq_closest_body.h -- the body of W1 of level 0 of a radiance query (k_radiance.hip), included once into each of its two
 // kernels: rq_closest_kernel (Q: RadianceArgs, a finished ray goes to radiance[]) and rf_closest_kernel (Q: FilmArgs, it goes to a film);
-// rq_finish is overloaded on Q.  Text included twice, not a shared function template: these kernels sit at their register budget, and
-// this way the radiance forms compile to exactly what they were before the film forms existed (profiles/r10_kernel_resources_diff.txt).
+// rq_finish is overloaded on Q.  The text level0.h's l0_closest_body was made from; this family keeps it (k_radiance.hip says why).
 // In scope: template parameters FAST, LDSS, PRUNE, PERM; kernel parameters P (DParams) and Q.
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");

@@ -136,27 +136,29 @@ def test_the_rust_crates_carry_them():
 def test_the_kernels_are_device_kernels_of_their_own():
     """The rays are made, walked and shaded in HIP kernels the library launches -- level 0's three passes in gather forms over the render's
     unchanged walk, and one reduction --; nothing expands the pairs into rays on the host, and no existing kernel file is touched for it."""
+    from level0_text import calls_the_bodies, level0_bodies
     src = read("lasgun_amd", "csrc", "k_gather.hip")
     for kernel in ("gather_closest_kernel", "gather_shade_kernel", "gather_combine_kernel", "gather_resolve_kernel"):
         assert re.search(r"__global__ void [^\n]*\b%s\(" % kernel, src), kernel
-    assert len(re.findall(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", src)) == 1, "one walk, closest hit; the lane form is a template bool"
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "wave_append(" in src and "shade_frame(" in src and "trav_launch<GatherKernels>" in src
+    level0_bodies()  # one walk, closest hit, a finished ray is (0 + li) * 1.0 ...
+    calls_the_bodies(src, 1, 1, 1)  # ... and the lane form is a template bool of the source
+    assert "wave_append(" not in src and "trav_launch<GatherKernels>" in src and "trav_set_lds_limit<GatherKernels>" in src
     assert "(M[0] * b.x + M[1] * b.y) + M[2] * b.z" in src and "(M[6] * b.x + M[7] * b.y) + M[8] * b.z" in src
-    assert "(vzero() + value) * 1.0" in src, "a finished ray is (0 + li) * 1.0"
+    assert "l0_finish_at(Q.li + 3ull * (it.pose * Q.n_dirs + it.k), value)" in src and "GatherSource<POSE>{Q}" in src, "a finished ray goes to its index of li"
     resolve = src[src.index("void __launch_bounds__(LG_BLOCK) gather_resolve_kernel("):src.index("// ---- host-callable launchers")]
     assert "atomic" not in resolve and "acc = acc + V3{l[0], l[1], l[2]} * w[0]" in resolve and "k < n_dirs; ++k" in resolve, "the sequential loop, one lane per (pose, c)"
     make = read("lasgun_amd", "csrc", "Makefile")
     assert "k_gather.o" in make and "-ffp-contract=off" in make and "gather_host.h" in make
     assert "gather_set_lds_limit" in read("lasgun_amd", "csrc", "accel.cpp")
     launch = read("lasgun_amd", "csrc", "launch.cpp")
-    assert "launch_gather_closest(" in launch and "launch_gather_shade(" in launch and "launch_gather_combine(" in launch
+    assert "bind_level0<GatherArgs, launch_gather_closest, launch_gather_shade, launch_gather_combine>(G)" in launch
     assert re.search(r"timed\(a, 1, stream, \[&\] \{ return launch_gather_resolve\(", launch), "the reduction is credited to kind 1"
     assert launch.count("static void enqueue_level0_query(") == 1, "one level-0 query over the ray source, not a copy"
     host = read("lasgun_amd", "csrc", "query.cpp")
     whole = host[host.index("// ---- radiance gathers"):host.index("// ---- ray films")]
     assert "radiance_possible(*a)" in whole and "enqueue_radiance_gather(" in whole
     assert "lg_radiance(" not in whole and "enqueue_radiance_query(" not in whole and "pairs * 6" not in whole, "no rays are built on the host"
-    assert "rq_closest_body.h" in read("profiles", "r16_kernel_resources_diff.txt")
+    assert "rq_closest_body.h" in read("profiles", "r16_kernel_resources_diff.txt") and "gather_closest_kernel" in read("profiles", "level0_shared_kernel_resources_diff.txt")
 
 
 def test_the_lane_rule_over_a_table_of_shapes():

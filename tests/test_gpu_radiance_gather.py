@@ -33,7 +33,7 @@ import pytest
 import lasgun_amd as la
 from lasgun_amd import _capi
 from lasgun_amd import scenes as S
-from test_gpu_radiance_query import bits, oracle_radiance, with_camera, many_lights_scene
+from test_gpu_radiance_query import L0_CASES, L0_FORMS, L0_IDS, bits, each_form, l0_scene, mixed_rays, oracle_radiance, with_camera, many_lights_scene
 from test_gpu_range_scan import NP, NB, explicit_rays, fib, rotations, setup as scan_setup
 from test_gpu_visibility import SCENES, FORMS, set_form, reset, spread
 
@@ -464,3 +464,23 @@ def test_errors_are_refused_before_any_launch_and_empty_sets_are_a_no_op():
     want = G.radiance_gather(accel, o[:n], b[:m], fr[:n], W[:m], ("radiance", "sums"))
     for p in dev:
         assert dev[p].cpu().numpy().view(np.uint64).tobytes() == want[p].tobytes(), p
+
+
+# ---- level 0's shared bodies: two tiles, the last one partial, in every form, KIND and lane form (test_gpu_radiance_query.py, section 6) --
+@pytest.mark.parametrize("name,builder,kind", L0_CASES, ids=L0_IDS)
+def test_two_tiles_in_every_form_and_lane_form_equal_the_restatement(name, builder, kind):
+    """2 poses x 65 directions and 65 poses x 2 directions: in direction lanes 2 x 2 tiles and 65 tiles of two rays, in pose lanes 65 tiles of
+    two rays and 2 x 2 tiles -- against lg_radiance on the explicit rays (which section 6 there holds to the oracle) and the sequential sums."""
+    accel = G.Accel.from_scene(l0_scene(builder, kind)(G))
+    _, poses, dirs = scan_setup(name)
+    checked = set()
+    for n, m in ((2, 65), (65, 2)):
+        o, b = np.ascontiguousarray(poses[spread(NP, n)]), np.ascontiguousarray(dirs[spread(NB, m)])
+        rays = explicit_rays(o, None, b)
+        mixed_rays(accel, rays, (name, kind, n, m))
+        W = np.ascontiguousarray(WEIGHTS[spread(NB, m)])
+        for form in each_form(accel):
+            L = G.radiance(accel, rays).reshape(n, m, 3)
+            check_gather((name, kind, form, n, m), accel, o, b, None, W, L, lanes_set=(DIR, POSE))
+            checked.add(form)
+    assert L0_FORMS[name] <= checked, (name, checked)

@@ -26,7 +26,7 @@ import pytest
 import lasgun_amd as la
 from lasgun_amd import scenes as S
 from light_subsets import light_count, subset_scene, group_pairs
-from test_gpu_radiance_query import bits, many_lights_scene, oracle_radiance
+from test_gpu_radiance_query import L0_CASES, L0_FORMS, L0_IDS, TWO_TILES, bits, each_form, l0_scene, many_lights_scene, mixed_rays, oracle_radiance
 
 pytestmark = pytest.mark.gpu
 
@@ -338,3 +338,25 @@ def test_errors_are_reported_and_nothing_is_launched():
     dev(dr.data_ptr(), two, do.data_ptr())
     torch.cuda.synchronize()
     assert do.cpu().numpy()[: 2 * n * 3].tobytes() == G.radiance_groups(accel, rays[:n], two).tobytes()
+
+
+# ---- level 0's shared bodies: two tiles, the last one partial, in every form, KIND and order (test_gpu_radiance_query.py, section 6) -----
+@pytest.mark.parametrize("name,builder,kind", L0_CASES, ids=L0_IDS)
+def test_two_tiles_in_every_form_and_order_give_the_oracles_planes(name, builder, kind):
+    scene_of = l0_scene(builder, kind)
+    accel = G.Accel.from_scene(scene_of(G))
+    pairs = group_pairs(G.light_count(accel))
+    checked = set()
+    for w, h in TWO_TILES:
+        rays = G.camera_rays(accel, w, h)
+        mixed_rays(accel, rays, (name, kind, w, h))
+        want = [bits(oracle_radiance(lambda api: subset_scene(api, scene_of, m, a), w, h).reshape(-1, 3)) for m, a in pairs]
+        for form in each_form(accel):
+            for order in (0, 1):
+                G.set_query_order(accel, order)
+                planes = G.radiance_groups(accel, rays, lg(pairs))
+                for g in range(len(pairs)):
+                    assert np.array_equal(bits(planes[g]), want[g]), (name, kind, form, order, w * h, g, pairs[g])
+            G.set_query_order(accel, 0)
+            checked.add(form)
+    assert L0_FORMS[name] <= checked, (name, checked)

@@ -20,7 +20,7 @@ import pytest
 import lasgun_amd as la
 from lasgun_amd import scenes as S
 from oracle_lib import oracle
-from test_gpu_radiance_query import FORM_SCENES, SECOND, bits, many_lights_scene, oracle_radiance, resolve, with_camera
+from test_gpu_radiance_query import FORM_SCENES, L0_CASES, L0_FORMS, L0_IDS, SECOND, TWO_TILES, bits, each_form, l0_scene, many_lights_scene, mixed_rays, oracle_radiance, resolve, with_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -494,3 +494,24 @@ def test_a_lens_film_end_to_end():
     fish = la.Lens(la.LENS_FISHEYE, (0.9, -0.2, 0.9), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, -1.0), 160.0)
     frays = G.lens_rays(fish, w, h, 1)
     assert np.array_equal(G.capture_lens(accel, fish, w, h), G.capture_rays(accel, frays, w, h))
+
+
+# ---- level 0's shared bodies: two tiles, the last one partial, in every form, KIND and order (test_gpu_radiance_query.py, section 6) -----
+@pytest.mark.parametrize("name,builder,kind", L0_CASES, ids=L0_IDS)
+def test_two_tiles_in_every_form_and_order_give_the_oracles_film(name, builder, kind):
+    scene_of = l0_scene(builder, kind)
+    accel = G.Accel.from_scene(scene_of(G))
+    assert G.camera_samples(accel) == 1
+    checked = set()
+    for w, h in TWO_TILES:
+        rays = G.camera_rays(accel, w, h)
+        mixed_rays(accel, rays, (name, kind, w, h))
+        want_a, want_d = oracle_film(scene_of, w, h), bits(oracle_radiance(scene_of, w, h))
+        for form in each_form(accel):
+            for order in (0, 1):
+                G.set_query_order(accel, order)
+                rgba, rgb = G.capture_rays(accel, rays, w, h, samples=1, rgb=True)  # (one sample a slot: the film forms of the three kernels)
+                assert np.array_equal(rgba, want_a) and np.array_equal(bits(rgb), want_d), (name, kind, form, order, w * h)
+            G.set_query_order(accel, 0)
+            checked.add(form)
+    assert L0_FORMS[name] <= checked, (name, checked)

@@ -14,7 +14,7 @@ import pytest
 
 import lasgun_amd as la
 from lasgun_amd import scenes as S
-from test_gpu_radiance_query import FORM_SCENES, SECOND, bits, many_lights_scene, oracle_radiance, with_camera
+from test_gpu_radiance_query import FORM_SCENES, L0_CASES, L0_FORMS, L0_IDS, SECOND, bits, each_form, l0_scene, many_lights_scene, mixed_rays, oracle_radiance, with_camera
 from test_gpu_ray_film import oracle_film
 from test_gpu_visibility import reset, set_form
 
@@ -322,3 +322,33 @@ def test_errors_are_reported_and_nothing_is_launched():
     torch.cuda.synchronize()
     assert da.cpu().numpy()[:2 * w * h * 4].tobytes() == a.tobytes() and (da.cpu().numpy()[2 * w * h * 4:] == 0xA5).all()
     assert dd.cpu().numpy()[:2 * w * h * 3].tobytes() == d.tobytes() and dd.cpu().numpy()[-1] == -7.0
+
+
+# ---- level 0's shared bodies: two tiles, the last one partial, in every form and KIND, one sample and four (test_gpu_radiance_query.py, section 6)
+@pytest.mark.parametrize("name,builder,kind", L0_CASES, ids=L0_IDS)
+def test_two_views_of_two_tiles_in_every_form_are_the_films_of_their_rays(name, builder, kind):
+    """2 views of 9 x 9 pixels: four tiles a view, three of them partial, at samples_root 1 and 2 -- against lg_capture_rays on the views' rays
+    written out (which test_gpu_ray_film.py holds to the oracle) and against the oracle's own renders of the scene rebuilt with each camera."""
+    scene_of = l0_scene(builder, kind)
+    accel = G.Accel.from_scene(scene_of(G))
+    w = h = 9
+    cameras = [s[3] for s in SECOND if s[0] == "cornell_glass"][0][:2]  # (both scenes stand in the same shell: a perspective and an orthographic view of it)
+    checked = set()
+    for ss in (0, 1):
+        views = [view_of(cam, supersampling=ss) for cam in cameras]
+        mixed_rays(accel, np.concatenate([G.view_rays(accel, v, w, h) for v in views]), (name, kind, ss))
+        def rebuilt(cam):
+            def scene_b(api):
+                scene = with_camera(scene_of(api), cam)
+                scene.camera.set_supersampling(ss)
+                return scene
+            return scene_b
+        films = [oracle_film(rebuilt(cam), w, h) for cam in cameras]
+        for form in each_form(accel):
+            want_a, want_d = by_rays(accel, views, w, h)
+            a, d = G.capture_views(accel, views, w, h, rgb=True)
+            assert a.tobytes() == want_a.tobytes() and d.tobytes() == want_d.tobytes(), (name, kind, form, ss)
+            for k in range(len(cameras)):
+                assert np.array_equal(a[k], films[k]), (name, kind, form, ss, k, "oracle")
+            checked.add(form)
+    assert L0_FORMS[name] <= checked, (name, checked)

@@ -129,12 +129,18 @@ def test_the_rust_crates_carry_them():
 
 
 def test_the_kernels_are_device_kernels_of_their_own_beside_the_unchanged_walk():
-    """G planes come from HIP kernels the library launches in one chain: the closest body a third time, a shade and a combine kernel with the
+    """G planes come from HIP kernels the library launches in one chain: the shared closest body, a shade and a combine kernel with the
     group loop, the spread pass; the table travels by value and DParams has no field for it; nothing loops over lg_radiance on the host."""
     src = read("lasgun_amd", "csrc", "k_light_groups.hip")
     for kernel in ("lg_closest_kernel", "lg_shade_kernel", "lg_combine_kernel", "lg_spread_kernel"):
         assert re.search(r"__global__ void [^\n]*\b%s\(const DParams P, const GroupArgs Q\)" % kernel, src), kernel
-    assert src.count('#include "rq_closest_body.h"') == 1 and "__launch_bounds__(LG_BLOCK, 3) lg_shade_kernel" in src
+    assert src.count("l0_closest_body<FAST, LDSS, PRUNE>(P, GroupRaySource<PERM>{Q})") == 1 and "__launch_bounds__(LG_BLOCK, 3) lg_shade_kernel" in src
+    shared = read("lasgun_amd", "csrc", "level0.h")
+    assert len(re.findall(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", shared)) == 1 and "walk<" not in src and "claim_tile" not in src
+    for fn in ("unsigned long long rq_ray_index(", "Ray rq_load_ray("):
+        assert shared.count(fn) == 1 and fn not in src, fn
+    finish = src[src.index("template <bool PERM> struct GroupRaySource {"):src.index("// plane g of a level's li")]
+    assert "for (uint32_t g = 0; g < Q.n_groups; ++g) lg_finish(Q, r, g, value);" in finish, "a finished miss goes to all G planes, in the source's own finish"
     code = "\n".join(line.split("//")[0] for line in src.split("#include", 1)[1].splitlines())
     assert "atomic" not in code.replace("wave_append", ""), "no atomics of its own: every element is written by exactly one lane"
     assert "trav_launch<GroupClosestKernels>" in src and "trav_set_lds_limit<GroupClosestKernels>" in src

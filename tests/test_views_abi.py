@@ -132,19 +132,23 @@ def test_capi_and_the_wrappers_mirror_them():
 
 
 def test_the_kernels_are_device_kernels_of_their_own():
+    from level0_text import calls_the_bodies, level0_bodies
     src = read("lasgun_amd", "csrc", "k_views.hip")
     for kernel in ("view_closest_kernel", "view_shade_kernel", "view_combine_kernel", "view_resolve_kernel"):
         assert re.search(r"__global__ void [^\n]*\b%s\(" % kernel, src), kernel
-    assert len(re.findall(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", src)) == 1, "one walk, closest hit"
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "wave_append(" in src and "shade_frame(" in src and "trav_launch<ViewKernels>" in src
-    assert "(vzero() + value) * 1.0" in src and "l0_tile(" in src and "__builtin_amdgcn_readfirstlane" in src
+    level0_bodies()  # one walk, closest hit
+    calls_the_bodies(src, 1, 1, 1)
+    assert "wave_append(" not in src and "trav_launch<ViewKernels>" in src and "trav_set_lds_limit<ViewKernels>" in src
+    assert "film_store(Q, it.px.pix, l0_finished(value))" in src and "l0_tile(" in src and "__builtin_amdgcn_readfirstlane" in src
+    assert "view_ray(P, view_load(Q, it.px.v), it.px.x, it.px.y, it.sample)" in src and "ViewSource{Q}" in src
     make = read("lasgun_amd", "csrc", "Makefile")
     kobjs = re.search(r"^KOBJS = (.*)$", make, flags=re.M).group(1).split()
     assert "k_views.o" in kobjs and "-ffp-contract=off" in make and "views_host.h" in make
     assert "view_set_lds_limit" in read("lasgun_amd", "csrc", "accel.cpp")
     launch = read("lasgun_amd", "csrc", "launch.cpp")
-    assert "launch_view_closest(" in launch and "launch_view_shade(" in launch and "launch_view_combine(" in launch
-    assert re.search(r"timed\(a, 1, stream, \[&\] \{ return launch_view_resolve\(", launch), "the resolve is credited to kind 1"
+    assert "bind_level0<ViewArgs, launch_view_closest, launch_view_shade, launch_view_combine>(V)" in launch
+    assert "l0.resolve_ = l0_flat<ViewArgs, launch_view_resolve>" in launch
+    assert re.search(r"timed\(a, 1, stream, \[&\] \{ return l0\.resolve\(", launch), "the resolve is credited to kind 1"
     assert launch.count("static void enqueue_level0_query(") == 1 and launch.count("struct WfChunk {") == 1, "one level-0 query over the ray source, not a copy"
     host = read("lasgun_amd", "csrc", "query.cpp")
     whole = host[host.index("// ---- views"):host.index("// ---- feature buffers")]
