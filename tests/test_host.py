@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import lasgun_amd as la
+import limit_scenes
 from golden_cases import CASES
 from lasgun_amd import scenes as S
 from oracle_lib import oracle
@@ -41,6 +42,8 @@ def test_no_cpu_fallback_without_a_device():
 BUILD_CASES = dict(CASES)
 BUILD_CASES["mixed_small"] = (lambda api: S.mixed_scene(api, 300, 40, 40), 0, 0)
 BUILD_CASES["mesh_100k"] = (lambda api: S.mesh_scene(api), 0, 0)
+for _name, _builder in limit_scenes.SCENES.items():  # eight levels, 64 / 65 accels, the deepest stacks (tests/limit_scenes.py)
+    BUILD_CASES[_name] = (_builder, 0, 0)
 
 
 @pytest.mark.parametrize("name", list(BUILD_CASES))

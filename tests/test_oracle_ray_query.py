@@ -9,6 +9,7 @@ import pytest
 
 import pyref
 import edge_rays as E
+import limit_scenes as L
 from lasgun_amd import scenes as S
 from oracle_lib import oracle
 from query_witness import Witness, bits, pod, portable_trig, same
@@ -24,7 +25,11 @@ SCENES = [("kitchen_sink", lambda api: S.kitchen_sink_scene(api), {}),
           ("random_3", lambda api: S.random_scene(api, 3), {}),
           ("f3", E.f3_scene, {}),
           ("f7", E.f7_scene, {"huge": True}),
-          ("grid", E.grid_scene, {"mesh": True})]
+          ("grid", E.grid_scene, {"mesh": True}),
+          # the scene graph's limits (tests/limit_scenes.py): the oracle is pinned at eight levels and past 64 accels HERE.  "camera": the
+          # scene's own camera rays beside the edge rays; "deepest": the accels at the end of the longest chains, in which some winners must lie
+          ("chain8_shallow", L.chain8_shallow, {"camera": True, "deepest": (7, 9)}),
+          ("accels65", L.accels65, {"camera": True, "deepest": (2, 4)})]
 
 
 @contextlib.contextmanager
@@ -39,7 +44,11 @@ def oracle_trig(o, portable):
 
 def scene_rays(pscene, wit, kw, seed):
     lo, hi, boxes = E.scene_geometry(wit, pscene)
-    return E.edge_rays(lo, hi, boxes=boxes, seed=seed, **kw)
+    rays, fam = E.edge_rays(lo, hi, boxes=boxes, seed=seed, **{k: v for k, v in kw.items() if k not in ("camera", "deepest")})
+    if kw.get("camera"):
+        cam = np.array([[*od[0], *od[1]] for y in range(L.H // 2) for x in range(L.W // 2) for od in pscene.camera.sample(x, y, L.W // 2, L.H // 2)])
+        rays, fam = np.concatenate([rays, cam]), np.concatenate([fam, np.array(["camera"] * len(cam))])
+    return rays, fam
 
 
 @pytest.mark.parametrize("portable", [False, True], ids=["libm", "portable"])
@@ -50,12 +59,12 @@ def test_oracle_queries_match_the_witness(name, builder, kw, portable):
     accel = o.Accel.from_scene(oscene)
     wit = Witness(pscene)
     rays, fam = scene_rays(pscene, wit, kw, seed=len(name))
-    n_hit, n_nan = {}, 0
+    n_hit, n_nan, n_deepest = {}, 0, 0
     with oracle_trig(o, portable):
         hits, mats = o.intersect(accel, rays)
         occ = o.occluded(accel, rays)
         for i, ray in enumerate(rays):
-            h, want, ctx = hits[i], wit.closest(ray[:3], ray[3:]), (name, fam[i], i, list(ray))
+            h, want, ctx = hits[i], wit.closest(ray[:3], ray[3:]), [name, fam[i], i, list(ray)]  # (a list: the messages below append to it)
             if want is None:
                 assert h["t"] == np.inf and h["kind"] == 0 and h["prim"] == 0xFFFFFFFF and h["instance"] == 0xFFFFFFFF, ctx
                 assert h["material"] == -1 and not occ[i], ctx
@@ -63,6 +72,7 @@ def test_oracle_queries_match_the_witness(name, builder, kw, portable):
                 continue
             n_hit[fam[i]] = n_hit.get(fam[i], 0) + 1
             n_nan += want["t"] != want["t"]
+            n_deepest += want["id"][2] in kw.get("deepest", ())
             assert same(h["t"], want["t"]), ctx + [h["t"], want["t"]]
             assert (int(h["kind"]), int(h["prim"]), int(h["instance"])) == want["id"], ctx + [h, want["id"]]
             kind, flat = pod(want["mat"])
@@ -74,6 +84,8 @@ def test_oracle_queries_match_the_witness(name, builder, kw, portable):
         assert n_hit.get(f, 0) >= 8, (name, f, n_hit)
     if kw.get("huge"):
         assert n_hit["F7"] >= 10 and n_nan >= 1, (n_hit, n_nan)
+    if kw.get("camera"):
+        assert n_hit["camera"] >= 64 and n_deepest >= 16, (name, n_hit, n_deepest)
 
 
 def test_f7_the_nan_winner_is_not_an_occluder():
