@@ -234,6 +234,22 @@ pub use sys::lg_scan_out as ScanOut;
 /// stated default (pose lanes iff n_poses >= n_beams); -1 for a bad `lanes`.  No device is touched.
 pub fn range_scan_lanes(n_poses: usize, n_beams: usize, lanes: i32) -> i32 { unsafe { sys::lg_range_scan_lanes(n_poses, n_beams, lanes) } }
 pub use sys::lg_layers_out as LayersOut;
+/// One rule of `Accel::trace_paths` (`lg_path_rule`, 24 bytes), indexed by a hit's material; `action` is one of `sys::LG_PATH_*`.
+pub use sys::lg_path_rule as PathRule;
+pub use sys::lg_paths_out as PathsOut;
+/// The planes `Accel::trace_paths` fills: `None` = not asked for; not all nine.
+#[derive(Default)]
+pub struct Paths<'a> {
+    pub hits: Option<&'a mut [sys::lg_hit]>,
+    pub point: Option<&'a mut [[f64; 3]]>,
+    pub id: Option<&'a mut [[u32; 4]]>,
+    pub along: Option<&'a mut [f64]>,
+    pub count: Option<&'a mut [u32]>,
+    pub end: Option<&'a mut [u32]>,
+    pub gain: Option<&'a mut [f64]>,
+    pub last: Option<&'a mut [[f64; 6]]>,
+    pub medium: Option<&'a mut [u32]>,
+}
 pub use sys::lg_gather_out as GatherOut;
 /// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
 /// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
@@ -440,6 +456,52 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `hit_layers` states (the library checks what HIP can tell it).
     pub unsafe fn hit_layers_device(&self, dev_rays: *const f64, n: usize, max_layers: u32, dev_out: &sys::lg_layers_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_hit_layers_device(self.ptr, dev_rays, n, max_layers, dev_out, hip_stream) != 0 {
+            panic!("lasgun: {}", last_error())
+        }
+    }
+    /// Ray paths (`lg_trace_paths`): every ray followed through up to `max_bounces` vertices, the rule per material the caller's
+    /// (`rules.len()` == the accel's material count).  Vertex j of ray i is at `j * rays.len() + i` of every vertex plane given: hits =
+    /// `intersect`'s record of segment j (the miss record behind a path's last vertex), point = its p, id = kind, prim, instance, material,
+    /// along = the running sum of t (+inf behind the last vertex).  Per ray: count = the vertices found, end = `sys::LG_PATH_END_*`, gain =
+    /// the product of the rules' gains, last = the ray a cut path resumes from (or the segment the path ended on), medium = the final
+    /// crossing parity.  `normal`: 0 the geometric, 1 the shading normal; `start_medium`: bit 0 per ray, `None` = all outside.
+    pub fn trace_paths(&self, rays: &[[f64; 6]], max_bounces: u32, rules: &[PathRule], normal: i32, start_medium: Option<&[u32]>, out: Paths) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_paths_out>() == 72 && std::mem::size_of::<sys::lg_path_rule>() == 24);
+        let n = rays.len();
+        let total = n.checked_mul(max_bounces as usize).expect("trace_paths: rays.len() * max_bounces overflows usize");
+        assert!(start_medium.map_or(true, |m| m.len() == n), "trace_paths: start_medium has one word per ray");
+        assert!(out.hits.as_ref().map_or(true, |p| p.len() == total) && out.point.as_ref().map_or(true, |p| p.len() == total)
+                && out.id.as_ref().map_or(true, |p| p.len() == total) && out.along.as_ref().map_or(true, |p| p.len() == total)
+                && out.count.as_ref().map_or(true, |p| p.len() == n) && out.end.as_ref().map_or(true, |p| p.len() == n)
+                && out.gain.as_ref().map_or(true, |p| p.len() == n) && out.last.as_ref().map_or(true, |p| p.len() == n)
+                && out.medium.as_ref().map_or(true, |p| p.len() == n),
+                "trace_paths: vertex planes of rays.len() * max_bounces elements, per-ray planes of rays.len()");
+        let o = sys::lg_paths_out {
+            hits: out.hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            point: out.point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            id: out.id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+            along: out.along.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            count: out.count.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            end: out.end.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            gain: out.gain.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            last: out.last.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            medium: out.medium.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+        };
+        let rc = unsafe {
+            sys::lg_trace_paths(self.ptr, rays.as_ptr() as *const f64, n, max_bounces, rules.as_ptr(), rules.len(), normal,
+                                start_medium.map_or(std::ptr::null(), |m| m.as_ptr()), &o)
+        };
+        if rc != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `trace_paths` for rays in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for);
+    /// `rules` is a host slice, copied before the call returns
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `trace_paths` states (the library checks what HIP can tell it).
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn trace_paths_device(&self, dev_rays: *const f64, n: usize, max_bounces: u32, rules: &[PathRule], normal: i32, dev_start_medium: *const u32,
+                                     dev_out: &sys::lg_paths_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_trace_paths_device(self.ptr, dev_rays, n, max_bounces, rules.as_ptr(), rules.len(), normal, dev_start_medium, dev_out, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
     }

@@ -273,6 +273,48 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void radiance_groups_device(const double *dev_rays, size_t n, const std::vector<lg_light_group> &groups, double *dev_radiance, void *hip_stream) const {
         if (lg_radiance_groups_device(h_, dev_rays, n, groups.data(), groups.size(), dev_radiance, hip_stream)) throw Error(lg_last_error());
     }
+    // ray paths (lg_trace_paths): every ray followed through up to max_bounces vertices, the rule per material the caller's (rules.size() ==
+    // material_count(); path_rule() makes one).  Vertex j of ray i at j * rays.size() + i of every vertex plane asked for (a null member is
+    // not asked for; not all nine): hits = lg_intersect's record of segment j (the miss record behind a path's last vertex), point = its p,
+    // id = kind, prim, instance, material, along = the running sum of t (+inf behind the last vertex).  Per ray: count = the vertices found,
+    // end = LG_PATH_END_*, gain = the product of the rules' gains, last = the ray a cut path resumes from (or the segment the path ended
+    // on), medium = the final crossing parity.  normal: 0 lg_hit::ng, 1 lg_hit::ns; start_medium: bit 0 per ray, or null (all outside)
+    struct Paths {
+        std::vector<lg_hit> *hits = nullptr;                  // [max_bounces*rays]
+        std::vector<std::array<double, 3>> *point = nullptr;
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;
+        std::vector<double> *along = nullptr;
+        std::vector<uint32_t> *count = nullptr;               // [rays]
+        std::vector<uint32_t> *end = nullptr;
+        std::vector<double> *gain = nullptr;
+        std::vector<std::array<double, 6>> *last = nullptr;
+        std::vector<uint32_t> *medium = nullptr;
+    };
+    static lg_path_rule path_rule(uint32_t action, double ior = 1.0, double gain = 1.0) { return lg_path_rule{action, 0u, ior, gain}; }
+    void trace_paths(const std::vector<std::array<double, 6>> &rays, uint32_t max_bounces, const std::vector<lg_path_rule> &rules, const Paths &out, int normal = 0,
+                     const std::vector<uint32_t> *start_medium = nullptr) const {
+        static_assert(sizeof(lg_paths_out) == 72 && sizeof(lg_path_rule) == 24, "lg_paths_out: nine pointers; lg_path_rule: 24 bytes");
+        if (max_bounces && rays.size() > SIZE_MAX / max_bounces) throw Error("trace_paths: rays.size() * max_bounces does not fit size_t");
+        if (start_medium && start_medium->size() != rays.size()) throw Error("trace_paths: start_medium has one word per ray");
+        const size_t n = rays.size() * max_bounces;
+        lg_paths_out o{};
+        if (out.hits) { out.hits->assign(n, lg_hit{}); o.hits = out.hits->data(); }
+        if (out.point) { out.point->assign(n, {0.0, 0.0, 0.0}); o.point = n ? (*out.point)[0].data() : nullptr; }
+        if (out.id) { out.id->assign(n, {0u, 0u, 0u, 0u}); o.id = n ? (*out.id)[0].data() : nullptr; }
+        if (out.along) { out.along->assign(n, 0.0); o.along = out.along->data(); }
+        if (out.count) { out.count->assign(rays.size(), 0u); o.count = out.count->data(); }
+        if (out.end) { out.end->assign(rays.size(), 0u); o.end = out.end->data(); }
+        if (out.gain) { out.gain->assign(rays.size(), 0.0); o.gain = out.gain->data(); }
+        if (out.last) { out.last->assign(rays.size(), {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.last = rays.empty() ? nullptr : (*out.last)[0].data(); }
+        if (out.medium) { out.medium->assign(rays.size(), 0u); o.medium = out.medium->data(); }
+        if (lg_trace_paths(h_, rays.empty() ? nullptr : rays[0].data(), rays.size(), max_bounces, rules.data(), rules.size(), normal,
+                           start_medium ? start_medium->data() : nullptr, &o))
+            throw Error(lg_last_error());
+    }
+    void trace_paths_device(const double *dev_rays, size_t n, uint32_t max_bounces, const std::vector<lg_path_rule> &rules, int normal, const uint32_t *dev_start_medium,
+                            const lg_paths_out &dev_out, void *hip_stream) const {
+        if (lg_trace_paths_device(h_, dev_rays, n, max_bounces, rules.data(), rules.size(), normal, dev_start_medium, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<std::array<double, 3>> out(rays.size());

@@ -895,6 +895,92 @@ typedef struct lg_layers_out {
 int lg_hit_layers(const lg_accel *, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out); /* host arrays; synchronous */
 int lg_hit_layers_device(const lg_accel *, const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out *dev_out,
                          void *hip_stream);
+/* Ray paths: follow each ray through up to max_bounces specular bounces in one call -- a laser or a lens bench through glass, room
+ * acoustics and radio ray launching (K reflections with a gain per surface), a lidar's multipath returns, a caustic or photon pass from a
+ * light, the specular chain of an integrator of one's own -- without the caller's own loop that traces, reads back 96 bytes a ray,
+ * reflects or refracts on the host, offsets the origin by a guess, compacts the live rays and uploads 48 bytes a ray, max_bounces times
+ * over.  One launch walks each ray up to max_bounces times; the ray stays in registers between the walks; only the planes asked for are
+ * written.  This is NOT the path the render follows (its li() is a tree: glass spawns two children; its reflection goes through the
+ * BSDF's local frame): it is a chain whose rule per material the caller gives.  An EXTRA; no counterpart in the reference.
+ * The contract is a loop over lg_intersect:
+ * Segments and vertices: ray i is 6 doubles as for lg_intersect; any f64 is accepted as it is.  Segment 0 of ray i is that ray, bit for
+ * bit.  Vertex j is what lg_intersect returns for segment j, bit for bit, exact ties included, in the accel's traversal mode exactly as
+ * for the other queries (reference, pruned, LDS-resident scene, fast mode); no switch of its own.  A miss ends the path with
+ * LG_PATH_END_ESCAPED.
+ * At a vertex: let p, ng, ns be the record's lg_hit::p, ::ng, ::ns, d the segment's direction and r = rules[material], with material the
+ * record's lg_hit::material.  rules has exactly lg_accel_material_count entries (n_rules says so) and is a HOST array in both forms,
+ * copied before the call returns: it may be freed on return.  A material outside 0 .. n_rules-1 is treated as LG_PATH_ABSORB.
+ * LG_PATH_ABSORB: the path ends with LG_PATH_END_ABSORBED.  Otherwise gain = gain * r.gain (from 1.0, sequential in f64; a NaN stays:
+ * where gain is NaN it is kept bit for bit, as along is), and then the next ray (o', d') is formed, all of it f64 with nothing fused and
+ * dot(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z:
+ *   N = normal ? ns : ng (normal: 0 uses lg_hit::ng, 1 uses lg_hit::ns).  s = dot(d, N).  If s > 0.0: N = -N and s = -s, per component.
+ *   LG_PATH_REFLECT: k = 2.0*s; d'[c] = d[c] - k*N[c]; o'[c] = p[c] + ng[c]*0x1p-36.
+ *   LG_PATH_PASS: d' is d's bits; o'[c] = p[c] - ng[c]*0x1p-36; medium ^= 1 -- the step of a hit layer.
+ *   LG_PATH_REFRACT: L = sqrt(dot(d,d)), q = 1.0/L, u[c] = d[c]*q, ci = -dot(u,N).  eta = medium ? r.ior : 1.0/r.ior.
+ *     sin2 = (eta*eta) * fmax(1.0 - ci*ci, 0.0), fmax the NaN-ignoring one.  If sin2 >= 1.0 (total internal reflection): REFLECT's two
+ *     lines on d, no toggle.  Else ct = sqrt(1.0 - sin2), a = eta*ci - ct, w[c] = eta*u[c] + a*N[c], d'[c] = w[c]*L,
+ *     o'[c] = p[c] - ng[c]*0x1p-36, medium ^= 1.
+ * Inside or outside is the crossing parity in medium, not a normal's sign: lg_hit::ns of a sphere hit from inside faces the ray, so a
+ * rule that reads the sign of d.ns never leaves a glass sphere.  medium starts at bit 0 of start_medium[i] (start_medium NULL: every ray
+ * starts outside, 0); only bit 0 is read.  The offset is always along ng, the geometric normal, which faces -d.
+ * After the next ray is formed: if any of the six components of (o', d') is not finite, the path ends with LG_PATH_END_DEGENERATE (gain
+ * and medium as the forming left them).  Otherwise, if j + 1 == max_bounces, it ends with LG_PATH_END_CUT.  Otherwise segment j+1 is
+ * (o', d').
+ * Planes (lg_paths_out) per vertex are VERTEX-MAJOR: element (j, i) is at j*n + i.  hits = the whole lg_hit of vertex j.  point = its p
+ * (3 doubles).  id = its kind, prim, instance, material.  along = the running sum of t: T_0 = t_0 and T_j = T_(j-1) + t_j, sequentially
+ * in f64, the 2^-36 steps NOT added, in units of each segment's own |d|; a NaN stays (where T_(j-1) is NaN, T_j is T_(j-1) bit for bit).
+ * Behind a path's last vertex: hits holds lg_intersect's miss record (t = +INF, zeros, kind 0, prim and instance ~0, material -1), id
+ * holds 0, ~0, ~0, -1, point holds +0s, along holds +INF.
+ * Planes per ray: count[i] = the number of vertices, 0 .. max_bounces.  end[i] = LG_PATH_END_*; LG_PATH_END_CUT goes with
+ * count == max_bounces.  gain[i] as above.  medium[i] = the final bit.  last[i] = 6 doubles, origin then direction: for CUT the next ray
+ * (o', d'); for ESCAPED the segment that missed; for ABSORBED and DEGENERATE the segment that found the last vertex.
+ * Resuming: a call of a bounces, then a call of b bounces on last and medium of its CUT rays (as rays and start_medium), gives rows
+ * a .. a+b-1 of one call of a+b, bit for bit, in hits, point and id; count (a + the second call's), end, last and medium agree too.
+ * along and gain RESTART in the second call (from t_0 and from 1.0): the caller adds and multiplies.
+ * Every element of every plane asked for is written, whatever the buffers held before, by exactly one lane: no atomics, no pre-fill.
+ * lg_accel_set_query_order(1) is honoured exactly as lg_hit_layers honours it: the tiles are cut from the sorted order of the GIVEN
+ * rays, every answer lands in its own ray's slots, the same bytes as order 0 (a query of 64 rays or fewer is walked as given).
+ * Limits and errors, as for lg_hit_layers: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors
+ * (non-zero, lg_last_error, nothing launched, no output touched), for n > 0: max_bounces == 0; n > (2^32 - 1) * 64, and n > 2^32 - 1
+ * with the sorted order; n * max_bounces or a plane's byte size that does not fit size_t; a NULL accel, rays, rules or out; all nine
+ * planes NULL; n_rules != lg_accel_material_count; an action above LG_PATH_REFRACT; reserved != 0; normal outside {0, 1}; in the device
+ * form also a pointer that is not device memory of the accel's device or is misaligned (rays 8 bytes; hits and id 16; point, along, gain
+ * and last 8; count, end, medium and start_medium 4), or a buffer that ends beyond its allocation.
+ * Device form: dev_out is a HOST struct of device pointers, rules a HOST array; it only enqueues on hip_stream; one stream at a time per
+ * accel.  Host form (synchronous): the rays go up, the planes come back into staging and are copied out at the end, so an error on the
+ * way leaves the caller's arrays as they were.
+ * Out of scope: branching (a glass vertex's two children: call twice with two tables); re-packing of lanes or re-sorting of rays between
+ * bounces (a wave walks while any of its paths is alive); a maximum range; nested or overlapping media beyond the one parity bit;
+ * multi-device. */
+#define LG_PATH_ABSORB  0u   /* the path ends at this vertex */
+#define LG_PATH_REFLECT 1u   /* mirror about the normal */
+#define LG_PATH_PASS    2u   /* straight on, as a hit layer does */
+#define LG_PATH_REFRACT 3u   /* Snell with `ior`; total internal reflection reflects */
+typedef struct lg_path_rule {
+    uint32_t action;    /* LG_PATH_* */
+    uint32_t reserved;  /* 0 */
+    double   ior;       /* LG_PATH_REFRACT: the material's index of refraction against the outside */
+    double   gain;      /* multiplied into the path's gain at every vertex that does not absorb */
+} lg_path_rule;         /* 24 bytes */
+#define LG_PATH_END_CUT 0u        /* alive after max_bounces vertices: count == max_bounces */
+#define LG_PATH_END_ESCAPED 1u    /* a segment missed */
+#define LG_PATH_END_ABSORBED 2u
+#define LG_PATH_END_DEGENERATE 3u /* the next ray had a non-finite component */
+typedef struct lg_paths_out {
+    lg_hit   *hits;    /* [max_bounces][n]     the whole record of vertex j of ray i, at j*n + i */
+    double   *point;   /* [max_bounces][n][3]  its p, +0s behind the last vertex */
+    uint32_t *id;      /* [max_bounces][n][4]  kind, prim, instance, material: the last 16 bytes of an lg_hit */
+    double   *along;   /* [max_bounces][n]     running sum of t, +INF behind the last vertex */
+    uint32_t *count;   /* [n]                  vertices found, 0 .. max_bounces */
+    uint32_t *end;     /* [n]                  LG_PATH_END_* */
+    double   *gain;    /* [n]                  product of the rules' gains */
+    double   *last;    /* [n][6]               the ray to resume from, or the segment the path ended on */
+    uint32_t *medium;  /* [n]                  the final parity bit */
+} lg_paths_out;        /* 72 bytes; each pointer may be NULL, all NULL is an error */
+int lg_trace_paths(const lg_accel *, const double *rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules,
+                   int normal, const uint32_t *start_medium, const lg_paths_out *out); /* host arrays; synchronous */
+int lg_trace_paths_device(const lg_accel *, const double *dev_rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules,
+                          size_t n_rules, int normal, const uint32_t *dev_start_medium, const lg_paths_out *dev_out, void *hip_stream);
 /* Light groups: li() of each ray split by subsets of the scene's lights, n_groups planes from one call -- light-group AOVs for
  * compositing, re-lighting a frame afterwards by changing intensities and colours, a light-mixing slider, a per-light contribution for
  * light placement -- without a scene and an accel rebuilt and a render repeated per group.  Nothing a walk finds depends on which

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -104,6 +104,7 @@ _EXTRA = {
     **DIRECTIONS_SIGNATURES,
     **RANGE_SCAN_SIGNATURES,
     **HIT_LAYERS_SIGNATURES,
+    **PATHS_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -132,6 +133,15 @@ assert _C.sizeof(CLayersOut) == 40, "lg_layers_out is 40 bytes"
 LAYER_PLANES = ("hits", "along", "id", "count", "inside")  # lg_layers_out's members, in its order
 _LAYER_SHAPE = {"hits": ((), HIT_DTYPE, True), "along": ((), _np.float64, True), "id": ((4,), _np.uint32, True), "count": ((), _np.uint32, False),
                 "inside": ((), _np.float64, False)}  # (trailing shape, dtype, per layer and ray -- else per ray)
+assert _C.sizeof(CPathRule) == 24 and _C.sizeof(CPathsOut) == 72, "lg_path_rule is 24 bytes, lg_paths_out 72"
+PATH_PLANES = ("hits", "point", "id", "along", "count", "end", "gain", "last", "medium")  # lg_paths_out's members, in its order
+_PATH_SHAPE = {"hits": ((), HIT_DTYPE, True), "point": ((3,), _np.float64, True), "id": ((4,), _np.uint32, True), "along": ((), _np.float64, True),
+               "count": ((), _np.uint32, False), "end": ((), _np.uint32, False), "gain": ((), _np.float64, False), "last": ((6,), _np.float64, False),
+               "medium": ((), _np.uint32, False)}  # (trailing shape, dtype, per vertex and ray -- else per ray)
+PATH_ABSORB, PATH_REFLECT, PATH_PASS, PATH_REFRACT = 0, 1, 2, 3                   # LG_PATH_*: lg_path_rule::action
+PATH_END_CUT, PATH_END_ESCAPED, PATH_END_ABSORBED, PATH_END_DEGENERATE = 0, 1, 2, 3  # LG_PATH_END_*: lg_paths_out::end
+PATH_RULE_DTYPE = _np.dtype([("action", _np.uint32), ("reserved", _np.uint32), ("ior", _np.float64), ("gain", _np.float64)])  # lg_path_rule
+assert PATH_RULE_DTYPE.itemsize == 24
 assert _C.sizeof(CGatherOut) == 16, "lg_gather_out is 16 bytes"
 GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
 GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
@@ -811,6 +821,78 @@ class HipApi(Api):
                      self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- ray paths (include/lasgun_hip.h, lg_trace_paths*): each ray followed through K specular bounces in one call
+    def path_rules(self, accel, default=PATH_ABSORB, gain=1.0):
+        """A rule table for trace_paths, one PATH_RULE_DTYPE record per material of the accel: glass -> PATH_REFRACT with the material's eta,
+        mirror and metal -> PATH_REFLECT, the rest -> `default`; every gain = `gain`.  A convention of this WRAPPER, not of the C contract
+        (lg_trace_paths takes whatever table the caller passes)."""
+        rules = _np.zeros(self.material_count(accel), dtype=PATH_RULE_DTYPE)
+        rules["action"], rules["ior"], rules["gain"] = int(default), 1.0, float(gain)
+        for i in range(len(rules)):
+            m = self.accel_material(accel, i)
+            if m["kind"] == 3:            # glass: p[6] = eta
+                rules[i]["action"], rules[i]["ior"] = PATH_REFRACT, m["p"][6]
+            elif m["kind"] in (2, 4):     # metal, mirror
+                rules[i]["action"] = PATH_REFLECT
+        return rules
+
+    @staticmethod
+    def _path_rules(rules):
+        r = _np.ascontiguousarray(rules)
+        if r.dtype != PATH_RULE_DTYPE or r.ndim != 1:
+            raise ValueError("rules: a 1-D array of PATH_RULE_DTYPE (la.path_rules(accel) makes one)")
+        return r
+
+    def trace_paths(self, accel, rays, max_bounces, rules, normal=0, start_medium=None, planes=("point", "id", "count", "end"), into=None):
+        """Every ray of an (n, 6) float64 array followed through up to max_bounces vertices: a dict of the planes asked for (any of
+        PATH_PLANES).  VERTEX-MAJOR: HIT_DTYPE (K, n) hits = lg_intersect's record of vertex j of ray i at [j, i] (the miss record behind a
+        path's last vertex), float64 (K, n, 3) point, uint32 (K, n, 4) id = kind, prim, instance, material, float64 (K, n) along = the
+        running sum of t (+inf behind the last vertex).  Per ray: uint32 (n,) count, end (PATH_END_*) and medium, float64 (n,) gain and
+        (n, 6) last = the ray to resume a cut path from (or the segment the path ended on).  rules: PATH_RULE_DTYPE, one per material
+        (path_rules(accel) is one convention); normal: 0 the geometric, 1 the shading normal; start_medium: (n,) uint32, bit 0 = the ray
+        starts inside (None: all outside).  `into`: a dict of C-contiguous arrays of those shapes, written in place."""
+        r = self._rays(rays)
+        n, k = r.shape[0], int(max_bounces)
+        planes = tuple(planes)
+        if any(p not in PATH_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (PATH_PLANES,))
+        if not 0 <= k <= 0xFFFFFFFF:
+            raise ValueError("max_bounces: 0 .. 2^32 - 1")
+        table = self._path_rules(rules)
+        sm = None
+        if start_medium is not None:
+            sm = _np.ascontiguousarray(start_medium, dtype=_np.uint32)
+            if sm.shape != (n,):
+                raise ValueError("start_medium: (n,) uint32")
+        out = {}
+        for p in planes:
+            tail, dt, per_vertex = _PATH_SHAPE[p]
+            shape = ((k, n) if per_vertex else (n,)) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CPathsOut(*[data(out.get(p)) for p in PATH_PLANES])
+        if self.call("trace_paths", accel.h, data(r), n, k, table.ctypes.data, len(table), int(normal), data(sm), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def trace_paths_device(self, accel, n, rays_ptr, max_bounces, rules, normal=0, start_medium_ptr=None, hits_ptr=None, point_ptr=None, id_ptr=None, along_ptr=None,
+                           count_ptr=None, end_ptr=None, gain_ptr=None, last_ptr=None, medium_ptr=None, stream=None):
+        """Enqueue the paths of n rays (device memory, 6 doubles each) into device memory, vertex-major: max_bounces * n elements at hits_ptr
+        (lg_hit, 16-byte aligned), point_ptr (3 f64), id_ptr (4 u32, 16-byte aligned) and along_ptr (f64), n elements at count_ptr, end_ptr,
+        medium_ptr (u32), gain_ptr (f64) and last_ptr (6 f64); each may be None, not all.  rules is a HOST table (PATH_RULE_DTYPE), copied
+        before the call returns; start_medium_ptr: n u32 in device memory or None.  The pointers are integers (torch: tensor.data_ptr()) or
+        objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CPathsOut(*[ptr(p) for p in (hits_ptr, point_ptr, id_ptr, along_ptr, count_ptr, end_ptr, gain_ptr, last_ptr, medium_ptr)])
+        table = self._path_rules(rules)
+        rays, sm = ptr(rays_ptr), ptr(start_medium_ptr)
+        if self.call("trace_paths_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), int(max_bounces), table.ctypes.data, len(table),
+                     int(normal), _C.c_void_p(sm) if sm is not None else None, _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- radiance gathers (include/lasgun_hip.h, lg_radiance_gather*): li() along K shared directions from N poses, reduced per pose
     @staticmethod
     def _gather_lanes(lanes):
@@ -1412,6 +1494,12 @@ api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=Fals
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
 api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
+def path_rules(accel, default=PATH_ABSORB, gain=1.0):
+    """The wrapper's one convention of a rule table for trace_paths: glass refracts with its eta, mirror and metal reflect, the rest `default`."""
+    return api.path_rules(accel, default, gain)
+
+
+api.Accel.trace_paths = lambda self, rays, max_bounces, rules=None, normal=0, start_medium=None, planes=("point", "id", "count", "end"): api.trace_paths(self, rays, max_bounces, api.path_rules(self) if rules is None else rules, normal, start_medium, planes)  # accel.trace_paths(rays, 8)
 api.Accel.radiance_gather = lambda self, origins, dirs, frames=None, weights=None, planes=("sums",), lanes=0: api.radiance_gather(self, origins, dirs, frames, weights, planes, lanes)  # accel.radiance_gather(origins, dirs, weights=w)
 api.Accel.views = lambda self, views, w, h, rgba=True, rgb=False: api.capture_views(self, views, w, h, rgba, rgb)  # accel.views(views, w, h)
 api.Accel.view_features = lambda self, views, w, h, planes=VIEW_FEATURE_PLANES, material_rgb=None: api.capture_view_features(self, views, w, h, planes, material_rgb)  # accel.view_features(views, w, h)

@@ -178,6 +178,13 @@ LIGHT_GROUPS_SIGNATURES = {
 GROUP_AMBIENT = 1  # LG_GROUP_AMBIENT
 MAX_LIGHT_GROUPS = 64  # LG_MAX_LIGHT_GROUPS
 
+# Ray paths (include/lasgun_hip.h, lg_trace_paths / lg_trace_paths_device): each ray followed through K specular bounces in one call, the
+# rule per material the caller's; vertex-major and per-ray planes; the GPU library's alone.
+PATHS_SIGNATURES = {
+    "trace_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "trace_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
 # directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
 GATHER_SIGNATURES = {
@@ -238,6 +245,15 @@ class CLayersOut(C.Structure):  # lg_layers_out: five pointers, 40 bytes; NULL =
 
 class CLightGroup(C.Structure):  # lg_light_group: 8 bytes; bit l of `lights` = light l in add order, flags = GROUP_AMBIENT or 0
     _fields_ = [("lights", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CPathRule(C.Structure):  # lg_path_rule: 24 bytes; action = LG_PATH_*, reserved = 0
+    _fields_ = [("action", C.c_uint32), ("reserved", C.c_uint32), ("ior", C.c_double), ("gain", C.c_double)]
+
+
+class CPathsOut(C.Structure):  # lg_paths_out: nine pointers, 72 bytes; NULL = not asked for
+    _fields_ = [("hits", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p), ("along", C.c_void_p), ("count", C.c_void_p), ("end", C.c_void_p),
+                ("gain", C.c_void_p), ("last", C.c_void_p), ("medium", C.c_void_p)]
 
 
 class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for

@@ -113,6 +113,14 @@ hipError_t launch_hit_layers(const DParams &P, const double *rays, unsigned long
                              double *inside, const uint32_t *tri_base, const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t hit_layers_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t hit_layers_set_lds_limit(size_t bytes, bool ldss);
+// k_paths.hip: ray paths (lg_trace_paths*) -- layers_kernel's loop with a direction update: at each hit the rule of its material (`rules`:
+// n_rules lg_path_rule records in DEVICE memory) ends the path or forms the next segment in registers (bounce.h); only the planes that are
+// not nullptr are written, vertex-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order
+hipError_t launch_trace_paths(const DParams &P, const double *rays, unsigned long long n, uint32_t max_bounces, const void *rules, uint32_t n_rules, bool use_ns,
+                              const uint32_t *start_medium, void *hits, double *point, void *id, double *along, uint32_t *count, uint32_t *end, double *gain, double *last,
+                              uint32_t *medium, const uint32_t *tri_base, const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t trace_paths_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t trace_paths_set_lds_limit(size_t bytes, bool ldss);
 // k_features.hip: feature buffers (lg_capture_features*) -- the closest-hit walk of the camera's own rays, an 8 x 8 tile of the rectangle per
 // wave and a pixel per lane; only the planes that are not nullptr are written, at DParams' output addressing (out_row0 / out_x0 / out_pitch)
 hipError_t launch_features(const DParams &P, float *depth, float *normal, float *albedo, float *coverage, void *id, const double *material_rgb, uint32_t nmat,
@@ -591,6 +599,8 @@ void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint3
 // ... and the staging alone, for a call that launches a kernel of its own over the table (lg_capture_view_features*): the device table
 // of this call, released by subsets_enqueued() behind the launch or by subsets_abandoned() where the call fails before it
 const DView *stage_view_table(const DView *views, size_t n_views, lg_accel::LaunchCtx &c, hipStream_t stream);
+// ... and the same for the rule table of lg_trace_paths* (`bytes`: a multiple of 8), released the same way
+const void *stage_rule_table(const void *rules, size_t bytes, lg_accel::LaunchCtx &c, hipStream_t stream);
 void set_rect(DParams &P, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1);
 unsigned long long subset_count(unsigned long long area, unsigned long long k, unsigned long long n);
 void set_subset(const lg_accel &a, hipStream_t stream, DParams &P, size_t k, size_t n, uint32_t w, uint32_t h);

@@ -653,6 +653,15 @@ const DView *stage_view_table(const DView *views, size_t n_views, lg_accel::Laun
     HIP_TRY(hipMemcpyAsync(t.buf.p, t.stage.p, bytes, hipMemcpyHostToDevice, stream));
     return reinterpret_cast<const DView *>(t.buf.p);
 }
+// ... and the rule table of a call (lg_trace_paths*), the same way: `bytes` of 64-bit words
+const void *stage_rule_table(const void *rules, size_t bytes, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    lg_accel::LaunchCtx::KsTable &t = live_table(c);
+    t.stage.need(std::max<size_t>(bytes, 8));
+    std::memcpy(t.stage.p, rules, bytes);
+    t.buf.alloc(std::max<size_t>(bytes / sizeof(unsigned long long), 128));
+    if (bytes) HIP_TRY(hipMemcpyAsync(t.buf.p, t.stage.p, bytes, hipMemcpyHostToDevice, stream));
+    return t.buf.p;
+}
 // A view batch (query.cpp, lg_capture_views*; the call checked there and in views_host.h): the table, then one level-0 query over the
 // batch's pixel tiles.
 void enqueue_view_batch(const lg_accel &a, const DView *views, ViewArgs V, uint32_t samples_root, lg_accel::LaunchCtx &c, hipStream_t stream) {

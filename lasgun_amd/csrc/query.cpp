@@ -1,11 +1,11 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
-// lg_layers_out / lg_features is, is scan_host.h's / layers_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
+// lg_layers_out / lg_paths_out / lg_features is, is scan_host.h's / layers_host.h's / paths_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
 
@@ -13,6 +13,7 @@
 #include "features_host.h"
 #include "gather_host.h"
 #include "layers_host.h"
+#include "paths_host.h"
 #include "light_groups_host.h"
 #include "scan_host.h"
 #include "views_host.h"
@@ -840,6 +841,61 @@ extern "C" int lg_hit_layers_device(const lg_accel *a, const double *dev_rays, s
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         layer_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
         enqueue_hit_layers(*a, dev_rays, n, max_layers, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- ray paths (lg_trace_paths*; k_paths.hip): each of the caller's rays followed through up to max_bounces vertices, the next segment
+// formed in the kernel by the rule of the hit's material, the answer as vertex-major and per-ray planes.  What needs no device -- the limits,
+// n * max_bounces and the sizes, the rule table's validation, the NULL and alignment rules, the staging -- is paths_host.h's.
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers): the
+// rules through the launch context's pinned staging into a table of the call's own (the caller's array may be freed on return), then ONE
+// launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is parked
+static void enqueue_trace_paths(const lg_accel &a, const double *rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules, int normal,
+                                const uint32_t *start_medium, const lg_paths_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    P.ntiles = (uint32_t)((n + 63) / 64);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    try {
+        const void *table = stage_rule_table(rules, n_rules * sizeof(lg_path_rule), c, stream);
+        const uint32_t *perm = query_order_of(a, c, rays, n, stream); // (ahead of the counter's memset on the stream)
+        const TraversalGrid g = traversal_grid(a, P, trace_paths_occupancy, c, stream);
+        HIP_TRY(launch_trace_paths(P, rays, n, max_bounces, table, (uint32_t)n_rules, normal == 1, start_medium, out.hits, out.point, out.id, out.along, out.count, out.end,
+                                   out.gain, out.last, out.medium, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
+        subsets_enqueued(a, stream);
+    } catch (...) { subsets_abandoned(a, stream); throw; }
+}
+// Host form: the rays (and the starting media) go up, the planes come back into staging and are copied out at the end
+extern "C" int lg_trace_paths(const lg_accel *a, const double *rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules, int normal,
+                              const uint32_t *start_medium, const lg_paths_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t total = check_paths(a, rays, n, max_bounces, rules, n_rules, lg_accel_material_count(a), normal, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        RoundTrip trip(*a);
+        PathsStaging st(*out, n, total);
+        const double *drays = trip.in(rays, n * 6);
+        const uint32_t *dmedium = trip.in(start_medium, n);
+        lg_paths_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        path_planes(dev, n, total, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        trip.run([&] { enqueue_trace_paths(*a, drays, n, max_bounces, rules, n_rules, normal, dmedium, dev, a->stream); });
+        place_paths(*out, st);
+    });
+}
+extern "C" int lg_trace_paths_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules, int normal,
+                                     const uint32_t *dev_start_medium, const lg_paths_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t total = check_paths(a, dev_rays, n, max_bounces, rules, n_rules, lg_accel_material_count(a), normal, dev_out);
+        check_paths_alignment(dev_rays, dev_start_medium, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        if (dev_start_medium) check_device_buffer(*a, dev_start_medium, n * sizeof(uint32_t), 4, "start_medium");
+        path_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        enqueue_trace_paths(*a, dev_rays, n, max_bounces, rules, n_rules, normal, dev_start_medium, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

@@ -66,11 +66,14 @@ id + count; row LX: the same call with inside alone (the x-ray image, 8 bytes ou
 Y8 / YX, 8 rounds of lg_intersect_device with the planes pre-filled, the next origins computed and the live rays compacted by torch on the
 same stream (the compaction's size comes back to the host every round: the route needs it).  Timed L8, Y8, LX, YX, so --repeats alternates
 them; Y's planes are checked against L's bytes.  These rows time --calls calls as given (at least 4; the Y rows half as many), not 20.
+Ray paths (lg_trace_paths_device) -- --rows paths (not part of "all"): the camera's rays of a --size^2 film, 8 bounces, glass refracts and
+everything else reflects.  Row P8: one call, point + id + count + end.  Row Z8: the route without it -- 8 rounds of lg_intersect_device with
+the next rays formed and the live rays compacted by torch on the same stream -- into the same planes, checked against P8's bytes.
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -815,6 +818,101 @@ def measure_layers(name, builder, size, calls, K=8):
              "gpu": torch.cuda.get_device_name(0)} for row, ms, bpr, rnd in rows]
 
 
+def measure_paths(name, builder, size, calls, K=8):
+    """Ray paths on the camera's rays of a size^2 film, K bounces, the table "glass refracts, everything else reflects", the geometric
+    normal.  Row P8: one lg_trace_paths_device call, point + id + count + end.  Row Z8: the route without it -- K rounds of
+    lg_intersect_device, the planes pre-filled, the next rays formed (the header's arithmetic, one torch operation per f64 operation) and
+    the live rays compacted by torch on the same stream -- into the same planes.  P8 / Z8 are timed in that order, so a repeat alternates
+    them; Z's planes are checked against P's bytes."""
+    if not hasattr(G, "trace_paths_device"):
+        return []
+    scene = builder(G)
+    accel = G.Accel.from_scene(scene)
+    s = torch.cuda.current_stream().cuda_stream
+    G.set_query_order(accel, 0)
+    n = size * size * G.camera_samples(accel)
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rules = la.path_rules(accel, default=la.PATH_REFLECT)
+    t_refract = torch.from_numpy((rules["action"] == la.PATH_REFRACT)).cuda()
+    t_ior = torch.from_numpy(rules["ior"].copy()).cuda()
+    miss = torch.tensor([0, -1, -1, -1], dtype=torch.int32, device="cuda")
+
+    def planes():
+        return (torch.empty((K, n, 3), dtype=torch.float64, device="cuda"), torch.empty((K, n, 4), dtype=torch.int32, device="cuda"),
+                torch.empty((n,), dtype=torch.int32, device="cuda"), torch.empty((n,), dtype=torch.int32, device="cuda"))
+
+    point, ident, count, end = planes()
+    z_point, z_ident, z_count, z_end = planes()
+    hits = torch.empty((n * 96,), dtype=torch.uint8, device="cuda")
+    medium = torch.empty((n,), dtype=torch.bool, device="cuda")
+    rounds = []
+    dot = lambda a, b: (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]  # noqa: E731
+    col = lambda v: v[:, None]  # noqa: E731
+
+    def loop():
+        """The caller's own loop: lg_intersect_device, read the records, reflect or refract, compact; K times over."""
+        z_point.zero_()
+        z_ident[:] = miss
+        z_count.zero_()
+        z_end.zero_()  # LG_PATH_END_CUT: what a ray alive after K rounds keeps
+        medium.zero_()
+        cur, live = rays, None
+        rounds.clear()
+        for j in range(K):
+            m = cur.shape[0]
+            if m == 0:
+                break
+            rounds.append(m)
+            G.intersect_device(accel, m, cur.data_ptr(), hits.data_ptr(), stream=s)
+            h64, h32 = hits.view(torch.float64)[:m * 12].view(m, 12), hits.view(torch.int32)[:m * 24].view(m, 24)
+            hit = h32[:, 20] != 0
+            on = hit.nonzero().squeeze(1)  # (the compaction: its size comes back to the host)
+            off = (~hit).nonzero().squeeze(1)
+            idx = on if live is None else live[on]
+            z_end[off if live is None else live[off]] = 1  # LG_PATH_END_ESCAPED
+            p, ng, d = h64[on, 1:4], h64[on, 4:7], cur[on, 3:]
+            z_point[j, idx] = p
+            z_ident[j, idx] = h32[on, 20:24]
+            z_count[idx] += 1
+            mat = h32[on, 23].long()
+            sdn = dot(d, ng)
+            flip = sdn > 0.0
+            N, sdn = torch.where(col(flip), -ng, ng), torch.where(flip, -sdn, sdn)
+            step = ng * ERR
+            mirrored = d - col(2.0 * sdn) * N
+            L = torch.sqrt(dot(d, d))
+            u = d * col(1.0 / L)
+            ci = -dot(u, N)
+            med = medium[idx]
+            eta = torch.where(med, t_ior[mat], 1.0 / t_ior[mat])
+            sin2 = (eta * eta) * torch.fmax(1.0 - ci * ci, torch.zeros_like(ci))
+            refracts = t_refract[mat] & ~(sin2 >= 1.0)
+            a = eta * ci - torch.sqrt(1.0 - sin2)
+            refracted = (col(eta) * u + col(a) * N) * col(L)
+            nxt = torch.cat([torch.where(col(refracts), p - step, p + step), torch.where(col(refracts), refracted, mirrored)], dim=1)
+            medium[idx] = med ^ refracts
+            fin = torch.isfinite(nxt).all(dim=1)
+            z_end[idx[~fin]] = 3  # LG_PATH_END_DEGENERATE
+            keep = fin.nonzero().squeeze(1)
+            cur, live = nxt[keep], idx[keep]
+
+    rows = []
+    ms = timed(lambda: G.trace_paths_device(accel, n, rays.data_ptr(), K, rules, 0, point_ptr=point.data_ptr(), id_ptr=ident.data_ptr(), count_ptr=count.data_ptr(),
+                                            end_ptr=end.data_ptr(), stream=s), calls, warmup=1)
+    rows.append(("P8: ray paths, one call, point + id + count + end", ms, None))
+    ms = timed(loop, max(calls // 2, 2), warmup=1)
+    rows.append(("Z8: K rounds of lg_intersect_device + torch bounces and compaction, point + id + count + end", ms, list(rounds)))
+    torch.cuda.synchronize()
+    same = {"point": torch.equal(point.view(torch.int64), z_point.view(torch.int64)), "id": torch.equal(ident, z_ident), "count": torch.equal(count, z_count),
+            "end": torch.equal(end, z_end)}
+    assert all(same.values()), ("Z8's planes are not P8's", same)
+    return [{"scene": name, "row": row, "film": [size, size], "rays": n, "max_bounces": K, "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1),
+             "bytes_out_per_ray": K * 40.0 + 8.0, "rounds": rnd, "count_hist": torch.bincount(count.cpu(), minlength=K + 1).tolist(),
+             "end_hist": torch.bincount(end.cpu(), minlength=4).tolist(), "calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2",
+             "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, rnd in rows]
+
+
 GROUP_LIGHTS = 4  # the builder's one light and three more (measure_groups)
 _GROUP_ACCELS = {}  # scene name -> (the accels rebuilt per group, their build's wall-clock ms): built once, whatever --repeats says
 
@@ -898,7 +996,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -907,8 +1005,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -932,7 +1030,9 @@ def main():
                 got += measure_layers(name, builder, args.size, max(args.calls, 4))
             if "groups" in want:
                 got += measure_groups(name, builder, args.size, max(args.calls, 3))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups"}:
+            if "paths" in want:
+                got += measure_paths(name, builder, args.size, max(args.calls, 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
