@@ -250,6 +250,18 @@ pub struct Paths<'a> {
     pub last: Option<&'a mut [[f64; 6]]>,
     pub medium: Option<&'a mut [u32]>,
 }
+pub use sys::lg_scatter_out as ScatterOut;
+/// The planes `Accel::scatter` fills, one row per ray: `None` = not asked for; not all seven.
+#[derive(Default)]
+pub struct Scatter<'a> {
+    pub hits: Option<&'a mut [sys::lg_hit]>,
+    pub direct: Option<&'a mut [[f64; 3]]>,
+    pub flags: Option<&'a mut [u32]>,
+    pub reflect: Option<&'a mut [[f64; 6]]>,
+    pub reflect_weight: Option<&'a mut [[f64; 3]]>,
+    pub refract: Option<&'a mut [[f64; 6]]>,
+    pub refract_weight: Option<&'a mut [[f64; 5]]>,
+}
 pub use sys::lg_gather_out as GatherOut;
 /// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
 /// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
@@ -504,6 +516,37 @@ impl<'s> Accel<'s> {
         if sys::lg_trace_paths_device(self.ptr, dev_rays, n, max_bounces, rules.as_ptr(), rules.len(), normal, dev_start_medium, dev_out, hip_stream) != 0 {
             panic!("lasgun: {}", last_error())
         }
+    }
+    /// Surface scatter (`lg_scatter`): one level of li()'s tree, opened.  Row i of every plane given belongs to ray i: hits = `intersect`'s
+    /// record, direct = the lights in order + ambient at a hit (the background li() returns at a miss), flags = `sys::LG_SCATTER_*`,
+    /// reflect / refract = the specular children's rays, reflect_weight = the reflected child's spectrum, refract_weight = spectrum[3],
+    /// |wi . ns|, pdf; an absent child's elements are +0.0.  li() to a depth of the caller's is
+    /// (direct + reflect_weight * L(reflect)) + ((spectrum * L(refract)) * cos) / pdf, level by level; the scene's own depth plays no part.
+    pub fn scatter(&self, rays: &[[f64; 6]], out: Scatter) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_scatter_out>() == 56);
+        let n = rays.len();
+        assert!(out.hits.as_ref().map_or(true, |p| p.len() == n) && out.direct.as_ref().map_or(true, |p| p.len() == n)
+                && out.flags.as_ref().map_or(true, |p| p.len() == n) && out.reflect.as_ref().map_or(true, |p| p.len() == n)
+                && out.reflect_weight.as_ref().map_or(true, |p| p.len() == n) && out.refract.as_ref().map_or(true, |p| p.len() == n)
+                && out.refract_weight.as_ref().map_or(true, |p| p.len() == n),
+                "scatter: every plane has rays.len() rows");
+        let o = sys::lg_scatter_out {
+            hits: out.hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            direct: out.direct.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            flags: out.flags.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            reflect: out.reflect.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            reflect_weight: out.reflect_weight.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            refract: out.refract.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            refract_weight: out.refract_weight.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+        };
+        if unsafe { sys::lg_scatter(self.ptr, rays.as_ptr() as *const f64, n, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `scatter` for rays in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `scatter` states (the library checks what HIP can tell it).
+    pub unsafe fn scatter_device(&self, dev_rays: *const f64, n: usize, dev_out: &sys::lg_scatter_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_scatter_device(self.ptr, dev_rays, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     /// Radiance along every ray (origin xyz, direction xyz): what the reference's `integrate` leaves for a pixel whose one sample is that
     /// ray (integrate.rs:16-20, 23-132) -- lights, shadows, ambient, specular recursion, background on a miss --, f64 RGB before quantisation.

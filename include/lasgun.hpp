@@ -315,6 +315,36 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
                             const lg_paths_out &dev_out, void *hip_stream) const {
         if (lg_trace_paths_device(h_, dev_rays, n, max_bounces, rules.data(), rules.size(), normal, dev_start_medium, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // surface scatter (lg_scatter): one level of li()'s tree, opened -- row i of every plane asked for (a null member is not asked for; not
+    // all seven) belongs to ray i: hits = lg_intersect's record, direct = the lights in order + ambient at a hit (the background li() returns
+    // at a miss), flags = LG_SCATTER_HIT | LG_SCATTER_REFLECT | LG_SCATTER_REFRACT, reflect / refract = the specular children's rays,
+    // reflect_weight = the reflected child's spectrum, refract_weight = spectrum[3], |wi . ns|, pdf; an absent child's elements are +0.0.
+    // li() to a depth of the caller's is (direct + reflect_weight * L(reflect)) + ((spectrum * L(refract)) * cos) / pdf, level by level
+    struct Scatter {
+        std::vector<lg_hit> *hits = nullptr;                        // [rays]
+        std::vector<std::array<double, 3>> *direct = nullptr;
+        std::vector<uint32_t> *flags = nullptr;
+        std::vector<std::array<double, 6>> *reflect = nullptr;
+        std::vector<std::array<double, 3>> *reflect_weight = nullptr;
+        std::vector<std::array<double, 6>> *refract = nullptr;
+        std::vector<std::array<double, 5>> *refract_weight = nullptr;
+    };
+    void scatter(const std::vector<std::array<double, 6>> &rays, const Scatter &out) const {
+        static_assert(sizeof(lg_scatter_out) == 56, "lg_scatter_out: seven pointers");
+        const size_t n = rays.size();
+        lg_scatter_out o{};
+        if (out.hits) { out.hits->assign(n, lg_hit{}); o.hits = out.hits->data(); }
+        if (out.direct) { out.direct->assign(n, {0.0, 0.0, 0.0}); o.direct = n ? (*out.direct)[0].data() : nullptr; }
+        if (out.flags) { out.flags->assign(n, 0u); o.flags = out.flags->data(); }
+        if (out.reflect) { out.reflect->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.reflect = n ? (*out.reflect)[0].data() : nullptr; }
+        if (out.reflect_weight) { out.reflect_weight->assign(n, {0.0, 0.0, 0.0}); o.reflect_weight = n ? (*out.reflect_weight)[0].data() : nullptr; }
+        if (out.refract) { out.refract->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.refract = n ? (*out.refract)[0].data() : nullptr; }
+        if (out.refract_weight) { out.refract_weight->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0}); o.refract_weight = n ? (*out.refract_weight)[0].data() : nullptr; }
+        if (lg_scatter(h_, rays.empty() ? nullptr : rays[0].data(), n, &o)) throw Error(lg_last_error());
+    }
+    void scatter_device(const double *dev_rays, size_t n, const lg_scatter_out &dev_out, void *hip_stream) const {
+        if (lg_scatter_device(h_, dev_rays, n, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<std::array<double, 3>> out(rays.size());

@@ -1024,6 +1024,76 @@ int lg_radiance_groups(const lg_accel *, const double *rays, size_t n, const lg_
                        double *radiance);                                   /* host arrays; synchronous */
 int lg_radiance_groups_device(const lg_accel *, const double *dev_rays, size_t n, const lg_light_group *groups /* host */, size_t n_groups,
                               double *dev_radiance, void *hip_stream);
+/* Surface scatter: one level of li()'s tree, opened -- for each ray its hit, the light and ambient sum at it, and the two specular
+ * children with the factors the render multiplies their li by.  For an integrator of one's own over the render's own materials:
+ * per-bounce AOVs (direct, first reflection, first refraction), a recursion depth chosen per call or per ray, Russian roulette, a path
+ * tracer in torch over lasgun's plastic, metal and glass, a debugger that shows why a pixel is the colour it is -- without restating
+ * the shading, which could never match bit for bit: the shading frame's tangents are in no record the library returns.  lg_trace_paths
+ * is a chain with the caller's rules; this is the render's own tree, one level at a time.  An EXTRA; no counterpart in the reference.
+ * Rays: ray i is 6 doubles as for lg_intersect; any f64 is accepted as it is.
+ * hits[i] is lg_intersect's record of ray i, bit for bit, exact ties included, in the accel's traversal mode exactly as for the other
+ * queries (reference, pruned, LDS-resident scene, fast mode); no switch of its own.
+ * For a hit (kind != 0), with sh the render's shading record of it (p, ng, ns, the tangent ss, wo = -normalize(d)):
+ *   direct[i] = the sum over the scene's lights, in lg_scene_add_point_light order from zero, of the visible lights' terms, then the
+ *     ambient term added last (integrate.rs:47-67): the value the render's shade pass computes before any child is added.  A light is
+ *     visible by the render's shadow test: the segment from p + ng*(2^-52 * 2^16) to the light is walked any-hit and the light counts iff
+ *     !(t < 1.0).  The walk is the render's own shadow pass, shadow-skip included.
+ *   The children are what the render's shade pass makes at a depth below the maximum (integrate.rs:69-77), whatever depth the accel
+ *   has: only glass and mirror materials have any; the transmitted child exists iff the BSDF samples one and
+ *   !(pdf <= 0 || spectrum == 0 || |wi . ns| == 0), the reflected child iff the BSDF samples one and
+ *   !(pdf <= 0 || spectrum == 0 || wi . ns <= 0).  flags[i] = LG_SCATTER_HIT | LG_SCATTER_REFLECT and / or LG_SCATTER_REFRACT.
+ *   reflect[i] = origin p + ng*(2^-52 * 2^16), direction -wo + 2 (wo . ns) ns (f64, nothing fused); reflect_weight[i] = the sample's
+ *     spectrum (integrate.rs:103).
+ *   refract[i] = origin p - ng*(2^-52 * 2^16) (= p - ng*2^-36), direction the sample's wi; refract_weight[i] = spectrum[3], |wi . ns|,
+ *     pdf (integrate.rs:129).  These are the eight doubles the render parks per hit for its combine pass, and the six per child it
+ *     appends to the next level's rays, the same bits.
+ * For a miss: hits[i] is lg_intersect's miss record, direct[i] = background(normalize(d)) -- the value li() returns --, flags[i] = 0.
+ * An absent child's ray and weight elements are +0.0.
+ * The scene's max_recursion_depth plays no part: the same scene built at two depths gives the same bytes.
+ * Composition -- what makes the planes usable.  With D a depth of the caller's choosing, + and * componentwise in f64, nothing fused:
+ *   L(ray, d) = direct                                   for a miss;
+ *             = (direct + 0) + 0                         for a hit with d == D;
+ *             = (direct + R) + T                         otherwise, with
+ *       R = reflect_weight * L(reflect, d+1), or +0 if the child is absent,
+ *       T = ((spectrum * L(refract, d+1)) * cos) / pdf, or +0 if absent  (cos, pdf: refract_weight[3], [4]).
+ *   (0 + L(ray, 0)) * 1.0 is lg_radiance's value for that ray on an accel of the same scene built at max_recursion_depth D, bit for bit
+ *   (the sum from zero and the product by one are the reference's pixel sum of one sample; they turn a -0.0 into +0.0).  A scene
+ *   without glass or mirror has no children at any depth.
+ * NaNs: where an input makes the hit's geometry NaN (a ray with a NaN or infinite component, a degenerate primitive), an element that
+ * is NaN in the render's own arithmetic is SOME NaN here: its sign and payload are not part of the contract (IEEE leaves open which
+ * of two NaNs an operation returns, and the compiler may order commutative operands differently per kernel).  Every finite element,
+ * every +-INF and every zero's sign is bit for bit.
+ * Every element of every plane asked for is written, whatever the buffers held before, by exactly one lane: no atomics, no pre-fill.
+ * lg_accel_set_query_order(1) is honoured exactly as lg_radiance honours it: the chunks are cut from the sorted order of the GIVEN
+ * rays, every answer lands in its own ray's rows, the same bytes as order 0 (a query of 64 rays or fewer is walked as given).
+ * Shared with lg_radiance: always the level-by-level pipeline, as a chain of one level; the LASGUN_WF_BUDGET_MB chunks (a chunk parks
+ * its hits' frames and visibility words; the planes are the caller's); lg_profile_* credit its kernels as a render's (closest 0,
+ * shadow 2, the emit pass 3).
+ * Limits and errors, as for lg_hit_layers: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors
+ * (non-zero, lg_last_error, nothing launched, no output touched), for n > 0: n > (2^32 - 1) * 64, and n > 2^32 - 1 with the sorted
+ * order; a plane's byte size that does not fit size_t; a NULL accel, rays or out; all seven planes NULL; a scene with more than 32
+ * lights (lg_radiance's refusal; the accel's recursion depth is never a reason to refuse); in the device form also a pointer that is
+ * not device memory of the accel's device or is misaligned (rays 8 bytes; hits 16; direct, reflect, reflect_weight, refract and
+ * refract_weight 8; flags 4), or a buffer that ends beyond its allocation.
+ * Device form: dev_out is a HOST struct of device pointers; it only enqueues on hip_stream, with lg_radiance_device's exceptions
+ * (growing the chunk's arrays, the sort's scratch); one stream at a time per accel.  Host form (synchronous): the rays go up, the planes
+ * come back into staging and are copied out at the end, so an error on the way leaves the caller's arrays as they were.
+ * Out of scope: the visibility word as a plane; BSDF evaluation for a caller-supplied wi; non-specular sampling; a multi-device split;
+ * re-packing of lanes (the emit pass runs over the render's hit queue as it is). */
+#define LG_SCATTER_HIT     1u   /* the ray hit a surface: hits[i].kind != 0 */
+#define LG_SCATTER_REFLECT 2u   /* the reflected child is present */
+#define LG_SCATTER_REFRACT 4u   /* the transmitted child is present */
+typedef struct lg_scatter_out {
+    lg_hit   *hits;            /* [n]     lg_intersect's record of ray i */
+    double   *direct;          /* [n][3]  hit: lights in order + ambient (integrate.rs:47-67); miss: the background li() returns */
+    uint32_t *flags;           /* [n]     LG_SCATTER_HIT 1, LG_SCATTER_REFLECT 2, LG_SCATTER_REFRACT 4 */
+    double   *reflect;         /* [n][6]  the reflected child's ray */
+    double   *reflect_weight;  /* [n][3]  its spectrum (integrate.rs:103) */
+    double   *refract;         /* [n][6]  the transmitted child's ray */
+    double   *refract_weight;  /* [n][5]  spectrum[3], |wi . ns|, pdf (integrate.rs:129) */
+} lg_scatter_out;              /* 56 bytes; each pointer may be NULL, all NULL is an error */
+int lg_scatter(const lg_accel *, const double *rays, size_t n, const lg_scatter_out *out);           /* host arrays; synchronous */
+int lg_scatter_device(const lg_accel *, const double *dev_rays, size_t n, const lg_scatter_out *dev_out, void *hip_stream);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

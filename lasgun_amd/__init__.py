@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -105,6 +105,7 @@ _EXTRA = {
     **RANGE_SCAN_SIGNATURES,
     **HIT_LAYERS_SIGNATURES,
     **PATHS_SIGNATURES,
+    **SCATTER_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -142,6 +143,10 @@ PATH_ABSORB, PATH_REFLECT, PATH_PASS, PATH_REFRACT = 0, 1, 2, 3                 
 PATH_END_CUT, PATH_END_ESCAPED, PATH_END_ABSORBED, PATH_END_DEGENERATE = 0, 1, 2, 3  # LG_PATH_END_*: lg_paths_out::end
 PATH_RULE_DTYPE = _np.dtype([("action", _np.uint32), ("reserved", _np.uint32), ("ior", _np.float64), ("gain", _np.float64)])  # lg_path_rule
 assert PATH_RULE_DTYPE.itemsize == 24
+assert _C.sizeof(CScatterOut) == 56, "lg_scatter_out is 56 bytes"
+SCATTER_PLANES = ("hits", "direct", "flags", "reflect", "reflect_weight", "refract", "refract_weight")  # lg_scatter_out's members, in its order
+_SCATTER_SHAPE = {"hits": ((), HIT_DTYPE), "direct": ((3,), _np.float64), "flags": ((), _np.uint32), "reflect": ((6,), _np.float64),
+                  "reflect_weight": ((3,), _np.float64), "refract": ((6,), _np.float64), "refract_weight": ((5,), _np.float64)}  # (trailing shape, dtype) per ray
 assert _C.sizeof(CGatherOut) == 16, "lg_gather_out is 16 bytes"
 GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
 GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
@@ -893,6 +898,46 @@ class HipApi(Api):
                      int(normal), _C.c_void_p(sm) if sm is not None else None, _C.addressof(f), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- surface scatter (include/lasgun_hip.h, lg_scatter*): one level of li()'s tree, opened
+    def scatter(self, accel, rays, planes=SCATTER_PLANES, into=None):
+        """One level of li()'s tree for every ray of an (n, 6) float64 array: a dict of the planes asked for (any of SCATTER_PLANES), each
+        indexed by the ray -- HIT_DTYPE (n,) hits = lg_intersect's record, float64 (n, 3) direct = the lights in order + ambient at a hit,
+        the background li() returns at a miss, uint32 (n,) flags = SCATTER_HIT | SCATTER_REFLECT | SCATTER_REFRACT, float64 (n, 6) reflect
+        and refract = the specular children's rays, (n, 3) reflect_weight = the reflected child's spectrum, (n, 5) refract_weight =
+        spectrum[3], |wi . ns|, pdf.  An absent child's elements are +0.0.  li() to depth D is
+        (direct + reflect_weight * L(reflect)) + (refract_weight[:3] * L(refract)) * cos / pdf, bottomed out by direct alone; the scene's
+        own max_recursion_depth plays no part.  `into`: a dict of C-contiguous arrays of those shapes, written in place.  Also
+        `accel.scatter(rays, planes=...)`."""
+        r = self._rays(rays)
+        n = r.shape[0]
+        planes = tuple(planes)
+        if any(p not in SCATTER_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (SCATTER_PLANES,))
+        out = {}
+        for p in planes:
+            tail, dt = _SCATTER_SHAPE[p]
+            shape = (n,) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CScatterOut(*[data(out.get(p)) for p in SCATTER_PLANES])
+        if self.call("scatter", accel.h, data(r), n, _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def scatter_device(self, accel, n, rays_ptr, hits_ptr=None, direct_ptr=None, flags_ptr=None, reflect_ptr=None, reflect_weight_ptr=None, refract_ptr=None,
+                       refract_weight_ptr=None, stream=None):
+        """Enqueue the scatter of n rays (device memory, 6 doubles each) into device memory, n rows each: hits_ptr (lg_hit, 16-byte aligned),
+        direct_ptr (3 f64), flags_ptr (u32), reflect_ptr and refract_ptr (6 f64), reflect_weight_ptr (3 f64), refract_weight_ptr (5 f64); each
+        may be None, not all.  The pointers are integers (torch: tensor.data_ptr()) or objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CScatterOut(*[ptr(p) for p in (hits_ptr, direct_ptr, flags_ptr, reflect_ptr, reflect_weight_ptr, refract_ptr, refract_weight_ptr)])
+        rays = ptr(rays_ptr)
+        if self.call("scatter_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- radiance gathers (include/lasgun_hip.h, lg_radiance_gather*): li() along K shared directions from N poses, reduced per pose
     @staticmethod
     def _gather_lanes(lanes):
@@ -1494,6 +1539,7 @@ api.Accel.open_directions = lambda self, points, dirs, normals=None, counts=Fals
 api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range",), lanes=0: api.range_scan(self, origins, beams, frames, planes, lanes)  # accel.range_scan(origins, beams)
 api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
 api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
+api.Accel.scatter = lambda self, rays, planes=SCATTER_PLANES: api.scatter(self, rays, planes)  # accel.scatter(rays)
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):
     """The wrapper's one convention of a rule table for trace_paths: glass refracts with its eta, mirror and metal reflect, the rest `default`."""
     return api.path_rules(accel, default, gain)

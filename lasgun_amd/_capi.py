@@ -185,6 +185,14 @@ PATHS_SIGNATURES = {
     "trace_paths_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# Surface scatter (include/lasgun_hip.h, lg_scatter / lg_scatter_device): one level of li()'s tree, opened -- the hit, the light and ambient
+# sum at it and the two specular children with their weights, as planes indexed by the ray; the GPU library's alone.
+SCATTER_SIGNATURES = {
+    "scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "scatter_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT = 1, 2, 4  # LG_SCATTER_*: lg_scatter_out::flags
+
 # Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
 # directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
 GATHER_SIGNATURES = {
@@ -254,6 +262,11 @@ class CPathRule(C.Structure):  # lg_path_rule: 24 bytes; action = LG_PATH_*, res
 class CPathsOut(C.Structure):  # lg_paths_out: nine pointers, 72 bytes; NULL = not asked for
     _fields_ = [("hits", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p), ("along", C.c_void_p), ("count", C.c_void_p), ("end", C.c_void_p),
                 ("gain", C.c_void_p), ("last", C.c_void_p), ("medium", C.c_void_p)]
+
+
+class CScatterOut(C.Structure):  # lg_scatter_out: seven pointers, 56 bytes; NULL = not asked for
+    _fields_ = [("hits", C.c_void_p), ("direct", C.c_void_p), ("flags", C.c_void_p), ("reflect", C.c_void_p), ("reflect_weight", C.c_void_p),
+                ("refract", C.c_void_p), ("refract_weight", C.c_void_p)]
 
 
 class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for

@@ -419,6 +419,21 @@ struct GroupArgs : RadianceArgs {
     DLightGroup groups[MAX_LIGHT_GROUPS];
 };
 
+// Surface scatter (k_scatter.hip; lg_scatter*): ONE level of li()'s tree, opened -- the same query's level 0 run as a one-level chain whose
+// closest pass writes the hit records and the misses' planes and whose emit pass, in the shade pass's place, writes the hits' planes at the
+// ray's own index.  Every plane may be nullptr (`radiance` is not used).  These are the caller's arrays: nothing is parked.
+struct ScatterArgs : RadianceArgs {
+    void *hits;                // [n] lg_hit, written as 6 x uint4 each, as k_query.hip writes one
+    double *direct;            // [n][3]
+    uint32_t *flags;           // [n] SCATTER_*
+    double *reflect;           // [n][6]
+    double *reflect_weight;    // [n][3]
+    double *refract;           // [n][6]
+    double *refract_weight;    // [n][5]
+    const uint32_t *tri_base;  // per accel: its mesh's first triangle in the triangle tables (lg_hit::prim of a triangle)
+};
+constexpr uint32_t SCATTER_HIT = 1u, SCATTER_REFLECT = 2u, SCATTER_REFRACT = 4u; // == LG_SCATTER_*
+
 // A radiance gather's level 0 (k_gather.hip; lg_radiance_gather*), beside the DParams of its chunk: the two tables the rays are made from,
 // where li goes, and where the chunk starts.  A batch of a call is a call of its own here: its poses' tables, its own li.
 struct GatherArgs {

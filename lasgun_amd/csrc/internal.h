@@ -59,6 +59,11 @@ hipError_t launch_rf_shade(const DParams &P, const FilmArgs &Q, uint32_t blocks,
 hipError_t launch_rf_combine(const DParams &P, const FilmArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rf_resolve(const FilmArgs &Q, const double *li, unsigned long long slots, uint32_t samples, uint32_t blocks, hipStream_t stream);
 hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
+// k_scatter.hip: surface scatter (lg_scatter*; launch.cpp, enqueue_scatter) -- level 0 as a chain of one level: the closest pass over the
+// query's rays (it writes the hit records and the misses' planes) and, in the shade pass's place, the emit pass (the hits' planes)
+hipError_t launch_scatter_closest(const DParams &P, const ScatterArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_scatter_emit(const DParams &P, const ScatterArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t scatter_set_lds_limit(size_t bytes, bool ldss);
 // k_light_groups.hip: light groups (lg_radiance_groups*; launch.cpp, enqueue_radiance_groups) -- the radiance query's level-0 closest pass with
 // a GroupArgs, and the shade and combine passes of EVERY level (P.wf_level) carrying Q.n_groups planes; the spread pass of the deepest level
 hipError_t launch_lg_closest(const DParams &P, const GroupArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
@@ -582,6 +587,8 @@ void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *r
 // One checked lg_radiance_groups* call: `groups` is the host table of n_groups entries (it travels by value in every launch's arguments)
 void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, const DLightGroup *groups, uint32_t n_groups, double *radiance, const uint32_t *perm,
                              lg_accel::LaunchCtx &c, hipStream_t stream);
+// One checked lg_scatter* call: Q's planes are the caller's device arrays (rays, perm, n, base and tri_base are set here)
+void enqueue_scatter(const lg_accel &a, const double *rays, size_t n, ScatterArgs Q, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream);
 // One checked lg_radiance_gather* call on device tables (query.cpp; gather_host.h): batch_poses = n_poses where radiance is given

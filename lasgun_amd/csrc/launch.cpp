@@ -509,6 +509,7 @@ struct Level0Call {
     uint32_t w = 1, h = 1;             // the film size the chunks' DParams are made for (views alone)
     uint32_t samples_root = 1;         // (the scene's camera may be supersampled; a query is not, and a view batch has its own samples_root)
     uint32_t planes = 1;               // planes of li per ray of every level (light groups alone: > 1)
+    bool one_level = false;            // the chain is level 0 alone whatever depth the scene has (surface scatter: no children are followed, no combine)
     const char *label = "";            // what LASGUN_DEBUG calls the query ...
     std::string note;                  // ... and how it ends its line (a query's rays: the order they are walked in)
 };
@@ -518,6 +519,7 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Call &call, BIND
     P0.ss_root = call.samples_root;
     const uint32_t S = P0.ss_root * P0.ss_root; // level-0 work items per pixel
     P0.ntiles = call.tiles;
+    if (call.one_level) P0.recursion = 0; // (levels_of: 1 -- the plan, the carve and P.wf_levels all follow from it; no level-by-level kernel reads P.recursion)
     const uint32_t levels = levels_of(a, P0);
     ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, call.planes));
     WfChunk K(plan, call.planes);
@@ -593,6 +595,27 @@ void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *r
 void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, const DLightGroup *groups, uint32_t n_groups, double *radiance, const uint32_t *perm,
                              lg_accel::LaunchCtx &c, hipStream_t stream) {
     enqueue_ray_query(a, rays, n, radiance, nullptr, groups, n_groups, perm, "radiance groups", c, stream);
+}
+// Surface scatter (query.cpp, lg_scatter*; the call checked there and in scatter_host.h): the same rays as level 0's source of a chain of ONE
+// level (Level0Call::one_level) whatever the scene's depth -- the closest pass and, in the shade pass's place, the emit pass are
+// k_scatter.hip's, the shadow pass between them is the render's.  The chunks are the pipeline's own: a chunk parks the hit queue, the frame
+// and the visibility words of its rays; the planes are the caller's, indexed by the ray.  With one level there is no combine pass to bind.
+void enqueue_scatter(const lg_accel &a, const double *rays, size_t n, ScatterArgs Q, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    Level0Call call;
+    call.tiles = (uint32_t)((n + 63) / 64);
+    call.label = "surface scatter";
+    call.note = perm ? "sorted order" : "as given";
+    call.one_level = true;
+    static_cast<RadianceArgs &>(Q) = RadianceArgs{rays, nullptr, perm, (unsigned long long)n, 0ull};
+    Q.tri_base = a.accel_tri_base.p;
+    enqueue_level0_query(a, call, [&](unsigned long long t0) {
+        Q.base = t0 * 64ull;
+        Level0 l0;
+        l0.q = &Q;
+        l0.closest_ = l0_closest<ScatterArgs, launch_scatter_closest>;
+        l0.shade_ = l0_flat<ScatterArgs, launch_scatter_emit>;
+        return l0;
+    }, c, stream);
 }
 // A radiance gather (query.cpp, lg_radiance_gather*; the call checked there and in gather_host.h): batch after batch of g.batch_poses whole
 // consecutive poses, each a level-0 query of its own over the batch's tiles -- its poses' rows of the tables, its own li -- with the

@@ -63,6 +63,11 @@ __device__ __forceinline__ void rq_finish(const FilmArgs &Q, unsigned long long 
     film_store(Q, off, l0_finished(value));
 }
 
+// A hook of the closest pass for a source that wants the hit itself (k_scatter.hip: t, kind, prim and instance are known only here): called by
+// every lane that hit, behind its frame's stores.  Empty for every source that does not overload it for its own type -- their kernels are
+// the code they were (profiles/r22_kernel_resources_diff.txt).
+template <class SRC> __device__ __forceinline__ void l0_closest_hit(const SRC &, const DParams &, const typename SRC::Item &, const Best &, const Shade &) {}
+
 // W1 of level 0 (wf_trace_kernel<FAST, false, LDSS, true, PRUNE>)
 template <bool FAST, bool LDSS, bool PRUNE, class SRC>
 __device__ __forceinline__ void l0_closest_body(const DParams &P, const SRC src) {
@@ -124,6 +129,7 @@ __device__ __forceinline__ void l0_closest_body(const DParams &P, const SRC src)
             f[6 * n] = sh.ns.x; f[7 * n] = sh.ns.y; f[8 * n] = sh.ns.z;
             f[9 * n] = sh.ss.x; f[10 * n] = sh.ss.y; f[11 * n] = sh.ss.z;
             f[12 * n] = (double)sh.mat;
+            l0_closest_hit(src, P, it, b, sh);
         } else if (active) { // integrate.rs:26-28
             const V3 value = background(P, normalize(ray.d));
             if (P.wf_levels == 1u) src.finish(P, it, i, value);

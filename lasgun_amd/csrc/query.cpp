@@ -2,7 +2,8 @@
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
 // k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
-// lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance).  With
+// lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
+// alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
 // lg_layers_out / lg_paths_out / lg_features is, is scan_host.h's / layers_host.h's / paths_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
@@ -14,6 +15,7 @@
 #include "gather_host.h"
 #include "layers_host.h"
 #include "paths_host.h"
+#include "scatter_host.h"
 #include "light_groups_host.h"
 #include "scan_host.h"
 #include "views_host.h"
@@ -896,6 +898,50 @@ extern "C" int lg_trace_paths_device(const lg_accel *a, const double *dev_rays, 
         if (dev_start_medium) check_device_buffer(*a, dev_start_medium, n * sizeof(uint32_t), 4, "start_medium");
         path_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
         enqueue_trace_paths(*a, dev_rays, n, max_bounces, rules, n_rules, normal, dev_start_medium, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- surface scatter (lg_scatter*; launch.cpp, enqueue_scatter; k_scatter.hip): one level of li()'s tree, opened -- the hit, the light and
+// ambient sum at it and the two specular children with their weights, as planes indexed by the ray.  What needs no device -- the limits,
+// the sizes, the NULL and alignment rules, the light count's refusal, the staging -- is scatter_host.h's.
+static_assert(SCATTER_HIT == LG_SCATTER_HIT && SCATTER_REFLECT == LG_SCATTER_REFLECT && SCATTER_REFRACT == LG_SCATTER_REFRACT, "dscene.h restates the contract's flags");
+// One call enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers)
+static void enqueue_scatter_query(const lg_accel &a, const double *rays, size_t n, const lg_scatter_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream);
+    ScatterArgs Q{};
+    Q.hits = out.hits; Q.direct = out.direct; Q.flags = out.flags;
+    Q.reflect = out.reflect; Q.reflect_weight = out.reflect_weight; Q.refract = out.refract; Q.refract_weight = out.refract_weight;
+    enqueue_scatter(a, rays, n, Q, perm, c, stream);
+}
+// Host form: the rays go up, the planes come back into staging and are copied out at the end
+extern "C" int lg_scatter(const lg_accel *a, const double *rays, size_t n, const lg_scatter_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_scatter(a, rays, n, out, a ? a->flat.lights.size() : 0);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        RoundTrip trip(*a);
+        ScatterStaging st(*out, n);
+        const double *drays = trip.in(rays, n * 6);
+        lg_scatter_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        scatter_planes(dev, n, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        trip.run([&] { enqueue_scatter_query(*a, drays, n, dev, a->stream); });
+        place_scatter(*out, st);
+    });
+}
+extern "C" int lg_scatter_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_scatter_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_scatter(a, dev_rays, n, dev_out, a ? a->flat.lights.size() : 0);
+        check_scatter_alignment(dev_rays, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        scatter_planes(*dev_out, n, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        enqueue_scatter_query(*a, dev_rays, n, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

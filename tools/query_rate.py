@@ -69,11 +69,15 @@ them; Y's planes are checked against L's bytes.  These rows time --calls calls a
 Ray paths (lg_trace_paths_device) -- --rows paths (not part of "all"): the camera's rays of a --size^2 film, 8 bounces, glass refracts and
 everything else reflects.  Row P8: one call, point + id + count + end.  Row Z8: the route without it -- 8 rounds of lg_intersect_device with
 the next rays formed and the live rays compacted by torch on the same stream -- into the same planes, checked against P8's bytes.
+Surface scatter (lg_scatter_device) -- --rows scatter (not part of "all"): the camera's rays of a --size^2 film.  Row R0: lg_radiance_device on the
+scene rebuilt at depth 0, the floor (the same closest and shadow passes, 24 bytes a ray).  Rows S2 / S7: direct + flags / all seven planes, with
+what they cost over the floor in ms and per byte written.  Row CD: li() composed to the scene's own depth over the device form with torch, against
+row RD, one lg_radiance_device call (measure_scatter).
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -967,6 +971,83 @@ def measure_groups(name, builder, size, calls):
              "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)} for row, ms, p, x_ in rows]
 
 
+def measure_scatter(name, builder, size, calls):
+    """Surface scatter on the camera's rays of a size^2 film.  Row R0, the yardstick: lg_radiance_device on the same scene rebuilt at depth
+    0 -- the same closest and shadow passes, 24 bytes written a ray.  Row S2: lg_scatter_device, direct + flags (28 bytes a ray).  Row S7: all
+    seven planes (284 bytes a ray).  over_floor_ms = the row's ms minus R0's of the same repeat, ns_per_byte_over_floor = that over the bytes
+    the row writes beyond R0's 24 a ray.  Then the price of opening the tree: row CD, the composition to the scene's own depth D through the
+    device form with torch on the same stream (mask, compact, multiply, add per level), against row RD, ONE lg_radiance_device call on the scene
+    as it is; CD's value is compared with RD's bytes (same_bytes).  Timed R0, S2, S7, CD, RD, so --repeats alternates them."""
+    if not hasattr(G, "scatter_device"):
+        return []
+    accel = G.Accel.from_scene(builder(G))
+    flat_scene = builder(G)
+    flat_scene.set_max_recursion_depth(0)
+    flat = G.Accel.from_scene(flat_scene)
+    depth = int(builder(pyref.Api).recursion)
+    for a in (accel, flat):
+        G.set_query_order(a, 0)
+    assert G.camera_samples(accel) == 1
+    s = torch.cuda.current_stream().cuda_stream
+    n = size * size
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device="cuda")  # noqa: E731
+    rad, hits, direct, flags = f64(n, 3), torch.empty((n * 24,), dtype=torch.int32, device="cuda"), f64(n, 3), torch.empty((n,), dtype=torch.int32, device="cuda")
+    reflect, rw, refract, tw = f64(n, 6), f64(n, 3), f64(n, 6), f64(n, 5)
+
+    def L(r, d):
+        m = r.shape[0]
+        di, fl = f64(m, 3), torch.empty((m,), dtype=torch.int32, device="cuda")
+        if d == depth:
+            G.scatter_device(accel, m, r, direct_ptr=di, flags_ptr=fl, stream=s)
+            return torch.where(((fl & 1) != 0)[:, None], (di + 0.0) + 0.0, di)
+        cr, wr, ct, wt = f64(m, 6), f64(m, 3), f64(m, 6), f64(m, 5)
+        G.scatter_device(accel, m, r, direct_ptr=di, flags_ptr=fl, reflect_ptr=cr, reflect_weight_ptr=wr, refract_ptr=ct, refract_weight_ptr=wt, stream=s)
+        hit, has_r, has_t = (fl & 1) != 0, (fl & 2) != 0, (fl & 4) != 0
+        R, T = torch.zeros_like(di), torch.zeros_like(di)
+        ir, it = has_r.nonzero().squeeze(1), has_t.nonzero().squeeze(1)
+        if ir.numel():
+            R[ir] = wr[ir] * L(cr[ir].contiguous(), d + 1)
+        if it.numel():
+            w = wt[it]
+            T[it] = ((w[:, :3] * L(ct[it].contiguous(), d + 1)) * w[:, 3:4]) / w[:, 4:5]
+        return torch.where(hit[:, None], (di + R) + T, di)
+
+    composed = [None]
+
+    def compose():
+        composed[0] = (0.0 + L(rays, 0)) * 1.0
+
+    rows = []
+    ms = timed(lambda: G.radiance_device(flat, n, rays.data_ptr(), rad.data_ptr(), stream=s), calls, warmup=1)
+    floor = ms
+    rows.append(("R0: lg_radiance_device, the scene rebuilt at depth 0 (the floor)", ms, 24, None))
+    ms = timed(lambda: G.scatter_device(accel, n, rays, direct_ptr=direct, flags_ptr=flags, stream=s), calls, warmup=1)
+    rows.append(("S2: lg_scatter_device, direct + flags", ms, 28, None))
+    ms = timed(lambda: G.scatter_device(accel, n, rays, hits_ptr=hits, direct_ptr=direct, flags_ptr=flags, reflect_ptr=reflect, reflect_weight_ptr=rw, refract_ptr=refract,
+                                        refract_weight_ptr=tw, stream=s), calls, warmup=1)
+    rows.append(("S7: lg_scatter_device, all seven planes", ms, 284, None))
+    ms = timed(compose, max(calls // 4, 2), warmup=1)
+    got = composed[0]
+    ms_rd = timed(lambda: G.radiance_device(accel, n, rays.data_ptr(), rad.data_ptr(), stream=s), calls, warmup=1)
+    torch.cuda.synchronize()
+    rows.append(("CD: li() composed to depth %d over lg_scatter_device with torch" % depth, ms, None, {"depth": depth, "same_bytes": bool(torch.equal(got.view(torch.int64), rad.view(torch.int64)))}))
+    rows.append(("RD: lg_radiance_device, the scene as it is, one call", ms_rd, 24, {"depth": depth}))
+    out = []
+    for row, ms, nbytes, x_ in rows:
+        r = {"scene": name, "row": row, "film": [size, size], "rays": n, "ms": round(ms, 4), "mrays_per_s": round(n / ms / 1e3, 1), **(x_ or {})}
+        if nbytes is not None:
+            r["bytes_per_ray"] = nbytes
+        if row[:2] in ("S2", "S7"):
+            r["over_floor_ms"] = round(ms - floor, 4)
+            r["ns_per_byte_over_floor"] = round((ms - floor) * 1e6 / ((nbytes - 24) * n), 5)
+        r.update({"calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+                  "gpu": torch.cuda.get_device_name(0)})
+        out.append(r)
+    return out
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -996,7 +1077,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -1005,8 +1086,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1032,7 +1113,9 @@ def main():
                 got += measure_groups(name, builder, args.size, max(args.calls, 3))
             if "paths" in want:
                 got += measure_paths(name, builder, args.size, max(args.calls, 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths"}:
+            if "scatter" in want:
+                got += measure_scatter(name, builder, args.size, max(args.calls, 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
