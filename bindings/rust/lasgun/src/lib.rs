@@ -262,6 +262,16 @@ pub struct Scatter<'a> {
     pub refract: Option<&'a mut [[f64; 6]]>,
     pub refract_weight: Option<&'a mut [[f64; 5]]>,
 }
+pub use sys::lg_light as Light;
+pub use sys::lg_light_set as LightSet;
+pub use sys::lg_lit_out as LitOut;
+/// The planes `Accel::scatter_lit` fills: `scatter`'s seven, `terms` (rays * K rows) and `visible` (rays * ceil(K / 32) words); not all nine `None`.
+#[derive(Default)]
+pub struct ScatterLit<'a> {
+    pub scatter: Scatter<'a>,
+    pub terms: Option<&'a mut [[f64; 3]]>,
+    pub visible: Option<&'a mut [u32]>,
+}
 pub use sys::lg_gather_out as GatherOut;
 /// The work item a radiance gather of these counts would use (`lg_radiance_gather_lanes`): 1 direction lanes, 2 pose lanes; `lanes` 0 asks
 /// for the stated default (pose lanes iff n_poses >= n_dirs); -1 for a bad `lanes`.  No device is touched.
@@ -547,6 +557,48 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `scatter` states (the library checks what HIP can tell it).
     pub unsafe fn scatter_device(&self, dev_rays: *const f64, n: usize, dev_out: &sys::lg_scatter_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_scatter_device(self.ptr, dev_rays, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// Lit scatter (`lg_scatter_lit`): `scatter` under lights that come with the call.  `lights`: K records shared by every ray
+    /// (`per_ray` false) or rays.len() * K records, ray i's at i * K (`per_ray` true); `ambient` stands where the scene's ambient colour
+    /// stands; the scene's own lights play no part.  `terms[i * K + k]` is light k's own term of ray i's `direct` (+0.0 where it is not
+    /// added), bit k & 31 of `visible[i * W + (k >> 5)]`, W = ceil(K / 32), is set iff light k is visible from the hit.
+    pub fn scatter_lit(&self, rays: &[[f64; 6]], lights: &[Light], per_ray: bool, ambient: [f64; 3], out: ScatterLit) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_light>() == 72 && std::mem::size_of::<sys::lg_light_set>() == 40 && std::mem::size_of::<sys::lg_lit_out>() == 72);
+        let n = rays.len();
+        assert!(!per_ray || n == 0 || lights.len() % n == 0, "scatter_lit: a per-ray table holds rays.len() * K lights");
+        let k = if per_ray { if n == 0 { 0 } else { lights.len() / n } } else { lights.len() };
+        let w = (k + 31) / 32;
+        assert!(k <= sys::LG_MAX_CALL_LIGHTS as usize, "scatter_lit: at most LG_MAX_CALL_LIGHTS lights");
+        let sc = out.scatter;
+        assert!(sc.hits.as_ref().map_or(true, |p| p.len() == n) && sc.direct.as_ref().map_or(true, |p| p.len() == n)
+                && sc.flags.as_ref().map_or(true, |p| p.len() == n) && sc.reflect.as_ref().map_or(true, |p| p.len() == n)
+                && sc.reflect_weight.as_ref().map_or(true, |p| p.len() == n) && sc.refract.as_ref().map_or(true, |p| p.len() == n)
+                && sc.refract_weight.as_ref().map_or(true, |p| p.len() == n) && out.terms.as_ref().map_or(true, |p| p.len() == n * k)
+                && out.visible.as_ref().map_or(true, |p| p.len() == n * w),
+                "scatter_lit: every scatter plane has rays.len() rows, terms rays.len() * K, visible rays.len() * ceil(K / 32)");
+        let o = sys::lg_lit_out {
+            scatter: sys::lg_scatter_out {
+                hits: sc.hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+                direct: sc.direct.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+                flags: sc.flags.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+                reflect: sc.reflect.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+                reflect_weight: sc.reflect_weight.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+                refract: sc.refract.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+                refract_weight: sc.refract_weight.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            },
+            terms: out.terms.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            visible: out.visible.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+        };
+        let ls = sys::lg_light_set { lights: if lights.is_empty() { std::ptr::null() } else { lights.as_ptr() }, count: k as u32, per_ray: per_ray as u32, ambient };
+        if unsafe { sys::lg_scatter_lit(self.ptr, rays.as_ptr() as *const f64, n, &ls, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `scatter_lit` for rays in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for);
+    /// `lights.lights` is a HOST table when `per_ray` is 0 (staged by the call: it may be freed on return), device memory when it is 1
+    ///
+    /// # Safety
+    /// The pointers must be memory of the kinds and sizes `scatter_lit` states (the library checks what HIP can tell it).
+    pub unsafe fn scatter_lit_device(&self, dev_rays: *const f64, n: usize, lights: &sys::lg_light_set, dev_out: &sys::lg_lit_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_scatter_lit_device(self.ptr, dev_rays, n, lights, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     /// Radiance along every ray (origin xyz, direction xyz): what the reference's `integrate` leaves for a pixel whose one sample is that
     /// ray (integrate.rs:16-20, 23-132) -- lights, shadows, ambient, specular recursion, background on a miss --, f64 RGB before quantisation.

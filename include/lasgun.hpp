@@ -345,6 +345,40 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void scatter_device(const double *dev_rays, size_t n, const lg_scatter_out &dev_out, void *hip_stream) const {
         if (lg_scatter_device(h_, dev_rays, n, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // lit scatter (lg_scatter_lit): scatter() under lights that come with the call -- `lights` shared by every ray (per_ray false: K records)
+    // or a table per ray (per_ray true: rays.size() * K records, ray i's at i * K), `ambient` in the scene's ambient colour's place; the
+    // scene's own lights play no part.  Beside scatter()'s planes: terms = every light's own term of direct ([ray * K + k], +0.0 where it is
+    // not added), visible = ceil(K / 32) words a ray, bit k & 31 of word k >> 5 set iff light k is visible from the hit
+    struct ScatterLit {
+        Scatter scatter;
+        std::vector<std::array<double, 3>> *terms = nullptr;        // [rays * K]
+        std::vector<uint32_t> *visible = nullptr;                   // [rays * ceil(K / 32)]
+    };
+    void scatter_lit(const std::vector<std::array<double, 6>> &rays, const std::vector<lg_light> &lights, bool per_ray, const std::array<double, 3> &ambient,
+                     const ScatterLit &out) const {
+        static_assert(sizeof(lg_light) == 72 && sizeof(lg_light_set) == 40 && sizeof(lg_lit_out) == 72, "lg_light, lg_light_set, lg_lit_out");
+        const size_t n = rays.size();
+        if (per_ray && n && lights.size() % n) throw Error("scatter_lit: a per-ray table holds rays.size() * K lights");
+        const size_t K = per_ray ? (n ? lights.size() / n : 0) : lights.size(), W = (K + 31) / 32;
+        if (K > LG_MAX_CALL_LIGHTS) throw Error("scatter_lit: at most LG_MAX_CALL_LIGHTS lights");
+        const Scatter &sc = out.scatter;
+        lg_lit_out o{};
+        if (sc.hits) { sc.hits->assign(n, lg_hit{}); o.scatter.hits = sc.hits->data(); }
+        if (sc.direct) { sc.direct->assign(n, {0.0, 0.0, 0.0}); o.scatter.direct = n ? (*sc.direct)[0].data() : nullptr; }
+        if (sc.flags) { sc.flags->assign(n, 0u); o.scatter.flags = sc.flags->data(); }
+        if (sc.reflect) { sc.reflect->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.scatter.reflect = n ? (*sc.reflect)[0].data() : nullptr; }
+        if (sc.reflect_weight) { sc.reflect_weight->assign(n, {0.0, 0.0, 0.0}); o.scatter.reflect_weight = n ? (*sc.reflect_weight)[0].data() : nullptr; }
+        if (sc.refract) { sc.refract->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.scatter.refract = n ? (*sc.refract)[0].data() : nullptr; }
+        if (sc.refract_weight) { sc.refract_weight->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0}); o.scatter.refract_weight = n ? (*sc.refract_weight)[0].data() : nullptr; }
+        if (out.terms) { out.terms->assign(n * K, {0.0, 0.0, 0.0}); o.terms = n * K ? (*out.terms)[0].data() : nullptr; }
+        if (out.visible) { out.visible->assign(n * W, 0u); o.visible = out.visible->data(); }
+        const lg_light_set ls{lights.empty() ? nullptr : lights.data(), (uint32_t)K, per_ray ? 1u : 0u, {ambient[0], ambient[1], ambient[2]}};
+        if (lg_scatter_lit(h_, rays.empty() ? nullptr : rays[0].data(), n, &ls, &o)) throw Error(lg_last_error());
+    }
+    // ... on device memory: dev_out's planes are device pointers; lights.lights is a HOST table when shared, device memory when per ray
+    void scatter_lit_device(const double *dev_rays, size_t n, const lg_light_set &lights, const lg_lit_out &dev_out, void *hip_stream) const {
+        if (lg_scatter_lit_device(h_, dev_rays, n, &lights, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // radiance along every ray (lg_radiance): li() as the render computes it, f64 RGB before quantisation
     std::vector<std::array<double, 3>> radiance(const std::vector<std::array<double, 6>> &rays) const {
         std::vector<std::array<double, 3>> out(rays.size());

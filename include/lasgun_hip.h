@@ -1094,6 +1094,65 @@ typedef struct lg_scatter_out {
 } lg_scatter_out;              /* 56 bytes; each pointer may be NULL, all NULL is an error */
 int lg_scatter(const lg_accel *, const double *rays, size_t n, const lg_scatter_out *out);           /* host arrays; synchronous */
 int lg_scatter_device(const lg_accel *, const double *dev_rays, size_t n, const lg_scatter_out *dev_out, void *hip_stream);
+/* Lit scatter: lg_scatter under lights that come with the CALL.  lg_scatter's `direct` counts the at most 32 point lights the scene held
+ * when lg_accel_from ran; here the call brings K point lights (0 .. LG_MAX_CALL_LIGHTS), one table shared by every ray or a table per ray,
+ * and an ambient colour, and hands out every light's own term and the visibility bits beside the sum.  For what an integrator of one's own
+ * needs of the render's BSDF: area and environment lights as samples (a new set per call, or per vertex for next-event estimation: each
+ * ray brings its own), more than 32 lights, and a light that moves -- no scene and no accel is rebuilt, the closest-hit walks do not
+ * depend on the lights at all.  An EXTRA; no counterpart in the reference.
+ * Lights: lg_light is lg_scene_add_point_light's arguments (position, intensity, falloff[3]: constant, linear, quadratic), 72 bytes; any
+ * f64 is accepted as it is.  per_ray == 0: lights[count], shared by every ray; per_ray == 1: lights[n][count], ray i's lights at
+ * lights[i * count ..].  `ambient` stands where the scene's ambient colour stands.
+ * Scatter planes: hits, flags, reflect, reflect_weight, refract and refract_weight are lg_scatter's, bit for bit -- the traversal mode, the
+ * exact ties, the NaN rule and the +0.0 of an absent child all as there.  The scene's own lights and ambient colour play no part in any
+ * plane; a scene with more than 32 lights is accepted.
+ * For a hit, with sh the render's shading record, L_k ray i's light k, all arithmetic f64 with nothing fused:
+ *   light k is visible iff the any-hit walk of the segment from sh.p (= p + ng * 2^-36) with direction L_k.position - sh.p answers
+ *     !(t < 1.0): lg_occluded of that ray, negated;
+ *   term_k = mul_ew(PI * intensity, bsdf_f(..)) * wi_dot_n / f_att, the render's expression for a point light (integrate.rs:53-62), and it
+ *     is added iff the light is visible and f_att != 0.0;
+ *   direct[i] = the sequential sum over k = 0 .. K-1 from +0.0 of the added terms, then mul_ew(ambient, bsdf_f(.., ns, ..)) added last: on
+ *     an accel of the same scene rebuilt with exactly these lights and this ambient, lg_scatter's direct, the same bytes;
+ *   terms[i][k] = +0.0 + term_k where the term is added, +0.0 otherwise (the sum from zero turns a -0.0 into +0.0: the plane equals a
+ *     single-light group of lg_radiance_groups at depth 0);
+ *   visible[i][k >> 5] bit k & 31 is set iff light k is visible by the test above, whatever its f_att and whether or not its term could
+ *     matter; W = ceil(K / 32) words a ray; bits at or above K are 0.
+ * For a miss: direct[i] is the background, as lg_scatter's; its terms are +0.0 and its visible words 0.
+ * K == 0: no shadow pass runs, direct is the ambient term alone; terms and visible have no elements (their pointers are not looked at).
+ * Where `visible` is not asked for, the shadow pass may leave out the walk of a (hit, light) whose term cannot depend on it (the light is
+ * on the other side of the surface for the BSDF and PI * intensity is finite: the term is a zero either way; or f_att == 0): direct and
+ * terms are the same bytes with and without `visible`.
+ * Every element of every plane asked for is written, whatever the buffers held before, by exactly one lane: no atomics, no pre-fill.
+ * lg_accel_set_query_order(1) is honoured as lg_scatter honours it; a per-ray light row follows its ray's index, not its slot.  The
+ * LASGUN_WF_BUDGET_MB chunks are the pipeline's own (a chunk parks its hits' frames and W visibility words a hit); lg_profile_* credit the
+ * kernels as lg_scatter's (closest 0, shadow 2, the emit pass 3).
+ * Limits and errors: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors (non-zero,
+ * lg_last_error, nothing launched, no output touched), for n > 0: lg_scatter's own except the scene's light count; a NULL `lights`;
+ * count > LG_MAX_CALL_LIGHTS; per_ray not 0 or 1; count > 0 with a NULL table; all nine planes NULL (with K == 0: all seven scatter
+ * planes); n * K * 72, n * K * 24 or n * W * 4 that does not fit size_t; in the device form also a pointer that is not device memory of
+ * the accel's device, is misaligned (lg_scatter's; terms and a per-ray table 8 bytes, visible 4) or ends beyond its allocation.
+ * Device form: dev_out is a HOST struct of device pointers.  lights->lights is DEVICE memory when per_ray == 1 (it is as large as the
+ * rays); when per_ray == 0 it is a HOST table, staged into a table of the call's own on the stream: it may be freed on return.  It only
+ * enqueues on hip_stream, with lg_scatter_device's exceptions; one stream at a time per accel.  Host form (synchronous): everything is
+ * host memory; the planes come back into staging and are copied out at the end, so an error on the way leaves the caller's arrays as
+ * they were.
+ * Out of scope: lights for the other radiance entry points; emitters that are not points (the caller samples them: the emitter's cosine
+ * and pdf are applied to `terms` by the caller); sampling the lights on the device; a multi-device split. */
+#define LG_MAX_CALL_LIGHTS 1024u
+typedef struct lg_light { double position[3], intensity[3], falloff[3]; } lg_light;   /* 72 bytes: lg_scene_add_point_light's arguments */
+typedef struct lg_light_set {
+    const lg_light *lights;  /* per_ray == 0: [count], shared by every ray; per_ray == 1: [n][count], ray i's lights at lights[i*count ..] */
+    uint32_t count;          /* K, 0 .. LG_MAX_CALL_LIGHTS */
+    uint32_t per_ray;        /* 0 or 1 */
+    double ambient[3];       /* stands where the scene's ambient colour stands */
+} lg_light_set;              /* 40 bytes */
+typedef struct lg_lit_out {
+    lg_scatter_out scatter;  /* the seven planes of lg_scatter; `direct` is under the CALL's lights and ambient */
+    double   *terms;         /* [n][K][3] */
+    uint32_t *visible;       /* [n][W], W = ceil(K/32): bit k&31 of word k>>5 */
+} lg_lit_out;                /* 72 bytes; each pointer may be NULL, all nine NULL is an error */
+int lg_scatter_lit(const lg_accel *, const double *rays, size_t n, const lg_light_set *lights, const lg_lit_out *out);   /* host arrays; synchronous */
+int lg_scatter_lit_device(const lg_accel *, const double *dev_rays, size_t n, const lg_light_set *lights, const lg_lit_out *dev_out, void *hip_stream);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -106,6 +106,7 @@ _EXTRA = {
     **HIT_LAYERS_SIGNATURES,
     **PATHS_SIGNATURES,
     **SCATTER_SIGNATURES,
+    **LIT_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -147,6 +148,33 @@ assert _C.sizeof(CScatterOut) == 56, "lg_scatter_out is 56 bytes"
 SCATTER_PLANES = ("hits", "direct", "flags", "reflect", "reflect_weight", "refract", "refract_weight")  # lg_scatter_out's members, in its order
 _SCATTER_SHAPE = {"hits": ((), HIT_DTYPE), "direct": ((3,), _np.float64), "flags": ((), _np.uint32), "reflect": ((6,), _np.float64),
                   "reflect_weight": ((3,), _np.float64), "refract": ((6,), _np.float64), "refract_weight": ((5,), _np.float64)}  # (trailing shape, dtype) per ray
+assert _C.sizeof(CLight) == 72 and _C.sizeof(CLightSet) == 40 and _C.sizeof(CLitOut) == 72, "lg_light is 72 bytes, lg_light_set 40, lg_lit_out 72"
+LIT_PLANES = SCATTER_PLANES + ("terms", "visible")  # lg_lit_out's members, in its order
+LIGHT_DTYPE = _np.dtype([("position", _np.float64, (3,)), ("intensity", _np.float64, (3,)), ("falloff", _np.float64, (3,))])  # lg_light
+assert LIGHT_DTYPE.itemsize == 72
+
+
+def Light(position, intensity, falloff=(1.0, 0.0, 0.0)):
+    """One point light of a scatter_lit call: lg_scene_add_point_light's arguments (falloff: constant, linear, quadratic)."""
+    return (tuple(float(x) for x in position), tuple(float(x) for x in intensity), tuple(float(x) for x in falloff))
+
+
+def lights_array(lights):
+    """The light table of a scatter_lit call as a C-contiguous LIGHT_DTYPE array: from a sequence of Light()s (K,), from an array of
+    that dtype of any shape, or from a float64 array whose last axis is the nine doubles of a record."""
+    if isinstance(lights, _np.ndarray) and lights.dtype == LIGHT_DTYPE:
+        return _np.ascontiguousarray(lights)
+    if isinstance(lights, _np.ndarray):
+        a = _np.ascontiguousarray(lights, dtype=_np.float64)
+        if a.ndim < 1 or a.shape[-1] != 9:
+            raise ValueError("lights: the last axis holds position, intensity and falloff, nine doubles")
+        return a.view(LIGHT_DTYPE).reshape(a.shape[:-1])
+    out = _np.zeros(len(lights), dtype=LIGHT_DTYPE)
+    for k, (p, i, f) in enumerate(lights):
+        out[k] = (p, i, f)
+    return out
+
+
 assert _C.sizeof(CGatherOut) == 16, "lg_gather_out is 16 bytes"
 GATHER_PLANES = ("radiance", "sums")  # lg_gather_out's members, in its order
 GATHER_LANES = {"auto": 0, "direction": 1, "pose": 2}
@@ -938,6 +966,75 @@ class HipApi(Api):
         if self.call("scatter_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), _C.addressof(f), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- lit scatter (include/lasgun_hip.h, lg_scatter_lit*): surface scatter under lights that come with the call
+    @staticmethod
+    def _light_set(lights, n, ambient, ptr=None):
+        """(CLightSet, K, per_ray, what keeps the table alive): lights (K,) are shared, (n, K) are per ray; `ptr`: the table's address where
+        it is not the array's own (a per-ray table on the device)."""
+        amb = (_C.c_double * 3)(*[float(x) for x in ambient])
+        if ptr is not None:
+            count, per_ray = lights
+            return CLightSet(int(ptr) or None, int(count), int(per_ray), amb), int(count), int(per_ray), None
+        tab = lights_array(lights)
+        if tab.ndim == 2 and tab.shape[0] != n:
+            raise ValueError("lights: (K,) shared by every ray, or (n, K) with a row per ray")
+        if tab.ndim not in (1, 2):
+            raise ValueError("lights: (K,) shared by every ray, or (n, K) with a row per ray")
+        count = tab.shape[-1]
+        return CLightSet(tab.ctypes.data if tab.size else None, count, 1 if tab.ndim == 2 else 0, amb), count, tab.ndim == 2, tab
+
+    def scatter_lit(self, accel, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES, into=None):
+        """scatter() under lights that come with the call, for every ray of an (n, 6) float64 array.  `lights`: a sequence of Light()s or a
+        lights_array of shape (K,), shared by every ray, or of shape (n, K), ray i's own lights in row i; K is 0 .. MAX_CALL_LIGHTS, and the
+        scene's own lights and ambient colour play no part.  A dict of the planes asked for (any of LIT_PLANES): the seven of scatter() --
+        `direct` is the sum of the visible lights' terms in order, then the ambient term under `ambient` -- and float64 (n, K, 3) terms =
+        every light's own term (+0.0 where it is not added), uint32 (n, ceil(K / 32)) visible = bit k & 31 of word k >> 5 is set iff light k
+        is visible from the hit.  `into`: a dict of C-contiguous arrays of those shapes, written in place.  Also `accel.scatter_lit(...)`."""
+        r = self._rays(rays)
+        n = r.shape[0]
+        planes = tuple(planes)
+        if any(p not in LIT_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (LIT_PLANES,))
+        ls, count, _, keep = self._light_set(lights, n, ambient)
+        shapes = dict(_SCATTER_SHAPE, terms=((count, 3), _np.float64), visible=(((count + 31) // 32,), _np.uint32))
+        out = {}
+        for p in planes:
+            tail, dt = shapes[p]
+            shape = (n,) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CLitOut(CScatterOut(*[data(out.get(p)) for p in SCATTER_PLANES]), data(out.get("terms")), data(out.get("visible")))
+        if self.call("scatter_lit", accel.h, data(r), n, _C.addressof(ls), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        del keep
+        return out
+
+    def scatter_lit_device(self, accel, n, rays_ptr, lights=None, ambient=(0.0, 0.0, 0.0), per_ray_lights_ptr=None, count=None, hits_ptr=None, direct_ptr=None,
+                           flags_ptr=None, reflect_ptr=None, reflect_weight_ptr=None, refract_ptr=None, refract_weight_ptr=None, terms_ptr=None, visible_ptr=None,
+                           stream=None):
+        """Enqueue scatter_lit of n rays (device memory, 6 doubles each) into device memory.  Shared lights: `lights`, a HOST table (a sequence
+        of Light()s or a lights_array of shape (K,)), staged by the call -- it may be dropped on return.  Per-ray lights:
+        `per_ray_lights_ptr`, DEVICE memory of n x count records of 72 bytes, ray i's at row i, and `count`.  The planes as for
+        scatter_device, and terms_ptr (n x K x 3 f64), visible_ptr (n x ceil(K / 32) u32); each may be None, not all.  The pointers are
+        integers (torch: tensor.data_ptr()) or objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        if per_ray_lights_ptr is not None:
+            ls, _, _, keep = self._light_set((count, 1), n, ambient, ptr=ptr(per_ray_lights_ptr))
+        else:
+            tab = lights_array(lights if lights is not None else [])
+            if tab.ndim != 1:
+                raise ValueError("lights: a host table of shape (K,); per-ray lights are device memory (per_ray_lights_ptr, count)")
+            ls, _, _, keep = self._light_set(tab, n, ambient)
+        f = CLitOut(CScatterOut(*[ptr(p) for p in (hits_ptr, direct_ptr, flags_ptr, reflect_ptr, reflect_weight_ptr, refract_ptr, refract_weight_ptr)]),
+                    ptr(terms_ptr), ptr(visible_ptr))
+        rays = ptr(rays_ptr)
+        if self.call("scatter_lit_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), _C.addressof(ls), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+        del keep
+
     # ---- radiance gathers (include/lasgun_hip.h, lg_radiance_gather*): li() along K shared directions from N poses, reduced per pose
     @staticmethod
     def _gather_lanes(lanes):
@@ -1540,6 +1637,7 @@ api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range"
 api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
 api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
 api.Accel.scatter = lambda self, rays, planes=SCATTER_PLANES: api.scatter(self, rays, planes)  # accel.scatter(rays)
+api.Accel.scatter_lit = lambda self, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES: api.scatter_lit(self, rays, lights, ambient, planes)  # accel.scatter_lit(rays, [la.Light(p, i)])
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):
     """The wrapper's one convention of a rule table for trace_paths: glass refracts with its eta, mirror and metal reflect, the rest `default`."""
     return api.path_rules(accel, default, gain)

@@ -193,6 +193,14 @@ SCATTER_SIGNATURES = {
 }
 SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT = 1, 2, 4  # LG_SCATTER_*: lg_scatter_out::flags
 
+# Lit scatter (include/lasgun_hip.h, lg_scatter_lit / lg_scatter_lit_device): surface scatter under lights that come with the call -- the
+# seven planes of lg_scatter, every light's own term and the visibility bits; the GPU library's alone.
+LIT_SIGNATURES = {
+    "scatter_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "scatter_lit_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+MAX_CALL_LIGHTS = 1024  # LG_MAX_CALL_LIGHTS
+
 # Radiance gathers (include/lasgun_hip.h, lg_radiance_gather / lg_radiance_gather_device / lg_radiance_gather_lanes): li() along K shared
 # directions from N poses, as a plane and / or reduced per pose by the caller's weights; the GPU library's alone.
 GATHER_SIGNATURES = {
@@ -267,6 +275,18 @@ class CPathsOut(C.Structure):  # lg_paths_out: nine pointers, 72 bytes; NULL = n
 class CScatterOut(C.Structure):  # lg_scatter_out: seven pointers, 56 bytes; NULL = not asked for
     _fields_ = [("hits", C.c_void_p), ("direct", C.c_void_p), ("flags", C.c_void_p), ("reflect", C.c_void_p), ("reflect_weight", C.c_void_p),
                 ("refract", C.c_void_p), ("refract_weight", C.c_void_p)]
+
+
+class CLight(C.Structure):  # lg_light: lg_scene_add_point_light's arguments, 72 bytes
+    _fields_ = [("position", C.c_double * 3), ("intensity", C.c_double * 3), ("falloff", C.c_double * 3)]
+
+
+class CLightSet(C.Structure):  # lg_light_set: the call's lights, 40 bytes
+    _fields_ = [("lights", C.c_void_p), ("count", C.c_uint32), ("per_ray", C.c_uint32), ("ambient", C.c_double * 3)]
+
+
+class CLitOut(C.Structure):  # lg_lit_out: lg_scatter_out, then terms and visible; nine pointers, 72 bytes; NULL = not asked for
+    _fields_ = [("scatter", CScatterOut), ("terms", C.c_void_p), ("visible", C.c_void_p)]
 
 
 class CGatherOut(C.Structure):  # lg_gather_out: two pointers, 16 bytes; NULL = not asked for

@@ -7,7 +7,7 @@
 // forms): a kernel file with such kernels adds itself here
 static void set_lds_limits(size_t bytes, bool ldss) {
     for (auto set : {mega_set_lds_limit, wf_set_lds_limit, queue_set_lds_limit, query_set_lds_limit, rq_set_lds_limit, visibility_set_lds_limit, features_set_lds_limit,
-                     open_directions_set_lds_limit, range_scan_set_lds_limit, hit_layers_set_lds_limit, trace_paths_set_lds_limit, gather_set_lds_limit, view_set_lds_limit, view_features_set_lds_limit, light_groups_set_lds_limit, scatter_set_lds_limit})
+                     open_directions_set_lds_limit, range_scan_set_lds_limit, hit_layers_set_lds_limit, trace_paths_set_lds_limit, gather_set_lds_limit, view_set_lds_limit, view_features_set_lds_limit, light_groups_set_lds_limit, scatter_set_lds_limit, lit_set_lds_limit})
         HIP_TRY(set(bytes, ldss));
 }
 

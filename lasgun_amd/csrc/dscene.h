@@ -434,6 +434,20 @@ struct ScatterArgs : RadianceArgs {
 };
 constexpr uint32_t SCATTER_HIT = 1u, SCATTER_REFLECT = 2u, SCATTER_REFRACT = 4u; // == LG_SCATTER_*
 
+// Lit scatter (k_lit.hip; lg_scatter_lit*): surface scatter under lights that come with the CALL -- the scene's own lights and ambient colour
+// play no part.  `lights` is one table of n_lights records shared by every ray (per_ray == 0: staged from the host, read through a
+// wave-uniform index) or n tables of n_lights, ray r's at lights[r * n_lights ..] (per_ray == 1: the caller's device memory).  A hit's
+// visibility is vis_words = ceil(n_lights / 32) words, word w of hit h parked at P.vis[w * P.wf_hit_stride + h].  `skip`: `visible` is not
+// asked for and the switch is on -- the shadow pass may leave out the walk of a (hit, light) whose term cannot depend on it.
+constexpr uint32_t MAX_CALL_LIGHTS = 1024u; // == LG_MAX_CALL_LIGHTS
+struct LitArgs : ScatterArgs {
+    const DLight *lights;      // [n_lights] or [n][n_lights]
+    double *terms;             // [n][n_lights][3]
+    uint32_t *visible;         // [n][vis_words]
+    uint32_t n_lights, per_ray, vis_words, skip;
+    double ambient[3];
+};
+
 // A radiance gather's level 0 (k_gather.hip; lg_radiance_gather*), beside the DParams of its chunk: the two tables the rays are made from,
 // where li goes, and where the chunk starts.  A batch of a call is a call of its own here: its poses' tables, its own li.
 struct GatherArgs {

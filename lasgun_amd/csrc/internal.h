@@ -64,6 +64,12 @@ hipError_t rq_set_lds_limit(size_t bytes, bool ldss);
 hipError_t launch_scatter_closest(const DParams &P, const ScatterArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_scatter_emit(const DParams &P, const ScatterArgs &Q, uint32_t blocks, hipStream_t stream);
 hipError_t scatter_set_lds_limit(size_t bytes, bool ldss);
+// k_lit.hip: lit scatter (lg_scatter_lit*; launch.cpp, enqueue_scatter_lit) -- surface scatter's chain under the call's lights: its own closest
+// pass (a miss's rows of `terms` and `visible` too), the shadow pass over hit tiles x visibility words, and the emit pass
+hipError_t launch_lit_closest(const DParams &P, const LitArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_lit_shadow(const DParams &P, const LitArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t launch_lit_emit(const DParams &P, const LitArgs &Q, uint32_t blocks, hipStream_t stream);
+hipError_t lit_set_lds_limit(size_t bytes, bool ldss);
 // k_light_groups.hip: light groups (lg_radiance_groups*; launch.cpp, enqueue_radiance_groups) -- the radiance query's level-0 closest pass with
 // a GroupArgs, and the shade and combine passes of EVERY level (P.wf_level) carrying Q.n_groups planes; the spread pass of the deepest level
 hipError_t launch_lg_closest(const DParams &P, const GroupArgs &Q, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
@@ -589,6 +595,9 @@ void enqueue_radiance_groups(const lg_accel &a, const double *rays, size_t n, co
                              lg_accel::LaunchCtx &c, hipStream_t stream);
 // One checked lg_scatter* call: Q's planes are the caller's device arrays (rays, perm, n, base and tri_base are set here)
 void enqueue_scatter(const lg_accel &a, const double *rays, size_t n, ScatterArgs Q, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
+// One checked lg_scatter_lit* call: Q's planes, and a per-ray light table, are the caller's device arrays; `shared` is the HOST table of a
+// call whose lights are shared (staged here; Q.lights is set from it)
+void enqueue_scatter_lit(const lg_accel &a, const double *rays, size_t n, LitArgs Q, const DLight *shared, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);
 void enqueue_ray_film(const lg_accel &a, const double *rays, size_t slots, uint32_t samples, const FilmArgs &film, const uint32_t *perm, lg_accel::LaunchCtx &c,
                       hipStream_t stream);
 // One checked lg_radiance_gather* call on device tables (query.cpp; gather_host.h): batch_poses = n_poses where radiance is given

@@ -242,6 +242,12 @@ struct Level0 {
     const void *q = nullptr;
     Closest closest_ = nullptr;
     Flat shade_ = nullptr, combine_ = nullptr, resolve_ = nullptr;
+    // level 0's shadow pass, where the lights are the call's and not the scene's (lit scatter, k_lit.hip): with own_shadow the render's
+    // shadow pass is not launched at level 0 whatever lights the scene has, and shadow_ (nullptr: a call without lights) is launched in its
+    // place over the hit tiles x vis_words work tiles
+    bool own_shadow = false;
+    Closest shadow_ = nullptr;
+    uint32_t vis_words = 1;
     GroupArgs *lg = nullptr;
     const std::vector<double *> *xout = nullptr;
     bool own() const { return q != nullptr; }
@@ -253,6 +259,7 @@ struct Level0 {
     }
     hipError_t spread(const DParams &P, uint32_t blocks, hipStream_t s) const { return launch_lg_spread(P, *lg, blocks, s); }
     hipError_t closest(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const { return closest_(P, q, fast, blocks, depth, s); }
+    hipError_t shadow(const DParams &P, bool fast, uint32_t blocks, uint32_t depth, hipStream_t s) const { return shadow_(P, q, fast, blocks, depth, s); }
     hipError_t shade(const DParams &P, uint32_t blocks, hipStream_t s) const { return shade_(P, q, blocks, s); }
     hipError_t combine(const DParams &P, uint32_t blocks, hipStream_t s) const { return combine_(P, q, blocks, s); }
     hipError_t resolve(const DParams &P, uint32_t blocks, hipStream_t s) const { return resolve_(P, q, blocks, s); }
@@ -337,10 +344,11 @@ struct WfChunk {
     double *frame = nullptr;
     uint32_t groups;             // light groups (Level0::lg): planes of li per ray of every level; 1 for every other chain
     std::vector<double *> xout;  // ... planes 1 .. groups-1 of each level, where there are any (plane 0 is L.out)
-    WfChunk(const ChunkPlan &p, uint32_t groups_ = 1) : plan(p), levels(p.levels), nlaunch(4 * p.levels), groups(groups_) {}
-    // ChunkPlan's `extra`: the hit queue, frame and visibility of the widest level; and 3 * 8 * (groups - 1) bytes per ray of each level of a recursive scene
-    static size_t extra_per_item(uint32_t levels, uint32_t groups = 1) {
-        return ((size_t)(4 + STASH_DOUBLES * 8 + 4) << (levels - 1)) * 7 / 4 + (levels > 1 ? (size_t)3 * 8 * (groups - 1) * (((size_t)1 << levels) - 1) : 0);
+    uint32_t vis_words;          // visibility words per hit slot (lit scatter, Level0::vis_words: > 1 with more than 32 lights in the call); 1 for every other chain
+    WfChunk(const ChunkPlan &p, uint32_t groups_ = 1, uint32_t vis_words_ = 1) : plan(p), levels(p.levels), nlaunch(4 * p.levels), groups(groups_), vis_words(vis_words_) {}
+    // ChunkPlan's `extra`: the hit queue, frame and visibility of the widest level (4 * (vis_words - 1) bytes more per hit slot); and 3 * 8 * (groups - 1) bytes per ray of each level of a recursive scene
+    static size_t extra_per_item(uint32_t levels, uint32_t groups = 1, uint32_t vis_words = 1) {
+        return ((size_t)(4 + STASH_DOUBLES * 8 + 4 * (size_t)vis_words) << (levels - 1)) * 7 / 4 + (levels > 1 ? (size_t)3 * 8 * (groups - 1) * (((size_t)1 << levels) - 1) : 0);
     }
     size_t hit_cap() const { return (size_t)plan.n0() << (levels - 1); }
     size_t hit_len() const { return hit_cap() + hit_cap() / 64 * (WF_FULL_MIN_HOST - 1); } // appended part: fewer than WF_FULL_MIN hits per block of 64 rays
@@ -350,7 +358,7 @@ struct WfChunk {
         L = plan.carve(cx.wf_mem.p, [&](auto &take) {
             hq = (uint32_t *)take(hit_len() * 4);
             frame = (double *)take(hit_len() * STASH_DOUBLES * 8);
-            vis = (uint32_t *)take(hit_len() * 4);
+            vis = (uint32_t *)take(hit_len() * 4 * vis_words);
             xout.assign(levels, nullptr);
             for (uint32_t d = 0; levels > 1 && groups > 1 && d < levels; ++d) xout[d] = (double *)take(((size_t)plan.n0() << d) * 3 * 8 * (groups - 1));
         });
@@ -400,6 +408,15 @@ struct WfChunk {
                 timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
                 P.l0_rel_n = 0u;
             }
+            if (own0 && l0.own_shadow) { // (the call's lights: hit tiles x visibility words work tiles)
+                if (l0.shadow_) {
+                    // hs.tiles * W in 32 bits: a chunk holds fewer than 2^31 rays (ChunkPlan, cap_limit), so fewer than 2^25 * 7 / 4 hit tiles, and W <= 32
+                    if (((unsigned long long)P.ntiles * 7ull / 4ull + 1ull) * l0.vis_words > 0xFFFFFFFFull) throw Error("level 0's shadow pass: hit tiles x visibility words do not fit 32 bits");
+                    const uint32_t sb = ldss ? trace_cap : (uint32_t)std::min<unsigned long long>(trace_cap, ((unsigned long long)P.ntiles * l0.vis_words + 3ull) / 4ull);
+                    level_params(d);
+                    timed(a, 2, ls, [&] { return l0.shadow(P, a.fast, sb, depth, ls); });
+                }
+            } else
             if (P.nlights > 0) {
                 level_params(d);
                 timed(a, 2, ls, [&] { return launch_wf_trace(P, a.fast, true, tb, depth, ls); });
@@ -510,6 +527,7 @@ struct Level0Call {
     uint32_t samples_root = 1;         // (the scene's camera may be supersampled; a query is not, and a view batch has its own samples_root)
     uint32_t planes = 1;               // planes of li per ray of every level (light groups alone: > 1)
     bool one_level = false;            // the chain is level 0 alone whatever depth the scene has (surface scatter: no children are followed, no combine)
+    uint32_t vis_words = 1;            // visibility words per hit slot (lit scatter alone: > 1 with more than 32 lights in the call)
     const char *label = "";            // what LASGUN_DEBUG calls the query ...
     std::string note;                  // ... and how it ends its line (a query's rays: the order they are walked in)
 };
@@ -521,8 +539,8 @@ static void enqueue_level0_query(const lg_accel &a, const Level0Call &call, BIND
     P0.ntiles = call.tiles;
     if (call.one_level) P0.recursion = 0; // (levels_of: 1 -- the plan, the carve and P.wf_levels all follow from it; no level-by-level kernel reads P.recursion)
     const uint32_t levels = levels_of(a, P0);
-    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, call.planes));
-    WfChunk K(plan, call.planes);
+    ChunkPlan plan(a, P0, false, S, WfChunk::extra_per_item(levels, call.planes, call.vis_words));
+    WfChunk K(plan, call.planes, call.vis_words);
     plan.fit([&] { K.carve(c); });
     const unsigned long long chunk_tiles = plan.chunk_tiles;
     Span span(a, stream);
@@ -616,6 +634,36 @@ void enqueue_scatter(const lg_accel &a, const double *rays, size_t n, ScatterArg
         l0.shade_ = l0_flat<ScatterArgs, launch_scatter_emit>;
         return l0;
     }, c, stream);
+}
+// Lit scatter (query.cpp, lg_scatter_lit*; the call checked there and in lit_host.h): surface scatter's chain with all three passes
+// k_lit.hip's -- the shadow pass between the closest and the emit pass walks the CALL's lights (Level0::own_shadow: the render's shadow pass
+// is not launched, whatever lights the scene has; a call without lights launches none).  Q.lights is device memory: a per-ray table is the
+// caller's, a shared one is staged here from the host array `shared` (which may be freed on return).  A chunk parks Q.vis_words visibility
+// words per hit slot.
+void enqueue_scatter_lit(const lg_accel &a, const double *rays, size_t n, LitArgs Q, const DLight *shared, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream) {
+    try {
+        if (!Q.per_ray && Q.n_lights) Q.lights = static_cast<const DLight *>(stage_rule_table(shared, (size_t)Q.n_lights * sizeof(DLight), c, stream));
+        Level0Call call;
+        call.tiles = (uint32_t)((n + 63) / 64);
+        call.label = "lit scatter";
+        call.note = std::string(perm ? "sorted order" : "as given") + ", " + std::to_string(Q.n_lights) + (Q.per_ray ? " lights per ray" : " shared lights") + (Q.skip ? ", skip" : "");
+        call.one_level = true;
+        call.vis_words = std::max(1u, Q.vis_words);
+        static_cast<RadianceArgs &>(Q) = RadianceArgs{rays, nullptr, perm, (unsigned long long)n, 0ull};
+        Q.tri_base = a.accel_tri_base.p;
+        enqueue_level0_query(a, call, [&](unsigned long long t0) {
+            Q.base = t0 * 64ull;
+            Level0 l0;
+            l0.q = &Q;
+            l0.closest_ = l0_closest<LitArgs, launch_lit_closest>;
+            l0.shade_ = l0_flat<LitArgs, launch_lit_emit>;
+            l0.own_shadow = true;
+            if (Q.n_lights) l0.shadow_ = l0_closest<LitArgs, launch_lit_shadow>;
+            l0.vis_words = call.vis_words;
+            return l0;
+        }, c, stream);
+        subsets_enqueued(a, stream);
+    } catch (...) { subsets_abandoned(a, stream); throw; }
 }
 // A radiance gather (query.cpp, lg_radiance_gather*; the call checked there and in gather_host.h): batch after batch of g.batch_poses whole
 // consecutive poses, each a level-0 query of its own over the batch's tiles -- its poses' rows of the tables, its own li -- with the

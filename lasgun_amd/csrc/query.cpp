@@ -3,7 +3,8 @@
 // k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
-// alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h).  With
+// alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
+// (enqueue_scatter_lit; k_lit.hip; lit_host.h).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
 // lg_layers_out / lg_paths_out / lg_features is, is scan_host.h's / layers_host.h's / paths_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
@@ -16,6 +17,7 @@
 #include "layers_host.h"
 #include "paths_host.h"
 #include "scatter_host.h"
+#include "lit_host.h"
 #include "light_groups_host.h"
 #include "scan_host.h"
 #include "views_host.h"
@@ -942,6 +944,67 @@ extern "C" int lg_scatter_device(const lg_accel *a, const double *dev_rays, size
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         scatter_planes(*dev_out, n, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
         enqueue_scatter_query(*a, dev_rays, n, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- lit scatter (lg_scatter_lit*; launch.cpp, enqueue_scatter_lit; k_lit.hip): surface scatter under lights that come with the call,
+// with every light's term and the visibility bits as two more planes.  What needs no device -- the light set's rules, W, the sizes, the
+// NULL and alignment rules, the staging -- is lit_host.h's.
+static_assert(MAX_CALL_LIGHTS == LG_MAX_CALL_LIGHTS && sizeof(DLight) == sizeof(lg_light), "dscene.h restates the contract's light record and limit");
+// The skip (k_lit.hip): on unless LASGUN_LIT_SKIP=0 (for the measurement of what it buys); never where `visible` is asked for
+static bool lit_skip_on() {
+    static const bool on = [] { const char *e = std::getenv("LASGUN_LIT_SKIP"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// One call enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers):
+// `table` is the light table where the kernels will find it -- a per-ray table on the device -- or, shared, the caller's host array
+static void enqueue_lit_query(const lg_accel &a, const double *rays, size_t n, const lg_light_set &lights, const lg_light *table, const LitSizes &z, const lg_lit_out &out,
+                              hipStream_t stream) {
+    check_queue_error(a);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream);
+    LitArgs Q{};
+    const lg_scatter_out &so = out.scatter;
+    Q.hits = so.hits; Q.direct = so.direct; Q.flags = so.flags;
+    Q.reflect = so.reflect; Q.reflect_weight = so.reflect_weight; Q.refract = so.refract; Q.refract_weight = so.refract_weight;
+    Q.terms = z.K ? out.terms : nullptr;
+    Q.visible = z.K ? out.visible : nullptr;
+    Q.n_lights = (uint32_t)z.K; Q.per_ray = lights.per_ray; Q.vis_words = (uint32_t)z.W;
+    Q.skip = z.K && !Q.visible && lit_skip_on() ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) Q.ambient[k] = lights.ambient[k];
+    Q.lights = lights.per_ray ? reinterpret_cast<const DLight *>(table) : nullptr;
+    enqueue_scatter_lit(a, rays, n, Q, lights.per_ray ? nullptr : reinterpret_cast<const DLight *>(table), perm, c, stream);
+}
+// Host form: the rays (and a per-ray light table) go up, the planes come back into staging and are copied out at the end
+extern "C" int lg_scatter_lit(const lg_accel *a, const double *rays, size_t n, const lg_light_set *lights, const lg_lit_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        const LitSizes z = check_lit(a, rays, n, lights, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        RoundTrip trip(*a);
+        LitStaging st(*out, z);
+        const double *drays = trip.in(rays, n * 6);
+        const lg_light *table = lights->per_ray && z.K ? trip.in(lights->lights, z.lights) : lights->lights;
+        lg_lit_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        lit_planes(dev, z, [&](auto *&p, auto member, size_t count, size_t, const char *) { if (p) p = trip.out(member(st).data(), count); });
+        trip.run([&] { enqueue_lit_query(*a, drays, n, *lights, table, z, dev, a->stream); });
+        place_lit(*out, z, st);
+    });
+}
+extern "C" int lg_scatter_lit_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_light_set *lights, const lg_lit_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        const LitSizes z = check_lit(a, dev_rays, n, lights, dev_out);
+        check_lit_alignment(dev_rays, *lights, *dev_out, z);
+        std::lock_guard<std::mutex> g(a->mtx);
+        check_sorted_count(*a, n);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        if (lights->per_ray && z.K) check_device_buffer(*a, lights->lights, z.lights * sizeof(lg_light), 8, "lights->lights");
+        lg_lit_out o = *dev_out;
+        lit_planes(o, z, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        enqueue_lit_query(*a, dev_rays, n, *lights, lights->lights, z, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

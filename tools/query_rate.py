@@ -73,11 +73,17 @@ Surface scatter (lg_scatter_device) -- --rows scatter (not part of "all"): the c
 scene rebuilt at depth 0, the floor (the same closest and shadow passes, 24 bytes a ray).  Rows S2 / S7: direct + flags / all seven planes, with
 what they cost over the floor in ms and per byte written.  Row CD: li() composed to the scene's own depth over the device form with torch, against
 row RD, one lg_radiance_device call (measure_scatter).
+Lit scatter (lg_scatter_lit_device) -- --rows lit (not part of "all"): the camera's rays of a --size^2 film.  Row F, the floor: lg_scatter_device,
+direct + flags, on the scene rebuilt with four lights.  Row L4: lg_scatter_lit_device with those four lights shared, on the scene without lights
+(same_bytes: its planes against F's).  Row L64: 64 shared lights.  Rows P1 / P16: 1 and 16 lights per ray, and P1t / P16t with terms.  Row L64v:
+L64 with visible asked for (every pair walked: the skip's yardstick inside one process; LASGUN_LIT_SKIP=0 turns the skip off for a whole run).
+Rows M64 / MR: one light at 64 positions by 64 calls on ONE accel against 64 rebuilt accels + lg_scatter_device, on a film of at most 1024^2
+(64 launch contexts of a 4096^2 chain would not fit), the rebuilds timed apart (build_ms) (measure_lit).
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -89,6 +95,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import lasgun_amd as la  # noqa: E402
@@ -1070,6 +1077,101 @@ def once(size):
     print(json.dumps({"once": True, "rays": n, "shadow_segments": int(segs.shape[0])}))
 
 
+_LIT_ACCELS = {}
+
+
+def measure_lit(name, builder, size, calls):
+    """Lit scatter on the camera's rays of a size^2 film (the rows: the module's docstring).  The four lights are measure_groups': the
+    builder's own at L and three more around it under the shell's ceiling; the other lights are drawn with a fixed seed from the box
+    L + [-0.8, 0.8] x [-0.5, 0] x [-0.8, 0.8] with intensities in [0.02, 0.2] and falloff (1, 0, 0).  Timed F, L4, L64, L64v, P1, P1t, P16, P16t,
+    M64, MR, so --repeats alternates them."""
+    if not hasattr(G, "scatter_lit_device"):
+        return []
+    from light_subsets import subset_scene
+    pscene = builder(pyref.Api)
+    (x, y, z), col0, fall0 = pscene.lights[0][0], pscene.lights[0][1], pscene.lights[0][2]
+    four = la.lights_array([la.Light((x, y, z), col0, fall0), la.Light((x + 0.8, y - 0.25, z + 0.8), (0.5, 0.4, 0.3)),
+                            la.Light((x - 0.8, y - 0.25, z + 0.8), (0.3, 0.4, 0.5)), la.Light((x, y - 0.25, z - 0.8), (0.4, 0.5, 0.3))])
+    ambient = tuple(float(c) for c in pscene.ambient)
+    rng = np.random.default_rng(23)
+    pool = np.zeros(64, dtype=la.LIGHT_DTYPE)
+    pool["position"] = np.array([x, y, z]) + rng.uniform([-0.8, -0.5, -0.8], [0.8, 0.0, 0.8], (64, 3))
+    pool["intensity"] = rng.uniform(0.02, 0.2, (64, 3))
+    pool["falloff"] = (1.0, 0.0, 0.0)
+
+    def relit(lights):
+        def scene_of(api):
+            scene = subset_scene(api, builder, 0, False)
+            for rec in lights:
+                scene.add_point_light(rec["position"].tolist(), rec["intensity"].tolist(), rec["falloff"].tolist())
+            scene.set_ambient_light(list(ambient))
+            return scene
+        return scene_of
+
+    small = min(size, 1024)
+    if name not in _LIT_ACCELS:
+        bare, lit4 = G.Accel.from_scene(relit(pool[:0])(G)), G.Accel.from_scene(relit(four)(G))
+        t0 = time.time()
+        moved = [G.Accel.from_scene(relit(pool[i:i + 1])(G)) for i in range(64)]
+        _LIT_ACCELS[name] = (bare, lit4, moved, (time.time() - t0) * 1e3)
+    bare, lit4, moved, build_ms = _LIT_ACCELS[name]
+    for a in [bare, lit4] + moved:
+        G.set_query_order(a, 0)
+    s = torch.cuda.current_stream().cuda_stream
+    n, ns = size * size, small * small
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(bare, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    rays_s = torch.empty((ns, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(bare, small, small, 0, 0, small, small, rays_s.data_ptr(), stream=s)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device="cuda")  # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device="cuda")  # noqa: E731
+    direct, flags, direct2, flags2, vis = f64(n, 3), i32(n), f64(n, 3), i32(n), i32(n, 2)
+    idx = torch.from_numpy(rng.integers(0, 64, (n, 16))).cuda()
+    tab = torch.from_numpy(pool.view(np.float64).reshape(64, 9).copy()).cuda()
+    tab16 = tab[idx].contiguous()            # (n, 16, 9): ray i's lights
+    tab1 = tab16[:, 0, :].contiguous()       # (n, 9)
+    del idx
+    terms = f64(n, 16, 3)
+    skip = os.environ.get("LASGUN_LIT_SKIP", "1") != "0"
+    rows = []
+
+    def row(tag, fn, k, nbytes, rays_n=n, c=calls, **extra):
+        ms = timed(fn, c, warmup=1)
+        rows.append((tag, ms, k, nbytes, rays_n, extra))
+        return ms
+
+    row("F: lg_scatter_device, direct + flags, the scene rebuilt with four lights (the floor)", lambda: G.scatter_device(lit4, n, rays, direct_ptr=direct, flags_ptr=flags, stream=s), 4, 28)
+    row("L4: lg_scatter_lit_device, the same four lights shared, direct + flags", lambda: G.scatter_lit_device(bare, n, rays, lights=four, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, stream=s), 4, 28)
+    torch.cuda.synchronize()
+    rows[-1][5]["same_bytes"] = bool(torch.equal(direct.view(torch.int64), direct2.view(torch.int64)) and torch.equal(flags, flags2))
+    row("L64: 64 shared lights, direct + flags", lambda: G.scatter_lit_device(bare, n, rays, lights=pool, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, stream=s), 64, 28)
+    kept = direct2.clone()
+    row("L64v: 64 shared lights, direct + flags + visible (every pair walked)", lambda: G.scatter_lit_device(bare, n, rays, lights=pool, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, visible_ptr=vis, stream=s), 64, 36)
+    torch.cuda.synchronize()
+    rows[-1][5]["same_bytes"] = bool(torch.equal(kept.view(torch.int64), direct2.view(torch.int64)))  # the skip changes no bit of direct
+    del kept
+    row("P1: one light per ray, direct + flags", lambda: G.scatter_lit_device(bare, n, rays, per_ray_lights_ptr=tab1, count=1, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, stream=s), 1, 28)
+    row("P1t: one light per ray, direct + flags + terms", lambda: G.scatter_lit_device(bare, n, rays, per_ray_lights_ptr=tab1, count=1, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, terms_ptr=terms, stream=s), 1, 52)
+    row("P16: 16 lights per ray, direct + flags", lambda: G.scatter_lit_device(bare, n, rays, per_ray_lights_ptr=tab16, count=16, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, stream=s), 16, 28)
+    row("P16t: 16 lights per ray, direct + flags + terms", lambda: G.scatter_lit_device(bare, n, rays, per_ray_lights_ptr=tab16, count=16, ambient=ambient, direct_ptr=direct2, flags_ptr=flags2, terms_ptr=terms, stream=s), 16, 28 + 16 * 24)
+    del tab16, tab1, terms
+    many, other = f64(64, ns, 3), f64(64, ns, 3)
+    row("M64: one light at 64 positions, 64 lg_scatter_lit_device calls on one accel, direct", lambda: [G.scatter_lit_device(bare, ns, rays_s, lights=pool[i:i + 1], ambient=ambient, direct_ptr=many.data_ptr() + 24 * ns * i, stream=s) for i in range(64)],
+        1, 24, rays_n=64 * ns, c=max(calls // 2, 2), film=[small, small])
+    row("MR: the same by 64 rebuilt accels + lg_scatter_device, direct (the rebuilds timed apart)", lambda: [G.scatter_device(a, ns, rays_s, direct_ptr=other.data_ptr() + 24 * ns * i, stream=s) for i, a in enumerate(moved)],
+        1, 24, rays_n=64 * ns, c=max(calls // 2, 2), film=[small, small], build_ms=round(build_ms, 1))
+    torch.cuda.synchronize()
+    rows[-2][5]["same_bytes"] = bool(torch.equal(many.view(torch.int64), other.view(torch.int64)))
+    out = []
+    for tag, ms, k, nbytes, rays_n, extra in rows:
+        r = {"scene": name, "row": tag, "film": [size, size], "rays": rays_n, "lights": k, "ms": round(ms, 4), "mrays_per_s": round(rays_n / ms / 1e3, 1), "bytes_per_ray": nbytes, "skip": skip}
+        r.update(extra)
+        r.update({"calls": calls, "traversal": "lds" if G.set_lds_scene(bare, True) else "l2", "prune": G.get_prune(bare), "device_source_sha16": la.device_source_sha16(),
+                  "gpu": torch.cuda.get_device_name(0)})
+        out.append(r)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
@@ -1077,7 +1179,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -1086,8 +1188,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1115,7 +1217,9 @@ def main():
                 got += measure_paths(name, builder, args.size, max(args.calls, 4))
             if "scatter" in want:
                 got += measure_scatter(name, builder, args.size, max(args.calls, 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter"}:
+            if "lit" in want:
+                got += measure_lit(name, builder, args.size, max(args.calls, 3))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
