@@ -52,6 +52,14 @@ def magnitude(a): return math.sqrt(dot(a, a))
 def normalize(a): return mul(a, _div(1.0, magnitude(a)))  # a zero vector becomes NaNs, as in cgmath
 def fmin(a, b): return b if (a != a) else (a if (b != b) else min(a, b))  # f64::min (NaN-ignoring)
 def fmax(a, b): return b if (a != a) else (a if (b != b) else max(a, b))
+
+
+# f64::max / f64::min against a LITERAL, as an optimised x86-64 build computes `x.max(0.0)` and `x.min(1.0)`: the constant is known not to
+# be NaN, so LLVM emits a bare `maxsd x, const` / `minsd x, const`, which returns its second source, the constant, when x is NaN AND when
+# both are zeros -- (-0.0).max(0.0) is +0.0 there, as v_max_f64 has it, where Python's max() would hand back its first argument.  (With two
+# unknown operands the lowering adds a select on NaN and returns the receiver on a tie of zeros; f64::max leaves that tie open.)
+def max_const(x, c): return x if x > c else c
+def min_const(x, c): return x if x < c else c
 ZERO = (0.0, 0.0, 0.0)
 
 
@@ -568,9 +576,13 @@ def closest(scene, o, d):
 # ---- BxDF utilities (core/bxdf/mod.rs:237-288) --------------------------------------------------
 def cos2_theta(w): return w[2] * w[2]
 def sin2_theta(w): return fmax(1.0 - cos2_theta(w), 0.0)
-def sin_theta(w): return math.sqrt(sin2_theta(w))
+def sin_theta(w): return _sqrt(sin2_theta(w))
 def tan_theta(w): return _div(sin_theta(w), w[2])
 def tan2_theta(w): return _div(sin2_theta(w), cos2_theta(w))
+
+
+def _sqrt(x):  # IEEE square root (math.sqrt raises on a negative operand): NaN there, -0 for -0
+    return math.sqrt(x) if not x < 0.0 else float("nan")
 
 
 def _div(a, b):  # IEEE division (Python raises on a zero divisor)
@@ -601,7 +613,7 @@ def refract(wi, n, eta):
     sin2_t = eta * eta * sin2_i
     if sin2_t >= 1.0:
         return None
-    cos_t = math.sqrt(1.0 - sin2_t)
+    cos_t = _sqrt(1.0 - sin2_t)
     return add(smul(eta * -1.0, wi), smul(eta * cos_i - cos_t, n))
 
 
@@ -611,11 +623,11 @@ def fr_dielectric(cos_i, eta_i, eta_t):
     if not cos_i > 0.0:
         eta_i, eta_t = eta_t, eta_i
         cos_i = abs(cos_i)
-    sin_i = math.sqrt(fmax(1.0 - cos_i * cos_i, 0.0))
-    sin_t = eta_i / eta_t * sin_i
+    sin_i = _sqrt(fmax(1.0 - cos_i * cos_i, 0.0))
+    sin_t = _div(eta_i, eta_t) * sin_i
     if sin_t >= 1.0:
         return 1.0
-    cos_t = math.sqrt(fmax(1.0 - sin_t * sin_t, 0.0))
+    cos_t = _sqrt(fmax(1.0 - sin_t * sin_t, 0.0))
     r_parl = _div((eta_t * cos_i) - (eta_i * cos_t), (eta_t * cos_i) + (eta_i * cos_t))
     r_perp = _div((eta_i * cos_i) - (eta_t * cos_t), (eta_i * cos_i) + (eta_t * cos_t))
     return (r_parl * r_parl + r_perp * r_perp) * 0.5
@@ -625,15 +637,15 @@ def fr_conductor(cos_i, eta_i, eta_t, k):
     cos_i = fmin(fmax(cos_i, -1.0), 1.0)
     out = []
     for c in range(3):
-        eta = eta_t[c] / eta_i[c]
-        etak = k[c] / eta_i[c]
+        eta = _div(eta_t[c], eta_i[c])
+        etak = _div(k[c], eta_i[c])
         cos2 = cos_i * cos_i
         sin2 = 1.0 - cos2
         eta2, etak2 = eta * eta, etak * etak
         t0 = eta2 - etak2 - sin2
-        a2plusb2 = math.sqrt(t0 * t0 + 4.0 * (eta2 * etak2))
+        a2plusb2 = _sqrt(t0 * t0 + 4.0 * (eta2 * etak2))
         t1 = a2plusb2 + cos2
-        a = math.sqrt(0.5 * (a2plusb2 + t0))
+        a = _sqrt(0.5 * (a2plusb2 + t0))
         t2 = 2.0 * cos_i * a
         rs = _div(t1 - t2, t1 + t2)
         t3 = cos2 * a2plusb2 + sin2 * sin2
@@ -670,17 +682,17 @@ def tr_d(ax, ay, wh):  # microfacet.rs:31-40
     if math.isinf(t2):
         return 0.0
     cos4 = cos2_theta(wh) * cos2_theta(wh)
-    e = ((cos_phi(wh) * cos_phi(wh)) / (ax * ax) + (sin_phi(wh) * sin_phi(wh)) / (ay * ay)) * t2
-    return 1.0 / (PI * ax * ay * cos4 * (1.0 + e) * (1.0 + e))
+    e = (_div(cos_phi(wh) * cos_phi(wh), ax * ax) + _div(sin_phi(wh) * sin_phi(wh), ay * ay)) * t2
+    return _div(1.0, PI * ax * ay * cos4 * (1.0 + e) * (1.0 + e))
 
 
 def tr_lambda(ax, ay, w):  # microfacet.rs:55-66
     att = abs(tan_theta(w))
     if math.isinf(att):
         return 0.0
-    alpha = math.sqrt((cos_phi(w) * cos_phi(w)) * ax * ax + (sin_phi(w) * sin_phi(w)) * ay * ay)
+    alpha = _sqrt((cos_phi(w) * cos_phi(w)) * ax * ax + (sin_phi(w) * sin_phi(w)) * ay * ay)
     a2t2 = (alpha * att) * (alpha * att)
-    return (math.sqrt(1.0 + a2t2) - 1.0) / 2.0
+    return (_sqrt(1.0 + a2t2) - 1.0) / 2.0
 
 
 def bxdf_f(b, wo, wi):  # bxdf/mod.rs:152-162
@@ -696,7 +708,7 @@ def bxdf_f(b, wo, wi):  # bxdf/mod.rs:152-162
         else:
             max_cos = 0.0
         if abs(wi[2]) > abs(wo[2]):
-            sin_alpha, tan_beta = so, si / abs(wi[2])
+            sin_alpha, tan_beta = so, _div(si, abs(wi[2]))
         else:
             sin_alpha, tan_beta = si, _div(so, abs(wo[2]))
         return mul(mul(r, FRAC_1_PI), a + bb * max_cos * sin_alpha * tan_beta)
@@ -710,7 +722,7 @@ def bxdf_f(b, wo, wi):  # bxdf/mod.rs:152-162
             return ZERO
         wh = normalize(wh)
         spectrum = substance_eval(sub_, dot(wi, wh))
-        g = 1.0 / (1.0 + tr_lambda(ax, ay, wo) + tr_lambda(ax, ay, wi))
+        g = _div(1.0, 1.0 + tr_lambda(ax, ay, wo) + tr_lambda(ax, ay, wi))
         return div(mulv(mul(mul(r, tr_d(ax, ay, wh)), g), spectrum), 4.0 * cos_i * cos_o)
     return ZERO  # specular BxDFs scatter only through sample_f
 
@@ -723,7 +735,7 @@ def bxdf_sample_f(b, wo):  # specular.rs:17-24, 43-63 (the only BxDFs the integr
     _, t, eta_a, eta_b = b
     entering = wo[2] > 0.0
     eta_i, eta_t = (eta_a, eta_b) if entering else (eta_b, eta_a)
-    wi = refract(wo, (0.0, 0.0, 1.0), eta_i / eta_t)
+    wi = refract(wo, (0.0, 0.0, 1.0), _div(eta_i, eta_t))
     if wi is None:
         return ZERO, ZERO, 0.0
     fr = substance_eval(("dielectric", eta_a, eta_b), wi[2])
@@ -790,14 +802,14 @@ class BSDF:  # interaction/bsdf.rs
         if pdf == 0.0:
             return spectrum, wi_l, pdf
         wi = self.to_world(wi_l)
-        spectrum = tuple(fmin(fmax(c, 0.0), 1.0) for c in spectrum)  # (every sampled BxDF is specular)
+        spectrum = tuple(min_const(max_const(c, 0.0), 1.0) for c in spectrum)  # bsdf.rs:133 (every sampled BxDF is specular)
         return spectrum, wi, pdf / float(len(match))
 
 
 # ---- integrator (integrate/integrate.rs:23-132, interaction/surface.rs:158-183, light/point.rs:42-54) ----
 def background(scene, d):  # material/background.rs:25-34
     a = abs(dot((0.0, 0.0, 1.0), d))
-    t = fmin(math.sqrt(1.0 - a * a) / scene.bg_scale, 1.0)  # powf(2.) is x * x (LLVM folds it)
+    t = fmin(_sqrt(1.0 - a * a) / scene.bg_scale, 1.0)  # powf(2.) is x * x (LLVM folds it)
     return tuple(scene.bg_inner[i] * (1.0 - t) + scene.bg_outer[i] * t for i in range(3))
 
 
