@@ -262,6 +262,19 @@ pub struct Scatter<'a> {
     pub refract: Option<&'a mut [[f64; 6]]>,
     pub refract_weight: Option<&'a mut [[f64; 5]]>,
 }
+pub use sys::lg_attr_out as AttrOut;
+/// The planes `Accel::hit_attributes` / `hit_attributes_of` fill, one row per ray: `None` = not asked for; not all seven (`hits` stays
+/// `None` for `hit_attributes_of`).
+#[derive(Default)]
+pub struct Attributes<'a> {
+    pub hits: Option<&'a mut [sys::lg_hit]>,
+    pub flags: Option<&'a mut [u32]>,
+    pub bary: Option<&'a mut [[f64; 3]]>,
+    pub uv: Option<&'a mut [[f64; 2]]>,
+    pub local: Option<&'a mut [[f64; 3]]>,
+    pub frame: Option<&'a mut [[f64; 6]]>,
+    pub dp: Option<&'a mut [[f64; 6]]>,
+}
 pub use sys::lg_light as Light;
 pub use sys::lg_light_set as LightSet;
 pub use sys::lg_lit_out as LitOut;
@@ -557,6 +570,54 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `scatter` states (the library checks what HIP can tell it).
     pub unsafe fn scatter_device(&self, dev_rays: *const f64, n: usize, dev_out: &sys::lg_scatter_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_scatter_device(self.ptr, dev_rays, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    fn attr_out(n: usize, out: Attributes, what: &str) -> sys::lg_attr_out {
+        const _: () = assert!(std::mem::size_of::<sys::lg_attr_out>() == 56);
+        assert!(out.hits.as_ref().map_or(true, |p| p.len() == n) && out.flags.as_ref().map_or(true, |p| p.len() == n)
+                && out.bary.as_ref().map_or(true, |p| p.len() == n) && out.uv.as_ref().map_or(true, |p| p.len() == n)
+                && out.local.as_ref().map_or(true, |p| p.len() == n) && out.frame.as_ref().map_or(true, |p| p.len() == n)
+                && out.dp.as_ref().map_or(true, |p| p.len() == n),
+                "{}: every plane has rays.len() rows", what);
+        sys::lg_attr_out {
+            hits: out.hits.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            flags: out.flags.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            bary: out.bary.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            uv: out.uv.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            local: out.local.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            frame: out.frame.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            dp: out.dp.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+        }
+    }
+    /// Hit attributes (`lg_hit_attributes`): every ray's closest hit with where on its primitive it lies and the frame it is shaded in.
+    /// Row i of every plane given belongs to ray i: hits = `intersect`'s record, flags = `sys::LG_ATTR_HIT` or 0, bary = a triangle hit's
+    /// barycentrics, uv = the surface parameter, local = the hit point in the primitive's own space, frame = the BSDF's tangents ss, ts,
+    /// dp = the world-space geometric dpdu, dpdv; a miss's rows are +0.0.
+    pub fn hit_attributes(&self, rays: &[[f64; 6]], out: Attributes) {
+        let n = rays.len();
+        let o = Self::attr_out(n, out, "hit_attributes");
+        if unsafe { sys::lg_hit_attributes(self.ptr, rays.as_ptr() as *const f64, n, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `hit_attributes` without a walk (`lg_hit_attributes_of`): the primitives that `records` NAME (kind, prim, instance of each are
+    /// read) resolved for `rays`; flags also `sys::LG_ATTR_NO_HIT` and `sys::LG_ATTR_BAD_RECORD`; `out.hits` must be `None`.
+    pub fn hit_attributes_of(&self, rays: &[[f64; 6]], records: &[sys::lg_hit], out: Attributes) {
+        let n = rays.len();
+        assert!(records.len() == n, "hit_attributes_of: one record per ray");
+        let o = Self::attr_out(n, out, "hit_attributes_of");
+        if unsafe { sys::lg_hit_attributes_of(self.ptr, rays.as_ptr() as *const f64, records.as_ptr(), n, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `hit_attributes` for rays in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `hit_attributes` states (the library checks what HIP can tell it).
+    pub unsafe fn hit_attributes_device(&self, dev_rays: *const f64, n: usize, dev_out: &sys::lg_attr_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_hit_attributes_device(self.ptr, dev_rays, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `hit_attributes_of` for rays and records in device memory, enqueued on a HIP stream
+    ///
+    /// # Safety
+    /// As `hit_attributes_device`; `dev_hits` holds n 16-byte aligned `lg_hit` records.
+    pub unsafe fn hit_attributes_of_device(&self, dev_rays: *const f64, dev_hits: *const sys::lg_hit, n: usize, dev_out: &sys::lg_attr_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_hit_attributes_of_device(self.ptr, dev_rays, dev_hits, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     /// Lit scatter (`lg_scatter_lit`): `scatter` under lights that come with the call.  `lights`: K records shared by every ray
     /// (`per_ray` false) or rays.len() * K records, ray i's at i * K (`per_ray` true); `ambient` stands where the scene's ambient colour

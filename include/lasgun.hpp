@@ -345,6 +345,39 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void scatter_device(const double *dev_rays, size_t n, const lg_scatter_out &dev_out, void *hip_stream) const {
         if (lg_scatter_device(h_, dev_rays, n, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // hit attributes (lg_hit_attributes / lg_hit_attributes_of): where on its primitive each ray's hit lies and the frame it is shaded in --
+    // row i of every plane asked for (a null member is not asked for; not all seven) belongs to ray i: hits = lg_intersect's record, flags =
+    // LG_ATTR_*, bary = a triangle hit's barycentrics, uv = the surface parameter, local = the hit point in the primitive's own space, frame =
+    // the BSDF's tangents ss, ts, dp = the world-space geometric dpdu, dpdv; a miss's rows are +0.0.  With `records` (one lg_hit per ray, of
+    // which kind, prim and instance are read) nothing is walked: the named primitives are resolved, and `hits` must stay null
+    struct Attributes {
+        std::vector<lg_hit> *hits = nullptr;                        // [rays]
+        std::vector<uint32_t> *flags = nullptr;
+        std::vector<std::array<double, 3>> *bary = nullptr;
+        std::vector<std::array<double, 2>> *uv = nullptr;
+        std::vector<std::array<double, 3>> *local = nullptr;
+        std::vector<std::array<double, 6>> *frame = nullptr;
+        std::vector<std::array<double, 6>> *dp = nullptr;
+    };
+    void hit_attributes(const std::vector<std::array<double, 6>> &rays, const Attributes &out, const std::vector<lg_hit> *records = nullptr) const {
+        static_assert(sizeof(lg_attr_out) == 56, "lg_attr_out: seven pointers");
+        const size_t n = rays.size();
+        if (records && records->size() != n) throw Error("hit_attributes: one record per ray");
+        lg_attr_out o{};
+        if (out.hits) { out.hits->assign(n, lg_hit{}); o.hits = out.hits->data(); }
+        if (out.flags) { out.flags->assign(n, 0u); o.flags = out.flags->data(); }
+        if (out.bary) { out.bary->assign(n, {0.0, 0.0, 0.0}); o.bary = n ? (*out.bary)[0].data() : nullptr; }
+        if (out.uv) { out.uv->assign(n, {0.0, 0.0}); o.uv = n ? (*out.uv)[0].data() : nullptr; }
+        if (out.local) { out.local->assign(n, {0.0, 0.0, 0.0}); o.local = n ? (*out.local)[0].data() : nullptr; }
+        if (out.frame) { out.frame->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.frame = n ? (*out.frame)[0].data() : nullptr; }
+        if (out.dp) { out.dp->assign(n, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}); o.dp = n ? (*out.dp)[0].data() : nullptr; }
+        const double *r = rays.empty() ? nullptr : rays[0].data();
+        if (records ? lg_hit_attributes_of(h_, r, records->data(), n, &o) : lg_hit_attributes(h_, r, n, &o)) throw Error(lg_last_error());
+    }
+    void hit_attributes_device(const double *dev_rays, size_t n, const lg_attr_out &dev_out, void *hip_stream, const lg_hit *dev_records = nullptr) const {
+        if (dev_records ? lg_hit_attributes_of_device(h_, dev_rays, dev_records, n, &dev_out, hip_stream) : lg_hit_attributes_device(h_, dev_rays, n, &dev_out, hip_stream))
+            throw Error(lg_last_error());
+    }
     // lit scatter (lg_scatter_lit): scatter() under lights that come with the call -- `lights` shared by every ray (per_ray false: K records)
     // or a table per ray (per_ray true: rays.size() * K records, ray i's at i * K), `ambient` in the scene's ambient colour's place; the
     // scene's own lights play no part.  Beside scatter()'s planes: terms = every light's own term of direct ([ray * K + k], +0.0 where it is

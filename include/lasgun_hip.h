@@ -1153,6 +1153,74 @@ typedef struct lg_lit_out {
 } lg_lit_out;                /* 72 bytes; each pointer may be NULL, all nine NULL is an error */
 int lg_scatter_lit(const lg_accel *, const double *rays, size_t n, const lg_light_set *lights, const lg_lit_out *out);   /* host arrays; synchronous */
 int lg_scatter_lit_device(const lg_accel *, const double *dev_rays, size_t n, const lg_light_set *lights, const lg_lit_out *dev_out, void *hip_stream);
+/* Hit attributes: where on the primitive a ray's hit lies, and the frame the render shades it in.  lg_hit says which primitive was hit
+ * (kind, prim, instance); these planes say where on it: the barycentrics of a triangle hit (to interpolate vertex attributes of the
+ * caller's own: colours, labels, skinning weights, flow), a surface parameter (u, v) to texture the hit with, the hit point in the
+ * primitive's own space (a procedural texture that sticks to an instanced, rotated or scaled object) and the tangents of the render's
+ * BSDF (an anisotropic lobe of the caller's own; lg_scatter's transmitted direction restated).  The render computes all of it for every
+ * shaded hit; this hands it out.  An EXTRA; no counterpart in the reference.  Everything is f64, nothing is fused.
+ * Two forms.  The WALKING form (lg_hit_attributes*) finds each ray's closest hit and resolves it: hits[i] is lg_intersect's record of
+ * ray i, bit for bit, exact ties included, in the accel's traversal mode exactly as for the other queries (reference, pruned,
+ * LDS-resident scene, fast mode); lg_accel_set_query_order(1) is honoured as lg_intersect honours it (the same bytes, each answer in
+ * its own ray's rows; a query of 64 rays or fewer is walked as given).  flags[i] = 0 for a miss, LG_ATTR_HIT for a hit.  A miss writes
+ * +0.0 into every other plane.  The _OF form (lg_hit_attributes_of*) walks nothing: it resolves the primitive a record NAMES -- a
+ * record of lg_intersect, of a layer of lg_hit_layers, of a vertex of lg_trace_paths, or a compacted subset of them -- for the ray given
+ * with it.  Only kind, prim and instance of each record are read; out->hits must be NULL.
+ * The attributes are a pure function of (ray, kind, prim, instance).  With lr = the ray taken into the primitive's accel-local space by
+ * the inverse transforms of the accels on the chain root .. instance, in order (bvh.rs:462), the primitive's own intersector is run on
+ * lr as the render's hit resolution runs it, giving t.  Then:
+ *   local = lr.o + lr.d * t; for a sphere taken before the centre is subtracted and before the pole nudge.
+ *   bary  = e0*invdet, e1*invdet, e2*invdet of Triangle::intersect (triangle.rs:161-251): the weights of the face's first, second and
+ *     third vertex; +0.0 for a sphere or a box.
+ *   uv, triangle: u = (b0*u0 + b1*u1) + b2*u2 and v likewise, (u_k, v_k) the face's texture coordinates widened from f32; where the
+ *     mesh has none, the reference's default (0,0), (1,0), (1,1) (triangle.rs:257-262).
+ *   uv, sphere: u = phi / (2.0*PI), v = theta / PI, phi and theta Sphere::intersect's own (sphere.rs:79-123), the p.x = 1e-5*r nudge at
+ *     a pole and the +2*PI wrap of a negative phi included, in the library's portable atan2 and acos (lg_math_eval ops 4 and 5).
+ *   uv, box: with j and k the axes the hit face's two differentials point along (cuboid.rs:126-130, in the order the intersector
+ *     returns them), u = (local[j] - min[j]) / (max[j] - min[j]) and v likewise with k; a flat box gives whatever IEEE gives.
+ *   bary, uv and local are primitive-local: no transform and no swap_backface changes them.
+ *   dp    = gu, gv: the geometric dpdu and dpdv after transform_ray_intersection of every accel on the way up (transform.rs:243-264)
+ *     and the backface swaps (surface.rs:88-99): what the render's shading receives.  lg_hit::ng is
+ *     face_forward(normalize(cross(gu, gv)), -normalize(d)).
+ *   frame = ss, ts: ss = normalize(the surface dpdu carried up the same way), ts = cross(ns, ss) with ns lg_hit's: the tangents of the
+ *     render's BSDF (bsdf.rs:34-35).
+ * _of form, per record: kind == 0 gives flags 0 and +0.0 in every plane.  A record that names no primitive of this accel gives
+ * LG_ATTR_BAD_RECORD and +0.0, and nothing is dereferenced through it: kind > 3; instance >= the accel's instance count; prim >= the
+ * count of its kind, or for a triangle >= the face count of the mesh that `instance` is; a sphere or box that does not sit in
+ * `instance`.  A named primitive whose own test rejects the ray gives LG_ATTR_NO_HIT and +0.0: a triangle where Triangle::intersect's
+ * tests up to t fail, a box where Bounds::intersect misses, a sphere with t < 0 (as bvh.rs accepts).  No comparison with another
+ * primitive's t is made.  Every other record gives LG_ATTR_HIT and the attributes above.  Given lg_intersect's own records of the same
+ * rays, the planes are the walking form's, the same bytes.
+ * NaNs: SOME NaN, as for lg_scatter -- an element that is NaN in the render's own arithmetic is a NaN here, its sign and payload no
+ * part of the contract; every finite element, every +-INF and every zero's sign is bit for bit.
+ * Every element of every plane asked for is written, whatever the buffers held before, by exactly one lane: no atomics, no pre-fill.
+ * Nothing is shaded: lights, materials and the recursion depth play no part, and a scene of 40 lights is accepted.
+ * Limits and errors, as for lg_hit_layers: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors
+ * (non-zero, lg_last_error, nothing launched, no output touched), for n > 0: n > (2^32 - 1) * 64, and in the walking form n > 2^32 - 1
+ * with the sorted order; a plane's byte size that does not fit size_t; a NULL accel, rays or out; all planes NULL; in the _of form a
+ * NULL `hits` argument or a non-NULL out->hits; in the device forms also a pointer that is not device memory of the accel's device or
+ * is misaligned (rays 8 bytes; hits 16; flags 4; bary, uv, local, frame and dp 8), or a buffer that ends beyond its allocation.
+ * Device forms: dev_out is a HOST struct of device pointers; they only enqueue on hip_stream (the walking form with lg_intersect_device's
+ * exception for the sort's scratch); one stream at a time per accel.  Host forms (synchronous): the rays (and records) go up, the
+ * planes come back into staging and are copied out at the end, so an error on the way leaves the caller's arrays as they were.
+ * Out of scope: texture lookup itself; ray differentials; a maximum range in the walk; a multi-device split. */
+#define LG_ATTR_HIT        1u   /* resolved: the planes hold the attributes */
+#define LG_ATTR_NO_HIT     2u   /* _of form: the record names a primitive this ray does not hit */
+#define LG_ATTR_BAD_RECORD 4u   /* _of form: the record names no primitive of this accel */
+typedef struct lg_attr_out {
+    lg_hit   *hits;            /* [n]     lg_intersect's record of ray i (walking form only; must be NULL in the _of form) */
+    uint32_t *flags;           /* [n]     0, LG_ATTR_HIT 1, LG_ATTR_NO_HIT 2, LG_ATTR_BAD_RECORD 4 */
+    double   *bary;            /* [n][3]  triangle: b0, b1, b2; otherwise +0.0 */
+    double   *uv;              /* [n][2] */
+    double   *local;           /* [n][3]  the hit point in the primitive's accel-local space */
+    double   *frame;           /* [n][6]  ss, ts: the BSDF's tangents (bsdf.rs:34-35) */
+    double   *dp;              /* [n][6]  gu, gv: world-space geometric dpdu, dpdv as the render's shading receives them */
+} lg_attr_out;                 /* 56 bytes; each pointer may be NULL, all NULL is an error */
+int lg_hit_attributes(const lg_accel *, const double *rays, size_t n, const lg_attr_out *out);         /* host arrays; synchronous */
+int lg_hit_attributes_device(const lg_accel *, const double *dev_rays, size_t n, const lg_attr_out *dev_out, void *hip_stream);
+int lg_hit_attributes_of(const lg_accel *, const double *rays, const lg_hit *hits, size_t n, const lg_attr_out *out);   /* host arrays; synchronous */
+int lg_hit_attributes_of_device(const lg_accel *, const double *dev_rays, const lg_hit *dev_hits, size_t n, const lg_attr_out *dev_out,
+                                void *hip_stream);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -107,6 +107,7 @@ _EXTRA = {
     **PATHS_SIGNATURES,
     **SCATTER_SIGNATURES,
     **LIT_SIGNATURES,
+    **ATTRIBUTES_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -150,6 +151,10 @@ _SCATTER_SHAPE = {"hits": ((), HIT_DTYPE), "direct": ((3,), _np.float64), "flags
                   "reflect_weight": ((3,), _np.float64), "refract": ((6,), _np.float64), "refract_weight": ((5,), _np.float64)}  # (trailing shape, dtype) per ray
 assert _C.sizeof(CLight) == 72 and _C.sizeof(CLightSet) == 40 and _C.sizeof(CLitOut) == 72, "lg_light is 72 bytes, lg_light_set 40, lg_lit_out 72"
 LIT_PLANES = SCATTER_PLANES + ("terms", "visible")  # lg_lit_out's members, in its order
+assert _C.sizeof(CAttrOut) == 56, "lg_attr_out is 56 bytes"
+ATTR_PLANES = ("hits", "flags", "bary", "uv", "local", "frame", "dp")  # lg_attr_out's members, in its order
+_ATTR_SHAPE = {"hits": ((), HIT_DTYPE), "flags": ((), _np.uint32), "bary": ((3,), _np.float64), "uv": ((2,), _np.float64), "local": ((3,), _np.float64),
+               "frame": ((6,), _np.float64), "dp": ((6,), _np.float64)}  # (trailing shape, dtype) per ray
 LIGHT_DTYPE = _np.dtype([("position", _np.float64, (3,)), ("intensity", _np.float64, (3,)), ("falloff", _np.float64, (3,))])  # lg_light
 assert LIGHT_DTYPE.itemsize == 72
 
@@ -966,6 +971,74 @@ class HipApi(Api):
         if self.call("scatter_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), _C.addressof(f), self._stream(accel, stream)):
             raise LasgunError(self.last_error())
 
+    # ---- hit attributes (include/lasgun_hip.h, lg_hit_attributes* / lg_hit_attributes_of*): where on its primitive a hit lies, and its frame
+    def _attr_out(self, n, planes, into, allowed):
+        planes = tuple(planes)
+        if any(p not in allowed for p in planes):
+            raise ValueError("planes: any of %s" % (allowed,))
+        out = {}
+        for p in planes:
+            tail, dt = _ATTR_SHAPE[p]
+            shape = (n,) + tail
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        return out, CAttrOut(*[data(out.get(p)) for p in ATTR_PLANES]), data
+
+    def hit_attributes(self, accel, rays, planes=ATTR_PLANES, into=None):
+        """The closest hit of every ray of an (n, 6) float64 array with its surface attributes: a dict of the planes asked for (any of
+        ATTR_PLANES), each indexed by the ray -- HIT_DTYPE (n,) hits = lg_intersect's record, uint32 (n,) flags = ATTR_HIT or 0 (a miss),
+        float64 (n, 3) bary = a triangle hit's barycentrics (the weights of the face's three vertices; +0.0 otherwise), (n, 2) uv = the
+        surface parameter (a triangle's interpolated texture coordinates, a sphere's phi / 2 pi and theta / pi, a box face's unit square),
+        (n, 3) local = the hit point in the primitive's own space, (n, 6) frame = the BSDF's tangents ss, ts, (n, 6) dp = the world-space
+        geometric dpdu, dpdv.  A miss's rows are +0.0.  `into`: a dict of C-contiguous arrays of those shapes, written in place.  Also
+        `accel.hit_attributes(rays, planes=...)`."""
+        r = self._rays(rays)
+        n = r.shape[0]
+        out, f, data = self._attr_out(n, planes, into, ATTR_PLANES)
+        if self.call("hit_attributes", accel.h, data(r), n, _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def hit_attributes_of(self, accel, rays, hits, planes=ATTR_PLANES[1:], into=None):
+        """The attributes of the primitives that records NAME, without a walk: `hits` is a HIT_DTYPE (n,) array (of intersect, of a layer of
+        hit_layers, a compacted subset ...) of which kind, prim and instance are read, `rays` the (n, 6) rays they belong to.  The planes of
+        hit_attributes but "hits"; flags = ATTR_HIT, 0 for a record of kind 0, ATTR_NO_HIT where the named primitive's own test rejects
+        the ray, ATTR_BAD_RECORD where the record names no primitive of this accel (the rows are +0.0 for all three)."""
+        r = self._rays(rays)
+        n = r.shape[0]
+        h = _np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        if h.shape != (n,):
+            raise ValueError("hits: a HIT_DTYPE array of shape (%d,)" % n)
+        out, f, data = self._attr_out(n, planes, into, ATTR_PLANES[1:])
+        if self.call("hit_attributes_of", accel.h, data(r), data(h), n, _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def hit_attributes_device(self, accel, n, rays_ptr, hits_ptr=None, flags_ptr=None, bary_ptr=None, uv_ptr=None, local_ptr=None, frame_ptr=None, dp_ptr=None,
+                              stream=None):
+        """Enqueue hit_attributes of n rays (device memory, 6 doubles each) into device memory, n rows each: hits_ptr (lg_hit, 16-byte
+        aligned), flags_ptr (u32), bary_ptr and local_ptr (3 f64), uv_ptr (2 f64), frame_ptr and dp_ptr (6 f64); each may be None, not all.
+        The pointers are integers (torch: tensor.data_ptr()) or objects with a data_ptr()."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CAttrOut(*[ptr(p) for p in (hits_ptr, flags_ptr, bary_ptr, uv_ptr, local_ptr, frame_ptr, dp_ptr)])
+        rays = ptr(rays_ptr)
+        if self.call("hit_attributes_device", accel.h, _C.c_void_p(rays) if rays is not None else None, int(n), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def hit_attributes_of_device(self, accel, n, rays_ptr, records_ptr, flags_ptr=None, bary_ptr=None, uv_ptr=None, local_ptr=None, frame_ptr=None, dp_ptr=None,
+                                 stream=None):
+        """Enqueue hit_attributes_of of n rays and n records (device memory: 6 doubles and one 16-byte aligned lg_hit each) into device
+        memory; the planes as for hit_attributes_device, without hits."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CAttrOut(None, *[ptr(p) for p in (flags_ptr, bary_ptr, uv_ptr, local_ptr, frame_ptr, dp_ptr)])
+        rays, recs = ptr(rays_ptr), ptr(records_ptr)
+        if self.call("hit_attributes_of_device", accel.h, _C.c_void_p(rays) if rays is not None else None, _C.c_void_p(recs) if recs is not None else None, int(n),
+                     _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
     # ---- lit scatter (include/lasgun_hip.h, lg_scatter_lit*): surface scatter under lights that come with the call
     @staticmethod
     def _light_set(lights, n, ambient, ptr=None):
@@ -1637,6 +1710,7 @@ api.Accel.range_scan = lambda self, origins, beams, frames=None, planes=("range"
 api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "count"): api.hit_layers(self, rays, max_layers, planes)  # accel.hit_layers(rays, 8)
 api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
 api.Accel.scatter = lambda self, rays, planes=SCATTER_PLANES: api.scatter(self, rays, planes)  # accel.scatter(rays)
+api.Accel.hit_attributes = lambda self, rays, planes=ATTR_PLANES: api.hit_attributes(self, rays, planes)  # accel.hit_attributes(rays, ("uv", "bary"))
 api.Accel.scatter_lit = lambda self, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES: api.scatter_lit(self, rays, lights, ambient, planes)  # accel.scatter_lit(rays, [la.Light(p, i)])
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):
     """The wrapper's one convention of a rule table for trace_paths: glass refracts with its eta, mirror and metal reflect, the rest `default`."""

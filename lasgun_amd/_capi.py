@@ -193,6 +193,17 @@ SCATTER_SIGNATURES = {
 }
 SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT = 1, 2, 4  # LG_SCATTER_*: lg_scatter_out::flags
 
+# Hit attributes (include/lasgun_hip.h, lg_hit_attributes* / lg_hit_attributes_of*): barycentrics, uv, the local point, the BSDF's tangents
+# and the geometric dpdu / dpdv of each ray's hit -- found by the walk, or named by a record --, as planes indexed by the ray; the GPU
+# library's alone.
+ATTRIBUTES_SIGNATURES = {
+    "hit_attributes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hit_attributes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "hit_attributes_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hit_attributes_of_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+}
+ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD = 1, 2, 4  # LG_ATTR_*: lg_attr_out::flags
+
 # Lit scatter (include/lasgun_hip.h, lg_scatter_lit / lg_scatter_lit_device): surface scatter under lights that come with the call -- the
 # seven planes of lg_scatter, every light's own term and the visibility bits; the GPU library's alone.
 LIT_SIGNATURES = {
@@ -275,6 +286,11 @@ class CPathsOut(C.Structure):  # lg_paths_out: nine pointers, 72 bytes; NULL = n
 class CScatterOut(C.Structure):  # lg_scatter_out: seven pointers, 56 bytes; NULL = not asked for
     _fields_ = [("hits", C.c_void_p), ("direct", C.c_void_p), ("flags", C.c_void_p), ("reflect", C.c_void_p), ("reflect_weight", C.c_void_p),
                 ("refract", C.c_void_p), ("refract_weight", C.c_void_p)]
+
+
+class CAttrOut(C.Structure):  # lg_attr_out: seven pointers, 56 bytes; NULL = not asked for
+    _fields_ = [("hits", C.c_void_p), ("flags", C.c_void_p), ("bary", C.c_void_p), ("uv", C.c_void_p), ("local", C.c_void_p), ("frame", C.c_void_p),
+                ("dp", C.c_void_p)]
 
 
 class CLight(C.Structure):  # lg_light: lg_scene_add_point_light's arguments, 72 bytes

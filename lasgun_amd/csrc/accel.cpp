@@ -1,13 +1,46 @@
 // lasgun_amd/csrc/accel.cpp -- Accel::from (src/accelerators/bvh.rs:135-202 on the host, host.cpp) as device tables: flatten, the LDS images,
 // grids and budgets from the device's occupancy, one upload; and the tables once more with what was left out of them (fast trees, leaf records).
 #include "internal.h"
+#include "attributes_host.h"
 #include "pairs_host.h"
+
+// What a record of lg_hit_attributes_of* may name (attributes_host.h, the counts table): a mesh accel's faces are its OBJ's (lg_hit::prim of
+// a triangle is the face number), and the leaves of a group's reference tree hold its spheres and boxes -- each sits in that group and in
+// no other.  A mesh's tree is not walked.
+static std::vector<uint32_t> attr_counts_of(const FlatScene &f, const Scene &scene) {
+    std::vector<uint32_t> faces(f.accels.size(), 0u), tri_base(f.accels.size(), 0u), sphere_accel(f.spheres.size(), NO_HIT), cuboid_accel(f.cuboids.size(), NO_HIT);
+    std::vector<uint32_t> todo;
+    for (size_t id = 0; id < f.accels.size(); ++id) {
+        const DAccel &A = f.accels[id];
+        if (A.flags & AF_MESH) {
+            const int64_t obj = id < f.accel_obj.size() ? f.accel_obj[id] : -1;
+            if (obj >= 0 && (size_t)obj < scene.meshes.size() && scene.meshes[(size_t)obj]) faces[id] = (uint32_t)(scene.meshes[(size_t)obj]->tri.size() / 3);
+            tri_base[id] = id < f.accel_tri_base.size() ? f.accel_tri_base[id] : 0u;
+            if ((size_t)tri_base[id] + faces[id] > f.tri_v.size() / 3) faces[id] = 0u; // (never past the triangle tables)
+            continue;
+        }
+        if (A.node_base >= f.nodes.size()) continue; // (an empty group has no tree)
+        todo.assign(1, 0u);
+        while (!todo.empty()) {
+            const uint32_t nidx = todo.back();
+            todo.pop_back();
+            const DNode &nd = f.nodes[A.node_base + nidx];
+            if (!(nd.meta & NODE_LEAF)) { todo.push_back(nidx + 1u); todo.push_back(nd.link); continue; }
+            for (uint32_t k = 0; k < (nd.meta & 0xFFFFu); ++k) {
+                const uint32_t ref = f.primref[(size_t)A.prim_base + nd.link + k], kind = ref >> 30, idx = ref & PRIM_INDEX_MASK;
+                if (kind == PK_SPHERE && idx < sphere_accel.size()) sphere_accel[idx] = (uint32_t)id;
+                else if (kind == PK_CUBOID && idx < cuboid_accel.size()) cuboid_accel[idx] = (uint32_t)id;
+            }
+        }
+    }
+    return attr_counts_build(faces, tri_base, sphere_accel, cuboid_accel);
+}
 
 // raise the dynamic-LDS limit of the traversal kernels of EVERY kernel file (ldss: their LDS-resident-scene forms; otherwise the 256-lane
 // forms): a kernel file with such kernels adds itself here
 static void set_lds_limits(size_t bytes, bool ldss) {
     for (auto set : {mega_set_lds_limit, wf_set_lds_limit, queue_set_lds_limit, query_set_lds_limit, rq_set_lds_limit, visibility_set_lds_limit, features_set_lds_limit,
-                     open_directions_set_lds_limit, range_scan_set_lds_limit, hit_layers_set_lds_limit, trace_paths_set_lds_limit, gather_set_lds_limit, view_set_lds_limit, view_features_set_lds_limit, light_groups_set_lds_limit, scatter_set_lds_limit, lit_set_lds_limit})
+                     open_directions_set_lds_limit, range_scan_set_lds_limit, hit_layers_set_lds_limit, trace_paths_set_lds_limit, gather_set_lds_limit, view_set_lds_limit, view_features_set_lds_limit, light_groups_set_lds_limit, scatter_set_lds_limit, lit_set_lds_limit, attributes_set_lds_limit})
         HIP_TRY(set(bytes, ldss));
 }
 
@@ -339,6 +372,7 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
             }
         }
         stage.add(a->accel_tri_base, f.accel_tri_base); // (ray queries: k_query.hip)
+        stage.add(a->attr_counts, attr_counts_of(a->flat, *a->scene)); // (lg_hit_attributes_of*: k_attributes.hip)
         stage.commit(a->arena);
         // Which organisation is the default (measured, tools/threshold_sweep.py): the megakernel unless the scene has
         // so many spheres / boxes that BVH-node and sphere tests dominate a ray (>= 512: with the scene tables in LDS
@@ -391,7 +425,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.cuboids, y.cuboids); swap(x.cuboid_mat, y.cuboid_mat); swap(x.tri_v, y.tri_v); swap(x.tri_n, y.tri_n); swap(x.tri_t, y.tri_t);
     swap(x.vpos, y.vpos); swap(x.vnorm, y.vnorm); swap(x.vtex, y.vtex); swap(x.leaf_soup, y.leaf_soup); swap(x.chunks, y.chunks); swap(x.strips, y.strips);
     swap(x.sphere_ref_leaf, y.sphere_ref_leaf); swap(x.cuboid_ref_leaf, y.cuboid_ref_leaf); swap(x.tri_ref_leaf, y.tri_ref_leaf); swap(x.accel_ref_leaf, y.accel_ref_leaf);
-    swap(x.accels, y.accels); swap(x.materials, y.materials); swap(x.lights, y.lights); swap(x.accel_tri_base, y.accel_tri_base);
+    swap(x.accels, y.accels); swap(x.materials, y.materials); swap(x.lights, y.lights); swap(x.accel_tri_base, y.accel_tri_base); swap(x.attr_counts, y.attr_counts);
     swap(x.lds_image, y.lds_image); swap(x.accel_image, y.accel_image); swap(x.accel_image_n16, y.accel_image_n16);
     swap(x.lds_image_n16, y.lds_image_n16); swap(x.lds_node_off, y.lds_node_off); swap(x.lds_prim_off, y.lds_prim_off);
     swap(x.lds_soup_off, y.lds_soup_off); swap(x.lds_accel_off, y.lds_accel_off);

@@ -124,6 +124,17 @@ hipError_t launch_hit_layers(const DParams &P, const double *rays, unsigned long
                              double *inside, const uint32_t *tri_base, const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t hit_layers_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t hit_layers_set_lds_limit(size_t bytes, bool ldss);
+// k_attributes.hip: hit attributes (lg_hit_attributes*) -- query_kernel's closest form with the attribute planes of each hit behind its
+// record (barycentrics, uv, local point, the BSDF's tangents, the geometric dpdu / dpdv; attr_resolve.h); only the planes that are not
+// nullptr are written, indexed by the ray; perm != nullptr: the tiles are cut from the sorted order.  launch_attr_of (lg_hit_attributes_of*):
+// no walk -- record i (lg_hit, DEVICE memory) names the primitive, checked against `counts` (attributes_host.h) before it is resolved
+hipError_t launch_attributes(const DParams &P, const double *rays, unsigned long long n, void *hits, uint32_t *flags, double *bary, double *uv, double *local,
+                             double *frame, double *dp, const uint32_t *tri_base, const uint32_t *perm, bool fast, uint32_t blocks, uint32_t stack_depth,
+                             hipStream_t stream);
+hipError_t launch_attr_of(const DParams &P, const double *rays, const void *records, unsigned long long n, const uint32_t *counts, uint32_t *flags, double *bary,
+                          double *uv, double *local, double *frame, double *dp, uint32_t blocks, hipStream_t stream);
+hipError_t attributes_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t attributes_set_lds_limit(size_t bytes, bool ldss);
 // k_paths.hip: ray paths (lg_trace_paths*) -- layers_kernel's loop with a direction update: at each hit the rule of its material (`rules`:
 // n_rules lg_path_rule records in DEVICE memory) ends the path or forms the next segment in registers (bounce.h); only the planes that are
 // not nullptr are written, vertex-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order
@@ -451,6 +462,7 @@ struct lg_accel {
     DevBuf<DMaterial> materials;
     DevBuf<DLight> lights;
     DevBuf<uint32_t> accel_tri_base; // ray queries only (k_query.hip): per accel, its mesh's first triangle (FlatScene::accel_tri_base)
+    DevBuf<uint32_t> attr_counts;    // lg_hit_attributes_of* only (k_attributes.hip): what a record may name (attributes_host.h, attr_counts_build)
     // launch resources (mutable: a `const lg_accel*` render call still enqueues work).  Everything a launch
     // scribbles on lives in a per-STREAM context, so launches of one accel on different streams (frame k+1's
     // primary pass filling the tail of frame k's shadow pass) do not share tile counters or per-pixel state.

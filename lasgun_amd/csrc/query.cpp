@@ -1,6 +1,6 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
 // alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <deque>
 
+#include "attributes_host.h"
 #include "bitrows_host.h"
 #include "features_host.h"
 #include "gather_host.h"
@@ -846,6 +847,69 @@ extern "C" int lg_hit_layers_device(const lg_accel *a, const double *dev_rays, s
         layer_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
         enqueue_hit_layers(*a, dev_rays, n, max_layers, *dev_out, (hipStream_t)hip_stream);
     });
+}
+
+// ---- hit attributes (lg_hit_attributes*, lg_hit_attributes_of*; k_attributes.hip): where on its primitive each ray's hit lies and the frame
+// it is shaded in, as planes indexed by the ray.  What needs no device -- the limits and the sizes, the NULL and alignment rules, the
+// staging, the counts table and the record check -- is attributes_host.h's.
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers).
+// records == nullptr, the walking form: ONE launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is
+// parked.  Otherwise the _of form: no walk, no tile counter, no sort; a grid-stride launch over the records.
+static void enqueue_hit_attributes(const lg_accel &a, const double *rays, const lg_hit *records, size_t n, const lg_attr_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    DParams P = base_params(a, 1, 1);
+    if (records) {
+        const unsigned long long want = ((unsigned long long)n + 255ull) / 256ull;
+        const uint32_t blocks = (uint32_t)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, (unsigned long long)a.cus * 8ull));
+        HIP_TRY(launch_attr_of(P, rays, records, n, a.attr_counts.p, out.flags, out.bary, out.uv, out.local, out.frame, out.dp, blocks, stream));
+        return;
+    }
+    P.ntiles = (uint32_t)((n + 63) / 64);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const uint32_t *perm = query_order_of(a, c, rays, n, stream); // (ahead of the counter's memset on the stream)
+    const TraversalGrid g = traversal_grid(a, P, attributes_occupancy, c, stream);
+    HIP_TRY(launch_attributes(P, rays, n, out.hits, out.flags, out.bary, out.uv, out.local, out.frame, out.dp, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
+}
+// Host forms: the rays (and the records) go up, the planes come back into staging and are copied out at the end
+static int hit_attributes_host(const lg_accel *a, const double *rays, const lg_hit *records, bool of_form, size_t n, const lg_attr_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_attributes(a, rays, records, of_form, n, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        if (!of_form) check_sorted_count(*a, n);
+        RoundTrip trip(*a);
+        AttrStaging st(*out, n);
+        const double *drays = trip.in(rays, n * 6);
+        const lg_hit *drecords = of_form ? trip.in(records, n) : nullptr;
+        lg_attr_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
+        attr_planes(dev, n, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        trip.run([&] { enqueue_hit_attributes(*a, drays, drecords, n, dev, a->stream); });
+        place_attributes(*out, st);
+    });
+}
+static int hit_attributes_device(const lg_accel *a, const double *dev_rays, const lg_hit *dev_records, bool of_form, size_t n, const lg_attr_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_attributes(a, dev_rays, dev_records, of_form, n, dev_out);
+        check_attributes_alignment(dev_rays, dev_records, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        if (!of_form) check_sorted_count(*a, n);
+        use_device(a->device);
+        check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
+        if (of_form) check_device_buffer(*a, dev_records, n * sizeof(lg_hit), 16, "hits");
+        attr_planes(*dev_out, n, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        enqueue_hit_attributes(*a, dev_rays, of_form ? dev_records : nullptr, n, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+extern "C" int lg_hit_attributes(const lg_accel *a, const double *rays, size_t n, const lg_attr_out *out) { return hit_attributes_host(a, rays, nullptr, false, n, out); }
+extern "C" int lg_hit_attributes_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_attr_out *dev_out, void *hip_stream) {
+    return hit_attributes_device(a, dev_rays, nullptr, false, n, dev_out, hip_stream);
+}
+extern "C" int lg_hit_attributes_of(const lg_accel *a, const double *rays, const lg_hit *hits, size_t n, const lg_attr_out *out) {
+    return hit_attributes_host(a, rays, hits, true, n, out);
+}
+extern "C" int lg_hit_attributes_of_device(const lg_accel *a, const double *dev_rays, const lg_hit *dev_hits, size_t n, const lg_attr_out *dev_out, void *hip_stream) {
+    return hit_attributes_device(a, dev_rays, dev_hits, true, n, dev_out, hip_stream);
 }
 
 // ---- ray paths (lg_trace_paths*; k_paths.hip): each of the caller's rays followed through up to max_bounces vertices, the next segment

@@ -79,11 +79,14 @@ direct + flags, on the scene rebuilt with four lights.  Row L4: lg_scatter_lit_d
 L64 with visible asked for (every pair walked: the skip's yardstick inside one process; LASGUN_LIT_SKIP=0 turns the skip off for a whole run).
 Rows M64 / MR: one light at 64 positions by 64 calls on ONE accel against 64 rebuilt accels + lg_scatter_device, on a film of at most 1024^2
 (64 launch contexts of a 4096^2 chain would not fit), the rebuilds timed apart (build_ms) (measure_lit).
+Hit attributes (lg_hit_attributes_device, lg_hit_attributes_of_device) -- --rows attributes (not part of "all"): the camera's rays of a --size^2 film.
+Row I, the floor: lg_intersect_device.  Rows A2 / A7: the walking form with uv + bary alone / with all seven planes.  Rows O / W: the _of form on a
+compacted tenth of the hits against re-walking that tenth.
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -1055,6 +1058,58 @@ def measure_scatter(name, builder, size, calls):
     return out
 
 
+def measure_attributes(name, builder, size, calls):
+    """Hit attributes on the camera's rays of a size^2 film.  Row I, the floor: lg_intersect_device (96 bytes written a ray).  Row A2: the
+    walking form, uv + bary alone (40 bytes a ray).  Row A7: all seven planes (244 bytes a ray).  over_floor_ms = the row's ms minus I's of the
+    same repeat.  Then the _of form on a compacted tenth of the hits (every tenth hit, rays and records gathered with torch outside the timed
+    call): row O, lg_hit_attributes_of_device, all six planes; row W, the route without it, the walking form on that tenth.  O's planes are
+    compared with W's bytes (same_bytes).  Timed I, A2, A7, O, W, so --repeats alternates them."""
+    if not hasattr(G, "hit_attributes_device"):
+        return []
+    accel = G.Accel.from_scene(builder(G))
+    G.set_query_order(accel, 0)
+    assert G.camera_samples(accel) == 1
+    s = torch.cuda.current_stream().cuda_stream
+    n = size * size
+    rays = torch.empty((n, 6), dtype=torch.float64, device="cuda")
+    G.camera_rays_device(accel, size, size, 0, 0, size, size, rays.data_ptr(), stream=s)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device="cuda")  # noqa: E731
+    u32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device="cuda")  # noqa: E731
+    hits, flags, bary, uv, local, frame, dp = u32(n, 24), u32(n), f64(n, 3), f64(n, 2), f64(n, 3), f64(n, 6), f64(n, 6)
+    rows = []
+    ms = timed(lambda: G.intersect_device(accel, n, rays.data_ptr(), hits.data_ptr(), stream=s), calls, warmup=1)
+    floor = ms
+    rows.append(("I: lg_intersect_device (the floor)", n, ms, 96, None))
+    ms = timed(lambda: G.hit_attributes_device(accel, n, rays, uv_ptr=uv, bary_ptr=bary, stream=s), calls, warmup=1)
+    rows.append(("A2: lg_hit_attributes_device, uv + bary", n, ms, 40, None))
+    ms = timed(lambda: G.hit_attributes_device(accel, n, rays, hits_ptr=hits, flags_ptr=flags, bary_ptr=bary, uv_ptr=uv, local_ptr=local, frame_ptr=frame, dp_ptr=dp, stream=s),
+               calls, warmup=1)
+    rows.append(("A7: lg_hit_attributes_device, all seven planes", n, ms, 244, None))
+    torch.cuda.synchronize()
+    tenth = (hits[:, 20] != 0).nonzero().squeeze(1)[::10]
+    m = int(tenth.numel())
+    if m:
+        r10, h10 = rays[tenth].contiguous(), hits[tenth].contiguous()
+        of = [u32(m), f64(m, 3), f64(m, 2), f64(m, 3), f64(m, 6), f64(m, 6)]
+        wk = [u32(m), f64(m, 3), f64(m, 2), f64(m, 3), f64(m, 6), f64(m, 6)]
+        names = ("flags_ptr", "bary_ptr", "uv_ptr", "local_ptr", "frame_ptr", "dp_ptr")
+        ms_o = timed(lambda: G.hit_attributes_of_device(accel, m, r10, h10, stream=s, **dict(zip(names, of))), calls, warmup=1)
+        ms_w = timed(lambda: G.hit_attributes_device(accel, m, r10, stream=s, **dict(zip(names, wk))), calls, warmup=1)
+        torch.cuda.synchronize()
+        same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(of, wk))
+        rows.append(("O: lg_hit_attributes_of_device, a compacted tenth of the hits, six planes", m, ms_o, 148, {"same_bytes": bool(same)}))
+        rows.append(("W: lg_hit_attributes_device on that tenth (re-walking it), six planes", m, ms_w, 148, None))
+    out = []
+    for row, nr, ms, nbytes, x_ in rows:
+        r = {"scene": name, "row": row, "film": [size, size], "rays": nr, "ms": round(ms, 4), "mrays_per_s": round(nr / ms / 1e3, 1), "bytes_per_ray": nbytes, **(x_ or {})}
+        if row[:2] in ("A2", "A7"):
+            r["over_floor_ms"] = round(ms - floor, 4)
+        r.update({"calls": calls, "traversal": "lds" if G.set_lds_scene(accel, True) else "l2", "prune": G.get_prune(accel), "device_source_sha16": la.device_source_sha16(),
+                  "gpu": torch.cuda.get_device_name(0)})
+        out.append(r)
+    return out
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -1179,7 +1234,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -1188,8 +1243,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1219,7 +1274,9 @@ def main():
                 got += measure_scatter(name, builder, args.size, max(args.calls, 4))
             if "lit" in want:
                 got += measure_lit(name, builder, args.size, max(args.calls, 3))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit"}:
+            if "attributes" in want:
+                got += measure_attributes(name, builder, args.size, max(args.calls, 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
