@@ -285,6 +285,20 @@ int lg_accel_last_packet_walk(const lg_accel *);
  * not (lasgun_amd/csrc/packet_host.h, PacketRefusal: 5 the root is a mesh, 6 a nested tree with interior nodes, 7 a nested accel inside a
  * nested accel, 8 a nested group's leaf holds another accel, 9 the root tree is deeper than the stack); -1 on an error. */
 int lg_scene_packet_walk_gate(const lg_scene *);
+/* The camera's level 0 of the level-by-level pipeline in its FUSED form: for a scene without recursion levels and
+ * with exactly one light, where the closest launch takes the packet form and the shadow launch the pair form, the closest pass shades in
+ * its epilogue (a hit whose shadow ray decides nothing is finished there; every other hit parks its point, the light's term and the
+ * ambient term) and the shadow pass adds the light's term where the light is visible and writes the pixel: two passes, no shade pass.
+ * Radiance queries, gathers, view batches, light groups, lit scatter and every other scene keep the three passes.  1 (default): on;
+ * 0: the three passes (A/B, tests; LASGUN_FUSED_SHADE=0 does the same for every accel).  Same bytes either way.
+ * lg_accel_last_fused_shade: the form level 0 of the last chain took (1 / 0; -1 before the first). */
+int lg_accel_set_fused_shade(const lg_accel *, int enabled);
+int lg_accel_last_fused_shade(const lg_accel *);
+/* That form's gate for a scene, without a device (tests): 0 where a render by the scene's own camera (camera_level0 = 1) takes the form
+ * with every switch at its default, otherwise the reason it does not (lasgun_amd/csrc/fused_host.h, FusedRefusal: 2 level 0 is not the
+ * camera's, 3 more than one level, 4 not exactly one light, 5 the closest launch would not take the packet form, 6 the shadow launch
+ * would not take the pair form); -1 on an error. */
+int lg_scene_fused_shade_gate(const lg_scene *, int camera_level0);
 /* The LDS image lg_accel_from would make for this scene, without a device (tests): its 32-bit words into words[0 .. cap), info[8] = {16-byte
  * units, node offset, primref offset, leaf-record offset, accel-record offset (all in units), 1 if it holds pair records, accels, node
  * records of the flat tables}.  Returns the number of words, 0 when the tables do not fit in LDS, -1 on an error. */

@@ -49,6 +49,9 @@ _EXTRA = {
     "accel_set_packet_walk": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_last_packet_walk": (_C.c_int, [_C.c_void_p]),
     "scene_packet_walk_gate": (_C.c_int, [_C.c_void_p]),
+    "accel_set_fused_shade": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_last_fused_shade": (_C.c_int, [_C.c_void_p]),
+    "scene_fused_shade_gate": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "scene_lds_image": (_C.c_longlong, [_C.c_void_p, _C.c_int, _C.POINTER(_C.c_uint32), _C.c_size_t, _C.POINTER(_C.c_uint32)]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
@@ -319,6 +322,26 @@ class HipApi(Api):
         """The scene graph's part of the packet walk's gate, without a device: 0 where the form may take the scene, otherwise the reason it
         may not (include/lasgun_hip.h, lg_scene_packet_walk_gate)."""
         v = self.call("scene_packet_walk_gate", scene.h)
+        if v < 0:
+            raise LasgunError(self.last_error())
+        return int(v)
+
+    def set_fused_shade(self, accel, enabled):
+        """The camera's level 0 of the level-by-level pipeline in its fused form: the closest and shadow passes shade between them, no
+        shade pass (default on; same bytes either way; include/lasgun_hip.h, lg_accel_set_fused_shade)."""
+        if self.call("accel_set_fused_shade", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def last_fused_shade(self, accel):
+        """The form level 0 of the last chain of the level-by-level pipeline took: True fused (two passes), False the three kernels,
+        None before the first."""
+        v = self.call("accel_last_fused_shade", accel.h)
+        return None if v < 0 else bool(v)
+
+    def scene_fused_shade_gate(self, scene, camera_level0=True):
+        """The fused form's gate for a scene, without a device: 0 where a render by the scene's own camera takes the form, otherwise the
+        reason it does not (include/lasgun_hip.h, lg_scene_fused_shade_gate)."""
+        v = self.call("scene_fused_shade_gate", scene.h, 1 if camera_level0 else 0)
         if v < 0:
             raise LasgunError(self.last_error())
         return int(v)

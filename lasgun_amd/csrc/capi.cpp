@@ -3,6 +3,7 @@
 #include "internal.h"
 #include "choice.h"
 #include "packet_host.h"
+#include "fused_host.h"
 
 // ============================================================================================
 extern "C" {
@@ -794,6 +795,39 @@ int lg_scene_packet_walk_gate(const lg_scene *s) {
         FlatScene f;
         flatten_scene(s->s, f, false, false);
         v = (int)packet_scene_gate(f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.max_stack + 2u);
+    });
+    return rc ? -1 : v;
+}
+int lg_accel_set_fused_shade(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("fused shade must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->fused_shade = enabled == 1;
+    return 0;
+}
+int lg_accel_last_fused_shade(const lg_accel *a) { // the form level 0 of the last chain of the level-by-level pipeline took: 1 fused (two passes), 0 the three kernels; -1 before the first
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->last_fused_shade;
+}
+// The fused form's gate for a scene without a device (fused_host.h, fused_shade_gate): 0 where a render of the scene by its own camera
+// (camera_level0 = 1) would take the form with every switch at its default, otherwise the FusedRefusal that says why not; -1 on an error.
+// The launch's part is restated from the scene alone: the pair form of the LDS image exists (scene_lds_image), the packet walk's gate
+// admits the scene graph (packet_scene_gate), the levels are the scene's (a specular material and a recursion depth).
+int lg_scene_fused_shade_gate(const lg_scene *s, int camera_level0) {
+    int v = 0;
+    int rc = guarded([&] {
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        std::vector<uint32_t> img;
+        uint32_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const bool pairs = scene_lds_image(s->s, true, img, inf) && inf[5] == 1u;
+        FusedAsk q;
+        q.switched_on = true;
+        q.camera_level0 = camera_level0 != 0;
+        q.levels = (f.has_specular && s->s.recursion > 0) ? (unsigned)s->s.recursion + 1u : 1u;
+        q.nlights = (unsigned long)f.lights.size();
+        q.packet_closest = pairs && packet_scene_gate(f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.max_stack + 2u) == PACKET_OK;
+        q.pair_shadow = pairs;
+        v = (int)fused_shade_gate(q);
     });
     return rc ? -1 : v;
 }

@@ -383,6 +383,9 @@ struct DParams {
     // The packet form of the plain exact walk (packet.h): 1 where the level-0 closest launch of the level-by-level pipeline
     // takes it (launch.cpp, packet_walk: the gate); 0 everywhere else
     uint32_t packet;
+    // The fused form of the camera's level 0 (k_wavefront.hip, FUSED): 1 where the closest and shadow launches of the level
+    // shade between them and no shade pass follows (launch.cpp, fused_shade: the gate; fused_host.h); 0 everywhere else
+    uint32_t fused;
 };
 static_assert(sizeof(DParams) <= 4096, "DParams is passed by value: a kernel's arguments are at most 4 KB");
 // does a closest / shadow pass of the level-by-level pipeline launched with these parameters walk the pair form of the LDS image?  (the plain exact walk from LDS alone)

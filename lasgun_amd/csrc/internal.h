@@ -543,6 +543,9 @@ struct lg_accel {
     // the packet form of level 0's closest pass (packet.h; launch.cpp, packet_walk: the gate)
     mutable bool packet_walk = true;   // lg_accel_set_packet_walk
     mutable int last_packet_walk = -1; // the last level-0 closest launch of the level-by-level pipeline: 1 the packet form, 0 the per-lane walk; -1 before the first
+    // the fused form of the camera's level 0 (k_wavefront.hip, FUSED; launch.cpp, fused_shade: the gate)
+    mutable bool fused_shade = true;   // lg_accel_set_fused_shade
+    mutable int last_fused_shade = -1; // the last chain of the level-by-level pipeline: 1 its level 0 took the fused form (two passes, no shade pass), 0 the three kernels; -1 before the first
     mutable int packet_scene = -1;     // the scene graph's part of the gate (packet_host.h, PacketRefusal), made at the first launch that asks; -1: not yet
     uint32_t ldss_blocks = 0;         // one 1024-lane workgroup per CU; 0 = variant unavailable for this scene
     uint32_t cus = 1;                 // compute units of the accel's device

@@ -160,15 +160,60 @@ __device__ __forceinline__ void l0_rewrite(const DParams &P, uint4 *scn, uint32_
         if (P.l0_rel[a].node_n + P.l0_rel[a].slot_n > SMALL) rewrite(a, tid, LG_LDSS_BLOCK);
 }
 
+// The fused form of the camera's level 0 (wf_trace_kernel<.., FUSED>): a scene without recursion and with ONE light has
+// li = (0 + [visible] term) + ambient at a hit, so two triples and one bit are all that has to cross from pass to pass.  Every f64 below
+// comes from the expression shade_lights / wf_shade_kernel<0, true> / finish_pixel evaluate, on the same operands in the same order
+// (shade.h: light_term, light_radiance, ambient_term, wo_terms) -- the frame is the one shade_frame has just made, which is the frame the
+// shade pass re-derives from its 13 parked doubles by the same expressions.
+// The closest pass's epilogue for a lane that hit: slot `h` of the hit queue, ray / work item `i`, pixel `px`.
+__device__ __forceinline__ void fused_closest_hit(const DParams &P, const Pixel &px, const unsigned long long i, const unsigned long long h, const Shade &sh) {
+    const DMaterial m = P.materials[sh.mat];
+    const WoTerms wt = wo_terms(m, sh, sh.wo);
+    const V3 amb = ambient_term(P, m, sh, wt); // integrate.rs:67
+    const DLight L = P.lights[0];
+    const LightTerm t = light_term(L, sh); // (once: for the flag and for the term)
+    // The shadow ray decides nothing: the light's term does not depend on its visibility (shade.h, light_irrelevant), or the reference
+    // skips the light whatever its visibility (f_att == 0, integrate.rs:56).  li = (0 + ambient) + 0 + 0, which is what shade_lights and
+    // the shade pass make of a visibility word of 0, goes to the film here; the shadow pass treats the flagged hit like a hole.
+    const bool done = (P.shadow_skip && light_irrelevant(t)) || t.f_att == 0.0;
+    P.wf_hq[h] = done ? (uint32_t)i | WF_SKIP : (uint32_t)i;
+    if (done) { finish_pixel(P, px, i, (vzero() + amb) + vzero() + vzero()); return; }
+    const V3 term = light_radiance(L, m, sh, wt, t); // integrate.rs:53-62
+    const unsigned long long n = P.wf_hit_stride;
+    double *f = P.frame + h;
+    f[0 * n] = sh.p.x; f[1 * n] = sh.p.y; f[2 * n] = sh.p.z; // interaction.p + p_err: where the shadow ray leaves from
+    f[3 * n] = term.x; f[4 * n] = term.y; f[5 * n] = term.z;
+    f[6 * n] = amb.x; f[7 * n] = amb.y; f[8 * n] = amb.z;
+}
+// The shadow pass's tail for the hit in slot `h`, whose light is visible or not: the sum in shade_lights' order, the pixel as the shade pass maps it.
+__device__ __forceinline__ void fused_shadow_tail(const DParams &P, const unsigned long long h, const bool visible) {
+    const unsigned long long n = P.wf_hit_stride;
+    const double *f = P.frame + h;
+    const V3 term{f[3 * n], f[4 * n], f[5 * n]}, amb{f[6 * n], f[7 * n], f[8 * n]};
+    V3 out = vzero();
+    if (visible) out = out + term; // integrate.rs:62
+    const V3 value = out + amb;    // integrate.rs:67
+    const unsigned long long j = hq_ray(P.wf_hq[h]);
+    uint32_t sample;
+    const uint32_t ptile = l0_tile(P, (uint32_t)(j >> 6), sample);
+    const Pixel px = pixel_of(P, P.tile0 + ptile, (uint32_t)(j & 63u));
+    finish_pixel(P, px, j, value + vzero() + vzero()); // integrate.rs:79 with no children
+}
+
 // W1 / W2: persistent traversal kernels of the wavefront pipeline (tile counter, per-lane LDS stack; LDSS as above).
 // L0: the launch is level 0's (rays from the camera, work items = the chunk's pixels in 8x8 tiles).
 // REL: level 0's closest pass with the image's node boxes and sphere slots relative to the camera's origin (l0_rewrite above).
 // PAIR: the image this launch copies holds pair records (P.lds_pairs).
 // PACKET: level 0's closest pass in the packet form (packet.h): one cursor and one stack per wave; the kernel then holds no per-lane walk.
-template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false, bool PAIR = false, bool PACKET = false>
+// FUSED: the camera's level 0 of a scene without recursion and with ONE light, in two passes instead of three (launch.cpp,
+// fused_shade: the gate).  The closest pass (packet form) shades in its epilogue: a hit whose shadow ray decides nothing is finished there,
+// every other hit parks its offset point, the light's term and the ambient term (nine doubles in planes 0-8 of P.frame); the shadow pass
+// (pair form) adds the light's term where the light is visible and finishes the pixel.  No visibility word, no shade pass.
+template <bool FAST, bool SHADOW, bool LDSS, bool L0, bool PRUNE = false, bool REFILL = false, bool REL = false, bool PAIR = false, bool PACKET = false, bool FUSED = false>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) wf_trace_kernel(const DParams P) {
     static_assert(!PAIR || (!FAST && LDSS && !PRUNE && !REFILL), "the pair records: the plain exact walk from LDS");
     static_assert(!PACKET || (PAIR && L0), "the packet form: level 0's closest pass over the pair records");
+    static_assert(!FUSED || (PAIR && (SHADOW || PACKET)), "the fused form: the packet closest pass and the pair shadow pass of the camera's level 0");
     static_assert(!REL || (!FAST && !SHADOW && LDSS && L0 && !PRUNE && !REFILL), "the origin-relative form: level 0's closest pass from LDS");
     static_assert(!REFILL || (SHADOW && LDSS && !FAST), "the refilling walk: the LDS-resident shadow pass");
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
@@ -264,17 +309,20 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             if (hit) {
                 Shade sh;
                 shade_frame(P, ray, b, sh);
-                // no light's term at this hit depends on the light being visible (shade.h): the shadow pass will not walk it
-                const bool skip = P.shadow_skip && shadow_skippable(P, sh);
-                P.wf_hq[h] = skip ? (uint32_t)i | WF_SKIP : (uint32_t)i;
-                if (skip) P.vis[h] = 0u;
-                const unsigned long long n = P.wf_hit_stride;
-                double *f = P.frame + h;
-                f[0 * n] = sh.praw.x; f[1 * n] = sh.praw.y; f[2 * n] = sh.praw.z;
-                f[3 * n] = sh.ng.x; f[4 * n] = sh.ng.y; f[5 * n] = sh.ng.z;
-                f[6 * n] = sh.ns.x; f[7 * n] = sh.ns.y; f[8 * n] = sh.ns.z;
-                f[9 * n] = sh.ss.x; f[10 * n] = sh.ss.y; f[11 * n] = sh.ss.z;
-                f[12 * n] = (double)sh.mat;
+                if constexpr (FUSED) fused_closest_hit(P, px, i, h, sh);
+                else {
+                    // no light's term at this hit depends on the light being visible (shade.h): the shadow pass will not walk it
+                    const bool skip = P.shadow_skip && shadow_skippable(P, sh);
+                    P.wf_hq[h] = skip ? (uint32_t)i | WF_SKIP : (uint32_t)i;
+                    if (skip) P.vis[h] = 0u;
+                    const unsigned long long n = P.wf_hit_stride;
+                    double *f = P.frame + h;
+                    f[0 * n] = sh.praw.x; f[1 * n] = sh.praw.y; f[2 * n] = sh.praw.z;
+                    f[3 * n] = sh.ng.x; f[4 * n] = sh.ng.y; f[5 * n] = sh.ng.z;
+                    f[6 * n] = sh.ns.x; f[7 * n] = sh.ns.y; f[8 * n] = sh.ns.z;
+                    f[9 * n] = sh.ss.x; f[10 * n] = sh.ss.y; f[11 * n] = sh.ss.z;
+                    f[12 * n] = (double)sh.mat;
+                }
             } else if (active) { // integrate.rs:26-28
                 const V3 value = background(P, normalize(ray.d));
                 if (P.wf_levels == 1u) finish_pixel(P, px, i, value);
@@ -289,22 +337,31 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             bool skip;
             if (!hit_of(P, hs, tile, lane, h, skip) || skip) continue; // (a tile of flagged hits alone: the wave claims its next tile at once)
             const unsigned long long n = P.wf_hit_stride;
-            // interaction.p + p_err, recomputed from the parked frame exactly as stash_get does
-            V3 praw{P.frame[0 * n + h], P.frame[1 * n + h], P.frame[2 * n + h]};
-            V3 ng{P.frame[3 * n + h], P.frame[4 * n + h], P.frame[5 * n + h]};
-            const double err = 2.220446049250313e-16 * 65536.0;
-            V3 hit_p = praw + ng * err;
-            uint32_t vis = 0u;
-            for (uint32_t l = 0; l < P.nlights; ++l) {
-                const DLight L = P.lights[l];
+            if constexpr (FUSED) { // (one light: the gate)
+                const V3 hit_p{P.frame[0 * n + h], P.frame[1 * n + h], P.frame[2 * n + h]}; // interaction.p + p_err, as the closest pass made it
+                const DLight L = P.lights[0];
                 Ray sray = ray_new(hit_p, V3{L.pos[0], L.pos[1], L.pos[2]} - hit_p); // point.rs:43-44
                 Best b;
-                bool tie = false;
                 walk<LDSS, FAST, PRUNE, false, false, PAIR ? 1 : 0>(P, sray, true, stack, stride, b, scn, cnt, arec);
-                (void)tie;
-                if (!(b.t < 1.0)) vis |= 1u << l; // point.rs:49
+                fused_shadow_tail(P, h, !(b.t < 1.0)); // point.rs:49
+            } else {
+                // interaction.p + p_err, recomputed from the parked frame exactly as stash_get does
+                V3 praw{P.frame[0 * n + h], P.frame[1 * n + h], P.frame[2 * n + h]};
+                V3 ng{P.frame[3 * n + h], P.frame[4 * n + h], P.frame[5 * n + h]};
+                const double err = 2.220446049250313e-16 * 65536.0;
+                V3 hit_p = praw + ng * err;
+                uint32_t vis = 0u;
+                for (uint32_t l = 0; l < P.nlights; ++l) {
+                    const DLight L = P.lights[l];
+                    Ray sray = ray_new(hit_p, V3{L.pos[0], L.pos[1], L.pos[2]} - hit_p); // point.rs:43-44
+                    Best b;
+                    bool tie = false;
+                    walk<LDSS, FAST, PRUNE, false, false, PAIR ? 1 : 0>(P, sray, true, stack, stride, b, scn, cnt, arec);
+                    (void)tie;
+                    if (!(b.t < 1.0)) vis |= 1u << l; // point.rs:49
+                }
+                P.vis[h] = vis;
             }
-            P.vis[h] = vis;
         }
     }
 }
@@ -463,6 +520,7 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
     const bool pairs = wf_takes_pairs(P, fast); // the image holds pair records: the plain exact walk from LDS in its pair form
     const bool ldss = P.lds_image && !fast; // LDS-resident scene: `blocks` = one workgroup per CU
     const bool l0 = !shadow && P.wf_level == 0u;
+    if (P.fused && !(pairs && ldss && P.wf_level == 0u && (shadow || P.packet))) return hipErrorInvalidValue; // the fused form was asked of a launch that takes other forms (launch.cpp, fused_shade: the gate): nothing is launched
     const uint32_t block = ldss ? LG_LDSS_BLOCK : LG_BLOCK;
     const uint32_t depth = fast ? stack_depth : P.stack_depth;
     size_t lds = (size_t)depth * block * sizeof(uint32_t) + (ldss ? (size_t)P.lds_image_n16 * 16u : (!fast && P.accel_image ? (size_t)P.accel_image_n16 * 16u : 0u));
@@ -484,9 +542,12 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         const bool refill = refill_on && !pairs && shadow && P.wf_level == 0u && (unsigned long long)P.ntiles >= 4ull * blocks * (block / 64u);
 #define LG_LAUNCH_PAIR(S, Z, R) hipLaunchKernelGGL((wf_trace_kernel<false, S, true, Z, false, false, R, true>), dim3(blocks), dim3(block), lds, stream, P)
 #define LG_LAUNCH_PACKET(R) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, R, true, true>), dim3(blocks), dim3(block), lds, stream, P)
-        if (pairs && l0 && P.packet) { if (P.l0_rel_n) LG_LAUNCH_PACKET(true); else LG_LAUNCH_PACKET(false); } // (launch.cpp, packet_walk: the gate)
+#define LG_LAUNCH_FUSED(R) hipLaunchKernelGGL((wf_trace_kernel<false, false, true, true, false, false, R, true, true, true>), dim3(blocks), dim3(block), lds, stream, P)
+        if (pairs && l0 && P.packet && P.fused) { if (P.l0_rel_n) LG_LAUNCH_FUSED(true); else LG_LAUNCH_FUSED(false); } // (launch.cpp, fused_shade: the gate)
+        else if (pairs && l0 && P.packet) { if (P.l0_rel_n) LG_LAUNCH_PACKET(true); else LG_LAUNCH_PACKET(false); } // (launch.cpp, packet_walk: the gate)
         else if (pairs) {
-            if (shadow) LG_LAUNCH_PAIR(true, false, false);
+            if (shadow && P.fused) hipLaunchKernelGGL((wf_trace_kernel<false, true, true, false, false, false, false, true, false, true>), dim3(blocks), dim3(block), lds, stream, P);
+            else if (shadow) LG_LAUNCH_PAIR(true, false, false);
             else if (l0 && P.l0_rel_n) LG_LAUNCH_PAIR(false, true, true);
             else if (l0) LG_LAUNCH_PAIR(false, true, false); else LG_LAUNCH_PAIR(false, false, false);
         } else
@@ -495,6 +556,7 @@ hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t bl
         else if (l0) LG_LAUNCH(false, false, true, true); else LG_LAUNCH(false, false, true, false);
 #undef LG_LAUNCH_PAIR
 #undef LG_LAUNCH_PACKET
+#undef LG_LAUNCH_FUSED
     }
     else { if (shadow) LG_LAUNCH(false, true, false, false); else if (l0) LG_LAUNCH(false, false, false, true); else LG_LAUNCH(false, false, false, false); }
 #undef LG_LAUNCH
@@ -545,7 +607,10 @@ hipError_t wf_set_lds_limit(size_t bytes, bool ldss) {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, false, false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true, true, true>),
-        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true, true>)};
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, true, true, true, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, false, true, true, false, false, false, true, true, true>),
+        reinterpret_cast<const void *>(wf_trace_kernel<false, true, true, false, false, false, false, true, false, true>)};
     const void *plain_fns[] = {
         reinterpret_cast<const void *>(wf_trace_kernel<false, false, false, true>),
         reinterpret_cast<const void *>(wf_trace_kernel<false, true, false, false>),

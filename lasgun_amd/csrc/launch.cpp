@@ -4,6 +4,7 @@
 #include "internal.h"
 #include "choice.h"
 #include "packet_host.h"
+#include "fused_host.h"
 
 // The launch context of `stream` (at most MAX_LAUNCH_CTXS are kept; the least recently used one is recycled after a
 // device-wide synchronise).  Caller holds a.mtx and has made the accel's device current.
@@ -332,6 +333,22 @@ static uint32_t packet_walk(const lg_accel &a, const DParams &P, bool camera_lev
     return a.packet_scene == (int)PACKET_OK ? 1u : 0u;
 }
 
+// The gate of the fused form of the camera's level 0 (k_wavefront.hip, FUSED; the predicate is fused_host.h's).  Wrong means
+// wrong pixels: the chain is the scene camera's own, level 0 is its only level, the scene has exactly one light, and this level's closest
+// launch takes the packet form (P.packet, set just before) and its shadow launch the pair form.  LASGUN_FUSED_SHADE=0 /
+// lg_accel_set_fused_shade(0): the three kernels, the parent's code path.
+static uint32_t fused_shade(const lg_accel &a, const DParams &P, bool camera_level0, uint32_t levels) {
+    static const bool env = env_on("LASGUN_FUSED_SHADE");
+    FusedAsk q;
+    q.switched_on = a.fused_shade && env;
+    q.camera_level0 = camera_level0;
+    q.levels = levels;
+    q.nlights = (unsigned long)P.nlights;
+    q.packet_closest = P.packet != 0u;
+    q.pair_shadow = wf_takes_pairs(P, a.fast);
+    return fused_shade_gate(q) == FUSED_OK ? 1u : 0u;
+}
+
 // ---- the level-by-level pipeline (k_wavefront.hip), shared by a render (enqueue_wavefront) and a radiance query (enqueue_radiance) ----
 // A chunk's arrays in a launch context: the level arrays, and beside them the hit queue, frame and visibility of the widest level (dense
 // part + appended part), the queue counts and a block of tile heads per launch
@@ -402,6 +419,8 @@ struct WfChunk {
             level_params(d);
             P.packet = packet_walk(a, P, d == 0 && !own0); // (the camera's level 0 alone; every other launch of the chain: 0)
             if (d == 0) a.last_packet_walk = (int)P.packet;
+            P.fused = d == 0 ? fused_shade(a, P, !own0 && !l0.every_level(), levels) : 0u; // (the camera's level 0 of a chain of one level: its closest and shadow launches shade, no shade pass follows)
+            if (d == 0) a.last_fused_shade = (int)P.fused;
             if (own0) timed(a, 0, ls, [&] { return l0.closest(P, a.fast, tb, depth, ls); });
             else {
                 if (d == 0) a.last_l0_relative = l0_relative(a, P) ? 1 : 0; // (the camera's level 0: the form is chosen per launch, from this launch's camera)
@@ -425,9 +444,9 @@ struct WfChunk {
             // (light groups, the deepest level of a recursive scene: the closest pass left a miss's background in plane 0 alone)
             if (l0.every_level() && d >= 1 && d + 1 == levels) timed(a, 1, ls, [&] { return l0.spread(P, flat_cap, ls); });
             if (own0 || l0.every_level()) timed(a, 3, ls, [&] { return l0.shade(P, fb, ls); });
-            else timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
+            else if (!P.fused) timed(a, 3, ls, [&] { return launch_wf_shade(P, fb, ls); });
         }
-        P.packet = 0u;
+        P.packet = 0u; P.fused = 0u;
         combine_levels(a, P, L, plan, ls, l0);
     }
 };

@@ -446,22 +446,32 @@ __device__ __forceinline__ bool shadow_skippable(const DParams &P, const Shade &
     for (uint32_t l = 0; l < P.nlights; ++l) all = all && light_irrelevant(light_term(P.lights[l], sh));
     return all;
 }
+// The two kinds of term li() sums at a hit, each ONE expression for every site that evaluates it: shade_lights below, and the fused form of
+// the camera's level 0 (k_wavefront.hip, FUSED), whose closest pass evaluates both and parks them for the shadow pass's tail.
+// A visible light's term (integrate.rs:53-62) from what light_term made of it; the caller has skipped a light with f_att == 0.
+__device__ __forceinline__ V3 light_radiance(const DLight &L, const DMaterial &m, const Shade &sh, const WoTerms &wt, const LightTerm &t) {
+    V3 fr = bsdf_f(m, sh, wt, t.wi, t.reflect);
+    V3 li_col{L.intensity[0], L.intensity[1], L.intensity[2]};
+    return mul_ew(PI * li_col, fr) * t.wi_dot_n / t.f_att;
+}
+// The ambient term (integrate.rs:67)
+__device__ __forceinline__ V3 ambient_term(const DParams &P, const DMaterial &m, const Shade &sh, const WoTerms &wt) {
+    const V3 nrm = sh.ns;
+    return mul_ew(P.ambient, bsdf_f(m, sh, wt, nrm, bsdf_reflect(sh, sh.wo, nrm)));
+}
 // li() of a hit up to its specular children: the lights in order, then the ambient term (integrate.rs:47-67).  `vis` bit l:
 // light l is visible from the hit (PointLight::sample, point.rs:49).  Shared by the level-by-level shade pass and the queue kernel.
 __device__ __forceinline__ V3 shade_lights(const DParams &P, const DMaterial &m, const Shade &sh, const uint32_t vis) {
     V3 output = vzero();
-    const V3 nrm = sh.ns;
     const WoTerms wt = wo_terms(m, sh, sh.wo);
     for (uint32_t l = 0; l < P.nlights; ++l) { // integrate.rs:47-66
         if (!((vis >> l) & 1u)) continue;
         const DLight L = P.lights[l];
         const LightTerm t = light_term(L, sh);
         if (t.f_att == 0.0) continue;
-        V3 fr = bsdf_f(m, sh, wt, t.wi, t.reflect);
-        V3 li_col{L.intensity[0], L.intensity[1], L.intensity[2]};
-        output = output + (mul_ew(PI * li_col, fr) * t.wi_dot_n / t.f_att);
+        output = output + light_radiance(L, m, sh, wt, t);
     }
-    return output + mul_ew(P.ambient, bsdf_f(m, sh, wt, nrm, bsdf_reflect(sh, sh.wo, nrm))); // integrate.rs:67
+    return output + ambient_term(P, m, sh, wt); // integrate.rs:67
 }
 
 // Camera::sample for sample `sidx` of pixel (x, y) (camera.rs:113-146)
