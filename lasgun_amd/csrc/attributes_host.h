@@ -1,19 +1,12 @@
 // lasgun_amd/csrc/attributes_host.h -- the part of lg_hit_attributes* (query.cpp) that touches no device: the limits, the planes' byte sizes
-// with their overflow checks, the one table of lg_attr_out's planes (attr_planes) with what follows from it -- the NULL and alignment rules,
-// the host forms' staging and its placement --, and the counts table a record of the _of form is checked against: its layout, its builder
+// with their overflow checks, the one table of lg_attr_out's planes (attr_planes) with what follows from it -- the NULL and alignment rules
+// (the size and alignment rules themselves and the host forms' staging are planes_host.h's) --, and the counts table a record of the _of form is checked against: its layout, its builder
 // and the check itself (attr_record_ok: ONE function for the host and for attr_of_kernel, k_attributes.hip).  Arithmetic on size_t that can
 // overflow and an index check that guards every dereference of the _of form, so kept free of HIP: tools/attributes_host_check.cpp runs
-// exactly this text under AddressSanitizer / UBSan on the CPU, and the entry points call it.  Shaped like scatter_host.h and kept apart from
-// it: its plane table names ScatterStaging's members, and tools/scatter_host_check.cpp includes that text as it is.
+// exactly this text under AddressSanitizer / UBSan on the CPU, and the entry points call it.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
 #include "../../include/lasgun_hip.h"
+#include "planes_host.h"
 
 #if defined(__HIPCC__)
 #define LG_ATTR_HD __host__ __device__ __forceinline__
@@ -29,8 +22,6 @@ static_assert(sizeof(lg_attr_out) == 56 && offsetof(lg_attr_out, hits) == 0 && o
 static_assert(sizeof(lg_hit) == 96, "lg_hit: 96 bytes, the widest row of a plane");
 constexpr uint32_t ATTR_HIT = 1u, ATTR_NO_HIT = 2u, ATTR_BAD_RECORD = 4u; // the flag words k_attributes.hip writes
 static_assert(ATTR_HIT == LG_ATTR_HIT && ATTR_NO_HIT == LG_ATTR_NO_HIT && ATTR_BAD_RECORD == LG_ATTR_BAD_RECORD, "the flag words k_attributes.hip writes");
-
-constexpr unsigned long long ATTR_MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits, as lg_intersect's are
 
 // ---- the counts table: what a record may name.  Words: [0] accels, [1] spheres, [2] boxes, [3] 0; then two words per accel -- the face
 // count of the mesh it is (0 for a group) and that mesh's first triangle in the triangle tables --; then per sphere the accel it sits in;
@@ -61,30 +52,17 @@ LG_ATTR_HD bool attr_record_ok(const uint32_t *counts, uint32_t kind, uint32_t p
 // a triangle's index in the triangle tables, for a record attr_record_ok has passed
 LG_ATTR_HD uint32_t attr_triangle_index(const uint32_t *counts, uint32_t prim, uint32_t instance) { return counts[ATTR_COUNTS_HEAD + 2ull * instance + 1ull] + prim; }
 
-// count * bytes_each as a size_t, refused where it does not fit the address space
-inline size_t attr_bytes(size_t count, size_t bytes_each, const char *what) {
-    if (bytes_each && count > SIZE_MAX / bytes_each) throw std::runtime_error(std::string(what) + " does not fit the address space");
-    return count * bytes_each;
-}
-
-// The host forms' outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
-struct AttrStaging {
-    std::vector<lg_hit> hits;
-    std::vector<uint32_t> flags;
-    std::vector<double> bary, uv, local, frame, dp;
-    AttrStaging(const lg_attr_out &out, size_t n);
-};
-// The seven planes of lg_attr_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, the
-// plane's staging, its elements, its alignment in bytes, its name) in the struct's order.  The alignment and NULL rules, the staging's
-// sizes, the host forms' device buffers and copies, the device forms' buffer checks and the placement all go through here.
+// The seven planes of lg_attr_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, its
+// elements, its alignment in bytes, its name) in the struct's order.  The alignment and NULL rules, the host forms' staging, device
+// buffers and copies and the device forms' buffer checks all go through here.
 template <class Out, class F> inline void attr_planes(Out &out, size_t n, F &&f) {
-    f(out.hits, &AttrStaging::hits, n, 16, "hits");
-    f(out.flags, &AttrStaging::flags, n, 4, "flags");
-    f(out.bary, &AttrStaging::bary, n * 3, 8, "bary");
-    f(out.uv, &AttrStaging::uv, n * 2, 8, "uv");
-    f(out.local, &AttrStaging::local, n * 3, 8, "local");
-    f(out.frame, &AttrStaging::frame, n * 6, 8, "frame");
-    f(out.dp, &AttrStaging::dp, n * 6, 8, "dp");
+    f(out.hits, n, 16, "hits");
+    f(out.flags, n, 4, "flags");
+    f(out.bary, n * 3, 8, "bary");
+    f(out.uv, n * 2, 8, "uv");
+    f(out.local, n * 3, 8, "local");
+    f(out.frame, n * 6, 8, "frame");
+    f(out.dp, n * 6, 8, "dp");
 }
 
 // Everything the contract calls an error that needs no device, thrown here; n is not 0 (an empty set is answered before this).  After it no
@@ -96,29 +74,16 @@ inline void check_attributes(const void *accel, const double *rays, const lg_hit
     if (of_form && !records) throw std::runtime_error("hits is NULL");
     if (!out) throw std::runtime_error("out is NULL");
     if (of_form && out->hits) throw std::runtime_error("out->hits is not NULL: the _of form reads records and writes none");
-    bool any = false;
-    attr_planes(*out, 0, [&](auto *p, auto, size_t, size_t, const char *) { any = any || p; });
-    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
-    if ((unsigned long long)n > ATTR_MAX_RAYS) throw std::runtime_error("too many rays in one query");
-    (void)attr_bytes(n, 6 * sizeof(double), "rays");
-    (void)attr_bytes(n, sizeof(lg_hit), "a plane of n rows"); // 96 bytes a row, the widest (hits)
-}
-inline AttrStaging::AttrStaging(const lg_attr_out &out, size_t n) {
-    attr_planes(out, n, [&](auto *p, auto plane, size_t count, size_t, const char *) { if (p) (this->*plane).resize(count); });
-}
-inline void place_attributes(const lg_attr_out &out, const AttrStaging &st) {
-    attr_planes(out, 0, [&](auto *p, auto plane, size_t, size_t, const char *) {
-        if (p && !(st.*plane).empty()) std::memcpy(p, (st.*plane).data(), (st.*plane).size() * sizeof *p);
-    });
+    require_any_plane([&](auto &&f) { attr_planes(*out, 0, f); });
+    if ((unsigned long long)n > QUERY_MAX_RAYS) throw std::runtime_error("too many rays in one query");
+    (void)checked_bytes(n, 6 * sizeof(double), "rays");
+    (void)checked_bytes(n, sizeof(lg_hit), "a plane of n rows"); // 96 bytes a row, the widest (hits)
 }
 // The device forms' alignment rule: rays 8 bytes, the records 16, the planes theirs (hits 16; flags 4; the double planes 8); NULL is not misaligned
 inline void check_attributes_alignment(const double *rays, const lg_hit *records, const lg_attr_out &out) {
-    const auto aligned = [](const void *p, size_t align, const char *what) {
-        if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
-    };
-    aligned(rays, 8, "rays");
-    aligned(records, 16, "hits");
-    attr_planes(out, 0, [&](auto *p, auto, size_t, size_t align, const char *what) { aligned(p, align, what); });
+    check_alignment(rays, 8, "rays");
+    check_alignment(records, 16, "hits");
+    check_planes_alignment([&](auto &&f) { attr_planes(out, 0, f); });
 }
 
 } // namespace lg

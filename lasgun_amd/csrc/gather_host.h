@@ -1,17 +1,12 @@
 // lasgun_amd/csrc/gather_host.h -- the part of lg_radiance_gather* (query.cpp) that touches no device: the lane rule, the two tile counts with
-// their 32-bit limit, the four byte sizes, the NULL and alignment rules, the batch a parked call is cut into, and the host form's staging and
-// placement.  Arithmetic on size_t that can overflow, so kept free of HIP: tools/gather_host_check.cpp runs exactly this text under
+// their 32-bit limit, the four byte sizes, the NULL and alignment rules, and the batch a parked call is cut into (the size and alignment
+// rules themselves and the host form's staging are planes_host.h's).  Arithmetic on size_t that can overflow, so kept free of HIP: tools/gather_host_check.cpp runs exactly this text under
 // AddressSanitizer / UBSan on the CPU, and lg_radiance_gather_lanes and both entry points call it.
 #pragma once
-#include <cstddef>
-#include <cstdint>
 #include <cstdlib>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
 #include "../../include/lasgun_hip.h"
+#include "planes_host.h"
 
 namespace lg {
 
@@ -40,12 +35,7 @@ inline bool gather_tiles(size_t n_poses, size_t n_dirs, int form, unsigned long 
     return true;
 }
 // count * each * bytes as a size_t, refused where it does not fit the address space
-inline size_t gather_bytes(size_t count, size_t each, size_t bytes, const char *what) {
-    if (each && count > SIZE_MAX / each) throw std::runtime_error(std::string(what) + " does not fit the address space");
-    const size_t n = count * each;
-    if (bytes && n > SIZE_MAX / bytes) throw std::runtime_error(std::string(what) + " does not fit the address space");
-    return n * bytes;
-}
+inline size_t gather_bytes(size_t count, size_t each, size_t bytes, const char *what) { return checked_bytes(checked_bytes(count, each, what), bytes, what); }
 
 // What a checked call is: its form, its tiles and its rays
 struct GatherShape {
@@ -81,12 +71,9 @@ inline GatherShape check_gather(const void *accel, const double *origins, size_t
 }
 // The device form's alignment rule: every pointer 8 bytes
 inline void check_gather_alignment(const double *origins, const double *frames, const double *dirs, const double *weights, const lg_gather_out &out) {
-    const auto aligned = [](const void *p, const char *what) {
-        if (p && (uintptr_t)p % 8) throw std::runtime_error(std::string(what) + " is not 8-byte aligned");
-    };
-    aligned(origins, "origins"); aligned(frames, "frames"); aligned(dirs, "dirs");
-    if (out.sums) aligned(weights, "weights");
-    aligned(out.radiance, "radiance"); aligned(out.sums, "sums");
+    check_alignment(origins, 8, "origins"); check_alignment(frames, 8, "frames"); check_alignment(dirs, 8, "dirs");
+    if (out.sums) check_alignment(weights, 8, "weights");
+    check_alignment(out.radiance, 8, "radiance"); check_alignment(out.sums, 8, "sums");
 }
 
 // LASGUN_GATHER_PARK_MB as bytes a batch may park: a positive integer of MiB, anything else (and no value) the default; clamped so that
@@ -109,19 +96,6 @@ inline size_t gather_batch_poses(size_t n_poses, size_t n_dirs, int form, size_t
     if (b < 1) b = 1;
     if (form == GATHER_POSE_LANES && b >= 64) b -= b % 64;
     return b < n_poses ? b : n_poses;
-}
-
-// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
-struct GatherStaging {
-    std::vector<double> radiance, sums;
-    GatherStaging(const lg_gather_out &out, size_t pairs, size_t n_poses, size_t n_weights) {
-        if (out.radiance) radiance.resize(pairs * 3);
-        if (out.sums) sums.resize(n_poses * n_weights * 3);
-    }
-};
-inline void place_gather(const lg_gather_out &out, const GatherStaging &st) {
-    if (out.radiance && !st.radiance.empty()) std::memcpy(out.radiance, st.radiance.data(), st.radiance.size() * sizeof(double));
-    if (out.sums && !st.sums.empty()) std::memcpy(out.sums, st.sums.data(), st.sums.size() * sizeof(double));
 }
 
 } // namespace lg

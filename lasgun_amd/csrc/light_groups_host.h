@@ -5,23 +5,16 @@
 // a caller's array, so kept free of HIP: tools/light_groups_host_check.cpp runs exactly this text under AddressSanitizer / UBSan on the
 // CPU, and both entry points call it.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
 #include "../../include/lasgun_hip.h"
+#include "planes_host.h"
 
 namespace lg {
 
 static_assert(sizeof(lg_light_group) == 8 && offsetof(lg_light_group, lights) == 0 && offsetof(lg_light_group, flags) == 4, "lg_light_group: two 32-bit words");
 static_assert(LG_MAX_LIGHT_GROUPS == 64 && LG_GROUP_AMBIENT == 1u, "the constants of the contract");
 
-constexpr unsigned long long GROUPS_MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits, as lg_radiance's are
 constexpr uint32_t GROUPS_KNOWN_FLAGS = LG_GROUP_AMBIENT;
-constexpr size_t GROUPS_MAX_LIGHTS = 32;                              // the level-by-level pipeline's visibility word
+constexpr size_t GROUPS_MAX_LIGHTS = 32; // the level-by-level pipeline's visibility word
 
 // the checked table of a call: what every launch is handed by value
 struct GroupTable {
@@ -51,7 +44,7 @@ inline GroupsShape check_light_groups(const void *accel, const double *rays, siz
         const uint32_t beyond = n_lights >= 32 ? 0u : groups[g].lights >> n_lights; // (a shift by 32 is not one C++ defines)
         if (beyond) throw std::runtime_error("groups[" + std::to_string(g) + "].lights names a light the scene does not have (" + std::to_string(n_lights) + " lights)");
     }
-    if ((unsigned long long)n > GROUPS_MAX_RAYS) throw std::runtime_error("too many rays in one query");
+    if ((unsigned long long)n > QUERY_MAX_RAYS) throw std::runtime_error("too many rays in one query");
     if (n > SIZE_MAX / (n_groups * 3 * sizeof(double))) throw std::runtime_error("n * n_groups * 24 does not fit the address space");
     if (n > SIZE_MAX / (6 * sizeof(double))) throw std::runtime_error("rays does not fit the address space");
     std::memset(&table, 0, sizeof table);
@@ -59,22 +52,10 @@ inline GroupsShape check_light_groups(const void *accel, const double *rays, siz
     table.n_groups = (uint32_t)n_groups;
     return GroupsShape{n * 6, n_groups * n * 3};
 }
-// The host form's planes on their way back: the copy from the device lands here and reaches the caller's array after the synchronise, so
-// an error on the way leaves that array as it was.
-struct GroupsStaging {
-    std::vector<double> radiance;
-    explicit GroupsStaging(const GroupsShape &shape) : radiance(shape.out_doubles) {}
-};
-inline void place_light_groups(double *radiance, const GroupsStaging &st) {
-    if (!st.radiance.empty()) std::memcpy(radiance, st.radiance.data(), st.radiance.size() * sizeof(double));
-}
 // The device form's alignment rule: 8 bytes for both buffers
 inline void check_light_groups_alignment(const double *rays, const double *radiance) {
-    const auto aligned = [](const void *p, const char *what) {
-        if (p && (uintptr_t)p % 8) throw std::runtime_error(std::string(what) + " is not 8-byte aligned");
-    };
-    aligned(rays, "rays");
-    aligned(radiance, "radiance");
+    check_alignment(rays, 8, "rays");
+    check_alignment(radiance, 8, "radiance");
 }
 
 } // namespace lg

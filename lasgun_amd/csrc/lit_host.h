@@ -1,8 +1,8 @@
 // lasgun_amd/csrc/lit_host.h -- the part of lg_scatter_lit* (query.cpp) that touches no device: the light set's rules, W, every size with its
-// overflow check, and the one table of lg_lit_out's nine planes (lit_planes) with what follows from it: the NULL and alignment rules, the
-// host form's staging and its placement.  Arithmetic on size_t that can overflow, so kept free of HIP: tools/lit_host_check.cpp runs exactly
-// this text under AddressSanitizer / UBSan on the CPU, and both entry points call it.  Shaped like scatter_host.h, whose limits and byte
-// arithmetic it uses, and kept apart from it: its plane table names LitStaging's members.
+// overflow check, and the one table of lg_lit_out's nine planes (lit_planes) with what follows from it: the NULL and alignment rules.
+// Arithmetic on size_t that can overflow, so kept free of HIP: tools/lit_host_check.cpp runs exactly this text under AddressSanitizer /
+// UBSan on the CPU, and both entry points call it.  Its table begins with scatter_host.h's, whose light limit it shares; the size and
+// alignment rules themselves and the host form's staging are planes_host.h's.
 #pragma once
 #include "scatter_host.h"
 
@@ -28,23 +28,14 @@ struct LitSizes {
     size_t lights = 0;   // records of the light table: K, or n * K per ray
 };
 
-// The host form's outputs on their way back: only what is asked for has any size
-struct LitStaging {
-    ScatterStaging scatter;
-    std::vector<double> terms;
-    std::vector<uint32_t> visible;
-    LitStaging(const lg_lit_out &out, const LitSizes &z);
-};
-// The nine planes of lg_lit_out (or of a copy that f may edit): the seven of scatter_planes through the staging's `scatter`, then the two
-// of the lights, each written down here and nowhere else: f(the struct's pointer, a function that gives the plane's staging vector, its
-// elements, its alignment in bytes, its name) in the struct's order.  With K == 0 terms and visible have no elements and are not planes.
+// The nine planes of lg_lit_out (or of a copy that f may edit): the seven of scatter_planes, then the two of the lights, each written down
+// here and nowhere else: f(the struct's pointer, its elements, its alignment in bytes, its name) in the struct's order.  With K == 0 terms
+// and visible have no elements and are not planes.
 template <class Out, class F> inline void lit_planes(Out &out, const LitSizes &z, F &&f) {
-    scatter_planes(out.scatter, z.n, [&](auto *&p, auto plane, size_t count, size_t align, const char *what) {
-        f(p, [plane](auto &st) -> auto & { return st.scatter.*plane; }, count, align, what);
-    });
+    scatter_planes(out.scatter, z.n, f);
     if (z.K) {
-        f(out.terms, [](auto &st) -> auto & { return st.terms; }, z.terms, (size_t)8, "terms");
-        f(out.visible, [](auto &st) -> auto & { return st.visible; }, z.visible, (size_t)4, "visible");
+        f(out.terms, z.terms, 8, "terms");
+        f(out.visible, z.visible, 4, "visible");
     }
 }
 
@@ -61,45 +52,25 @@ inline LitSizes check_lit(const void *accel, const double *rays, size_t n, const
     if (lights->count && !lights->lights) throw std::runtime_error("lights->lights is NULL with count > 0");
     LitSizes z;
     z.n = n; z.K = lights->count; z.W = lit_words(lights->count);
-    bool any = false;
-    {
-        lg_lit_out probe = *out;
-        lit_planes(probe, z, [&](auto *p, auto, size_t, size_t, const char *) { any = any || p; });
-    }
-    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
-    (void)scatter_bytes(n, 6 * sizeof(double), "rays");
-    (void)scatter_bytes(n, sizeof(lg_hit), "a plane of n rows");
-    const size_t nk = scatter_bytes(n, z.K, "n * count");              // n * K
-    (void)scatter_bytes(nk, sizeof(lg_light), "a light table per ray"); // n * K * 72, whichever form the call takes: one rule
-    (void)scatter_bytes(nk, 3 * sizeof(double), "terms");              // n * K * 24
+    require_any_plane([&](auto &&f) { lit_planes(*out, z, f); });
+    (void)checked_bytes(n, 6 * sizeof(double), "rays");
+    (void)checked_bytes(n, sizeof(lg_hit), "a plane of n rows");
+    const size_t nk = checked_bytes(n, z.K, "n * count");              // n * K
+    (void)checked_bytes(nk, sizeof(lg_light), "a light table per ray"); // n * K * 72, whichever form the call takes: one rule
+    (void)checked_bytes(nk, 3 * sizeof(double), "terms");              // n * K * 24
     z.terms = nk * 3;
-    (void)scatter_bytes(scatter_bytes(n, z.W, "n * words"), sizeof(uint32_t), "visible"); // n * W * 4
+    (void)checked_bytes(checked_bytes(n, z.W, "n * words"), sizeof(uint32_t), "visible"); // n * W * 4
     z.visible = n * z.W;
     z.lights = lights->per_ray ? nk : z.K;
-    if ((unsigned long long)n > SCATTER_MAX_RAYS) throw std::runtime_error("too many rays in one query"); // (behind the sizes: with a 64-bit size_t none of them can wrap below this limit)
+    if ((unsigned long long)n > QUERY_MAX_RAYS) throw std::runtime_error("too many rays in one query"); // (behind the sizes: with a 64-bit size_t none of them can wrap below this limit)
     return z;
-}
-inline LitStaging::LitStaging(const lg_lit_out &out, const LitSizes &z) : scatter(out.scatter, 0) {
-    lg_lit_out o = out;
-    lit_planes(o, z, [&](auto *p, auto member, size_t count, size_t, const char *) { if (p) member(*this).resize(count); });
-}
-inline void place_lit(const lg_lit_out &out, const LitSizes &z, const LitStaging &st) {
-    lg_lit_out o = out;
-    lit_planes(o, z, [&](auto *p, auto member, size_t, size_t, const char *) {
-        const auto &v = member(st);
-        if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof *p);
-    });
 }
 // The device form's alignment rule: rays 8 bytes, the planes theirs (lg_scatter's; terms 8, visible 4), a per-ray light table 8; NULL is
 // not misaligned
 inline void check_lit_alignment(const double *rays, const lg_light_set &lights, const lg_lit_out &out, const LitSizes &z) {
-    const auto aligned = [](const void *p, size_t align, const char *what) {
-        if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
-    };
-    aligned(rays, 8, "rays");
-    if (lights.per_ray && z.K) aligned(lights.lights, 8, "lights->lights");
-    lg_lit_out o = out;
-    lit_planes(o, z, [&](auto *p, auto, size_t, size_t align, const char *what) { aligned(p, align, what); });
+    check_alignment(rays, 8, "rays");
+    if (lights.per_ray && z.K) check_alignment(lights.lights, 8, "lights->lights");
+    check_planes_alignment([&](auto &&f) { lit_planes(out, z, f); });
 }
 
 } // namespace lg

@@ -1,18 +1,11 @@
 // lasgun_amd/csrc/paths_host.h -- the part of lg_trace_paths* (query.cpp) that touches no device: the limits, the product n * max_bounces
 // and the planes' byte sizes with their overflow checks, the rule table's validation, and the one table of lg_paths_out's planes
-// (path_planes) with what follows from it: the NULL and alignment rules, the host form's staging and its placement.  Arithmetic on size_t
-// that can overflow, so kept free of HIP: tools/paths_host_check.cpp runs exactly this text under AddressSanitizer / UBSan on the CPU, and
-// both entry points call it.  Shaped like layers_host.h and kept apart from it: its plane table names LayersStaging's members, and
-// tools/layers_host_check.cpp includes that text as it is.
+// (path_planes) with what follows from it: the NULL and alignment rules (the size and alignment rules themselves and the host form's
+// staging are planes_host.h's).  Arithmetic on size_t that can overflow, so kept free of HIP: tools/paths_host_check.cpp runs exactly this
+// text under AddressSanitizer / UBSan on the CPU, and both entry points call it.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
 #include "../../include/lasgun_hip.h"
+#include "planes_host.h"
 
 namespace lg {
 
@@ -25,38 +18,19 @@ static_assert(sizeof(lg_paths_out) == 72 && offsetof(lg_paths_out, hits) == 0 &&
               "lg_paths_out: nine pointers, 72 bytes");
 static_assert(sizeof(lg_hit) == 96, "lg_hit: 96 bytes, the widest element of a vertex plane");
 
-constexpr unsigned long long PATHS_MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits, as lg_intersect's are
-
-// count * bytes_each as a size_t, refused where it does not fit the address space
-inline size_t paths_bytes(size_t count, size_t bytes_each, const char *what) {
-    if (bytes_each && count > SIZE_MAX / bytes_each) throw std::runtime_error(std::string(what) + " does not fit the address space");
-    return count * bytes_each;
-}
-
-// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
-struct PathsStaging {
-    std::vector<lg_hit> hits;
-    std::vector<double> point;
-    std::vector<uint32_t> id;
-    std::vector<double> along;
-    std::vector<uint32_t> count, end;
-    std::vector<double> gain, last;
-    std::vector<uint32_t> medium;
-    PathsStaging(const lg_paths_out &out, size_t n, size_t total);
-};
-// The nine planes of lg_paths_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, the
-// plane's staging, its elements, its alignment in bytes, its name) in the struct's order; total = n * max_bounces.  The alignment and NULL
-// rules, the staging's sizes, the host form's device buffers and copies, the device form's buffer checks and the placement all go through here.
+// The nine planes of lg_paths_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, its
+// elements, its alignment in bytes, its name) in the struct's order; total = n * max_bounces.  The alignment and NULL rules, the host
+// form's staging, device buffers and copies and the device form's buffer checks all go through here.
 template <class Out, class F> inline void path_planes(Out &out, size_t n, size_t total, F &&f) {
-    f(out.hits, &PathsStaging::hits, total, 16, "hits");
-    f(out.point, &PathsStaging::point, total * 3, 8, "point");
-    f(out.id, &PathsStaging::id, total * 4, 16, "id");
-    f(out.along, &PathsStaging::along, total, 8, "along");
-    f(out.count, &PathsStaging::count, n, 4, "count");
-    f(out.end, &PathsStaging::end, n, 4, "end");
-    f(out.gain, &PathsStaging::gain, n, 8, "gain");
-    f(out.last, &PathsStaging::last, n * 6, 8, "last");
-    f(out.medium, &PathsStaging::medium, n, 4, "medium");
+    f(out.hits, total, 16, "hits");
+    f(out.point, total * 3, 8, "point");
+    f(out.id, total * 4, 16, "id");
+    f(out.along, total, 8, "along");
+    f(out.count, n, 4, "count");
+    f(out.end, n, 4, "end");
+    f(out.gain, n, 8, "gain");
+    f(out.last, n * 6, 8, "last");
+    f(out.medium, n, 4, "medium");
 }
 
 // The rule table: exactly one rule per material of the accel, a known action, reserved 0
@@ -78,35 +52,22 @@ inline size_t check_paths(const void *accel, const double *rays, size_t n, uint3
     if (!accel) throw std::runtime_error("accel is NULL");
     if (!rays) throw std::runtime_error("rays is NULL");
     if (!out) throw std::runtime_error("out is NULL");
-    bool any = false;
-    path_planes(*out, 0, 0, [&](auto *p, auto, size_t, size_t, const char *) { any = any || p; });
-    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
+    require_any_plane([&](auto &&f) { path_planes(*out, 0, 0, f); });
     if (max_bounces == 0) throw std::runtime_error("max_bounces is 0: at least one vertex");
     if (normal != 0 && normal != 1) throw std::runtime_error("normal is " + std::to_string(normal) + ": 0 (lg_hit::ng) or 1 (lg_hit::ns)");
-    if ((unsigned long long)n > PATHS_MAX_RAYS) throw std::runtime_error("too many rays in one query");
+    if ((unsigned long long)n > QUERY_MAX_RAYS) throw std::runtime_error("too many rays in one query");
     if (n > SIZE_MAX / max_bounces) throw std::runtime_error("n * max_bounces does not fit the address space");
     const size_t total = n * (size_t)max_bounces;
-    (void)paths_bytes(n, 6 * sizeof(double), "rays");
-    (void)paths_bytes(total, sizeof(lg_hit), "a plane of n * max_bounces elements"); // 96 bytes an element, the widest (hits)
+    (void)checked_bytes(n, 6 * sizeof(double), "rays");
+    (void)checked_bytes(total, sizeof(lg_hit), "a plane of n * max_bounces elements"); // 96 bytes an element, the widest (hits)
     check_path_rules(rules, n_rules, material_count);
     return total;
 }
-inline PathsStaging::PathsStaging(const lg_paths_out &out, size_t n, size_t total) {
-    path_planes(out, n, total, [&](auto *p, auto plane, size_t count, size_t, const char *) { if (p) (this->*plane).resize(count); });
-}
-inline void place_paths(const lg_paths_out &out, const PathsStaging &st) {
-    path_planes(out, 0, 0, [&](auto *p, auto plane, size_t, size_t, const char *) {
-        if (p && !(st.*plane).empty()) std::memcpy(p, (st.*plane).data(), (st.*plane).size() * sizeof *p);
-    });
-}
 // The device form's alignment rule: rays 8 bytes, start_medium 4, the planes theirs; NULL is not misaligned
 inline void check_paths_alignment(const double *rays, const uint32_t *start_medium, const lg_paths_out &out) {
-    const auto aligned = [](const void *p, size_t align, const char *what) {
-        if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
-    };
-    aligned(rays, 8, "rays");
-    aligned(start_medium, 4, "start_medium");
-    path_planes(out, 0, 0, [&](auto *p, auto, size_t, size_t align, const char *what) { aligned(p, align, what); });
+    check_alignment(rays, 8, "rays");
+    check_alignment(start_medium, 4, "start_medium");
+    check_planes_alignment([&](auto &&f) { path_planes(out, 0, 0, f); });
 }
 
 } // namespace lg

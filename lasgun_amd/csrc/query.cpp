@@ -6,8 +6,10 @@
 // alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
 // (enqueue_scatter_lit; k_lit.hip; lit_host.h).  With
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
-// its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below); what a plane of lg_scan_out /
-// lg_layers_out / lg_paths_out / lg_features is, is scan_host.h's / layers_host.h's / paths_host.h's / features_host.h's one table, what a bit row is, bitrows_host.h's: device-free text, sanitized on the CPU.
+// its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below), whose host-memory half is
+// planes_host.h's HostStaging; what a plane of a query's output struct is, is that query's one table (scan_host.h, layers_host.h,
+// attributes_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
+// helpers below; what a bit row is, is bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
 
@@ -17,6 +19,7 @@
 #include "gather_host.h"
 #include "layers_host.h"
 #include "paths_host.h"
+#include "planes_host.h"
 #include "scatter_host.h"
 #include "lit_host.h"
 #include "light_groups_host.h"
@@ -30,7 +33,6 @@ static_assert(sizeof(lg_hit) == 96 && offsetof(lg_hit, p) == 8 && offsetof(lg_hi
               "lg_hit: the layout k_query.hip writes (six 16-byte stores per hit)");
 static_assert(sizeof(lg_material) == sizeof(Material), "lg_material wraps Material");
 
-static constexpr unsigned long long MAX_RAYS = 0xFFFFFFFFull * 64ull; // 64-ray tiles are counted in 32 bits
 static constexpr unsigned long long MAX_SORTED_RAYS = 0xFFFFFFFFull;  // the sorted order's indices are 32-bit
 // A query of at most 64 rays is one wave's tile whatever the order: it is walked as given (the same bytes; lg_query_order* sort any n)
 static constexpr size_t SORT_MIN_RAYS = 65;
@@ -130,12 +132,13 @@ static void check_sorted_count(const lg_accel &a, size_t n) {
 // the inputs up, enqueues, copies the outputs down, synchronises and places what was staged, all in that order.  An output is DIRECT (out: the
 // copy lands in the caller's memory), STAGED (staged: it lands in a buffer of this call's and reaches the caller's array after the synchronise:
 // an error on the way leaves that array as it was) or HELD (held: staged, and the form places it).  A NULL array is one not asked for: NULL.
+// The device buffers and the copies are here; the buffers of this call's and their placement are `staging` (planes_host.h).
 class RoundTrip {
     struct Copy { void *to; const void *from; size_t bytes; };
     const lg_accel &a;
     std::deque<DevBuf<uint8_t>> mem;
-    std::deque<std::vector<uint8_t>> stage;
-    std::vector<Copy> up, down, place;
+    HostStaging staging;
+    std::vector<Copy> up, down;
     template <class T> T *device(size_t n) { mem.emplace_back(); mem.back().alloc(std::max<size_t>(n, 1) * sizeof(T)); return reinterpret_cast<T *>(mem.back().p); }
 
   public:
@@ -155,17 +158,11 @@ class RoundTrip {
     }
     template <class T> T *out(T *host, size_t n) { return host ? out(host, n, n) : nullptr; }
     template <class T> T *held(size_t n, const T **staged) {
-        stage.emplace_back(n * sizeof(T));
-        *staged = reinterpret_cast<const T *>(stage.back().data());
-        return out(reinterpret_cast<T *>(stage.back().data()), n, n);
+        T *s = staging.hold<T>(n);
+        *staged = s;
+        return out(s, n, n);
     }
-    template <class T> T *staged(T *host, size_t n) {
-        if (!host) return nullptr;
-        const T *s = nullptr;
-        T *d = held(n, &s);
-        place.push_back({host, s, n * sizeof(T)});
-        return d;
-    }
+    template <class T> T *staged(T *host, size_t n) { return host ? out(staging.stage(host, n), n, n) : nullptr; }
     // a copy down from device memory that is not this call's, for the enqueue to ask for (it precedes the outputs')
     void download(void *host, const void *dev, size_t bytes) { HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, a.stream)); }
     template <class Enqueue> void run(Enqueue &&enqueue) {
@@ -173,9 +170,18 @@ class RoundTrip {
         enqueue();
         for (const Copy &c : down) download(c.to, c.from, c.bytes);
         sync_checked(a);
-        for (const Copy &c : place) std::memcpy(c.to, c.from, c.bytes);
+        staging.place();
     }
 };
+// The visitor of a plane table (planes_host.h) for a host form, over a copy of the caller's struct: every plane asked for becomes its device
+// buffer, staged; `each`: the table counts elements a pixel, and a plane has that many times `each`
+static auto staged_planes(RoundTrip &trip, size_t each = 1) {
+    return [&trip, each](auto *&p, size_t count, size_t, const char *) { p = trip.staged(p, count * each); };
+}
+// ... and for a device form, over the caller's struct: every plane asked for is a device buffer of the accel's, aligned and long enough
+static auto device_planes(const lg_accel &a, size_t each = 1) {
+    return [&a, each](auto *p, size_t count, size_t align, const char *what) { if (p) check_device_buffer(a, p, count * each * sizeof *p, align, what); };
+}
 
 // Both host forms: the rays up, the query on the accel's stream, the results straight back (as lg_capture_pixels)
 static int query_host(const lg_accel *a, const double *rays, size_t n, void *out, bool any) {
@@ -184,7 +190,7 @@ static int query_host(const lg_accel *a, const double *rays, size_t n, void *out
         if (!a) throw Error("accel is NULL");
         if (!rays) throw Error("rays is NULL");
         if (!out) throw Error(any ? "occluded is NULL" : "hits is NULL");
-        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        if (n > QUERY_MAX_RAYS) throw Error("too many rays in one query");
         const size_t out_bytes = n * (any ? 1u : sizeof(lg_hit));
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
@@ -198,7 +204,7 @@ static int query_device(const lg_accel *a, const double *dev_rays, size_t n, voi
     return guarded([&] {
         if (n == 0) return;
         if (!a) throw Error("accel is NULL");
-        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        if (n > QUERY_MAX_RAYS) throw Error("too many rays in one query");
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         use_device(a->device);
@@ -324,7 +330,7 @@ extern "C" int lg_open_directions_device(const lg_accel *a, const double *dev_po
 
 // ---- range scans (lg_range_scan*; k_scan.hip): the rays (origins[i], frames[i] * beams[k]) made in the kernel, their first hits written
 // as planes and reduced per pose.  The arithmetic that needs no device -- the lane rule, the tile counts, the sizes, the NULL and
-// alignment rules, the staging -- is scan_host.h's.
+// alignment rules -- is scan_host.h's.
 extern "C" int lg_range_scan_lanes(size_t n_poses, size_t n_beams, int lanes) { return scan_lanes(n_poses, n_beams, lanes); }
 // One scan enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts and buffers): the two
 // pre-fills, then the kernel in the shape's form
@@ -339,7 +345,7 @@ static void enqueue_range_scan(const lg_accel &a, const double *origins, const d
     HIP_TRY(launch_range_scan(P, origins, frames, n_poses, beams, n_beams, shape.form == SCAN_POSE_LANES, out.range, out.point, out.normal, out.id, out.hits,
                               reinterpret_cast<uint32_t *>(out.nearest), a.accel_tri_base.p, a.fast, g.blocks, g.depth, stream));
 }
-// Host form: the tables go up, the planes come back into staging and are copied out at the end
+// Host form: the tables go up, the planes come back staged
 extern "C" int lg_range_scan(const lg_accel *a, const double *origins, const double *frames, size_t n_poses, const double *beams, size_t n_beams, int lanes,
                              const lg_scan_out *out) {
     return guarded([&] {
@@ -348,12 +354,10 @@ extern "C" int lg_range_scan(const lg_accel *a, const double *origins, const dou
         const size_t pairs = shape.pairs;
         std::lock_guard<std::mutex> g(a->mtx);
         RoundTrip trip(*a);
-        ScanStaging st(*out, n_poses, pairs);
         const double *dorigins = trip.in(origins, n_poses * 3), *dframes = trip.in(frames, n_poses * 9), *dbeams = trip.in(beams, n_beams * 3);
-        lg_scan_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        scan_planes(dev, n_poses, pairs, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        lg_scan_out dev = *out; // ... where a plane asked for becomes its device buffer
+        scan_planes(dev, n_poses, pairs, staged_planes(trip));
         trip.run([&] { enqueue_range_scan(*a, dorigins, dframes, n_poses, dbeams, n_beams, shape, dev, a->stream); });
-        place_scan(*out, st);
     });
 }
 extern "C" int lg_range_scan_device(const lg_accel *a, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_beams, size_t n_beams,
@@ -368,7 +372,7 @@ extern "C" int lg_range_scan_device(const lg_accel *a, const double *dev_origins
         check_device_buffer(*a, dev_origins, n_poses * 3 * sizeof(double), 8, "origins");
         if (dev_frames) check_device_buffer(*a, dev_frames, n_poses * 9 * sizeof(double), 8, "frames");
         check_device_buffer(*a, dev_beams, n_beams * 3 * sizeof(double), 8, "beams");
-        scan_planes(*dev_out, n_poses, pairs, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        scan_planes(*dev_out, n_poses, pairs, device_planes(*a));
         enqueue_range_scan(*a, dev_origins, dev_frames, n_poses, dev_beams, n_beams, shape, *dev_out, (hipStream_t)hip_stream);
     });
 }
@@ -394,7 +398,7 @@ extern "C" int lg_radiance(const lg_accel *a, const double *rays, size_t n, doub
         if (!a) throw Error("accel is NULL");
         if (!rays) throw Error("rays is NULL");
         if (!radiance) throw Error("radiance is NULL");
-        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        if (n > QUERY_MAX_RAYS) throw Error("too many rays in one query");
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         radiance_possible(*a);
@@ -408,7 +412,7 @@ extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, siz
     return guarded([&] {
         if (n == 0) return;
         if (!a) throw Error("accel is NULL");
-        if (n > MAX_RAYS) throw Error("too many rays in one query");
+        if (n > QUERY_MAX_RAYS) throw Error("too many rays in one query");
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         radiance_possible(*a);
@@ -420,8 +424,8 @@ extern "C" int lg_radiance_device(const lg_accel *a, const double *dev_rays, siz
 }
 
 // ---- light groups (lg_radiance_groups*; launch.cpp, enqueue_radiance_groups; k_light_groups.hip): the radiance query with n_groups planes
-// of li per ray.  What needs no device -- the limits, a group's rules, the sizes, the NULL and alignment rules, the table as it travels, the
-// host form's staging -- is light_groups_host.h's.
+// of li per ray.  What needs no device -- the limits, a group's rules, the sizes, the NULL and alignment rules, the table as it travels -- is
+// light_groups_host.h's.
 static_assert(sizeof(DLightGroup) == sizeof(lg_light_group) && MAX_LIGHT_GROUPS == LG_MAX_LIGHT_GROUPS && GROUP_AMBIENT == LG_GROUP_AMBIENT, "dscene.h restates the contract's group");
 extern "C" int lg_accel_light_count(const lg_accel *a) { return a ? (int)a->flat.lights.size() : -1; }
 // One call enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers)
@@ -441,11 +445,9 @@ extern "C" int lg_radiance_groups(const lg_accel *a, const double *rays, size_t 
         check_sorted_count(*a, n);
         radiance_possible(*a);
         RoundTrip trip(*a);
-        GroupsStaging st(shape);
         const double *drays = trip.in(rays, shape.ray_doubles);
-        double *dout = trip.out(st.radiance.data(), shape.out_doubles);
+        double *dout = trip.staged(radiance, shape.out_doubles);
         trip.run([&] { enqueue_groups_query(*a, drays, n, table, dout, a->stream); });
-        place_light_groups(radiance, st);
     });
 }
 extern "C" int lg_radiance_groups_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_light_group *groups, size_t n_groups, double *dev_radiance,
@@ -468,7 +470,7 @@ extern "C" int lg_radiance_groups_device(const lg_accel *a, const double *dev_ra
 
 // ---- radiance gathers (lg_radiance_gather*; launch.cpp, enqueue_radiance_gather; k_gather.hip): li() of the rays (origins[i], frames[i] *
 // dirs[k]) made in the kernel, written as a plane and / or reduced per pose by the caller's weights.  The arithmetic that needs no device --
-// the lane rule, the tile counts, the sizes, the NULL and alignment rules, the batch, the staging -- is gather_host.h's.
+// the lane rule, the tile counts, the sizes, the NULL and alignment rules, the batch -- is gather_host.h's.
 extern "C" int lg_radiance_gather_lanes(size_t n_poses, size_t n_dirs, int lanes) { return gather_lanes(n_poses, n_dirs, lanes); }
 // One gather enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked counts, scene and buffers)
 static void enqueue_gather(const lg_accel &a, const double *origins, const double *frames, size_t n_poses, const double *dirs, size_t n_dirs, const double *weights,
@@ -479,7 +481,7 @@ static void enqueue_gather(const lg_accel &a, const double *origins, const doubl
     const GatherCall g{origins, frames, dirs, out.sums ? weights : nullptr, n_poses, n_dirs, out.sums ? n_weights : 0, shape.form == GATHER_POSE_LANES, out.radiance, out.sums, batch};
     enqueue_radiance_gather(a, g, ctx_for(a, stream), stream);
 }
-// Host form: the tables go up, the outputs come back into staging and are copied out at the end
+// Host form: the tables go up, the outputs come back staged
 extern "C" int lg_radiance_gather(const lg_accel *a, const double *origins, const double *frames, size_t n_poses, const double *dirs, size_t n_dirs, const double *weights,
                                   size_t n_weights, int lanes, const lg_gather_out *out) {
     return guarded([&] {
@@ -488,14 +490,10 @@ extern "C" int lg_radiance_gather(const lg_accel *a, const double *origins, cons
         std::lock_guard<std::mutex> g(a->mtx);
         radiance_possible(*a);
         RoundTrip trip(*a);
-        GatherStaging st(*out, shape.pairs, n_poses, n_weights);
         const double *dorigins = trip.in(origins, n_poses * 3), *dframes = trip.in(frames, n_poses * 9), *ddirs = trip.in(dirs, n_dirs * 3);
         const double *dweights = out->sums ? trip.in(weights, n_dirs * n_weights) : nullptr;
-        lg_gather_out dev = *out; // ... where an output asked for becomes its device buffer, which comes back into its staging
-        if (dev.radiance) dev.radiance = trip.out(st.radiance.data(), st.radiance.size());
-        if (dev.sums) dev.sums = trip.out(st.sums.data(), st.sums.size());
+        const lg_gather_out dev{trip.staged(out->radiance, shape.pairs * 3), trip.staged(out->sums, n_poses * n_weights * 3)};
         trip.run([&] { enqueue_gather(*a, dorigins, dframes, n_poses, ddirs, n_dirs, dweights, n_weights, shape, dev, a->stream); });
-        place_gather(*out, st);
     });
 }
 extern "C" int lg_radiance_gather_device(const lg_accel *a, const double *dev_origins, const double *dev_frames, size_t n_poses, const double *dev_dirs, size_t n_dirs,
@@ -521,7 +519,7 @@ extern "C" int lg_radiance_gather_device(const lg_accel *a, const double *dev_or
 // pixels * samples as a ray count lg_radiance accepts
 static size_t film_ray_count(const lg_accel &a, size_t pixels, uint32_t samples) {
     if (samples == 0) throw Error("samples is 0: a pixel slot has at least one ray");
-    if (pixels > MAX_RAYS / samples) throw Error("too many rays in one query (pixels * samples)");
+    if (pixels > QUERY_MAX_RAYS / samples) throw Error("too many rays in one query (pixels * samples)");
     const size_t n = pixels * (size_t)samples;
     check_sorted_count(a, n);
     return n;
@@ -724,21 +722,25 @@ static void enqueue_features(const lg_accel &a, uint32_t w, uint32_t h, uint32_t
     HIP_TRY(launch_features(P, out.depth, out.normal, out.albedo, out.coverage, out.id, out.albedo ? material_rgb : nullptr, (uint32_t)a.flat.material_pods.size(),
                             a.accel_tri_base.p, a.fast, g.blocks, g.depth, stream));
 }
-// Host form: the table goes up, the rectangle's pixels come back COMPACT into staging and are placed at their film offsets here -- nothing
-// outside the rectangle is read or written, and an error on the way leaves the caller's planes as they were
+// Host form: the table goes up, the rectangle's pixels come back COMPACT into held buffers and are placed at their film offsets here --
+// nothing outside the rectangle is read or written, and an error on the way leaves the caller's planes as they were
 extern "C" int lg_capture_features(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *material_rgb) {
     return guarded([&] {
         const size_t pixels = check_features(a, out, w, h, x0, y0, x1, y1, material_rgb);
         if (pixels == 0) return;
         std::lock_guard<std::mutex> g(a->mtx);
         RoundTrip trip(*a);
-        FeatureStaging st(*out, pixels);
-        lg_features dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        feature_planes(dev, [&](auto *&p, auto plane, size_t per_pixel, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), pixels * per_pixel); });
+        lg_features dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into compact[its place in the table]
+        std::vector<const void *> compact;
+        feature_planes(dev, [&](auto *&p, size_t per_pixel, size_t, const char *) {
+            const std::remove_reference_t<decltype(*p)> *rows = nullptr;
+            if (p) p = trip.held(pixels * per_pixel, &rows);
+            compact.push_back(rows);
+        });
         // the table for albedo alone (a scene without materials: an element to point at, nothing copied)
         const double *dtable = out->albedo ? trip.in(material_rgb, a->flat.material_pods.size() * 3) : nullptr;
         trip.run([&] { enqueue_features(*a, w, h, x0, y0, x1, y1, dev, dtable, true, a->stream); });
-        place_features(*out, st, w, x0, y0, x1, y1);
+        place_features(*out, compact.data(), w, x0, y0, x1, y1);
     });
 }
 extern "C" int lg_capture_features_device(const lg_accel *a, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const lg_features *out, const double *dev_material_rgb,
@@ -748,7 +750,7 @@ extern "C" int lg_capture_features_device(const lg_accel *a, uint32_t w, uint32_
         std::lock_guard<std::mutex> g(a->mtx);
         use_device(a->device);
         const size_t npix = (size_t)w * h, nmat = a->flat.material_pods.size();
-        feature_planes(*out, [&](auto *p, auto, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, npix * per_pixel * sizeof *p, align, what); });
+        feature_planes(*out, device_planes(*a, npix));
         if (out->albedo) check_device_buffer(*a, dev_material_rgb, nmat * 3 * sizeof(double), 8, "material_rgb");
         enqueue_features(*a, w, h, x0, y0, x1, y1, *out, dev_material_rgb, false, (hipStream_t)hip_stream);
     });
@@ -785,7 +787,7 @@ extern "C" int lg_capture_view_features(const lg_accel *a, const lg_view *views,
         std::lock_guard<std::mutex> g(a->mtx);
         RoundTrip trip(*a);
         lg_view_features dev = *out; // ... where a plane asked for becomes its device buffer
-        view_feature_planes(dev, [&](auto *&p, size_t per_pixel, size_t, const char *) { p = trip.staged(p, shape.pixels * per_pixel); });
+        view_feature_planes(dev, staged_planes(trip, shape.pixels));
         // the table for albedo alone (a scene without materials: an element to point at, nothing copied)
         const double *dtable = out->albedo ? trip.in(material_rgb, a->flat.material_pods.size() * 3) : nullptr;
         trip.run([&] { enqueue_view_features(*a, views, n_views, w, h, shape, dev, dtable, a->stream); });
@@ -799,7 +801,7 @@ extern "C" int lg_capture_view_features_device(const lg_accel *a, const lg_view 
         check_view_features_alignment(*dev_out, dev_material_rgb);
         std::lock_guard<std::mutex> g(a->mtx);
         use_device(a->device);
-        view_feature_planes(*dev_out, [&](auto *p, size_t per_pixel, size_t align, const char *what) { if (p) check_device_buffer(*a, p, shape.pixels * per_pixel * sizeof *p, align, what); });
+        view_feature_planes(*dev_out, device_planes(*a, shape.pixels));
         if (dev_out->albedo) check_device_buffer(*a, dev_material_rgb, a->flat.material_pods.size() * 3 * sizeof(double), 8, "material_rgb");
         enqueue_view_features(*a, views, n_views, w, h, shape, *dev_out, dev_material_rgb, (hipStream_t)hip_stream);
     });
@@ -807,7 +809,7 @@ extern "C" int lg_capture_view_features_device(const lg_accel *a, const lg_view 
 
 // ---- hit layers (lg_hit_layers*; k_layers.hip): the first max_layers surfaces along each of the caller's rays, the next segment made in
 // the kernel, the answer as layer-major planes.  The arithmetic that needs no device -- the limits, n * max_layers and the sizes, the NULL
-// and alignment rules, the staging -- is layers_host.h's.
+// and alignment rules -- is layers_host.h's.
 // One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the counts and the buffers):
 // ONE launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is parked
 static void enqueue_hit_layers(const lg_accel &a, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out &out, hipStream_t stream) {
@@ -819,7 +821,7 @@ static void enqueue_hit_layers(const lg_accel &a, const double *rays, size_t n, 
     const TraversalGrid g = traversal_grid(a, P, hit_layers_occupancy, c, stream);
     HIP_TRY(launch_hit_layers(P, rays, n, max_layers, out.hits, out.along, out.id, out.count, out.inside, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
 }
-// Host form: the rays go up, the planes come back into staging and are copied out at the end
+// Host form: the rays go up, the planes come back staged
 extern "C" int lg_hit_layers(const lg_accel *a, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out) {
     return guarded([&] {
         if (n == 0) return;
@@ -827,12 +829,10 @@ extern "C" int lg_hit_layers(const lg_accel *a, const double *rays, size_t n, ui
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         RoundTrip trip(*a);
-        LayersStaging st(*out, n, total);
         const double *drays = trip.in(rays, n * 6);
-        lg_layers_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        layer_planes(dev, n, total, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        lg_layers_out dev = *out; // ... where a plane asked for becomes its device buffer
+        layer_planes(dev, n, total, staged_planes(trip));
         trip.run([&] { enqueue_hit_layers(*a, drays, n, max_layers, dev, a->stream); });
-        place_layers(*out, st);
     });
 }
 extern "C" int lg_hit_layers_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t max_layers, const lg_layers_out *dev_out, void *hip_stream) {
@@ -844,14 +844,14 @@ extern "C" int lg_hit_layers_device(const lg_accel *a, const double *dev_rays, s
         check_sorted_count(*a, n);
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
-        layer_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        layer_planes(*dev_out, n, total, device_planes(*a));
         enqueue_hit_layers(*a, dev_rays, n, max_layers, *dev_out, (hipStream_t)hip_stream);
     });
 }
 
 // ---- hit attributes (lg_hit_attributes*, lg_hit_attributes_of*; k_attributes.hip): where on its primitive each ray's hit lies and the frame
 // it is shaded in, as planes indexed by the ray.  What needs no device -- the limits and the sizes, the NULL and alignment rules, the
-// staging, the counts table and the record check -- is attributes_host.h's.
+// counts table and the record check -- is attributes_host.h's.
 // One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers).
 // records == nullptr, the walking form: ONE launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is
 // parked.  Otherwise the _of form: no walk, no tile counter, no sort; a grid-stride launch over the records.
@@ -870,7 +870,7 @@ static void enqueue_hit_attributes(const lg_accel &a, const double *rays, const 
     const TraversalGrid g = traversal_grid(a, P, attributes_occupancy, c, stream);
     HIP_TRY(launch_attributes(P, rays, n, out.hits, out.flags, out.bary, out.uv, out.local, out.frame, out.dp, a.accel_tri_base.p, perm, a.fast, g.blocks, g.depth, stream));
 }
-// Host forms: the rays (and the records) go up, the planes come back into staging and are copied out at the end
+// Host forms: the rays (and the records) go up, the planes come back staged
 static int hit_attributes_host(const lg_accel *a, const double *rays, const lg_hit *records, bool of_form, size_t n, const lg_attr_out *out) {
     return guarded([&] {
         if (n == 0) return;
@@ -878,13 +878,11 @@ static int hit_attributes_host(const lg_accel *a, const double *rays, const lg_h
         std::lock_guard<std::mutex> g(a->mtx);
         if (!of_form) check_sorted_count(*a, n);
         RoundTrip trip(*a);
-        AttrStaging st(*out, n);
         const double *drays = trip.in(rays, n * 6);
         const lg_hit *drecords = of_form ? trip.in(records, n) : nullptr;
-        lg_attr_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        attr_planes(dev, n, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        lg_attr_out dev = *out; // ... where a plane asked for becomes its device buffer
+        attr_planes(dev, n, staged_planes(trip));
         trip.run([&] { enqueue_hit_attributes(*a, drays, drecords, n, dev, a->stream); });
-        place_attributes(*out, st);
     });
 }
 static int hit_attributes_device(const lg_accel *a, const double *dev_rays, const lg_hit *dev_records, bool of_form, size_t n, const lg_attr_out *dev_out, void *hip_stream) {
@@ -897,7 +895,7 @@ static int hit_attributes_device(const lg_accel *a, const double *dev_rays, cons
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         if (of_form) check_device_buffer(*a, dev_records, n * sizeof(lg_hit), 16, "hits");
-        attr_planes(*dev_out, n, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        attr_planes(*dev_out, n, device_planes(*a));
         enqueue_hit_attributes(*a, dev_rays, of_form ? dev_records : nullptr, n, *dev_out, (hipStream_t)hip_stream);
     });
 }
@@ -914,7 +912,7 @@ extern "C" int lg_hit_attributes_of_device(const lg_accel *a, const double *dev_
 
 // ---- ray paths (lg_trace_paths*; k_paths.hip): each of the caller's rays followed through up to max_bounces vertices, the next segment
 // formed in the kernel by the rule of the hit's material, the answer as vertex-major and per-ray planes.  What needs no device -- the limits,
-// n * max_bounces and the sizes, the rule table's validation, the NULL and alignment rules, the staging -- is paths_host.h's.
+// n * max_bounces and the sizes, the rule table's validation, the NULL and alignment rules -- is paths_host.h's.
 // One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers): the
 // rules through the launch context's pinned staging into a table of the call's own (the caller's array may be freed on return), then ONE
 // launch over the rays' 64-ray tiles -- no chunks: the outputs are the caller's, and nothing is parked
@@ -933,7 +931,7 @@ static void enqueue_trace_paths(const lg_accel &a, const double *rays, size_t n,
         subsets_enqueued(a, stream);
     } catch (...) { subsets_abandoned(a, stream); throw; }
 }
-// Host form: the rays (and the starting media) go up, the planes come back into staging and are copied out at the end
+// Host form: the rays (and the starting media) go up, the planes come back staged
 extern "C" int lg_trace_paths(const lg_accel *a, const double *rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules, int normal,
                               const uint32_t *start_medium, const lg_paths_out *out) {
     return guarded([&] {
@@ -942,13 +940,11 @@ extern "C" int lg_trace_paths(const lg_accel *a, const double *rays, size_t n, u
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         RoundTrip trip(*a);
-        PathsStaging st(*out, n, total);
         const double *drays = trip.in(rays, n * 6);
         const uint32_t *dmedium = trip.in(start_medium, n);
-        lg_paths_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        path_planes(dev, n, total, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        lg_paths_out dev = *out; // ... where a plane asked for becomes its device buffer
+        path_planes(dev, n, total, staged_planes(trip));
         trip.run([&] { enqueue_trace_paths(*a, drays, n, max_bounces, rules, n_rules, normal, dmedium, dev, a->stream); });
-        place_paths(*out, st);
     });
 }
 extern "C" int lg_trace_paths_device(const lg_accel *a, const double *dev_rays, size_t n, uint32_t max_bounces, const lg_path_rule *rules, size_t n_rules, int normal,
@@ -962,14 +958,14 @@ extern "C" int lg_trace_paths_device(const lg_accel *a, const double *dev_rays, 
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         if (dev_start_medium) check_device_buffer(*a, dev_start_medium, n * sizeof(uint32_t), 4, "start_medium");
-        path_planes(*dev_out, n, total, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        path_planes(*dev_out, n, total, device_planes(*a));
         enqueue_trace_paths(*a, dev_rays, n, max_bounces, rules, n_rules, normal, dev_start_medium, *dev_out, (hipStream_t)hip_stream);
     });
 }
 
 // ---- surface scatter (lg_scatter*; launch.cpp, enqueue_scatter; k_scatter.hip): one level of li()'s tree, opened -- the hit, the light and
 // ambient sum at it and the two specular children with their weights, as planes indexed by the ray.  What needs no device -- the limits,
-// the sizes, the NULL and alignment rules, the light count's refusal, the staging -- is scatter_host.h's.
+// the sizes, the NULL and alignment rules, the light count's refusal -- is scatter_host.h's.
 static_assert(SCATTER_HIT == LG_SCATTER_HIT && SCATTER_REFLECT == LG_SCATTER_REFLECT && SCATTER_REFRACT == LG_SCATTER_REFRACT, "dscene.h restates the contract's flags");
 // One call enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call and the buffers)
 static void enqueue_scatter_query(const lg_accel &a, const double *rays, size_t n, const lg_scatter_out &out, hipStream_t stream) {
@@ -981,7 +977,7 @@ static void enqueue_scatter_query(const lg_accel &a, const double *rays, size_t 
     Q.reflect = out.reflect; Q.reflect_weight = out.reflect_weight; Q.refract = out.refract; Q.refract_weight = out.refract_weight;
     enqueue_scatter(a, rays, n, Q, perm, c, stream);
 }
-// Host form: the rays go up, the planes come back into staging and are copied out at the end
+// Host form: the rays go up, the planes come back staged
 extern "C" int lg_scatter(const lg_accel *a, const double *rays, size_t n, const lg_scatter_out *out) {
     return guarded([&] {
         if (n == 0) return;
@@ -989,12 +985,10 @@ extern "C" int lg_scatter(const lg_accel *a, const double *rays, size_t n, const
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         RoundTrip trip(*a);
-        ScatterStaging st(*out, n);
         const double *drays = trip.in(rays, n * 6);
-        lg_scatter_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        scatter_planes(dev, n, [&](auto *&p, auto plane, size_t count, size_t, const char *) { if (p) p = trip.out((st.*plane).data(), count); });
+        lg_scatter_out dev = *out; // ... where a plane asked for becomes its device buffer
+        scatter_planes(dev, n, staged_planes(trip));
         trip.run([&] { enqueue_scatter_query(*a, drays, n, dev, a->stream); });
-        place_scatter(*out, st);
     });
 }
 extern "C" int lg_scatter_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_scatter_out *dev_out, void *hip_stream) {
@@ -1006,14 +1000,14 @@ extern "C" int lg_scatter_device(const lg_accel *a, const double *dev_rays, size
         check_sorted_count(*a, n);
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
-        scatter_planes(*dev_out, n, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        scatter_planes(*dev_out, n, device_planes(*a));
         enqueue_scatter_query(*a, dev_rays, n, *dev_out, (hipStream_t)hip_stream);
     });
 }
 
 // ---- lit scatter (lg_scatter_lit*; launch.cpp, enqueue_scatter_lit; k_lit.hip): surface scatter under lights that come with the call,
 // with every light's term and the visibility bits as two more planes.  What needs no device -- the light set's rules, W, the sizes, the
-// NULL and alignment rules, the staging -- is lit_host.h's.
+// NULL and alignment rules -- is lit_host.h's.
 static_assert(MAX_CALL_LIGHTS == LG_MAX_CALL_LIGHTS && sizeof(DLight) == sizeof(lg_light), "dscene.h restates the contract's light record and limit");
 // The skip (k_lit.hip): on unless LASGUN_LIT_SKIP=0 (for the measurement of what it buys); never where `visible` is asked for
 static bool lit_skip_on() {
@@ -1039,7 +1033,7 @@ static void enqueue_lit_query(const lg_accel &a, const double *rays, size_t n, c
     Q.lights = lights.per_ray ? reinterpret_cast<const DLight *>(table) : nullptr;
     enqueue_scatter_lit(a, rays, n, Q, lights.per_ray ? nullptr : reinterpret_cast<const DLight *>(table), perm, c, stream);
 }
-// Host form: the rays (and a per-ray light table) go up, the planes come back into staging and are copied out at the end
+// Host form: the rays (and a per-ray light table) go up, the planes come back staged
 extern "C" int lg_scatter_lit(const lg_accel *a, const double *rays, size_t n, const lg_light_set *lights, const lg_lit_out *out) {
     return guarded([&] {
         if (n == 0) return;
@@ -1047,13 +1041,11 @@ extern "C" int lg_scatter_lit(const lg_accel *a, const double *rays, size_t n, c
         std::lock_guard<std::mutex> g(a->mtx);
         check_sorted_count(*a, n);
         RoundTrip trip(*a);
-        LitStaging st(*out, z);
         const double *drays = trip.in(rays, n * 6);
         const lg_light *table = lights->per_ray && z.K ? trip.in(lights->lights, z.lights) : lights->lights;
-        lg_lit_out dev = *out; // ... where a plane asked for becomes its device buffer, which comes back into its staging
-        lit_planes(dev, z, [&](auto *&p, auto member, size_t count, size_t, const char *) { if (p) p = trip.out(member(st).data(), count); });
+        lg_lit_out dev = *out; // ... where a plane asked for becomes its device buffer
+        lit_planes(dev, z, staged_planes(trip));
         trip.run([&] { enqueue_lit_query(*a, drays, n, *lights, table, z, dev, a->stream); });
-        place_lit(*out, z, st);
     });
 }
 extern "C" int lg_scatter_lit_device(const lg_accel *a, const double *dev_rays, size_t n, const lg_light_set *lights, const lg_lit_out *dev_out, void *hip_stream) {
@@ -1066,8 +1058,7 @@ extern "C" int lg_scatter_lit_device(const lg_accel *a, const double *dev_rays, 
         use_device(a->device);
         check_device_buffer(*a, dev_rays, n * 6 * sizeof(double), 8, "rays");
         if (lights->per_ray && z.K) check_device_buffer(*a, lights->lights, z.lights * sizeof(lg_light), 8, "lights->lights");
-        lg_lit_out o = *dev_out;
-        lit_planes(o, z, [&](auto *p, auto, size_t count, size_t align, const char *what) { if (p) check_device_buffer(*a, p, count * sizeof *p, align, what); });
+        lit_planes(*dev_out, z, device_planes(*a));
         enqueue_lit_query(*a, dev_rays, n, *lights, lights->lights, z, *dev_out, (hipStream_t)hip_stream);
     });
 }
@@ -1084,7 +1075,7 @@ static unsigned long long lens_ray_count(const lg_lens *lens, uint32_t w, uint32
     if (root == 0) throw Error("samples_root is 0");
     if (!offsets && pixels != (size_t)w * h) throw Error("lens rays: without pixel_offsets, pixels must be width * height");
     const unsigned long long S = (unsigned long long)root * root;
-    if (pixels > MAX_RAYS / S) throw Error("too many lens rays (pixels * samples_root^2)");
+    if (pixels > QUERY_MAX_RAYS / S) throw Error("too many lens rays (pixels * samples_root^2)");
     return pixels * S;
 }
 static void enqueue_lens_rays(const lg_lens *lens, uint32_t w, uint32_t h, uint32_t root, const uint64_t *dev_offsets, unsigned long long n, double *dev_rays,

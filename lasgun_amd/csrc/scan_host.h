@@ -1,16 +1,11 @@
 // lasgun_amd/csrc/scan_host.h -- the part of lg_range_scan* (query.cpp) that touches no device: the lane rule, the two tile counts with
 // their 32-bit limit, the planes' byte sizes, and the one table of lg_scan_out's planes (scan_planes) with what follows from it: the NULL and
-// alignment rules, the host form's staging and its placement.  Arithmetic on size_t that can overflow, so kept free of HIP:
+// alignment rules (the size and alignment rules themselves and the host form's staging are planes_host.h's).  Arithmetic on size_t that
+// can overflow, so kept free of HIP:
 // tools/scan_host_check.cpp runs exactly this text under AddressSanitizer / UBSan on the CPU, and lg_range_scan_lanes and both entry points call it.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
 #include "../../include/lasgun_hip.h"
+#include "planes_host.h"
 
 namespace lg {
 
@@ -40,29 +35,16 @@ inline bool scan_tiles(size_t n_poses, size_t n_beams, int form, unsigned long l
     *tiles = a * b;
     return true;
 }
-// count * bytes_each as a size_t, refused where it does not fit the address space
-inline size_t scan_bytes(size_t count, size_t bytes_each, const char *what) {
-    if (bytes_each && count > SIZE_MAX / bytes_each) throw std::runtime_error(std::string(what) + " does not fit the address space");
-    return count * bytes_each;
-}
-
-// The host form's outputs on their way back: only what is asked for has any size.  An error on the way leaves the caller's arrays as they were.
-struct ScanStaging {
-    std::vector<float> range, point, normal;
-    std::vector<uint32_t> id, hits;
-    std::vector<float> nearest;
-    ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs);
-};
-// The six planes of lg_scan_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, the
-// plane's staging, its elements, its alignment in bytes, its name) in the struct's order.  The alignment and NULL rules, the staging's
-// sizes, the host form's device buffers and copies, the device form's buffer checks and the placement all go through here.
+// The six planes of lg_scan_out (or of a copy that f may edit), each written down here and nowhere else: f(the struct's pointer, its
+// elements, its alignment in bytes, its name) in the struct's order.  The alignment and NULL rules, the host form's staging, device
+// buffers and copies and the device form's buffer checks all go through here.
 template <class Out, class F> inline void scan_planes(Out &out, size_t n_poses, size_t pairs, F &&f) {
-    f(out.range, &ScanStaging::range, pairs, 4, "range");
-    f(out.point, &ScanStaging::point, pairs * 3, 4, "point");
-    f(out.normal, &ScanStaging::normal, pairs * 3, 4, "normal");
-    f(out.id, &ScanStaging::id, pairs * 4, 16, "id");
-    f(out.hits, &ScanStaging::hits, n_poses, 4, "hits");
-    f(out.nearest, &ScanStaging::nearest, n_poses, 4, "nearest");
+    f(out.range, pairs, 4, "range");
+    f(out.point, pairs * 3, 4, "point");
+    f(out.normal, pairs * 3, 4, "normal");
+    f(out.id, pairs * 4, 16, "id");
+    f(out.hits, n_poses, 4, "hits");
+    f(out.nearest, n_poses, 4, "nearest");
 }
 
 // What a checked call is: its form, its tiles and its pairs
@@ -77,9 +59,7 @@ inline ScanShape check_scan(const void *accel, const double *origins, size_t n_p
     if (!out) throw std::runtime_error("out is NULL");
     if (!origins) throw std::runtime_error("origins is NULL");
     if (!beams) throw std::runtime_error("beams is NULL");
-    bool any = false;
-    scan_planes(*out, 0, 0, [&](auto *p, auto, size_t, size_t, const char *) { any = any || p; });
-    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
+    require_any_plane([&](auto &&f) { scan_planes(*out, 0, 0, f); });
     const int form = scan_lanes(n_poses, n_beams, lanes);
     if (form < 0) throw std::runtime_error("lanes is " + std::to_string(lanes) + ": 0 (auto), 1 (beam lanes) or 2 (pose lanes)");
     if ((unsigned long long)n_beams > SCAN_MAX_BEAMS) throw std::runtime_error("too many beams in one scan: at most 2^32 - 1");
@@ -89,27 +69,16 @@ inline ScanShape check_scan(const void *accel, const double *origins, size_t n_p
                                                          : "too many pairs in one scan: tiles of one pose x 64 beams are counted in 32 bits");
     if (n_poses > SIZE_MAX / n_beams) throw std::runtime_error("n_poses * n_beams does not fit the address space");
     const size_t pairs = n_poses * n_beams;
-    (void)scan_bytes(n_poses, 9 * sizeof(double), "frames");
-    (void)scan_bytes(pairs, 4 * sizeof(uint32_t), "a plane of n_poses * n_beams elements"); // 16 bytes an element, the widest (id): no count or size of scan_planes wraps
+    (void)checked_bytes(n_poses, 9 * sizeof(double), "frames");
+    (void)checked_bytes(pairs, 4 * sizeof(uint32_t), "a plane of n_poses * n_beams elements"); // 16 bytes an element, the widest (id): no count or size of scan_planes wraps
     return {form, (uint32_t)tiles, pairs};
 }
-inline ScanStaging::ScanStaging(const lg_scan_out &out, size_t n_poses, size_t pairs) {
-    scan_planes(out, n_poses, pairs, [&](auto *p, auto plane, size_t count, size_t, const char *) { if (p) (this->*plane).resize(count); });
-}
-inline void place_scan(const lg_scan_out &out, const ScanStaging &st) {
-    scan_planes(out, 0, 0, [&](auto *p, auto plane, size_t, size_t, const char *) {
-        if (p && !(st.*plane).empty()) std::memcpy(p, (st.*plane).data(), (st.*plane).size() * sizeof *p);
-    });
-}
 // The device form's alignment rule: the inputs 8 bytes, the planes theirs (id 16, the others 4)
-inline void check_alignment(const void *p, size_t align, const char *what) {
-    if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
-}
 inline void check_scan_alignment(const double *origins, const double *frames, const double *beams, const lg_scan_out &out) {
     check_alignment(origins, 8, "origins");
     check_alignment(frames, 8, "frames");
     check_alignment(beams, 8, "beams");
-    scan_planes(out, 0, 0, [](auto *p, auto, size_t, size_t align, const char *what) { check_alignment(p, align, what); });
+    check_planes_alignment([&](auto &&f) { scan_planes(out, 0, 0, f); });
 }
 
 } // namespace lg

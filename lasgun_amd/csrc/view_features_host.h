@@ -32,9 +32,7 @@ inline ViewShape check_view_features(const void *accel, const lg_view *views, si
     if (!accel) throw std::runtime_error("accel is NULL");
     if (!views) throw std::runtime_error("views is NULL");
     if (!out) throw std::runtime_error("out is NULL");
-    bool any = false;
-    view_feature_planes(*out, [&](auto *p, size_t, size_t, const char *) { any = any || p; });
-    if (!any) throw std::runtime_error("every plane of out is NULL: at least one output");
+    require_any_plane([&](auto &&f) { view_feature_planes(*out, f); });
     if (out->albedo && !material_rgb) throw std::runtime_error("albedo is requested and material_rgb is NULL");
     if (w == 0 || h == 0) throw std::runtime_error("view features: an empty film (width or height is 0)");
     // (a tile's pixel coordinates are 32-bit: the last tile of a row or column may reach 7 pixels beyond the film's edge)
@@ -59,9 +57,7 @@ inline ViewShape check_view_features(const void *accel, const lg_view *views, si
 }
 // The device form's alignment rule: id 16 bytes (one store a pixel), the float planes 4, material_rgb 8 where albedo asks for it
 inline void check_view_features_alignment(const lg_view_features &out, const double *material_rgb) {
-    view_feature_planes(out, [&](auto *p, size_t, size_t align, const char *what) {
-        if (p && (uintptr_t)p % align) throw std::runtime_error(std::string(what) + " is not " + std::to_string(align) + "-byte aligned");
-    });
+    check_planes_alignment([&](auto &&f) { view_feature_planes(out, f); });
     if (out.albedo && (uintptr_t)material_rgb % 8) throw std::runtime_error("material_rgb is not 8-byte aligned");
 }
 

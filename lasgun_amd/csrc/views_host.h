@@ -12,6 +12,7 @@
 
 #include "../../include/lasgun_hip.h"
 #include "dscene.h"
+#include "planes_host.h"
 
 namespace lg {
 
@@ -87,8 +88,8 @@ inline ViewShape check_views(const void *accel, const lg_view *views, size_t n_v
 }
 // The device form's alignment rule: rgba 4 bytes (one word a pixel), rgb 8
 inline void check_views_alignment(const void *rgba, const void *rgb) {
-    if (rgba && (uintptr_t)rgba % 4) throw std::runtime_error("rgba is not 4-byte aligned");
-    if (rgb && (uintptr_t)rgb % 8) throw std::runtime_error("rgb is not 8-byte aligned");
+    check_alignment(rgba, 4, "rgba");
+    check_alignment(rgb, 8, "rgb");
 }
 // lg_view -> the record the kernels read: the fields as given, and Camera::set_supersampling's ss_distance = 1.0 / (double)samples_root
 inline DView to_dview(const lg_view &v) {

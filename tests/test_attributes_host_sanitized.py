@@ -30,13 +30,13 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     query = read("lasgun_amd", "csrc", "query.cpp")
     assert '#include "attributes_host.h"' in query and "check_attributes(a, rays, records, of_form, n, out)" in query and \
         "check_attributes(a, dev_rays, dev_records, of_form, n, dev_out)" in query, "query.cpp runs the text that was checked"
-    assert "check_attributes_alignment(dev_rays, dev_records, *dev_out)" in query and "place_attributes(*out, st)" in query and "AttrStaging st(*out, n)" in query
+    assert "check_attributes_alignment(dev_rays, dev_records, *dev_out)" in query and "attr_planes(dev, n, staged_planes(trip))" in query
     kernel = read("lasgun_amd", "csrc", "k_attributes.hip")
     assert '#include "attributes_host.h"' in kernel and "if (!attr_record_ok(Q.counts, id.x, id.y, id.z)) flags = ATTR_BAD_RECORD;" in kernel, \
         "the kernel checks a record with the function that was checked, before it reads through it"
     assert kernel.index("attr_record_ok(Q.counts") < kernel.index("attr_triangle_index(Q.counts") < kernel.index("attr_resolve(P, ray, pk, idx, id.z, got)")
     assert "attr_counts_build(faces, tri_base, sphere_accel, cuboid_accel)" in read("lasgun_amd", "csrc", "accel.cpp")
     check = read("tools", "attributes_host_check.cpp")
-    for edge in ("EDGE = TOP / 96", "ATTR_MAX_RAYS + 1", "planes < 128", "refused(&accel, D, h, true, 2, &all)", "refused(&accel, D, nullptr, true, 2, &no_hits)",
+    for edge in ("EDGE = TOP / 96", "QUERY_MAX_RAYS + 1", "planes < 128", "refused(&accel, D, h, true, 2, &all)", "refused(&accel, D, nullptr, true, 2, &no_hits)",
                  "new uint32_t[table.size()]", "0xFFFFFFFFu}"):
         assert edge in check, ("the checks at their edges", edge)

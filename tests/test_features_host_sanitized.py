@@ -21,4 +21,4 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, env=env)
     assert run.returncode == 0 and "features_host_check: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
-    assert '#include "features_host.h"' in query and "check_features(a, out," in query and "place_features(*out, st," in query, "query.cpp runs the text that was checked"
+    assert '#include "features_host.h"' in query and "check_features(a, out," in query and "trip.held(pixels * per_pixel, &rows)" in query and "place_features(*out, compact.data()," in query, "query.cpp runs the text that was checked"

@@ -23,7 +23,7 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     assert run.returncode == 0 and "gather_host_check: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
     assert '#include "gather_host.h"' in query and "check_gather(a, origins," in query and "check_gather(a, dev_origins," in query, "query.cpp runs the text that was checked"
-    assert "check_gather_alignment(dev_origins," in query and "place_gather(*out, st)" in query and "return gather_lanes(n_poses, n_dirs, lanes)" in query
+    assert "check_gather_alignment(dev_origins," in query and "trip.staged(out->radiance, shape.pairs * 3), trip.staged(out->sums, n_poses * n_weights * 3)" in query and "return gather_lanes(n_poses, n_dirs, lanes)" in query
     assert "gather_batch_poses(n_poses, n_dirs, shape.form, park_bytes)" in query and 'gather_park_bytes(std::getenv("LASGUN_GATHER_PARK_MB"))' in query
     check = open(os.path.join(ROOT, "tools", "gather_host_check.cpp")).read()
     for limit in ("tiles(M, 64, 1) == (long long)M", "tiles(M + 1, 64, 1) == -1", "tiles(64 * M, 1, 2) == (long long)M", "tiles(64 * M + 1, 1, 2) == -1",

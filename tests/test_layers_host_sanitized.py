@@ -24,7 +24,7 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
     assert '#include "layers_host.h"' in query and "check_layers(a, rays, n, max_layers, out)" in query and "check_layers(a, dev_rays, n, max_layers, dev_out)" in query, \
         "query.cpp runs the text that was checked"
-    assert "check_layers_alignment(dev_rays, *dev_out)" in query and "place_layers(*out, st)" in query and "LayersStaging st(*out, n, total)" in query
+    assert "check_layers_alignment(dev_rays, *dev_out)" in query and "layer_planes(dev, n, total, staged_planes(trip))" in query
     check = open(os.path.join(ROOT, "tools", "layers_host_check.cpp")).read()
     for edge in ("EDGE = TOP / 96", "refused(&accel, D, under + 1, k, &all)", "refused(&accel, D, 1, 0, &all)", "check_layers(&accel, D, 1, KMAX, &all) == KMAX",
                  "planes < 32"):

@@ -25,7 +25,7 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     assert '#include "light_groups_host.h"' in query, "query.cpp runs the text that was checked"
     assert "check_light_groups(a, rays, n, groups, n_groups, radiance, a->flat.lights.size(), table)" in query
     assert "check_light_groups(a, dev_rays, n, groups, n_groups, dev_radiance, a->flat.lights.size(), table)" in query
-    assert "check_light_groups_alignment(dev_rays, dev_radiance)" in query and "place_light_groups(radiance, st)" in query and "GroupsStaging st(shape)" in query
+    assert "check_light_groups_alignment(dev_rays, dev_radiance)" in query and "trip.staged(radiance, shape.out_doubles)" in query
     check = open(os.path.join(ROOT, "tools", "light_groups_host_check.cpp")).read()
-    for edge in ("LG_MAX_LIGHT_GROUPS + 1, OUT, 0)", "n_lights <= 32", "(bit >= n_lights)", "GROUPS_MAX_RAYS + 1, many, 1", "many, TOP, OUT, 0)"):
+    for edge in ("LG_MAX_LIGHT_GROUPS + 1, OUT, 0)", "n_lights <= 32", "(bit >= n_lights)", "QUERY_MAX_RAYS + 1, many, 1", "many, TOP, OUT, 0)"):
         assert edge in check, ("the checks at their edges", edge)

@@ -24,8 +24,8 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
     assert '#include "lit_host.h"' in query, "query.cpp runs the text that was checked"
     assert "check_lit(a, rays, n, lights, out)" in query and "check_lit(a, dev_rays, n, lights, dev_out)" in query
-    assert "check_lit_alignment(dev_rays, *lights, *dev_out, z)" in query and "place_lit(*out, z, st)" in query and "LitStaging st(*out, z)" in query
+    assert "check_lit_alignment(dev_rays, *lights, *dev_out, z)" in query and "lit_planes(dev, z, staged_planes(trip))" in query
     check = open(os.path.join(ROOT, "tools", "lit_host_check.cpp")).read()
-    for edge in ("TOP / 72 / 1024 + 1", "TOP / 24 / 1024 + 1", "TOP / 4 / 32 + 1", "SCATTER_MAX_RAYS + 1", "LG_MAX_CALL_LIGHTS + 1", "planes < 512",
+    for edge in ("TOP / 72 / 1024 + 1", "TOP / 24 / 1024 + 1", "TOP / 4 / 32 + 1", "QUERY_MAX_RAYS + 1", "LG_MAX_CALL_LIGHTS + 1", "planes < 512",
                  "want_align[9] = {16, 8, 4, 8, 8, 8, 8, 8, 4}", "{0, 1, 31, 32, 33, 64, 65, 70}"):
         assert edge in check, ("the checks at their edges", edge)

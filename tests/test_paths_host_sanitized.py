@@ -25,7 +25,7 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     assert '#include "paths_host.h"' in query, "query.cpp runs the text that was checked"
     assert "check_paths(a, rays, n, max_bounces, rules, n_rules, lg_accel_material_count(a), normal, out)" in query
     assert "check_paths(a, dev_rays, n, max_bounces, rules, n_rules, lg_accel_material_count(a), normal, dev_out)" in query
-    assert "check_paths_alignment(dev_rays, dev_start_medium, *dev_out)" in query and "place_paths(*out, st)" in query and "PathsStaging st(*out, n, total)" in query
+    assert "check_paths_alignment(dev_rays, dev_start_medium, *dev_out)" in query and "path_planes(dev, n, total, staged_planes(trip))" in query
     check = open(os.path.join(ROOT, "tools", "paths_host_check.cpp")).read()
     for edge in ("EDGE = TOP / 96", "refused(&accel, D, under + 1, k, &all)", "refused(&accel, D, 1, 0, &all)", "checked(&accel, 1, KMAX, &all) == KMAX",
                  "planes < 512", "action > LG_PATH_REFRACT", "r[m].reserved = 1u"):

@@ -23,7 +23,7 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     assert run.returncode == 0 and "scan_host_check: ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr[-4000:])
     query = open(os.path.join(ROOT, "lasgun_amd", "csrc", "query.cpp")).read()
     assert '#include "scan_host.h"' in query and "check_scan(a, origins," in query and "check_scan(a, dev_origins," in query, "query.cpp runs the text that was checked"
-    assert "check_scan_alignment(dev_origins," in query and "place_scan(*out, st)" in query and "return scan_lanes(n_poses, n_beams, lanes)" in query
+    assert "check_scan_alignment(dev_origins," in query and "scan_planes(dev, n_poses, pairs, staged_planes(trip))" in query and "return scan_lanes(n_poses, n_beams, lanes)" in query
     check = open(os.path.join(ROOT, "tools", "scan_host_check.cpp")).read()
     for limit in ("tiles(M, 64, 1) == (long long)M", "tiles(M + 1, 64, 1) == -1", "tiles(64 * M, 8, 2) == (long long)M", "tiles(64 * M + 1, 8, 2) == -1"):
         assert limit in check, ("the tile counts at their limit and one above, both forms", limit)

@@ -25,8 +25,8 @@ def test_the_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     assert '#include "scatter_host.h"' in query, "query.cpp runs the text that was checked"
     assert "check_scatter(a, rays, n, out, a ? a->flat.lights.size() : 0)" in query
     assert "check_scatter(a, dev_rays, n, dev_out, a ? a->flat.lights.size() : 0)" in query
-    assert "check_scatter_alignment(dev_rays, *dev_out)" in query and "place_scatter(*out, st)" in query and "ScatterStaging st(*out, n)" in query
+    assert "check_scatter_alignment(dev_rays, *dev_out)" in query and "scatter_planes(dev, n, staged_planes(trip))" in query
     check = open(os.path.join(ROOT, "tools", "scatter_host_check.cpp")).read()
-    for edge in ("EDGE = TOP / 96", "refused(&accel, D, SCATTER_MAX_RAYS + 1, &all)", "refused(&accel, D, 3, &none)", "planes < 128", "(size_t)33", "(size_t)32",
+    for edge in ("EDGE = TOP / 96", "refused(&accel, D, QUERY_MAX_RAYS + 1, &all)", "refused(&accel, D, 3, &none)", "planes < 128", "(size_t)33", "(size_t)32",
                  "want_align[7] = {16, 8, 4, 8, 8, 8, 8}"):
         assert edge in check, ("the checks at their edges", edge)

@@ -3,39 +3,23 @@
 // records, the host forms' staging, the counts table and attr_record_ok) in a stand-alone program, meant to be built with
 // -fsanitize=address,undefined and run on the CPU (tests/test_attributes_host_sanitized.py does).  The counts go up to 2^64 - 1: an
 // overflow in forming a size is a UBSan report or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel"
-// that fills the staged planes with values that name their element; every caller's array is a heap block of exactly its size, so a copy
+// that fills the staged planes with bytes that name their place (host_check.h, staged_round); every caller's array is a heap block of exactly its size, so a copy
 // past an end is an ASan report.  attr_record_ok is the function attr_of_kernel calls before it reads anything through a record: here it
 // runs over an exhaustive small grid of records against a table that is a heap block of exactly its size, and is compared with a
 // brute-force statement of the contract.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/attributes_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/attributes_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
 
 static bool refused(const void *accel, const double *rays, const lg_hit *records, bool of_form, size_t n, const lg_attr_out *out) {
-    try {
-        check_attributes(accel, rays, records, of_form, n, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_attributes(accel, rays, records, of_form, n, out); });
 }
 static bool misaligned(const void *rays, const void *records, const lg_attr_out &out) {
-    try {
-        check_attributes_alignment((const double *)rays, (const lg_hit *)records, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_attributes_alignment((const double *)rays, (const lg_hit *)records, out); });
 }
 // lg_attr_out with the planes of a 7-bit mask named from `all`
 static lg_attr_out subset(const lg_attr_out &all, unsigned planes) {
@@ -43,42 +27,17 @@ static lg_attr_out subset(const lg_attr_out &all, unsigned planes) {
                        planes & 16u ? all.local : nullptr, planes & 32u ? all.frame : nullptr, planes & 64u ? all.dp : nullptr};
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at
 static void run(size_t n, unsigned planes) {
-    const size_t width[7] = {1, 1, 3, 2, 3, 6, 6};
-    std::unique_ptr<lg_hit[]> hits(planes & 1u ? new lg_hit[n] : nullptr);
-    std::unique_ptr<uint32_t[]> flags(planes & 2u ? new uint32_t[n] : nullptr);
-    std::unique_ptr<double[]> dbl[5];
-    for (int k = 0; k < 5; ++k) dbl[k].reset(planes & (4u << k) ? new double[n * width[2 + k]] : nullptr);
-    const lg_attr_out out{hits.get(), flags.get(), dbl[0].get(), dbl[1].get(), dbl[2].get(), dbl[3].get(), dbl[4].get()};
+    const lg_attr_out all{(lg_hit *)ASKED, (uint32_t *)ASKED, (double *)ASKED, (double *)ASKED, (double *)ASKED, (double *)ASKED, (double *)ASKED};
+    lg_attr_out out = subset(all, planes);
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     check_attributes(&accel, D, nullptr, false, n, &out);
-    AttrStaging st(out, n);
-    EXPECT(st.hits.size() == (out.hits ? n : 0) && st.flags.size() == (out.flags ? n : 0) && st.bary.size() == (out.bary ? 3 * n : 0) && st.uv.size() == (out.uv ? 2 * n : 0) &&
-           st.local.size() == (out.local ? 3 * n : 0) && st.frame.size() == (out.frame ? 6 * n : 0) && st.dp.size() == (out.dp ? 6 * n : 0));
-    size_t staged_bytes = 0, want_bytes = 0;
-    attr_planes(out, n, [&](auto *p, auto plane, size_t elems, size_t, const char *) { if (p) { staged_bytes += (st.*plane).size() * sizeof *p; want_bytes += elems * sizeof *p; } });
-    EXPECT(staged_bytes == want_bytes);
-    EXPECT(want_bytes == n * ((out.hits ? 96 : 0) + (out.flags ? 4 : 0) + (out.bary ? 24 : 0) + (out.uv ? 16 : 0) + (out.local ? 24 : 0) + (out.frame ? 48 : 0) + (out.dp ? 48 : 0)));
-    std::vector<double> *staged[5] = {&st.bary, &st.uv, &st.local, &st.frame, &st.dp};
-    for (size_t i = 0; i < n; ++i) { // the stubbed launch
-        if (out.hits) {
-            lg_hit h;
-            std::memset(&h, 0, sizeof h);
-            h.t = (double)i + 0.25; h.prim = (uint32_t)i; h.material = -(int32_t)i;
-            st.hits[i] = h;
-        }
-        if (out.flags) st.flags[i] = (uint32_t)(i + 7);
-        for (int k = 0; k < 5; ++k)
-            for (size_t c = 0; c < width[2 + k] && !staged[k]->empty(); ++c) (*staged[k])[i * width[2 + k] + c] = (double)(i * 8 + c) + 0.125 * (k + 1);
-    }
-    place_attributes(out, st);
-    for (size_t i = 0; i < n; ++i) {
-        if (hits) EXPECT(hits[i].t == (double)i + 0.25 && hits[i].prim == (uint32_t)i && hits[i].material == -(int32_t)i);
-        if (flags) EXPECT(flags[i] == (uint32_t)(i + 7));
-        for (int k = 0; k < 5; ++k)
-            for (size_t c = 0; c < width[2 + k] && dbl[k]; ++c) EXPECT(dbl[k][i * width[2 + k] + c] == (double)(i * 8 + c) + 0.125 * (k + 1));
-    }
+    const StagedRound r = staged_round([&](auto &&f) { attr_planes(out, n, f); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 96 * n : 0, planes & 2u ? 4 * n : 0, planes & 4u ? 8 * 3 * n : 0, planes & 8u ? 8 * 2 * n : 0, planes & 16u ? 8 * 3 * n : 0,
+                                                 planes & 32u ? 8 * 6 * n : 0, planes & 64u ? 8 * 6 * n : 0}));
+    const size_t want_bytes = n * ((planes & 1u ? 96 : 0) + (planes & 2u ? 4 : 0) + (planes & 4u ? 24 : 0) + (planes & 8u ? 16 : 0) + (planes & 16u ? 24 : 0) + (planes & 32u ? 48 : 0) + (planes & 64u ? 48 : 0));
+    EXPECT(r.bytes == want_bytes);
 }
 
 // attr_record_ok over every record of a small grid, for one scene description, against the contract said in plain loops
@@ -112,7 +71,7 @@ int main() {
     const lg_attr_out no_hits = subset(all, 0x7Eu);
     const size_t TOP = ~(size_t)0, EDGE = TOP / 96; // the most lg_hit records an address space holds
     static_assert(sizeof(size_t) == 8, "the limits below are written for a 64-bit size_t");
-    static_assert(ATTR_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
+    static_assert(QUERY_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
     // ---- check_attributes: every error of the contract that needs no device, both forms
     EXPECT(!refused(&accel, D, nullptr, false, 3, &all));
     EXPECT(refused(nullptr, D, nullptr, false, 3, &all));
@@ -125,15 +84,11 @@ int main() {
     EXPECT(refused(nullptr, D, h, true, 2, &no_hits) && refused(&accel, nullptr, h, true, 2, &no_hits) && refused(&accel, D, h, true, 2, nullptr));
     EXPECT(refused(&accel, D, h, true, 2, &none));
     // the ray limit: (2^32 - 1) * 64 and one above; the address space: SIZE_MAX / 96 rows and one above
-    EXPECT(!refused(&accel, D, nullptr, false, ATTR_MAX_RAYS, &all) && refused(&accel, D, nullptr, false, ATTR_MAX_RAYS + 1, &all) && refused(&accel, D, nullptr, false, TOP, &all));
-    EXPECT(!refused(&accel, D, h, true, ATTR_MAX_RAYS, &no_hits) && refused(&accel, D, h, true, ATTR_MAX_RAYS + 1, &no_hits));
-    EXPECT(ATTR_MAX_RAYS <= EDGE); // (so the ray limit is the one that binds; the sizes are checked all the same)
-    EXPECT(attr_bytes(0, 96, "x") == 0 && attr_bytes(EDGE, 96, "x") == EDGE * 96 && attr_bytes(5, 0, "x") == 0);
-    {
-        bool thrown = false;
-        try { (void)attr_bytes(EDGE + 1, 96, "x"); } catch (const std::exception &) { thrown = true; }
-        EXPECT(thrown);
-    }
+    EXPECT(!refused(&accel, D, nullptr, false, QUERY_MAX_RAYS, &all) && refused(&accel, D, nullptr, false, QUERY_MAX_RAYS + 1, &all) && refused(&accel, D, nullptr, false, TOP, &all));
+    EXPECT(!refused(&accel, D, h, true, QUERY_MAX_RAYS, &no_hits) && refused(&accel, D, h, true, QUERY_MAX_RAYS + 1, &no_hits));
+    EXPECT(QUERY_MAX_RAYS <= EDGE); // (so the ray limit is the one that binds; the sizes are checked all the same)
+    EXPECT(checked_bytes(0, 96, "x") == 0 && checked_bytes(EDGE, 96, "x") == EDGE * 96 && checked_bytes(5, 0, "x") == 0);
+    EXPECT(throws([&] { (void)checked_bytes(EDGE + 1, 96, "x"); }));
     // ---- the NULL rule: every combination of the seven planes; only all NULL is refused; the _of form refuses every one with hits
     for (unsigned planes = 0; planes < 128; ++planes) {
         const lg_attr_out o = subset(all, planes);

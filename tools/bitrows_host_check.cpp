@@ -5,35 +5,19 @@
 // buffer on a card.  Nothing is allocated for the limits (the counts and a stand-in pointer are enough); for the placement the caller's
 // bits are a heap block of exactly the extent, (rows - 1) * row_bytes + used bytes, so an overrun of the last row is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/bitrows_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/bitrows_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const char *const TOO_MANY = "too many tiles", *const ROWS = "n_rows";
 
 // refused with the family's wording where that is the refusal
 static bool refused(size_t rows, size_t cols, unsigned tile_rows, const void *bits, size_t row_bytes) {
-    try {
-        check_bit_rows(rows, cols, tile_rows, bits, row_bytes, TOO_MANY, ROWS);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_bit_rows(rows, cols, tile_rows, bits, row_bytes, TOO_MANY, ROWS); });
 }
 static std::string refusal(size_t rows, size_t cols, unsigned tile_rows, const void *bits, size_t row_bytes) {
-    try {
-        check_bit_rows(rows, cols, tile_rows, bits, row_bytes, TOO_MANY, ROWS);
-    } catch (const std::exception &e) {
-        return e.what();
-    }
-    return "";
+    return thrown([&] { check_bit_rows(rows, cols, tile_rows, bits, row_bytes, TOO_MANY, ROWS); });
 }
 
 // one placement: compact rows that name their byte into a block of exactly the extent, filled with 0xA5

@@ -4,40 +4,29 @@
 // name their pixel.  Every film plane is a heap block of exactly width*height pixels, so a placement that reads or writes outside the
 // rectangle's rows, or past a plane's end, is a sanitizer report; a wrong placement inside is caught by the values.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/features_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/features_host.h"
+#include "host_check.h"
 
 using namespace lg;
 
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
-
 static bool refused(const void *accel, const lg_features *out, uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, const double *table) {
-    try {
-        (void)check_features(accel, out, w, h, x0, y0, x1, y1, table);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_features(accel, out, w, h, x0, y0, x1, y1, table); });
 }
 
 // the stubbed launch: pixel (x, y) of the rectangle, compact index i, gets values made of its film offset
-static void stub_launch(FeatureStaging &st, uint32_t w, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
+static void stub_launch(const lg_features &st, uint32_t w, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
     size_t i = 0;
     for (uint32_t y = y0; y < y1; ++y)
         for (uint32_t x = x0; x < x1; ++x, ++i) {
             const float v = (float)((size_t)y * w + x);
-            if (!st.depth.empty()) st.depth[i] = v;
-            if (!st.coverage.empty()) st.coverage[i] = v + 0.5f;
+            if (st.depth) st.depth[i] = v;
+            if (st.coverage) st.coverage[i] = v + 0.5f;
             for (size_t c = 0; c < 3; ++c) {
-                if (!st.normal.empty()) st.normal[3 * i + c] = v + 0.125f * (float)(c + 1);
-                if (!st.albedo.empty()) st.albedo[3 * i + c] = -(v + 0.125f * (float)(c + 1));
+                if (st.normal) st.normal[3 * i + c] = v + 0.125f * (float)(c + 1);
+                if (st.albedo) st.albedo[3 * i + c] = -(v + 0.125f * (float)(c + 1));
             }
             for (size_t c = 0; c < 4; ++c)
-                if (!st.id.empty()) st.id[4 * i + c] = (uint32_t)((size_t)y * w + x) * 4u + (uint32_t)c;
+                if (st.id) st.id[4 * i + c] = (uint32_t)((size_t)y * w + x) * 4u + (uint32_t)c;
         }
 }
 
@@ -62,11 +51,17 @@ static void run(uint32_t w, uint32_t h, uint32_t x0, uint32_t y0, uint32_t x1, u
     const size_t pixels = check_features(&accel, &out, w, h, x0, y0, x1, y1, table);
     EXPECT(pixels == (size_t)(x1 - x0) * (y1 - y0));
     if (pixels == 0) return;
-    FeatureStaging st(out, pixels);
-    EXPECT(st.depth.size() == (out.depth ? pixels : 0) && st.normal.size() == (out.normal ? 3 * pixels : 0) && st.albedo.size() == (out.albedo ? 3 * pixels : 0) &&
-           st.coverage.size() == (out.coverage ? pixels : 0) && st.id.size() == (out.id ? 4 * pixels : 0));
+    HostStaging staging;
+    lg_features st = out; // ... where a plane asked for becomes its compact rows, held as query.cpp holds them: a buffer of exactly their size
+    std::vector<const void *> compact;
+    feature_planes(st, [&](auto *&p, size_t per_pixel, size_t, const char *) {
+        if (p) p = staging.hold<std::remove_reference_t<decltype(*p)>>(pixels * per_pixel);
+        compact.push_back(p);
+    });
+    EXPECT(compact.size() == 5);
     stub_launch(st, w, x0, y0, x1, y1);
-    place_features(out, st, w, x0, y0, x1, y1);
+    place_features(out, compact.data(), w, x0, y0, x1, y1);
+    staging.place(); // (nothing was staged: the form places what it holds)
     for (uint32_t y = 0; y < h; ++y)
         for (uint32_t x = 0; x < w; ++x) {
             const size_t i = (size_t)y * w + x;

@@ -3,38 +3,22 @@
 // into, the host form's staging) in a stand-alone program, meant to be built with -fsanitize=address,undefined and run on the CPU
 // (tests/test_gather_host_sanitized.py does).  The counts go up to 2^64 - 1: an overflow in forming a tile count, a size or a batch is a
 // UBSan report or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel" that fills the staged outputs
-// batch by batch with values that name their element; every caller's array is a heap block of exactly its size, so a copy past an end is
+// batch by batch with bytes that name their place (host_check.h, staged_round); every caller's array is a heap block of exactly its size, so a copy past an end is
 // an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/gather_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/gather_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
 static bool refused(const void *accel, const double *origins, size_t n_poses, const double *dirs, size_t n_dirs, const double *weights, size_t n_weights, int lanes,
                     const lg_gather_out *out) {
-    try {
-        (void)check_gather(accel, origins, n_poses, dirs, n_dirs, weights, n_weights, lanes, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_gather(accel, origins, n_poses, dirs, n_dirs, weights, n_weights, lanes, out); });
 }
 static bool misaligned(const void *origins, const void *frames, const void *dirs, const void *weights, const lg_gather_out &out) {
-    try {
-        check_gather_alignment((const double *)origins, (const double *)frames, (const double *)dirs, (const double *)weights, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_gather_alignment((const double *)origins, (const double *)frames, (const double *)dirs, (const double *)weights, out); });
 }
 // the tile count of a shape in a form, -1 where it passes 2^32 - 1
 static long long tiles(size_t n_poses, size_t n_dirs, int form) {
@@ -50,33 +34,26 @@ static long long bytes(size_t count, size_t each, size_t b) {
     }
 }
 
-// one host-form call without a device: check, stage, "launch" batch by batch as launch.cpp walks the poses, place; then every element
+// one host-form call without a device: check, the batches as launch.cpp walks the poses, then stage, "launch" and place (staged_round)
 static void run(size_t n_poses, size_t n_dirs, size_t n_weights, int lanes, unsigned planes, size_t park_bytes) {
     const size_t pairs = n_poses * n_dirs;
-    std::unique_ptr<double[]> radiance(planes & 1u ? new double[3 * pairs] : nullptr), sums(planes & 2u ? new double[3 * n_poses * n_weights] : nullptr);
-    const lg_gather_out out{radiance.get(), sums.get()};
+    lg_gather_out out{planes & 1u ? (double *)ASKED : nullptr, planes & 2u ? (double *)ASKED : nullptr};
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     const GatherShape shape = check_gather(&accel, D, n_poses, D, n_dirs, D, n_weights, lanes, &out);
     EXPECT(shape.pairs == pairs && shape.form == gather_lanes(n_poses, n_dirs, lanes) && (long long)shape.tiles == tiles(n_poses, n_dirs, shape.form));
-    GatherStaging st(out, pairs, n_poses, n_weights);
-    EXPECT(st.radiance.size() == (out.radiance ? 3 * pairs : 0) && st.sums.size() == (out.sums ? 3 * n_poses * n_weights : 0));
     const size_t batch = out.radiance ? n_poses : gather_batch_poses(n_poses, n_dirs, shape.form, park_bytes);
     EXPECT(batch >= 1 && batch <= n_poses);
     EXPECT(out.radiance || batch == 1 || batch * n_dirs * 24 <= park_bytes);
     size_t covered = 0;
-    for (size_t p0 = 0; p0 < n_poses; p0 += batch) { // the stubbed launch: a batch's tiles stay within the call's
+    for (size_t p0 = 0; p0 < n_poses; p0 += batch) { // a batch's tiles stay within the call's
         const size_t np = n_poses - p0 < batch ? n_poses - p0 : batch;
         EXPECT(tiles(np, n_dirs, shape.form) >= 0 && tiles(np, n_dirs, shape.form) <= (long long)shape.tiles);
-        for (size_t i = p0; i < p0 + np; ++i) {
-            for (size_t e = 0; out.radiance && e < 3 * n_dirs; ++e) st.radiance[3 * i * n_dirs + e] = (double)(3 * i * n_dirs + e);
-            for (size_t e = 0; out.sums && e < 3 * n_weights; ++e) st.sums[3 * i * n_weights + e] = -(double)(3 * i * n_weights + e) - 0.5;
-        }
         covered += np;
     }
     EXPECT(covered == n_poses);
-    place_gather(out, st);
-    for (size_t e = 0; radiance && e < 3 * pairs; ++e) EXPECT(radiance[e] == (double)e);
-    for (size_t e = 0; sums && e < 3 * n_poses * n_weights; ++e) EXPECT(sums[e] == -(double)e - 0.5);
+    // the two outputs as query.cpp stages them: 3 doubles a ray, 3 doubles a pose and weight set
+    const StagedRound r = staged_round([&](auto &&f) { f(out.radiance, pairs * 3, 8, "radiance"); f(out.sums, n_poses * n_weights * 3, 8, "sums"); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 24 * pairs : 0, planes & 2u ? 24 * n_poses * n_weights : 0}));
 }
 
 int main() {

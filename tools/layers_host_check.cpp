@@ -2,37 +2,22 @@
 // n * max_layers and the planes' byte sizes with their overflow checks, the NULL and alignment rules of lg_layers_out, the host form's
 // staging) in a stand-alone program, meant to be built with -fsanitize=address,undefined and run on the CPU
 // (tests/test_layers_host_sanitized.py does).  The counts go up to 2^64 - 1: an overflow in forming a product or a size is a UBSan report
-// or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel" that fills the staged planes with values that
-// name their element; every caller's array is a heap block of exactly its size, so a copy past an end is an ASan report.
+// or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel" that fills the staged planes with bytes that
+// name their place (host_check.h, staged_round); every caller's array is a heap block of exactly its size, so a copy past an end is an
+// ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/layers_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/layers_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
 
 static bool refused(const void *accel, const double *rays, size_t n, uint32_t max_layers, const lg_layers_out *out) {
-    try {
-        (void)check_layers(accel, rays, n, max_layers, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_layers(accel, rays, n, max_layers, out); });
 }
 static bool misaligned(const void *rays, const lg_layers_out &out) {
-    try {
-        check_layers_alignment((const double *)rays, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_layers_alignment((const double *)rays, out); });
 }
 // lg_layers_out with the planes of a 5-bit mask named from `all`
 static lg_layers_out subset(const lg_layers_out &all, unsigned planes) {
@@ -40,49 +25,18 @@ static lg_layers_out subset(const lg_layers_out &all, unsigned planes) {
                          planes & 16u ? all.inside : nullptr};
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at
 static void run(size_t n, uint32_t max_layers, unsigned planes) {
     const size_t total = n * max_layers;
-    std::unique_ptr<lg_hit[]> hits(planes & 1u ? new lg_hit[total] : nullptr);
-    std::unique_ptr<double[]> along(planes & 2u ? new double[total] : nullptr), inside(planes & 16u ? new double[n] : nullptr);
-    std::unique_ptr<uint32_t[]> id(planes & 4u ? new uint32_t[4 * total] : nullptr), count(planes & 8u ? new uint32_t[n] : nullptr);
-    const lg_layers_out out{hits.get(), along.get(), id.get(), count.get(), inside.get()};
+    const lg_layers_out all{(lg_hit *)ASKED, (double *)ASKED, (uint32_t *)ASKED, (uint32_t *)ASKED, (double *)ASKED};
+    lg_layers_out out = subset(all, planes);
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     EXPECT(check_layers(&accel, D, n, max_layers, &out) == total);
-    LayersStaging st(out, n, total);
-    EXPECT(st.hits.size() == (out.hits ? total : 0) && st.along.size() == (out.along ? total : 0) && st.id.size() == (out.id ? 4 * total : 0) &&
-           st.count.size() == (out.count ? n : 0) && st.inside.size() == (out.inside ? n : 0));
     // what the host form allocates on the device and copies back: the table's counts in the plane's own elements
-    size_t staged_bytes = 0, want_bytes = 0;
-    layer_planes(out, n, total, [&](auto *p, auto plane, size_t elems, size_t, const char *) { if (p) { staged_bytes += (st.*plane).size() * sizeof *p; want_bytes += elems * sizeof *p; } });
-    EXPECT(staged_bytes == want_bytes);
-    EXPECT(want_bytes == (out.hits ? 96 * total : 0) + (out.along ? 8 * total : 0) + (out.id ? 16 * total : 0) + (out.count ? 4 * n : 0) + (out.inside ? 8 * n : 0));
-    for (size_t e = 0; e < total; ++e) { // the stubbed launch
-        if (out.hits) {
-            lg_hit h;
-            std::memset(&h, 0, sizeof h);
-            h.t = (double)e + 0.25; h.prim = (uint32_t)e; h.material = -(int32_t)e;
-            st.hits[e] = h;
-        }
-        if (out.along) st.along[e] = (double)e + 0.5;
-        for (size_t c = 0; c < 4; ++c)
-            if (out.id) st.id[4 * e + c] = (uint32_t)(4 * e + c);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (out.count) st.count[i] = (uint32_t)(i + 7);
-        if (out.inside) st.inside[i] = (double)i + 0.125;
-    }
-    place_layers(out, st);
-    for (size_t e = 0; e < total; ++e) {
-        if (hits) EXPECT(hits[e].t == (double)e + 0.25 && hits[e].prim == (uint32_t)e && hits[e].material == -(int32_t)e);
-        if (along) EXPECT(along[e] == (double)e + 0.5);
-        for (size_t c = 0; c < 4; ++c)
-            if (id) EXPECT(id[4 * e + c] == (uint32_t)(4 * e + c));
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (count) EXPECT(count[i] == (uint32_t)(i + 7));
-        if (inside) EXPECT(inside[i] == (double)i + 0.125);
-    }
+    const StagedRound r = staged_round([&](auto &&f) { layer_planes(out, n, total, f); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 96 * total : 0, planes & 2u ? 8 * total : 0, planes & 4u ? 4 * 4 * total : 0, planes & 8u ? 4 * n : 0, planes & 16u ? 8 * n : 0}));
+    const size_t want_bytes = (planes & 1u ? 96 * total : 0) + (planes & 2u ? 8 * total : 0) + (planes & 4u ? 16 * total : 0) + (planes & 8u ? 4 * n : 0) + (planes & 16u ? 8 * n : 0);
+    EXPECT(r.bytes == want_bytes);
 }
 
 int main() {
@@ -95,7 +49,7 @@ int main() {
     const size_t TOP = ~(size_t)0, EDGE = TOP / 96; // the most lg_hit records an address space holds
     const uint32_t KMAX = 0xFFFFFFFFu;
     static_assert(sizeof(size_t) == 8, "the limits below are written for a 64-bit size_t");
-    static_assert(LAYERS_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
+    static_assert(QUERY_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
     // ---- check_layers: every error of the contract that needs no device
     EXPECT(!refused(&accel, D, 3, 5, &all) && check_layers(&accel, D, 3, 5, &all) == 15);
     EXPECT(refused(nullptr, D, 3, 5, &all));
@@ -103,32 +57,28 @@ int main() {
     EXPECT(refused(&accel, D, 3, 5, nullptr));
     EXPECT(refused(&accel, D, 3, 5, &none));
     // max_layers of 0, 1 and 2^32 - 1
-    EXPECT(refused(&accel, D, 1, 0, &all) && refused(&accel, D, LAYERS_MAX_RAYS, 0, &all));
+    EXPECT(refused(&accel, D, 1, 0, &all) && refused(&accel, D, QUERY_MAX_RAYS, 0, &all));
     EXPECT(!refused(&accel, D, 1, 1, &all) && check_layers(&accel, D, 1, 1, &all) == 1);
     EXPECT(!refused(&accel, D, 1, KMAX, &all) && check_layers(&accel, D, 1, KMAX, &all) == KMAX);
     EXPECT(!refused(&accel, D, 65, KMAX, &all) && check_layers(&accel, D, 65, KMAX, &all) == 65ull * KMAX);
     // the ray limit: (2^32 - 1) * 64 and one above
-    EXPECT(!refused(&accel, D, LAYERS_MAX_RAYS, 1, &all) && check_layers(&accel, D, LAYERS_MAX_RAYS, 1, &all) == LAYERS_MAX_RAYS);
-    EXPECT(refused(&accel, D, LAYERS_MAX_RAYS + 1, 1, &all) && refused(&accel, D, TOP, 1, &all) && refused(&accel, D, TOP, KMAX, &all));
+    EXPECT(!refused(&accel, D, QUERY_MAX_RAYS, 1, &all) && check_layers(&accel, D, QUERY_MAX_RAYS, 1, &all) == QUERY_MAX_RAYS);
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS + 1, 1, &all) && refused(&accel, D, TOP, 1, &all) && refused(&accel, D, TOP, KMAX, &all));
     // n * max_layers just under, at and over SIZE_MAX / 96: the hits plane's bytes fit or do not, whichever planes are asked for
     const uint32_t KS[] = {(uint32_t)1 << 20, 1000003u, KMAX};
     for (uint32_t k : KS) {
         const size_t under = EDGE / k; // under * k <= EDGE < (under + 1) * k
-        EXPECT(under <= LAYERS_MAX_RAYS && under * k <= EDGE && EDGE - under * k < k);
+        EXPECT(under <= QUERY_MAX_RAYS && under * k <= EDGE && EDGE - under * k < k);
         EXPECT(!refused(&accel, D, under, k, &all) && check_layers(&accel, D, under, k, &all) == under * k);
         EXPECT(refused(&accel, D, under + 1, k, &all));
         const lg_layers_out only_count = subset(all, 8u); // the limit does not depend on the planes asked for
         EXPECT(!refused(&accel, D, under, k, &only_count) && refused(&accel, D, under + 1, k, &only_count));
     }
     // the product itself: n * max_layers beyond 2^64 is refused before it is formed
-    EXPECT(refused(&accel, D, LAYERS_MAX_RAYS, KMAX, &all) && refused(&accel, D, (size_t)1 << 33, (uint32_t)1 << 31, &all));
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS, KMAX, &all) && refused(&accel, D, (size_t)1 << 33, (uint32_t)1 << 31, &all));
     // the sizes
-    EXPECT(layers_bytes(0, 96, "x") == 0 && layers_bytes(EDGE, 96, "x") == EDGE * 96 && layers_bytes(5, 0, "x") == 0);
-    {
-        bool thrown = false;
-        try { (void)layers_bytes(EDGE + 1, 96, "x"); } catch (const std::exception &) { thrown = true; }
-        EXPECT(thrown);
-    }
+    EXPECT(checked_bytes(0, 96, "x") == 0 && checked_bytes(EDGE, 96, "x") == EDGE * 96 && checked_bytes(5, 0, "x") == 0);
+    EXPECT(throws([&] { (void)checked_bytes(EDGE + 1, 96, "x"); }));
     // ---- the NULL rule: every combination of the five planes; only all NULL is refused
     for (unsigned planes = 0; planes < 32; ++planes) {
         const lg_layers_out o = subset(all, planes);

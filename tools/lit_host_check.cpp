@@ -2,52 +2,32 @@
 // n * K * 24 and n * W * 4 with their overflow checks, the NULL and alignment rules of lg_lit_out's nine planes, the host form's staging)
 // in a stand-alone program, meant to be built with -fsanitize=address,undefined and run on the CPU (tests/test_lit_host_sanitized.py does).
 // The counts go up to 2^64 - 1: an overflow in forming a size is a UBSan report or a wrong value here, not a short buffer on a card.  The
-// launch is stubbed out: a "kernel" that fills the staged planes with values that name their element; every caller's array is a heap block
+// launch is stubbed out: a "kernel" that fills the staged planes with bytes that name their place (host_check.h, staged_round); every caller's array is a heap block
 // of exactly its size, so a copy past an end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/lit_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/lit_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
 static const lg_light ONE_LIGHT = {{0.0, 1.0, 0.0}, {1.0, 1.0, 1.0}, {1.0, 0.0, 0.0}};
 
 static lg_light_set set_of(const lg_light *table, uint32_t count, uint32_t per_ray) { return lg_light_set{table, count, per_ray, {0.1, 0.2, 0.3}}; }
 static bool refused(const void *accel, const double *rays, size_t n, const lg_light_set *lights, const lg_lit_out *out) {
-    try {
-        (void)check_lit(accel, rays, n, lights, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_lit(accel, rays, n, lights, out); });
 }
 static bool misaligned(const void *rays, const lg_light_set &lights, const lg_lit_out &out, size_t n) {
-    try {
-        LitSizes z;
-        z.n = n; z.K = lights.count; z.W = lit_words(lights.count);
-        check_lit_alignment((const double *)rays, lights, out, z);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { LitSizes z; z.n = n; z.K = lights.count; z.W = lit_words(lights.count); check_lit_alignment((const double *)rays, lights, out, z); });
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at.  planes: a 9-bit mask
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at.
+// planes: a 9-bit mask
 static void run(size_t n, uint32_t K, uint32_t per_ray, unsigned planes) {
     const size_t W = (K + 31) / 32;
-    std::unique_ptr<lg_hit[]> hits(planes & 1u ? new lg_hit[n] : nullptr);
-    std::unique_ptr<double[]> direct(planes & 2u ? new double[3 * n] : nullptr), reflect(planes & 8u ? new double[6 * n] : nullptr),
-        reflect_weight(planes & 16u ? new double[3 * n] : nullptr), refract(planes & 32u ? new double[6 * n] : nullptr),
-        refract_weight(planes & 64u ? new double[5 * n] : nullptr), terms(planes & 128u ? new double[n * K * 3 + 1] : nullptr);
-    std::unique_ptr<uint32_t[]> flags(planes & 4u ? new uint32_t[n] : nullptr), visible(planes & 256u ? new uint32_t[n * W + 1] : nullptr);
-    const lg_lit_out out{{hits.get(), direct.get(), flags.get(), reflect.get(), reflect_weight.get(), refract.get(), refract_weight.get()}, terms.get(), visible.get()};
+    const auto asked = [&](unsigned bit, auto *type) { return planes & bit ? reinterpret_cast<decltype(type)>(ASKED) : nullptr; };
+    lg_lit_out out{{asked(1u, (lg_hit *)nullptr), asked(2u, (double *)nullptr), asked(4u, (uint32_t *)nullptr), asked(8u, (double *)nullptr), asked(16u, (double *)nullptr),
+                    asked(32u, (double *)nullptr), asked(64u, (double *)nullptr)}, asked(128u, (double *)nullptr), asked(256u, (uint32_t *)nullptr)};
     std::unique_ptr<lg_light[]> table(new lg_light[(per_ray ? n : 1) * K + 1]);
     const lg_light_set ls = set_of(table.get(), K, per_ray);
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
@@ -56,33 +36,18 @@ static void run(size_t n, uint32_t K, uint32_t per_ray, unsigned planes) {
     if (!any) return;
     const LitSizes z = check_lit(&accel, D, n, &ls, &out);
     EXPECT(z.n == n && z.K == K && z.W == W && z.terms == n * K * 3 && z.visible == n * W && z.lights == (per_ray ? n * K : K));
-    LitStaging st(out, z);
-    EXPECT(st.scatter.hits.size() == (out.scatter.hits ? n : 0) && st.scatter.direct.size() == (out.scatter.direct ? 3 * n : 0) &&
-           st.scatter.flags.size() == (out.scatter.flags ? n : 0) && st.scatter.refract_weight.size() == (out.scatter.refract_weight ? 5 * n : 0));
-    EXPECT(st.terms.size() == (out.terms && K ? n * K * 3 : 0) && st.visible.size() == (out.visible && K ? n * W : 0));
-    // the "kernel": every staged element gets a value that names it
-    for (size_t i = 0; i < st.terms.size(); ++i) st.terms[i] = 0.5 + (double)i;
-    for (size_t i = 0; i < st.visible.size(); ++i) st.visible[i] = 0xA0000000u + (uint32_t)i;
-    for (size_t i = 0; i < st.scatter.direct.size(); ++i) st.scatter.direct[i] = 0.25 + (double)i;
-    for (size_t i = 0; i < st.scatter.flags.size(); ++i) st.scatter.flags[i] = (uint32_t)(i & 7u);
-    if (terms) terms[n * K * 3] = -7.0; // (the element behind the plane: placement must not reach it)
-    if (visible) visible[n * W] = 0x77777777u;
-    place_lit(out, z, st);
-    bool ok = true;
-    for (size_t i = 0; terms && K && i < n * K * 3; ++i) ok = ok && terms[i] == 0.5 + (double)i;
-    for (size_t i = 0; visible && K && i < n * W; ++i) ok = ok && visible[i] == 0xA0000000u + (uint32_t)i;
-    for (size_t i = 0; direct && i < 3 * n; ++i) ok = ok && direct[i] == 0.25 + (double)i;
-    for (size_t i = 0; flags && i < n; ++i) ok = ok && flags[i] == (uint32_t)(i & 7u);
-    EXPECT(ok);
-    EXPECT(!terms || terms[n * K * 3] == -7.0);
-    EXPECT(!visible || visible[n * W] == 0x77777777u);
     // the plane table: nine planes with lights, seven without, in the struct's order, with their alignments
-    lg_lit_out copy = out;
     size_t seen = 0;
     const size_t want_align[9] = {16, 8, 4, 8, 8, 8, 8, 8, 4};
     bool table_ok = true;
-    lit_planes(copy, z, [&](auto *p, auto, size_t, size_t align, const char *what) { (void)p; table_ok = table_ok && what[0] != 0 && align == want_align[seen]; ++seen; });
+    lit_planes(out, z, [&](auto *p, size_t, size_t align, const char *what) { (void)p; table_ok = table_ok && what[0] != 0 && align == want_align[seen]; ++seen; });
     EXPECT(table_ok && seen == (K ? 9u : 7u));
+    // the staging: each plane's bytes; terms and visible are n * K * 3 doubles and n * W words exactly (their blocks end there)
+    const StagedRound r = staged_round([&](auto &&f) { lit_planes(out, z, f); });
+    std::vector<size_t> want{planes & 1u ? 96 * n : 0, planes & 2u ? 8 * 3 * n : 0, planes & 4u ? 4 * n : 0, planes & 8u ? 8 * 6 * n : 0, planes & 16u ? 8 * 3 * n : 0, planes & 32u ? 8 * 6 * n : 0,
+                             planes & 64u ? 8 * 5 * n : 0};
+    if (K) { want.push_back(planes & 128u ? 8 * n * K * 3 : 0); want.push_back(planes & 256u ? 4 * n * W : 0); }
+    EXPECT(r.plane_bytes == want);
 }
 
 int main() {
@@ -117,9 +82,9 @@ int main() {
 
     // the sizes at the edge of the address space: n * K * 72, n * K * 24, n * W * 4, and the ray limit
     const size_t TOP = SIZE_MAX;
-    EXPECT(!refused(&accel, D, SCATTER_MAX_RAYS, &one, &all));
-    EXPECT(refused(&accel, D, SCATTER_MAX_RAYS + 1, &one, &all));
-    { const lg_light_set s = set_of(&ONE_LIGHT, LG_MAX_CALL_LIGHTS, 1); EXPECT(!refused(&accel, D, SCATTER_MAX_RAYS, &s, &all)); } // 2^38 * 2^10 * 72 < 2^64
+    EXPECT(!refused(&accel, D, QUERY_MAX_RAYS, &one, &all));
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS + 1, &one, &all));
+    { const lg_light_set s = set_of(&ONE_LIGHT, LG_MAX_CALL_LIGHTS, 1); EXPECT(!refused(&accel, D, QUERY_MAX_RAYS, &s, &all)); } // 2^38 * 2^10 * 72 < 2^64
     { const lg_light_set s = set_of(&ONE_LIGHT, 1024, 0);
       EXPECT(refused(&accel, D, TOP / 72 / 1024 + 1, &s, &all));  // n * K * 72 wraps
       EXPECT(refused(&accel, D, TOP / 24 / 1024 + 1, &s, &all));  // n * K * 24 wraps

@@ -2,40 +2,24 @@
 // n * max_bounces and the planes' byte sizes with their overflow checks, the rule table's validation, the NULL and alignment rules of
 // lg_paths_out, the host form's staging) in a stand-alone program, meant to be built with -fsanitize=address,undefined and run on the CPU
 // (tests/test_paths_host_sanitized.py does).  The counts go up to 2^64 - 1: an overflow in forming a product or a size is a UBSan report
-// or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel" that fills the staged planes with values that
-// name their element; every caller's array is a heap block of exactly its size, so a copy past an end is an ASan report.
+// or a wrong value here, not a short buffer on a card.  The launch is stubbed out: a "kernel" that fills the staged planes with bytes that
+// name their place (host_check.h, staged_round); every caller's array is a heap block of exactly its size, so a copy past an end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/paths_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/paths_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
 static const lg_path_rule RULES[3] = {{LG_PATH_REFRACT, 0u, 1.5, 1.0}, {LG_PATH_REFLECT, 0u, 1.0, 0.5}, {LG_PATH_ABSORB, 0u, 1.0, 1.0}};
 
 static bool refused(const void *accel, const double *rays, size_t n, uint32_t max_bounces, const lg_paths_out *out, const lg_path_rule *rules = RULES, size_t n_rules = 3,
                     size_t materials = 3, int normal = 0) {
-    try {
-        (void)check_paths(accel, rays, n, max_bounces, rules, n_rules, materials, normal, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_paths(accel, rays, n, max_bounces, rules, n_rules, materials, normal, out); });
 }
 static size_t checked(const void *accel, size_t n, uint32_t max_bounces, const lg_paths_out *out) { return check_paths(accel, D, n, max_bounces, RULES, 3, 3, 0, out); }
 static bool misaligned(const void *rays, const void *start_medium, const lg_paths_out &out) {
-    try {
-        check_paths_alignment((const double *)rays, (const uint32_t *)start_medium, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_paths_alignment((const double *)rays, (const uint32_t *)start_medium, out); });
 }
 // lg_paths_out with the planes of a 9-bit mask named from `all`, in the struct's order
 static lg_paths_out subset(const lg_paths_out &all, unsigned planes) {
@@ -44,65 +28,20 @@ static lg_paths_out subset(const lg_paths_out &all, unsigned planes) {
                         planes & 64u ? all.gain : nullptr,  planes & 128u ? all.last : nullptr, planes & 256u ? all.medium : nullptr};
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at
 static void run(size_t n, uint32_t max_bounces, unsigned planes) {
     const size_t total = n * max_bounces;
-    std::unique_ptr<lg_hit[]> hits(planes & 1u ? new lg_hit[total] : nullptr);
-    std::unique_ptr<double[]> point(planes & 2u ? new double[3 * total] : nullptr), along(planes & 8u ? new double[total] : nullptr),
-        gain(planes & 64u ? new double[n] : nullptr), last(planes & 128u ? new double[6 * n] : nullptr);
-    std::unique_ptr<uint32_t[]> id(planes & 4u ? new uint32_t[4 * total] : nullptr), count(planes & 16u ? new uint32_t[n] : nullptr),
-        end(planes & 32u ? new uint32_t[n] : nullptr), medium(planes & 256u ? new uint32_t[n] : nullptr);
-    const lg_paths_out out{hits.get(), point.get(), id.get(), along.get(), count.get(), end.get(), gain.get(), last.get(), medium.get()};
+    const lg_paths_out all{(lg_hit *)ASKED, (double *)ASKED, (uint32_t *)ASKED, (double *)ASKED, (uint32_t *)ASKED, (uint32_t *)ASKED, (double *)ASKED, (double *)ASKED, (uint32_t *)ASKED};
+    lg_paths_out out = subset(all, planes);
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     EXPECT(checked(&accel, n, max_bounces, &out) == total);
-    PathsStaging st(out, n, total);
-    EXPECT(st.hits.size() == (out.hits ? total : 0) && st.point.size() == (out.point ? 3 * total : 0) && st.id.size() == (out.id ? 4 * total : 0) &&
-           st.along.size() == (out.along ? total : 0) && st.count.size() == (out.count ? n : 0) && st.end.size() == (out.end ? n : 0) &&
-           st.gain.size() == (out.gain ? n : 0) && st.last.size() == (out.last ? 6 * n : 0) && st.medium.size() == (out.medium ? n : 0));
     // what the host form allocates on the device and copies back: the table's counts in the plane's own elements
-    size_t staged_bytes = 0, want_bytes = 0;
-    path_planes(out, n, total, [&](auto *p, auto plane, size_t elems, size_t, const char *) { if (p) { staged_bytes += (st.*plane).size() * sizeof *p; want_bytes += elems * sizeof *p; } });
-    EXPECT(staged_bytes == want_bytes);
-    EXPECT(want_bytes == (out.hits ? 96 * total : 0) + (out.point ? 24 * total : 0) + (out.id ? 16 * total : 0) + (out.along ? 8 * total : 0) + (out.count ? 4 * n : 0) +
-                             (out.end ? 4 * n : 0) + (out.gain ? 8 * n : 0) + (out.last ? 48 * n : 0) + (out.medium ? 4 * n : 0));
-    for (size_t e = 0; e < total; ++e) { // the stubbed launch
-        if (out.hits) {
-            lg_hit h;
-            std::memset(&h, 0, sizeof h);
-            h.t = (double)e + 0.25; h.prim = (uint32_t)e; h.material = -(int32_t)e;
-            st.hits[e] = h;
-        }
-        for (size_t c = 0; c < 3; ++c)
-            if (out.point) st.point[3 * e + c] = (double)(3 * e + c) + 0.75;
-        for (size_t c = 0; c < 4; ++c)
-            if (out.id) st.id[4 * e + c] = (uint32_t)(4 * e + c);
-        if (out.along) st.along[e] = (double)e + 0.5;
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (out.count) st.count[i] = (uint32_t)(i + 7);
-        if (out.end) st.end[i] = (uint32_t)(i + 11);
-        if (out.gain) st.gain[i] = (double)i + 0.125;
-        for (size_t c = 0; c < 6; ++c)
-            if (out.last) st.last[6 * i + c] = (double)(6 * i + c) + 0.375;
-        if (out.medium) st.medium[i] = (uint32_t)(i + 13);
-    }
-    place_paths(out, st);
-    for (size_t e = 0; e < total; ++e) {
-        if (hits) EXPECT(hits[e].t == (double)e + 0.25 && hits[e].prim == (uint32_t)e && hits[e].material == -(int32_t)e);
-        for (size_t c = 0; c < 3; ++c)
-            if (point) EXPECT(point[3 * e + c] == (double)(3 * e + c) + 0.75);
-        for (size_t c = 0; c < 4; ++c)
-            if (id) EXPECT(id[4 * e + c] == (uint32_t)(4 * e + c));
-        if (along) EXPECT(along[e] == (double)e + 0.5);
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (count) EXPECT(count[i] == (uint32_t)(i + 7));
-        if (end) EXPECT(end[i] == (uint32_t)(i + 11));
-        if (gain) EXPECT(gain[i] == (double)i + 0.125);
-        for (size_t c = 0; c < 6; ++c)
-            if (last) EXPECT(last[6 * i + c] == (double)(6 * i + c) + 0.375);
-        if (medium) EXPECT(medium[i] == (uint32_t)(i + 13));
-    }
+    const StagedRound r = staged_round([&](auto &&f) { path_planes(out, n, total, f); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 96 * total : 0, planes & 2u ? 8 * 3 * total : 0, planes & 4u ? 4 * 4 * total : 0, planes & 8u ? 8 * total : 0, planes & 16u ? 4 * n : 0,
+                                                 planes & 32u ? 4 * n : 0, planes & 64u ? 8 * n : 0, planes & 128u ? 8 * 6 * n : 0, planes & 256u ? 4 * n : 0}));
+    const size_t want_bytes = (planes & 1u ? 96 * total : 0) + (planes & 2u ? 24 * total : 0) + (planes & 4u ? 16 * total : 0) + (planes & 8u ? 8 * total : 0) + (planes & 16u ? 4 * n : 0) +
+                              (planes & 32u ? 4 * n : 0) + (planes & 64u ? 8 * n : 0) + (planes & 128u ? 48 * n : 0) + (planes & 256u ? 4 * n : 0);
+    EXPECT(r.bytes == want_bytes);
 }
 
 int main() {
@@ -115,7 +54,7 @@ int main() {
     const size_t TOP = ~(size_t)0, EDGE = TOP / 96; // the most lg_hit records an address space holds
     const uint32_t KMAX = 0xFFFFFFFFu;
     static_assert(sizeof(size_t) == 8, "the limits below are written for a 64-bit size_t");
-    static_assert(PATHS_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
+    static_assert(QUERY_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
     // ---- check_paths: every error of the contract that needs no device
     EXPECT(!refused(&accel, D, 3, 5, &all) && checked(&accel, 3, 5, &all) == 15);
     EXPECT(refused(nullptr, D, 3, 5, &all));
@@ -123,36 +62,32 @@ int main() {
     EXPECT(refused(&accel, D, 3, 5, nullptr));
     EXPECT(refused(&accel, D, 3, 5, &none));
     // max_bounces of 0, 1 and 2^32 - 1
-    EXPECT(refused(&accel, D, 1, 0, &all) && refused(&accel, D, PATHS_MAX_RAYS, 0, &all));
+    EXPECT(refused(&accel, D, 1, 0, &all) && refused(&accel, D, QUERY_MAX_RAYS, 0, &all));
     EXPECT(!refused(&accel, D, 1, 1, &all) && checked(&accel, 1, 1, &all) == 1);
     EXPECT(!refused(&accel, D, 1, KMAX, &all) && checked(&accel, 1, KMAX, &all) == KMAX);
     EXPECT(!refused(&accel, D, 65, KMAX, &all) && checked(&accel, 65, KMAX, &all) == 65ull * KMAX);
     // the ray limit: (2^32 - 1) * 64 and one above
-    EXPECT(!refused(&accel, D, PATHS_MAX_RAYS, 1, &all) && checked(&accel, PATHS_MAX_RAYS, 1, &all) == PATHS_MAX_RAYS);
-    EXPECT(refused(&accel, D, PATHS_MAX_RAYS + 1, 1, &all) && refused(&accel, D, TOP, 1, &all) && refused(&accel, D, TOP, KMAX, &all));
+    EXPECT(!refused(&accel, D, QUERY_MAX_RAYS, 1, &all) && checked(&accel, QUERY_MAX_RAYS, 1, &all) == QUERY_MAX_RAYS);
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS + 1, 1, &all) && refused(&accel, D, TOP, 1, &all) && refused(&accel, D, TOP, KMAX, &all));
     // n * max_bounces just under, at and over SIZE_MAX / 96: the hits plane's bytes fit or do not, whichever planes are asked for
     const uint32_t KS[] = {(uint32_t)1 << 20, 1000003u, KMAX};
     for (uint32_t k : KS) {
         const size_t under = EDGE / k; // under * k <= EDGE < (under + 1) * k
-        EXPECT(under <= PATHS_MAX_RAYS && under * k <= EDGE && EDGE - under * k < k);
+        EXPECT(under <= QUERY_MAX_RAYS && under * k <= EDGE && EDGE - under * k < k);
         EXPECT(!refused(&accel, D, under, k, &all) && checked(&accel, under, k, &all) == under * k);
         EXPECT(refused(&accel, D, under + 1, k, &all));
         const lg_paths_out only_count = subset(all, 16u); // the limit does not depend on the planes asked for
         EXPECT(!refused(&accel, D, under, k, &only_count) && refused(&accel, D, under + 1, k, &only_count));
         // no count of the plane table wraps at the edge: the widest in elements (id, 4 a vertex) and in bytes (hits)
         size_t most = 0;
-        path_planes(all, under, under * k, [&](auto *p, auto, size_t elems, size_t, const char *) { EXPECT(elems <= TOP / sizeof *p); most = elems > most ? elems : most; });
+        path_planes(all, under, under * k, [&](auto *p, size_t elems, size_t, const char *) { EXPECT(elems <= TOP / sizeof *p); most = elems > most ? elems : most; });
         EXPECT(most == 4 * under * k || most == 6 * under);
     }
     // the product itself: n * max_bounces beyond 2^64 is refused before it is formed
-    EXPECT(refused(&accel, D, PATHS_MAX_RAYS, KMAX, &all) && refused(&accel, D, (size_t)1 << 33, (uint32_t)1 << 31, &all));
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS, KMAX, &all) && refused(&accel, D, (size_t)1 << 33, (uint32_t)1 << 31, &all));
     // the sizes
-    EXPECT(paths_bytes(0, 96, "x") == 0 && paths_bytes(EDGE, 96, "x") == EDGE * 96 && paths_bytes(5, 0, "x") == 0);
-    {
-        bool thrown = false;
-        try { (void)paths_bytes(EDGE + 1, 96, "x"); } catch (const std::exception &) { thrown = true; }
-        EXPECT(thrown);
-    }
+    EXPECT(checked_bytes(0, 96, "x") == 0 && checked_bytes(EDGE, 96, "x") == EDGE * 96 && checked_bytes(5, 0, "x") == 0);
+    EXPECT(throws([&] { (void)checked_bytes(EDGE + 1, 96, "x"); }));
     // ---- the rules: NULL, a count that is not the accel's, an unknown action, reserved set; normal outside {0, 1}
     EXPECT(refused(&accel, D, 3, 5, &all, nullptr, 3, 3));
     EXPECT(refused(&accel, D, 3, 5, &all, RULES, 2, 3) && refused(&accel, D, 3, 5, &all, RULES, 3, 2) && refused(&accel, D, 3, 5, &all, RULES, 0, 3));

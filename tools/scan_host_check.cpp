@@ -2,37 +2,21 @@
 // with their 32-bit limit, the planes' byte sizes, the NULL and alignment rules of lg_scan_out, the host form's staging) in a stand-alone
 // program, meant to be built with -fsanitize=address,undefined and run on the CPU (tests/test_scan_host_sanitized.py does).  The counts
 // go up to 2^64 - 1: an overflow in forming a tile count or a size is a UBSan report or a wrong value here, not a short buffer on a card.
-// The launch is stubbed out: a "kernel" that fills the staged planes with values that name their element; every caller's array is a heap
+// The launch is stubbed out: a "kernel" that fills the staged planes with bytes that name their place (host_check.h, staged_round); every caller's array is a heap
 // block of exactly its size, so a copy past an end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/scan_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/scan_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
 static bool refused(const void *accel, const double *origins, size_t n_poses, const double *beams, size_t n_beams, int lanes, const lg_scan_out *out) {
-    try {
-        (void)check_scan(accel, origins, n_poses, beams, n_beams, lanes, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { (void)check_scan(accel, origins, n_poses, beams, n_beams, lanes, out); });
 }
 static bool misaligned(const void *origins, const void *frames, const void *beams, const lg_scan_out &out) {
-    try {
-        check_scan_alignment((const double *)origins, (const double *)frames, (const double *)beams, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_scan_alignment((const double *)origins, (const double *)frames, (const double *)beams, out); });
 }
 // the tile count of a shape in a form, -1 where it passes 2^32 - 1
 static long long tiles(size_t n_poses, size_t n_beams, int form) {
@@ -40,46 +24,18 @@ static long long tiles(size_t n_poses, size_t n_beams, int form) {
     return scan_tiles(n_poses, n_beams, form, &t) ? (long long)t : -1;
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at
 static void run(size_t n_poses, size_t n_beams, int lanes, unsigned planes) {
     const size_t pairs = n_poses * n_beams;
-    std::unique_ptr<float[]> range(planes & 1u ? new float[pairs] : nullptr), point(planes & 2u ? new float[3 * pairs] : nullptr),
-        normal(planes & 4u ? new float[3 * pairs] : nullptr), nearest(planes & 32u ? new float[n_poses] : nullptr);
-    std::unique_ptr<uint32_t[]> id(planes & 8u ? new uint32_t[4 * pairs] : nullptr), hits(planes & 16u ? new uint32_t[n_poses] : nullptr);
-    const lg_scan_out out{range.get(), point.get(), normal.get(), id.get(), hits.get(), nearest.get()};
+    lg_scan_out out{planes & 1u ? (float *)ASKED : nullptr, planes & 2u ? (float *)ASKED : nullptr, planes & 4u ? (float *)ASKED : nullptr,
+                    planes & 8u ? (uint32_t *)ASKED : nullptr, planes & 16u ? (uint32_t *)ASKED : nullptr, planes & 32u ? (float *)ASKED : nullptr};
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     const ScanShape shape = check_scan(&accel, D, n_poses, D, n_beams, lanes, &out);
     EXPECT(shape.pairs == pairs && shape.form == scan_lanes(n_poses, n_beams, lanes) && (long long)shape.tiles == tiles(n_poses, n_beams, shape.form));
-    ScanStaging st(out, n_poses, pairs);
-    EXPECT(st.range.size() == (out.range ? pairs : 0) && st.point.size() == (out.point ? 3 * pairs : 0) && st.normal.size() == (out.normal ? 3 * pairs : 0) &&
-           st.id.size() == (out.id ? 4 * pairs : 0) && st.hits.size() == (out.hits ? n_poses : 0) && st.nearest.size() == (out.nearest ? n_poses : 0));
-    for (size_t e = 0; e < pairs; ++e) { // the stubbed launch
-        if (out.range) st.range[e] = (float)e;
-        for (size_t c = 0; c < 3; ++c) {
-            if (out.point) st.point[3 * e + c] = (float)e + 0.125f * (float)(c + 1);
-            if (out.normal) st.normal[3 * e + c] = -((float)e + 0.125f * (float)(c + 1));
-        }
-        for (size_t c = 0; c < 4; ++c)
-            if (out.id) st.id[4 * e + c] = (uint32_t)(4 * e + c);
-    }
-    for (size_t i = 0; i < n_poses; ++i) {
-        if (out.hits) st.hits[i] = (uint32_t)(i + 7);
-        if (out.nearest) st.nearest[i] = (float)i + 0.5f;
-    }
-    place_scan(out, st);
-    for (size_t e = 0; e < pairs; ++e) {
-        if (range) EXPECT(range[e] == (float)e);
-        for (size_t c = 0; c < 3; ++c) {
-            if (point) EXPECT(point[3 * e + c] == (float)e + 0.125f * (float)(c + 1));
-            if (normal) EXPECT(normal[3 * e + c] == -((float)e + 0.125f * (float)(c + 1)));
-        }
-        for (size_t c = 0; c < 4; ++c)
-            if (id) EXPECT(id[4 * e + c] == (uint32_t)(4 * e + c));
-    }
-    for (size_t i = 0; i < n_poses; ++i) {
-        if (hits) EXPECT(hits[i] == (uint32_t)(i + 7));
-        if (nearest) EXPECT(nearest[i] == (float)i + 0.5f);
-    }
+    const StagedRound r = staged_round([&](auto &&f) { scan_planes(out, n_poses, pairs, f); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 4 * pairs : 0, planes & 2u ? 4 * 3 * pairs : 0, planes & 4u ? 4 * 3 * pairs : 0, planes & 8u ? 4 * 4 * pairs : 0,
+                                                 planes & 16u ? 4 * n_poses : 0, planes & 32u ? 4 * n_poses : 0}));
+    EXPECT(r.bytes == pairs * ((planes & 1u ? 4 : 0) + (planes & 2u ? 12 : 0) + (planes & 4u ? 12 : 0) + (planes & 8u ? 16 : 0)) + n_poses * ((planes & 16u ? 4 : 0) + (planes & 32u ? 4 : 0)));
 }
 
 int main() {
@@ -133,12 +89,8 @@ int main() {
         EXPECT(c.form == 2 && c.tiles == 0xFFFFFFFFu && c.pairs == 64 * M * 8);
     }
     // the sizes
-    EXPECT(scan_bytes(0, 16, "x") == 0 && scan_bytes(TOP / 16, 16, "x") == TOP / 16 * 16 && scan_bytes(5, 0, "x") == 0);
-    {
-        bool thrown = false;
-        try { (void)scan_bytes(TOP / 16 + 1, 16, "x"); } catch (const std::exception &) { thrown = true; }
-        EXPECT(thrown);
-    }
+    EXPECT(checked_bytes(0, 16, "x") == 0 && checked_bytes(TOP / 16, 16, "x") == TOP / 16 * 16 && checked_bytes(5, 0, "x") == 0);
+    EXPECT(throws([&] { (void)checked_bytes(TOP / 16 + 1, 16, "x"); }));
     // a single NULL output in every position is accepted, a single non-NULL one too
     for (int k = 0; k < 6; ++k) {
         lg_scan_out one = none, but = all;

@@ -2,37 +2,21 @@
 // sizes with their overflow checks, the light count's refusal, the NULL and alignment rules of lg_scatter_out, the host form's staging) in
 // a stand-alone program, meant to be built with -fsanitize=address,undefined and run on the CPU (tests/test_scatter_host_sanitized.py
 // does).  The counts go up to 2^64 - 1: an overflow in forming a size is a UBSan report or a wrong value here, not a short buffer on a
-// card.  The launch is stubbed out: a "kernel" that fills the staged planes with values that name their element; every caller's array is a
+// card.  The launch is stubbed out: a "kernel" that fills the staged planes with bytes that name their place (host_check.h, staged_round); every caller's array is a
 // heap block of exactly its size, so a copy past an end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/scatter_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/scatter_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static const double D[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
 
 static bool refused(const void *accel, const double *rays, size_t n, const lg_scatter_out *out, size_t lights = 1) {
-    try {
-        check_scatter(accel, rays, n, out, lights);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_scatter(accel, rays, n, out, lights); });
 }
 static bool misaligned(const void *rays, const lg_scatter_out &out) {
-    try {
-        check_scatter_alignment((const double *)rays, out);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_scatter_alignment((const double *)rays, out); });
 }
 // lg_scatter_out with the planes of a 7-bit mask named from `all`, in the struct's order
 static lg_scatter_out subset(const lg_scatter_out &all, unsigned planes) {
@@ -41,61 +25,20 @@ static lg_scatter_out subset(const lg_scatter_out &all, unsigned planes) {
                           planes & 32u ? all.refract : nullptr,       planes & 64u ? all.refract_weight : nullptr};
 }
 
-// one host-form call without a device: check, stage, "launch", place; then every element of every output is looked at
+// one host-form call without a device: check, then stage, "launch" and place (staged_round); every byte of every output is looked at
 static void run(size_t n, unsigned planes) {
-    std::unique_ptr<lg_hit[]> hits(planes & 1u ? new lg_hit[n] : nullptr);
-    std::unique_ptr<double[]> direct(planes & 2u ? new double[3 * n] : nullptr), reflect(planes & 8u ? new double[6 * n] : nullptr),
-        reflect_weight(planes & 16u ? new double[3 * n] : nullptr), refract(planes & 32u ? new double[6 * n] : nullptr),
-        refract_weight(planes & 64u ? new double[5 * n] : nullptr);
-    std::unique_ptr<uint32_t[]> flags(planes & 4u ? new uint32_t[n] : nullptr);
-    const lg_scatter_out out{hits.get(), direct.get(), flags.get(), reflect.get(), reflect_weight.get(), refract.get(), refract_weight.get()};
+    const lg_scatter_out all{(lg_hit *)ASKED, (double *)ASKED, (uint32_t *)ASKED, (double *)ASKED, (double *)ASKED, (double *)ASKED, (double *)ASKED};
+    lg_scatter_out out = subset(all, planes);
     int accel = 0; // (any non-NULL handle: the checks do not look behind it)
     EXPECT(!refused(&accel, D, n, &out));
-    ScatterStaging st(out, n);
-    EXPECT(st.hits.size() == (out.hits ? n : 0) && st.direct.size() == (out.direct ? 3 * n : 0) && st.flags.size() == (out.flags ? n : 0) &&
-           st.reflect.size() == (out.reflect ? 6 * n : 0) && st.reflect_weight.size() == (out.reflect_weight ? 3 * n : 0) &&
-           st.refract.size() == (out.refract ? 6 * n : 0) && st.refract_weight.size() == (out.refract_weight ? 5 * n : 0));
     // what the host form allocates on the device and copies back: the table's counts in the plane's own elements
-    size_t staged_bytes = 0, want_bytes = 0;
-    scatter_planes(out, n, [&](auto *p, auto plane, size_t elems, size_t, const char *) { if (p) { staged_bytes += (st.*plane).size() * sizeof *p; want_bytes += elems * sizeof *p; } });
-    EXPECT(staged_bytes == want_bytes);
-    EXPECT(want_bytes == n * ((out.hits ? 96 : 0) + (out.direct ? 24 : 0) + (out.flags ? 4 : 0) + (out.reflect ? 48 : 0) + (out.reflect_weight ? 24 : 0) +
-                              (out.refract ? 48 : 0) + (out.refract_weight ? 40 : 0)));
+    const StagedRound r = staged_round([&](auto &&f) { scatter_planes(out, n, f); });
+    EXPECT(r.plane_bytes == (std::vector<size_t>{planes & 1u ? 96 * n : 0, planes & 2u ? 8 * 3 * n : 0, planes & 4u ? 4 * n : 0, planes & 8u ? 8 * 6 * n : 0, planes & 16u ? 8 * 3 * n : 0,
+                                                 planes & 32u ? 8 * 6 * n : 0, planes & 64u ? 8 * 5 * n : 0}));
+    const size_t want_bytes = n * ((planes & 1u ? 96 : 0) + (planes & 2u ? 24 : 0) + (planes & 4u ? 4 : 0) + (planes & 8u ? 48 : 0) + (planes & 16u ? 24 : 0) + (planes & 32u ? 48 : 0) +
+                                   (planes & 64u ? 40 : 0));
+    EXPECT(r.bytes == want_bytes);
     if (planes == 127u) EXPECT(want_bytes == n * SCATTER_ROW_BYTES);
-    for (size_t i = 0; i < n; ++i) { // the stubbed launch
-        if (out.hits) {
-            lg_hit h;
-            std::memset(&h, 0, sizeof h);
-            h.t = (double)i + 0.25; h.prim = (uint32_t)i; h.material = -(int32_t)i;
-            st.hits[i] = h;
-        }
-        if (out.flags) st.flags[i] = (uint32_t)(i + 7);
-        for (size_t c = 0; c < 3; ++c) {
-            if (out.direct) st.direct[3 * i + c] = (double)(3 * i + c) + 0.75;
-            if (out.reflect_weight) st.reflect_weight[3 * i + c] = (double)(3 * i + c) + 0.125;
-        }
-        for (size_t c = 0; c < 6; ++c) {
-            if (out.reflect) st.reflect[6 * i + c] = (double)(6 * i + c) + 0.375;
-            if (out.refract) st.refract[6 * i + c] = (double)(6 * i + c) + 0.625;
-        }
-        for (size_t c = 0; c < 5; ++c)
-            if (out.refract_weight) st.refract_weight[5 * i + c] = (double)(5 * i + c) + 0.5;
-    }
-    place_scatter(out, st);
-    for (size_t i = 0; i < n; ++i) {
-        if (hits) EXPECT(hits[i].t == (double)i + 0.25 && hits[i].prim == (uint32_t)i && hits[i].material == -(int32_t)i);
-        if (flags) EXPECT(flags[i] == (uint32_t)(i + 7));
-        for (size_t c = 0; c < 3; ++c) {
-            if (direct) EXPECT(direct[3 * i + c] == (double)(3 * i + c) + 0.75);
-            if (reflect_weight) EXPECT(reflect_weight[3 * i + c] == (double)(3 * i + c) + 0.125);
-        }
-        for (size_t c = 0; c < 6; ++c) {
-            if (reflect) EXPECT(reflect[6 * i + c] == (double)(6 * i + c) + 0.375);
-            if (refract) EXPECT(refract[6 * i + c] == (double)(6 * i + c) + 0.625);
-        }
-        for (size_t c = 0; c < 5; ++c)
-            if (refract_weight) EXPECT(refract_weight[5 * i + c] == (double)(5 * i + c) + 0.5);
-    }
 }
 
 int main() {
@@ -107,7 +50,7 @@ int main() {
     const lg_scatter_out all{h, d, u, d, d, d, d}, none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t TOP = ~(size_t)0, EDGE = TOP / 96; // the most lg_hit records an address space holds
     static_assert(sizeof(size_t) == 8, "the limits below are written for a 64-bit size_t");
-    static_assert(SCATTER_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
+    static_assert(QUERY_MAX_RAYS == 0xFFFFFFFFull * 64ull, "64-ray tiles counted in 32 bits");
     static_assert(SCATTER_ROW_BYTES == 284, "96 + 24 + 4 + 48 + 24 + 48 + 40");
     // ---- check_scatter: every error of the contract that needs no device
     EXPECT(!refused(&accel, D, 3, &all));
@@ -116,21 +59,17 @@ int main() {
     EXPECT(refused(&accel, D, 3, nullptr));
     EXPECT(refused(&accel, D, 3, &none));
     // the ray limit: (2^32 - 1) * 64 and one above; it is below what an address space holds of lg_hit records, so no size wraps
-    EXPECT(!refused(&accel, D, SCATTER_MAX_RAYS, &all));
-    EXPECT(refused(&accel, D, SCATTER_MAX_RAYS + 1, &all) && refused(&accel, D, EDGE, &all) && refused(&accel, D, EDGE + 1, &all) && refused(&accel, D, TOP, &all));
-    EXPECT(SCATTER_MAX_RAYS < EDGE);
+    EXPECT(!refused(&accel, D, QUERY_MAX_RAYS, &all));
+    EXPECT(refused(&accel, D, QUERY_MAX_RAYS + 1, &all) && refused(&accel, D, EDGE, &all) && refused(&accel, D, EDGE + 1, &all) && refused(&accel, D, TOP, &all));
+    EXPECT(QUERY_MAX_RAYS < EDGE);
     {
         size_t most = 0; // no count of the plane table wraps at the limit: the widest in elements (reflect, 6 a ray) and in bytes (hits)
-        scatter_planes(all, (size_t)SCATTER_MAX_RAYS, [&](auto *p, auto, size_t elems, size_t, const char *) { EXPECT(elems <= TOP / sizeof *p); most = elems > most ? elems : most; });
-        EXPECT(most == 6 * (size_t)SCATTER_MAX_RAYS);
+        scatter_planes(all, (size_t)QUERY_MAX_RAYS, [&](auto *p, size_t elems, size_t, const char *) { EXPECT(elems <= TOP / sizeof *p); most = elems > most ? elems : most; });
+        EXPECT(most == 6 * (size_t)QUERY_MAX_RAYS);
     }
     // the sizes
-    EXPECT(scatter_bytes(0, 96, "x") == 0 && scatter_bytes(EDGE, 96, "x") == EDGE * 96 && scatter_bytes(5, 0, "x") == 0);
-    {
-        bool thrown = false;
-        try { (void)scatter_bytes(EDGE + 1, 96, "x"); } catch (const std::exception &) { thrown = true; }
-        EXPECT(thrown);
-    }
+    EXPECT(checked_bytes(0, 96, "x") == 0 && checked_bytes(EDGE, 96, "x") == EDGE * 96 && checked_bytes(5, 0, "x") == 0);
+    EXPECT(throws([&] { (void)checked_bytes(EDGE + 1, 96, "x"); }));
     // the lights: 0 .. 32 are served, 33 and more refused (lg_radiance's refusal); there is no depth to refuse
     for (size_t lights : {(size_t)0, (size_t)1, (size_t)32}) EXPECT(!refused(&accel, D, 3, &all, lights));
     for (size_t lights : {(size_t)33, (size_t)64, TOP}) EXPECT(refused(&accel, D, 3, &all, lights));

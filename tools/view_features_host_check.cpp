@@ -1,20 +1,14 @@
 // tools/view_features_host_check.cpp -- the device-free host code of lg_capture_view_features* (lasgun_amd/csrc/view_features_host.h: the
 // plane table, every NULL rule, the film's limits, the pixel-tile count with its 32-bit limit, each plane's byte size, the views' own rules
-// and the uniform-samples rule, the alignment rule) in a stand-alone program, meant to be built with -fsanitize=address,undefined and run
+// and the uniform-samples rule, the alignment rule, the host form's staging through planes_host.h's HostStaging) in a stand-alone program, meant to be built with -fsanitize=address,undefined and run
 // on the CPU (tests/test_view_features_host_sanitized.py does).  The counts go up to 2^64 - 1: an overflow in forming a tile count or a
 // size is a UBSan report or a wrong value here, not a short buffer on a card.  Every table is a heap block of exactly its size, so a read
 // past a table's end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/view_features_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/view_features_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 static lg_view view(uint32_t root, uint32_t reserved = 0) {
     lg_view v;
@@ -39,21 +33,11 @@ static lg_view_features planes(int mask, size_t shift = 0) {
 }
 static const double *const TABLE = reinterpret_cast<const double *>(mem);
 static std::string refusal(const void *accel, const lg_view *views, size_t n, uint32_t w, uint32_t h, const lg_view_features *out, const double *table = TABLE) {
-    try {
-        (void)check_view_features(accel, views, n, w, h, out, table);
-    } catch (const std::exception &e) {
-        return e.what();
-    }
-    return "";
+    return thrown([&] { (void)check_view_features(accel, views, n, w, h, out, table); });
 }
 static bool has(const std::string &s, const char *word) { return s.find(word) != std::string::npos; }
 static std::string misaligned(const lg_view_features &out, const double *table = TABLE) {
-    try {
-        check_view_features_alignment(out, table);
-    } catch (const std::exception &e) {
-        return e.what();
-    }
-    return "";
+    return thrown([&] { check_view_features_alignment(out, table); });
 }
 
 int main() {
@@ -103,6 +87,15 @@ int main() {
         const ViewShape s = check_view_features(&accel, two.get(), 2, 45, 27, &all, TABLE);
         EXPECT(s.samples_root == 256 && s.tiles_x == 6 && s.tiles_per_view == 24 && s.pixel_tiles == 48 && s.pixels == 2 * 45 * 27);
         two[0] = view(1); two[1] = view(1);
+        // the host form's staging (query.cpp: the table's elements a pixel times the call's pixels), for every subset of the planes
+        for (int mask = 1; mask <= ALL; ++mask) {
+            lg_view_features out = planes(mask);
+            const StagedRound r = staged_round([&](auto &&f) {
+                view_feature_planes(out, [&](auto *&p, size_t per_pixel, size_t align, const char *what) { f(p, s.pixels * per_pixel, align, what); });
+            });
+            EXPECT(r.plane_bytes == (std::vector<size_t>{mask & DEPTH ? 4 * s.pixels : 0, mask & NORMAL ? 12 * s.pixels : 0, mask & ALBEDO ? 12 * s.pixels : 0,
+                                                         mask & COVERAGE ? 4 * s.pixels : 0, mask & ID ? 16 * s.pixels : 0, mask & POINT ? 12 * s.pixels : 0}));
+        }
     }
     // ---- each plane's byte size at SIZE_MAX and one above: n_views * w * h * 4, 12 and 16 (the tile count is out of the way at w = h = 1
     // only below 2^32 views, so the sizes are driven through view_bytes, the function check_view_features calls per plane)

@@ -4,16 +4,10 @@
 // counts go up to 2^64 - 1: an overflow in forming a tile count or a size is a UBSan report or a wrong value here, not a short buffer on a
 // card.  Every table is a heap block of exactly its size, so a read past a table's end is an ASan report.
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/views_host_check.cpp -o check && ./check
-#include <cstdio>
-#include <cstdlib>
-#include <memory>
-
 #include "../lasgun_amd/csrc/views_host.h"
+#include "host_check.h"
 
 using namespace lg;
-
-static int failures = 0;
-#define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } } while (0)
 
 // the work tiles of a call, -1 where they pass 2^32 - 1
 static long long tiles(size_t n_views, uint32_t w, uint32_t h, unsigned long long S) {
@@ -36,20 +30,10 @@ static lg_view view(uint32_t root, uint32_t reserved = 0) {
     return v;
 }
 static std::string refusal(const void *accel, const lg_view *views, size_t n, uint32_t w, uint32_t h, const void *rgba, const void *rgb) {
-    try {
-        (void)check_views(accel, views, n, w, h, rgba, rgb);
-    } catch (const std::exception &e) {
-        return e.what();
-    }
-    return "";
+    return thrown([&] { (void)check_views(accel, views, n, w, h, rgba, rgb); });
 }
 static bool misaligned(const void *rgba, const void *rgb) {
-    try {
-        check_views_alignment(rgba, rgb);
-    } catch (const std::exception &e) {
-        return e.what()[0] != 0;
-    }
-    return false;
+    return throws([&] { check_views_alignment(rgba, rgb); });
 }
 
 int main() {
@@ -108,6 +92,13 @@ int main() {
         const ViewShape s = check_views(&accel, many.get(), K, 45, 27, out, nullptr);
         EXPECT(s.samples_root == 3 && s.tiles_x == 6 && s.tiles_per_view == 24 && s.pixel_tiles == 130 * 24 && s.pixels == K * 45 * 27);
         EXPECT(tiles(K, 45, 27, 9) == 130 * 24 * 9);
+        // the host form's staging (query.cpp: 4 bytes and 3 doubles a pixel), for every subset of the two films
+        for (unsigned films = 1; films < 4; ++films) {
+            uint8_t *rgba = films & 1u ? (uint8_t *)ASKED : nullptr;
+            double *rgb = films & 2u ? (double *)ASKED : nullptr;
+            const StagedRound r = staged_round([&](auto &&f) { f(rgba, s.pixels * 4, 4, "rgba"); f(rgb, s.pixels * 3, 8, "rgb"); });
+            EXPECT(r.plane_bytes == (std::vector<size_t>{films & 1u ? 4 * s.pixels : 0, films & 2u ? 24 * s.pixels : 0}));
+        }
         // lg_view -> DView: the fields as given, ss_distance = 1 / samples_root
         many[7].origin[1] = -0.0; many[7].aux[2] = 1e300; many[7].pixel_separation = 1.0;
         const std::vector<DView> d = to_dviews(many.get(), K);
