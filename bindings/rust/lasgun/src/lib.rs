@@ -275,6 +275,15 @@ pub struct Attributes<'a> {
     pub frame: Option<&'a mut [[f64; 6]]>,
     pub dp: Option<&'a mut [[f64; 6]]>,
 }
+pub use sys::lg_closest_out as ClosestOut;
+/// The planes `Accel::closest_points` fills, one row per point: `None` = not asked for; not all three.  (Like the rest of this crate:
+/// uncompiled here -- no Rust toolchain --, held to the C header textually by tests/test_rust_bindings.py and tests/test_closest_points_abi.py.)
+#[derive(Default)]
+pub struct Closest<'a> {
+    pub distance: Option<&'a mut [f64]>,
+    pub point: Option<&'a mut [[f64; 3]]>,
+    pub id: Option<&'a mut [[u32; 4]]>,
+}
 pub use sys::lg_light as Light;
 pub use sys::lg_light_set as LightSet;
 pub use sys::lg_lit_out as LitOut;
@@ -570,6 +579,29 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `scatter` states (the library checks what HIP can tell it).
     pub unsafe fn scatter_device(&self, dev_rays: *const f64, n: usize, dev_out: &sys::lg_scatter_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_scatter_device(self.ptr, dev_rays, n, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// Closest points (`lg_closest_points`): for each point (world space) the nearest surface point of the scene.  Row i of every plane
+    /// given belongs to point i: distance (+inf where no surface lies within `radius`; `f64::INFINITY` = no limit), point = the closest
+    /// point in world space (+0.0 for a miss), id = kind, prim, instance, material as in `lg_hit` (0, !0, !0, -1 for a miss).  The header's
+    /// arithmetic over every primitive, bit for bit; a scene with a sphere under a non-uniform scale is refused (`sys::lg_scene_closest_gate` says which instance).
+    pub fn closest_points(&self, points: &[[f64; 3]], radius: f64, out: Closest) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_closest_out>() == 24);
+        let n = points.len();
+        assert!(out.distance.as_ref().map_or(true, |p| p.len() == n) && out.point.as_ref().map_or(true, |p| p.len() == n)
+                && out.id.as_ref().map_or(true, |p| p.len() == n), "closest_points: every plane has points.len() rows");
+        let o = sys::lg_closest_out {
+            distance: out.distance.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            point: out.point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            id: out.id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+        };
+        if unsafe { sys::lg_closest_points(self.ptr, points.as_ptr() as *const f64, n, radius, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `closest_points` for points in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `closest_points` states (the library checks what HIP can tell it).
+    pub unsafe fn closest_points_device(&self, dev_points: *const f64, n: usize, radius: f64, dev_out: &sys::lg_closest_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_closest_points_device(self.ptr, dev_points, n, radius, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     fn attr_out(n: usize, out: Attributes, what: &str) -> sys::lg_attr_out {
         const _: () = assert!(std::mem::size_of::<sys::lg_attr_out>() == 56);

@@ -12,6 +12,7 @@
 // Rust panics and `Result`s become exceptions (lasgun::Error, lasgun::ObjError).
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -377,6 +378,27 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void hit_attributes_device(const double *dev_rays, size_t n, const lg_attr_out &dev_out, void *hip_stream, const lg_hit *dev_records = nullptr) const {
         if (dev_records ? lg_hit_attributes_of_device(h_, dev_rays, dev_records, n, &dev_out, hip_stream) : lg_hit_attributes_device(h_, dev_rays, n, &dev_out, hip_stream))
             throw Error(lg_last_error());
+    }
+    // closest points (lg_closest_points): for each point (world space) the nearest surface point of the scene -- row i of every plane asked
+    // for (a null member is not asked for; not all three) belongs to point i: distance (+INF where no surface lies within `radius`), point =
+    // the closest point in world space (+0.0 for a miss), id = kind, prim, instance, material as in lg_hit (0, ~0, ~0, -1 for a miss).  The
+    // header's arithmetic over every primitive, bit for bit; a scene with a sphere under a non-uniform scale is refused (lg_scene_closest_gate)
+    struct Closest {
+        std::vector<double> *distance = nullptr;                    // [points]
+        std::vector<std::array<double, 3>> *point = nullptr;
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;
+    };
+    void closest_points(const std::vector<std::array<double, 3>> &points, const Closest &out, double radius = INFINITY) const {
+        static_assert(sizeof(lg_closest_out) == 24, "lg_closest_out: three pointers");
+        const size_t n = points.size();
+        lg_closest_out o{};
+        if (out.distance) { out.distance->assign(n, INFINITY); o.distance = out.distance->data(); }
+        if (out.point) { out.point->assign(n, {0.0, 0.0, 0.0}); o.point = n ? (*out.point)[0].data() : nullptr; }
+        if (out.id) { out.id->assign(n, {0u, ~0u, ~0u, ~0u}); o.id = n ? (*out.id)[0].data() : nullptr; }
+        if (lg_closest_points(h_, points.empty() ? nullptr : points[0].data(), n, radius, &o)) throw Error(lg_last_error());
+    }
+    void closest_points_device(const double *dev_points, size_t n, double radius, const lg_closest_out &dev_out, void *hip_stream) const {
+        if (lg_closest_points_device(h_, dev_points, n, radius, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
     // lit scatter (lg_scatter_lit): scatter() under lights that come with the call -- `lights` shared by every ray (per_ray false: K records)
     // or a table per ray (per_ray true: rays.size() * K records, ray i's at i * K), `ambient` in the scene's ambient colour's place; the

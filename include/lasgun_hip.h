@@ -1235,6 +1235,69 @@ int lg_hit_attributes_device(const lg_accel *, const double *dev_rays, size_t n,
 int lg_hit_attributes_of(const lg_accel *, const double *rays, const lg_hit *hits, size_t n, const lg_attr_out *out);   /* host arrays; synchronous */
 int lg_hit_attributes_of_device(const lg_accel *, const double *dev_rays, const lg_hit *dev_hits, size_t n, const lg_attr_out *dev_out,
                                 void *hip_stream);
+
+/* Closest points: for each of n POINTS, the nearest surface point of the scene, its distance and the primitive it lies on -- the query
+ * that starts from a point and not from a ray (collision and clearance probes, lidar and robotics pipelines, probe placement; with
+ * lg_hit_layers' parity, a signed distance).  An EXTRA; no counterpart in the reference: the contract is the arithmetic below, and the
+ * answer is that arithmetic over ALL primitives of the scene, bit for bit -- it depends on neither the trees nor the visit order, and
+ * the accel's traversal mode (reference, pruned, LDS-resident scene, fast mode) and lg_accel_set_query_order play no part: the same
+ * bytes in every mode.  `points` is n x 3 f64, world space.  All f64, nothing fused, dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ * World position: W_A(x) takes a point of accel A's local space to world space: A's own transform applied as the library applies a
+ *   transform to a point (((c0*x + c1*y) + c2*z) + c3*1.0 per component), then its parent's, and so on up to and including the root's.
+ * Triangle (kind 3): the triangle the ray walk sees -- the first three vertices of a face, f32 positions widened -- with its vertices
+ *   a, b, c taken through W_A, A the mesh instance.  Closest point x of q (Ericson, Real-Time Collision Detection, 5.1.5), in this order:
+ *   1. ab=b-a, ac=c-a, ap=q-a; d1=dot(ab,ap), d2=dot(ac,ap).  d1<=0 && d2<=0: x = a.
+ *   2. bp=q-b; d3=dot(ab,bp), d4=dot(ac,bp).  d3>=0 && d4<=d3: x = b.
+ *   3. vc=d1*d4-d3*d2.  vc<=0 && d1>=0 && d3<=0: x = a+ab*(d1/(d1-d3)).
+ *   4. cp=q-c; d5=dot(ab,cp), d6=dot(ac,cp).  d6>=0 && d5<=d6: x = c.
+ *   5. vb=d5*d2-d1*d6.  vb<=0 && d2>=0 && d6<=0: x = a+ac*(d2/(d2-d6)).
+ *   6. va=d3*d6-d5*d4.  va<=0 && (d4-d3)>=0 && (d5-d6)>=0: x = b+(c-b)*((d4-d3)/((d4-d3)+(d5-d6))).
+ *   7. otherwise den=1/((va+vb)+vc), x = (a+ab*(vb*den))+ac*(vc*den).
+ *   The candidate's squared distance is dot(q-x, q-x).
+ * Box (kind 2): corner k (k = 0 .. 7) has the box's max on axis x / y / z where bit 0 / 1 / 2 of k is set and its min otherwise; the eight
+ *   corners go through W_A.  The surface is twelve triangles of corners, in this order: -x (0,2,6) (0,6,4); +x (1,3,7) (1,7,5);
+ *   -y (0,1,5) (0,5,4); +y (2,3,7) (2,7,6); -z (0,1,3) (0,3,2); +z (4,5,7) (4,7,6) -- each face cut by the diagonal from its lowest corner
+ *   to its highest.  The lowest squared distance of the twelve wins, the first triangle a tie.  Under a general affine instance the box
+ *   is a parallelepiped and this is exact for it.  A point inside a box gets the distance to its surface.
+ * Sphere (kind 1), centre c and radius r: cw = W_A(c), pw = W_A(c + (r,0,0)), rw = sqrt(dot(pw-cw, pw-cw)); v = q-cw, l = sqrt(dot(v,v));
+ *   d = fabs(l-rw), squared distance d*d; x = cw + v*(rw/l), and x = pw where l == 0.  A sphere is a sphere in world space only under a
+ *   similarity: lg_scene_closest_gate below.  A point inside a sphere gets the distance to its surface.
+ * Winner: a candidate is admissible iff its squared distance is <= radius*radius and < +INF (a NaN never wins).  The smallest squared
+ *   distance among the admissible candidates wins; an exact tie goes to the smallest (instance, kind, prim) in lg_hit's numbering.
+ *   distance = sqrt of the winner's squared distance, point = its x, id = kind, prim, instance, material -- lg_hit's last 16 bytes,
+ *   material what lg_intersect reports for a hit on that primitive.  Where nothing is admissible, and for a point with a non-finite
+ *   coordinate: distance = +INF, point = +0.0, id = 0, ~0, ~0, -1.
+ * Every element of every plane asked for is written, whatever the buffers held, by exactly one lane: no atomics, no pre-fill.  Lights
+ * and materials' parameters play no part; a scene of more than 32 lights is accepted.
+ * lg_scene_closest_gate (no device is needed): -1 where every accel that holds a sphere has a cumulative linear part L (the 3 x 3 part
+ *   of the composed transforms root .. accel) with L^T L within 2^-40, relative to its largest entry, of a multiple of the identity;
+ *   otherwise the first accel (in lg_hit's instance numbering) that holds a sphere and fails it: lg_closest_points* then fail, naming
+ *   that instance.  Meshes and boxes pass under any invertible affine chain.  -2 on an error.  shrink (may be NULL): shrink[a], for
+ *   a < min(cap, instances), a proven lower bound of the smallest singular value of accel a's local -> world linear part (0 where
+ *   nothing is proven: a singular or badly conditioned chain), which the kernel's pruning test uses.
+ * Limits and errors: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors (non-zero,
+ * lg_last_error, nothing launched, no output touched), for n > 0: a NULL accel, points or out; all three planes NULL; a radius that is
+ * NaN or negative (+INF: no limit); n > (2^32 - 1) * 64, or a plane's byte size that does not fit size_t; a scene the gate refuses; a
+ * scene whose trees are too deep for the kernel's per-lane stack (lg_scene_closest_depth; refused, never truncated); in the device form also a pointer that is
+ * not device memory of the accel's device or is misaligned (points, distance and point 8 bytes; id 16), or a buffer that ends beyond
+ * its allocation.  The device form only enqueues on hip_stream (dev_out is a HOST struct of device pointers; one stream at a time per
+ * accel), except that an accel's first call builds and uploads the query's own tables after a synchronise.  The host form is
+ * synchronous: the points go up, the planes come back into staging and are copied out at the end, so an error on the way leaves the
+ * caller's arrays as they were.
+ * Out of scope: per-point radii, the k nearest, a normal at the closest point, the sorted order, a multi-device split. */
+typedef struct lg_closest_out {
+    double   *distance;        /* [n]     sqrt(d2) of the winner, +INF where nothing is admissible */
+    double   *point;           /* [n][3]  the winner's closest point, world space; +0.0 for a miss */
+    uint32_t *id;              /* [n][4]  kind, prim, instance, material: lg_hit's last 16 bytes; miss: 0, ~0, ~0, -1 */
+} lg_closest_out;              /* 24 bytes; each pointer may be NULL, all NULL is an error */
+int lg_closest_points(const lg_accel *, const double *points, size_t n, double radius, const lg_closest_out *out);   /* host arrays; synchronous */
+int lg_closest_points_device(const lg_accel *, const double *dev_points, size_t n, double radius, const lg_closest_out *dev_out, void *hip_stream);
+int lg_scene_closest_gate(const lg_scene *, double *shrink, int cap);
+/* The entries of the kernel's per-lane stack that lg_closest_points* need for this scene, without a device: up to 32 fit the default 64 KiB
+ * of dynamic LDS, up to LG_CLOSEST_MAX_DEPTH the 128 KiB the call raises the kernel's limit to; a scene that needs more is refused by the
+ * call.  -1 on an error. */
+#define LG_CLOSEST_MAX_DEPTH 64
+int lg_scene_closest_depth(const lg_scene *);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD, CLOSEST_SIGNATURES, CClosestOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -111,6 +111,7 @@ _EXTRA = {
     **SCATTER_SIGNATURES,
     **LIT_SIGNATURES,
     **ATTRIBUTES_SIGNATURES,
+    **CLOSEST_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -158,6 +159,9 @@ assert _C.sizeof(CAttrOut) == 56, "lg_attr_out is 56 bytes"
 ATTR_PLANES = ("hits", "flags", "bary", "uv", "local", "frame", "dp")  # lg_attr_out's members, in its order
 _ATTR_SHAPE = {"hits": ((), HIT_DTYPE), "flags": ((), _np.uint32), "bary": ((3,), _np.float64), "uv": ((2,), _np.float64), "local": ((3,), _np.float64),
                "frame": ((6,), _np.float64), "dp": ((6,), _np.float64)}  # (trailing shape, dtype) per ray
+assert _C.sizeof(CClosestOut) == 24, "lg_closest_out is 24 bytes"
+CLOSEST_PLANES = ("distance", "point", "id")  # lg_closest_out's members, in its order
+_CLOSEST_SHAPE = {"distance": ((), _np.float64), "point": ((3,), _np.float64), "id": ((4,), _np.uint32)}  # (trailing shape, dtype) per point
 LIGHT_DTYPE = _np.dtype([("position", _np.float64, (3,)), ("intensity", _np.float64, (3,)), ("falloff", _np.float64, (3,))])  # lg_light
 assert LIGHT_DTYPE.itemsize == 72
 
@@ -1040,6 +1044,92 @@ class HipApi(Api):
             raise LasgunError(self.last_error())
         return out
 
+    # ---- closest points (include/lasgun_hip.h, lg_closest_points*): the nearest surface point of the scene for each of a batch of points
+    def closest_points(self, accel, points, radius=float("inf"), planes=None, into=None):
+        """The nearest surface point of the scene for every point of an (n, 3) float64 array (world space): a dict of the planes asked
+        for (any of CLOSEST_PLANES; None: all three), each indexed by the point -- float64 (n,) distance, +inf where no surface lies
+        within `radius`; float64 (n, 3) point, the closest point in world space (+0.0 for a miss); uint32 (n, 4) id = kind, prim,
+        instance, material as in lg_hit (0, ~0, ~0, -1 for a miss).  The answer is the header's arithmetic over every primitive of the
+        scene, bit for bit, in every traversal mode; exact ties go to the smallest (instance, kind, prim).  A point inside a sphere or
+        a box gets the distance to its surface; a point with a non-finite coordinate the miss record.  A scene that holds a sphere
+        under a non-uniform scale is refused (scene_closest_gate).  `into`: a dict of C-contiguous arrays of those shapes, written in
+        place.  Also `accel.closest_points(points, radius=..., planes=...)`."""
+        q = _np.ascontiguousarray(points, dtype=_np.float64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("points: an (n, 3) float64 array")
+        n = q.shape[0]
+        planes = CLOSEST_PLANES if planes is None else tuple(planes)
+        if any(p not in CLOSEST_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (CLOSEST_PLANES,))
+        out = {}
+        for p in planes:
+            tail, dt = _CLOSEST_SHAPE[p]
+            shape = (n,) + tail
+            if into is not None and p not in into:
+                raise ValueError("into: no array for the plane %r that is asked for" % (p,))
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CClosestOut(*[data(out.get(p)) for p in CLOSEST_PLANES])
+        if self.call("closest_points", accel.h, data(q), n, float(radius), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def closest_points_device(self, accel, n, points_ptr, radius=float("inf"), distance_ptr=None, point_ptr=None, id_ptr=None, stream=None):
+        """Enqueue closest_points of n points (device memory, 3 doubles each) into device memory, n rows each: distance_ptr (f64),
+        point_ptr (3 f64), id_ptr (4 u32, 16-byte aligned); each may be None, not all.  The pointers are integers (torch:
+        tensor.data_ptr()) or objects with a data_ptr().  An accel's first call also builds the query's own tables."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        f = CClosestOut(*[ptr(p) for p in (distance_ptr, point_ptr, id_ptr)])
+        pts = ptr(points_ptr)
+        if self.call("closest_points_device", accel.h, _C.c_void_p(pts) if pts is not None else None, int(n), float(radius), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def scene_closest_gate(self, scene):
+        """closest_points' gate for a scene, without a device: (verdict, shrink) -- verdict -1 where every accel that holds a sphere sits
+        under a similarity (uniform scale, rotations, translations), otherwise the first instance that does not, which closest_points
+        names when it refuses the scene; shrink: float64 (instances,), one entry for EVERY instance of the scene: a proven lower bound of
+        the smallest singular value of each accel's local -> world linear part, 0 where nothing is proven (include/lasgun_hip.h,
+        lg_scene_closest_gate)."""
+        cap = 4096
+        while True:  # the C entry point writes min(cap, instances) entries and does not say how many there are: grow until one stays unwritten
+            shrink = _np.full(cap, _np.nan, dtype=_np.float64)
+            v = self.call("scene_closest_gate", scene.h, shrink.ctypes.data_as(_C.POINTER(_C.c_double)), cap)
+            if v < -1:
+                raise LasgunError(self.last_error())
+            if _np.isnan(shrink[-1]):
+                return int(v), shrink[~_np.isnan(shrink)].copy()
+            cap *= 8
+
+    CLOSEST_MAX_DEPTH = 64  # LG_CLOSEST_MAX_DEPTH
+
+    def scene_closest_depth(self, scene):
+        """The entries of the kernel's per-lane stack that closest_points needs for a scene, without a device: up to 32 fit the default
+        64 KiB of dynamic LDS, up to CLOSEST_MAX_DEPTH the 128 KiB the call raises the kernel's limit to; a scene that needs more is
+        refused (include/lasgun_hip.h, lg_scene_closest_depth)."""
+        v = self.call("scene_closest_depth", scene.h)
+        if v < 0:
+            raise LasgunError(self.last_error())
+        return int(v)
+
+    def signed_distance(self, accel, points, max_layers=32):
+        """A CONVENTION of this wrapper over closest_points and hit_layers, for scenes made of CLOSED solids only (spheres, boxes,
+        watertight meshes that do not intersect one another's surfaces at the point): closest_points' distance, negated where the ray
+        from the point along +x crosses an odd number of surfaces (hit_layers' count), and NaN where that count reached max_layers (the
+        parity is then unknown) or the point is not finite.  An open mesh, a point exactly on a surface or a +x ray that grazes an edge
+        gives a parity that means nothing; the magnitude is closest_points' whatever the sign."""
+        q = _np.ascontiguousarray(points, dtype=_np.float64)
+        d = self.closest_points(accel, q, planes=("distance",))["distance"]
+        rays = _np.concatenate([q, _np.broadcast_to(_np.array([1.0, 0.0, 0.0]), q.shape)], axis=1)
+        finite = _np.isfinite(q).all(axis=1)
+        rays[~finite, :3] = 0.0
+        count = self.hit_layers(accel, rays, int(max_layers), ("count",))["count"] if len(q) else _np.zeros(0, dtype=_np.uint32)
+        out = _np.where(count % 2 == 1, -d, d)
+        out[(count >= int(max_layers)) | ~finite] = _np.nan
+        return out
+
     def hit_attributes_device(self, accel, n, rays_ptr, hits_ptr=None, flags_ptr=None, bary_ptr=None, uv_ptr=None, local_ptr=None, frame_ptr=None, dp_ptr=None,
                               stream=None):
         """Enqueue hit_attributes of n rays (device memory, 6 doubles each) into device memory, n rows each: hits_ptr (lg_hit, 16-byte
@@ -1734,6 +1824,8 @@ api.Accel.hit_layers = lambda self, rays, max_layers, planes=("along", "id", "co
 api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self, rays, groups)  # accel.radiance_groups(rays, per_light_groups(n))
 api.Accel.scatter = lambda self, rays, planes=SCATTER_PLANES: api.scatter(self, rays, planes)  # accel.scatter(rays)
 api.Accel.hit_attributes = lambda self, rays, planes=ATTR_PLANES: api.hit_attributes(self, rays, planes)  # accel.hit_attributes(rays, ("uv", "bary"))
+api.Accel.closest_points = lambda self, points, radius=float("inf"), planes=None: api.closest_points(self, points, radius, planes)  # accel.closest_points(points, radius=0.5)
+api.Accel.signed_distance = lambda self, points, max_layers=32: api.signed_distance(self, points, max_layers)  # accel.signed_distance(points): closed solids only
 api.Accel.scatter_lit = lambda self, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES: api.scatter_lit(self, rays, lights, ambient, planes)  # accel.scatter_lit(rays, [la.Light(p, i)])
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):
     """The wrapper's one convention of a rule table for trace_paths: glass refracts with its eta, mirror and metal reflect, the rest `default`."""

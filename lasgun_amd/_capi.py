@@ -204,6 +204,15 @@ ATTRIBUTES_SIGNATURES = {
 }
 ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD = 1, 2, 4  # LG_ATTR_*: lg_attr_out::flags
 
+# Closest points (include/lasgun_hip.h, lg_closest_points / lg_closest_points_device / lg_scene_closest_gate / lg_scene_closest_depth): for each point the nearest
+# surface point of the scene, its distance and the primitive it lies on, as planes indexed by the point; the GPU library's alone.
+CLOSEST_SIGNATURES = {
+    "closest_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]),
+    "closest_points_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p]),
+    "scene_closest_gate": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
+    "scene_closest_depth": (C.c_int, [C.c_void_p]),
+}
+
 # Lit scatter (include/lasgun_hip.h, lg_scatter_lit / lg_scatter_lit_device): surface scatter under lights that come with the call -- the
 # seven planes of lg_scatter, every light's own term and the visibility bits; the GPU library's alone.
 LIT_SIGNATURES = {
@@ -291,6 +300,10 @@ class CScatterOut(C.Structure):  # lg_scatter_out: seven pointers, 56 bytes; NUL
 class CAttrOut(C.Structure):  # lg_attr_out: seven pointers, 56 bytes; NULL = not asked for
     _fields_ = [("hits", C.c_void_p), ("flags", C.c_void_p), ("bary", C.c_void_p), ("uv", C.c_void_p), ("local", C.c_void_p), ("frame", C.c_void_p),
                 ("dp", C.c_void_p)]
+
+
+class CClosestOut(C.Structure):  # lg_closest_out: three pointers, 24 bytes; NULL = not asked for
+    _fields_ = [("distance", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p)]
 
 
 class CLight(C.Structure):  # lg_light: lg_scene_add_point_light's arguments, 72 bytes

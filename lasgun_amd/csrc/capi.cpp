@@ -4,6 +4,7 @@
 #include "choice.h"
 #include "packet_host.h"
 #include "fused_host.h"
+#include "closest_host.h"
 
 // ============================================================================================
 extern "C" {
@@ -795,6 +796,33 @@ int lg_scene_packet_walk_gate(const lg_scene *s) {
         FlatScene f;
         flatten_scene(s->s, f, false, false);
         v = (int)packet_scene_gate(f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.max_stack + 2u);
+    });
+    return rc ? -1 : v;
+}
+// The sphere gate of lg_closest_points* for a scene without a device (closest_host.h, closest_gate over the flattened tables): -1 where every
+// accel that holds a sphere sits under a similarity, otherwise the first one that does not; shrink[a] (may be NULL; at most `cap` written):
+// the proven lower bound of the smallest singular value of accel a's local -> world linear part; -2 on an error.
+int lg_scene_closest_gate(const lg_scene *s, double *shrink, int cap) {
+    int v = -1;
+    int rc = guarded([&] {
+        if (!s) throw Error("scene is NULL");
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        v = closest_gate(ClosestScene{f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.leaf_soup.data(),
+                                      f.leaf_soup.size()}, shrink, cap);
+    });
+    return rc ? -2 : v;
+}
+// The per-lane stack entries lg_closest_points* would need for a scene, without a device (closest_host.h, closest_tables): a scene that needs
+// more than LG_CLOSEST_MAX_DEPTH is refused by the call; -1 on an error.
+int lg_scene_closest_depth(const lg_scene *s) {
+    int v = 0;
+    int rc = guarded([&] {
+        if (!s) throw Error("scene is NULL");
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        v = (int)closest_tables(ClosestScene{f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(), f.leaf_soup.data(),
+                                             f.leaf_soup.size()}).depth;
     });
     return rc ? -1 : v;
 }

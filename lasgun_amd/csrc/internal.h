@@ -135,6 +135,16 @@ hipError_t launch_attr_of(const DParams &P, const double *rays, const void *reco
                           double *uv, double *local, double *frame, double *dp, uint32_t blocks, hipStream_t stream);
 hipError_t attributes_occupancy(const DParams &P, bool fast, uint32_t stack_depth, int *blocks_per_cu);
 hipError_t attributes_set_lds_limit(size_t bytes, bool ldss);
+// k_closest.hip: closest points (lg_closest_points*) -- for each point the nearest surface point of the scene, a 64-point tile per wave and a
+// point per lane, a distance-ordered walk of the reference trees from the global tables with a per-lane stack of stack_depth (node, accel)
+// entries in dynamic LDS; `cl`: the ClosestAccel table (closest_host.h), qmax the largest |q|_inf it prunes for, r2 = radius * radius; only
+// the planes that are not nullptr are written
+hipError_t launch_closest(const DParams &P, const double *points, unsigned long long n, double r2, double qmax, double *distance, double *point, void *id,
+                          const uint32_t *tri_base, const void *cl, uint32_t *tile_counter, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
+hipError_t closest_occupancy(uint32_t stack_depth, int *blocks_per_cu);
+hipError_t closest_set_lds_limit(size_t bytes);
+size_t closest_stack_bytes(uint32_t stack_depth);
+struct ClosestTables; // closest_host.h
 // k_paths.hip: ray paths (lg_trace_paths*) -- layers_kernel's loop with a direction update: at each hit the rule of its material (`rules`:
 // n_rules lg_path_rule records in DEVICE memory) ends the path or forms the next segment in registers (bounce.h); only the planes that are
 // not nullptr are written, vertex-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order
@@ -463,6 +473,10 @@ struct lg_accel {
     DevBuf<DLight> lights;
     DevBuf<uint32_t> accel_tri_base; // ray queries only (k_query.hip): per accel, its mesh's first triangle (FlatScene::accel_tri_base)
     DevBuf<uint32_t> attr_counts;    // lg_hit_attributes_of* only (k_attributes.hip): what a record may name (attributes_host.h, attr_counts_build)
+    // lg_closest_points* only (k_closest.hip): the gate's verdict, the stack depth and the pruning test's constants per accel (closest_host.h),
+    // made from `flat` and uploaded at the accel's first such call -- no part of the tables lg_accel_from builds or lg_accel_info counts
+    mutable std::shared_ptr<ClosestTables> closest;
+    mutable DevBuf<uint8_t> closest_cl;
     // launch resources (mutable: a `const lg_accel*` render call still enqueues work).  Everything a launch
     // scribbles on lives in a per-STREAM context, so launches of one accel on different streams (frame k+1's
     // primary pass filling the tail of frame k's shadow pass) do not share tile counters or per-pixel state.

@@ -1,6 +1,6 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_closest_points*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_closest.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
 // alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
@@ -8,13 +8,14 @@
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below), whose host-memory half is
 // planes_host.h's HostStaging; what a plane of a query's output struct is, is that query's one table (scan_host.h, layers_host.h,
-// attributes_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
+// attributes_host.h, closest_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
 // helpers below; what a bit row is, is bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
 
 #include "attributes_host.h"
 #include "bitrows_host.h"
+#include "closest_host.h"
 #include "features_host.h"
 #include "gather_host.h"
 #include "layers_host.h"
@@ -908,6 +909,75 @@ extern "C" int lg_hit_attributes_of(const lg_accel *a, const double *rays, const
 }
 extern "C" int lg_hit_attributes_of_device(const lg_accel *a, const double *dev_rays, const lg_hit *dev_hits, size_t n, const lg_attr_out *dev_out, void *hip_stream) {
     return hit_attributes_device(a, dev_rays, dev_hits, true, n, dev_out, hip_stream);
+}
+
+// ---- closest points (lg_closest_points*; k_closest.hip): for each of the caller's points the nearest surface point of the scene.  What
+// needs no device -- the limits and the sizes, the NULL and alignment rules, the sphere gate, the pruning test's constants and the stack
+// depth -- is closest_host.h's.
+// The query's own tables, made from the accel's flattened scene at its first call (caller holds a.mtx and has made the device current)
+static const ClosestTables &closest_tables_of(const lg_accel &a) {
+    if (!a.closest) {
+        const FlatScene &f = a.flat;
+        auto t = std::make_shared<ClosestTables>(closest_tables(ClosestScene{f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(),
+                                                                             f.primref.size(), f.leaf_soup.data(), f.leaf_soup.size()}));
+        a.closest_cl.obtain(t->accel.size() * sizeof(ClosestAccel));
+        HIP_TRY(hipMemcpy(a.closest_cl.p, t->accel.data(), t->accel.size() * sizeof(ClosestAccel), hipMemcpyHostToDevice));
+        a.closest = t;
+    }
+    return *a.closest;
+}
+// What the scene itself may be refused for, in the contract's order
+static const ClosestTables &check_closest_scene(const lg_accel &a) {
+    const ClosestTables &t = closest_tables_of(a);
+    if (t.refused >= 0)
+        throw Error("closest points: instance " + std::to_string(t.refused) + " holds a sphere under a transform chain that is no similarity (lg_scene_closest_gate)");
+    if (t.depth > CLOSEST_MAX_DEPTH)
+        throw Error("closest points: the scene's trees need a stack of " + std::to_string(t.depth) + " entries, the kernel's holds " + std::to_string(CLOSEST_MAX_DEPTH));
+    return t;
+}
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call, the scene and the
+// buffers): ONE launch over the points' 64-point tiles -- no chunks: the outputs are the caller's, and nothing is parked
+static void enqueue_closest(const lg_accel &a, const ClosestTables &t, const double *points, size_t n, double radius, const lg_closest_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    const DParams P = base_params(a, 1, 1);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const size_t lds = closest_stack_bytes(t.depth);
+    // beyond the default 64 KiB the kernel's limit is raised -- always to the most any scene may ask for, so that two accels of different
+    // depths used from two threads never lower it under each other's launch
+    if (lds > (64u << 10)) HIP_TRY(closest_set_lds_limit(closest_stack_bytes(CLOSEST_MAX_DEPTH)));
+    int per_cu = 0;
+    HIP_TRY(closest_occupancy(t.depth, &per_cu));
+    const unsigned long long tiles = ((unsigned long long)n + 63ull) / 64ull, want = (tiles + 3ull) / 4ull; // four waves a workgroup
+    const uint32_t blocks = (uint32_t)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, (unsigned long long)(per_cu < 1 ? 1 : per_cu) * a.cus));
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(launch_closest(P, points, n, radius * radius, t.qmax, out.distance, out.point, out.id, a.accel_tri_base.p, a.closest_cl.p, c.tile_counter.p, blocks, t.depth, stream));
+}
+// Host form: the points go up, the planes come back staged
+extern "C" int lg_closest_points(const lg_accel *a, const double *points, size_t n, double radius, const lg_closest_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_closest(a, points, n, radius, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        RoundTrip trip(*a);
+        const ClosestTables &t = check_closest_scene(*a);
+        const double *dpoints = trip.in(points, n * 3);
+        lg_closest_out dev = *out; // ... where a plane asked for becomes its device buffer
+        closest_planes(dev, n, staged_planes(trip));
+        trip.run([&] { enqueue_closest(*a, t, dpoints, n, radius, dev, a->stream); });
+    });
+}
+extern "C" int lg_closest_points_device(const lg_accel *a, const double *dev_points, size_t n, double radius, const lg_closest_out *dev_out, void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_closest(a, dev_points, n, radius, dev_out);
+        check_closest_alignment(dev_points, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        const ClosestTables &t = check_closest_scene(*a);
+        check_device_buffer(*a, dev_points, n * 3 * sizeof(double), 8, "points");
+        closest_planes(*dev_out, n, device_planes(*a));
+        enqueue_closest(*a, t, dev_points, n, radius, *dev_out, (hipStream_t)hip_stream);
+    });
 }
 
 // ---- ray paths (lg_trace_paths*; k_paths.hip): each of the caller's rays followed through up to max_bounces vertices, the next segment

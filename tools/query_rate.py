@@ -82,11 +82,14 @@ Rows M64 / MR: one light at 64 positions by 64 calls on ONE accel against 64 reb
 Hit attributes (lg_hit_attributes_device, lg_hit_attributes_of_device) -- --rows attributes (not part of "all"): the camera's rays of a --size^2 film.
 Row I, the floor: lg_intersect_device.  Rows A2 / A7: the walking form with uv + bary alone / with all seven planes.  Rows O / W: the _of form on a
 compacted tenth of the hits against re-walking that tenth.
+Closest points (lg_closest_points_device) -- --rows closest (not part of "all"): 2^20 points of a 128 x 128 x 64 grid over 1.2 x the scene's
+bounds (the root box through the root's transform), in grid order.  Row C: all three planes, radius +INF; row Cr: radius 5 % of the bounds'
+diagonal.  Timed C, Cr, so --repeats alternates them.
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes|closest[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -1110,6 +1113,32 @@ def measure_attributes(name, builder, size, calls):
     return out
 
 
+def measure_closest(name, builder, calls):
+    """Closest points on 2^20 grid points (128 x 128 x 64, grid order) over 1.2 x the scene's bounds, all three planes (48 bytes written a
+    point).  Row C: radius +INF; row Cr: radius 5 % of the bounds' diagonal."""
+    if not hasattr(G, "closest_points_device"):
+        return []
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    probe = G.intersect(accel, G.camera_rays(accel, 64, 64))
+    p = probe["p"][probe["kind"] != 0]
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    mid, half = (lo + hi) / 2.0, (hi - lo) / 2.0 * 1.2
+    ax = [mid[k] + half[k] * np.linspace(-1.0, 1.0, m) for k, m in enumerate((128, 128, 64))]
+    grid = np.ascontiguousarray(np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3))
+    n = len(grid)
+    pts = torch.from_numpy(grid).cuda()
+    dist, point, ids = torch.empty((n,), dtype=torch.float64, device="cuda"), torch.empty((n, 3), dtype=torch.float64, device="cuda"), torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    diag = float(np.sqrt(((hi - lo) ** 2).sum()))
+    out = []
+    for row, radius in (("C: lg_closest_points_device, three planes, radius +INF", float("inf")), ("Cr: the same, radius 5 % of the bounds' diagonal", 0.05 * diag)):
+        ms = timed(lambda: G.closest_points_device(accel, n, pts, radius, distance_ptr=dist, point_ptr=point, id_ptr=ids, stream=s), calls, warmup=1)
+        found = int((ids[:, 0] != 0).sum())
+        out.append({"scene": name, "row": row, "points": n, "radius": radius, "ms": round(ms, 4), "mpoints_per_s": round(n / ms / 1e3, 2), "bytes_per_point": 48, "within_radius": found,
+                    "calls": calls, "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)})
+    return out
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -1234,7 +1263,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -1243,8 +1272,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1276,7 +1305,9 @@ def main():
                 got += measure_lit(name, builder, args.size, max(args.calls, 3))
             if "attributes" in want:
                 got += measure_attributes(name, builder, args.size, max(args.calls, 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes"}:
+            if "closest" in want:
+                got += measure_closest(name, builder, max(args.calls, 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
