@@ -299,6 +299,23 @@ int lg_accel_last_fused_shade(const lg_accel *);
  * camera's, 3 more than one level, 4 not exactly one light, 5 the closest launch would not take the packet form, 6 the shadow launch
  * would not take the pair form); -1 on an error. */
 int lg_scene_fused_shade_gate(const lg_scene *, int camera_level0);
+/* The frame table of flat triangles: lg_accel_from makes, on the device, one record per triangle of every mesh
+ * instance without vertex normals and with at most 1,024 triangles -- what a hit's shading frame holds that no ray enters: the normals
+ * and tangents carried up the scene graph for both signs of the triangle's normal, and the material -- provided the accel's records are
+ * at most 4,096 together.  The fused form's closest pass reads a hit's record instead of evaluating those expressions again; every other
+ * kernel, and every hit without a record, evaluates them as before.  1 (default): on; 0: no launch reads the table (A/B, tests;
+ * LASGUN_TRI_FRAMES=0 does the same for every accel).  Same bytes either way.
+ * lg_accel_last_tri_frames: whether the level-0 closest launch of the last chain read the table (1 / 0; -1 before the first). */
+int lg_accel_set_tri_frames(const lg_accel *, int enabled);
+int lg_accel_last_tri_frames(const lg_accel *);
+/* The table's plan for a scene, without a device (tests; lasgun_amd/csrc/tri_frames_host.h): returns the records an accel of the scene
+ * would hold, 0 where it would hold no table; base[a] (may be NULL; at most `cap` written) is accel a's first record, 0xFFFFFFFF where
+ * it has none; -1 on an error. */
+int lg_scene_tri_frames_gate(const lg_scene *, uint32_t *base, int cap);
+/* The table an accel holds, as its device made it (tests): up to `cap` records of 176 bytes into `records` (may be NULL) -- 21 doubles
+ * c[3], ng0[3], ss[3], ns[2][3], ts[2][3] (the two variants: the triangle's normal as it is, and negated), then the material as an
+ * int32 and a word of padding.  Returns the records the accel holds (0: no table), -1 on an error.  Synchronous. */
+int lg_accel_read_tri_frames(const lg_accel *, void *records, int cap);
 /* The LDS image lg_accel_from would make for this scene, without a device (tests): its 32-bit words into words[0 .. cap), info[8] = {16-byte
  * units, node offset, primref offset, leaf-record offset, accel-record offset (all in units), 1 if it holds pair records, accels, node
  * records of the flat tables}.  Returns the number of words, 0 when the tables do not fit in LDS, -1 on an error. */

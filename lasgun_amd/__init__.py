@@ -52,6 +52,10 @@ _EXTRA = {
     "accel_set_fused_shade": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_last_fused_shade": (_C.c_int, [_C.c_void_p]),
     "scene_fused_shade_gate": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_set_tri_frames": (_C.c_int, [_C.c_void_p, _C.c_int]),
+    "accel_last_tri_frames": (_C.c_int, [_C.c_void_p]),
+    "scene_tri_frames_gate": (_C.c_int, [_C.c_void_p, _C.POINTER(_C.c_uint32), _C.c_int]),
+    "accel_read_tri_frames": (_C.c_int, [_C.c_void_p, _C.c_void_p, _C.c_int]),
     "scene_lds_image": (_C.c_longlong, [_C.c_void_p, _C.c_int, _C.POINTER(_C.c_uint32), _C.c_size_t, _C.POINTER(_C.c_uint32)]),
     "accel_set_streaming": (_C.c_int, [_C.c_void_p, _C.c_int]),
     "accel_get_prune": (_C.c_int, [_C.c_void_p]),
@@ -127,6 +131,9 @@ class Hit(_C.Structure):  # lg_hit (include/lasgun_hip.h): one closest hit of a 
 
 HIT_DTYPE = _np.dtype(Hit)  # the numpy mirror of lg_hit: what HipApi.intersect returns
 assert _C.sizeof(Hit) == 96 and HIT_DTYPE.itemsize == 96, "lg_hit is 96 bytes"
+# a record of the frame table (include/lasgun_hip.h, lg_accel_read_tri_frames): 176 bytes
+TRI_FRAME_DTYPE = _np.dtype([("c", "<f8", (3,)), ("ng0", "<f8", (3,)), ("ss", "<f8", (3,)), ("ns", "<f8", (2, 3)), ("ts", "<f8", (2, 3)), ("mat", "<i4"), ("pad", "<u4")])
+assert TRI_FRAME_DTYPE.itemsize == 176, "a frame record is 176 bytes"
 LENS_EQUIRECTANGULAR, LENS_FISHEYE = 0, 1  # lg_lens::kind
 assert _C.sizeof(CLens) == 112, "lg_lens is 112 bytes"
 assert _C.sizeof(CFeatures) == 40, "lg_features is 40 bytes"
@@ -349,6 +356,38 @@ class HipApi(Api):
         if v < 0:
             raise LasgunError(self.last_error())
         return int(v)
+
+    def set_tri_frames(self, accel, enabled):
+        """The frame table of flat triangles in the fused form's closest pass: a hit on a triangle with a record reads there what no ray
+        enters (default on; same bytes either way; include/lasgun_hip.h, lg_accel_set_tri_frames)."""
+        if self.call("accel_set_tri_frames", accel.h, 1 if enabled else 0):
+            raise LasgunError(self.last_error())
+
+    def last_tri_frames(self, accel):
+        """Whether the level-0 closest launch of the last chain of the level-by-level pipeline read the frame table: True, False, None
+        before the first."""
+        v = self.call("accel_last_tri_frames", accel.h)
+        return None if v < 0 else bool(v)
+
+    def read_tri_frames(self, accel):
+        """The accel's frame table as its device made it: a structured array of TRI_FRAME_DTYPE, one record per (mesh instance, triangle)
+        in the plan's order (include/lasgun_hip.h, lg_accel_read_tri_frames)."""
+        n = self.call("accel_read_tri_frames", accel.h, None, 0)
+        if n < 0:
+            raise LasgunError(self.last_error())
+        rows = _np.zeros(n, dtype=TRI_FRAME_DTYPE)
+        if n and self.call("accel_read_tri_frames", accel.h, rows.ctypes.data, n) != n:
+            raise LasgunError(self.last_error())
+        return rows
+
+    def scene_tri_frames_gate(self, scene, cap=4096):
+        """The frame table's plan for a scene, without a device: (records, base) -- the records an accel of the scene would hold (0: no
+        table) and, per accel (the first `cap` of them), its first record or None (include/lasgun_hip.h, lg_scene_tri_frames_gate)."""
+        base = (_C.c_uint32 * cap)(*([0xFFFFFFFE] * cap))
+        v = self.call("scene_tri_frames_gate", scene.h, base, cap)
+        if v < 0:
+            raise LasgunError(self.last_error())
+        return int(v), [None if b == 0xFFFFFFFF else int(b) for b in base if b != 0xFFFFFFFE]
 
     def last_organisation(self, accel):
         """What the accel's last launch ran as: "megakernel", "wavefront" (level by level), "queue"; None before the first."""

@@ -3,6 +3,7 @@
 #include "internal.h"
 #include "attributes_host.h"
 #include "pairs_host.h"
+#include "tri_frames_host.h"
 
 // What a record of lg_hit_attributes_of* may name (attributes_host.h, the counts table): a mesh accel's faces are its OBJ's (lg_hit::prim of
 // a triangle is the face number), and the leaves of a group's reference tree hold its spheres and boxes -- each sits in that group and in
@@ -34,6 +35,24 @@ static std::vector<uint32_t> attr_counts_of(const FlatScene &f, const Scene &sce
         }
     }
     return attr_counts_build(faces, tri_base, sphere_accel, cuboid_accel);
+}
+
+// The frame table's plan for a flattened scene (tri_frames_host.h), without a device: every accel as the plan sees it -- a mesh instance's
+// triangles are its OBJ's faces, from its mesh's first triangle on -- and the plan itself: base[a] per accel, the records returned.
+static std::vector<TriFramesAccel> tri_frames_accels(const FlatScene &f, const Scene &scene) {
+    std::vector<TriFramesAccel> t(f.accels.size());
+    for (size_t id = 0; id < f.accels.size(); ++id) {
+        t[id] = TriFramesAccel{f.accels[id].flags, id < f.accel_tri_base.size() ? f.accel_tri_base[id] : 0u, 0u};
+        const int64_t obj = id < f.accel_obj.size() ? f.accel_obj[id] : -1;
+        if ((f.accels[id].flags & AF_MESH) && obj >= 0 && (size_t)obj < scene.meshes.size() && scene.meshes[(size_t)obj])
+            t[id].faces = (uint32_t)std::min<size_t>(scene.meshes[(size_t)obj]->tri.size() / 3, 0xFFFFFFFFu);
+    }
+    return t;
+}
+uint32_t scene_tri_frames(const FlatScene &f, const Scene &scene, std::vector<uint32_t> &base) {
+    const std::vector<TriFramesAccel> t = tri_frames_accels(f, scene);
+    base.assign(t.size(), NO_HIT);
+    return tri_frames_plan(t.data(), t.size(), f.tri_v.size() / 3, base.data());
 }
 
 // raise the dynamic-LDS limit of the traversal kernels of EVERY kernel file (ldss: their LDS-resident-scene forms; otherwise the 256-lane
@@ -373,7 +392,26 @@ static void build_and_upload(lg_accel *a, bool with_fast) {
         }
         stage.add(a->accel_tri_base, f.accel_tri_base); // (ray queries: k_query.hip)
         stage.add(a->attr_counts, attr_counts_of(a->flat, *a->scene)); // (lg_hit_attributes_of*: k_attributes.hip)
+        // The frame table of flat triangles (tri_frames_host.h: the plan): its records are staged as zeros and filled on the
+        // device, by the per-hit path's own text (k_tri_frames.hip), before lg_accel_from returns.
+        std::vector<uint32_t> tf_base;
+        a->tri_frame_records = scene_tri_frames(a->flat, *a->scene, tf_base);
+        {
+            std::vector<DTriFrameJob> jobs(a->tri_frame_records);
+            const std::vector<TriFramesAccel> ta = tri_frames_accels(a->flat, *a->scene);
+            if (a->tri_frame_records && !tri_frames_jobs(ta.data(), ta.size(), a->flat.tri_v.size() / 3, tf_base.data(), a->tri_frame_records, jobs.data()))
+                throw Error("frame table: the plan does not add up");
+            stage.add(a->tri_frame_base, tf_base); stage.add(a->tri_frame_jobs, jobs);
+            stage.add(a->tri_frames, std::vector<DTriFrame>(a->tri_frame_records));
+        }
         stage.commit(a->arena);
+        if (a->tri_frame_records) {
+            DParams T{};
+            T.accels = a->accels.p; T.tri_v = a->tri_v.p; T.tri_t = a->tri_t.p; T.vpos = a->vpos.p; T.vtex = a->vtex.p;
+            T.default_material = a->flat.default_material;
+            HIP_TRY(launch_tri_frames(T, a->tri_frame_jobs.p, a->tri_frame_records, a->tri_frames.p, a->stream));
+            HIP_TRY(hipStreamSynchronize(a->stream)); // (a caller's stream may carry the first launch that reads it)
+        }
         // Which organisation is the default (measured, tools/threshold_sweep.py): the megakernel unless the scene has
         // so many spheres / boxes that BVH-node and sphere tests dominate a ray (>= 512: with the scene tables in LDS
         // the megakernel keeps up to ~50 node + primitive tests per ray; beyond that the traversal kernels' lower
@@ -426,6 +464,7 @@ static void swap_tables(lg_accel &x, lg_accel &y) {
     swap(x.vpos, y.vpos); swap(x.vnorm, y.vnorm); swap(x.vtex, y.vtex); swap(x.leaf_soup, y.leaf_soup); swap(x.chunks, y.chunks); swap(x.strips, y.strips);
     swap(x.sphere_ref_leaf, y.sphere_ref_leaf); swap(x.cuboid_ref_leaf, y.cuboid_ref_leaf); swap(x.tri_ref_leaf, y.tri_ref_leaf); swap(x.accel_ref_leaf, y.accel_ref_leaf);
     swap(x.accels, y.accels); swap(x.materials, y.materials); swap(x.lights, y.lights); swap(x.accel_tri_base, y.accel_tri_base); swap(x.attr_counts, y.attr_counts);
+    swap(x.tri_frames, y.tri_frames); swap(x.tri_frame_jobs, y.tri_frame_jobs); swap(x.tri_frame_base, y.tri_frame_base); swap(x.tri_frame_records, y.tri_frame_records);
     swap(x.lds_image, y.lds_image); swap(x.accel_image, y.accel_image); swap(x.accel_image_n16, y.accel_image_n16);
     swap(x.lds_image_n16, y.lds_image_n16); swap(x.lds_node_off, y.lds_node_off); swap(x.lds_prim_off, y.lds_prim_off);
     swap(x.lds_soup_off, y.lds_soup_off); swap(x.lds_accel_off, y.lds_accel_off);

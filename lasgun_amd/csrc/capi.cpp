@@ -859,6 +859,47 @@ int lg_scene_fused_shade_gate(const lg_scene *s, int camera_level0) {
     });
     return rc ? -1 : v;
 }
+int lg_accel_set_tri_frames(const lg_accel *a, int enabled) {
+    if (enabled != 0 && enabled != 1) return fail("tri frames must be 0 or 1");
+    std::lock_guard<std::mutex> g(a->mtx);
+    a->tri_frames_on = enabled == 1;
+    return 0;
+}
+int lg_accel_last_tri_frames(const lg_accel *a) { // the level-0 closest launch of the last chain of the level-by-level pipeline: 1 it read the frame table, 0 it did not; -1 before the first
+    std::lock_guard<std::mutex> g(a->mtx);
+    return a->last_tri_frames;
+}
+// The accel's frame table as the device holds it (tests): up to `cap` records of 176 bytes (dscene.h, DTriFrame) into `records` (may be NULL);
+// returns the records the accel holds, -1 on an error.
+int lg_accel_read_tri_frames(const lg_accel *a, void *records, int cap) {
+    int v = 0;
+    int rc = guarded([&] {
+        if (!a) throw Error("accel is NULL");
+        std::lock_guard<std::mutex> g(a->mtx);
+        v = (int)a->tri_frame_records;
+        const size_t n = std::min<size_t>(a->tri_frame_records, cap > 0 ? (size_t)cap : 0u);
+        if (records && n) {
+            use_device(a->device);
+            HIP_TRY(hipMemcpy(records, a->tri_frames.p, n * sizeof(DTriFrame), hipMemcpyDeviceToHost));
+        }
+    });
+    return rc ? -1 : v;
+}
+// The frame table's plan for a scene without a device (tri_frames_host.h, tri_frames_plan over the flattened tables): the records an accel
+// of the scene would hold (0: no table), and base[a] (may be NULL; at most `cap` written) -- accel a's first record, 0xFFFFFFFF where it
+// has none; -1 on an error.
+int lg_scene_tri_frames_gate(const lg_scene *s, uint32_t *base, int cap) {
+    int v = 0;
+    int rc = guarded([&] {
+        if (!s) throw Error("scene is NULL");
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        std::vector<uint32_t> b;
+        v = (int)scene_tri_frames(f, s->s, b);
+        for (int i = 0; base && i < cap && (size_t)i < b.size(); ++i) base[i] = b[(size_t)i];
+    });
+    return rc ? -1 : v;
+}
 int lg_accel_set_mode(const lg_accel *a, int mode) {
     if (mode != 0 && mode != 1) return fail("mode must be 0 (reference traversal) or 1 (fast)");
     std::lock_guard<std::mutex> g(a->mtx);

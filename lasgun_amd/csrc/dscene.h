@@ -233,6 +233,20 @@ struct DRelAccel {
     uint32_t slot_n;   // ... and how many carry a 48-byte leaf record (0 for a mesh accel: triangles stay absolute)
 };
 
+// The frame table (tri_frames_host.h: which accels get records; k_tri_frames.hip: the build kernel; shade.h, shade_frame_tri: the reader;
+// DESIGN.md 3.2): one record per (mesh instance accel, triangle) of a mesh without vertex normals -- what resolve_hit and shade_frame make
+// of the triangle and the chain of accels above it, which no ray enters.  c = cross(dp02, dp12) in the mesh's local space, whose sign
+// against the local ray picks the variant; ng0 the geometric normal before face_forward(ng0, wo); ss; ns and ts = cross(ns, ss) for
+// n = c (variant 0) and n = -c (variant 1) carried up the chain; the material.  21 doubles and a word.
+struct DTriFrame {
+    double c[3], ng0[3], ss[3];
+    double ns[2][3], ts[2][3];
+    int32_t mat;
+    uint32_t pad;
+};
+static_assert(sizeof(DTriFrame) == 176, "DTriFrame is 21 doubles and a word (tri_frames_host.h, TRI_FRAME_BYTES)");
+struct DTriFrameJob { uint32_t accel, tri; }; // a record's (accel, global triangle index), for the build kernel
+
 struct DParams {
     // ---- scene tables
     const DNode *nodes;
@@ -386,6 +400,12 @@ struct DParams {
     // The fused form of the camera's level 0 (k_wavefront.hip, FUSED): 1 where the closest and shadow launches of the level
     // shade between them and no shade pass follows (launch.cpp, fused_shade: the gate; fused_host.h); 0 everywhere else
     uint32_t fused;
+    // The frame table (DTriFrame above), set for the fused packet closest launch alone (launch.cpp, tri_frames: the gate); nullptr everywhere
+    // else.  tri_frame_base[a]: accel a's first record, NO_HIT where it has none; tri_base[a]: its mesh's first triangle in the triangle
+    // tables -- triangle `idx` of accel a is record tri_frame_base[a] + (idx - tri_base[a]).
+    const DTriFrame *tri_frames;
+    const uint32_t *tri_frame_base;
+    const uint32_t *tri_base;
 };
 static_assert(sizeof(DParams) <= 4096, "DParams is passed by value: a kernel's arguments are at most 4 KB");
 // does a closest / shadow pass of the level-by-level pipeline launched with these parameters walk the pair form of the LDS image?  (the plain exact walk from LDS alone)

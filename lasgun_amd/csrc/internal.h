@@ -36,6 +36,8 @@ hipError_t trace_occupancy(uint32_t stack_depth, bool fast, size_t extra_lds, in
 hipError_t launch_wf_trace(const DParams &P, bool fast, bool shadow, uint32_t blocks, uint32_t stack_depth, hipStream_t stream);
 hipError_t launch_wf_shade(const DParams &P, uint32_t blocks, hipStream_t stream);
 hipError_t launch_wf_combine(const DParams &P, uint32_t blocks, hipStream_t stream);
+// k_tri_frames.hip: the frame table's build kernel (tri_frames_host.h); P: the scene tables alone
+hipError_t launch_tri_frames(const DParams &P, const DTriFrameJob *jobs, uint32_t n, DTriFrame *out, hipStream_t stream);
 // k_query.hip: ray queries (query.cpp) -- hits != nullptr: closest hit into lg_hit[n]; occluded != nullptr: the any-hit walk, one byte per ray
 // perm != nullptr: the rays are walked in that order (slot s walks ray perm[s]); answers go to the ray's own slot either way
 hipError_t launch_query(const DParams &P, const double *rays, unsigned long long n, void *hits, uint8_t *occluded, const uint32_t *tri_base,
@@ -473,6 +475,11 @@ struct lg_accel {
     DevBuf<DLight> lights;
     DevBuf<uint32_t> accel_tri_base; // ray queries only (k_query.hip): per accel, its mesh's first triangle (FlatScene::accel_tri_base)
     DevBuf<uint32_t> attr_counts;    // lg_hit_attributes_of* only (k_attributes.hip): what a record may name (attributes_host.h, attr_counts_build)
+    // the frame table of flat triangles (tri_frames_host.h: the plan; k_tri_frames.hip fills it at the build; DParams::tri_frames)
+    DevBuf<DTriFrame> tri_frames;
+    DevBuf<DTriFrameJob> tri_frame_jobs; // the build kernel's list, one entry per record
+    DevBuf<uint32_t> tri_frame_base;     // per accel: its first record, NO_HIT where it has none
+    uint32_t tri_frame_records = 0;      // records of the table; 0: the accel holds none
     // lg_closest_points* only (k_closest.hip): the gate's verdict, the stack depth and the pruning test's constants per accel (closest_host.h),
     // made from `flat` and uploaded at the accel's first such call -- no part of the tables lg_accel_from builds or lg_accel_info counts
     mutable std::shared_ptr<ClosestTables> closest;
@@ -560,6 +567,9 @@ struct lg_accel {
     // the fused form of the camera's level 0 (k_wavefront.hip, FUSED; launch.cpp, fused_shade: the gate)
     mutable bool fused_shade = true;   // lg_accel_set_fused_shade
     mutable int last_fused_shade = -1; // the last chain of the level-by-level pipeline: 1 its level 0 took the fused form (two passes, no shade pass), 0 the three kernels; -1 before the first
+    // the frame table in the fused packet closest pass (shade.h, shade_frame_tri; launch.cpp, tri_frames: the gate)
+    mutable bool tri_frames_on = true; // lg_accel_set_tri_frames
+    mutable int last_tri_frames = -1;  // the last chain of the level-by-level pipeline: 1 its level-0 closest launch read the table, 0 it did not; -1 before the first
     mutable int packet_scene = -1;     // the scene graph's part of the gate (packet_host.h, PacketRefusal), made at the first launch that asks; -1: not yet
     uint32_t ldss_blocks = 0;         // one 1024-lane workgroup per CU; 0 = variant unavailable for this scene
     uint32_t cus = 1;                 // compute units of the accel's device
@@ -616,6 +626,8 @@ void sync_checked(const lg_accel &a);
 DParams base_params(const lg_accel &a, uint32_t w, uint32_t h);
 void set_lds_scene(const lg_accel &a, DParams &P);
 bool scene_lds_image(const Scene &scene, bool pairs, std::vector<uint32_t> &img, uint32_t info[8]); // accel.cpp: the LDS image of a scene alone, no device
+// accel.cpp: the frame table's plan of a flattened scene (tri_frames_host.h), no device -- base[a] per accel, the table's records returned
+uint32_t scene_tri_frames(const FlatScene &f, const Scene &scene, std::vector<uint32_t> &base);
 void ensure_aux_streams(const lg_accel &a, unsigned n);
 void enqueue(const lg_accel &a, DParams &P, bool stats, hipStream_t stream);
 void enqueue_radiance(const lg_accel &a, const double *rays, size_t n, double *radiance, const uint32_t *perm, lg_accel::LaunchCtx &c, hipStream_t stream);

@@ -308,9 +308,15 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             } else if (!hit && mine) P.wf_hq[i] = WF_NONE; // a hole of a dense block
             if (hit) {
                 Shade sh;
-                shade_frame(P, ray, b, sh);
-                if constexpr (FUSED) fused_closest_hit(P, px, i, h, sh);
-                else {
+                if constexpr (FUSED) {
+                    // A tile whose hits are all flat triangles with a record in the accel's frame table (a tile of the headline's walls) reads
+                    // there what no ray enters (shade.h, shade_frame_tri); a tile with any other hit in it -- a sphere, a cuboid, a mesh
+                    // without records -- takes shade_frame in every lane.  The vote is of the lanes that hit; the branch is the wave's.
+                    if (__builtin_amdgcn_ballot_w64(!tri_frame_hit(P, b)) == 0ull) shade_frame_tri(P, ray, b, sh);
+                    else shade_frame(P, ray, b, sh);
+                    fused_closest_hit(P, px, i, h, sh);
+                } else {
+                    shade_frame(P, ray, b, sh);
                     // no light's term at this hit depends on the light being visible (shade.h): the shadow pass will not walk it
                     const bool skip = P.shadow_skip && shadow_skippable(P, sh);
                     P.wf_hq[h] = skip ? (uint32_t)i | WF_SKIP : (uint32_t)i;

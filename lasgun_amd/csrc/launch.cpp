@@ -5,6 +5,7 @@
 #include "choice.h"
 #include "packet_host.h"
 #include "fused_host.h"
+#include "tri_frames_host.h"
 
 // The launch context of `stream` (at most MAX_LAUNCH_CTXS are kept; the least recently used one is recycled after a
 // device-wide synchronise).  Caller holds a.mtx and has made the accel's device current.
@@ -349,6 +350,18 @@ static uint32_t fused_shade(const lg_accel &a, const DParams &P, bool camera_lev
     return fused_shade_gate(q) == FUSED_OK ? 1u : 0u;
 }
 
+// The gate of the frame table in the fused packet closest launch (shade.h, shade_frame_tri; the predicate is
+// tri_frames_host.h's): that launch alone, when the accel holds a table.  Sets P.tri_frames / tri_frame_base / tri_base, or leaves them
+// null.  LASGUN_TRI_FRAMES=0 / lg_accel_set_tri_frames(0): every hit takes shade_frame's text, the parent's code path.
+static bool tri_frames(const lg_accel &a, DParams &P) {
+    static const bool env = env_on("LASGUN_TRI_FRAMES");
+    P.tri_frames = nullptr; P.tri_frame_base = nullptr; P.tri_base = nullptr;
+    if (!tri_frames_launch_gate(a.tri_frames_on && env, P.fused != 0u && P.packet != 0u && P.wf_level == 0u, a.tri_frame_records)) return false;
+    if (!a.tri_frames.p || !a.tri_frame_base.p || !a.accel_tri_base.p || a.tri_frames.n != a.tri_frame_records) return false;
+    P.tri_frames = a.tri_frames.p; P.tri_frame_base = a.tri_frame_base.p; P.tri_base = a.accel_tri_base.p;
+    return true;
+}
+
 // ---- the level-by-level pipeline (k_wavefront.hip), shared by a render (enqueue_wavefront) and a radiance query (enqueue_radiance) ----
 // A chunk's arrays in a launch context: the level arrays, and beside them the hit queue, frame and visibility of the widest level (dense
 // part + appended part), the queue counts and a block of tile heads per launch
@@ -420,12 +433,14 @@ struct WfChunk {
             P.packet = packet_walk(a, P, d == 0 && !own0); // (the camera's level 0 alone; every other launch of the chain: 0)
             if (d == 0) a.last_packet_walk = (int)P.packet;
             P.fused = d == 0 ? fused_shade(a, P, !own0 && !l0.every_level(), levels) : 0u; // (the camera's level 0 of a chain of one level: its closest and shadow launches shade, no shade pass follows)
-            if (d == 0) a.last_fused_shade = (int)P.fused;
+            if (d == 0) { a.last_fused_shade = (int)P.fused; a.last_tri_frames = 0; }
             if (own0) timed(a, 0, ls, [&] { return l0.closest(P, a.fast, tb, depth, ls); });
             else {
                 if (d == 0) a.last_l0_relative = l0_relative(a, P) ? 1 : 0; // (the camera's level 0: the form is chosen per launch, from this launch's camera)
+                if (d == 0) a.last_tri_frames = tri_frames(a, P) ? 1 : 0;   // (the fused packet closest launch alone reads the frame table)
                 timed(a, 0, ls, [&] { return launch_wf_trace(P, a.fast, false, tb, depth, ls); });
                 P.l0_rel_n = 0u;
+                P.tri_frames = nullptr; P.tri_frame_base = nullptr; P.tri_base = nullptr;
             }
             if (own0 && l0.own_shadow) { // (the call's lights: hit tiles x visibility words work tiles)
                 if (l0.shadow_) {

@@ -326,20 +326,75 @@ __device__ __forceinline__ const uint4 *load_accel_image(const DParams &P, uint3
 // Shading frame of a hit from the ray that found it (resolve_hit + SurfaceInteraction::from,
 // surface.rs:158-183).  Pure function of (ray, best): recomputed after each shadow traversal
 // instead of being kept in registers across it, which is what lets 4-5 waves share a SIMD.
+// The axes SurfaceInteraction::from and BSDF::new make of a resolved intersection, the part with no ray in it: the geometric normal before
+// face_forward, then ns, ss, ts.  shade_frame evaluates it per hit, the frame table's build kernel (k_tri_frames.hip) once per record.
+__device__ __forceinline__ V3 frame_ng0(const Isect &is) { return normalize(cross(is.gu, is.gv)); }
+__device__ __forceinline__ V3 frame_ns(const Isect &is) { return is.has_n ? normalize(is.n) : normalize(cross(is.su, is.sv)); }
+__device__ __forceinline__ V3 frame_ss(const Isect &is) { return normalize(is.su); } // si.surface.dpdu (bsdf.rs:34)
+struct FrameAxes {
+    V3 ng0, ns, ss, ts;
+};
+__device__ __forceinline__ FrameAxes frame_axes(const Isect &is) { // (the build kernel's: all four at once)
+    FrameAxes ax;
+    ax.ng0 = frame_ng0(is);
+    ax.ns = frame_ns(is);
+    ax.ss = frame_ss(is);
+    ax.ts = cross(ax.ns, ax.ss); // bsdf.rs:35
+    return ax;
+}
 __device__ __forceinline__ void shade_frame(const DParams &P, const Ray &ray, const Best &best, Shade &sh) {
     Isect is;
     sh.mat = resolve_hit(P, ray, best, is);
     sh.wo = -normalize(ray.d);
-    sh.ng = face_forward(normalize(cross(is.gu, is.gv)), sh.wo);
-    sh.ns = is.has_n ? normalize(is.n) : normalize(cross(is.su, is.sv));
+    sh.ng = face_forward(frame_ng0(is), sh.wo);
+    sh.ns = frame_ns(is);
     const double err = 2.220446049250313e-16 * 65536.0; // N::epsilon() * 2^16
     V3 p = ray.o + ray.d * is.t;
     V3 p_err = sh.ng * err;
     sh.praw = p;
     sh.p = p + p_err;
     sh.pm = p - p_err;
-    sh.ss = normalize(is.su);    // si.surface.dpdu (bsdf.rs:34)
+    sh.ss = frame_ss(is);
     sh.ts = cross(sh.ns, sh.ss); // bsdf.rs:35
+}
+// shade_frame's part with the ray in it, for a frame whose axes come from the table: the world ray, the hit's t, ng0
+__device__ __forceinline__ void shade_frame_finish(const Ray &ray, const double t, const V3 ng0, Shade &sh) {
+    sh.wo = -normalize(ray.d);
+    sh.ng = face_forward(ng0, sh.wo);
+    const double err = 2.220446049250313e-16 * 65536.0; // N::epsilon() * 2^16
+    V3 p = ray.o + ray.d * t;
+    V3 p_err = sh.ng * err;
+    sh.praw = p;
+    sh.p = p + p_err;
+    sh.pm = p - p_err;
+}
+
+// The same frame for a hit whose triangle has a record in the accel's frame table (DTriFrame, dscene.h): everything of
+// resolve_hit and frame_axes that no ray enters was evaluated at the accel build by that very text (k_tri_frames.hip), for both signs
+// face_forward(c, -lr.d) can pick; what is left per hit is the local ray and triangle_t for t, the sign, and shade_frame_finish.
+__device__ __forceinline__ bool tri_frame_hit(const DParams &P, const Best &best) {
+    return P.tri_frames && (best.ref >> 30) == PK_TRIANGLE && P.tri_frame_base[best.accel] != NO_HIT;
+}
+// Called by the lanes of a wave in which EVERY lane that hit has a record (the caller's vote): the table's path and shade_frame are then
+// two branches of a wave-uniform choice and neither holds a register across the other.  Both in one divergent flow were measured:
+// the merged results of the record lanes stay live across resolve_hit's sphere branch, the kernel -- at its 128 registers -- spills 60
+// more of them per lane, and the pass is slower than without the table.
+__device__ __forceinline__ void shade_frame_tri(const DParams &P, const Ray &ray, const Best &best, Shade &sh) {
+    const Ray lr = local_ray(P, ray, best.accel);
+    const uint32_t idx = best.ref & PRIM_INDEX_MASK;
+    const uint32_t *vi = P.tri_v + 3ull * idx;
+    TriHit h;
+    triangle_t(load_f3(P.vpos, vi[0]), load_f3(P.vpos, vi[1]), load_f3(P.vpos, vi[2]), lr, h); // is.t, as triangle_full makes it
+    const DTriFrame *f = P.tri_frames + (P.tri_frame_base[best.accel] + (idx - P.tri_base[best.accel]));
+    const V3 c{f->c[0], f->c[1], f->c[2]};
+    const bool flip = dot(c, -lr.d) < 0.0; // face_forward(c, -lr.d) took -c: variant 1 (both are fetched: no load waits for the sign)
+    const V3 ns0{f->ns[0][0], f->ns[0][1], f->ns[0][2]}, ns1{f->ns[1][0], f->ns[1][1], f->ns[1][2]};
+    const V3 ts0{f->ts[0][0], f->ts[0][1], f->ts[0][2]}, ts1{f->ts[1][0], f->ts[1][1], f->ts[1][2]};
+    sh.mat = f->mat;
+    sh.ns = flip ? ns1 : ns0;
+    sh.ts = flip ? ts1 : ts0;
+    sh.ss = V3{f->ss[0], f->ss[1], f->ss[2]};
+    shade_frame_finish(ray, h.t, V3{f->ng0[0], f->ng0[1], f->ng0[2]}, sh);
 }
 
 // Park / restore the shading frame in HBM across the shadow traversals ([field][lane]: coalesced).

@@ -350,12 +350,10 @@ __device__ __forceinline__ void sphere_full(const DSphere &s, const Ray &ray, do
     else isect_set(is, t, dpdv, dpdu);
 }
 
-// Triangle::intersect from the partial derivatives on (triangle.rs:257-304)
-__device__ __forceinline__ void triangle_full(const DParams &P, uint32_t tri, uint32_t aflags, const Ray &ray, Isect &is) {
-    const uint32_t *vi = P.tri_v + 3ull * tri;
-    V3 p0 = load_f3(P.vpos, vi[0]), p1 = load_f3(P.vpos, vi[1]), p2 = load_f3(P.vpos, vi[2]);
-    TriHit h;
-    triangle_t(p0, p1, p2, ray, h);
+// What Triangle::intersect makes of the triangle alone (triangle.rs:257-277, 300): dpdu, dpdv and c = cross(dp02, dp12), the normal of a
+// mesh without vertex normals before face_forward.  No ray in it: triangle_full evaluates it per hit, the frame table's build kernel
+// (k_tri_frames.hip) once per triangle -- one text, so the same bits.
+__device__ __forceinline__ void triangle_partials(const DParams &P, uint32_t tri, uint32_t aflags, V3 p0, V3 p1, V3 p2, V3 &dpdu, V3 &dpdv) {
     double uv[3][2];
     if (aflags & AF_HAS_UV) {
         const uint32_t *ti = P.tri_t + 3ull * tri;
@@ -368,7 +366,6 @@ __device__ __forceinline__ void triangle_full(const DParams &P, uint32_t tri, ui
     double duv12x = uv[1][0] - uv[2][0], duv12y = uv[1][1] - uv[2][1];
     V3 dp02 = p0 - p2, dp12 = p1 - p2;
     double determinant = (duv02x * duv12y) - (duv02y * duv12x);
-    V3 dpdu, dpdv;
     if (determinant == 0.0) {
         coordinate_system(cross(p2 - p1, p1 - p0), dpdu, dpdv);
     } else {
@@ -376,6 +373,17 @@ __device__ __forceinline__ void triangle_full(const DParams &P, uint32_t tri, ui
         dpdu = (duv12y * dp02 - duv02y * dp12) * inv;
         dpdv = (-duv12x * dp02 - duv02x * dp12) * inv;
     }
+}
+__device__ __forceinline__ V3 triangle_c(V3 p0, V3 p1, V3 p2) { return cross(p0 - p2, p1 - p2); } // cross(dp02, dp12) (triangle.rs:300)
+
+// Triangle::intersect from the partial derivatives on (triangle.rs:257-304)
+__device__ __forceinline__ void triangle_full(const DParams &P, uint32_t tri, uint32_t aflags, const Ray &ray, Isect &is) {
+    const uint32_t *vi = P.tri_v + 3ull * tri;
+    V3 p0 = load_f3(P.vpos, vi[0]), p1 = load_f3(P.vpos, vi[1]), p2 = load_f3(P.vpos, vi[2]);
+    TriHit h;
+    triangle_t(p0, p1, p2, ray, h);
+    V3 dpdu, dpdv;
+    triangle_partials(P, tri, aflags, p0, p1, p2, dpdu, dpdv);
     isect_set(is, h.t, dpdu, dpdv);
     if (aflags & AF_HAS_N) {
         const uint32_t *ni = P.tri_n + 3ull * tri;
@@ -389,7 +397,7 @@ __device__ __forceinline__ void triangle_full(const DParams &P, uint32_t tri, ui
         is.su = ss; is.sv = ts;
     } else {
         is.has_n = true;
-        is.n = face_forward(cross(dp02, dp12), -ray.d);
+        is.n = face_forward(triangle_c(p0, p1, p2), -ray.d);
     }
 }
 
@@ -1915,6 +1923,33 @@ __device__ __forceinline__ void audit_fast_ray(const DParams &P, const Ray &ray,
 // hit resolution: the winning primitive's RayIntersection carried back to world space
 // (primitive intersect, then bvh.rs:509-519 / transform.rs:243-264 for every accel on the way up)
 // ------------------------------------------------------------------------------------------
+// The way up of a hit found in `accel`: transform_ray_intersection (transform.rs:243-264), the material (bvh.rs:513-515) and the backface
+// swap (surface.rs:88-99) of every accel from `accel` to the root.  Returns the RayIntersection's material.  No ray in it: resolve_hit
+// walks it per hit, the frame table's build kernel (k_tri_frames.hip) once per triangle and sign of its normal.
+__device__ __forceinline__ int32_t chain_up(const DParams &P, uint32_t accel, Isect &is) {
+    int32_t isect_mat = P.default_material; // RayIntersection::new -> Material::default()
+    int32_t a = (int32_t)accel;
+    while (a >= 0) {
+        const DAccel *A = P.accels + a;
+        // transform_ray_intersection (transform.rs:243-264)
+        V3 gu = xf_vector(A->m, is.gu), gv = xf_vector(A->m, is.gv);
+        if (vne(is.gu, is.su) || vne(is.gv, is.sv)) {
+            is.su = xf_vector(A->m, is.su); is.sv = xf_vector(A->m, is.sv);
+        } else {
+            is.su = gu; is.sv = gv;
+        }
+        is.gu = gu; is.gv = gv;
+        if (is.has_n) is.n = xf_normal(A->minv, is.n);
+        if (A->material >= 0) isect_mat = A->material; // bvh.rs:513-515
+        if (A->flags & AF_SWAP_BACKFACE) {             // surface.rs:88-99
+            V3 tmp = is.gu; is.gu = is.gv; is.gv = tmp;
+            tmp = is.su; is.su = is.sv; is.sv = tmp;
+            if (is.has_n) is.n = -is.n;
+        }
+        a = A->parent;
+    }
+    return isect_mat;
+}
 __device__ __forceinline__ int32_t resolve_hit(const DParams &P, const Ray &wray, const Best &best, Isect &is) {
     Ray lr = local_ray(P, wray, best.accel);
     uint32_t kind = best.ref >> 30, idx = best.ref & PRIM_INDEX_MASK;
@@ -1936,27 +1971,7 @@ __device__ __forceinline__ int32_t resolve_hit(const DParams &P, const Ray &wray
     } else {
         triangle_full(P, idx, P.accels[best.accel].flags, lr, is);
     }
-    int32_t isect_mat = P.default_material; // RayIntersection::new -> Material::default()
-    int32_t a = (int32_t)best.accel;
-    while (a >= 0) {
-        const DAccel *A = P.accels + a;
-        // transform_ray_intersection (transform.rs:243-264)
-        V3 gu = xf_vector(A->m, is.gu), gv = xf_vector(A->m, is.gv);
-        if (vne(is.gu, is.su) || vne(is.gv, is.sv)) {
-            is.su = xf_vector(A->m, is.su); is.sv = xf_vector(A->m, is.sv);
-        } else {
-            is.su = gu; is.sv = gv;
-        }
-        is.gu = gu; is.gv = gv;
-        if (is.has_n) is.n = xf_normal(A->minv, is.n);
-        if (A->material >= 0) isect_mat = A->material; // bvh.rs:513-515
-        if (A->flags & AF_SWAP_BACKFACE) {             // surface.rs:88-99
-            V3 tmp = is.gu; is.gu = is.gv; is.gv = tmp;
-            tmp = is.su; is.su = is.sv; is.sv = tmp;
-            if (is.has_n) is.n = -is.n;
-        }
-        a = A->parent;
-    }
+    const int32_t isect_mat = chain_up(P, best.accel, is);
     return prim_mat >= 0 ? prim_mat : isect_mat; // integrate.rs:30
 }
 
