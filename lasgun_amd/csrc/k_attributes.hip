@@ -3,7 +3,8 @@
 // dpdu / dpdv --, as planes indexed by the ray.  What resolve_hit / triangle_full / sphere_full / cuboid_hit<true> compute for every shaded
 // hit and drop; attr_resolve.h restates them with it kept.
 //
-// attr_kernel, the walking form: query_kernel's closest form (k_query.hip) -- its prologue, its tile claim, one ray per lane, 64-ray tiles
+// attr_kernel, the walking form: query_kernel's closest form (k_query.hip) -- its prologue, its tile claim (in this file's own text, not
+// over tilewalk.h: over the shared header a row of this family measured slower, profiles/tilewalk_account.md), one ray per lane, 64-ray tiles
 // of the caller's array, the grid sized in query.cpp (traversal_grid), the forms launched through travform.h, PERM as there, the record
 // resolved by shade_frame and written as six 16-byte stores -- with the attribute planes behind it.  The walk is walk<LDSS, FAST, PRUNE>,
 // unchanged.  The evaluation that fills the record has query_kernel's uses and no others; the planes come from a second evaluation of the

@@ -1,7 +1,7 @@
 // lasgun_amd/csrc/k_directions.hip -- direction sets (include/lasgun_hip.h, lg_open_directions*): which of K shared directions are open above
 // each of N points.  Pair (i, k) is the ray (points[i], dirs[k]), both as given: no arithmetic makes it, and nothing is written out as rays.
 //
-// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
+// The kernel's prologue and tile cursor are tilewalk.h's; the grid is sized in query.cpp (traversal_grid) and the forms are
 // launched through travform.h.  The walk is any-hit: walk<LDSS, FAST, PRUNE>(.., any = true, ..), unchanged.  What differs is the work
 // item, and it is not k_visibility.hip's 8 x 8 block: a tile is 64 consecutive POINTS x 8 consecutive DIRECTIONS, one byte of each of 64
 // rows.  tile = point_block * dir_bytes + dir_byte: consecutive tiles keep their points and step through the directions.  Lane l owns
@@ -16,6 +16,7 @@
 // wave's adds are 64 consecutive words; integer sums do not depend on the order the tiles finish in.  Lanes behind n_points walk nothing
 // and store nothing.
 #include "travform.h"
+#include "tilewalk.h"
 
 namespace lg {
 
@@ -35,26 +36,12 @@ template <bool FAST, bool LDSS, bool PRUNE>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) directions_kernel(const DParams P, const DirectionArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads();
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    const uint32_t lane = threadIdx.x & 63u;
+    TileWalk<FAST, LDSS> tw;
+    if (!tw.begin(P)) return;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
     for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        const uint32_t tile = tw.next(P, final);
         if (tile == NO_TILE) break;
         const uint32_t pb = tile / Q.dir_bytes, db = tile - pb * Q.dir_bytes;
         const unsigned long long point = 64ull * pb + lane;
@@ -76,11 +63,10 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
             const V3 d{dk[0], dk[1], dk[2]};
             bool up = active;
             if (Q.normals) up = active && (n.x * d.x + n.y * d.y) + n.z * d.z > 0.0; // (a NaN sum, a zero and a perpendicular direction: not above)
-            Best b;
-            b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
+            Best b = fresh_best();
             if (up) {
                 const Ray ray = ray_new(o, d); // origin and direction as given
-                walk<LDSS, FAST, PRUNE>(P, ray, true, stack, stride, b, scn, cnt, arec);
+                walk<LDSS, FAST, PRUNE>(P, ray, true, tw.stack, tw.stride, b, tw.scn, cnt, tw.arec);
                 nabove += 1u;
                 if (!(b.t < 1.0)) byte |= 1u << j; // open: lg_occluded's test (point.rs:49) answers 0
             }

@@ -1,7 +1,7 @@
 // lasgun_amd/csrc/k_features.hip -- feature buffers (include/lasgun_hip.h, lg_capture_features*): depth, normal, albedo, coverage and ids of
 // the primary hits of the scene's own camera, the rays made in registers as the render makes them (camera_ray) and never written anywhere.
 //
-// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
+// The kernel's prologue, tile cursor and id word are tilewalk.h's; the grid is sized in query.cpp (traversal_grid) and the forms are
 // launched through travform.h.  The walk is closest hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged.  What differs is the work
 // item: a tile is an 8 x 8 block of the rectangle (pixel_of, mode 0, as the render's tiles) and a lane is one PIXEL.  The lane loops over
 // the pixel's samples s = 0 .. S-1, so the whole wave walks sample s together (64 neighbouring rays, as a render's wave) and each pixel's
@@ -13,6 +13,7 @@
 // outside the rectangle and is never touched (a tile row's 8 lanes still cover 96 contiguous bytes); id is one 16-byte store.  At most
 // 48 bytes a pixel, whatever S is.  Lanes outside the rectangle walk nothing and write nothing.
 #include "travform.h"
+#include "tilewalk.h"
 
 namespace lg {
 
@@ -31,39 +32,24 @@ template <bool FAST, bool LDSS, bool PRUNE>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) features_kernel(const DParams P, const FeatureArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads();
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    const uint32_t lane = threadIdx.x & 63u;
+    TileWalk<FAST, LDSS> tw;
+    if (!tw.begin(P)) return;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
     const uint32_t S = P.ss_root * P.ss_root;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
     for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        const uint32_t tile = tw.next(P, final);
         if (tile == NO_TILE) break;
         const Pixel px = pixel_of(P, tile, lane);
         double tsum = 0.0;
         V3 nsum{0.0, 0.0, 0.0}, asum{0.0, 0.0, 0.0};
         uint32_t nhit = 0u;
-        uint4 id0 = make_uint4(0u, NO_HIT, NO_HIT, 0xFFFFFFFFu); // kind 0, prim / instance ~0, material -1: lg_hit's miss
+        uint4 id0 = hit_id_none(); // lg_hit's miss
         for (uint32_t s = 0u; s < S; ++s) {
-            Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
+            Ray ray = idle_ray();
             if (px.active) ray = camera_ray(P, px.x, px.y, s);
-            Best b;
-            b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
-            if (px.active) walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+            Best b = fresh_best();
+            if (px.active) walk<LDSS, FAST, PRUNE>(P, ray, false, tw.stack, tw.stride, b, tw.scn, cnt, tw.arec);
             if (!px.active || b.ref == NO_HIT) continue;
             Shade sh;
             shade_frame(P, ray, b, sh);
@@ -74,10 +60,7 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
                 const double *c = Q.material_rgb + 3ull * (uint32_t)sh.mat;
                 asum = asum + V3{c[0], c[1], c[2]};
             }
-            if (s == 0u) {
-                const uint32_t pk = b.ref >> 30, idx = b.ref & PRIM_INDEX_MASK;
-                id0 = make_uint4(pk + 1u, pk == PK_TRIANGLE ? idx - Q.tri_base[b.accel] : idx, b.accel, (uint32_t)sh.mat);
-            }
+            if (s == 0u) id0 = hit_id(b, sh, Q.tri_base);
         }
         if (!px.active) continue;
         const double inv = 1.0 / (double)S;

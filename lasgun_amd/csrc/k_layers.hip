@@ -3,8 +3,8 @@
 // layer j's p - ng * 2^-36 -- shade_frame's pm (shade.h), the origin the render gives a glass hit's transmitted ray -- and keeps the
 // direction's bits.  The ray stays in registers between the walks; only the planes asked for are written.
 //
-// The kernel's prologue and tile loop repeat query_kernel's closest form (k_query.hip): one ray per lane, 64-ray tiles of the caller's
-// array, the grid sized in query.cpp (traversal_grid), the forms launched through travform.h, PERM as there.  The walk is closest hit:
+// The kernel's prologue, tile cursor and record writer are tilewalk.h's, its work item query_kernel's (k_query.hip): one ray per lane, 64-ray
+// tiles of the caller's array, the grid sized in query.cpp (traversal_grid), the forms launched through travform.h, PERM as there.  The walk is closest hit:
 // walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged, with a fresh Best per segment, and a hit is resolved as query_kernel resolves
 // it (shade_frame, the face number through tri_base; layer_next_origin says why pm is evaluated apart).  What lives across the walks
 // besides the ray: T (the running parameter), inside (t_1 + t_3 + ..) and count -- 5 VGPRs; nothing is parked in memory.  Lanes are not
@@ -15,6 +15,7 @@
 // along: one 8-byte store; count and inside: once per ray, after the loop.  Every element of every plane asked for is written by exactly
 // one lane: no atomics, no pre-fill.  Lanes past the last ray (n % 64) walk nothing and write nothing.
 #include "travform.h"
+#include "tilewalk.h"
 
 namespace lg {
 
@@ -31,34 +32,20 @@ struct LayersArgs {
     const uint32_t *perm;      // PERM forms only: [n], the ray walked in each slot
 };
 
-__device__ __forceinline__ uint4 layer_bits2(double a, double b) {
-    const unsigned long long x = (unsigned long long)__double_as_longlong(a), y = (unsigned long long)__double_as_longlong(b);
-    return make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
-}
-
 // the planes of a layer behind a ray's last one, at element e: lg_intersect's miss record, its id words, +INF
 __device__ __forceinline__ void layer_store_miss(const LayersArgs &Q, unsigned long long e) {
-    const uint4 none = make_uint4(0u, NO_HIT, NO_HIT, 0xFFFFFFFFu); // kind 0, prim / instance ~0, material -1
-    if (Q.hits) {
-        uint4 *out = Q.hits + 6ull * e;
-        out[0] = layer_bits2(INFINITY, 0.0); out[1] = layer_bits2(0.0, 0.0); out[2] = layer_bits2(0.0, 0.0);
-        out[3] = layer_bits2(0.0, 0.0); out[4] = layer_bits2(0.0, 0.0);
-        out[5] = none;
-    }
-    if (Q.id) Q.id[e] = none;
+    if (Q.hits) store_hit_none(Q.hits + 6ull * e);
+    if (Q.id) Q.id[e] = hit_id_none();
     if (Q.along) Q.along[e] = INFINITY;
 }
 
 // The origin of the segment behind a hit: shade_frame's pm, from an evaluation of its own behind an optimisation barrier.  With pm live in
 // the evaluation that fills the record, the compiler forms some components of ng as -(-ng) (pm = p - ng * err wants -ng): the same number,
 // but where the hit's geometry is NaN (an origin at 1e300, a quadratic that overflowed) the other NaN sign -- and the record would no
-// longer be lg_intersect's bit for bit.  So the record's evaluation has query_kernel's uses and no others, and pm comes from this one.
-__device__ __forceinline__ double layer_opaque(double x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
+// longer be lg_intersect's bit for bit.  So the record's evaluation has query_kernel's uses and no others (store_hit, tilewalk.h), and pm
+// comes from this one.
 __device__ __forceinline__ V3 layer_next_origin(const DParams &P, const Ray &r, const Best &b) {
-    const Ray ray = ray_new(V3{layer_opaque(r.o.x), layer_opaque(r.o.y), layer_opaque(r.o.z)}, V3{layer_opaque(r.d.x), layer_opaque(r.d.y), layer_opaque(r.d.z)});
+    const Ray ray = ray_opaque(r);
     Shade sh;
     shade_frame(P, ray, b, sh);
     return sh.pm;
@@ -68,37 +55,19 @@ template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) layers_kernel(const DParams P, const LayersArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads();
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    const uint32_t lane = threadIdx.x & 63u;
+    TileWalk<FAST, LDSS> tw;
+    if (!tw.begin(P)) return;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
     const uint32_t K = Q.max_layers;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
     for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        const uint32_t tile = tw.next(P, final);
         if (tile == NO_TILE) break;
         unsigned long long i = (unsigned long long)tile * 64ull + lane;
         const bool active = i < Q.n;
         if (PERM && active) i = Q.perm[i];
-        Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
-        if (active) {
-            const double2 *r = reinterpret_cast<const double2 *>(Q.rays + 6ull * i);
-            const double2 a = r[0], b = r[1], c = r[2];
-            ray = ray_new(V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}); // Ray3::new: the direction as given
-        }
+        Ray ray = idle_ray();
+        if (active) ray = load_ray(Q.rays, i);
         // ---- the layer loop: segment j of every lane still alive, while the wave has one (j is uniform)
         bool alive = active;
         double T = 0.0, inside = 0.0;
@@ -106,24 +75,16 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         for (; j < K && wave_any(alive); ++j) {
             const unsigned long long e = (unsigned long long)j * Q.n + i;
             if (alive) {
-                Best b;
-                b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
-                walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+                Best b = fresh_best();
+                walk<LDSS, FAST, PRUNE>(P, ray, false, tw.stack, tw.stride, b, tw.scn, cnt, tw.arec);
                 if (b.ref == NO_HIT) {
                     layer_store_miss(Q, e);
                     alive = false; // a miss: the ray is finished
                 } else {
                     Shade sh;
                     shade_frame(P, ray, b, sh);
-                    const uint32_t pk = b.ref >> 30, idx = b.ref & PRIM_INDEX_MASK;
-                    const uint32_t prim = pk == PK_TRIANGLE ? idx - Q.tri_base[b.accel] : idx;
-                    const uint4 id = make_uint4(pk + 1u, prim, b.accel, (uint32_t)sh.mat); // lg_hit::kind: 1 sphere, 2 box, 3 triangle
-                    if (Q.hits) {
-                        uint4 *out = Q.hits + 6ull * e;
-                        out[0] = layer_bits2(b.t, sh.praw.x); out[1] = layer_bits2(sh.praw.y, sh.praw.z);
-                        out[2] = layer_bits2(sh.ng.x, sh.ng.y); out[3] = layer_bits2(sh.ng.z, sh.ns.x); out[4] = layer_bits2(sh.ns.y, sh.ns.z);
-                        out[5] = id;
-                    }
+                    const uint4 id = hit_id(b, sh, Q.tri_base);
+                    if (Q.hits) store_hit(Q.hits + 6ull * e, b, sh, id);
                     if (Q.id) Q.id[e] = id;
                     // T_0 = t_0, T_j = T_{j-1} + t_j: the 2^-36 steps are not added.  A NaN stays (here and in inside): which of two NaNs a
                     // sum returns is the operand order's, and that is the compiler's

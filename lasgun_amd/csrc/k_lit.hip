@@ -62,7 +62,8 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
 }
 
 // W2: the shadow pass under the call's lights.  The prologue, the LDS stacks and images and the launch bounds are the shadow form's of
-// wf_trace_kernel (k_wavefront.hip, SHADOW branch; read the two side by side).  Q.n_lights >= 1 (the host launches nothing for K == 0).
+// wf_trace_kernel (k_wavefront.hip, SHADOW branch; read the two side by side), in this file's own text and not over tilewalk.h: over it five
+// rows of this family measured slower than the parent's by more than its spread (profiles/tilewalk_account.md).  Q.n_lights >= 1 (the host launches nothing for K == 0).
 template <bool FAST, bool LDSS, bool PRUNE, bool PER_RAY>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) lit_shadow_kernel(const DParams P, const LitArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");

@@ -3,9 +3,9 @@
 // vertex the rule of the hit's material (the caller's table, read per lane) ends the path or forms segment j+1 -- mirrored, straight on or
 // refracted, bounce.h's arithmetic.  The ray stays in registers between the walks; only the planes asked for are written.
 //
-// The kernel is layers_kernel's shape (k_layers.hip) with a direction update: the same prologue, tile claim and wave-uniform loop over the
-// unchanged walk<LDSS, FAST, PRUNE>(.., any = false, ..) with a fresh Best per segment; the grid sized in query.cpp (traversal_grid), the
-// forms launched through travform.h, PERM as there.  A hit is resolved as query_kernel resolves it (shade_frame, the face number through
+// The kernel is layers_kernel's shape (k_layers.hip) with a direction update: tilewalk.h's prologue, tile cursor and record writer, and the
+// same wave-uniform loop over the unchanged walk<LDSS, FAST, PRUNE>(.., any = false, ..) with a fresh Best per segment; the grid sized in
+// query.cpp (traversal_grid), the forms launched through travform.h, PERM as there.  A hit is resolved as query_kernel resolves it (shade_frame, the face number through
 // tri_base); what the next ray needs (p, ng, ns) comes from a second evaluation behind an optimisation barrier (path_vertex says why).
 // What lives across the walks besides the ray: T (the running parameter), gain, count, medium and end -- 7 VGPRs; nothing is parked in
 // memory.  Lanes are not re-packed when paths end: a wave walks while any of its lanes is alive, a lane whose path has ended writes the
@@ -16,6 +16,7 @@
 // point: three 8-byte stores; along: one; count, end, gain, last and medium: once per ray, after the loop.  Every element of every plane
 // asked for is written by exactly one lane: no atomics, no pre-fill.  Lanes past the last ray (n % 64) walk nothing and write nothing.
 #include "travform.h"
+#include "tilewalk.h"
 #include "bounce.h"
 
 namespace lg {
@@ -48,22 +49,11 @@ struct PathsArgs {
     const uint32_t *perm;         // PERM forms only: [n], the ray walked in each slot
 };
 
-__device__ __forceinline__ uint4 path_bits2(double a, double b) {
-    const unsigned long long x = (unsigned long long)__double_as_longlong(a), y = (unsigned long long)__double_as_longlong(b);
-    return make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
-}
-
 // the planes of a vertex behind a path's last one, at element e: lg_intersect's miss record, its id words, +0s, +INF
 __device__ __forceinline__ void path_store_miss(const PathsArgs &Q, unsigned long long e) {
-    const uint4 none = make_uint4(0u, NO_HIT, NO_HIT, 0xFFFFFFFFu); // kind 0, prim / instance ~0, material -1
-    if (Q.hits) {
-        uint4 *out = Q.hits + 6ull * e;
-        out[0] = path_bits2(INFINITY, 0.0); out[1] = path_bits2(0.0, 0.0); out[2] = path_bits2(0.0, 0.0);
-        out[3] = path_bits2(0.0, 0.0); out[4] = path_bits2(0.0, 0.0);
-        out[5] = none;
-    }
+    if (Q.hits) store_hit_none(Q.hits + 6ull * e);
     if (Q.point) { double *pt = Q.point + 3ull * e; pt[0] = 0.0; pt[1] = 0.0; pt[2] = 0.0; }
-    if (Q.id) Q.id[e] = none;
+    if (Q.id) Q.id[e] = hit_id_none();
     if (Q.along) Q.along[e] = INFINITY;
 }
 
@@ -72,15 +62,11 @@ __device__ __forceinline__ void path_store_miss(const PathsArgs &Q, unsigned lon
 // ng or ns as -(-x) (the bounce wants -N and p - ng * 2^-36): the same number, but where the hit's geometry is NaN the other NaN sign --
 // and the record would no longer be lg_intersect's bit for bit (k_layers.hip, layer_next_origin, met this).  So the record's evaluation
 // has query_kernel's uses and no others, and the bounce reads this one.
-__device__ __forceinline__ double path_opaque(double x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 struct PathVertex {
     V3 d, p, ng, ns;
 };
 __device__ __forceinline__ PathVertex path_vertex(const DParams &P, const Ray &r, const Best &b) {
-    const Ray ray = ray_new(V3{path_opaque(r.o.x), path_opaque(r.o.y), path_opaque(r.o.z)}, V3{path_opaque(r.d.x), path_opaque(r.d.y), path_opaque(r.d.z)});
+    const Ray ray = ray_opaque(r);
     Shade sh;
     shade_frame(P, ray, b, sh);
     return PathVertex{ray.d, sh.praw, sh.ng, sh.ns};
@@ -90,37 +76,21 @@ template <bool FAST, bool LDSS, bool PRUNE, bool PERM>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) paths_kernel(const DParams P, const PathsArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads();
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    const uint32_t lane = threadIdx.x & 63u;
+    TileWalk<FAST, LDSS> tw;
+    if (!tw.begin(P)) return;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
     const uint32_t K = Q.max_bounces;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
     for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        const uint32_t tile = tw.next(P, final);
         if (tile == NO_TILE) break;
         unsigned long long i = (unsigned long long)tile * 64ull + lane;
         const bool active = i < Q.n;
         if (PERM && active) i = Q.perm[i];
-        Ray ray = ray_new(V3{0.0, 0.0, 0.0}, V3{0.0, 0.0, 1.0});
+        Ray ray = idle_ray();
         uint32_t medium = 0u;
         if (active) {
-            const double2 *r = reinterpret_cast<const double2 *>(Q.rays + 6ull * i);
-            const double2 a = r[0], b = r[1], c = r[2];
-            ray = ray_new(V3{a.x, a.y, b.x}, V3{b.y, c.x, c.y}); // Ray3::new: the direction as given
+            ray = load_ray(Q.rays, i);
             if (Q.start_medium) medium = Q.start_medium[i] & 1u;
         }
         // ---- the bounce loop: segment j of every lane still alive, while the wave has one (j is uniform)
@@ -130,9 +100,8 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
         for (; j < K && wave_any(alive); ++j) {
             const unsigned long long e = (unsigned long long)j * Q.n + i;
             if (alive) {
-                Best b;
-                b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
-                walk<LDSS, FAST, PRUNE>(P, ray, false, stack, stride, b, scn, cnt, arec);
+                Best b = fresh_best();
+                walk<LDSS, FAST, PRUNE>(P, ray, false, tw.stack, tw.stride, b, tw.scn, cnt, tw.arec);
                 if (b.ref == NO_HIT) {
                     path_store_miss(Q, e);
                     end = PATH_END_ESCAPED; // a segment missed: the ray in the registers is that segment
@@ -140,15 +109,8 @@ __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES
                 } else {
                     Shade sh;
                     shade_frame(P, ray, b, sh);
-                    const uint32_t pk = b.ref >> 30, idx = b.ref & PRIM_INDEX_MASK;
-                    const uint32_t prim = pk == PK_TRIANGLE ? idx - Q.tri_base[b.accel] : idx;
-                    const uint4 id = make_uint4(pk + 1u, prim, b.accel, (uint32_t)sh.mat); // lg_hit::kind: 1 sphere, 2 box, 3 triangle
-                    if (Q.hits) {
-                        uint4 *out = Q.hits + 6ull * e;
-                        out[0] = path_bits2(b.t, sh.praw.x); out[1] = path_bits2(sh.praw.y, sh.praw.z);
-                        out[2] = path_bits2(sh.ng.x, sh.ng.y); out[3] = path_bits2(sh.ng.z, sh.ns.x); out[4] = path_bits2(sh.ns.y, sh.ns.z);
-                        out[5] = id;
-                    }
+                    const uint4 id = hit_id(b, sh, Q.tri_base);
+                    if (Q.hits) store_hit(Q.hits + 6ull * e, b, sh, id);
                     if (Q.id) Q.id[e] = id;
                     if (Q.point) { double *pt = Q.point + 3ull * e; pt[0] = sh.praw.x; pt[1] = sh.praw.y; pt[2] = sh.praw.z; } // (the record's own p)
                     // T_0 = t_0, T_j = T_{j-1} + t_j: the 2^-36 steps are not added.  A NaN stays (here and in gain): which of two NaNs an

@@ -5,7 +5,9 @@
 // (kcommon.h: banded by XCD where the scene sits in LDS, one head word otherwise), a per-lane LDS stack, the scene image copied into LDS
 // once per workgroup where the accel keeps it there.  A ray is 48 bytes in, read as three 16-byte loads; a closest hit is 96 bytes out
 // (lg_hit), written as six 16-byte stores -- a wave writes 6 KiB in one piece; an occlusion answer is one byte.  Lanes past the last ray
-// (n % 64) walk nothing and write nothing.
+// (n % 64) walk nothing and write nothing.  The prologue, the tile loop and the record writer are what tilewalk.h holds for the family's other
+// tiled kernels; this file keeps its own text of them: over the shared header its rows measured slower than the parent's by more than
+// its spread (profiles/tilewalk_account.md, profiles/tilewalk_ab.jsonl).
 //
 // PERM (lg_accel_set_query_order(1)): the tiles are cut from the SORTED order of the rays (k_sort.hip) -- slot s = tile * 64 + lane walks
 // ray i = perm[s], read from rays[6i] and answered in hits[6i] / occluded[i]: no gathered copy of the rays, no scatter pass over the hits

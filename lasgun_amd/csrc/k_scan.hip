@@ -3,8 +3,9 @@
 // the beam -- d[c] = (M[3c]*b.x + M[3c+1]*b.y) + M[3c+2]*b.z, f64, in this order, nothing fused (-ffp-contract=off) -- and is never
 // written out as a ray; what comes back is not lg_hit records but only the planes asked for.
 //
-// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
-// launched through travform.h.  The walk is closest hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged, and the hit is resolved
+// The kernel's prologue and tile loop are those of tilewalk.h, which the tiled kernels of the query family share, in this file's own text:
+// over the shared header rows of this family measured slower than the parent's by more than its spread (profiles/tilewalk_account.md).
+// The grid is sized in query.cpp (traversal_grid) and the forms are launched through travform.h.  The walk is closest hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged, and the hit is resolved
 // as query_kernel resolves it (shade_frame, the face number through tri_base) -- but only where point, normal or id is asked for: range,
 // hits and nearest need b.t and b.ref alone.  What differs is the work item, and there are two (POSE):
 //   beam lanes (POSE = false): a tile is one POSE x 64 consecutive BEAMS, tile = pose * beam_tiles + beam_block.  The origin and the frame

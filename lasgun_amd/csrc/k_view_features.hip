@@ -3,7 +3,8 @@
 // features_kernel (k_features.hip) with the camera a row of a table (DView; view_ray.h, as k_views.hip reads it) instead of eight fields of
 // DParams, and one more accumulator triple.
 //
-// The prologue, the tile claim, the LDS image and the stacks are features_kernel's; the grid is sized in query.cpp (traversal_grid) and the
+// The prologue, the tile claim, the LDS image and the stacks are features_kernel's as they stood before tilewalk.h, in this file's own text
+// (over the shared header this family's rows measured slower than the parent's by more than its spread, profiles/tilewalk_account.md); the grid is sized in query.cpp (traversal_grid) and the
 // forms are launched through travform.h.  The walk is closest hit: walk<LDSS, FAST, PRUNE>(.., any = false, ..), unchanged.  A tile is
 // global pixel tile G = v * tiles_per_view + t of view_pixel -- an 8 x 8 tile of film v -- and a lane is one PIXEL, looping over its samples
 // s = 0 .. S-1: the wave walks sample s together, and each pixel's sums come out in sample order with no cross-lane step.  v is the same in

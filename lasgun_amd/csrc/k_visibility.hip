@@ -1,7 +1,7 @@
 // lasgun_amd/csrc/k_visibility.hip -- visibility matrices (include/lasgun_hip.h, lg_visibility*): occlusion between two point sets, the
 // segments made in registers as the render's shadow pass makes its own (k_wavefront.hip: hit point and light position), the answer bit-packed.
 //
-// The kernel's prologue and tile loop repeat query_kernel's (k_query.hip); the grid is sized in query.cpp (traversal_grid) and the forms are
+// The kernel's prologue and tile cursor are tilewalk.h's; the grid is sized in query.cpp (traversal_grid) and the forms are
 // launched through travform.h.  The walk is any-hit: walk<LDSS, FAST, PRUNE>(.., any = true, ..), unchanged.  What differs is the work
 // item: an 8 x 8 BLOCK of the matrix.  Lane l of the wave that claimed block (ti, tj) walks the segment from[8 ti + (l >> 3)] ->
 // to[8 tj + (l & 7)]: a wave reads 8 + 8 points (384 bytes) where lg_occluded reads 64 rays (3 KiB), and its 64 segments share 8 origins
@@ -13,6 +13,7 @@
 // atomics and no pre-clear -- and adds the byte's popcount to blocked[row] (zeroed on the same stream ahead of the launch, query.cpp;
 // integer addition: the counts do not depend on the order the blocks finish in).
 #include "travform.h"
+#include "tilewalk.h"
 
 namespace lg {
 
@@ -30,37 +31,22 @@ template <bool FAST, bool LDSS, bool PRUNE>
 __global__ void __launch_bounds__(LDSS ? LG_LDSS_BLOCK : LG_BLOCK, LG_TRAV_WAVES_PER_SIMD) visibility_kernel(const DParams P, const VisibilityArgs Q) {
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t ntiles = P.ntiles;
-    if (ntiles == 0u) return; // (uniform: before the LDS copy and its barrier)
-    uint32_t *stack = lds_stack + tid;
-    constexpr uint32_t stride = LDSS ? LG_LDSS_BLOCK : LG_BLOCK;
-    const uint4 *scn = nullptr;
-    if (LDSS) {
-        uint4 *dst = reinterpret_cast<uint4 *>(lds_stack + P.stack_depth * stride);
-        copy_to_lds(dst, reinterpret_cast<const uint4 *>(P.lds_image), P.lds_image_n16, tid, stride);
-        __syncthreads();
-        scn = dst;
-    }
-    const uint4 *const arec = (LDSS || FAST) ? nullptr : load_accel_image(P, P.stack_depth * LG_BLOCK);
+    const uint32_t lane = threadIdx.x & 63u;
+    TileWalk<FAST, LDSS> tw;
+    if (!tw.begin(P)) return;
     Counters cnt = {0, 0, 0, 0, 0, 0, 0, 0, 0}; (void)cnt;
-    if (!wave_has_work(ntiles)) return;
-    uint32_t band = LDSS ? xcc_id() : 0u, bands_left = TILE_HEADS;
     for (bool final = false; !final;) {
-        uint32_t tile;
-        if (LDSS) tile = claim_tile(P.tile_counter, ntiles, band, bands_left, final);
-        else tile = claim_tile_single(P.tile_counter, ntiles, final);
+        const uint32_t tile = tw.next(P, final);
         if (tile == NO_TILE) break;
         const uint32_t ti = tile / Q.tiles_j, tj = tile - ti * Q.tiles_j;
         const unsigned long long row = 8ull * ti + (lane >> 3), col = 8ull * tj + (lane & 7u);
         const bool active = row < Q.n_from && col < Q.n_to;
-        Best b;
-        b.ref = NO_HIT; b.t = INFINITY; b.accel = 0u;
+        Best b = fresh_best();
         if (active) {
             const double *f = Q.from + 3ull * row, *t = Q.to + 3ull * col;
             const V3 o{f[0], f[1], f[2]};
             const Ray ray = ray_new(o, V3{t[0] - o.x, t[1] - o.y, t[2] - o.z}); // the segment from -> to: three subtractions, direction as it comes out
-            walk<LDSS, FAST, PRUNE>(P, ray, true, stack, stride, b, scn, cnt, arec);
+            walk<LDSS, FAST, PRUNE>(P, ray, true, tw.stack, tw.stride, b, tw.scn, cnt, tw.arec);
         }
         const unsigned long long mask = __builtin_amdgcn_ballot_w64(active && b.t < 1.0); // point.rs:49
         if ((lane & 7u) != 0u || row >= Q.n_from) continue;

@@ -18,7 +18,9 @@
 // bodies.  The bodies were once repeated per family for the register budget of these kernels; measured on the shared form
 // (profiles/level0_shared_kernel_resources_diff.txt): every kernel over them keeps its vgpr, sgpr, LDS and workgroup size.  The radiance
 // and film kernels (k_radiance.hip) keep the text these bodies were made from: over the bodies three of their rows measured slower
-// than the parent's by more than its own spread (profiles/level0_shared_ab.jsonl).
+// than the parent's by more than its own spread (profiles/level0_shared_ab.jsonl).  The closest body's prologue and tile loop are what
+// tilewalk.h holds for the tiled query kernels, in this file's own text: over the shared header gather, scatter and lit rows measured
+// slower than the parent's by more than its spread (profiles/tilewalk_account.md), and the body is one for all its families.
 #pragma once
 #include "wflevel.h"
 

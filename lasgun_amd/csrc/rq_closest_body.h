@@ -1,6 +1,7 @@
 // lasgun_amd/csrc/rq_closest_body.h -- the body of W1 of level 0 of a radiance query (k_radiance.hip), included once into each of its two
 // kernels: rq_closest_kernel (Q: RadianceArgs, a finished ray goes to radiance[]) and rf_closest_kernel (Q: FilmArgs, it goes to a film);
-// rq_finish is overloaded on Q.  The text level0.h's l0_closest_body was made from; this family keeps it (k_radiance.hip says why).
+// rq_finish is overloaded on Q.  The text level0.h's l0_closest_body was made from; this family keeps it (k_radiance.hip says why),
+// and keeps it whole: over tilewalk.h's prologue and cursor three radiance and film rows measured slower (profiles/tilewalk_account.md).
 // In scope: template parameters FAST, LDSS, PRUNE, PERM; kernel parameters P (DParams) and Q.
     static_assert(!(FAST && LDSS), "the LDS-resident scene holds the reference tree only");
     static_assert(!(FAST && PRUNE), "the fast mode prunes its own trees by its own rule");

@@ -9,6 +9,7 @@ import re
 import sys
 
 import numpy as np
+import tilewalk_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -100,7 +101,8 @@ def test_the_kernel_is_a_device_kernel_of_its_own():
     src = read("lasgun_amd", "csrc", "k_directions.hip")
     assert re.search(r"__global__ void [^\n]*\bdirections_kernel\(", src)
     assert re.search(r"walk<LDSS, FAST, PRUNE>\(P, ray, true,", src)
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "atomicAdd(" in src
+    tilewalk_text.over_tilewalk(src)
+    assert "atomicAdd(" in src
     assert "k_directions.o" in read("lasgun_amd", "csrc", "Makefile")
     host = read("lasgun_amd", "csrc", "query.cpp")
     body = host[host.index("static void enqueue_open_directions("):host.index('extern "C" int lg_open_directions(')]

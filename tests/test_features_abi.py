@@ -7,6 +7,7 @@ import ctypes
 import os
 import re
 import sys
+import tilewalk_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -113,9 +114,10 @@ def test_the_kernel_is_a_device_kernel_of_its_own():
     src = read("lasgun_amd", "csrc", "k_features.hip")
     assert re.search(r"__global__ void [^\n]*\bfeatures_kernel\(", src)
     assert re.search(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", src)
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "pixel_of(P, tile, lane)" in src and "camera_ray(P, px.x, px.y, s)" in src
-    assert "shade_frame(" in src and "copy_to_lds(" in src and "load_accel_image(" in src and "Q.tri_base[" in src
-    assert "atomic" not in src.replace("claim_tile", ""), "the sums need no cross-lane or cross-wave step"
+    tilewalk_text.over_tilewalk(src)  # the claim, the LDS copy, the accel records and the id word: the shared header's
+    assert "pixel_of(P, tile, lane)" in src and "camera_ray(P, px.x, px.y, s)" in src
+    assert "shade_frame(" in src and "id0 = hit_id(b, sh, Q.tri_base);" in src and "uint4 id0 = hit_id_none();" in src
+    assert "atomic" not in src, "the sums need no cross-lane or cross-wave step"
     assert "k_features.o" in read("lasgun_amd", "csrc", "Makefile")
     host = read("lasgun_amd", "csrc", "query.cpp")
     body = host[host.index("static void enqueue_features("):host.index('extern "C" int lg_capture_features(')]

@@ -33,7 +33,7 @@ G = la.api
 ERR = 2.220446049250313e-16 * 65536.0  # the shading offset, 2^-36 (integrate.rs:40)
 FULL = 1031                            # points and directions per scene: 17 blocks of 64 points x 129 bytes of 8 directions
 GRID = (48, 36)                        # the coarse camera grid the points are first hits of
-SHAPES = [(63, 7), (64, 8), (65, 9), (1, 64), (129, 1), (17, 130), (257, 1031), (FULL, FULL)]
+SHAPES = [(63, 7), (64, 8), (65, 9), (1, 64), (63, 1), (65, 1), (129, 1), (17, 130), (257, 1031), (FULL, FULL)]
 BELOW, BLOCKED, OPEN = 0, 1, 2
 
 

@@ -163,7 +163,7 @@ def test_every_traversal_form_gives_the_contracts_planes(name, form):
 
 
 # ---- 2: rectangles -----------------------------------------------------------------------------------------------------------------------
-RECTS = [(0, 0, 96, 64), (3, 5, 20, 14), (8, 8, 16, 16), (0, 31, 96, 32), (47, 0, 48, 64)]
+RECTS = [(0, 0, 96, 64), (3, 5, 20, 14), (8, 8, 16, 16), (0, 31, 96, 32), (47, 0, 48, 64), (41, 29, 50, 36), (41, 29, 54, 34)]  # (the last two: 63 and 65 pixels)
 
 
 @pytest.mark.parametrize("name", ["cornell_glass", "instanced"])

@@ -288,7 +288,7 @@ def test_sizes(ss):
     ref_a, ref_d = G.capture_rays(accel, rays, w, h, samples=samples, rgb=True)
     for order in (0, 1):
         G.set_query_order(accel, order)
-        for n in (0, 1, 7, 64, 65, 4097):
+        for n in (0, 1, 7, 63, 64, 65, 4097):
             film = np.full((h, w, 4), 0xA5, dtype=np.uint8)
             rgb = np.full((h, w, 3), -7.0)
             G.capture_rays(accel, rays[: n * samples], w, h, samples=samples, into=(film, rgb))

@@ -155,6 +155,15 @@ def test_every_traversal_form_gives_identical_bytes(name, builder):
     fits = G.set_lds_scene(accel, False)
     ref_h, ref_o = G.intersect(accel, rays).tobytes(), G.occluded(accel, rays)
     assert ref_h and ref_o.any() and not ref_o.all()
+    mid = (1 << 19) - 31  # (where the coherent rays of the batch both hit and miss)
+
+    def small(form):
+        """Launches of one tile, full or not, and of two: a ray's answer does not depend on the batch it comes in."""
+        for n in (1, 63, 64, 65):
+            assert G.intersect(accel, rays[mid:mid + n]).tobytes() == ref_h[96 * mid:96 * (mid + n)], (name, form, n)
+            assert np.array_equal(G.occluded(accel, rays[mid:mid + n]), ref_o[mid:mid + n]), (name, form, n)
+
+    small("reference")
     forms = [("prune", lambda: G.set_prune(accel, True))]
     if fits:
         forms += [("lds", lambda: (G.set_prune(accel, False), G.set_lds_scene(accel, True))),
@@ -164,6 +173,7 @@ def test_every_traversal_form_gives_identical_bytes(name, builder):
         setup()
         assert G.intersect(accel, rays).tobytes() == ref_h, (name, form)
         assert np.array_equal(G.occluded(accel, rays), ref_o), (name, form)
+        small(form)
         checked.append(form)
     if name != "spheres":
         G.set_prune(accel, None)
@@ -175,6 +185,7 @@ def test_every_traversal_form_gives_identical_bytes(name, builder):
         else:
             assert G.intersect(accel, rays).tobytes() == ref_h, (name, "fast")
             assert np.array_equal(G.occluded(accel, rays), ref_o), (name, "fast")
+            small("fast")
             checked.append("fast")
             G.set_mode(accel, False)
     assert checked

@@ -170,7 +170,7 @@ def test_three_mixed_cameras_equal_the_cpu_oracles_hits(name, builder, cameras):
 
 
 # ---- 3: film shapes with guard bytes ------------------------------------------------------------------------------------------------------
-SHAPES = [(1, 1), (7, 9), (8, 8), (9, 8), (13, 11), (64, 1), (1, 64)]
+SHAPES = [(1, 1), (7, 9), (8, 8), (9, 8), (13, 5), (13, 11), (64, 1), (1, 64)]
 SUBSETS = [(p,) for p in PLANES] + [("depth", "id", "point"), PLANES]
 
 

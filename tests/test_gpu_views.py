@@ -96,7 +96,7 @@ def test_three_cameras_in_one_call_give_the_oracles_renders(name, builder, specu
 
 
 # ---- 4: shapes where the mapping can go wrong -------------------------------------------------------------------------------------------------
-SHAPES = [(1, 1), (7, 9), (8, 8), (9, 8), (13, 11), (64, 1), (1, 64)]
+SHAPES = [(1, 1), (7, 9), (8, 8), (9, 8), (13, 5), (13, 11), (64, 1), (1, 64)]
 GUARD = 64
 
 

@@ -36,7 +36,7 @@ RADIUS = 1.0                           # the to points' sphere, in half-diagonal
 SCENES = {"cornell_glass": FORM_SCENES[0][1],                 # a sphere, a cube and the shell's five planes: resident in LDS
           "instanced": lambda api: S.instanced_scene(api),    # one mesh three times in scaled, rotated groups nested two deep; two lights
           "mesh_glass": FORM_SCENES[1][1]}                    # the torus in a scaled, rotated group: the scene the fast mode is run on
-SHAPES = [(7, 9), (8, 8), (9, 7), (64, 1), (1, 64), (17, 130), (257, 1031), (FULL, FULL)]
+SHAPES = [(7, 9), (8, 8), (9, 7), (5, 13), (64, 1), (1, 64), (17, 130), (257, 1031), (FULL, FULL)]
 
 
 def set_form(accel, form):

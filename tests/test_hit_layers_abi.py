@@ -10,6 +10,7 @@ import re
 import sys
 
 import numpy as np
+import tilewalk_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -128,7 +129,10 @@ def test_the_kernel_is_a_device_kernel_of_its_own_over_the_unchanged_walk():
     src = read("lasgun_amd", "csrc", "k_layers.hip")
     assert re.search(r"__global__ void [^\n]*\blayers_kernel\(", src)
     assert len(re.findall(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", src)) == 1, "closest hit"
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "shade_frame(" in src and "tri_base" in src and "wave_any(alive)" in src
+    tilewalk_text.over_tilewalk(src)  # the prologue, the cursor, the record, the id word and the barrier helper: the shared header's
+    assert "shade_frame(" in src and "const uint4 id = hit_id(b, sh, Q.tri_base);" in src and "wave_any(alive)" in src
+    assert "if (Q.hits) store_hit(Q.hits + 6ull * e, b, sh, id);" in src and "if (Q.hits) store_hit_none(Q.hits + 6ull * e);" in src
+    assert "const Ray ray = ray_opaque(r);" in src, "pm comes from an evaluation of its own behind the barrier"
     assert "return sh.pm;" in src and "ray_new(layer_next_origin(P, ray, b), ray.d)" in src, "the next segment starts at shade_frame's pm, the direction kept"
     assert "atomic" not in src.split("#include")[1], "no atomics: every element is written by exactly one lane"
     assert "trav_launch<LayersKernels>" in src and "trav_occupancy<LayersKernels>" in src and "trav_set_lds_limit<LayersKernels>" in src

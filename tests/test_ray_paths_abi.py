@@ -11,6 +11,7 @@ import re
 import sys
 
 import numpy as np
+import tilewalk_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -167,8 +168,10 @@ def test_the_kernel_is_a_device_kernel_of_its_own_over_the_unchanged_walk():
     src = read("lasgun_amd", "csrc", "k_paths.hip")
     assert re.search(r"__global__ void [^\n]*\bpaths_kernel\(", src) and "template <bool FAST, bool LDSS, bool PRUNE, bool PERM>" in src
     assert len(re.findall(r"walk<LDSS, FAST, PRUNE>\(P, ray, false,", src)) == 1, "closest hit"
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "tri_base" in src and "wave_any(alive)" in src
-    assert '#include "bounce.h"' in src and src.count("shade_frame(P, ray, b, sh)") == 2 and 'asm volatile("" : "+v"(x))' in src
+    tilewalk_text.over_tilewalk(src)  # the prologue, the cursor, the record, the id word and the barrier helper: the shared header's
+    assert "const uint4 id = hit_id(b, sh, Q.tri_base);" in src and "wave_any(alive)" in src
+    assert "if (Q.hits) store_hit(Q.hits + 6ull * e, b, sh, id);" in src and "if (Q.hits) store_hit_none(Q.hits + 6ull * e);" in src
+    assert '#include "bounce.h"' in src and src.count("shade_frame(P, ray, b, sh)") == 2 and "const Ray ray = ray_opaque(r);" in src
     assert "bounce_next(action, ior, v.d, v.p, v.ng, Q.use_ns ? v.ns : v.ng, medium)" in src, "the next ray from the second evaluation"
     assert "gain = gain != gain ? gain : gain * rgain" in src and "T != T ? T : T + b.t" in src, "a NaN stays: selected, not left to the operation"
     assert "atomic" not in src.split("#include")[1], "no atomics: every element is written by exactly one lane"

@@ -6,6 +6,7 @@ import ctypes
 import os
 import re
 import sys
+import tilewalk_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -89,7 +90,8 @@ def test_the_kernel_is_a_device_kernel_of_its_own():
     src = read("lasgun_amd", "csrc", "k_visibility.hip")
     assert re.search(r"__global__ void [^\n]*\bvisibility_kernel\(", src)
     assert re.search(r"walk<LDSS, FAST, PRUNE>\(P, ray, true,", src)
-    assert "claim_tile(" in src and "claim_tile_single(" in src and "__builtin_amdgcn_ballot_w64(" in src
+    tilewalk_text.over_tilewalk(src)
+    assert "__builtin_amdgcn_ballot_w64(" in src
     assert "k_visibility.o" in read("lasgun_amd", "csrc", "Makefile")
     host = read("lasgun_amd", "csrc", "query.cpp")
     body = host[host.index("static void enqueue_visibility("):host.index('extern "C" int lg_visibility(')]
