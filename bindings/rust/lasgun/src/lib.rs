@@ -284,6 +284,18 @@ pub struct Closest<'a> {
     pub point: Option<&'a mut [[f64; 3]]>,
     pub id: Option<&'a mut [[u32; 4]]>,
 }
+pub use sys::lg_nearest_out as NearestOut;
+/// The planes `Accel::nearest` fills: `touch` and `count` one row per point, `distance` / `point` / `id` slot-major (k * points rows, slot j
+/// of point i at j * points + i); `None` = not asked for; not all five.  (Like the rest of this crate: uncompiled here -- no Rust toolchain --,
+/// held to the C header textually by tests/test_rust_bindings.py and tests/test_nearest_abi.py.)
+#[derive(Default)]
+pub struct Nearest<'a> {
+    pub touch: Option<&'a mut [u8]>,
+    pub count: Option<&'a mut [u32]>,
+    pub distance: Option<&'a mut [f64]>,
+    pub point: Option<&'a mut [[f64; 3]]>,
+    pub id: Option<&'a mut [[u32; 4]]>,
+}
 pub use sys::lg_light as Light;
 pub use sys::lg_light_set as LightSet;
 pub use sys::lg_lit_out as LitOut;
@@ -602,6 +614,35 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `closest_points` states (the library checks what HIP can tell it).
     pub unsafe fn closest_points_device(&self, dev_points: *const f64, n: usize, radius: f64, dev_out: &sys::lg_closest_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_closest_points_device(self.ptr, dev_points, n, radius, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// Proximity queries (`lg_nearest`): for each point (world space), under `radii[i]` (`None`: the shared `radius`; `f64::INFINITY` = no
+    /// limit), the `k` nearest primitives in ascending (squared distance, key) order, the count of ALL primitives within the radius and
+    /// whether any is.  `touch` alone leaves a point's walk at its first contact; `count` has to meet every primitive within the radius.
+    /// One candidate per primitive, `closest_points`' own: slot 0 under a shared radius is its answer, byte for byte.
+    pub fn nearest(&self, points: &[[f64; 3]], radii: Option<&[f64]>, radius: f64, k: u32, out: Nearest) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_nearest_out>() == 40);
+        let n = points.len();
+        let nk = n * k as usize;
+        assert!(k <= sys::LG_NEAREST_MAX_K && radii.map_or(true, |r| r.len() == n), "nearest: k <= LG_NEAREST_MAX_K, one radius per point");
+        assert!(out.touch.as_ref().map_or(true, |p| p.len() == n) && out.count.as_ref().map_or(true, |p| p.len() == n)
+                && out.distance.as_ref().map_or(true, |p| p.len() == nk) && out.point.as_ref().map_or(true, |p| p.len() == nk)
+                && out.id.as_ref().map_or(true, |p| p.len() == nk), "nearest: touch and count have points.len() rows, a slot plane k times as many");
+        let o = sys::lg_nearest_out {
+            touch: out.touch.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            count: out.count.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            distance: out.distance.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            point: out.point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            id: out.id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+        };
+        let r = radii.map_or(std::ptr::null(), |r| r.as_ptr());
+        if unsafe { sys::lg_nearest(self.ptr, points.as_ptr() as *const f64, r, n, radius, k, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `nearest` for points (and radii, or null) in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `nearest` states (the library checks what HIP can tell it).
+    pub unsafe fn nearest_device(&self, dev_points: *const f64, dev_radii: *const f64, n: usize, radius: f64, k: u32, dev_out: &sys::lg_nearest_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_nearest_device(self.ptr, dev_points, dev_radii, n, radius, k, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     fn attr_out(n: usize, out: Attributes, what: &str) -> sys::lg_attr_out {
         const _: () = assert!(std::mem::size_of::<sys::lg_attr_out>() == 56);

@@ -400,6 +400,34 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void closest_points_device(const double *dev_points, size_t n, double radius, const lg_closest_out &dev_out, void *hip_stream) const {
         if (lg_closest_points_device(h_, dev_points, n, radius, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // proximity queries (lg_nearest): for each point (world space), under radii[i] (`radii` null: the shared `radius`), the k nearest
+    // primitives in ascending (squared distance, key) order, slot-major -- element (j, i) at j * points + i --, the count of ALL primitives
+    // within the radius and whether any is.  A null member is not asked for; not all five.  touch alone leaves at the first contact; count
+    // has to meet every primitive within the radius.  One candidate per primitive, closest_points' own: slot 0 is its answer
+    struct Nearest {
+        std::vector<uint8_t> *touch = nullptr;                      // [points]
+        std::vector<uint32_t> *count = nullptr;                     // [points]
+        std::vector<double> *distance = nullptr;                    // [k * points]
+        std::vector<std::array<double, 3>> *point = nullptr;        // [k * points]
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;         // [k * points]
+    };
+    void nearest(const std::vector<std::array<double, 3>> &points, const std::vector<double> *radii, uint32_t k, const Nearest &out, double radius = INFINITY) const {
+        static_assert(sizeof(lg_nearest_out) == 40, "lg_nearest_out: five pointers");
+        const size_t n = points.size();
+        if (radii && radii->size() != n) throw Error("nearest: one radius per point");
+        if (k > LG_NEAREST_MAX_K) throw Error("nearest: k is beyond LG_NEAREST_MAX_K");
+        const size_t nk = n * k;
+        lg_nearest_out o{};
+        if (out.touch) { out.touch->assign(n, 0); o.touch = out.touch->data(); }
+        if (out.count) { out.count->assign(n, 0u); o.count = out.count->data(); }
+        if (out.distance) { out.distance->assign(nk, INFINITY); o.distance = out.distance->data(); }
+        if (out.point) { out.point->assign(nk, {0.0, 0.0, 0.0}); o.point = nk ? (*out.point)[0].data() : nullptr; }
+        if (out.id) { out.id->assign(nk, {0u, ~0u, ~0u, ~0u}); o.id = nk ? (*out.id)[0].data() : nullptr; }
+        if (lg_nearest(h_, points.empty() ? nullptr : points[0].data(), radii ? radii->data() : nullptr, n, radius, k, &o)) throw Error(lg_last_error());
+    }
+    void nearest_device(const double *dev_points, const double *dev_radii, size_t n, double radius, uint32_t k, const lg_nearest_out &dev_out, void *hip_stream) const {
+        if (lg_nearest_device(h_, dev_points, dev_radii, n, radius, k, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // lit scatter (lg_scatter_lit): scatter() under lights that come with the call -- `lights` shared by every ray (per_ray false: K records)
     // or a table per ray (per_ray true: rays.size() * K records, ray i's at i * K), `ambient` in the scene's ambient colour's place; the
     // scene's own lights play no part.  Beside scatter()'s planes: terms = every light's own term of direct ([ray * K + k], +0.0 where it is

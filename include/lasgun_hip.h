@@ -1301,7 +1301,8 @@ int lg_hit_attributes_of_device(const lg_accel *, const double *dev_rays, const 
  * accel), except that an accel's first call builds and uploads the query's own tables after a synchronise.  The host form is
  * synchronous: the points go up, the planes come back into staging and are copied out at the end, so an error on the way leaves the
  * caller's arrays as they were.
- * Out of scope: per-point radii, the k nearest, a normal at the closest point, the sorted order, a multi-device split. */
+ * Out of scope: per-point radii, the k nearest, a normal at the closest point, the sorted order, a multi-device split (per-point radii
+ * and the k nearest are lg_nearest's, below). */
 typedef struct lg_closest_out {
     double   *distance;        /* [n]     sqrt(d2) of the winner, +INF where nothing is admissible */
     double   *point;           /* [n][3]  the winner's closest point, world space; +0.0 for a miss */
@@ -1315,6 +1316,70 @@ int lg_scene_closest_gate(const lg_scene *, double *shrink, int cap);
  * call.  -1 on an error. */
 #define LG_CLOSEST_MAX_DEPTH 64
 int lg_scene_closest_depth(const lg_scene *);
+
+/* Proximity queries: for each of n POINTS, under a radius of its own, the k NEAREST primitives of the scene in order, how many
+ * primitives lie within the radius at all, and whether any does -- sphere-set collision checks (a robot or a character as spheres of
+ * different radii against the world: `touch` alone), contact generation and clearance (a probe near an edge or a corner touches several
+ * primitives: all of the nearest few, and how many lie within the margin).  An EXTRA, as lg_closest_points is; the contract is that
+ * query's arithmetic kept for more than one winner, and the answer is that arithmetic over ALL primitives of the scene, bit for bit.
+ * Candidates: one candidate per primitive of the scene: its (d2, x, key) exactly as lg_closest_points defines them -- W_A, Ericson's
+ *   steps 1-7 for a triangle, a box as the best of its twelve triangles (ONE candidate per box), a sphere by centre and pole.  The key is
+ *   instance << 34 | kind << 32 | prim in lg_hit's numbering.  The sphere gate (lg_scene_closest_gate) and the depth rule
+ *   (lg_scene_closest_depth) are lg_closest_points' own.
+ * Radius: the radius r_i of point i is radii[i] where `radii` is not NULL, otherwise `radius`.  Where radii is given, radius is not read
+ *   and not checked.  A per-point radius that is NaN or < 0 makes that point a miss -- not an error: a device array cannot be checked
+ *   before the launch, and the host form behaves the same.  -0.0 is zero.  A shared radius that is NaN or negative is an error, as in
+ *   lg_closest_points.
+ * Admissible and order: a candidate is admissible iff d2 <= r_i*r_i && d2 < +INF, r_i*r_i one f64 product (a NaN never is).  A point
+ *   with a non-finite coordinate has no admissible candidate.  The admissible candidates are ordered ascending by (d2, key): the squared
+ *   distance first, an exact tie by the key.
+ * Slots: slot j (0-based) holds the j-th candidate of that order for j < min(count, k): distance = sqrt(d2), point = x, id = kind, prim,
+ *   instance, material as in lg_closest_points, its material rule included.  Every other slot holds the miss row: distance = +INF,
+ *   point = +0.0, id = 0, ~0, ~0, -1.  Hence, for a shared radius, slot 0 is lg_closest_points' planes byte for byte.  The slot planes are
+ *   slot-major: element (j, i) at j*n + i, as lg_hit_layers' planes are layer-major.
+ * count is the number of admissible candidates -- ALL of them, not capped at k; touch is 1 iff count > 0, else 0.
+ * Writes: every element of every plane asked for is written, whatever the buffers held, by exactly one lane: no atomics, no pre-fill.
+ * Traversal: the accel's traversal mode, lg_accel_set_query_order, lights and materials' parameters play no part: the same bytes in every
+ *   mode; a scene of more than 32 lights is accepted.
+ * k: 0 .. LG_NEAREST_MAX_K.  k == 0 is legal iff no slot plane (distance, point, id) is asked for; k > 0 with no slot plane is legal, and
+ *   k then plays no part.
+ * What it costs follows from the planes asked for.  touch alone: a point's walk ends at its first admissible candidate.  Slot planes
+ *   without count: the walk leaves out what provably lies beyond the k-th best so far and beyond r_i.  count, with or without slot
+ *   planes: every admissible candidate has to be met, so only r_i prunes -- at an infinite radius this visits every primitive for every
+ *   point, by definition.
+ * Limits and errors: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors (non-zero,
+ *   lg_last_error, nothing launched, no output touched), for n > 0, in this order: a NULL accel, points or out; all five planes NULL; a
+ *   shared radius that is NaN or negative (+INF: no limit); k > LG_NEAREST_MAX_K, or k == 0 with a slot plane; n > (2^32 - 1) * 64; n * k
+ *   or a plane's byte size that does not fit size_t; a scene the gate refuses; a scene whose trees are too deep for the per-lane stack;
+ *   a scene whose stack plus lists exceed the LDS a workgroup may have (below; refused, never truncated); in the device form also a
+ *   pointer that is not device memory of the accel's device or is misaligned (touch 1 byte, count 4, points, radii, distance and point 8;
+ *   id 16), or a buffer that ends beyond its allocation.
+ * LDS: a workgroup of 256 lanes keeps per lane a stack of lg_scene_closest_depth entries of 8 bytes and, with a slot plane, a list of k
+ *   entries of 20 bytes (d2, key, the primitive's leaf slot: a winner's x is evaluated again from it at the end, the same bits):
+ *   lg_scene_nearest_lds(scene, k) = 256 * (8 * depth + 20 * k) bytes; no device is needed; 0 on an error (a NULL scene, k beyond
+ *   LG_NEAREST_MAX_K).  The limit is 160 KiB on gfx950, and the call refuses exactly where lg_scene_nearest_lds(scene, k) exceeds it, k
+ *   taken as 0 where no slot plane is asked for.  LG_NEAREST_MAX_K is 8 because 64 stack entries of 8 bytes and 8 list entries of 16
+ *   bytes fill 160 KiB for 256 lanes; this list entry is 4 bytes wider, so a scene of depth 64 is answered up to k = 6, one of depth 60
+ *   or less at every k.
+ * Stream: the device form only enqueues on hip_stream (dev_out is a HOST struct of device pointers; one stream at a time per accel),
+ *   with the one exception lg_closest_points_device already has: an accel's first call of either builds and uploads the query's own
+ *   tables after a synchronise.  The host form is synchronous: points and radii go up, the planes come back into staging and are copied
+ *   out at the end, so an error on the way leaves the caller's arrays as they were.
+ * Out of scope: de-duplicating coplanar neighbours (two triangles that share an edge both answer a point nearest that edge, with the same
+ *   d2); a normal at the point; world-space vertex tables or run skipping inside fat leaves -- the known remedy for slow meshes stays a
+ *   separate piece of work --; the sorted order; a multi-device split. */
+#define LG_NEAREST_MAX_K 8
+typedef struct lg_nearest_out {
+    uint8_t  *touch;           /* [n]        1 iff count > 0, else 0 */
+    uint32_t *count;           /* [n]        the number of admissible candidates -- ALL of them, not capped at k */
+    double   *distance;        /* [k][n]     slot-major: element (j, i) at j*n + i; sqrt(d2), +INF for an empty slot */
+    double   *point;           /* [k][n][3]  the candidate's closest point, world space; +0.0 for an empty slot */
+    uint32_t *id;              /* [k][n][4]  kind, prim, instance, material; empty slot: 0, ~0, ~0, -1 */
+} lg_nearest_out;              /* 40 bytes; each pointer may be NULL, all NULL is an error */
+int lg_nearest(const lg_accel *, const double *points, const double *radii, size_t n, double radius, uint32_t k, const lg_nearest_out *out);   /* host arrays; synchronous */
+int lg_nearest_device(const lg_accel *, const double *dev_points, const double *dev_radii, size_t n, double radius, uint32_t k, const lg_nearest_out *dev_out,
+                      void *hip_stream);
+size_t lg_scene_nearest_lds(const lg_scene *, uint32_t k);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

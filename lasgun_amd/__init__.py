@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD, CLOSEST_SIGNATURES, CClosestOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD, CLOSEST_SIGNATURES, NEAREST_SIGNATURES, CClosestOut, CNearestOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -116,6 +116,7 @@ _EXTRA = {
     **LIT_SIGNATURES,
     **ATTRIBUTES_SIGNATURES,
     **CLOSEST_SIGNATURES,
+    **NEAREST_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -169,6 +170,11 @@ _ATTR_SHAPE = {"hits": ((), HIT_DTYPE), "flags": ((), _np.uint32), "bary": ((3,)
 assert _C.sizeof(CClosestOut) == 24, "lg_closest_out is 24 bytes"
 CLOSEST_PLANES = ("distance", "point", "id")  # lg_closest_out's members, in its order
 _CLOSEST_SHAPE = {"distance": ((), _np.float64), "point": ((3,), _np.float64), "id": ((4,), _np.uint32)}  # (trailing shape, dtype) per point
+assert _C.sizeof(CNearestOut) == 40, "lg_nearest_out is 40 bytes"
+NEAREST_PLANES = ("touch", "count", "distance", "point", "id")  # lg_nearest_out's members, in its order
+NEAREST_SLOT_PLANES = NEAREST_PLANES[2:]  # slot-major (k, n, ...): only these make k play a part
+NEAREST_MAX_K = 8  # LG_NEAREST_MAX_K
+_NEAREST_SHAPE = {"touch": ((), _np.uint8), "count": ((), _np.uint32), **_CLOSEST_SHAPE}  # (trailing shape, dtype) per point (per slot and point for a slot plane)
 LIGHT_DTYPE = _np.dtype([("position", _np.float64, (3,)), ("intensity", _np.float64, (3,)), ("falloff", _np.float64, (3,))])  # lg_light
 assert LIGHT_DTYPE.itemsize == 72
 
@@ -1153,6 +1159,80 @@ class HipApi(Api):
             raise LasgunError(self.last_error())
         return int(v)
 
+    # ---- proximity queries (include/lasgun_hip.h, lg_nearest*): the k nearest primitives of each point under a radius of its own
+    def nearest(self, accel, points, radii=None, radius=float("inf"), k=1, planes=None, into=None):
+        """The k nearest primitives of the scene for every point of an (n, 3) float64 array (world space), each point under its own
+        radius: `radii` (an (n,) float64 array; a NaN or negative entry makes that point a miss) or, with radii None, the shared
+        `radius`.  A dict of the planes asked for (any of NEAREST_PLANES; None: all five): uint8 (n,) touch, 1 where any primitive lies
+        within the radius; uint32 (n,) count, how many do -- all of them, not capped at k; and slot-major float64 (k, n) distance,
+        float64 (k, n, 3) point, uint32 (k, n, 4) id: slot j is the j-th candidate in ascending (squared distance, key = instance, kind,
+        prim) order, an empty slot the miss row (+inf, +0.0, (0, ~0, ~0, -1)).  One candidate per primitive, closest_points' own, so slot 0
+        under a shared radius is closest_points' answer byte for byte.  k is 0 .. NEAREST_MAX_K and plays a part only with a slot plane.
+        What it costs follows from the planes: touch alone stops at the first contact; slot planes without count prune by the k-th best;
+        count has to meet every primitive within the radius (at radius +inf: every primitive, for every point).  `into`: a dict of
+        C-contiguous arrays of those shapes, written in place.  Also `accel.nearest(points, radii=..., k=...)`."""
+        q = _np.ascontiguousarray(points, dtype=_np.float64)
+        if q.ndim != 2 or q.shape[1] != 3:
+            raise ValueError("points: an (n, 3) float64 array")
+        n = q.shape[0]
+        r = None
+        if radii is not None:
+            r = _np.ascontiguousarray(radii, dtype=_np.float64)
+            if r.shape != (n,):
+                raise ValueError("radii: an (n,) float64 array, one radius per point")
+        planes = NEAREST_PLANES if planes is None else tuple(planes)
+        if any(p not in NEAREST_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (NEAREST_PLANES,))
+        k = int(k)
+        if not 0 <= k <= NEAREST_MAX_K:
+            raise ValueError("k: 0 .. %d" % NEAREST_MAX_K)
+        out = {}
+        for p in planes:
+            tail, dt = _NEAREST_SHAPE[p]
+            shape = ((k, n) if p in NEAREST_SLOT_PLANES else (n,)) + tail
+            if into is not None and p not in into:
+                raise ValueError("into: no array for the plane %r that is asked for" % (p,))
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        if k == 0 and n and any(p in NEAREST_SLOT_PLANES for p in planes):
+            raise ValueError("k: 0 with a slot plane (distance, point, id) asked for")
+        f = CNearestOut(*[data(out.get(p)) for p in NEAREST_PLANES])
+        if self.call("nearest", accel.h, data(q), data(r), n, float(radius), k, _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def nearest_device(self, accel, n, points_ptr, radii_ptr=None, radius=float("inf"), k=1, touch_ptr=None, count_ptr=None, distance_ptr=None, point_ptr=None, id_ptr=None,
+                       stream=None):
+        """Enqueue nearest of n points (device memory, 3 doubles each; radii_ptr: n doubles or None for the shared radius) into device
+        memory: touch_ptr (n u8), count_ptr (n u32), and slot-major distance_ptr (k x n f64), point_ptr (k x n x 3 f64), id_ptr (k x n x
+        4 u32, 16-byte aligned); each may be None, not all.  The pointers are integers (torch: tensor.data_ptr()) or objects with a
+        data_ptr().  An accel's first call also builds the query's own tables."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        void = lambda p: _C.c_void_p(p) if p is not None else None  # noqa: E731
+        f = CNearestOut(*[ptr(p) for p in (touch_ptr, count_ptr, distance_ptr, point_ptr, id_ptr)])
+        if self.call("nearest_device", accel.h, void(ptr(points_ptr)), void(ptr(radii_ptr)), int(n), float(radius), int(k), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def scene_nearest_lds(self, scene, k):
+        """The dynamic LDS a workgroup of nearest needs for a scene and k, without a device: 256 * (8 * scene_closest_depth + 20 * k)
+        bytes; a call is refused exactly where this exceeds 160 KiB (include/lasgun_hip.h, lg_scene_nearest_lds)."""
+        v = self.call("scene_nearest_lds", scene.h, int(k))
+        if v == 0:
+            raise LasgunError(self.last_error())
+        return int(v)
+
+    def touching(self, accel, centres, radii):
+        """A CONVENIENCE of this wrapper over nearest's touch plane: for spheres (centres (n, 3), radii (n,) or one number) a bool (n,)
+        array, True where the scene's SURFACE comes within the sphere's radius of its centre -- the collision test of a sphere set.  A
+        sphere wholly inside a solid, farther from its surface than its radius, does not touch it; a NaN or negative radius never
+        touches.  The walk of a sphere ends at its first contact."""
+        q = _np.ascontiguousarray(centres, dtype=_np.float64)
+        r = _np.ascontiguousarray(_np.broadcast_to(_np.asarray(radii, dtype=_np.float64), q.shape[:1]))
+        return self.nearest(accel, q, radii=r, k=0, planes=("touch",))["touch"].astype(bool)
+
     def signed_distance(self, accel, points, max_layers=32):
         """A CONVENTION of this wrapper over closest_points and hit_layers, for scenes made of CLOSED solids only (spheres, boxes,
         watertight meshes that do not intersect one another's surfaces at the point): closest_points' distance, negated where the ray
@@ -1864,6 +1944,8 @@ api.Accel.radiance_groups = lambda self, rays, groups: api.radiance_groups(self,
 api.Accel.scatter = lambda self, rays, planes=SCATTER_PLANES: api.scatter(self, rays, planes)  # accel.scatter(rays)
 api.Accel.hit_attributes = lambda self, rays, planes=ATTR_PLANES: api.hit_attributes(self, rays, planes)  # accel.hit_attributes(rays, ("uv", "bary"))
 api.Accel.closest_points = lambda self, points, radius=float("inf"), planes=None: api.closest_points(self, points, radius, planes)  # accel.closest_points(points, radius=0.5)
+api.Accel.nearest = lambda self, points, radii=None, radius=float("inf"), k=1, planes=None: api.nearest(self, points, radii, radius, k, planes)  # accel.nearest(points, radii=r, k=4)
+api.Accel.touching = lambda self, centres, radii: api.touching(self, centres, radii)  # accel.touching(centres, radii): a bool per sphere
 api.Accel.signed_distance = lambda self, points, max_layers=32: api.signed_distance(self, points, max_layers)  # accel.signed_distance(points): closed solids only
 api.Accel.scatter_lit = lambda self, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES: api.scatter_lit(self, rays, lights, ambient, planes)  # accel.scatter_lit(rays, [la.Light(p, i)])
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):

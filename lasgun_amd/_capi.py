@@ -213,6 +213,14 @@ CLOSEST_SIGNATURES = {
     "scene_closest_depth": (C.c_int, [C.c_void_p]),
 }
 
+# Proximity queries (include/lasgun_hip.h, lg_nearest / lg_nearest_device / lg_scene_nearest_lds): for each point, under a radius of its own, the
+# k nearest primitives in order as slot-major planes, the count of those within the radius and whether any is; the GPU library's alone.
+NEAREST_SIGNATURES = {
+    "nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_void_p]),
+    "nearest_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "scene_nearest_lds": (C.c_size_t, [C.c_void_p, C.c_uint32]),
+}
+
 # Lit scatter (include/lasgun_hip.h, lg_scatter_lit / lg_scatter_lit_device): surface scatter under lights that come with the call -- the
 # seven planes of lg_scatter, every light's own term and the visibility bits; the GPU library's alone.
 LIT_SIGNATURES = {
@@ -304,6 +312,10 @@ class CAttrOut(C.Structure):  # lg_attr_out: seven pointers, 56 bytes; NULL = no
 
 class CClosestOut(C.Structure):  # lg_closest_out: three pointers, 24 bytes; NULL = not asked for
     _fields_ = [("distance", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p)]
+
+
+class CNearestOut(C.Structure):  # lg_nearest_out: five pointers, 40 bytes; NULL = not asked for
+    _fields_ = [("touch", C.c_void_p), ("count", C.c_void_p), ("distance", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p)]
 
 
 class CLight(C.Structure):  # lg_light: lg_scene_add_point_light's arguments, 72 bytes

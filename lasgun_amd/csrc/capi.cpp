@@ -5,6 +5,7 @@
 #include "packet_host.h"
 #include "fused_host.h"
 #include "closest_host.h"
+#include "nearest_host.h"
 
 // ============================================================================================
 extern "C" {
@@ -825,6 +826,20 @@ int lg_scene_closest_depth(const lg_scene *s) {
                                              f.leaf_soup.size()}).depth;
     });
     return rc ? -1 : v;
+}
+// The dynamic LDS lg_nearest* would ask for per workgroup for a scene and k, without a device (nearest_host.h, nearest_lds_bytes over
+// closest_tables' depth): a call whose value exceeds 160 KiB is refused; 0 on an error.
+size_t lg_scene_nearest_lds(const lg_scene *s, uint32_t k) {
+    size_t v = 0;
+    int rc = guarded([&] {
+        if (!s) throw Error("scene is NULL");
+        if (k > NEAREST_MAX_K) throw Error("k is beyond LG_NEAREST_MAX_K");
+        FlatScene f;
+        flatten_scene(s->s, f, false, false);
+        v = nearest_lds_bytes(closest_tables(ClosestScene{f.accels.data(), f.accels.size(), f.nodes.data(), f.nodes.size(), f.primref.data(), f.primref.size(),
+                                                          f.leaf_soup.data(), f.leaf_soup.size()}).depth, k);
+    });
+    return rc ? 0 : v;
 }
 int lg_accel_set_fused_shade(const lg_accel *a, int enabled) {
     if (enabled != 0 && enabled != 1) return fail("fused shade must be 0 or 1");

@@ -147,6 +147,16 @@ hipError_t closest_occupancy(uint32_t stack_depth, int *blocks_per_cu);
 hipError_t closest_set_lds_limit(size_t bytes);
 size_t closest_stack_bytes(uint32_t stack_depth);
 struct ClosestTables; // closest_host.h
+// k_nearest.hip: proximity queries (lg_nearest*) -- closest_kernel's walk keeping the k nearest candidates of each point in a per-lane list
+// behind the stack in dynamic LDS (nearest_host.h, nearest_lds_bytes(stack_depth, k)), counting the candidates within the point's radius, or
+// leaving at the first one: `form` is nearest_form(count asked for, a slot plane asked for); radii: nullptr for the shared radius
+// (r2 = radius * radius); k: the list entries a lane keeps (0 without a slot plane); only the planes that are not nullptr are written
+int nearest_form(bool count, bool slots);
+hipError_t launch_nearest(const DParams &P, int form, const double *points, const double *radii, unsigned long long n, double r2, double qmax, uint32_t k, uint8_t *touch,
+                          uint32_t *count, double *distance, double *point, void *id, const uint32_t *tri_base, const void *cl, uint32_t *tile_counter, uint32_t blocks,
+                          uint32_t stack_depth, hipStream_t stream);
+hipError_t nearest_occupancy(int form, uint32_t stack_depth, uint32_t k, int *blocks_per_cu);
+hipError_t nearest_set_lds_limit(size_t bytes);
 // k_paths.hip: ray paths (lg_trace_paths*) -- layers_kernel's loop with a direction update: at each hit the rule of its material (`rules`:
 // n_rules lg_path_rule records in DEVICE memory) ends the path or forms the next segment in registers (bounce.h); only the planes that are
 // not nullptr are written, vertex-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order

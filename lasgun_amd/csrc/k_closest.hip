@@ -23,6 +23,11 @@
 //
 // Every element of every plane asked for is written by exactly one lane: no atomics, no pre-fill.  Lanes past the last point walk nothing
 // and write nothing.
+//
+// The walk's pieces -- ClosestArgs, closest_world, ClosestLevel, closest_enter, closest_box_d2, closest_skip, closest_candidate, closest_leaf,
+// closest_material, closest_begin, closest_next_tile -- are k_nearest.hip's too (lg_nearest*: the k nearest, counts, per-point radii): it includes THIS text with
+// LG_CLOSEST_WALK_ONLY defined, which leaves out the kernel, its stack and its launchers.  One text, no copy: the tests that pin these
+// lines read them here.
 #include "closest_host.h"
 #include "closest_prim.h"
 #include "kcommon.h"
@@ -33,7 +38,9 @@
 
 namespace lg {
 
+#ifndef LG_CLOSEST_WALK_ONLY
 extern __shared__ uint32_t closest_stack[];
+#endif
 
 struct ClosestArgs {
     const double *points;      // [n][3]
@@ -109,8 +116,38 @@ __device__ __forceinline__ bool closest_skip(const ClosestLevel &L, double box_d
     return lb > 0.0 && lb * lb > lim * (1.0 + 0x1p-40);
 }
 
-__device__ __forceinline__ void closest_leaf(const DParams &P, const ClosestArgs &Q, const ClosestLevel &L, V3 qw, const DNode *n, ClosestBest &best, uint32_t *stack,
-                                             uint32_t &sp) {
+// The candidate of one leaf slot (`slot` indexes P.leaf_soup; kind, idx: the halves of its primref; never a nested accel) of accel `accel`,
+// and its prim in lg_hit's numbering.  It reads nothing of the walk's state: the same slot gives the same bits whenever it is asked
+// (k_nearest.hip evaluates a list's winners again at the end).
+__device__ __forceinline__ ClosestPt closest_candidate(const DParams &P, const ClosestArgs &Q, uint32_t accel, uint32_t slot, uint32_t kind, uint32_t idx, V3 qw, uint32_t &prim) {
+    const uint4 *rec = reinterpret_cast<const uint4 *>(P.leaf_soup + slot);
+    const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+    ClosestPt c;
+    prim = idx;
+    if (kind == PK_TRIANGLE) {
+        const V3 a = closest_world(P, accel, V3{(double)__uint_as_float(r0.x), (double)__uint_as_float(r0.y), (double)__uint_as_float(r0.z)});
+        const V3 b = closest_world(P, accel, V3{(double)__uint_as_float(r0.w), (double)__uint_as_float(r1.x), (double)__uint_as_float(r1.y)});
+        const V3 cc = closest_world(P, accel, V3{(double)__uint_as_float(r1.z), (double)__uint_as_float(r1.w), (double)__uint_as_float(r2.x)});
+        c = closest_triangle(qw, a, b, cc);
+        prim = idx - Q.tri_base[accel];
+    } else if (kind == PK_SPHERE) {
+        const double cx = __hiloint2double((int)r0.y, (int)r0.x), cy = __hiloint2double((int)r0.w, (int)r0.z);
+        const double cz = __hiloint2double((int)r1.y, (int)r1.x), r = __hiloint2double((int)r1.w, (int)r1.z);
+        c = closest_sphere(qw, closest_world(P, accel, V3{cx, cy, cz}), closest_world(P, accel, V3{cx + r, cy + 0.0, cz + 0.0}));
+    } else {
+        const double mn[3] = {__hiloint2double((int)r0.y, (int)r0.x), __hiloint2double((int)r0.w, (int)r0.z), __hiloint2double((int)r1.y, (int)r1.x)};
+        const double mx[3] = {__hiloint2double((int)r1.w, (int)r1.z), __hiloint2double((int)r2.y, (int)r2.x), __hiloint2double((int)r2.w, (int)r2.z)};
+        V3 w[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[q] = closest_world(P, accel, V3{(q & 1) ? mx[0] : mn[0], (q & 2) ? mx[1] : mn[1], (q & 4) ? mx[2] : mn[2]});
+        c = closest_box(qw, w);
+    }
+    return c;
+}
+// A leaf: its nested accels pushed as (node 0, that accel), every other slot's candidate handed to offer(c, kind, prim, slot) -- kind the
+// primref's (lg_hit's less one)
+template <class Offer>
+__device__ __forceinline__ void closest_leaf(const DParams &P, const ClosestArgs &Q, const ClosestLevel &L, V3 qw, const DNode *n, uint32_t *stack, uint32_t &sp, Offer &&offer) {
     const uint32_t count = n->meta & 0xFFFFu, first = L.prim_base + n->link;
     for (uint32_t k = 0; k < count; ++k) {
         const uint32_t ref = P.primref[first + k], kind = ref >> 30, idx = ref & PRIM_INDEX_MASK;
@@ -120,29 +157,9 @@ __device__ __forceinline__ void closest_leaf(const DParams &P, const ClosestArgs
             ++sp;
             continue;
         }
-        const uint4 *rec = reinterpret_cast<const uint4 *>(P.leaf_soup + (first + k));
-        const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-        ClosestPt c;
-        uint32_t prim = idx;
-        if (kind == PK_TRIANGLE) {
-            const V3 a = closest_world(P, L.accel, V3{(double)__uint_as_float(r0.x), (double)__uint_as_float(r0.y), (double)__uint_as_float(r0.z)});
-            const V3 b = closest_world(P, L.accel, V3{(double)__uint_as_float(r0.w), (double)__uint_as_float(r1.x), (double)__uint_as_float(r1.y)});
-            const V3 cc = closest_world(P, L.accel, V3{(double)__uint_as_float(r1.z), (double)__uint_as_float(r1.w), (double)__uint_as_float(r2.x)});
-            c = closest_triangle(qw, a, b, cc);
-            prim = idx - Q.tri_base[L.accel];
-        } else if (kind == PK_SPHERE) {
-            const double cx = __hiloint2double((int)r0.y, (int)r0.x), cy = __hiloint2double((int)r0.w, (int)r0.z);
-            const double cz = __hiloint2double((int)r1.y, (int)r1.x), r = __hiloint2double((int)r1.w, (int)r1.z);
-            c = closest_sphere(qw, closest_world(P, L.accel, V3{cx, cy, cz}), closest_world(P, L.accel, V3{cx + r, cy + 0.0, cz + 0.0}));
-        } else {
-            const double mn[3] = {__hiloint2double((int)r0.y, (int)r0.x), __hiloint2double((int)r0.w, (int)r0.z), __hiloint2double((int)r1.y, (int)r1.x)};
-            const double mx[3] = {__hiloint2double((int)r1.w, (int)r1.z), __hiloint2double((int)r2.y, (int)r2.x), __hiloint2double((int)r2.w, (int)r2.z)};
-            V3 w[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) w[q] = closest_world(P, L.accel, V3{(q & 1) ? mx[0] : mn[0], (q & 2) ? mx[1] : mn[1], (q & 4) ? mx[2] : mn[2]});
-            c = closest_box(qw, w);
-        }
-        closest_offer(best, c, Q.r2, closest_key(L.accel, kind + 1u, prim));
+        uint32_t prim;
+        const ClosestPt c = closest_candidate(P, Q, L.accel, first + k, kind, idx, qw, prim);
+        offer(c, kind, prim, first + k);
     }
 }
 
@@ -160,13 +177,19 @@ __device__ __forceinline__ int32_t closest_material(const DParams &P, uint32_t k
     return prim_mat >= 0 ? prim_mat : mat;
 }
 
+// The prologue and the tile cursor of a kernel of this family: has the wave anything to do (a launch of n tiles is claimed by its first n
+// waves), and its next 64-point tile, the same in every lane, or NO_TILE (kcommon.h says how a launch ends)
+__device__ __forceinline__ bool closest_begin(uint32_t ntiles) { return ntiles != 0u && wave_has_work(ntiles); }
+__device__ __forceinline__ uint32_t closest_next_tile(const ClosestArgs &Q, uint32_t ntiles, bool &final) { return claim_tile_single(Q.tile_counter, ntiles, final); }
+
+#ifndef LG_CLOSEST_WALK_ONLY
 __global__ void __launch_bounds__(LG_BLOCK) closest_kernel(const DParams P, const ClosestArgs Q) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t ntiles = Q.ntiles;
-    if (ntiles == 0u || !wave_has_work(ntiles)) return;
+    if (!closest_begin(ntiles)) return;
     uint32_t *stack = closest_stack + tid;
     for (bool final = false; !final;) {
-        const uint32_t tile = claim_tile_single(Q.tile_counter, ntiles, final);
+        const uint32_t tile = closest_next_tile(Q, ntiles, final);
         if (tile == NO_TILE) break;
         const unsigned long long i = (unsigned long long)tile * 64ull + lane;
         if (i >= Q.n) continue;
@@ -195,7 +218,9 @@ __global__ void __launch_bounds__(LG_BLOCK) closest_kernel(const DParams P, cons
                 const DNode *n = P.nodes + (L.node_base + node);
                 const uint32_t meta = n->meta;
                 if (meta & NODE_LEAF) {
-                    closest_leaf(P, Q, L, qw, n, best, stack, sp);
+                    closest_leaf(P, Q, L, qw, n, stack, sp, [&](const ClosestPt &c, uint32_t kind, uint32_t prim, uint32_t) {
+                        closest_offer(best, c, Q.r2, closest_key(L.accel, kind + 1u, prim));
+                    });
                     continue;
                 }
                 const uint32_t c0 = node + 1u, c1 = n->link;
@@ -241,5 +266,6 @@ hipError_t closest_set_lds_limit(size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(closest_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 size_t closest_stack_bytes(uint32_t stack_depth) { return closest_lds_bytes(stack_depth); }
+#endif // LG_CLOSEST_WALK_ONLY
 
 } // namespace lg

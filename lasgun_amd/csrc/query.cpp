@@ -1,6 +1,6 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_closest_points*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_closest_points*, lg_nearest*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_closest.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_closest.hip, k_nearest.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
 // alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
@@ -8,7 +8,7 @@
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below), whose host-memory half is
 // planes_host.h's HostStaging; what a plane of a query's output struct is, is that query's one table (scan_host.h, layers_host.h,
-// attributes_host.h, closest_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
+// attributes_host.h, closest_host.h, nearest_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
 // helpers below; what a bit row is, is bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
@@ -16,6 +16,7 @@
 #include "attributes_host.h"
 #include "bitrows_host.h"
 #include "closest_host.h"
+#include "nearest_host.h"
 #include "features_host.h"
 #include "gather_host.h"
 #include "layers_host.h"
@@ -977,6 +978,67 @@ extern "C" int lg_closest_points_device(const lg_accel *a, const double *dev_poi
         check_device_buffer(*a, dev_points, n * 3 * sizeof(double), 8, "points");
         closest_planes(*dev_out, n, device_planes(*a));
         enqueue_closest(*a, t, dev_points, n, radius, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- proximity queries (lg_nearest*; k_nearest.hip): for each of the caller's points, under a radius of its own, the k nearest primitives
+// in order, the count of those within the radius, and whether any is.  The scene's tables, its gate and its depth rule are closest points'
+// own (closest_tables_of, check_closest_scene); what else needs no device -- the five planes, k, n * k and the sizes, the LDS rule -- is
+// nearest_host.h's.
+// What the scene itself may be refused for, in the contract's order: the gate, the stack's depth, then stack plus lists against the LDS
+static const ClosestTables &check_nearest_scene(const lg_accel &a, uint32_t entries) {
+    const ClosestTables &t = check_closest_scene(a);
+    check_nearest_lds(t.depth, entries);
+    return t;
+}
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call, the scene and the
+// buffers): ONE launch over the points' 64-point tiles, in the form the planes asked for need, the grid sized by that form's occupancy
+static void enqueue_nearest(const lg_accel &a, const ClosestTables &t, const double *points, const double *radii, size_t n, double radius, uint32_t entries,
+                            const lg_nearest_out &out, hipStream_t stream) {
+    check_queue_error(a);
+    const DParams P = base_params(a, 1, 1);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const int form = nearest_form(out.count != nullptr, entries != 0u);
+    // beyond the default 64 KiB the kernels' limit is raised -- always to the most any call may ask for, so that two accels used from two
+    // threads never lower it under each other's launch
+    if (nearest_lds_bytes(t.depth, entries) > (64u << 10)) HIP_TRY(nearest_set_lds_limit(NEAREST_LDS_LIMIT));
+    int per_cu = 0;
+    HIP_TRY(nearest_occupancy(form, t.depth, entries, &per_cu));
+    const unsigned long long tiles = ((unsigned long long)n + 63ull) / 64ull, want = (tiles + 3ull) / 4ull; // four waves a workgroup
+    const uint32_t blocks = (uint32_t)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, (unsigned long long)(per_cu < 1 ? 1 : per_cu) * a.cus));
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(launch_nearest(P, form, points, radii, n, radii ? 0.0 : radius * radius, t.qmax, entries, out.touch, out.count, out.distance, out.point, out.id, a.accel_tri_base.p,
+                           a.closest_cl.p, c.tile_counter.p, blocks, t.depth, stream));
+}
+// Host form: points and radii go up, the planes come back staged
+extern "C" int lg_nearest(const lg_accel *a, const double *points, const double *radii, size_t n, double radius, uint32_t k, const lg_nearest_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t nk = check_nearest(a, points, radii, n, radius, k, out);
+        const uint32_t entries = nearest_entries(*out, k);
+        std::lock_guard<std::mutex> g(a->mtx);
+        RoundTrip trip(*a);
+        const ClosestTables &t = check_nearest_scene(*a, entries);
+        const double *dpoints = trip.in(points, n * 3), *dradii = trip.in(radii, n);
+        lg_nearest_out dev = *out; // ... where a plane asked for becomes its device buffer
+        nearest_planes(dev, n, nk, staged_planes(trip));
+        trip.run([&] { enqueue_nearest(*a, t, dpoints, dradii, n, radius, entries, dev, a->stream); });
+    });
+}
+extern "C" int lg_nearest_device(const lg_accel *a, const double *dev_points, const double *dev_radii, size_t n, double radius, uint32_t k, const lg_nearest_out *dev_out,
+                                 void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        const size_t nk = check_nearest(a, dev_points, dev_radii, n, radius, k, dev_out);
+        check_nearest_alignment(dev_points, dev_radii, *dev_out);
+        const uint32_t entries = nearest_entries(*dev_out, k);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        const ClosestTables &t = check_nearest_scene(*a, entries);
+        check_device_buffer(*a, dev_points, n * 3 * sizeof(double), 8, "points");
+        if (dev_radii) check_device_buffer(*a, dev_radii, n * sizeof(double), 8, "radii");
+        nearest_planes(*dev_out, n, nk, device_planes(*a));
+        enqueue_nearest(*a, t, dev_points, dev_radii, n, radius, entries, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

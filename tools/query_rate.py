@@ -85,11 +85,15 @@ compacted tenth of the hits against re-walking that tenth.
 Closest points (lg_closest_points_device) -- --rows closest (not part of "all"): 2^20 points of a 128 x 128 x 64 grid over 1.2 x the scene's
 bounds (the root box through the root's transform), in grid order.  Row C: all three planes, radius +INF; row Cr: radius 5 % of the bounds'
 diagonal.  Timed C, Cr, so --repeats alternates them.
+Proximity queries (lg_nearest_device) -- --rows nearest (not part of "all"): the same 2^20 grid points.  Rows N1 / N4 / N8: k = 1, 4, 8 with
+distance + id at radius 5 % of the bounds' diagonal and at +INF, each beside row F, lg_closest_points_device with distance + id at that radius
+(the floor for k = 1; over_closest_points: the ratio).  Row T: touch alone at 5 %, beside row Fd, lg_closest_points_device with distance
+alone; row Q: count alone at 5 %.  --calls at most 4.
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes|closest[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes|nearest|closest[,...]] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -1139,6 +1143,52 @@ def measure_closest(name, builder, calls):
     return out
 
 
+def measure_nearest(name, builder, calls):
+    """Proximity queries (lg_nearest_device) on measure_closest's 2^20 grid points, beside lg_closest_points_device on the same points in the
+    same session.  Rows N1 / N4 / N8: k = 1, 4, 8 with distance + id (24 bytes a slot and point), at radius 5 % of the bounds' diagonal and at
+    +INF, each with its ratio to row F, lg_closest_points_device with distance + id at that radius -- the floor for k = 1.  Row T: the
+    touch-only form at 5 %, beside row Fd, lg_closest_points_device with distance alone.  Row Q: count alone at 5 %."""
+    if not hasattr(G, "nearest_device"):
+        return []
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    probe = G.intersect(accel, G.camera_rays(accel, 64, 64))
+    p = probe["p"][probe["kind"] != 0]
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    mid, half = (lo + hi) / 2.0, (hi - lo) / 2.0 * 1.2
+    ax = [mid[k] + half[k] * np.linspace(-1.0, 1.0, m) for k, m in enumerate((128, 128, 64))]
+    grid = np.ascontiguousarray(np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3))
+    n = len(grid)
+    pts = torch.from_numpy(grid).cuda()
+    dist, ids = torch.empty((8, n), dtype=torch.float64, device="cuda"), torch.empty((8, n, 4), dtype=torch.int32, device="cuda")
+    touch, count = torch.empty((n,), dtype=torch.uint8, device="cuda"), torch.empty((n,), dtype=torch.int32, device="cuda")
+    diag = float(np.sqrt(((hi - lo) ** 2).sum()))
+    out = []
+
+    def row(label, radius, ms, nbytes, floor=None, **more):
+        r = {"scene": name, "row": label, "points": n, "radius": radius, "ms": round(ms, 4), "mpoints_per_s": round(n / ms / 1e3, 2), "bytes_per_point": nbytes, **more,
+             "calls": calls, "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)}
+        if floor is not None:
+            r["over_closest_points"] = round(ms / floor, 3)
+        out.append(r)
+
+    for tag, radius in (("radius 5 % of the bounds' diagonal", 0.05 * diag), ("radius +INF", float("inf"))):
+        floor = timed(lambda: G.closest_points_device(accel, n, pts, radius, distance_ptr=dist, id_ptr=ids, stream=s), calls, warmup=1)
+        row("F: lg_closest_points_device, distance + id, " + tag, radius, floor, 24, within_radius=int((ids[0, :, 0] != 0).sum()))
+        for k in (1, 4, 8):
+            ms = timed(lambda: G.nearest_device(accel, n, pts, None, radius, k, distance_ptr=dist, id_ptr=ids, stream=s), calls, warmup=1)
+            row("N%d: lg_nearest_device, k = %d, distance + id, %s" % (k, k, tag), radius, ms, 24 * k, floor, filled_slots=int((ids[:k, :, 0] != 0).sum()))
+    radius = 0.05 * diag
+    floor = timed(lambda: G.closest_points_device(accel, n, pts, radius, distance_ptr=dist, stream=s), calls, warmup=1)
+    row("Fd: lg_closest_points_device, distance alone, radius 5 % of the bounds' diagonal", radius, floor, 8)
+    ms = timed(lambda: G.nearest_device(accel, n, pts, None, radius, 0, touch_ptr=touch, stream=s), calls, warmup=1)
+    row("T: lg_nearest_device, touch alone (leaves at the first contact), radius 5 % of the bounds' diagonal", radius, ms, 1, floor, touching=int(touch.sum()))
+    ms = timed(lambda: G.nearest_device(accel, n, pts, None, radius, 0, count_ptr=count, stream=s), calls, warmup=1)
+    row("Q: lg_nearest_device, count alone (meets every primitive within the radius), radius 5 % of the bounds' diagonal", radius, ms, 4, floor,
+        largest_count=int(count.max()), mean_count=round(float(count.double().mean()), 3))
+    return out
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -1263,7 +1313,7 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest")
     ap.add_argument("--out", default=None)
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
@@ -1272,8 +1322,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1307,7 +1357,9 @@ def main():
                 got += measure_attributes(name, builder, args.size, max(args.calls, 4))
             if "closest" in want:
                 got += measure_closest(name, builder, max(args.calls, 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest"}:
+            if "nearest" in want:
+                got += measure_nearest(name, builder, min(max(args.calls, 2), 4))
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
