@@ -296,6 +296,18 @@ pub struct Nearest<'a> {
     pub point: Option<&'a mut [[f64; 3]]>,
     pub id: Option<&'a mut [[u32; 4]]>,
 }
+pub use sys::lg_segments_out as SegmentsOut;
+/// The planes `Accel::closest_segments` fills, one row per segment: `touch`, `distance`, `param` (s in [0, 1]: the segment's own closest
+/// point is p0 + (p1 - p0) * s), `point` (ON THE SURFACE) and `id`; `None` = not asked for; not all five.  (Like the rest of this crate:
+/// uncompiled here -- no Rust toolchain --, held to the C header textually by tests/test_rust_bindings.py and tests/test_closest_segments_abi.py.)
+#[derive(Default)]
+pub struct Segments<'a> {
+    pub touch: Option<&'a mut [u8]>,
+    pub distance: Option<&'a mut [f64]>,
+    pub param: Option<&'a mut [f64]>,
+    pub point: Option<&'a mut [[f64; 3]]>,
+    pub id: Option<&'a mut [[u32; 4]]>,
+}
 pub use sys::lg_light as Light;
 pub use sys::lg_light_set as LightSet;
 pub use sys::lg_lit_out as LitOut;
@@ -643,6 +655,34 @@ impl<'s> Accel<'s> {
     /// The pointers must be device memory of the accel's device of the sizes `nearest` states (the library checks what HIP can tell it).
     pub unsafe fn nearest_device(&self, dev_points: *const f64, dev_radii: *const f64, n: usize, radius: f64, k: u32, dev_out: &sys::lg_nearest_out, hip_stream: *mut std::ffi::c_void) {
         if sys::lg_nearest_device(self.ptr, dev_points, dev_radii, n, radius, k, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// Segment proximity (`lg_closest_segments`): for each segment p0 .. p1 (world space, six numbers), under `radii[i]` (`None`: the
+    /// shared `radius`; `f64::INFINITY` = no limit), the nearest surface point of the scene to the segment, the segment's parameter there,
+    /// the distance and the primitive: capsules and swept spheres against the world.  `touch` alone leaves a segment's walk at its first
+    /// contact.  A segment with p0 == p1 answers as `nearest` does at k = 1.
+    pub fn closest_segments(&self, segments: &[[f64; 6]], radii: Option<&[f64]>, radius: f64, out: Segments) {
+        const _: () = assert!(std::mem::size_of::<sys::lg_segments_out>() == 40);
+        let n = segments.len();
+        assert!(radii.map_or(true, |r| r.len() == n), "closest_segments: one radius per segment");
+        assert!(out.touch.as_ref().map_or(true, |p| p.len() == n) && out.distance.as_ref().map_or(true, |p| p.len() == n)
+                && out.param.as_ref().map_or(true, |p| p.len() == n) && out.point.as_ref().map_or(true, |p| p.len() == n)
+                && out.id.as_ref().map_or(true, |p| p.len() == n), "closest_segments: every plane has segments.len() rows");
+        let o = sys::lg_segments_out {
+            touch: out.touch.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            distance: out.distance.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            param: out.param.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr()),
+            point: out.point.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut f64),
+            id: out.id.map_or(std::ptr::null_mut(), |p| p.as_mut_ptr() as *mut u32),
+        };
+        let r = radii.map_or(std::ptr::null(), |r| r.as_ptr());
+        if unsafe { sys::lg_closest_segments(self.ptr, segments.as_ptr() as *const f64, r, n, radius, &o) } != 0 { panic!("lasgun: {}", last_error()) }
+    }
+    /// `closest_segments` for segments (and radii, or null) in device memory, enqueued on a HIP stream: `dev_out`'s members are device pointers (null = not asked for)
+    ///
+    /// # Safety
+    /// The pointers must be device memory of the accel's device of the sizes `closest_segments` states (the library checks what HIP can tell it).
+    pub unsafe fn closest_segments_device(&self, dev_segments: *const f64, dev_radii: *const f64, n: usize, radius: f64, dev_out: &sys::lg_segments_out, hip_stream: *mut std::ffi::c_void) {
+        if sys::lg_closest_segments_device(self.ptr, dev_segments, dev_radii, n, radius, dev_out, hip_stream) != 0 { panic!("lasgun: {}", last_error()) }
     }
     fn attr_out(n: usize, out: Attributes, what: &str) -> sys::lg_attr_out {
         const _: () = assert!(std::mem::size_of::<sys::lg_attr_out>() == 56);

@@ -428,6 +428,32 @@ class Accel { // `Accel::from(&scene)`: borrows the scene, which must outlive it
     void nearest_device(const double *dev_points, const double *dev_radii, size_t n, double radius, uint32_t k, const lg_nearest_out &dev_out, void *hip_stream) const {
         if (lg_nearest_device(h_, dev_points, dev_radii, n, radius, k, &dev_out, hip_stream)) throw Error(lg_last_error());
     }
+    // segment proximity (lg_closest_segments): for each segment p0 .. p1 (world space), under (*radii)[i] (null: the shared `radius`), the
+    // nearest surface point of the scene to the segment, the segment's parameter there (its own closest point is p0 + (p1 - p0) * param),
+    // the distance and the primitive: capsules and swept spheres against the world.  A null member is not asked for; not all five.  touch
+    // alone leaves at the first contact.  A segment with p0 == p1 answers as nearest() does at k = 1
+    struct Segments {
+        std::vector<uint8_t> *touch = nullptr;                      // [segments]
+        std::vector<double> *distance = nullptr;                    // [segments]
+        std::vector<double> *param = nullptr;                       // [segments]
+        std::vector<std::array<double, 3>> *point = nullptr;        // [segments], ON THE SURFACE
+        std::vector<std::array<uint32_t, 4>> *id = nullptr;         // [segments]
+    };
+    void closest_segments(const std::vector<std::array<double, 6>> &segments, const std::vector<double> *radii, const Segments &out, double radius = INFINITY) const {
+        static_assert(sizeof(lg_segments_out) == 40, "lg_segments_out: five pointers");
+        const size_t n = segments.size();
+        if (radii && radii->size() != n) throw Error("closest_segments: one radius per segment");
+        lg_segments_out o{};
+        if (out.touch) { out.touch->assign(n, 0); o.touch = out.touch->data(); }
+        if (out.distance) { out.distance->assign(n, INFINITY); o.distance = out.distance->data(); }
+        if (out.param) { out.param->assign(n, 0.0); o.param = out.param->data(); }
+        if (out.point) { out.point->assign(n, {0.0, 0.0, 0.0}); o.point = n ? (*out.point)[0].data() : nullptr; }
+        if (out.id) { out.id->assign(n, {0u, ~0u, ~0u, ~0u}); o.id = n ? (*out.id)[0].data() : nullptr; }
+        if (lg_closest_segments(h_, segments.empty() ? nullptr : segments[0].data(), radii ? radii->data() : nullptr, n, radius, &o)) throw Error(lg_last_error());
+    }
+    void closest_segments_device(const double *dev_segments, const double *dev_radii, size_t n, double radius, const lg_segments_out &dev_out, void *hip_stream) const {
+        if (lg_closest_segments_device(h_, dev_segments, dev_radii, n, radius, &dev_out, hip_stream)) throw Error(lg_last_error());
+    }
     // lit scatter (lg_scatter_lit): scatter() under lights that come with the call -- `lights` shared by every ray (per_ray false: K records)
     // or a table per ray (per_ray true: rays.size() * K records, ray i's at i * K), `ambient` in the scene's ambient colour's place; the
     // scene's own lights play no part.  Beside scatter()'s planes: terms = every light's own term of direct ([ray * K + k], +0.0 where it is

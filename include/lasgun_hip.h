@@ -1380,6 +1380,73 @@ int lg_nearest(const lg_accel *, const double *points, const double *radii, size
 int lg_nearest_device(const lg_accel *, const double *dev_points, const double *dev_radii, size_t n, double radius, uint32_t k, const lg_nearest_out *dev_out,
                       void *hip_stream);
 size_t lg_scene_nearest_lds(const lg_scene *, uint32_t k);
+
+/* Segment proximity: for each of n SEGMENTS p0 .. p1, under a radius of its own, the nearest surface point of the scene to the segment,
+ * the parameter of the segment's own closest point, the distance and the primitive -- a capsule (a robot link: a segment with a radius)
+ * against the world, and a sphere swept from one pose to the next: "did it touch anything on the way from p0 to p1", the discrete form
+ * of continuous collision detection, which sampled spheres miss for thin geometry and a ray, having no thickness, cannot answer.  An
+ * EXTRA, as lg_closest_points and lg_nearest are; the contract is the arithmetic below, and the answer is that arithmetic over ALL
+ * primitives of the scene, bit for bit.  `segments` is n x 6 f64, world space: p0, then p1.  All f64, nothing fused,
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x).
+ * Candidates: one candidate (d2, s, x) per primitive: d2 the squared distance, s the segment's parameter -- the segment's own closest
+ *   point is p0 + (p1-p0)*s --, x the point ON THE PRIMITIVE.  The primitive's world geometry is formed exactly as lg_closest_points forms
+ *   it (W_A; f32 vertices widened; a box's eight corners; a sphere's cw and pw).  clamp(v) = v<=0 ? +0.0 : (v>=1 ? 1.0 : v); every s leaves
+ *   through clamp or is a literal, so it is never -0.0.  The key is lg_nearest's: instance << 34 | kind << 32 | prim.
+ * Degenerate segment (p0 == p1 in all three components): the candidate is lg_closest_points' own for p0, with s = +0.0: such a segment
+ *   answers with lg_nearest's k = 1 bytes.
+ * Triangle a, b, c: six sub-candidates in this order; the lowest d2 wins, the first a tie, a NaN d2 never replaces anything.
+ *   1. Crossing (Ericson 5.3.6, two-sided): ab=b-a, ac=c-a, qp=p0-p1; n=cross(ab,ac); d=dot(qp,n); ap=p0-a; t=dot(ap,n); e=cross(qp,ap);
+ *      v=dot(ac,e); w=-dot(ab,e); where d<0 all of d, t, v, w are negated.  Verdict: d>0 && d<+INF && t>=0 && t<=d && v>=0 && w>=0 &&
+ *      v+w<=d; then s = clamp(t/d), y = p0+(p1-p0)*s, and the verdict is CONFIRMED iff the squared distance of y from the triangle by
+ *      lg_closest_points' steps 1-7 is <= g*g, g = 2^-46 * the largest |component| of y, a, b, c (fmax).  Crosses iff both: d2 = +0.0,
+ *      x = y.  (For a segment in the triangle's plane the signs are noise; the confirmation ties a false "crosses" to formed points.  A
+ *      true crossing at a grazing angle may fail it and is then answered by 2-6 with a small d2 above zero.)
+ *   2. lg_closest_points' triangle steps 1-7 for p0, s = 0.     3. The same for p1, s = 1.
+ *   4. The segment against edge a .. b (Ericson 5.1.9 with EPSILON = 0), e0=a, e1=b: d1=p1-p0, d2v=e1-e0, r=p0-e0; A=dot(d1,d1),
+ *      E=dot(d2v,d2v), f=dot(d2v,r).  A<=0 && E<=0: s=0, t=0.  Else A<=0: s=0, t=clamp(f/E).  Else c=dot(d1,r), and E<=0: t=0,
+ *      s=clamp(-c/A); else b=dot(d1,d2v), den=A*E-b*b, s = den!=0 ? clamp((b*f-c*E)/den) : 0, t=(b*s+f)/E, then t<0: t=0, s=clamp(-c/A);
+ *      t>1: t=1, s=clamp((b-c)/A).  c1=p0+d1*s, c2=e0+d2v*t, w=c1-c2: d2 = dot(w,w), x = c2.
+ *   5. The same against edge b .. c.     6. The same against edge c .. a.
+ *   Apart from the crossing's exact +0.0 every d2 is the squared length between a formed point of the segment and a formed point of the
+ *   primitive, never an algebraic shortcut.
+ * Box: its twelve triangles in lg_closest_points' order, each by the triangle rule; the lowest d2 wins, the first triangle a tie, a NaN
+ *   never replaces anything.  A segment wholly inside a box gets the distance to its surface.
+ * Sphere: pc=pw-cw, rw=sqrt(dot(pc,pc)); u=p1-p0, uu=dot(u,u); v0=p0-cw, v1=p1-cw; tt=dot(cw-p0,u); s* = uu>0 ? clamp(tt/uu) : 0;
+ *   m=p0+u*s*, vm=m-cw, lmin=sqrt(dot(vm,vm)); l0=sqrt(dot(v0,v0)), l1=sqrt(dot(v1,v1)); the far endpoint is p1 iff l1>l0 (p0 on a tie), lmax
+ *   its l and v its v0 or v1.
+ *   lmin>rw: d=lmin-rw, d2=d*d, x=cw+vm*(rw/lmin), s=s*.   Else lmax<rw: d=rw-lmax, d2=d*d, x=cw+v*(rw/lmax) (pw where lmax==0), s=0 or 1.
+ *   Else, where lmin<=rw && lmax>=rw && lmax<+INF, the segment crosses the surface: d2 = +0.0; B=dot(v0,u), C=dot(v0,v0)-rw*rw,
+ *   disc=B*B-uu*C, q=sqrt(disc), s1=(-B-q)/uu, s2=(-B+q)/uu; s = clamp(s1) where 0<=s1<=1, else clamp(s2) where 0<=s2<=1, and x=p0+u*s;
+ *   where rounding leaves neither root in range: s=s*, x=m.  Otherwise (a NaN): no candidate.
+ * Radius, admissible, winner, material, writes, traversal: lg_nearest's rules, word for word.  radii may be NULL, and the shared radius
+ *   then holds; a per-segment radius that is NaN or < 0 makes that segment a miss, not an error; a shared radius that is NaN or negative
+ *   is an error; -0.0 is zero.  A candidate is admissible iff d2 <= r_i*r_i && d2 < +INF.  A segment with a non-finite coordinate is a
+ *   miss.  The winner is the smallest (d2, key).  touch = 1 iff an admissible candidate exists; distance = sqrt(d2) of the winner, param its
+ *   s, point its x, id = kind, prim, instance, material by lg_nearest's material rule; a miss: touch 0, distance +INF, param +0.0, point
+ *   +0.0, id 0, ~0, ~0, -1.  Every element of every plane asked for is written by exactly one lane.  The accel's traversal mode,
+ *   lg_accel_set_query_order and lights play no part; a scene of more than 32 lights is accepted.
+ * What it costs: `touch` alone asked for: a segment's walk ends at its first admissible candidate.  Every other plane set keeps the best.
+ * Limits and errors: n == 0 is a successful no-op that writes nothing, answered BEFORE every other check.  Errors (non-zero,
+ *   lg_last_error, nothing launched, no output touched), for n > 0, in this order: a NULL accel, segments or out; all five planes NULL; a
+ *   shared radius that is NaN or negative (+INF: no limit); n > (2^32 - 1) * 64; a byte size that does not fit size_t; a scene the gate
+ *   refuses (lg_scene_closest_gate); a scene whose trees are too deep for the per-lane stack (lg_scene_closest_depth); in the device form
+ *   also a pointer that is not device memory of the accel's device or is misaligned (touch 1 byte; segments, radii, distance, param and
+ *   point 8; id 16), or a buffer that ends beyond its allocation.  LDS is the stack alone, 256 * 8 * depth bytes.
+ * Stream: the device form only enqueues on hip_stream (dev_out is a HOST struct of device pointers; one stream at a time per accel), with
+ *   the one exception its siblings have: an accel's first call of any of them builds and uploads the query's own tables after a
+ *   synchronise.  The host form is synchronous and stages: an error on the way leaves the caller's arrays as they were.
+ * Out of scope: k > 1 and counts; a time of impact along the segment (a true sphere cast: the FIRST s at which a sphere of radius r_i
+ *   touches, where this gives the s of the closest approach); world-space vertex tables for fat leaves; a multi-device split. */
+typedef struct lg_segments_out {
+    uint8_t  *touch;           /* [n]     1 iff an admissible candidate exists */
+    double   *distance;        /* [n]     sqrt(d2) of the winner, +INF for a miss */
+    double   *param;           /* [n]     s in [0, 1]: the segment's own closest point is p0 + (p1 - p0) * s; +0.0 for a miss */
+    double   *point;           /* [n][3]  the winner's point ON THE SURFACE, world space; +0.0 for a miss */
+    uint32_t *id;              /* [n][4]  kind, prim, instance, material; miss: 0, ~0, ~0, -1 */
+} lg_segments_out;             /* 40 bytes; each pointer may be NULL, all NULL is an error */
+int lg_closest_segments(const lg_accel *, const double *segments /* [n][6]: p0, p1 */, const double *radii, size_t n, double radius, const lg_segments_out *out);
+int lg_closest_segments_device(const lg_accel *, const double *dev_segments, const double *dev_radii, size_t n, double radius, const lg_segments_out *dev_out,
+                               void *hip_stream);
 /* The scene's point lights, the number of mask bits a light group may use; -1 for a NULL accel. */
 int lg_accel_light_count(const lg_accel *);
 /* Order in which a query's rays are walked: 0 (default) = as given; 1 = sorted on the device by a coherence key.

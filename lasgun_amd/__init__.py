@@ -11,7 +11,7 @@ import os as _os
 
 import numpy as _np
 
-from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD, CLOSEST_SIGNATURES, NEAREST_SIGNATURES, CClosestOut, CNearestOut  # noqa: F401
+from ._capi import Api, CStats, LasgunError, ObjError, QUERY_ORDER_SIGNATURES, RADIANCE_SIGNATURES, RAY_FILM_SIGNATURES, VISIBILITY_SIGNATURES, DIRECTIONS_SIGNATURES, RANGE_SCAN_SIGNATURES, HIT_LAYERS_SIGNATURES, PATHS_SIGNATURES, LIGHT_GROUPS_SIGNATURES, GATHER_SIGNATURES, FEATURES_SIGNATURES, VIEWS_SIGNATURES, VIEW_FEATURES_SIGNATURES, CView, CLens, CFeatures, CViewFeatures, CScanOut, CLayersOut, CPathRule, CPathsOut, CGatherOut, CLightGroup, GROUP_AMBIENT, MAX_LIGHT_GROUPS, SCATTER_SIGNATURES, CScatterOut, SCATTER_HIT, SCATTER_REFLECT, SCATTER_REFRACT, LIT_SIGNATURES, CLight, CLightSet, CLitOut, MAX_CALL_LIGHTS, ATTRIBUTES_SIGNATURES, CAttrOut, ATTR_HIT, ATTR_NO_HIT, ATTR_BAD_RECORD, CLOSEST_SIGNATURES, NEAREST_SIGNATURES, SEGMENTS_SIGNATURES, CClosestOut, CNearestOut, CSegmentsOut  # noqa: F401
 from . import scenes  # noqa: F401
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
@@ -117,6 +117,7 @@ _EXTRA = {
     **ATTRIBUTES_SIGNATURES,
     **CLOSEST_SIGNATURES,
     **NEAREST_SIGNATURES,
+    **SEGMENTS_SIGNATURES,
     **LIGHT_GROUPS_SIGNATURES,
     **GATHER_SIGNATURES,
     **FEATURES_SIGNATURES,
@@ -175,6 +176,9 @@ NEAREST_PLANES = ("touch", "count", "distance", "point", "id")  # lg_nearest_out
 NEAREST_SLOT_PLANES = NEAREST_PLANES[2:]  # slot-major (k, n, ...): only these make k play a part
 NEAREST_MAX_K = 8  # LG_NEAREST_MAX_K
 _NEAREST_SHAPE = {"touch": ((), _np.uint8), "count": ((), _np.uint32), **_CLOSEST_SHAPE}  # (trailing shape, dtype) per point (per slot and point for a slot plane)
+assert _C.sizeof(CSegmentsOut) == 40, "lg_segments_out is 40 bytes"
+SEGMENT_PLANES = ("touch", "distance", "param", "point", "id")  # lg_segments_out's members, in its order
+_SEGMENT_SHAPE = {"touch": ((), _np.uint8), "param": ((), _np.float64), **_CLOSEST_SHAPE}  # (trailing shape, dtype) per segment
 LIGHT_DTYPE = _np.dtype([("position", _np.float64, (3,)), ("intensity", _np.float64, (3,)), ("falloff", _np.float64, (3,))])  # lg_light
 assert LIGHT_DTYPE.itemsize == 72
 
@@ -1233,6 +1237,72 @@ class HipApi(Api):
         r = _np.ascontiguousarray(_np.broadcast_to(_np.asarray(radii, dtype=_np.float64), q.shape[:1]))
         return self.nearest(accel, q, radii=r, k=0, planes=("touch",))["touch"].astype(bool)
 
+    # ---- segment proximity (include/lasgun_hip.h, lg_closest_segments*): capsules and swept spheres against the scene
+    def closest_segments(self, accel, segments, radii=None, radius=float("inf"), planes=None, into=None):
+        """The nearest surface point of the scene to every segment of an (n, 6) float64 array (world space: p0, then p1), each segment
+        under its own radius: `radii` (an (n,) float64 array; a NaN or negative entry makes that segment a miss) or, with radii None,
+        the shared `radius`.  A dict of the planes asked for (any of SEGMENT_PLANES; None: all five): uint8 (n,) touch, 1 where the
+        scene's surface comes within the radius of the segment; float64 (n,) distance (+inf: a miss); float64 (n,) param, s in [0, 1]:
+        the segment's own closest point is p0 + (p1 - p0) * s; float64 (n, 3) point, ON THE SURFACE; uint32 (n, 4) id = kind, prim,
+        instance, material (a miss: 0, ~0, ~0, -1).  A segment with p0 == p1 answers as nearest(k=1) does for that point.  touch alone
+        stops at the first contact.  `into`: a dict of C-contiguous arrays of those shapes, written in place.  Also
+        `accel.closest_segments(segments, radii=...)`."""
+        q = _np.ascontiguousarray(segments, dtype=_np.float64)
+        if q.ndim != 2 or q.shape[1] != 6:
+            raise ValueError("segments: an (n, 6) float64 array: p0, then p1")
+        n = q.shape[0]
+        r = None
+        if radii is not None:
+            r = _np.ascontiguousarray(radii, dtype=_np.float64)
+            if r.shape != (n,):
+                raise ValueError("radii: an (n,) float64 array, one radius per segment")
+        planes = SEGMENT_PLANES if planes is None else tuple(planes)
+        if any(p not in SEGMENT_PLANES for p in planes):
+            raise ValueError("planes: any of %s" % (SEGMENT_PLANES,))
+        out = {}
+        for p in planes:
+            tail, dt = _SEGMENT_SHAPE[p]
+            shape = (n,) + tail
+            if into is not None and p not in into:
+                raise ValueError("into: no array for the plane %r that is asked for" % (p,))
+            arr = into[p] if into is not None else _np.zeros(shape, dtype=dt)
+            if arr.dtype != dt or arr.shape != shape or not arr.flags["C_CONTIGUOUS"]:
+                raise ValueError("into[%r]: a C-contiguous %s array of shape %s" % (p, _np.dtype(dt).name, shape))
+            out[p] = arr
+        data = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        f = CSegmentsOut(*[data(out.get(p)) for p in SEGMENT_PLANES])
+        if self.call("closest_segments", accel.h, data(q), data(r), n, float(radius), _C.addressof(f)):
+            raise LasgunError(self.last_error())
+        return out
+
+    def closest_segments_device(self, accel, n, segments_ptr, radii_ptr=None, radius=float("inf"), touch_ptr=None, distance_ptr=None, param_ptr=None, point_ptr=None,
+                                id_ptr=None, stream=None):
+        """Enqueue closest_segments of n segments (device memory, 6 doubles each; radii_ptr: n doubles or None for the shared radius) into
+        device memory: touch_ptr (n u8), distance_ptr and param_ptr (n f64), point_ptr (n x 3 f64), id_ptr (n x 4 u32, 16-byte aligned);
+        each may be None, not all.  The pointers are integers (torch: tensor.data_ptr()) or objects with a data_ptr().  An accel's first
+        call also builds the query's own tables."""
+        ptr = lambda p: None if p is None else int(p.data_ptr()) if hasattr(p, "data_ptr") else int(p)  # noqa: E731
+        void = lambda p: _C.c_void_p(p) if p is not None else None  # noqa: E731
+        f = CSegmentsOut(*[ptr(p) for p in (touch_ptr, distance_ptr, param_ptr, point_ptr, id_ptr)])
+        if self.call("closest_segments_device", accel.h, void(ptr(segments_ptr)), void(ptr(radii_ptr)), int(n), float(radius), _C.addressof(f), self._stream(accel, stream)):
+            raise LasgunError(self.last_error())
+
+    def capsules_touching(self, accel, p0, p1, radii):
+        """A CONVENIENCE of this wrapper over closest_segments' touch plane: for capsules (axes p0 .. p1, each (n, 3); radii (n,) or one
+        number) a bool (n,) array, True where the scene's SURFACE comes within the capsule's radius of its axis -- a robot's links
+        against the world.  A capsule wholly inside a solid, farther from its surface than its radius, does not touch it; a NaN or
+        negative radius never touches.  The walk of a capsule ends at its first contact."""
+        a, b = _np.ascontiguousarray(p0, dtype=_np.float64), _np.ascontiguousarray(p1, dtype=_np.float64)
+        if a.ndim != 2 or a.shape[1] != 3 or b.shape != a.shape:
+            raise ValueError("p0, p1: two (n, 3) float64 arrays")
+        r = _np.ascontiguousarray(_np.broadcast_to(_np.asarray(radii, dtype=_np.float64), a.shape[:1]))
+        return self.closest_segments(accel, _np.concatenate([a, b], axis=1), radii=r, planes=("touch",))["touch"].astype(bool)
+
+    def sweep_touching(self, accel, centres_from, centres_to, radii):
+        """capsules_touching under the swept-sphere reading: did a sphere of radius radii[i] touch the scene's surface anywhere on its
+        straight way from centres_from[i] to centres_to[i] -- the step check of continuous collision detection.  No time of impact."""
+        return self.capsules_touching(accel, centres_from, centres_to, radii)
+
     def signed_distance(self, accel, points, max_layers=32):
         """A CONVENTION of this wrapper over closest_points and hit_layers, for scenes made of CLOSED solids only (spheres, boxes,
         watertight meshes that do not intersect one another's surfaces at the point): closest_points' distance, negated where the ray
@@ -1946,6 +2016,9 @@ api.Accel.hit_attributes = lambda self, rays, planes=ATTR_PLANES: api.hit_attrib
 api.Accel.closest_points = lambda self, points, radius=float("inf"), planes=None: api.closest_points(self, points, radius, planes)  # accel.closest_points(points, radius=0.5)
 api.Accel.nearest = lambda self, points, radii=None, radius=float("inf"), k=1, planes=None: api.nearest(self, points, radii, radius, k, planes)  # accel.nearest(points, radii=r, k=4)
 api.Accel.touching = lambda self, centres, radii: api.touching(self, centres, radii)  # accel.touching(centres, radii): a bool per sphere
+api.Accel.closest_segments = lambda self, segments, radii=None, radius=float("inf"), planes=None: api.closest_segments(self, segments, radii, radius, planes)  # accel.closest_segments(segments, radii=r)
+api.Accel.capsules_touching = lambda self, p0, p1, radii: api.capsules_touching(self, p0, p1, radii)  # accel.capsules_touching(p0, p1, radii): a bool per capsule
+api.Accel.sweep_touching = lambda self, centres_from, centres_to, radii: api.sweep_touching(self, centres_from, centres_to, radii)  # accel.sweep_touching(a, b, radii): a bool per swept sphere
 api.Accel.signed_distance = lambda self, points, max_layers=32: api.signed_distance(self, points, max_layers)  # accel.signed_distance(points): closed solids only
 api.Accel.scatter_lit = lambda self, rays, lights, ambient=(0.0, 0.0, 0.0), planes=LIT_PLANES: api.scatter_lit(self, rays, lights, ambient, planes)  # accel.scatter_lit(rays, [la.Light(p, i)])
 def path_rules(accel, default=PATH_ABSORB, gain=1.0):

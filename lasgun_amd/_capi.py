@@ -221,6 +221,13 @@ NEAREST_SIGNATURES = {
     "scene_nearest_lds": (C.c_size_t, [C.c_void_p, C.c_uint32]),
 }
 
+# Segment proximity (include/lasgun_hip.h, lg_closest_segments / lg_closest_segments_device): for each segment p0 .. p1, under a radius of its
+# own, the nearest surface point of the scene to the segment, the segment's parameter, the distance and the primitive; the GPU library's alone.
+SEGMENTS_SIGNATURES = {
+    "closest_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]),
+    "closest_segments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p]),
+}
+
 # Lit scatter (include/lasgun_hip.h, lg_scatter_lit / lg_scatter_lit_device): surface scatter under lights that come with the call -- the
 # seven planes of lg_scatter, every light's own term and the visibility bits; the GPU library's alone.
 LIT_SIGNATURES = {
@@ -316,6 +323,10 @@ class CClosestOut(C.Structure):  # lg_closest_out: three pointers, 24 bytes; NUL
 
 class CNearestOut(C.Structure):  # lg_nearest_out: five pointers, 40 bytes; NULL = not asked for
     _fields_ = [("touch", C.c_void_p), ("count", C.c_void_p), ("distance", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p)]
+
+
+class CSegmentsOut(C.Structure):  # lg_segments_out: five pointers, 40 bytes; NULL = not asked for
+    _fields_ = [("touch", C.c_void_p), ("distance", C.c_void_p), ("param", C.c_void_p), ("point", C.c_void_p), ("id", C.c_void_p)]
 
 
 class CLight(C.Structure):  # lg_light: lg_scene_add_point_light's arguments, 72 bytes

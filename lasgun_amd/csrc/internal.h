@@ -157,6 +157,15 @@ hipError_t launch_nearest(const DParams &P, int form, const double *points, cons
                           uint32_t stack_depth, hipStream_t stream);
 hipError_t nearest_occupancy(int form, uint32_t stack_depth, uint32_t k, int *blocks_per_cu);
 hipError_t nearest_set_lds_limit(size_t bytes);
+// k_segments.hip: segment proximity (lg_closest_segments*) -- closest_kernel's walk for a segment a lane (segment_prim.h's candidates, a
+// segment-against-box pruning in two stages), the stack alone in dynamic LDS; touch_only: `touch` is the only plane asked for and a lane
+// leaves at its first admissible candidate; radii: nullptr for the shared radius (r2 = radius * radius); only the planes that are not
+// nullptr are written
+hipError_t launch_segments(const DParams &P, bool touch_only, const double *segments, const double *radii, unsigned long long n, double r2, double qmax, uint8_t *touch,
+                           double *distance, double *param, double *point, void *id, const uint32_t *tri_base, const void *cl, uint32_t *tile_counter, uint32_t blocks,
+                           uint32_t stack_depth, hipStream_t stream);
+hipError_t segments_occupancy(bool touch_only, uint32_t stack_depth, int *blocks_per_cu);
+hipError_t segments_set_lds_limit(size_t bytes);
 // k_paths.hip: ray paths (lg_trace_paths*) -- layers_kernel's loop with a direction update: at each hit the rule of its material (`rules`:
 // n_rules lg_path_rule records in DEVICE memory) ends the path or forms the next segment in registers (bounce.h); only the planes that are
 // not nullptr are written, vertex-major: element (j, i) at j * n + i; perm != nullptr: the tiles are cut from the sorted order

@@ -1,6 +1,6 @@
-// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_closest_points*, lg_nearest*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
+// lasgun_amd/csrc/query.cpp -- ray queries (include/lasgun_hip.h: lg_intersect*, lg_occluded*, lg_visibility*, lg_open_directions*, lg_range_scan*, lg_hit_layers*, lg_hit_attributes*, lg_closest_points*, lg_nearest*, lg_closest_segments*, lg_trace_paths*, lg_radiance*, lg_radiance_gather*, lg_camera_rays*, lg_view_rays*, lg_capture_views*,
 // lg_capture_features*, lg_capture_view_features*, lg_accel_material, lg_accel_instance): the caller's buffers checked, then one launch of the query's kernel (k_query.hip;
-// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_closest.hip, k_nearest.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
+// k_visibility.hip, k_directions.hip, k_scan.hip, k_layers.hip, k_attributes.hip, k_closest.hip, k_nearest.hip, k_segments.hip, k_paths.hip, k_features.hip and k_view_features.hip for the structured queries) on the caller's stream, sized like
 // the render's level-by-level traversal passes (launch.cpp, enqueue_wavefront) and walking in the accel's traversal mode -- or, for
 // lg_radiance*, that pipeline itself with the caller's rays as its level 0 (launch.cpp, enqueue_radiance), and for lg_scatter* its level 0
 // alone as a chain of one level (launch.cpp, enqueue_scatter; k_scatter.hip; scatter_host.h), under the call's own lights for lg_scatter_lit*
@@ -8,7 +8,7 @@
 // lg_accel_set_query_order(1) the rays' keys and their sort (k_sort.hip) are enqueued ahead of it on the same stream, and the walk takes
 // its tiles from the sorted order; lg_query_order* return that order.  A host form is one RoundTrip (below), whose host-memory half is
 // planes_host.h's HostStaging; what a plane of a query's output struct is, is that query's one table (scan_host.h, layers_host.h,
-// attributes_host.h, closest_host.h, nearest_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
+// attributes_host.h, closest_host.h, nearest_host.h, segments_host.h, paths_host.h, scatter_host.h, lit_host.h, features_host.h, view_features_host.h), staged and checked through the two
 // helpers below; what a bit row is, is bitrows_host.h's: device-free text, sanitized on the CPU.
 #include <cstddef>
 #include <deque>
@@ -17,6 +17,7 @@
 #include "bitrows_host.h"
 #include "closest_host.h"
 #include "nearest_host.h"
+#include "segments_host.h"
 #include "features_host.h"
 #include "gather_host.h"
 #include "layers_host.h"
@@ -1039,6 +1040,57 @@ extern "C" int lg_nearest_device(const lg_accel *a, const double *dev_points, co
         if (dev_radii) check_device_buffer(*a, dev_radii, n * sizeof(double), 8, "radii");
         nearest_planes(*dev_out, n, nk, device_planes(*a));
         enqueue_nearest(*a, t, dev_points, dev_radii, n, radius, entries, *dev_out, (hipStream_t)hip_stream);
+    });
+}
+
+// ---- segment proximity (lg_closest_segments*; k_segments.hip): for each of the caller's segments, under a radius of its own, the nearest
+// surface point of the scene to the segment.  The scene's tables, its gate and its depth rule are closest points' own (closest_tables_of,
+// check_closest_scene); what else needs no device -- the five planes, the sizes -- is segments_host.h's.  The LDS is the stack alone.
+// One query enqueued on `stream` (caller holds a.mtx, has made the accel's device current and has checked the call, the scene and the
+// buffers): ONE launch over the segments' 64-segment tiles, in the form the planes asked for need
+static void enqueue_segments(const lg_accel &a, const ClosestTables &t, const double *segments, const double *radii, size_t n, double radius, const lg_segments_out &out,
+                             hipStream_t stream) {
+    check_queue_error(a);
+    const DParams P = base_params(a, 1, 1);
+    lg_accel::LaunchCtx &c = ctx_for(a, stream);
+    const bool touch_only = segments_touch_only(out);
+    // beyond the default 64 KiB the kernels' limit is raised -- always to the most any scene may need, as closest points does
+    if (closest_stack_bytes(t.depth) > (64u << 10)) HIP_TRY(segments_set_lds_limit(closest_stack_bytes(CLOSEST_MAX_DEPTH)));
+    int per_cu = 0;
+    HIP_TRY(segments_occupancy(touch_only, t.depth, &per_cu));
+    const unsigned long long tiles = ((unsigned long long)n + 63ull) / 64ull, want = (tiles + 3ull) / 4ull; // four waves a workgroup
+    const uint32_t blocks = (uint32_t)std::max<unsigned long long>(1ull, std::min<unsigned long long>(want, (unsigned long long)(per_cu < 1 ? 1 : per_cu) * a.cus));
+    HIP_TRY(hipMemsetAsync(c.tile_counter.p, 0, TILE_COUNTER_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(launch_segments(P, touch_only, segments, radii, n, radii ? 0.0 : radius * radius, t.qmax, out.touch, out.distance, out.param, out.point, out.id, a.accel_tri_base.p,
+                            a.closest_cl.p, c.tile_counter.p, blocks, t.depth, stream));
+}
+// Host form: segments and radii go up, the planes come back staged
+extern "C" int lg_closest_segments(const lg_accel *a, const double *segments, const double *radii, size_t n, double radius, const lg_segments_out *out) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_segments(a, segments, radii, n, radius, out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        RoundTrip trip(*a);
+        const ClosestTables &t = check_closest_scene(*a);
+        const double *dsegments = trip.in(segments, n * 6), *dradii = trip.in(radii, n);
+        lg_segments_out dev = *out; // ... where a plane asked for becomes its device buffer
+        segments_planes(dev, n, staged_planes(trip));
+        trip.run([&] { enqueue_segments(*a, t, dsegments, dradii, n, radius, dev, a->stream); });
+    });
+}
+extern "C" int lg_closest_segments_device(const lg_accel *a, const double *dev_segments, const double *dev_radii, size_t n, double radius, const lg_segments_out *dev_out,
+                                          void *hip_stream) {
+    return guarded([&] {
+        if (n == 0) return;
+        check_segments(a, dev_segments, dev_radii, n, radius, dev_out);
+        check_segments_alignment(dev_segments, dev_radii, *dev_out);
+        std::lock_guard<std::mutex> g(a->mtx);
+        use_device(a->device);
+        const ClosestTables &t = check_closest_scene(*a);
+        check_device_buffer(*a, dev_segments, n * 6 * sizeof(double), 8, "segments");
+        if (dev_radii) check_device_buffer(*a, dev_radii, n * sizeof(double), 8, "radii");
+        segments_planes(*dev_out, n, device_planes(*a));
+        enqueue_segments(*a, t, dev_segments, dev_radii, n, radius, *dev_out, (hipStream_t)hip_stream);
     });
 }
 

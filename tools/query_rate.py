@@ -89,11 +89,15 @@ Proximity queries (lg_nearest_device) -- --rows nearest (not part of "all"): the
 distance + id at radius 5 % of the bounds' diagonal and at +INF, each beside row F, lg_closest_points_device with distance + id at that radius
 (the floor for k = 1; over_closest_points: the ratio).  Row T: touch alone at 5 %, beside row Fd, lg_closest_points_device with distance
 alone; row Q: count alone at 5 %.  --calls at most 4.
+Segment proximity (lg_closest_segments_device) -- --rows segments (not part of "all"): 2^20 segments (--segments N: fewer) centred on the grid
+points of --rows closest, lengths 1 % and 100 % of the bounds' diagonal, radius +INF and 5 % of it.  Rows S: distance + id; St: touch alone;
+N: lg_nearest_device, k = 1, on the midpoints, the yardstick.  What stage 2 of the pruning buys: build a second library in a copy of the tree with
+`make -C lasgun_amd/csrc EXTRA_DEVFLAGS=-DLG_SEGMENTS_NO_STAGE2`, name it in LASGUN_HIP_LIB and run --long-only --label "stage 2 compiled out".
 Light groups (lg_radiance_groups_device) -- --rows groups (not part of "all"): the camera's rays of a --size^2 film on each scene given four
 point lights (the builder's one and three more, positions in the rows), G = 6 groups: base, ambient, the four lights.  Row G6: one call.
 Beside it: row GK, G calls of lg_radiance_device on G accels rebuilt per group (builds timed apart: build_ms; planes compared: same_bytes);
 row R1, one lg_radiance_device call on the full scene, the floor.  Timed G6, GK, R1, so --repeats alternates them; --calls calls as given (at least 3).
-usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes|nearest|closest[,...]] [--out profiles/r08_query_order.jsonl]
+usage: python tools/query_rate.py [--calls 20] [--size 4096] [--repeats 1] [--order 0|1] [--rows all|queries|radiance|frame|film|visibility|features|directions|scan|gather|views|viewfeatures|layers|groups|paths|scatter|lit|attributes|nearest|closest|segments[,...]] [--segments N] [--long-only] [--label TEXT] [--out profiles/r08_query_order.jsonl]
        python tools/query_rate.py --once     (one headline frame rendered, then (a), (c) and (r8) once: for rocprofv3 --kernel-trace --stats)"""
 import argparse
 import json
@@ -1189,6 +1193,59 @@ def measure_nearest(name, builder, calls):
     return out
 
 
+def measure_segments(name, builder, calls, count=1 << 20, long_only=False, label=None):
+    """Segment proximity (lg_closest_segments_device) on `count` segments (2^20 by default) whose midpoints are measure_closest's grid
+    points (the first `count` of a seeded shuffle), directions seeded, lengths 1 % and 100 % of the bounds' diagonal, at radius +INF and at
+    5 % of the diagonal.  Rows S: distance + id (the best form); rows St: touch alone (leaves at the first contact; at radius 5 % only --
+    at +INF the first candidate ends every walk).  Beside them the yardstick, row N: lg_nearest_device, k = 1, distance + id on the
+    segments' midpoints at that radius (`over_nearest_midpoints`: the ratio).  long_only: the 100 % rows alone -- what a library built with
+    -DLG_SEGMENTS_NO_STAGE2 (LASGUN_HIP_LIB names it; `label` says so in the rows) is measured on, to show what stage 2 of the pruning buys."""
+    if not hasattr(G, "closest_segments_device"):
+        return []
+    accel = G.Accel.from_scene(builder(G))
+    s = torch.cuda.current_stream().cuda_stream
+    probe = G.intersect(accel, G.camera_rays(accel, 64, 64))
+    p = probe["p"][probe["kind"] != 0]
+    lo, hi = p.min(axis=0), p.max(axis=0)
+    mid, half = (lo + hi) / 2.0, (hi - lo) / 2.0 * 1.2
+    ax = [mid[k] + half[k] * np.linspace(-1.0, 1.0, m) for k, m in enumerate((128, 128, 64))]
+    grid = np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3)
+    rng = np.random.default_rng(30)
+    n = min(int(count), len(grid))
+    centre = np.ascontiguousarray(grid if n == len(grid) else grid[np.sort(rng.permutation(len(grid))[:n])])
+    d = rng.normal(0.0, 1.0, (n, 3))
+    d /= np.sqrt((d * d).sum(axis=1))[:, None]
+    diag = float(np.sqrt(((hi - lo) ** 2).sum()))
+    pts = torch.from_numpy(centre).cuda()
+    dist, ids = torch.empty((n,), dtype=torch.float64, device="cuda"), torch.empty((n, 4), dtype=torch.int32, device="cuda")
+    touch = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    out = []
+
+    def row(tag, radius, length, ms, nbytes, floor=None, **more):
+        r = {"scene": name, "row": tag, "segments": n, "radius": radius, "length": length, "ms": round(ms, 4), "msegments_per_s": round(n / ms / 1e3, 2), "bytes_per_segment": nbytes,
+             **more, "calls": calls, "build": label or "product", "device_source_sha16": la.device_source_sha16(), "gpu": torch.cuda.get_device_name(0)}
+        if floor is not None:
+            r["over_nearest_midpoints"] = round(ms / floor, 3)
+        out.append(r)
+
+    for rtag, radius in (("radius +INF", float("inf")), ("radius 5 % of the bounds' diagonal", 0.05 * diag)):
+        floor = timed(lambda: G.nearest_device(accel, n, pts, None, radius, 1, distance_ptr=dist, id_ptr=ids, stream=s), calls, warmup=1)
+        row("N: lg_nearest_device, k = 1, distance + id, the segments' midpoints, " + rtag, radius, 0.0, floor, 24, within_radius=int((ids[:, 0] != 0).sum()))
+        for ltag, frac in (("length 1 %", 0.01), ("length 100 %", 1.0)):
+            if long_only and frac != 1.0:
+                continue
+            length = frac * diag
+            segs = torch.from_numpy(np.ascontiguousarray(np.concatenate([centre - d * (0.5 * length), centre + d * (0.5 * length)], axis=1))).cuda()
+            ms = timed(lambda: G.closest_segments_device(accel, n, segs, None, radius, distance_ptr=dist, id_ptr=ids, stream=s), calls, warmup=1)
+            row("S: lg_closest_segments_device, distance + id, %s, %s" % (ltag, rtag), radius, length, ms, 24, floor, within_radius=int((ids[:, 0] != 0).sum()),
+                at_zero=int((dist == 0.0).sum()))
+            if radius != float("inf"):
+                ms = timed(lambda: G.closest_segments_device(accel, n, segs, None, radius, touch_ptr=touch, stream=s), calls, warmup=1)
+                row("St: lg_closest_segments_device, touch alone (leaves at the first contact), %s, %s" % (ltag, rtag), radius, length, ms, 1, floor, touching=int(touch.sum()))
+            del segs
+    return out
+
+
 def once(size):
     """The headline frame rendered once, then its rays queried once (closest, then the shadow segments to light 0)."""
     scene = S.spheres_scene(G)
@@ -1313,8 +1370,11 @@ def main():
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--order", type=int, choices=(0, 1), default=None)
-    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest")
+    ap.add_argument("--rows", default="all", help="comma-separated: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest, segments")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--segments", type=int, default=1 << 20, help="--rows segments: how many segments (at most the grid's 2^20)")
+    ap.add_argument("--long-only", action="store_true", help="--rows segments: the rows of full-length segments alone")
+    ap.add_argument("--label", default=None, help="--rows segments: the rows' `build` (default: product), for a library named by LASGUN_HIP_LIB")
     ap.add_argument("--once", action="store_true")
     args = ap.parse_args()
     G.set_device(0)
@@ -1322,8 +1382,8 @@ def main():
         once(args.size)
         return
     want = set(args.rows.split(","))
-    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest"}:
-        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest")
+    if not want or want - {"all", "queries", "radiance", "frame", "film", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest", "segments"}:
+        ap.error("--rows: all, queries, radiance, frame, film, visibility, features, directions, scan, gather, views, viewfeatures, layers, groups, paths, scatter, lit, attributes, closest, nearest, segments")
     t0 = time.time()
     rows = []
     for repeat in range(max(args.repeats, 1)):
@@ -1359,7 +1419,9 @@ def main():
                 got += measure_closest(name, builder, max(args.calls, 4))
             if "nearest" in want:
                 got += measure_nearest(name, builder, min(max(args.calls, 2), 4))
-            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest"}:
+            if "segments" in want:
+                got += measure_segments(name, builder, min(max(args.calls, 2), 4), args.segments, args.long_only, args.label)
+            if want - {"queries", "visibility", "features", "directions", "scan", "gather", "views", "viewfeatures", "layers", "groups", "paths", "scatter", "lit", "attributes", "closest", "nearest", "segments"}:
                 got += measure_radiance(name, builder, args.size, max(args.calls, 20), args.seed, args.order, frame_only=want == {"frame"},
                                         film_rows=bool(want & {"all", "film"}), radiance_rows=bool(want & {"all", "radiance"}))
             for r in got:
